@@ -10,6 +10,12 @@ Workloads (BASELINE.json configs): c3 (default) = 32x256 crops, batch 256 per GP
 bf16 operands / fp32 accumulate; c2 = 32x100, batch 64, fp32 MFMA; ref = the reference's own default shape
 (src/train.lua:41,47: batch 400, He=512) in bf16.
 --scaling weak (default): the per-GPU batch is fixed; strong: the GLOBAL batch is the workload's batch, split over the ranks.
+
+A plain run sets up, warms up, times the --steps steps and prints the headline line (image-lines/s, ms_per_step).  --full adds
+everything else, as before: the sustained loop, per-family times, decode / dictionary / beam-5 decode, the C2 fp32 secondary, the
+data path, the bandwidth-bound kernels, the roofline replays and the CPU baseline.  --dump-outputs DIR then runs the timed path's
+step once more, untimed, from the seeded starting state on the last timed step's batch, and writes what it gives its caller (see
+dump_outputs), so that two runs or two builds can be compared output for output.
 """
 import argparse
 import json
@@ -124,6 +130,31 @@ def cpu_baseline(wl, budget_s=40.0):
         return {"value": None, "unit": "image-lines/s", "cores": n, "kind": "port", "sample": f"not measured: {type(e).__name__}"}
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_MAX_ELEMS = 1 << 22            # per array: 16 MB of float32, so the arrays of a step stay well under 64 MB together
+DUMP_SEED = 910820
+
+
+def dump_outputs(out_dir, arrays, max_elems=DUMP_MAX_ELEMS, seed=DUMP_SEED):
+    """Writes each tensor of `arrays` as out_dir/<name>.npy: float32 stays float32, any other dtype becomes float64.  A tensor of
+    more than max_elems entries is written flattened as a fixed sample: the sorted distinct indices among max_elems draws of a
+    generator seeded with `seed`, so the same length always gives the same entries and two builds compare entry for entry.
+    Returns {name: number of entries written}."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > max_elems:
+            idx = np.unique(np.random.default_rng(seed).integers(0, t.numel(), size=max_elems))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        t = t.to(torch.float32 if t.dtype == torch.float32 else torch.float64).cpu()
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+        written[name] = t.numel()
+    return written
+
+
 # ------------------------------------------------------------------------------------------------ main
 def parse():
     ap = argparse.ArgumentParser()
@@ -134,13 +165,19 @@ def parse():
     ap.add_argument("--compute", default=None, choices=["f32", "bf16"])
     ap.add_argument("--batch", type=int, default=None, help="lines per GPU instead of the workload's own (c5: BASELINE names no batch; 16 / 64 / 128 are reported)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--decode-steps", type=int, default=20)
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C2 fp32 and data-path secondary measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure (sustained loop, families, decode, secondaries, roofline, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run one more step from the seeded starting state on the last timed step's batch and write "
+                         "its results as DIR/<name>.npy: loss, grad_norms, bn_state, params and grad_params (the last two a fixed seeded "
+                         "sample when larger than 4 M entries)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--decode-steps", type=int, default=20, help="with --full: timed calls per decode measurement (0 = none)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the C2 fp32 and data-path secondary measurements")
     ap.add_argument("--dropout", type=float, default=0.0, help="-dropout of the reference (LSTM.lua:68-69,116-118); 0 = the reference default")
     ap.add_argument("--provider", default="callback", choices=["callback", "rccl"],
                     help="N > 1: who sums the gradients -- torch.distributed through aocr_comm_set_callback, or the library's own RCCL binding (aocr_comm_init_rank)")
-    ap.add_argument("--sustain-seconds", type=float, default=8.0, help="keep stepping after the timed steps until this much GPU time has passed")
+    ap.add_argument("--sustain-seconds", type=float, default=8.0, help="with --full: keep stepping after the timed steps until this much GPU time has passed")
     return ap.parse_args()
 
 
@@ -201,7 +238,8 @@ def main():
         rccl_ranks = int(probe.item())
     img, tgt, tge, nnz = aocr.synth.synth_batch(B, W, seed=1234 + rank, max_len=L - 1, H=IMG_H)
     dev = m.device
-    params0, bn0 = m.params.clone(), m.bn_state.clone()      # the replica the decode legs run on (decode must not depend on how long the training loop ran)
+    if args.full or args.dump_outputs:                       # the replica the decode legs and the --dump-outputs step run on (decode must
+        params0, bn0 = m.params.clone(), m.bn_state.clone()  # not depend on how long the training loop ran)
     images = torch.from_numpy(img).to(device=dev, dtype=torch.float32)
     targets = torch.from_numpy(tgt).to(dev); targets_eval = torch.from_numpy(tge).to(dev)
     assert targets.shape[1] == L
@@ -219,12 +257,12 @@ def main():
             bi, _, _, _ = aocr.synth.synth_batch(B, wl["widths"][wi], seed=1234 + rank, max_len=L - 1, H=IMG_H)
             bucket_imgs.append(torch.from_numpy(bi).to(device=dev, dtype=torch.float32))
     step_no = [0]
+    last_images = [images]                              # the batch of the latest step (c4: its width bucket)
 
     def step():
         if bucket_imgs is not None:
-            im = bucket_imgs[step_no[0] % len(bucket_imgs)]; step_no[0] += 1
-            return m.train_step_device(im, targets, targets_eval)
-        return m.train_step_device(images, targets, targets_eval)
+            last_images[0] = bucket_imgs[step_no[0] % len(bucket_imgs)]; step_no[0] += 1
+        return m.train_step_device(last_images[0], targets, targets_eval)
 
     def healthy() -> bool:
         """False if a whole-sequence kernel of ANY rank gave up waiting for its group since the last call (results invalid)."""
@@ -262,9 +300,24 @@ def main():
         if rank == 0:
             print("[bench] a whole-sequence kernel timed out waiting for its group; re-measuring on the launch chains", file=sys.stderr, flush=True)
     lines_per_s = global_B * args.steps / el
+    # ---- --dump-outputs: the timed path's step once more, untimed, on the last timed step's batch but from the seeded starting state, and
+    # what it gives its caller.  The state the last timed step itself started from is not the same from run to run: the split-K filter
+    # gradients and the BatchNorm sums are atomic (their order varies), and the warm-up and timed steps on one batch amplify those rounding
+    # differences.  One step from the seeded state keeps them at rounding level.  The trained state is put back for the --full legs.
+    if args.dump_outputs:
+        trained = (m.params.clone(), m.bn_state.clone())
+        m.params.copy_(params0); m.bn_state.copy_(bn0)
+        out_loss = m.train_step_device(last_images[0], targets, targets_eval)
+        sync()
+        if not healthy():
+            sys.exit("bench.py: a whole-sequence kernel timed out in the --dump-outputs step: its outputs are invalid, none written")
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"loss": out_loss, "grad_norms": m.last_norms, "bn_state": m.bn_state, "params": m.params,
+                                             "grad_params": m.grad_params})
+        m.params.copy_(trained[0]); m.bn_state.copy_(trained[1])
     # ---- steady state: keep the GPU busy long enough for an external sampler, report it separately (never `value`)
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         n = max(args.steps, int(args.sustain_seconds / max(el / args.steps, 1e-4)) + 1)
         sync(); t0 = time.perf_counter()
         for _ in range(n):
@@ -273,12 +326,12 @@ def main():
         es = time.perf_counter() - t0
         sustained = {"steps": n, "seconds": es, "ms_per_step": 1e3 * es / n, "image_lines_per_s": global_B * n / es, "healthy": healthy()}
     exposed = None
-    if world > 1:                                       # part of the gradient exchange the backward pass did not hide, last step (max over ranks)
+    if args.full and world > 1:                         # part of the gradient exchange the backward pass did not hide, last step (max over ranks)
         ex = torch.tensor([m.comm_exposed_ms()], device=dev, dtype=torch.float64)
         dist.all_reduce(ex, op=dist.ReduceOp.MAX)
         exposed = float(ex.item())
     replica_drift = None
-    if world > 1:                                       # every rank must hold the same parameters after the timed steps
+    if args.full and world > 1:                         # every rank must hold the same parameters after the timed steps
         cs = m.params.double().abs().sum().reshape(1)
         hi, lo = cs.clone(), cs.clone()
         dist.all_reduce(hi, op=dist.ReduceOp.MAX); dist.all_reduce(lo, op=dist.ReduceOp.MIN)
@@ -293,8 +346,8 @@ def main():
     # contains the gradient all-reduce and the synchronised BatchNorm sums: a rank that skipped them would leave the others waiting);
     # rank 0 reports
     families = None
-    fam_all = m.profile_families(step, repeats=3)
-    if rank == 0:
+    fam_all = m.profile_families(step, repeats=3) if args.full else None
+    if rank == 0 and args.full:
         fam = fam_all
         # algorithmic FLOPs per image of each family: the three conv passes; both recurrences of the encoder (h W_h2h forward, dz W_h2h
         # backward); the hoisted GEMMs = input projections / embedding part / projector (forward, d(input), d(weight)) plus the weight
@@ -328,7 +381,7 @@ def main():
         grp = [int(min(lab.shape[1], last[g:g + 32].max() + 2)) for g in range(0, B, 32)]
         return int(sum(min(32, B - g) * grp[g // 32] for g in range(0, B, 32))), max(grp)
 
-    if args.decode_steps > 0:
+    if args.full and args.decode_steps > 0:
         trained = (m.params.clone(), m.bn_state.clone())
         m.params.copy_(params0); m.bn_state.copy_(bn0)
         Hd, T = 2 * wl["He"], (IMG_H // 16 - 1) * (W // 4 - 1)
@@ -380,7 +433,7 @@ def main():
                                       "note": "floor: MI355X_MICROARCH.md price list (handoff-1to1 idle 0.8-1.0 us per dependent hop; boundary 1.45 us per dependent launch; "
                                               "HBM 8 TB/s for a context that does not fit the Infinity Cache); measured with every step executed (AOCR_NO_DEC_EARLY=1): beam_ms / 50"}
         m.params.copy_(trained[0]); m.bn_state.copy_(trained[1])
-    if args.decode_steps > 0:
+    if args.full and args.decode_steps > 0:
         # the same step under -use_dictionary: a synthetic 90 k-word lexicon as a device-resident flat trie (trained parameters: the
         # early exit is the point of this leg)
         if not args.no_secondary and BEAM == 1:
@@ -413,7 +466,7 @@ def main():
 
     # ---- secondary line (N = 1 only): BASELINE.json configs[1] = C2 in exact-fp32 MFMA mode (the 1e-4 logit-parity configuration)
     c2 = None
-    if world == 1 and args.workload == "c3" and not args.no_secondary:
+    if args.full and world == 1 and args.workload == "c3" and not args.no_secondary:
         w2 = WORKLOADS["c2"]
         m2 = aocr.Model().create(dict(encoder_num_hidden=w2["He"], encoder_num_layers=w2["Le"], decoder_num_layers=w2["Ld"],
                                       input_feed=True, batch_size=w2["B"], max_img_w=w2["W"], max_decoder_l=50, max_beam=1,
@@ -435,7 +488,7 @@ def main():
     # (dec_chain.hip: the 5 hypotheses of an image are rows of one chain, 6 images per 32-CU group, launches of <= 8 groups); the per-step launch chain
     # (AOCR_NO_DEC_CHAINS_BEAM=1: one cell / attention / project_select / state-gather launch set per step) is timed beside it
     beam5 = None
-    if world == 1 and args.workload == "c3" and not args.no_secondary and args.decode_steps > 0:
+    if args.full and world == 1 and args.workload == "c3" and not args.no_secondary and args.decode_steps > 0:
         m5 = aocr.Model().create(dict(encoder_num_hidden=wl["He"], encoder_num_layers=wl["Le"], decoder_num_layers=wl["Ld"], input_feed=True,
                                       batch_size=B, max_img_w=W, max_decoder_l=50, max_beam=5, compute=wl["compute"], learning_rate=0.1, seed=910820))
 
@@ -459,7 +512,7 @@ def main():
 
     # ---- data path, HBM-bound
     dp = None
-    if world == 1 and not args.no_secondary:
+    if args.full and world == 1 and not args.no_secondary:
         from aocr.data import ImageDesc
         n, sh, sw, ow = B, 48, 384, W
         src = torch.randint(0, 256, (n * sh * sw * 3,), dtype=torch.uint8, device=dev)
@@ -483,7 +536,7 @@ def main():
 
     out = None
     hbm_kernels = None
-    if rank == 0 and wl["compute"] == "bf16" and world == 1 and not wl.get("widths"):
+    if args.full and rank == 0 and wl["compute"] == "bf16" and world == 1 and not wl.get("widths"):
         # ---- the BANDWIDTH-bound kernels ("report HBM GB/s for those kernels separately"): each replayed by the library on the
         # buffers of a training step with the arguments the step passes (aocr_profile_kernel ids >= 2), HIP events on the model's stream;
         # algorithmic bytes = what the kernel must read and write once.  `frac` is against the 8 TB/s spec; ~6.3 TB/s is what a float4 copy
@@ -507,8 +560,9 @@ def main():
             hbm_kernels[kname] = {"us_per_launch": 1e3 * ms_k, "algorithmic_MB": by / 1e6, "GBps": gbps, "frac_of_8TBps": gbps / HBM_PEAK_GBPS,
                                   "frac_of_6.3TBps_achievable": gbps / 6300.0, "what": what}
         step(); torch.cuda.synchronize()                  # the replays clobbered activations / gradients: leave the model in a defined state
-    if rank == 0:
-        bf16 = wl["compute"] == "bf16"
+    bf16 = wl["compute"] == "bf16"
+    roof = best = None
+    if args.full and rank == 0:
         ms, kfl = m.profile_kernel(0, 20)                # conv6 forward, HIP events on the model's stream
         ach = kfl / (ms * 1e-3) / 1e12
         best = {"bound": "mfma", "kernel": "conv6 forward implicit GEMM (512->512 3x3 + ReLU + pool), gemm_halo4_bf16_kernel", "achieved": ach,
@@ -542,8 +596,9 @@ def main():
                 r_["mfma_only_sustained_TFLOPs"] = mo
                 r_["frac_of_mfma_only_sustained"] = r_["achieved"] / mo if mo else None
                 r_["mfma_only_source"] = mo_src + " (tools/ubench/gemm4w.hip, measured this round on the pool; a file constant, NOT measured in this run)"
+    if rank == 0:
         out = {
-            "metric": "image-lines/sec (train step)", "value": lines_per_s, "unit": "image-lines/s", "n_gpus": world,
+            "metric": "image-lines/sec (train step)", "value": lines_per_s, "unit": "image-lines/s", "n_gpus": world, "full": args.full,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * el / args.steps, "higher_is_better": True,
             "scaling": args.scaling if world > 1 else "weak", "vs_baseline": None, "dtype": "bf16" if bf16 else "f32", "data": "synthetic",
             "config": {"workload": f"{args.workload}: {wl['name']}", "global_batch": global_B, "per_gpu_batch": B, "img": f"{IMG_H}x{W}",
@@ -560,7 +615,7 @@ def main():
             "replica_drift": replica_drift, "loss": loss_val, "secondary": c2, "data_path": dp,
             "roofline": roof, "roofline_best": best, "hbm_kernels": hbm_kernels,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(wl)
     m.shutdown()
     if world > 1:

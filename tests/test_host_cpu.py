@@ -42,6 +42,32 @@ def test_bench_flop_model_matches_survey():
     assert abs(b.flops(256, 256, 1, 2, 24)["total"] / 1e9 - 3.6048) < 1e-3      # C3 forward
 
 
+def test_bench_options_and_dump_outputs(tmp_path, monkeypatch):
+    """bench.py's --full / --dump-outputs options and the writer behind --dump-outputs (host side): float32 stays float32, other dtypes
+    become float64, a tensor over the limit is written as the same seeded sample every time, and the largest workload stays under 64 MB."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7"])
+    a = b.parse()
+    assert a.steps == 7 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "out"
+    arrays = {"loss": torch.tensor([2.5]), "params": torch.arange(5000, dtype=torch.float32), "bn": torch.ones(3, dtype=torch.float64),
+              "ids": torch.arange(4, dtype=torch.int32)}
+    w1 = b.dump_outputs(str(tmp_path / "a"), arrays, max_elems=1000)
+    w2 = b.dump_outputs(str(tmp_path / "b"), arrays, max_elems=1000)
+    assert w1 == w2 and w1["loss"] == 1 and w1["bn"] == 3 and w1["ids"] == 4 and 0 < w1["params"] <= 1000
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert got["loss"].dtype == np.float32 and got["params"].dtype == np.float32 and got["bn"].dtype == np.float64 and got["ids"].dtype == np.float64
+    assert np.array_equal(got["ids"], [0, 1, 2, 3]) and got["loss"][0] == 2.5
+    p = got["params"]                                                    # arange: the values are the sampled indices
+    assert np.all(np.diff(p) > 0) and p[0] >= 0 and p[-1] < 5000 and np.array_equal(p, np.load(tmp_path / "b" / "params.npy"))
+    # parameters + gradients of the largest workload (34 M entries each, both sampled) + loss, norms and running statistics: under 64 MB
+    assert 2 * 4 * b.DUMP_MAX_ELEMS + 4 * (1 + 10 + 2560) < 64 * 2**20
+
+
 def _dp_worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     sys.path.insert(0, os.path.join(ROOT, "torch-attention-ocr_amd")); sys.path.insert(0, os.path.join(ROOT, "oracle"))

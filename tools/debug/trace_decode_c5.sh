@@ -3,7 +3,7 @@
 set -u
 R=${GRAFT_REPO_ROOT:?run through gpurun}; B=${1:-256}; O=$R/gpurun_out/dec_trace_raw; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O -- python3 $R/bench.py --workload c5 --batch $B --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --decode-steps 2 --sustain-seconds 0 > $O/run.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O -- python3 $R/bench.py --full --workload c5 --batch $B --steps 1 --warmup 1 --no-cpu-baseline --no-secondary --decode-steps 2 --sustain-seconds 0 > $O/run.log 2>&1
 cd $R
 python3 - "$(ls $O/*/*kernel_trace.csv | head -1)" > gpurun_out/dec_trace_c5.txt <<'PY'
 import csv, sys

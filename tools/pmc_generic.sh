@@ -2,7 +2,7 @@
 # per-kernel mean of arbitrary PMC counters over the default workload (run via gpurun): tools/pmc_generic.sh <tag> <counter...> -> gpurun_out/pmc/<tag>.txt
 R=$GRAFT_REPO_ROOT; tag=$1; shift; O=$R/gpurun_out/pmc; mkdir -p $O; rm -rf $O/raw_$tag
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/raw_$tag -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --decode-steps 1 --no-secondary --sustain-seconds 0 > $O/run_$tag.log 2>&1
+timeout 900 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/raw_$tag -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --decode-steps 1 --no-secondary --sustain-seconds 0 > $O/run_$tag.log 2>&1
 cd $R
 f=$(ls $O/raw_$tag/*/*counter_collection.csv | head -1); kt=$(ls $O/raw_$tag/*/*kernel_trace.csv | head -1)
 python - "$f" "$kt" "$@" > $O/$tag.txt <<'PY'

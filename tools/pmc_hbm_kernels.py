@@ -23,7 +23,7 @@ fetch, write = mean_by_kernel(sys.argv[1], "FETCH_SIZE"), mean_by_kernel(sys.arg
 dur = collections.defaultdict(list)
 for r in csv.DictReader(open(sys.argv[3])):
     dur[r["Kernel_Name"]].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
-print("# rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --kernel-trace -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --decode-steps 0 --no-secondary --sustain-seconds 0 (two passes)")
+print("# rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --kernel-trace -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --decode-steps 0 --no-secondary --sustain-seconds 0 (two passes)")
 print("# per kernel symbol, mean over ALL its launches of the run (every shape it is launched with: the three BatchNorm layers, the three un-pool layers, ...):")
 print("# launches | fetch MB (x2 corrected) | write MB | total MB | us in the counter run | GB/s in the counter run")
 for key in KERNELS:

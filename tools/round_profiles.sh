@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:?GRAFT_REPO_ROOT is not set (this script runs on the GPU box
 [ -f "$R/bench.py" ] || { echo "no bench.py under $R" >&2; exit 2; }
 O="$R/gpurun_out/prof_$TAG"; rm -rf "$O"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 SHORT="--steps 2 --warmup 1 --no-cpu-baseline --decode-steps 0 --no-secondary --sustain-seconds 0"
 timeout 600 $B > $O/bench_c3_bf16.json 2> $O/bench.err
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $B --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --sustain-seconds 1 > $O/bench_stats.log 2>&1
