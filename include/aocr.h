@@ -210,6 +210,20 @@ int aocr_decode_dict(aocr_model* m, const float* images_dev, const int32_t* targ
                      const aocr_trie* trie, int32_t* labels_dev, float* scores_dev,
                      float* gold_scores_dev, float* loss_dev);
 
+/* Forward-only recognition without labels: eval-mode CNN, encoder, beam search over max_decoder_l
+ * steps (beam 1 = greedy), back-trace.  There is no gold pass and no loss.  Every row starts from
+ * GO (2).  trie may be NULL (no dictionary; otherwise as aocr_decode_dict).
+ * labels_dev (B,max_decoder_l) int32 and scores_dev (B): what aocr_decode_dict returns for the
+ * same images, bit for bit.  Optional (NULL = not wanted), along the winning hypothesis:
+ *   char_logp_dev (B,max_decoder_l): log-probability of each emitted token at its step (the
+ *     increase of the hypothesis' running score: sums to scores_dev up to rounding);
+ *   attn_dev (B,max_decoder_l,T), T = W/4 - 1: the attention weights that produced each token.
+ * Positions after the first EOS are 0 in both (the PAD-at-no-cost steps, model.lua:448-449;
+ * a PAD emitted before any EOS ends a hypothesis the same way); that EOS itself is included. */
+int aocr_recognize(aocr_model* m, const float* images_dev, int32_t B, int32_t W, int32_t beam,
+                   const aocr_trie* trie, int32_t* labels_dev, float* scores_dev,
+                   float* char_logp_dev, float* attn_dev);
+
 /* Debug / parity taps: device pointer + shape of a named intermediate of the last
  * step ("feats" (T,B,512), "context" (B,T,2He), "logits" (L,B,40), "dfeats", "dcontext"). */
 int aocr_get_tensor(aocr_model* m, const char* name, const void** ptr_dev, int32_t* ndim, int64_t shape[4]);

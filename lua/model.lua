@@ -359,6 +359,31 @@ function model:step(batch, forward_only, beam_size, trie)
     return loss, {num_nonzeros, accuracy}
 end
 
+-- label-free recognition (include/aocr.h aocr_recognize): images (B,1,32,W) values 0..255, no targets, no gold pass.  Returns labels (B,Lt)
+-- IntTensor, scores (B), char_logp (B,Lt) FloatTensor and, with want_attention, the attention weights (B,Lt,T), T = W/4 - 1.
+function model:recognize(images, beam_size, trie, want_attention)
+    local input_batch = images:float():contiguous()
+    local batch_size, W = input_batch:size(1), input_batch:size(4)
+    local Lt, T = self.max_decoder_l, math.floor(W / 4) - 1
+    beam_size = math.min(beam_size or 1, self.target_vocab_size)
+    A.upload(self.images_dev, input_batch, batch_size * 32 * W * 4)
+    local tdesc = nil
+    if trie ~= nil then
+        if self.trie_cache == nil or self.trie_cache.source ~= trie then self.trie_cache = Dict.flatten(trie, A) end
+        tdesc = self.trie_cache.desc
+    end
+    if self.clogp_dev == nil then self.clogp_dev = A.device_bytes(self.batch_size * Lt * 4) end
+    if want_attention and self.attn_dev == nil then self.attn_dev = A.device_bytes(self.batch_size * Lt * (math.floor(self.max_img_w / 4) - 1) * 4) end
+    A.check(A.lib.aocr_recognize(self.handle, self.images_dev:as('float*'), batch_size, W, beam_size, tdesc, self.labels_dev:as('int32_t*'),
+                                 self.scores_dev:as('float*'), self.clogp_dev:as('float*'), want_attention and self.attn_dev:as('float*') or nil), 'aocr_recognize')
+    local labels = torch.IntTensor(batch_size, Lt); A.download(labels, self.labels_dev, batch_size * Lt * 4)
+    local scores = torch.FloatTensor(batch_size); A.download(scores, self.scores_dev, batch_size * 4)
+    local char_logp = torch.FloatTensor(batch_size, Lt); A.download(char_logp, self.clogp_dev, batch_size * Lt * 4)
+    local attn = nil
+    if want_attention then attn = torch.FloatTensor(batch_size, Lt, T); A.download(attn, self.attn_dev, batch_size * Lt * T * 4) end
+    return labels, scores, char_logp, attn
+end
+
 -- ------------------------------------------------------------------------------------------------ model.lua:708-731
 function model:vis(output_dir)
     local path = paths.concat(output_dir, 'results.txt')
@@ -374,7 +399,7 @@ function model:save(model_path)
 end
 
 local DEVICE_BUFFERS = {'params_dev', 'grads_dev', 'bn_dev', 'ws_dev', 'scal_dev', 'images_dev', 'targets_dev', 'targets_eval_dev', 'labels_dev',
-                        'scores_dev', 'gold_dev', 'dist_dev', 'tlen_dev', 'tge_pad_dev'}
+                        'scores_dev', 'gold_dev', 'dist_dev', 'tlen_dev', 'tge_pad_dev', 'clogp_dev', 'attn_dev'}
 function model:shutdown()
     if self.visualize_file then self.visualize_file:close(); self.visualize_file = nil end
     if self.handle ~= nil then A.lib.aocr_model_destroy(self.handle); self.handle = nil end

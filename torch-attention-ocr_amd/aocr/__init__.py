@@ -6,7 +6,7 @@ package loads the shared library and fails loudly if it is missing.
 """
 from . import _lib                      # noqa: F401  (raises ImportError when libaocr.so is absent)
 from ._lib import AocrError, Config, COMPUTE_BF16, COMPUTE_F32, lib, last_error, check, ptr, param_table
-from .model import Model, eval_word_err_rate, numlist2str, GROUPS
+from .model import Model, eval_word_err_rate, numlist2str, encoder_columns, GROUPS
 from . import synth
 from . import data
 from .data import DataGen
@@ -15,4 +15,4 @@ from . import t7, checkpoint
 from .dictionary import Trie, load_dictionary, build_trie, levenshtein
 
 __all__ = ["Model", "DataGen", "data", "dictionary", "t7", "checkpoint", "Trie", "load_dictionary", "build_trie", "levenshtein", "AocrError", "Config", "COMPUTE_F32", "COMPUTE_BF16", "lib", "last_error", "check", "ptr",
-           "param_table", "eval_word_err_rate", "numlist2str", "GROUPS", "synth"]
+           "param_table", "eval_word_err_rate", "numlist2str", "encoder_columns", "GROUPS", "synth"]

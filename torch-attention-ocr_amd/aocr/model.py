@@ -41,6 +41,15 @@ def numlist2str(ids):
     return "".join(chr(v - 1 - 13 + 97) if v > 13 else chr(v - 1 - 3 + 48) for v in ids)
 
 
+def encoder_columns(W: int) -> np.ndarray:
+    """Image column every encoder step is centred on (T = W/4 - 1 steps).  cnn.lua: conv1..conv6 are 3x3 / pad 1 (width kept), the two
+    2x2 / stride 2 max-pools after conv1 and conv2 halve it (W/4; the later pools are (2,1) / (1,2) with horizontal stride 1), and conv7 (2x2,
+    no pad) makes T = W/4 - 1.  Step t thus reads pooled columns t, t+1, i.e. image columns 4t .. 4t+7, centred at 4t + 4 (0-based, between
+    pixels 4t+3 and 4t+4)."""
+    T = W // 4 - 1
+    return 4.0 * np.arange(max(T, 0), dtype=np.float64) + 4.0
+
+
 def eval_word_err_rate(labels: np.ndarray, target_labels: np.ndarray, visualize: bool = False):
     """evalWordErrRate, src/utils/utils.lua:136-175: sequences are cut at the first EOS (3) and compared exactly."""
     B = labels.shape[0]
@@ -368,6 +377,53 @@ class Model:
             check(lib.aocr_decode_dict(self._h, ptr(images), ptr(targets), ptr(targets_eval), B, W, targets.shape[1], beam_size,
                                        C.byref(desc), ptr(labels), ptr(scores), ptr(gold), ptr(loss_dev)), "aocr_decode_dict")
         return labels, scores, gold, loss_dev
+
+    def recognize_device(self, images, beam_size=1, trie=None, attention=False, char_scores=False):
+        """Label-free recognition (aocr_recognize) of a preprocessed (B,1,32,W) batch already in HBM; enqueues only.  Returns device tensors
+        (labels (B,max_decoder_l) int32, scores (B), char_logp (B,max_decoder_l) or None, attention (B,max_decoder_l,T) or None, T = W/4 - 1).
+        labels / scores are what decode_device returns for the same images; no targets, no gold pass."""
+        B, _, _, W = images.shape
+        Lt = self.max_decoder_l
+        T = W // 4 - 1
+        check(lib.aocr_model_set_stream(self._h, self._stream()))
+        labels = torch.empty((B, Lt), dtype=torch.int32, device=self.device)
+        scores = torch.empty(B, dtype=torch.float32, device=self.device)
+        clp = torch.empty((B, Lt), dtype=torch.float32, device=self.device) if char_scores else None
+        attn = torch.empty((B, Lt, max(T, 1)), dtype=torch.float32, device=self.device) if attention else None
+        desc = None
+        if trie is not None:
+            if trie._dev is None:
+                trie.to(self.device)
+            desc = trie.desc()
+        check(lib.aocr_recognize(self._h, ptr(images), B, W, beam_size, C.byref(desc) if desc is not None else None, ptr(labels), ptr(scores),
+                                 ptr(clp), ptr(attn)), "aocr_recognize")
+        return labels, scores, clp, attn
+
+    def recognize(self, images, beam_size=None, trie=None, attention=False, width=None):
+        """Read images without labels.  images: a preprocessed (B,1,32,W) tensor, or a list of uint8 (H,W) / (H,W,3) arrays (load_image), which
+        go through preprocess_batch at `width` (default max_img_w).  Returns a namespace: labels (B,max_decoder_l) int32, scores (B), text (per
+        row, cut at the first EOS), char_logp (B,max_decoder_l), attention (B,max_decoder_l,T) when asked for (else None) and columns (T): the
+        image column every encoder step is centred on."""
+        if isinstance(images, (list, tuple)):
+            from .data import preprocess_batch
+            images = preprocess_batch(list(images), int(width or self.max_img_w), self.device, self._stream())
+        else:
+            images = torch.as_tensor(images).to(device=self.device, dtype=torch.float32).contiguous()
+        assert images.dim() == 4 and images.shape[1] == 1 and images.shape[2] == self.img_h
+        beam_size = min(beam_size or 1, self.target_vocab_size)
+        labels, scores, clp, attn = self.recognize_device(images, beam_size, trie, attention, True)
+        labels_h = labels.cpu().numpy()
+        text = []
+        for row in labels_h:
+            ids = []
+            for v in row:
+                if v == EOS:
+                    break
+                ids.append(int(v))
+            text.append(numlist2str(ids))
+        self.check_health()
+        return SimpleNamespace(labels=labels_h, scores=scores.cpu().numpy(), text=text, char_logp=clp.cpu().numpy(),
+                               attention=attn.cpu().numpy() if attn is not None else None, columns=encoder_columns(images.shape[3]))
 
     def profile_kernel(self, which=0, iters=20):
         """HIP-event timing of one hot kernel at the last step's shape: (ms per launch, flops per launch)."""

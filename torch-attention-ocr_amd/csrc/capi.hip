@@ -384,6 +384,37 @@ int aocr_decode_dict(aocr_model* m, const float* images_dev, const int32_t* targ
   return check_launch(trie ? "aocr_decode_dict" : "aocr_decode");
 }
 
+// Label-free recognition: the forward half of aocr_decode_dict without the gold pass.  GO (2) starts every row from tgt_pad, so that the search
+// paths read their first tokens exactly as they do in a decode call; the optional outputs come from the search's own history (decode_beam).
+int aocr_recognize(aocr_model* m, const float* images_dev, int32_t B, int32_t W, int32_t beam, const aocr_trie* trie, int32_t* labels_dev,
+                   float* scores_dev, float* char_logp_dev, float* attn_dev) {
+  REQUIRE(m, "NULL model");
+  const int Lt = m->cfg.max_decoder_l;                                    // model.lua:273: always max_decoder_l steps (S8)
+  Dims d; if (step_dims(m, B, W, Lt, d)) return 1;
+  REQUIRE(images_dev && labels_dev && scores_dev, "NULL argument");
+  if (trie && check_trie(trie, m->V)) return 1;
+  if (beam > m->V) beam = m->V;                                           // model.lua:229
+  REQUIRE(beam >= 1 && beam <= m->cfg.max_beam, "beam=%d outside 1..%d", beam, m->cfg.max_beam);
+  const bool hist = char_logp_dev || attn_dev;
+  fill_i32(m->s, m->tgt_pad, 2, (int64_t)B * Lt);                         // GO, model.lua:388 (the rest of the row is never read)
+  prof_mark(m, AOCR_PROF_OTHER);
+  m->tab_valid = false;
+  cnn_forward(m, images_dev, d, 0, 0);                                    // model.lua:280-281: evaluate()
+  encoder_forward(m, d);
+  prof_mark(m, AOCR_PROF_DECODE);
+  decode_beam(m, d, m->tgt_pad, beam, labels_dev, scores_dev, trie, hist ? m->attn_hist : nullptr, hist ? m->sc_hist : nullptr);
+  if (hist) {
+    // the greedy whole-sequence kernels select without a parent history (hist_par is then not written): k = 1 walks row b alone
+    const bool greedy = beam == 1;
+    recognize_gather(m->s, labels_dev, greedy ? nullptr : m->hist_par, greedy ? nullptr : m->beam_scores, m->sc_hist, m->attn_hist, char_logp_dev,
+                     attn_dev, Lt, B, beam, d.T);
+  }
+  prof_mark(m, -1);
+  m->ctxa_fresh = false;                                                  // (no gold pass consumes ctx W_a of this call)
+  m->last = d; m->last_valid = 1; m->last_train = false; m->tab_valid = false;
+  return check_launch("aocr_recognize");
+}
+
 int aocr_get_tensor(aocr_model* m, const char* name, const void** ptr_dev, int32_t* ndim, int64_t shape[4]) {
   REQUIRE(m && name && ptr_dev && ndim && shape, "NULL argument");
   REQUIRE(m->last_valid, "no step has run yet");

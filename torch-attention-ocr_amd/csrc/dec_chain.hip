@@ -140,7 +140,9 @@ template <int C> struct IC { static constexpr int value = C; };
 // exchange buffers are a rolling window of four (rows of this launch's groups only); the state gather by parent beam (model.lua:516-535) is
 // a lane permutation of the OLD-state partial products and of the cell states (nothing moves in memory); the image's owner (member of its first
 // row) runs project_select_kernel's selection over the k rows and publishes token + parent of every new row; history for beam_backtrace.
-template <bool DEC, bool RES, bool BEAM = false>     // RES: T <= 64 -- the 16-step tile of ctx . W_a a wave multiplies stays in its registers for the whole loop (64 VGPRs)
+// HIST (with DEC, aocr_recognize): the attention row of every search row and every step to a_all, the running score of every hypothesis after
+// every step to sc_hist (DecClFwdArgs); the other instantiations do not contain these stores.
+template <bool DEC, bool RES, bool BEAM = false, bool HIST = false>     // RES: T <= 64 -- the 16-step tile of ctx . W_a a wave multiplies stays in its registers for the whole loop (64 VGPRs)
 __global__ __launch_bounds__(256, 1) void dec_ch_fwd_kernel(DecClFwdArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   [[maybe_unused]] const u64 t_kernel0 = __builtin_readcyclecounter();
@@ -363,7 +365,8 @@ __global__ __launch_bounds__(256, 1) void dec_ch_fwd_kernel(DecClFwdArgs p) {
   // one-instruction stores of a phase behind its operand prefetch (what the next landing's counted wait leaves in flight).  Decode (DEC) keeps the state in
   // registers and reads nothing back: the saved gates, cell-state slots, attention weights and the fp32 out are not written at all -- a store instruction
   // costs ~250-400 cycles of issue on this path whatever it carries (tools/debug/enc_stamp.py), six per chain and step
-  constexpr int S1 = DEC ? 1 : 3, S2 = DEC ? 2 : 4, S3 = DEC ? 1 : 2, S4 = DEC ? 4 : 2;
+  static_assert(DEC || !HIST, "the search history exists in decode only");
+  constexpr int S1 = DEC ? 1 : 3, S2 = DEC ? 2 : 4, S3 = (DEC && !HIST) ? 1 : 2, S4 = DEC ? 4 : 2;      // (HIST: P3 stores the attention row too)
 
   for (int t = 0; t < L && !dead; ++t) {
     int ot = tid; asm volatile("" : "+v"(ot));                     // opaque per-step copy of the thread id: the address arithmetic stays inside the step
@@ -574,6 +577,14 @@ __global__ __launch_bounds__(256, 1) void dec_ch_fwd_kernel(DecClFwdArgs p) {
       for (int w = 0; w < 4; ++w) { v0 += part[w * HD + 2 * tid]; v1 += part[w * HD + 2 * tid + 1]; }
       pst4(rvalid ? (void*)(p.cat_b + cof(t) + (size_t)arow * 2 * HD + 2 * ot) : (void*)otrash, sane(bfpair(v0, v1)), local);      // c of row `member`: units 2 tid, 2 tid + 1
       if constexpr (!DEC) st4f(rvalid && ot < T ? (void*)(p.a_all + ((size_t)t * B + arow) * T + ot) : (void*)otrash, av);
+      if constexpr (HIST) {                                         // the search row's attention: greedy [t][B][T]; beam [t][B k][T], row image * kin + hypothesis
+        bool hv = rvalid; size_t hr = (size_t)t * B + arow;
+        if constexpr (BEAM) {                                       // (step 0: the k rows of an image are one hypothesis, kin = 1 -- the launch chain's layout)
+          const int j = (member & (RC - 1)) % kb, kin = t == 0 ? 1 : kb;
+          hv = rvalid && j < kin; hr = (size_t)t * B * kb + (size_t)aimg * kin + j;
+        }
+        st4f(hv && ot < T ? (void*)(p.a_all + hr * T + ot) : (void*)otrash, av);
+      }
     };
     // =================== P4: out = tanh(W_c [c ; h2]), LSTM.lua:153-157.  stores: publish + the fp32 copy = 2 (+ the pre-fill behind chain 1)
     auto P4 = [&](auto cc) {
@@ -672,6 +683,7 @@ __global__ __launch_bounds__(256, 1) void dec_ch_fwd_kernel(DecClFwdArgs p) {
         node = p.trie_child[p.trie_base[node] + __popcll(tmask & ((1ull << bi) - 1ull))];
       if (olane == 0) {
         if (rvalid) { p.labels[(size_t)arow * p.tok0_stride + t] = bi + 1; if (t == L - 1) p.scores[arow] = best; }
+        if constexpr (HIST) { if (rvalid) p.sc_hist[(size_t)t * B + arow] = best; }
         pst4(p.tokx + (size_t)gx * 32 + member, (((p.epoch * 4096u + (unsigned)(t + 1)) & 0xFFFFFFu) << 8) | (unsigned)(bi + 1), local);
       }
       // this parity's row is read: unwritten again for step t + 2 (in memory long before its writers get there: they need this step's token first)
@@ -793,6 +805,7 @@ __global__ __launch_bounds__(256, 1) void dec_ch_fwd_kernel(DecClFwdArgs p) {
         const size_t ho = ((size_t)t * B + aimg) * kb + olane;
         p.hist_tok[ho] = tokv; p.hist_par[ho] = par;
         if (t == L - 1) p.beam_scores[(size_t)aimg * kb + olane] = mysc;
+        if constexpr (HIST) p.sc_hist[ho] = mysc;
         pst4(p.tokx + (size_t)gx * 32 + member + olane, (((p.epoch * 4096u + (unsigned)(t + 1)) & (0xFFFFFFFFu >> 9)) << 9) | ((unsigned)par << 6) | (unsigned)tokv, local);
       }
       CH_STAMP2(5);
@@ -1310,6 +1323,11 @@ void dec_chain_forward(hipStream_t s, const DecClFwdArgs& a0, bool greedy_decode
   (void)hipFuncSetAttribute((const void*)dec_ch_fwd_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CH_FWD_LDS);
   (void)hipFuncSetAttribute((const void*)dec_ch_fwd_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CH_DEC_LDS);
   (void)hipFuncSetAttribute((const void*)dec_ch_fwd_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CH_DEC_LDS);
+  const bool hist = greedy_decode && a0.sc_hist;                   // aocr_recognize: the variant that keeps the search history
+  if (hist) {
+    (void)hipFuncSetAttribute((const void*)dec_ch_fwd_kernel<true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CH_DEC_LDS);
+    (void)hipFuncSetAttribute((const void*)dec_ch_fwd_kernel<true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CH_DEC_LDS);
+  }
   const bool res = a0.T <= 64 && !getenv("AOCR_CH_NO_RES");
   for (int g0 = 0; g0 < groups; g0 += per_pass) {
     DecClFwdArgs a = a0; a.group0 = g0; a.ngroups = std::min(per_pass, groups - g0); a.force_remote = getenv("AOCR_CL_REMOTE") != nullptr;
@@ -1317,7 +1335,9 @@ void dec_chain_forward(hipStream_t s, const DecClFwdArgs& a0, bool greedy_decode
     const dim3 grid(8 * NM * ((a.ngroups + 7) / 8));
     if (greedy_decode) {
       a.pgroups = groups; a.tokx = reinterpret_cast<unsigned*>(a.pbuf + (size_t)2 * groups * 32 * 32 * 40); a.no_early = getenv("AOCR_NO_DEC_EARLY") != nullptr;
-      if (res) hipLaunchKernelGGL((dec_ch_fwd_kernel<true, true>), grid, dim3(256), (size_t)CH_DEC_LDS, s, a);
+      if (hist && res) hipLaunchKernelGGL((dec_ch_fwd_kernel<true, true, false, true>), grid, dim3(256), (size_t)CH_DEC_LDS, s, a);
+      else if (hist) hipLaunchKernelGGL((dec_ch_fwd_kernel<true, false, false, true>), grid, dim3(256), (size_t)CH_DEC_LDS, s, a);
+      else if (res) hipLaunchKernelGGL((dec_ch_fwd_kernel<true, true>), grid, dim3(256), (size_t)CH_DEC_LDS, s, a);
       else hipLaunchKernelGGL((dec_ch_fwd_kernel<true, false>), grid, dim3(256), (size_t)CH_DEC_LDS, s, a);
     } else if (res) hipLaunchKernelGGL((dec_ch_fwd_kernel<false, true>), grid, dim3(256), (size_t)CH_FWD_LDS, s, a);
     else hipLaunchKernelGGL((dec_ch_fwd_kernel<false, false>), grid, dim3(256), (size_t)CH_FWD_LDS, s, a);
@@ -1344,6 +1364,11 @@ void dec_chain_beam_forward(hipStream_t s, const DecClFwdArgs& a0) {
   const int groups = beam_groups(a0.B, a0.beam), per_pass = beam_pass_groups(a0.B, a0.L, a0.beam), cap = chain_per_pass();
   (void)hipFuncSetAttribute((const void*)dec_ch_fwd_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(CH_DEC_LDS + CH_BEAM_EXTRA));
   (void)hipFuncSetAttribute((const void*)dec_ch_fwd_kernel<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(CH_DEC_LDS + CH_BEAM_EXTRA));
+  const bool hist = a0.sc_hist != nullptr;                         // aocr_recognize: the variant that keeps the search history
+  if (hist) {
+    (void)hipFuncSetAttribute((const void*)dec_ch_fwd_kernel<true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(CH_DEC_LDS + CH_BEAM_EXTRA));
+    (void)hipFuncSetAttribute((const void*)dec_ch_fwd_kernel<true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(CH_DEC_LDS + CH_BEAM_EXTRA));
+  }
   const bool res = a0.T <= 64 && !getenv("AOCR_CH_NO_RES");
   unsigned epoch = a0.epoch;
   for (int g0 = 0; g0 < groups; g0 += per_pass, ++epoch) {
@@ -1352,7 +1377,9 @@ void dec_chain_beam_forward(hipStream_t s, const DecClFwdArgs& a0) {
     a.rows_slot = 32 * per_pass;
     a.pgroups = cap; a.tokx = reinterpret_cast<unsigned*>(a.pbuf + (size_t)2 * cap * 32 * 32 * 40);
     const dim3 grid(8 * NM * ((a.ngroups + 7) / 8));
-    if (res) hipLaunchKernelGGL((dec_ch_fwd_kernel<true, true, true>), grid, dim3(256), (size_t)(CH_DEC_LDS + CH_BEAM_EXTRA), s, a);
+    if (hist && res) hipLaunchKernelGGL((dec_ch_fwd_kernel<true, true, true, true>), grid, dim3(256), (size_t)(CH_DEC_LDS + CH_BEAM_EXTRA), s, a);
+    else if (hist) hipLaunchKernelGGL((dec_ch_fwd_kernel<true, false, true, true>), grid, dim3(256), (size_t)(CH_DEC_LDS + CH_BEAM_EXTRA), s, a);
+    else if (res) hipLaunchKernelGGL((dec_ch_fwd_kernel<true, true, true>), grid, dim3(256), (size_t)(CH_DEC_LDS + CH_BEAM_EXTRA), s, a);
     else hipLaunchKernelGGL((dec_ch_fwd_kernel<true, false, true>), grid, dim3(256), (size_t)(CH_DEC_LDS + CH_BEAM_EXTRA), s, a);
   }
 }

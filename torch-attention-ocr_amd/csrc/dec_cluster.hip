@@ -162,9 +162,11 @@ __device__ __forceinline__ void raise_and_wait(unsigned* flags, unsigned tag, in
 // published twice -- as it is (the recurrence of layer 1 reads it at step t+1) and masked (hm_b: the operand of layer 2, gathered into
 // the H1 buffer; H1 is re-fetched unmasked at the start of the next step) --, out(t) only masked (projector, input feed and the
 // backward kernel all see Dropout(out); the backward kernel divides the mask out again for tanh').
-template <bool DEC, bool DROP = false>
+// HIST (with DEC, aocr_recognize): the running score after every step to sc_hist [L][B] (the attention rows are in a_all in every variant).
+template <bool DEC, bool DROP = false, bool HIST = false>
 __global__ __launch_bounds__(256, 1) void dec_cl_fwd_kernel(DecClFwdArgs p) {
   static_assert(!(DEC && DROP), "evaluate(): no dropout in decode");
+  static_assert(DEC || !HIST, "the search history exists in decode only");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   unsigned char* const F = lds;                        // feed (out(t-1)), later c(t)
   unsigned char* const H1 = lds + R * PA;              // h1(t-1), later h1(t)
@@ -595,6 +597,7 @@ __global__ __launch_bounds__(256, 1) void dec_cl_fwd_kernel(DecClFwdArgs p) {
           node = p.trie_child[p.trie_base[node] + __popcll(tmask & ((1ull << bi) - 1ull))];
         if (olane == 0) {
           if (rvalid) { p.labels[(size_t)arow * p.tok0_stride + t] = bi + 1; if (t == L - 1) p.scores[arow] = best; }
+          if constexpr (HIST) { if (rvalid) p.sc_hist[(size_t)t * B + arow] = best; }
           pst4(p.tokx + (size_t)group * 32 + member, (unsigned)(bi + 1), local);
         }
       }
@@ -1000,10 +1003,16 @@ void dec_cluster_forward(hipStream_t s, const DecClFwdArgs& a0, bool greedy_deco
   (void)hipFuncSetAttribute((const void*)dec_cl_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   (void)hipFuncSetAttribute((const void*)dec_cl_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   (void)hipFuncSetAttribute((const void*)dec_cl_fwd_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const bool hist = greedy_decode && a0.sc_hist;                   // aocr_recognize: the variant that keeps the score history
+  if (hist) (void)hipFuncSetAttribute((const void*)dec_cl_fwd_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   for (int g0 = 0; g0 < groups; g0 += per_pass) {
     DecClFwdArgs a = a0; a.group0 = g0; a.ngroups = std::min(per_pass, groups - g0); a.force_remote = getenv("AOCR_CL_REMOTE") != nullptr; a.no_early = getenv("AOCR_NO_DEC_EARLY") != nullptr;
     a.stamps = getenv("AOCR_DC_STAMPS") ? a.xtab + (size_t)groups * NM : nullptr;   // debugging aid: cycles per phase of workgroup 0
-    if (greedy_decode) { a.tokx = reinterpret_cast<unsigned*>(a.pbuf + (size_t)groups * 32 * 32 * 40); hipLaunchKernelGGL(dec_cl_fwd_kernel<true>, dim3(8 * NM * ((a.ngroups + 7) / 8)), dim3(256), lds, s, a); }
+    if (greedy_decode) {
+      a.tokx = reinterpret_cast<unsigned*>(a.pbuf + (size_t)groups * 32 * 32 * 40);
+      if (hist) hipLaunchKernelGGL((dec_cl_fwd_kernel<true, false, true>), dim3(8 * NM * ((a.ngroups + 7) / 8)), dim3(256), lds, s, a);
+      else hipLaunchKernelGGL(dec_cl_fwd_kernel<true>, dim3(8 * NM * ((a.ngroups + 7) / 8)), dim3(256), lds, s, a);
+    }
     else if (a.drop_h.thr != 0 || a.drop_out.thr != 0) hipLaunchKernelGGL((dec_cl_fwd_kernel<false, true>), dim3(8 * NM * ((a.ngroups + 7) / 8)), dim3(256), lds, s, a);
     else hipLaunchKernelGGL(dec_cl_fwd_kernel<false>, dim3(8 * NM * ((a.ngroups + 7) / 8)), dim3(256), lds, s, a);
   }

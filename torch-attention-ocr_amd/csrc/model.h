@@ -101,6 +101,9 @@ struct aocr_model {
   aocr::bf16_t *bh_b[2][aocr::MAXL] = {}, *bfeed_b[2] = {}, *bh_new_b[aocr::MAXL] = {}, *bcat_b = nullptr;
   float *bzx1, *bzx_tab, *bq, *ba, *bcat, *bout, *blogits, *blogp, *beam_scores;     // bzx_tab [V][4Hd]: per-token first-layer gate input
   int32_t *hist_tok, *hist_par, *tgt_pad, *tge_pad, *trie_loc[2];   // trie_loc: dictionary node of every beam (ping-pong)
+  // search history of aocr_recognize (model_carve: a region of its own, written only when the caller asks for attention or character scores):
+  // attn_hist max_decoder_l x batch_size x max_beam x T_max floats, sc_hist max_decoder_l x batch_size x max_beam
+  float *attn_hist = nullptr, *sc_hist = nullptr;
   void* sgd_scratch;
   float* wg_part = nullptr; size_t wg_part_floats = 0;     // split-K slabs of the filter gradients (conv_backward_filter)
 
@@ -161,6 +164,8 @@ void decoder_tf_forward(aocr_model* m, const Dims& d, const int32_t* tgt, int64_
 void loss_and_dlogits(aocr_model* m, const Dims& d, const int32_t* tge, int64_t st, int64_t sb, float grad_scale, bool want_grad,
                       float* loss_dev);
 void backward_all(aocr_model* m, const float* images, const int32_t* tgt, const Dims& d);
+// attn_hist / sc_hist (aocr_recognize, both or neither): the search history -- attention [Lt][B k][T] (row image * kin + hypothesis, kin = 1 at
+// step 0) and running scores [Lt][B][k] of every hypothesis after every step; every path decode_beam takes records them (DecClFwdArgs::sc_hist)
 void decode_beam(aocr_model* m, const Dims& d, const int32_t* tgt, int beam, int32_t* labels, float* scores,
-                 const aocr_trie* trie = nullptr);
+                 const aocr_trie* trie = nullptr, float* attn_hist = nullptr, float* sc_hist = nullptr);
 }  // namespace aocr

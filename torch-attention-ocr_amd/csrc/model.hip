@@ -163,6 +163,7 @@ int model_carve(aocr_model* m, void* base, size_t bytes) {
   m->bcat = a.get<float>(R * 2 * Hd); m->bout = a.get<float>(R * Hd); m->blogits = a.get<float>(R * LOGIT_LD);
   m->blogp = a.get<float>(R * m->V); m->beam_scores = a.get<float>(R);
   m->hist_tok = a.get<int32_t>(L * R); m->hist_par = a.get<int32_t>(L * R);
+  m->attn_hist = a.get<float>(L * R * T); m->sc_hist = a.get<float>(L * R);          // aocr_recognize's search history
   m->tgt_pad = a.get<int32_t>(B * L); m->tge_pad = a.get<int32_t>(B * L);
   m->trie_loc[0] = a.get<int32_t>(R); m->trie_loc[1] = a.get<int32_t>(R);
   m->sgd_scratch = a.get<char>(sgd_scratch_bytes());
@@ -1356,7 +1357,8 @@ void backward_all(aocr_model* m, const float* images, const int32_t* tgt, const 
 // beam search, model.lua:360-536 + back-trace :573-585.  Rows r = b*k + beam; the context is not replicated
 // (the attention kernel maps row -> image with ctx_div).
 // ------------------------------------------------------------------------------------------------
-void decode_beam(aocr_model* m, const Dims& d, const int32_t* tgt, int beam, int32_t* labels, float* scores, const aocr_trie* trie) {
+void decode_beam(aocr_model* m, const Dims& d, const int32_t* tgt, int beam, int32_t* labels, float* scores, const aocr_trie* trie,
+                 float* attn_hist, float* sc_hist) {
   hipStream_t s = m->s; const bool bf = m->bf16;
   const int B = d.B, T = d.T, Lt = d.L, Hd = m->Hd, E = m->E, V = m->V, Ld = m->Ld;
   const int k = beam;
@@ -1379,7 +1381,7 @@ void decode_beam(aocr_model* m, const Dims& d, const int32_t* tgt, int beam, int
     a.w1i = m->dec[0].swi.wb; a.w1h = m->dec[0].swh.wb; a.w2i = m->dec[1].swi.wb; a.w2h = m->dec[1].swh.wb; a.wc = m->swc.wb;
     a.b2i = m->dec[1].bi; a.b2h = m->dec[1].bh; a.zx1 = m->bzx_tab; a.ctxb = m->context_b; a.ctxa = m->ctxa_b;
     for (int l = 0; l < 2; ++l) { a.cs[l] = m->dcs[l]; a.hsb[l] = m->dhs_b[l]; a.gates[l] = nullptr; }
-    a.a_all = m->a_all; a.out = m->out_all; a.cat_b = m->cat_b; a.out_b = m->out_b;
+    a.a_all = attn_hist ? attn_hist : m->a_all; a.sc_hist = sc_hist; a.out = m->out_all; a.cat_b = m->cat_b; a.out_b = m->out_b;
     a.xbuf = m->dc_xbuf; a.xtab = m->dc_xtab; a.err = m->cl_err;
     a.tok0 = tgt; a.tok0_stride = Lt; a.wo = m->wo; a.bo = m->bo; a.V = V; a.pbuf = m->dc_pbuf; a.labels = labels; a.scores = scores;
     if (trie) { a.trie_mask = (const unsigned long long*)trie->child_mask_dev; a.trie_base = trie->child_base_dev; a.trie_child = trie->child_dev; }
@@ -1401,7 +1403,7 @@ void decode_beam(aocr_model* m, const Dims& d, const int32_t* tgt, int beam, int
     a.w1i = m->dec[0].swi.wb; a.w1h = m->dec[0].swh.wb; a.w2i = m->dec[1].swi.wb; a.w2h = m->dec[1].swh.wb; a.wc = m->swc.wb;
     a.b2i = m->dec[1].bi; a.b2h = m->dec[1].bh; a.zx1 = m->bzx_tab; a.ctxb = m->context_b; a.ctxa = m->ctxa_b;
     for (int l = 0; l < 2; ++l) { a.cs[l] = m->dcs[l]; a.hsb[l] = m->dhs_b[l]; a.gates[l] = nullptr; }
-    a.a_all = m->a_all; a.out = m->out_all; a.cat_b = m->cat_b; a.out_b = m->out_b;
+    a.a_all = attn_hist ? attn_hist : m->a_all; a.sc_hist = sc_hist; a.out = m->out_all; a.cat_b = m->cat_b; a.out_b = m->out_b;
     a.xbuf = m->dc_xbuf; a.xtab = m->dc_xtab; a.err = m->cl_err;
     a.tok0 = tgt; a.tok0_stride = Lt; a.wo = m->wo; a.bo = m->bo; a.V = V; a.pbuf = m->dc_pbuf; a.labels = labels; a.scores = scores;
     a.beam = k; a.hist_tok = m->hist_tok; a.hist_par = m->hist_par; a.beam_scores = m->beam_scores;
@@ -1432,7 +1434,7 @@ void decode_beam(aocr_model* m, const Dims& d, const int32_t* tgt, int beam, int
       io.gates[l] = nullptr;
     }
     float* out = (direct && m->cfg.input_feed) ? m->bfeed[nxt] : m->bout;
-    io.q = m->bq; io.a = m->ba; io.cat = m->bcat; io.out = out;
+    io.q = m->bq; io.a = attn_hist ? attn_hist + (size_t)t * B * k * T : m->ba; io.cat = m->bcat; io.out = out;      // (rows b kin + beam, as the history's)
     if (dsh) {
       io.feed_b = m->bfeed_b[cur]; io.cat_b = m->bcat_b;
       io.out_b = (direct && m->cfg.input_feed) ? m->bfeed_b[nxt] : nullptr;       // (beam > 1: the gather below writes the next feed's shadow from the fp32 rows)
@@ -1449,14 +1451,14 @@ void decode_beam(aocr_model* m, const Dims& d, const int32_t* tgt, int beam, int
     }
     if (V <= 64 && Hd % 4 == 0) {                        // projector + LogSoftMax + selection in one launch
       project_select(s, out, Hd, m->wo, m->bo, Hd, t == 0 ? nullptr : tok, m->beam_scores, m->hist_tok + (size_t)t * B * k,
-                     m->hist_par + (size_t)t * B * k, B, kin, k, V, tv);
+                     m->hist_par + (size_t)t * B * k, B, kin, k, V, tv, sc_hist ? sc_hist + (size_t)t * B * k : nullptr);
     } else {
       SmallKKArgs z; z.a = make_loadk(out, Hd, R, Hd); z.b = make_loadk(m->wo, Hd, V, Hd);
       z.ep = make_store(m->blogits, LOGIT_LD, R, V, m->bo, nullptr, 0); z.K = Hd;
       launch_small_kk(s, bf, 1, &z, R, V);
       logsoftmax_nll(s, m->blogits, LOGIT_LD, tgt, 0, 0, R, m->blogp, nullptr, nullptr, R, V, 0.f);
       beam_select(s, m->blogp, t == 0 ? nullptr : tok, m->beam_scores, m->hist_tok + (size_t)t * B * k,
-                  m->hist_par + (size_t)t * B * k, B, kin, k, V, nullptr, 0, tv);
+                  m->hist_par + (size_t)t * B * k, B, kin, k, V, nullptr, 0, tv, sc_hist ? sc_hist + (size_t)t * B * k : nullptr);
     }
     if (!direct) {
       const int32_t* par = m->hist_par + (size_t)t * B * k;

@@ -221,14 +221,15 @@ struct ShadowJob { const float* w; bf16_t* wb; bf16_t* wtb; int64_t ld, ldb, ldt
 void shadow_jobs(hipStream_t s, const ShadowJob* jobs_dev, int njobs, int total_tiles, int tile_off = 0);      // tiles [tile_off, tile_off + total_tiles) of the table
 // flat dictionary trie + the per-beam node ids of one decode step (mask == nullptr: unconstrained); needs V <= 64
 struct TrieView { const unsigned long long* mask; const int32_t* base; const int32_t* child; const int32_t* loc_in; int32_t* loc_out; };
+// sc_out (optional, recognition): a second copy of the kout new running scores, [B][kout] (the score history of aocr_recognize)
 void beam_select(hipStream_t s, const float* logp, const int32_t* prev_tok, float* beam_scores, int32_t* tokens,
                  int32_t* parents, int B, int kin, int kout, int V, const float* logits = nullptr, int64_t ldl = 0,
-                 const TrieView* tv = nullptr);
+                 const TrieView* tv = nullptr, float* sc_out = nullptr);
 // logits != nullptr (and V <= 64): raw projector outputs, the LogSoftMax is applied inside (logp is then unused)
 // projector + LogSoftMax + beam bookkeeping of one decode step in one launch (V <= 64, Hd % 4 == 0)
 void project_select(hipStream_t s, const float* h, int64_t ldh, const float* wo, const float* bo, int Hd, const int32_t* prev_tok,
                     float* beam_scores, int32_t* tokens, int32_t* parents, int B, int kin, int kout, int V,
-                    const TrieView* tv = nullptr);
+                    const TrieView* tv = nullptr, float* sc_out = nullptr);
 void token_rows(hipStream_t s, const float* table, const int32_t* tok, int64_t stride, float* dst, int R, int width);   // dst[r] = table[tok[r*stride]-1]
 // dst[b*kout+i][:] = src[(kin==1 ? b : b*kin + parents[b*kout+i])][:]
 void gather_beam_rows_many(hipStream_t s, int n, const float* const* src, float* const* dst, int64_t ld, const int32_t* parents, int B, int kin, int kout, int width,
@@ -237,6 +238,11 @@ void gather_beam_rows(hipStream_t s, const float* src, int64_t lds, float* dst, 
                       int kin, int kout, int width);
 void beam_backtrace(hipStream_t s, const int32_t* hist_tok, const int32_t* hist_par, const float* beam_scores,
                     int32_t* labels, float* scores, int Lt, int B, int k);
+// aocr_recognize's optional outputs from the search history: the winning hypothesis of each image (backtrace_kernel's rule; k = 1 / hist_par ==
+// nullptr: greedy), walked back through hist_par [Lt][B][k]; char_logp [B][Lt] = score differences of sc_hist [Lt][B][k], attn [B][Lt][T] = its
+// rows of attn_hist [Lt][B k][T] (row b kin + parent, kin = 1 at step 0).  Steps after the first EOS / PAD of labels are 0.  Either output may be nullptr.
+void recognize_gather(hipStream_t s, const int32_t* labels, const int32_t* hist_par, const float* beam_scores, const float* sc_hist,
+                      const float* attn_hist, float* char_logp, float* attn, int Lt, int B, int k, int T);
 void fill_i32(hipStream_t s, int32_t* p, int32_t v, int64_t n);
 // Levenshtein distance between two id rows cut at the first EOS (utils.lua:55-94 over the strings of utils.lua:136-168)
 void edit_distance(hipStream_t s, const int32_t* labels, const int32_t* targets, int B, int L, int32_t* dist, int32_t* target_len);
@@ -299,6 +305,9 @@ struct DecClFwdArgs {
   // round 4, teacher-forced loop: zx1 as the per-token table [V][4 Hd] too (zx_tok = the input tokens, token of (step t, row b) = zx_tok[t zx_st + b zx_sb]):
   // no (L B, 4 Hd) gate-input tensor is written or read; V must be set
   const int32_t* zx_tok = nullptr; int64_t zx_st = 0, zx_sb = 0;
+  // label-free recognition (aocr_recognize; the kernels' HIST variants only): cumulative score of every hypothesis after every step, [L][B][k]
+  // (greedy: [L][B]); the attention rows go to a_all, [L][B k][T] with row image * kin + hypothesis (kin = 1 at step 0)
+  float* sc_hist = nullptr;
 };
 // decoder BPTT in one launch (dec_cluster.hip); reads what the forward cluster kernel saved (interleaved gates)
 struct DecClBwdArgs {

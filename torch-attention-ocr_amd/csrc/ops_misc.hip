@@ -2206,7 +2206,7 @@ __device__ __forceinline__ int trie_next(const TrieView& tv, int node, int v0, b
 __global__ __launch_bounds__(64) void beam_select_kernel(const float* __restrict__ logp, const int32_t* __restrict__ prev_tok,
                                                          float* __restrict__ beam_scores, int32_t* __restrict__ tokens,
                                                          int32_t* __restrict__ parents, int kin, int kout, int V,
-                                                         const float* __restrict__ logits, int64_t ldl, TrieView tv) {
+                                                         const float* __restrict__ logits, int64_t ldl, TrieView tv, float* __restrict__ sc_out) {
   extern __shared__ float cand[];                               // kin*V
   const int b = blockIdx.x, lane = threadIdx.x;
   const bool first = prev_tok == nullptr;
@@ -2258,6 +2258,7 @@ __global__ __launch_bounds__(64) void beam_select_kernel(const float* __restrict
     __syncthreads();
   }
   for (int k = lane; k < kout; k += 64) beam_scores[b * kout + k] = cand[n + k];
+  if (sc_out) for (int k = lane; k < kout; k += 64) sc_out[b * kout + k] = cand[n + k];      // recognition: the score history
 }
 // Decode step tail in ONE launch: projector (output_projector.lua:3-8: logits = W_o h + b), LogSoftMax, finished-beam masking,
 // score accumulation and top-k selection (model.lua:399-404,446-458,516).  One workgroup per batch element; the kin x V logits are
@@ -2266,7 +2267,8 @@ constexpr int PS_NW = 16;                                      // waves per batc
 __global__ __launch_bounds__(64 * PS_NW) void project_select_kernel(const float* __restrict__ h, int64_t ldh, const float* __restrict__ wo,
                                                              const float* __restrict__ bo, int Hd, const int32_t* __restrict__ prev_tok,
                                                              float* __restrict__ beam_scores, int32_t* __restrict__ tokens,
-                                                             int32_t* __restrict__ parents, int kin, int kout, int V, TrieView tv) {
+                                                             int32_t* __restrict__ parents, int kin, int kout, int V, TrieView tv,
+                                                             float* __restrict__ sc_out) {
   extern __shared__ float cand[];                               // kin*V (+ kout stash)
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool first = prev_tok == nullptr;
@@ -2322,20 +2324,21 @@ __global__ __launch_bounds__(64 * PS_NW) void project_select_kernel(const float*
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     }
     for (int k = lane; k < kout; k += 64) beam_scores[b * kout + k] = cand[n + k];
+    if (sc_out) for (int k = lane; k < kout; k += 64) sc_out[b * kout + k] = cand[n + k];    // recognition: the score history
   }
 }
 void project_select(hipStream_t s, const float* h, int64_t ldh, const float* wo, const float* bo, int Hd, const int32_t* prev_tok,
-                    float* beam_scores, int32_t* tokens, int32_t* parents, int B, int kin, int kout, int V, const TrieView* tv) {
+                    float* beam_scores, int32_t* tokens, int32_t* parents, int B, int kin, int kout, int V, const TrieView* tv, float* sc_out) {
   size_t sh = (size_t)(kin * V + kout) * sizeof(float);
   hipLaunchKernelGGL(project_select_kernel, dim3(B), dim3(64 * PS_NW), sh, s, h, ldh, wo, bo, Hd, prev_tok, beam_scores, tokens, parents, kin, kout, V,
-                     tv ? *tv : TrieView{});
+                     tv ? *tv : TrieView{}, sc_out);
 }
 void beam_select(hipStream_t s, const float* logp, const int32_t* prev_tok, float* beam_scores, int32_t* tokens, int32_t* parents,
-                 int B, int kin, int kout, int V, const float* logits, int64_t ldl, const TrieView* tv) {
+                 int B, int kin, int kout, int V, const float* logits, int64_t ldl, const TrieView* tv, float* sc_out) {
   size_t sh = (size_t)(kin * V + kout) * sizeof(float);
   if (V > 64) logits = nullptr;                                 // the fused LogSoftMax needs one lane per class
   hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(64), sh, s, logp, prev_tok, beam_scores, tokens, parents, kin, kout, V, logits, ldl,
-                     tv ? *tv : TrieView{});
+                     tv ? *tv : TrieView{}, sc_out);
 }
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ src, int64_t lds, float* __restrict__ dst,
                                                           int64_t ldd, const int32_t* __restrict__ parents, int B, int kin, int kout,
@@ -2408,6 +2411,42 @@ __global__ void backtrace_kernel(const int32_t* __restrict__ hist_tok, const int
 void beam_backtrace(hipStream_t s, const int32_t* hist_tok, const int32_t* hist_par, const float* beam_scores, int32_t* labels,
                     float* scores, int Lt, int B, int k) {
   hipLaunchKernelGGL(backtrace_kernel, dim3(cdiv(B, 128)), dim3(128), 0, s, hist_tok, hist_par, beam_scores, labels, scores, Lt, B, k);
+}
+// aocr_recognize: one wave per image.  The walk back through the parents is wave-uniform (every lane follows it); lanes stride T, so
+// each attention row is read and written as one coalesced pass of the wave.
+__global__ __launch_bounds__(64) void recognize_gather_kernel(const int32_t* __restrict__ labels, const int32_t* __restrict__ hist_par,
+                                                              const float* __restrict__ beam_scores, const float* __restrict__ sc_hist,
+                                                              const float* __restrict__ attn_hist, float* __restrict__ char_logp,
+                                                              float* __restrict__ attn, int Lt, int B, int k, int T) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  int tend = Lt - 1;                                            // the first EOS / PAD: every later step is PAD at no cost (model.lua:448-449)
+  for (int t = 0; t < Lt; ++t) { const int v = labels[(int64_t)b * Lt + t]; if (v == 1 || v == 3) { tend = t; break; } }
+  int idx = 0;
+  if (k > 1) {                                                  // the winning hypothesis: torch.max's first maximum, as backtrace_kernel
+    float best = beam_scores[(int64_t)b * k];
+    for (int i = 1; i < k; ++i) if (beam_scores[(int64_t)b * k + i] > best) { best = beam_scores[(int64_t)b * k + i]; idx = i; }
+  }
+  for (int t = Lt - 1; t >= 0; --t) {
+    const int kin = t == 0 ? 1 : k;
+    const int par = (k > 1 && hist_par) ? hist_par[((int64_t)t * B + b) * k + idx] : 0;
+    const bool on = t <= tend;
+    if (char_logp && lane == 0) {
+      float v = 0.f;
+      if (on) v = sc_hist[((int64_t)t * B + b) * k + idx] - (t > 0 ? sc_hist[((int64_t)(t - 1) * B + b) * k + par] : 0.f);
+      char_logp[(int64_t)b * Lt + t] = v;
+    }
+    if (attn) {
+      const float* src = attn_hist + ((int64_t)t * B * k + (int64_t)b * kin + par) * T;
+      float* dst = attn + ((int64_t)b * Lt + t) * T;
+      for (int j = lane; j < T; j += 64) dst[j] = on ? src[j] : 0.f;
+    }
+    idx = par;
+  }
+}
+void recognize_gather(hipStream_t s, const int32_t* labels, const int32_t* hist_par, const float* beam_scores, const float* sc_hist,
+                      const float* attn_hist, float* char_logp, float* attn, int Lt, int B, int k, int T) {
+  if (!char_logp && !attn) return;
+  hipLaunchKernelGGL(recognize_gather_kernel, dim3(B), dim3(64), 0, s, labels, hist_par, beam_scores, sc_hist, attn_hist, char_logp, attn, Lt, B, k, T);
 }
 __global__ void fill_i32_kernel(int32_t* p, int32_t v, int64_t n) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
