@@ -1,0 +1,47 @@
+"""CPU: the kernel-test shim (tests/kprobe.hip) still matches csrc/ops.h.  The shim is compiled here and every aocr:: symbol it
+leaves undefined must be defined by libaocr.so -- a launcher whose signature changed in ops.h without the library being rebuilt,
+or a wrapper calling a signature that no longer exists, fails here instead of as a load error on the GPU box."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "torch-attention-ocr_amd", "csrc")
+LIB = os.path.join(ROOT, "torch-attention-ocr_amd", "aocr", "libaocr.so")
+
+
+def _hipcc():
+    for c in (shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
+        if c and os.path.exists(c):
+            return c
+    return None
+
+
+def _symbols(path, *flags):
+    out = subprocess.run(["nm", "-D", *flags, path], check=True, capture_output=True, text=True).stdout
+    return {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
+
+
+def test_kprobe_symbols_resolve_in_libaocr(tmp_path):
+    hipcc = _hipcc()
+    if hipcc is None or shutil.which("nm") is None:
+        pytest.skip("no hipcc / nm on this machine")
+    assert os.path.exists(LIB), "libaocr.so not built (run __graft_entry__.build())"
+    so = str(tmp_path / "libkprobe.so")
+    subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value",
+                    "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, os.path.join(ROOT, "tests", "kprobe.hip"), "-o", so,
+                    "-L" + os.path.dirname(LIB), "-laocr"], check=True, capture_output=True)
+    undef = _symbols(so, "--undefined-only")
+    wanted = {s for s in undef if s.startswith("_ZN4aocr")}
+    # every launcher the shim wraps is reached through a mangled aocr:: reference
+    for name in ("conv_forward", "conv_backward_data", "conv_backward_filter", "conv_weight_shadows", "splitk_reduce", "gemm_hh",
+                 "gemm_hh_shadow", "gemm_hh_cat", "grouped_wgrad", "bn_relu_forward"):
+        assert any(f"{len(name)}{name}E" in s for s in wanted), f"the shim does not call aocr::{name}"
+    defined = _symbols(LIB, "--defined-only")
+    missing = sorted(wanted - defined)
+    assert not missing, f"aocr:: symbols the shim needs but libaocr.so does not define (ops.h signature drift?): {missing}"
+    exported = _symbols(so, "--defined-only")
+    for name in ("kp_conv_forward", "kp_conv_backward_data", "kp_conv_backward_filter", "kp_grouped_wgrad", "kp_gemm_hh_cat"):
+        assert name in exported

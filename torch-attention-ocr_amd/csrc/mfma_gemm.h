@@ -417,9 +417,13 @@ struct LoadConvKh {
     if (c.ch >= g.C) { c.ch -= g.C; if (++c.kw == g.KW) { c.kw = 0; ++c.kh; } }
   }
   __device__ __forceinline__ uint4 load8(const Ctx& c, const Cur& u, int chunk) const {
-    int sy = c.y + g.sgn * u.kh + g.off, sx = c.x + g.sgn * u.kw + g.off;
-    bool ok = c.ok && u.k < g.K && (unsigned)sy < (unsigned)g.H && (unsigned)sx < (unsigned)g.W;
-    if (ok) return *reinterpret_cast<const uint4*>(src + (((int64_t)c.b * g.H + sy) * g.W + sx) * g.C + u.ch + 8 * chunk);
+    int kh = u.kh, kw = u.kw, ch = u.ch + 8 * chunk;
+    if (g.C % 32) {                                   // (C % 8 == 0) a 32-wide tile straddles taps: each 8-channel chunk finds its own tap
+      const int k = u.k + 8 * chunk, tap = k / g.C; ch = k - tap * g.C; kh = tap / g.KW; kw = tap - kh * g.KW;
+    }
+    int sy = c.y + g.sgn * kh + g.off, sx = c.x + g.sgn * kw + g.off;
+    bool ok = c.ok && u.k + 8 * chunk < g.K && (unsigned)sy < (unsigned)g.H && (unsigned)sx < (unsigned)g.W;
+    if (ok) return *reinterpret_cast<const uint4*>(src + (((int64_t)c.b * g.H + sy) * g.W + sx) * g.C + ch);
     return make_uint4(0, 0, 0, 0);
   }
   // LDS-DMA staging: C % 32 == 0, so a 32-k tile is 32 channels of ONE tap and (kh, kw, ch) are wave-uniform scalars;

@@ -12,12 +12,20 @@ static void split_k(int K, int chunk, int& ksplit, int& kper) {
   if (kper < chunk) kper = chunk;
   ksplit = cdiv(K, kper); if (ksplit < 1) ksplit = 1;
 }
+// dispatch trace (AOCR_TRACE set, read per call): one stderr line per launch of the bf16-source conv / GEMM entry points,
+// "[aocr] <function>: <kernel>[<instantiation>] M N K", so the kernel tests can prove which branch a shape reached
+static thread_local const char* t_trace_fn = nullptr;
+struct TraceScope { explicit TraceScope(const char* fn) { t_trace_fn = fn; } ~TraceScope() { t_trace_fn = nullptr; } };
+static void trace_launch(const char* kernel, const char* inst, long long M, long long N, long long K) {
+  if (t_trace_fn && getenv("AOCR_TRACE")) fprintf(stderr, "[aocr] %s: %s[%s] %lld %lld %lld\n", t_trace_fn, kernel, inst, M, N, K);
+}
 // LDS-tiled bf16 kernel (any loader pair, fp32 or bf16 sources)
 template <class AL, class BL, class EP>
 static void launch_lds(hipStream_t s, const AL& a, const BL& b, const EP& ep, int M, int N, int K, int ksplit) {
   if (M <= 0 || N <= 0) return;
   int kper; split_k(K, 32, ksplit, kper);
   const int gx = cdiv(N, 128), gy = cdiv(M, 128);
+  trace_launch("gemm_lds_bf16_kernel", "32", M, N, K);
   hipLaunchKernelGGL((gemm_lds_bf16_kernel<AL, BL, EP>), dim3(gx * gy, 1, ksplit), dim3(256), 0, s, a, b, ep, K, kper, gx, gy);
 }
 // 256 x 256 x 32 LDS-DMA kernel (bf16 K-contiguous operand pairs).  One workgroup per CU, so it is chosen only when the grid
@@ -48,6 +56,7 @@ static void launch_dma_narrow(hipStream_t s, const AL& a, const BL& b, const EP&
   const int gy = cdiv(M, 256);
   const char* const ns = getenv("AOCR_NO_NARROW_STAGED");  // A/B and parity: the quad epilogue (read per call)
   const int staged = !(ns && ns[0] == '1');
+  trace_launch("gemm_dma_narrow_kernel", N % 128 == 0 ? "2" : "1", M, N, K);
   if (N % 128 == 0) { const int gx = N / 128; hipLaunchKernelGGL((gemm_dma_narrow_kernel<AL, BL, EP, 2>), dim3(gx * gy), dim3(512), 0, s, a, b, ep, K, gx, gy, zero_page(), staged); }   // (N > 128: column blocks of 128)
   else          hipLaunchKernelGGL((gemm_dma_narrow_kernel<AL, BL, EP, 1>), dim3(gy), dim3(512), 0, s, a, b, ep, K, 1, gy, zero_page(), staged);
 }
@@ -64,6 +73,7 @@ static void launch_dma128(hipStream_t s, const AL& a, const BL& b, const EP& ep,
   // <= one workgroup per compute unit: a deep ring (7 tiles in flight) is all the latency hiding that workgroup has; otherwise two workgroups of 3 tiles in flight
   static const int cus = [] { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
   const char* const w4 = getenv("AOCR_DMA128_W4");         // A/B: the 4-wave form at every grid size
+  trace_launch("gemm_dma128_kernel", gx * gy > cus ? "4,4" : (w4 && w4[0] == '1') ? "8,4" : "8,8", M, N, K);
   if (gx * gy <= cus && !(w4 && w4[0] == '1')) hipLaunchKernelGGL((gemm_dma128_kernel<AL, BL, EP, 8, 8>), dim3(gx * gy), dim3(512), 0, s, a, b, ep, K, gx, gy, zero_page());
   else if (gx * gy <= cus) hipLaunchKernelGGL((gemm_dma128_kernel<AL, BL, EP, 8, 4>), dim3(gx * gy), dim3(256), 0, s, a, b, ep, K, gx, gy, zero_page());
   else hipLaunchKernelGGL((gemm_dma128_kernel<AL, BL, EP, 4, 4>), dim3(gx * gy), dim3(256), 0, s, a, b, ep, K, gx, gy, zero_page());
@@ -79,6 +89,7 @@ static void launch_dma(hipStream_t s, const AL& a, const BL& b, const EP& ep, in
   const int gx = N / 256, gy = cdiv(M, 256);
   const char* const so = getenv("AOCR_HALO4_STAGED");        // the same switch as the halo kernel's: output tiles through LDS (read per call: tests toggle it)
   const int opt = so ? atoi(so) : 7;
+  trace_launch("gemm_dma_bf16_kernel", tag ? "tag" : "", M, N, K);
   if (tag) hipLaunchKernelGGL((gemm_dma_bf16_kernel<AL, BL, EP, 0, false, false, 1>), dim3(gx * gy), dim3(512), 0, s, a, b, ep, K, gx, gy, zero_page(), opt);
   else hipLaunchKernelGGL((gemm_dma_bf16_kernel<AL, BL, EP>), dim3(gx * gy), dim3(512), 0, s, a, b, ep, K, gx, gy, zero_page(), opt);
 }
@@ -101,11 +112,13 @@ static void launch_halo(hipStream_t s, const LoadConvKh& a, const LoadKh& b, con
     if (!eight) {
       const char* const so = getenv("AOCR_HALO4_STAGED");
       const int opt = so ? atoi(so) : 7;   // 1: fp32 tile of the data gradient, 2: of conv3 / conv5 forward, 4: pooled tile -- through LDS
+      trace_launch("gemm_halo4_bf16_kernel", SGN > 0 ? "fwd" : "dgrad", M, N, 9LL * a.g.C);
       if (tag) hipLaunchKernelGGL((gemm_halo4_bf16_kernel<EP, SGN, 1>), dim3(gx * gy), dim3(256), 0, s, a, b, ep, gx, gy, zero_page(), opt);
       else hipLaunchKernelGGL((gemm_halo4_bf16_kernel<EP, SGN>), dim3(gx * gy), dim3(256), 0, s, a, b, ep, gx, gy, zero_page(), opt);
       return;
     }
   }
+  trace_launch("gemm_halo_bf16_kernel", SGN > 0 ? "fwd" : "dgrad", M, N, 9LL * a.g.C);
   if (tag) hipLaunchKernelGGL((gemm_halo_bf16_kernel<EP, SGN, MT, NT, 1>), dim3(gx * gy), dim3(512), 0, s, a, b, ep, gx, gy, zero_page());
   else hipLaunchKernelGGL((gemm_halo_bf16_kernel<EP, SGN, MT, NT>), dim3(gx * gy), dim3(512), 0, s, a, b, ep, gx, gy, zero_page());
 }
@@ -593,6 +606,7 @@ void project_loss(hipStream_t s, const float* out, int64_t ldo, const float* wo,
 
 void gemm_hh(hipStream_t s, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, float* C, int64_t ldc, int M, int N, int K,
              const float* bias, const float* bias2, int flags) {
+  const TraceScope ts("gemm_hh");
   LoadKh a; a.p = A; a.ld = lda; a.rows = M; a.K = K;
   LoadKh b; b.p = B; b.ld = ldb; b.rows = N; b.K = K;
   // (the 256 x 256 LDS-DMA kernel was measured slower here: K = 512 is only 16 tiles deep -- hoisted encoder projection at C3,
@@ -610,6 +624,7 @@ void gemm_hh(hipStream_t s, const bf16_t* A, int64_t lda, const bf16_t* B, int64
 // shape does not take that kernel (the caller then runs two products).
 bool gemm_hh_cat(hipStream_t s, const bf16_t* A0, const bf16_t* A1, int64_t lda, const bf16_t* B0, const bf16_t* B1, int64_t ldb, float* C, int64_t ldc, int M, int N, int K0, int K1) {
   if (getenv("AOCR_NO_HH_NARROW") || env_is_1("AOCR_NO_HH_CAT") || dma_disabled() || (M % 256 && (M < 256 || env_is_1("AOCR_HH_NARROW_FULL_ONLY"))) || N % 128 || K0 % 32 || K1 % 32 || cdiv(M, 256) * (N / 128) < 200) return false;
+  const TraceScope ts("gemm_hh_cat");
   LoadKhCat a; a.p0 = A0; a.p1 = A1; a.ld0 = a.ld1 = lda; a.rows = M; a.K0 = K0; a.K = K0 + K1;
   LoadKhCat b; b.p0 = B0; b.p1 = B1; b.ld0 = b.ld1 = ldb; b.rows = N; b.K0 = K0; b.K = K0 + K1;
   launch_dma_narrow(s, a, b, make_store(C, ldc, M, N, nullptr, nullptr, 0), M, N, K0 + K1);
@@ -618,6 +633,7 @@ bool gemm_hh_cat(hipStream_t s, const bf16_t* A0, const bf16_t* A1, int64_t lda,
 
 void gemm_hh_shadow(hipStream_t s, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, float* C, int64_t ldc, bf16_t* Cb, int64_t ldcb,
                     int M, int N, int K) {
+  const TraceScope ts("gemm_hh_shadow");
   LoadKh a; a.p = A; a.ld = lda; a.rows = M; a.K = K;
   LoadKh b; b.p = B; b.ld = ldb; b.rows = N; b.K = K;
   EpStore e = make_store(C, ldc, M, N, nullptr, nullptr, 0); e.Cb = Cb; e.ldcb = ldcb;
@@ -649,6 +665,7 @@ static void grouped_launch(hipStream_t s, const WGradProblem* const* q, int cnt,
     first += cdiv(q[i]->M, 128) * P.gx * ksplit;
   }
   g.total = first; (void)shadows;
+  for (int i = 0; i < cnt; ++i) trace_launch(shadows ? "wgrad_tr_grouped_kernel" : "gemm_lds_grouped_kernel", "", q[i]->M, q[i]->N, q[i]->K);
   hipLaunchKernelGGL(kernel, dim3(first), dim3(256), 0, s, g);
 }
 
@@ -673,11 +690,13 @@ static int grouped_launch_dma(hipStream_t s, const WGradProblem* const* q, int c
     P.C = q[i]->C; P.ldc = q[i]->ldc; P.f4first = f4; f4 += (long long)P.M * (P.N / 4);
   }
   g.total = first; g.f4total = f4;
+  for (int i = 0; i < cnt; ++i) trace_launch("wgrad_dma_grouped_kernel", "slab_reduce", q[i]->M, q[i]->N, q[i]->K);
   hipLaunchKernelGGL((wgrad_dma_grouped_kernel<0>), dim3(first), dim3(512), 0, s, g, zero_page());
   hipLaunchKernelGGL((wgrad_slab_reduce_kernel<0>), dim3((unsigned)((f4 + 255) / 256)), dim3(256), 0, s, g);
   return cnt;
 }
 void grouped_wgrad(hipStream_t s, bool bf16, const WGradProblem* p, int n, float* part, size_t part_floats) {
+  const TraceScope ts("grouped_wgrad");
   if (!bf16) {                                                // fp32 mode: one launch per problem
     for (int i = 0; i < n; ++i)
       gemm(s, false, p[i].A, p[i].lda, false, p[i].B, p[i].ldb, false, p[i].C, p[i].ldc, p[i].M, p[i].N, p[i].K, nullptr, nullptr, EP_ATOMIC);
@@ -716,6 +735,7 @@ static LoadConvK make_convk(const float* src, int B, int Hs, int Ws, int C, int 
 void conv_forward(hipStream_t s, bool bf16, const float* x, const float* w, const float* bias, float* y, uint8_t* idx, int B,
                   int H, int W, int Cin, int Cout, int ks, int pad, int relu, int pool, const bf16_t* xb, const bf16_t* wb,
                   bf16_t* yb, int profile_tag, const float* bn_save, const float* bn_w, const float* bn_b, double* bn_part, int* bn_chunks, int* y_bf16) {
+  const TraceScope ts("conv_forward");
   const int Ho = H + 2 * pad - ks + 1, Wo = W + 2 * pad - ks + 1;
   LoadConvK a = make_convk(x, B, H, W, Cin, ks, 1, -pad, Ho, Wo, pool);
   EpConv ep; ep.y = y; ep.idx = idx; ep.bias = bias; ep.Cout = Cout; ep.rows = a.rows; ep.pmode = pool; ep.relu = relu; ep.yb = yb;
@@ -754,6 +774,7 @@ void conv_forward(hipStream_t s, bool bf16, const float* x, const float* w, cons
 
 void conv_backward_data(hipStream_t s, bool bf16, const float* dy, const float* w, float* dx, int B, int H, int W, int Cin,
                         int Cout, int ks, int pad, const bf16_t* dyb, const bf16_t* wtb, const float* wtf, int* dx16, const BnBwdFuse* bnb, int* bnb_chunks) {
+  const TraceScope ts("conv_backward_data");
   const int Ho = H + 2 * pad - ks + 1, Wo = W + 2 * pad - ks + 1;
   LoadConvK a = make_convk(dy, B, Ho, Wo, Cout, ks, -1, pad, H, W, 0);
   EpStore ep = make_store(dx, Cin, a.rows, Cin);
@@ -802,6 +823,7 @@ void conv_backward_data(hipStream_t s, bool bf16, const float* dy, const float* 
 
 void conv_backward_filter(hipStream_t s, bool bf16, const float* x, const float* dy, float* dw, float* dbias, int B, int H,
                           int W, int Cin, int Cout, int ks, int pad, const bf16_t* xb, const bf16_t* dyb, float* part, size_t part_floats, int profile_tag) {
+  const TraceScope ts("conv_backward_filter");
   const int Ho = H + 2 * pad - ks + 1, Wo = W + 2 * pad - ks + 1;
   const int P = B * Ho * Wo, N = ks * ks * Cin;
   LoadConvXcol b; b.x = x; b.H = H; b.W = W; b.Cin = Cin; b.KW = ks; b.pad = pad; b.Ho = Ho; b.Wo = Wo; b.N = N; b.K = P;
@@ -834,6 +856,8 @@ void conv_backward_filter(hipStream_t s, bool bf16, const float* x, const float*
         // (IM = !AOCR_NO_WGRAD_ISSUE_MID: MFMAs start behind their own k-half's reads, DMA issue between the halves -- mfma_gemm.h)
 #define AOCR_WGH(TAGV, MGV, RGV, IMV, THREADS, MTV) hipLaunchKernelGGL((conv_wgrad_halo_kernel<TAGV, MGV, RGV, IMV>), dim3(htiles * ksh), dim3(THREADS), 0, s, dyb, xb, part, (long long)mn, B, H, W, Cin, Cout, Cin / 32, Cout / MTV, ksh, per, zero_page())
         const bool im = !env_is_1("AOCR_NO_WGRAD_ISSUE_MID");
+        { char inst[48]; snprintf(inst, sizeof inst, "%d,%s,%s", hmt, W % 32 ? "ragged" : "whole", im ? "issue_mid" : "no_issue_mid");
+          trace_launch("conv_wgrad_halo_kernel", inst, Cout, N, P); }
         if (W % 32) {                                            // ragged rows: the form with the row-end pointer steps and the d y validity compare
           if (hmt == 128) { if (im) AOCR_WGH(0, 2, true, true, 256, 128); else AOCR_WGH(0, 2, true, false, 256, 128); }
           else { if (im) AOCR_WGH(0, 4, true, true, 512, 256); else AOCR_WGH(0, 4, true, false, 512, 256); }
@@ -851,6 +875,7 @@ void conv_backward_filter(hipStream_t s, bool bf16, const float* x, const float*
       int ks2 = tiles >= 128 ? (tiles >= 200 ? 1 : 2) : 256 / tiles, kper2; split_k(P, 32, ks2, kper2);      // one round of the 256 CUs
       const size_t mn = (size_t)Cout * N;
       float* const slab = (part && ks2 > 1 && mn * ks2 <= part_floats && !getenv("AOCR_WGRAD_ATOMIC")) ? part : nullptr;
+      trace_launch("conv_wgrad_dma_kernel", slab ? "slab" : "atomic", Cout, N, P);
       if (profile_tag)        // the same kernel under its own symbol (ABL bit 256 selects nothing): aocr_profile_kernel, per-kernel rocprofv3 / PMC rows
         hipLaunchKernelGGL((conv_wgrad_dma_kernel<EpStore, 256>), dim3(tiles * ks2), dim3(512), 0, s, ah, bh, ep, P, kper2, cdiv(N, 256), Cout / 256, zero_page(), ks2, slab, (long long)mn);
       else
@@ -863,6 +888,7 @@ void conv_backward_filter(hipStream_t s, bool bf16, const float* x, const float*
     const int gx = cdiv(N, 128), gy = cdiv(Cout, 128);
     const size_t mn = (size_t)Cout * N;
     float* const slab = (part && ks > 1 && mn * ks <= part_floats && !getenv("AOCR_WGRAD_ATOMIC")) ? part : nullptr;
+    trace_launch("conv_wgrad_tr_kernel", slab ? "slab" : "atomic", Cout, N, P);
     hipLaunchKernelGGL((conv_wgrad_tr_kernel<EpStore>), dim3(gx * gy * ks), dim3(256), 0, s, ah, bh, ep, P, kper, gx, gy, ks, slab, (long long)mn);
     if (slab) splitk_reduce(s, slab, ks, mn, dw);
   } else {
