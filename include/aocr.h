@@ -403,6 +403,29 @@ typedef struct aocr_image_desc {
 int aocr_preprocess_lines(void* stream, const uint8_t* src_dev, const aocr_image_desc* desc_dev, int32_t n_images,
                           int32_t out_h, int32_t out_w, float* out_dev);
 
+/* ---- training augmentation: affine warp, contrast / brightness, additive noise -----------------------------------------
+ * in_dev, out_dev: (n_images, 1, H, W) fp32 in 0..255, the output layout of aocr_preprocess_lines; they must not alias.
+ * warp_dev[i]: the record of image i.  Per output pixel (x, y), every operation one rounded single-precision op, in this order:
+ *   sx = (m00*x + m01*y) + m02, sy = (m10*x + m11*y) + m12, clamped to [-1, W] and [-1, H] (NaN becomes -1);
+ *   x0 = floor(sx), fx = sx - x0 (the same for y); the taps (x0,y0) (x0+1,y0) (x0,y0+1) (x0+1,y0+1) = a b c d read in_dev inside
+ *   [0,W) x [0,H) and are `fill` elsewhere;  top = (1-fx)*a + fx*b, bot = (1-fx)*c + fx*d, s = (1-fy)*top + fy*bot;
+ *   v = gain*s + offset;
+ *   r = splitmix64(splitmix64(seed ^ counter*0xD1342543DE82EF95) + idx), idx = (i*H + y)*W + x (the construction of the dropout
+ *   masks), u1 = (r >> 40) * 2^-24, u2 = ((r >> 16) & 0xFFFFFF) * 2^-24, v = v + noise*((u1 + u2) - 1): triangular on (-1, 1)
+ *   times `noise`, variance noise^2 / 6;
+ *   out = min(max(v, 0), 255).
+ * The record (1,0,0, 0,1,0, 1,0, fill, 0) returns in_dev bit for bit; an integer translation returns shifted input and `fill`.
+ * n_images <= 65535; n_images == 0 is a no-op.  The call only enqueues work. */
+typedef struct aocr_warp {
+  float m00, m01, m02;   /* source x = m00*x + m01*y + m02  (x, y: 0-based output pixel indices) */
+  float m10, m11, m12;   /* source y = m10*x + m11*y + m12 */
+  float gain, offset;    /* v = gain*s + offset (contrast g about mid-gray: offset = 128*(1-g) + brightness, folded on the host) */
+  float fill;            /* value of the source outside the image, 0..255 */
+  float noise;           /* amplitude of the additive triangular noise, 0 = none */
+} aocr_warp;
+int aocr_augment_lines(void* stream, const float* in_dev, const aocr_warp* warp_dev, int32_t n_images, int32_t H, int32_t W,
+                       uint64_t seed, uint64_t counter, float* out_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -84,6 +84,8 @@ int aocr_beam_select_dict(void* stream, const float* logp_dev, const int32_t* pr
 int aocr_edit_distance(void* stream, const int32_t* labels_dev, const int32_t* targets_dev, int32_t B, int32_t L, int32_t* dist_dev, int32_t* target_len_dev);
 typedef struct aocr_image_desc { int64_t offset; int32_t height, width, channels, reserved; } aocr_image_desc;
 int aocr_preprocess_lines(void* stream, const uint8_t* src_dev, const aocr_image_desc* desc_dev, int32_t n_images, int32_t out_h, int32_t out_w, float* out_dev);
+typedef struct aocr_warp { float m00, m01, m02; float m10, m11, m12; float gain, offset; float fill; float noise; } aocr_warp;
+int aocr_augment_lines(void* stream, const float* in_dev, const aocr_warp* warp_dev, int32_t n_images, int32_t H, int32_t W, uint64_t seed, uint64_t counter, float* out_dev);
 ]]
 
 local M = {}

@@ -41,10 +41,13 @@ function DataGen:__init(data_base_dir, data_path, max_aspect_ratio, max_encoder_
 end
 
 function DataGen:shuffle() shuffle(self.lines) end
+-- optional training augmentation (lua/augment.lua: Augmenter{...}), nil for evaluation data; batch k is drawn under counter k
+-- (augment_counter is a plain field: a resumed run sets it)
+function DataGen:setAugment(augment) self.augment, self.augment_counter = augment, 0 end
 function DataGen:size() return #self.lines end
 
 -- the images of one width bucket: decoded bytes back to back -> device -> (n,1,32,imgW) float 0..255, one launch
-local function preprocess(items, imgW)
+local function preprocess(items, imgW, augment, counter)
     local n, total = #items, 0
     for _, it in ipairs(items) do total = total + it.h * it.w * it.c end
     local src = ffi.new('uint8_t[?]', total)
@@ -58,13 +61,21 @@ local function preprocess(items, imgW)
     local src_dev, desc_dev, out_dev = A.device_bytes(total), A.device_bytes(n * ffi.sizeof('aocr_image_desc')), A.device_bytes(n * 32 * imgW * 4)
     A.upload(src_dev, src, total); A.upload(desc_dev, desc, n * ffi.sizeof('aocr_image_desc'))
     A.check(A.lib.aocr_preprocess_lines(nil, src_dev:as('uint8_t*'), desc_dev:as('aocr_image_desc*'), n, 32, imgW, out_dev:as('float*')), 'aocr_preprocess_lines')
+    if augment then                                                        -- warp / contrast / noise where the batch already is
+        local warp, warp_bytes = augment:params(n, 32, imgW, counter), n * ffi.sizeof('aocr_warp')
+        local warp_dev, aug_dev = A.device_bytes(warp_bytes), A.device_bytes(n * 32 * imgW * 4)
+        A.upload(warp_dev, warp, warp_bytes)
+        A.check(A.lib.aocr_augment_lines(nil, out_dev:as('float*'), warp_dev:as('aocr_warp*'), n, 32, imgW, augment.seed, counter, aug_dev:as('float*')), 'aocr_augment_lines')
+        out_dev, aug_dev = aug_dev, out_dev
+        warp_dev:free(); aug_dev:free()                                    -- hipFree waits for the kernel that still reads them
+    end
     local images = torch.FloatTensor(n, 1, 32, imgW)
     A.download(images, out_dev, n * 32 * imgW * 4)
     src_dev:free(); desc_dev:free(); out_dev:free()
     return images
 end
 
-local function emit(bucket, imgW)
+local function emit(self, bucket, imgW)
     local n = #bucket
     local max_target_length = -math.huge
     for i = 1, n do max_target_length = math.max(max_target_length, #bucket[i].label_list) end
@@ -77,7 +88,9 @@ local function emit(bucket, imgW)
         for j = 1, #ll - 1 do targets[i][j] = ll[j]; targets_eval[i][j] = ll[j + 1] end
         img_paths[i] = bucket[i].path
     end
-    return {preprocess(bucket, imgW), targets, targets_eval, num_nonzeros, img_paths}
+    local images = preprocess(bucket, imgW, self.augment, self.augment_counter)
+    if self.augment then self.augment_counter = self.augment_counter + 1 end
+    return {images, targets, targets_eval, num_nonzeros, img_paths}
 end
 
 function DataGen:nextBatch(batch_size)
@@ -96,7 +109,7 @@ function DataGen:nextBatch(batch_size)
             if self.buffer[imgW] == nil then self.buffer[imgW] = {} end
             table.insert(self.buffer[imgW], {bytes = hwc, h = h, w = w, c = c, label_list = label_list, path = img_path})
             if #self.buffer[imgW] == batch_size then
-                local out = emit(self.buffer[imgW], imgW)
+                local out = emit(self, self.buffer[imgW], imgW)
                 self.buffer[imgW] = nil
                 return out
             end
@@ -107,7 +120,7 @@ function DataGen:nextBatch(batch_size)
     -- end of the list: flush the buckets one by one (data_gen.lua:123-153)
     for imgW, bucket in pairs(self.buffer) do
         if #bucket > 0 then
-            local out = emit(bucket, imgW)
+            local out = emit(self, bucket, imgW)
             self.buffer[imgW] = nil
             return out
         end

@@ -14,7 +14,9 @@ Differences from the reference, all deliberate:
     ``force_width=None`` applies the aspect-ratio rule of lines 72-77;
   * ``shuffle`` uses numpy's generator instead of Lua's ``math.random`` (not reproducible across the two anyway);
   * the reference caches the scaled image per line after its first visit; here the decoded uint8 image is cached on the host
-    and scaled on the device when its batch is emitted (the scaled tensor goes straight into HBM).
+    and scaled on the device when its batch is emitted (the scaled tensor goes straight into HBM);
+  * ``augment=Augmenter(...)`` (aocr/augment.py; the reference has none) warps / jitters every emitted batch on the device, batch ``k`` under
+    counter ``augment_counter = k``; with ``augment=None`` nothing changes.
 """
 from __future__ import annotations
 
@@ -119,8 +121,10 @@ def preprocess_batch(images_u8, out_w, device=None, stream=None):
 
 
 class DataGen:
-    def __init__(self, data_base_dir, data_path, max_aspect_ratio, force_width=100, loader=None, device=None):
+    def __init__(self, data_base_dir, data_path, max_aspect_ratio, force_width=100, loader=None, device=None, augment=None):
         self.imgH = IMG_H
+        self.augment = augment                   # an aocr.Augmenter (training data) or None (evaluation data: the images as they are)
+        self.augment_counter = 0                 # batch counter of the augmenter: +1 per emitted batch; a resumed run sets it
         self.data_base_dir = data_base_dir
         self.data_path = data_path
         self.max_aspect_ratio = max_aspect_ratio
@@ -160,6 +164,9 @@ class DataGen:
     def _emit(self, img_w):
         items = self.buffer.pop(img_w)
         images = preprocess_batch([it[0] for it in items], img_w, self.device)
+        if self.augment is not None:
+            images = self.augment.apply(images, self.augment_counter)
+            self.augment_counter += 1
         max_len = max(len(it[1]) for it in items)
         targets = np.ones((len(items), max_len - 1), np.int32)
         targets_eval = np.ones((len(items), max_len - 1), np.int32)

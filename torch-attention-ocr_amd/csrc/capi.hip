@@ -729,4 +729,14 @@ int aocr_preprocess_lines(void* stream, const uint8_t* src_dev, const aocr_image
   return check_launch("aocr_preprocess_lines");
 }
 
+int aocr_augment_lines(void* stream, const float* in_dev, const aocr_warp* warp_dev, int32_t n_images, int32_t H, int32_t W, uint64_t seed,
+                       uint64_t counter, float* out_dev) {
+  REQUIRE(in_dev && warp_dev && out_dev, "NULL argument");
+  REQUIRE(in_dev != out_dev, "in_dev and out_dev must not alias");
+  REQUIRE(n_images >= 0 && H >= 1 && W >= 1 && (int64_t)H * W <= INT32_MAX, "bad sizes: n_images=%d H=%d W=%d", n_images, H, W);
+  REQUIRE(n_images <= 65535, "n_images=%d: at most 65535 images per call", n_images);
+  augment_lines((hipStream_t)stream, in_dev, warp_dev, n_images, H, W, seed, counter, out_dev);
+  return check_launch("aocr_augment_lines");
+}
+
 }  // extern "C"

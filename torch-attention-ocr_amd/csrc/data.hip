@@ -62,7 +62,48 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
   out[((int64_t)img * out_h + y) * out_w + x] = scale_elem(tmp, d.height, out_h, y);
 }
 
+// Training augmentation behind preprocess_kernel (include/aocr.h: aocr_augment_lines): an affine warp with bilinear taps, gain / offset,
+// additive triangular noise, clamp to 0..255.  One thread per output pixel, four gathers and one store; every float operation is one
+// rounded single-precision op in the order of tests/augment_ref.py.  The noise is counter-based like the dropout masks (epilogues.h).
+__global__ __launch_bounds__(256) void augment_kernel(const float* __restrict__ in, const aocr_warp* __restrict__ warp, int H, int W,
+                                                      unsigned long long base, float* __restrict__ out) {
+  const int img = blockIdx.y;
+  const int id = blockIdx.x * 256 + threadIdx.x;
+  if (id >= H * W) return;
+  const int y = id / W, x = id - y * W;
+  const aocr_warp w = warp[img];
+  const float xf = (float)x, yf = (float)y;
+  float sx = __fadd_rn(__fadd_rn(__fmul_rn(w.m00, xf), __fmul_rn(w.m01, yf)), w.m02);
+  float sy = __fadd_rn(__fadd_rn(__fmul_rn(w.m10, xf), __fmul_rn(w.m11, yf)), w.m12);
+  sx = fminf(fmaxf(sx, -1.0f), (float)W);                  // keeps the int conversion defined; NaN -> -1 (all taps outside)
+  sy = fminf(fmaxf(sy, -1.0f), (float)H);
+  const float x0f = floorf(sx), y0f = floorf(sy);
+  const float fx = __fsub_rn(sx, x0f), fy = __fsub_rn(sy, y0f);
+  const int x0 = (int)x0f, y0 = (int)y0f;
+  const float* src = in + (int64_t)img * H * W;
+  auto tap = [&](int row, int col) { return (row >= 0 && row < H && col >= 0 && col < W) ? src[(int64_t)row * W + col] : w.fill; };
+  const float a = tap(y0, x0), b = tap(y0, x0 + 1), c = tap(y0 + 1, x0), d = tap(y0 + 1, x0 + 1);
+  const float gx = __fsub_rn(1.0f, fx), gy = __fsub_rn(1.0f, fy);
+  const float top = __fadd_rn(__fmul_rn(gx, a), __fmul_rn(fx, b));
+  const float bot = __fadd_rn(__fmul_rn(gx, c), __fmul_rn(fx, d));
+  const float s = __fadd_rn(__fmul_rn(gy, top), __fmul_rn(fy, bot));
+  float v = __fadd_rn(__fmul_rn(w.gain, s), w.offset);
+  const int64_t idx = ((int64_t)img * H + y) * W + x;
+  const unsigned long long r = splitmix64_(base + (unsigned long long)idx);
+  const float k24 = 1.0f / 16777216.0f;
+  const float u1 = __fmul_rn((float)(uint32_t)(r >> 40), k24), u2 = __fmul_rn((float)(uint32_t)((r >> 16) & 0xFFFFFFull), k24);
+  v = __fadd_rn(v, __fmul_rn(w.noise, __fsub_rn(__fadd_rn(u1, u2), 1.0f)));
+  out[idx] = fminf(fmaxf(v, 0.0f), 255.0f);
+}
+
 }  // namespace
+
+void augment_lines(hipStream_t s, const float* in, const aocr_warp* warp, int n_images, int H, int W, uint64_t seed, uint64_t counter,
+                   float* out) {
+  if (n_images <= 0) return;
+  const unsigned long long base = splitmix64_(seed ^ (counter * 0xD1342543DE82EF95ull));
+  hipLaunchKernelGGL(augment_kernel, dim3(cdiv((int64_t)H * W, 256), n_images), dim3(256), 0, s, in, warp, H, W, base, out);
+}
 
 void preprocess_lines(hipStream_t s, const uint8_t* src, const aocr_image_desc* desc, int n_images, int out_h, int out_w, float* out) {
   if (n_images <= 0) return;

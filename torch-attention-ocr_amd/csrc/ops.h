@@ -343,4 +343,7 @@ void enc_seq_backward(hipStream_t s, const EncSeqBwdArgs& a);
 void enc_seq_forward(hipStream_t s, const EncSeqFwdArgs& a);
 // data path (data.hip): 255*rgb2y + image.scale to (out_h, out_w) for n images sharing out_w
 void preprocess_lines(hipStream_t s, const uint8_t* src, const aocr_image_desc* desc, int n_images, int out_h, int out_w, float* out);
+// training augmentation (data.hip): affine warp + gain / offset + counter-based noise of n (1,H,W) images, in != out
+void augment_lines(hipStream_t s, const float* in, const aocr_warp* warp, int n_images, int H, int W, uint64_t seed, uint64_t counter,
+                   float* out);
 }  // namespace aocr
