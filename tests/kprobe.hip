@@ -1,5 +1,5 @@
-// tests/libkprobe.so: extern "C" wrappers around the host launchers of the bf16-source conv / GEMM paths (csrc/ops.h), for
-// tests/test_kernels_bf16_gpu.py.  Test infrastructure: no kernels of its own, not part of the product's C ABI (include/aocr.h).
+// tests/libkprobe.so: extern "C" wrappers around the host launchers of the bf16-source conv / GEMM paths and of the fused recurrent-step
+// kernels (csrc/ops.h), for tests/test_kernels_bf16_gpu.py and tests/test_step_kernels_bf16_gpu.py.  Test infrastructure: no kernels of its own, not part of the product's C ABI (include/aocr.h).
 // Every wrapper enqueues on the given stream and returns hipGetLastError().  Pointers to bf16 data are passed as the raw addresses
 // of torch.bfloat16 tensors (the same bit layout as bf16_t).
 #include "ops.h"
@@ -83,6 +83,107 @@ size_t kp_bn_scratch_bytes(int C) { return aocr::bn_scratch_bytes(C); }
 
 int kp_bn_eval_prepare(hipStream_t s, const float* rm, const float* rv, float* save, int C) {
   aocr::bn_eval_prepare(s, rm, rv, save, C);
+  return (int)hipGetLastError();
+}
+
+// ---- the fused recurrent-step launchers.  One flat struct per problem (tests/test_step_kernels_bf16_gpu.py mirrors them as ctypes.Structure); a null pointer
+// means "absent".  An operand is one K segment (p1 == null, K = K0) or two ([p0 | p1], K = K0 + K1) with a row stride each; the A side of an _hh wrapper is the
+// bf16 shadow, of an _h wrapper the fp32 buffer (B is always a bf16 weight shadow).
+struct KpOperand { const void* p0; int64_t ld0; int K0; const void* p1; int64_t ld1; int K1; int rows; };
+struct KpDrop { unsigned long long base, thr; float scale; long long off; };
+struct KpStore {
+  KpOperand a, b;
+  float* C; int64_t ldc; const float* bias; const float* bias2; int flags;
+  float* C1; int64_t ldc1; int N0;
+  void* Cb; int64_t ldcb;
+  const float* dg; const float* dout; int64_t ldd;
+};
+struct KpGatesFwd {
+  KpOperand a, b;
+  const float* zx; int64_t ldzx; const float* b1; const float* b2;
+  const float* c_prev; int64_t ldcp; float* c_out; int64_t ldc; float* h_out; int64_t ldh; float* h_out2; int64_t ldh2;
+  float* gates; int64_t ldg; void* hb; int64_t ldhb; void* hb2; int64_t ldhb2;
+  const int32_t* zx_tok; int64_t zx_tok_stride; KpDrop drop;
+};
+struct KpGatesBwd {
+  KpOperand a, b;
+  const float* dh1; int64_t ld1; const float* dh2; int64_t ld2; const float* dh3; int64_t ld3; const float* dc_in; int64_t lddc;
+  const float* gates; int64_t ldg; const float* c_prev; int64_t ldcp; const float* c; int64_t ldcc;
+  float* dz; int64_t lddz; float* dc_out; int64_t lddco; void* dzb; int64_t lddzb; KpDrop drop; int gil;
+};
+
+}  // extern "C"
+
+namespace {
+using namespace aocr;
+LoadKh2 kh(const KpOperand& o) {
+  return o.p1 ? make_loadkh2(H16(o.p0), o.ld0, o.K0, H16(o.p1), o.ld1, o.K1, o.rows) : make_loadkh(H16(o.p0), o.ld0, o.rows, o.K0);
+}
+LoadK kf(const KpOperand& o) {
+  return o.p1 ? make_loadk2((const float*)o.p0, o.ld0, o.K0, (const float*)o.p1, o.ld1, o.K1, o.rows) : make_loadk((const float*)o.p0, o.ld0, o.rows, o.K0);
+}
+void load_a(LoadKh2& l, const KpOperand& o) { l = kh(o); }
+void load_a(LoadK& l, const KpOperand& o) { l = kf(o); }
+DropSpec drop_of(const KpDrop& d) { DropSpec s; s.base = d.base; s.thr = d.thr; s.scale = d.scale; s.off = d.off; return s; }
+EpStore ep_of(const KpStore& p, int M, int N) {
+  EpStore e = make_store(p.C, p.ldc, M, N, p.bias, p.bias2, p.flags);
+  if (p.C1) { e.C1 = p.C1; e.ldc1 = p.ldc1; e.N0 = p.N0; }
+  e.Cb = W16(p.Cb); e.ldcb = p.ldcb; e.dg = p.dg; e.dout = p.dout; e.ldd = p.ldd;
+  return e;
+}
+EpGatesFwd ep_of(const KpGatesFwd& p, int M, int H) {
+  EpGatesFwd e;
+  e.zx = p.zx; e.ldzx = p.ldzx; e.b1 = p.b1; e.b2 = p.b2; e.c_prev = p.c_prev; e.ldcp = p.ldcp; e.c_out = p.c_out; e.ldc = p.ldc;
+  e.h_out = p.h_out; e.ldh = p.ldh; e.h_out2 = p.h_out2; e.ldh2 = p.ldh2; e.gates = p.gates; e.ldg = p.ldg; e.M = M; e.H = H;
+  e.hb = W16(p.hb); e.ldhb = p.ldhb; e.hb2 = W16(p.hb2); e.ldhb2 = p.ldhb2; e.zx_tok = p.zx_tok; e.zx_tok_stride = p.zx_tok_stride;
+  e.drop = drop_of(p.drop);
+  return e;
+}
+EpGatesBwd ep_of(const KpGatesBwd& p, int M, int H) {
+  EpGatesBwd e;
+  e.dh1 = p.dh1; e.ld1 = p.ld1; e.dh2 = p.dh2; e.ld2 = p.ld2; e.dh3 = p.dh3; e.ld3 = p.ld3; e.dc_in = p.dc_in; e.lddc = p.lddc;
+  e.gates = p.gates; e.ldg = p.ldg; e.c_prev = p.c_prev; e.ldcp = p.ldcp; e.c = p.c; e.ldcc = p.ldcc; e.dz = p.dz; e.lddz = p.lddz;
+  e.dc_out = p.dc_out; e.lddco = p.lddco; e.M = M; e.H = H; e.dzb = W16(p.dzb); e.lddzb = p.lddzb; e.drop = drop_of(p.drop); e.gil = p.gil != 0;
+  return e;
+}
+// nz = 1..3 problems -> the launcher's argument sets (SmallArgs<A loader, LoadKh2, epilogue>)
+template <class ARGS, class P> int fill(ARGS (&z)[3], int nz, const P* p, int M, int cols) {
+  if (nz < 1 || nz > 3) return (int)hipErrorInvalidValue;
+  for (int i = 0; i < nz; ++i) { load_a(z[i].a, p[i].a); z[i].b = kh(p[i].b); z[i].ep = ep_of(p[i], M, cols); z[i].K = z[i].a.K; }
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+#define KP_SMALL(name, ARGS, P, launcher)                                        \
+  int name(hipStream_t s, int nz, const P* p, int M, int cols) {                 \
+    aocr::ARGS z[3];                                                             \
+    if (int rc = fill(z, nz, p, M, cols)) return rc;                             \
+    aocr::launcher(s, nz, z, M, cols);                                           \
+    return (int)hipGetLastError();                                               \
+  }
+KP_SMALL(kp_small_gates_fwd_hh, GatesFwdArgsHH, KpGatesFwd, launch_small_gates_fwd_hh)
+KP_SMALL(kp_small_gates_fwd_h, GatesFwdArgsH, KpGatesFwd, launch_small_gates_fwd_h)
+KP_SMALL(kp_small_hh, SmallArgsHH, KpStore, launch_small_hh)
+KP_SMALL(kp_small_h, SmallArgsH, KpStore, launch_small_h)
+KP_SMALL(kp_small_gates_bwd_hh, GatesBwdArgsHH, KpGatesBwd, launch_small_gates_bwd_hh)
+KP_SMALL(kp_small_gates_bwd_h, GatesBwdArgsH, KpGatesBwd, launch_small_gates_bwd_h)
+#undef KP_SMALL
+
+// the cell backward without a product (the operands of *p are ignored)
+int kp_gates_elem_bwd(hipStream_t s, const KpGatesBwd* p, int M, int H) {
+  aocr::gates_elem_bwd(s, ep_of(*p, M, H), M, H);
+  return (int)hipGetLastError();
+}
+
+// *taken = 1 when the 128 x 128 tiled form ran (0: the shape is not taken and nothing was launched)
+int kp_big_step_store(hipStream_t s, const KpStore* p, int M, int N, int* taken) {
+  *taken = aocr::big_step_store(s, kh(p->a), kh(p->b), ep_of(*p, M, N), M, N) ? 1 : 0;
+  return (int)hipGetLastError();
+}
+int kp_big_step_gates_fwd(hipStream_t s, const KpGatesFwd* p, int M, int H, float* zbuf, size_t zbuf_floats, int* taken) {
+  *taken = aocr::big_step_gates_fwd(s, kh(p->a), kh(p->b), ep_of(*p, M, H), M, H, zbuf, zbuf_floats) ? 1 : 0;
   return (int)hipGetLastError();
 }
 

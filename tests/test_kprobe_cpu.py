@@ -37,11 +37,15 @@ def test_kprobe_symbols_resolve_in_libaocr(tmp_path):
     wanted = {s for s in undef if s.startswith("_ZN4aocr")}
     # every launcher the shim wraps is reached through a mangled aocr:: reference
     for name in ("conv_forward", "conv_backward_data", "conv_backward_filter", "conv_weight_shadows", "splitk_reduce", "gemm_hh",
-                 "gemm_hh_shadow", "gemm_hh_cat", "grouped_wgrad", "bn_relu_forward"):
+                 "gemm_hh_shadow", "gemm_hh_cat", "grouped_wgrad", "bn_relu_forward",
+                 "launch_small_gates_fwd_hh", "launch_small_gates_fwd_h", "launch_small_hh", "launch_small_h", "launch_small_gates_bwd_hh",
+                 "launch_small_gates_bwd_h", "gates_elem_bwd", "big_step_store", "big_step_gates_fwd"):
         assert any(f"{len(name)}{name}E" in s for s in wanted), f"the shim does not call aocr::{name}"
     defined = _symbols(LIB, "--defined-only")
     missing = sorted(wanted - defined)
     assert not missing, f"aocr:: symbols the shim needs but libaocr.so does not define (ops.h signature drift?): {missing}"
     exported = _symbols(so, "--defined-only")
-    for name in ("kp_conv_forward", "kp_conv_backward_data", "kp_conv_backward_filter", "kp_grouped_wgrad", "kp_gemm_hh_cat"):
+    for name in ("kp_conv_forward", "kp_conv_backward_data", "kp_conv_backward_filter", "kp_grouped_wgrad", "kp_gemm_hh_cat",
+                 "kp_small_gates_fwd_hh", "kp_small_gates_fwd_h", "kp_small_hh", "kp_small_h", "kp_small_gates_bwd_hh", "kp_small_gates_bwd_h",
+                 "kp_gates_elem_bwd", "kp_big_step_store", "kp_big_step_gates_fwd"):
         assert name in exported

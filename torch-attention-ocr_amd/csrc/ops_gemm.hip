@@ -19,6 +19,13 @@ struct TraceScope { explicit TraceScope(const char* fn) { t_trace_fn = fn; } ~Tr
 static void trace_launch(const char* kernel, const char* inst, long long M, long long N, long long K) {
   if (t_trace_fn && getenv("AOCR_TRACE")) fprintf(stderr, "[aocr] %s: %s[%s] %lld %lld %lld\n", t_trace_fn, kernel, inst, M, N, K);
 }
+// the recurrent-step launchers' line: the instantiation names the template arguments that differ between their branches -- NT, the GATES kind (0 plain, 1 gate
+// tiles, 2 half gate tiles), waves and, for two row tiles per workgroup, "mt2": gemm_step_kernel[2,2,w8], gemm_step_kernel[4,1,w4,mt2]
+static void trace_step(int nt, int gates, int waves, int mt, long long M, long long N, long long K) {
+  if (!t_trace_fn || !getenv("AOCR_TRACE")) return;
+  char inst[32]; snprintf(inst, sizeof inst, "%d,%d,w%d%s", nt, gates, waves, mt == 2 ? ",mt2" : "");
+  trace_launch("gemm_step_kernel", inst, M, N, K);
+}
 // LDS-tiled bf16 kernel (any loader pair, fp32 or bf16 sources)
 template <class AL, class BL, class EP>
 static void launch_lds(hipStream_t s, const AL& a, const BL& b, const EP& ep, int M, int N, int K, int ksplit) {
@@ -219,8 +226,8 @@ static bool quarter_gate_tiles(int H, int M, int nz) {
   static const bool off = getenv("AOCR_NO_QUARTER_TILES") != nullptr;
   return !off && H % 8 == 0 && (H / 32) * cdiv(M, 32) * nz < 128;
 }
-static bool step_waves16() { static const bool on = getenv("AOCR_STEP_WAVES16") != nullptr; return on; }
-static bool step_waves8() { static const bool on = getenv("AOCR_STEP_WAVES4") == nullptr; return on; }
+static bool step_waves16() { return getenv("AOCR_STEP_WAVES16") != nullptr; }      // (read per call, like every dispatch switch: tests reach all three wave counts in one process)
+static bool step_waves8() { return getenv("AOCR_STEP_WAVES4") == nullptr; }
 template <int NT, bool GATES, class ARGS>
 static void launch_small(hipStream_t s, bool bf16, int nz, const ARGS* z, int M, int ncols, int gate_stride) {
   if (M <= 0 || ncols <= 0) return;
@@ -292,6 +299,8 @@ static bool half_gate_tiles(int H, int M, int nz) {
 template <int NT, bool GATES, class ARGS>
 static void launch_small_bf16(hipStream_t s, int nz, const ARGS* z, int M, int ncols, int gate_stride) {
   if (M <= 0 || ncols <= 0) return;
+  const TraceScope ts("launch_small_bf16");
+  const bool w8 = step_waves8(), w16 = w8 && step_waves16();
   dim3 grid(GATES ? cdiv(ncols, 32) : cdiv(ncols, 32 * NT), cdiv(M, 32), nz);
   SmallArgs2<decltype(z[0].a), decltype(z[0].b), decltype(z[0].ep)> zz; zz.z[0] = z[0]; zz.z[1] = z[nz > 1 ? 1 : 0]; zz.z[2] = z[nz > 2 ? 2 : 0];
   bool staged = ncols % 32 == 0;                              // wave-private-LDS kernel: full-line loads, needs 64-aligned K
@@ -301,7 +310,8 @@ static void launch_small_bf16(hipStream_t s, int nz, const ARGS* z, int M, int n
   if (staged) {
     if constexpr (GATES && NT == 4) {
       if (half_gate_tiles(ncols, M, nz)) {
-        if (step_waves8())
+        trace_step(2, 2, w8 ? 8 : 4, 1, M, ncols, z[0].K);
+        if (w8)
           hipLaunchKernelGGL((gemm_step_kernel<2, 2, decltype(z[0].a), decltype(z[0].ep), 8>), dim3(ncols / 16, cdiv(M, 32), nz), dim3(512), 0, s, zz, gate_stride);
         else
           hipLaunchKernelGGL((gemm_step_kernel<2, 2, decltype(z[0].a), decltype(z[0].ep)>), dim3(ncols / 16, cdiv(M, 32), nz), dim3(256), 0, s, zz, gate_stride);
@@ -309,20 +319,24 @@ static void launch_small_bf16(hipStream_t s, int nz, const ARGS* z, int M, int n
       }
     }
     if constexpr (NT == 1) {
-      if (step_waves8() && step_waves16() && z[0].K >= 1024) {                    // 147 KB of LDS; 64 k per wave at K = 1024
+      if (w16 && z[0].K >= 1024) {                    // 147 KB of LDS; 64 k per wave at K = 1024
+        trace_step(NT, GATES ? 1 : 0, 16, 1, M, ncols, z[0].K);
         hipLaunchKernelGGL((gemm_step_kernel<NT, GATES ? 1 : 0, decltype(z[0].a), decltype(z[0].ep), 16>), grid, dim3(1024), 0, s, zz, gate_stride);
         return;
       }
     }
     if constexpr (NT <= 2) {
-      if (step_waves8()) {
+      if (w8) {
+        trace_step(NT, GATES ? 1 : 0, 8, 1, M, ncols, z[0].K);
         hipLaunchKernelGGL((gemm_step_kernel<NT, GATES ? 1 : 0, decltype(z[0].a), decltype(z[0].ep), 8>), grid, dim3(512), 0, s, zz, gate_stride);
         return;
       }
     }
+    trace_step(NT, GATES ? 1 : 0, 4, 1, M, ncols, z[0].K);
     hipLaunchKernelGGL((gemm_step_kernel<NT, GATES ? 1 : 0, decltype(z[0].a), decltype(z[0].ep)>), grid, dim3(256), 0, s, zz, gate_stride);
     return;
   }
+  trace_launch("gemm_small_kernel", NT == 4 ? (GATES ? "bf16,4,gates" : "bf16,4,plain") : (GATES ? "bf16,1,gates" : "bf16,1,plain"), M, ncols, z[0].K);
   hipLaunchKernelGGL((gemm_small_kernel<true, NT, GATES, decltype(z[0].a), decltype(z[0].b), decltype(z[0].ep)>), grid, dim3(256), 0, s,
                      zz, gate_stride);
 }
@@ -349,17 +363,21 @@ static bool stepl_eligible(const ARGS* z, int nz, int M) {
 template <int NT, bool GATES, class ARGS>
 static void launch_small_bf16_hh(hipStream_t s, int nz, const ARGS* z, int M, int ncols, int gate_stride) {
   if (M <= 0 || ncols <= 0) return;
+  const TraceScope ts("launch_small_bf16_hh");
+  const bool w8 = step_waves8(), w16 = w8 && step_waves16();
   dim3 grid(GATES ? cdiv(ncols, 32) : cdiv(ncols, 32 * NT), cdiv(M, 32), nz);
   SmallArgs2<decltype(z[0].a), decltype(z[0].b), decltype(z[0].ep)> zz; zz.z[0] = z[0]; zz.z[1] = z[nz > 1 ? 1 : 0]; zz.z[2] = z[nz > 2 ? 2 : 0];
   if constexpr (GATES && NT == 4) {
     // large batch (round 6; the reference-default decoder: 400 rows x Hd = 1024): 64 x 128 gate tiles on the LDS-DMA ring, eight waves, four-unit epilogue (stepl.h)
     if (stepl_eligible(z, nz, M) && (stepl_min_wgs() >= 0 ? (ncols / 32) * cdiv(M, 64) * nz >= stepl_min_wgs() : (ncols / 16) * cdiv(M, 32) * nz > 256)) {
       const int gx = ncols / 32, gy = cdiv(M, 64);
+      trace_launch("gemm_stepl_kernel", "gates", M, ncols, z[0].K);
       hipLaunchKernelGGL((gemm_stepl_kernel<2, 4, 1, decltype(z[0].ep), 6, 2, 8, true>), dim3(gx * gy * nz), dim3(512), 0, s, zz, gate_stride, gx, gy);
       return;
     }
     if (half_gate_tiles(ncols, M, nz)) {
-      if (step_waves8())
+      trace_step(2, 2, w8 ? 8 : 4, 1, M, ncols, z[0].K);
+      if (w8)
         hipLaunchKernelGGL((gemm_step_kernel<2, 2, decltype(z[0].a), decltype(z[0].ep), 8>), dim3(ncols / 16, cdiv(M, 32), nz), dim3(512), 0, s, zz, gate_stride);
       else
         hipLaunchKernelGGL((gemm_step_kernel<2, 2, decltype(z[0].a), decltype(z[0].ep)>), dim3(ncols / 16, cdiv(M, 32), nz), dim3(256), 0, s, zz, gate_stride);
@@ -369,6 +387,7 @@ static void launch_small_bf16_hh(hipStream_t s, int nz, const ARGS* z, int M, in
     // the weight tile is streamed by half as many row blocks and every weight fragment feeds two MFMAs.  AOCR_NO_STEP_MT2=1: off
     { const char* e = getenv("AOCR_NO_STEP_MT2");
       if (!(e && e[0] == '1') && cdiv(ncols, 32) * cdiv(M, 64) * nz >= 200) {
+        trace_step(NT, 1, 4, 2, M, ncols, z[0].K);
         hipLaunchKernelGGL((gemm_step_kernel<NT, 1, decltype(z[0].a), decltype(z[0].ep), 4, 2>), dim3(cdiv(ncols, 32), cdiv(M, 64), nz), dim3(256), 0, s, zz, gate_stride);
         return;
       } }
@@ -378,6 +397,7 @@ static void launch_small_bf16_hh(hipStream_t s, int nz, const ARGS* z, int M, in
     const int lw = ncols % 128 == 0 ? (ncols / 128) * cdiv(M, 64) * nz : 0;          // its workgroups
     if (lw > 0 && stepl_eligible(z, nz, M) && (stepl_min_wgs() >= 0 ? lw >= stepl_min_wgs() : lw >= 160 && (nz == 3 || (nz == 1 && z[0].K >= 4096)))) {
       const int gx = ncols / 128, gy = cdiv(M, 64);
+      trace_launch("gemm_stepl_kernel", "plain", M, ncols, z[0].K);
       hipLaunchKernelGGL((gemm_stepl_kernel<2, 4, 0, decltype(z[0].ep), 6, 2, 8, true>), dim3(gx * gy * nz), dim3(512), 0, s, zz, gate_stride, gx, gy);
       return;
     }
@@ -388,7 +408,8 @@ static void launch_small_bf16_hh(hipStream_t s, int nz, const ARGS* z, int M, in
     // split and summation order as the one-tile form: bit-identical.  AOCR_NO_STEP_MT2=1: off
     { const char* e = getenv("AOCR_NO_STEP_MT2");
       const char* const mk = getenv("AOCR_STEP_MT2_MINK");        // the K from which the two-tile form is taken (A/B on the reference-default step: decoder 3.31 ms at 4096, 3.26 at 2048, 3.31 at 1024)
-      if (!(e && e[0] == '1') && nz == 1 && z[0].K >= (mk ? atoi(mk) : 2048) && M >= 320 && cdiv(ncols, 32) * cdiv(M, 64) >= 200 && step_waves8()) {
+      if (!(e && e[0] == '1') && nz == 1 && z[0].K >= (mk ? atoi(mk) : 2048) && M >= 320 && cdiv(ncols, 32) * cdiv(M, 64) >= 200 && w8) {
+        trace_step(1, 0, 8, 2, M, ncols, z[0].K);
         hipLaunchKernelGGL((gemm_step_kernel<1, 0, decltype(z[0].a), decltype(z[0].ep), 8, 2>), dim3(cdiv(ncols, 32), cdiv(M, 64), nz), dim3(512), 0, s, zz, gate_stride);
         return;
       } }
@@ -396,17 +417,20 @@ static void launch_small_bf16_hh(hipStream_t s, int nz, const ARGS* z, int M, in
   // (measured and dropped: 64 x 64 tiles -- NT = 2, MT = 2, eight waves -- for the plain step products of the backward pass at M = 400: 336 workgroups instead of
   //  1248, 350 MB instead of 640 MB per launch, decoder backward 2.27 -> 2.34 ms: there the many small workgroups are what hides the latency)
   if constexpr (NT == 1) {
-    if (step_waves8() && step_waves16() && z[0].K >= 1024) {
+    if (w16 && z[0].K >= 1024) {
+      trace_step(NT, GATES ? 1 : 0, 16, 1, M, ncols, z[0].K);
       hipLaunchKernelGGL((gemm_step_kernel<NT, GATES ? 1 : 0, decltype(z[0].a), decltype(z[0].ep), 16>), grid, dim3(1024), 0, s, zz, gate_stride);
       return;
     }
   }
   if constexpr (NT <= 2) {
-    if (step_waves8()) {
+    if (w8) {
+      trace_step(NT, GATES ? 1 : 0, 8, 1, M, ncols, z[0].K);
       hipLaunchKernelGGL((gemm_step_kernel<NT, GATES ? 1 : 0, decltype(z[0].a), decltype(z[0].ep), 8>), grid, dim3(512), 0, s, zz, gate_stride);
       return;
     }
   }
+  trace_step(NT, GATES ? 1 : 0, 4, 1, M, ncols, z[0].K);
   hipLaunchKernelGGL((gemm_step_kernel<NT, GATES ? 1 : 0, decltype(z[0].a), decltype(z[0].ep)>), grid, dim3(256), 0, s, zz, gate_stride);
 }
 // ---- recurrent-step products at LARGE batch (round 5; the reference's default shape: 400 rows, Hd = 1024).  The step kernels above are built for latency at 32-256
@@ -426,10 +450,14 @@ bool big_step_eligible(int M, int N, int K) {
   // N = 1024 products 19-25 us against 17 -- decoder 5.06 -> 5.82 ms per step of the reference-default workload.  Both forms are bound by what one compute unit pulls from L2.
   return env_is_1("AOCR_BIG_STEP") && M >= min_rows && N >= 1024 && dma128_eligible(M, N, K, 32);
 }
-bool big_step_store(hipStream_t s, const LoadKh2& a, const LoadKh2& b, const EpStore& ep, int M, int N) {
+static bool big_step_store_(hipStream_t s, const LoadKh2& a, const LoadKh2& b, const EpStore& ep, int M, int N) {       // (the caller holds the TraceScope)
   if (!big_step_eligible(M, N, a.K) || (a.p1 && a.K0 % 32) || (b.p1 && b.K0 % 32) || (a.p1 != nullptr) != (b.p1 != nullptr) || (a.p1 && a.K0 != b.K0)) return false;
   launch_dma128(s, cat_of(a), cat_of(b), ep, M, N, a.K);
   return true;
+}
+bool big_step_store(hipStream_t s, const LoadKh2& a, const LoadKh2& b, const EpStore& ep, int M, int N) {
+  const TraceScope ts("big_step_store");
+  return big_step_store_(s, a, b, ep, M, N);
 }
 __global__ __launch_bounds__(256) void gates_elem_fwd_kernel(const float* __restrict__ z, int64_t ldz, EpGatesFwd ep) {
   const int j = blockIdx.x * 256 + threadIdx.x, row = blockIdx.y;
@@ -451,10 +479,14 @@ __global__ __launch_bounds__(256) void gates_elem_bwd_kernel(EpGatesBwd ep) {
 }
 void gates_elem_bwd(hipStream_t s, const EpGatesBwd& ep, int M, int H) {
   if (M <= 0 || H <= 0) return;
+  const TraceScope ts("gates_elem_bwd");
+  trace_launch("gates_elem_bwd_kernel", "", M, H, 0);
   hipLaunchKernelGGL(gates_elem_bwd_kernel, dim3(cdiv(H, 256), M), dim3(256), 0, s, ep);
 }
 bool big_step_gates_fwd(hipStream_t s, const LoadKh2& a, const LoadKh2& b, const EpGatesFwd& ep, int M, int H, float* zbuf, size_t zbuf_floats) {
-  if (!zbuf || zbuf_floats < (size_t)M * 4 * H || !big_step_store(s, a, b, make_store(zbuf, 4 * H, M, 4 * H, nullptr, nullptr, 0), M, 4 * H)) return false;
+  const TraceScope ts("big_step_gates_fwd");
+  if (!zbuf || zbuf_floats < (size_t)M * 4 * H || !big_step_store_(s, a, b, make_store(zbuf, 4 * H, M, 4 * H, nullptr, nullptr, 0), M, 4 * H)) return false;
+  trace_launch("gates_elem_fwd_kernel", "", M, H, 0);
   hipLaunchKernelGGL(gates_elem_fwd_kernel, dim3(cdiv(H, 256), M), dim3(256), 0, s, zbuf, (int64_t)4 * H, ep);
   return true;
 }
