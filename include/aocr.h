@@ -389,6 +389,29 @@ int aocr_beam_select_dict(void* stream, const float* logp_dev, const int32_t* pr
 int aocr_edit_distance(void* stream, const int32_t* labels_dev, const int32_t* targets_dev, int32_t B, int32_t L,
                        int32_t* dist_dev, int32_t* target_len_dev);
 
+/* Lexicon snapping, the lexicon-based recognition of the literature: every prediction is replaced by the word of a list at the smallest
+ * edit distance.  A word list in device memory: row w holds the 1-based vocab ids (1..255) of word w, then 0 up to `stride`.
+ * A word has at most stride-1 ids; an all-zero row is the empty word.  stride: a multiple of 16, 16..256; words_dev 16-byte aligned. */
+typedef struct aocr_lexicon {
+  const uint8_t* words_dev;    /* (n_words, stride) */
+  int32_t n_words, stride;
+} aocr_lexicon;
+
+/* Bytes of device scratch aocr_lexicon_nearest needs for B rows against n_words words (0 for a list one workgroup per row covers). */
+size_t aocr_lexicon_scratch_bytes(int32_t B, int32_t n_words);
+
+/* For every row b of labels_dev (B, L) int32, cut at its first EOS (3) exactly as aocr_edit_distance cuts it:
+ *   index_dev[b] = the word w in [row_begin[b], row_begin[b+1]) with the smallest string.levenshtein distance
+ *                  (utils.lua:55-94, unit costs) to the cut row; ties go to the LOWEST w;
+ *   dist_dev[b]  = that distance.
+ * row_begin_dev (B+1) int32, non-decreasing: per-image lexicons (rows search disjoint or overlapping slices of one list);
+ * NULL = every row searches [0, n_words).  An empty range gives index -1, dist -1.  The bounds read from row_begin_dev are
+ * clamped to [0, n_words] on the device; a label id outside 1..255 before the EOS matches no lexicon id.
+ * L <= 64.  B == 0 is a no-op.  Enqueues only, never synchronises; the result does not depend on launch geometry or run
+ * (bit-identical between calls). */
+int aocr_lexicon_nearest(void* stream, const int32_t* labels_dev, int32_t B, int32_t L, const aocr_lexicon* lex,
+                         const int32_t* row_begin_dev, void* scratch_dev, int32_t* index_dev, int32_t* dist_dev);
+
 /* ---- data path ----------------------------------------------------------------------------------
  * data_gen.lua:68-79: img = 255 * image.rgb2y(img); img = image.scale(img, imgW, 32) for every decoded image of a batch
  * (all images of a batch share imgW: the loader buckets by width, data_gen.lua:91-99).

@@ -82,6 +82,9 @@ int aocr_logsoftmax_nll(void* stream, const float* logits_dev, int64_t ld, const
 int aocr_beam_select(void* stream, const float* logp_dev, const int32_t* prev_tok_dev, float* beam_scores_dev, int32_t* tokens_dev, int32_t* parents_dev, int32_t B, int32_t kin, int32_t kout, int32_t V);
 int aocr_beam_select_dict(void* stream, const float* logp_dev, const int32_t* prev_tok_dev, float* beam_scores_dev, int32_t* tokens_dev, int32_t* parents_dev, int32_t B, int32_t kin, int32_t kout, int32_t V, const aocr_trie* trie, const int32_t* loc_in_dev, int32_t* loc_out_dev);
 int aocr_edit_distance(void* stream, const int32_t* labels_dev, const int32_t* targets_dev, int32_t B, int32_t L, int32_t* dist_dev, int32_t* target_len_dev);
+typedef struct aocr_lexicon { const uint8_t* words_dev; int32_t n_words, stride; } aocr_lexicon;
+size_t aocr_lexicon_scratch_bytes(int32_t B, int32_t n_words);
+int aocr_lexicon_nearest(void* stream, const int32_t* labels_dev, int32_t B, int32_t L, const aocr_lexicon* lex, const int32_t* row_begin_dev, void* scratch_dev, int32_t* index_dev, int32_t* dist_dev);
 typedef struct aocr_image_desc { int64_t offset; int32_t height, width, channels, reserved; } aocr_image_desc;
 int aocr_preprocess_lines(void* stream, const uint8_t* src_dev, const aocr_image_desc* desc_dev, int32_t n_images, int32_t out_h, int32_t out_w, float* out_dev);
 typedef struct aocr_warp { float m00, m01, m02; float m10, m11, m12; float gain, offset; float fill; float noise; } aocr_warp;

@@ -31,6 +31,11 @@ class TrieDesc(C.Structure):
                 ("n_nodes", C.c_int32), ("n_edges", C.c_int32)]
 
 
+class LexiconDesc(C.Structure):
+    """mirror of `aocr_lexicon` (include/aocr.h)."""
+    _fields_ = [("words_dev", C.c_void_p), ("n_words", C.c_int32), ("stride", C.c_int32)]
+
+
 class Config(C.Structure):
     """mirror of `aocr_config` (include/aocr.h)."""
     _fields_ = [(n, C.c_int32) for n in (
@@ -102,6 +107,8 @@ SIGNATURES = {
     "aocr_logsoftmax_nll": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _f32]),
     "aocr_beam_select_dict": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "aocr_edit_distance": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "aocr_lexicon_scratch_bytes": (_sz, [_i32, _i32]),
+    "aocr_lexicon_nearest": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "aocr_preprocess_lines": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "aocr_augment_lines": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_uint64, C.c_uint64, _vp]),
     "aocr_beam_select": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32]),

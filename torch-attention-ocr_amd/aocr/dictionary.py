@@ -10,6 +10,11 @@ admissibility test runs inside the selection kernel (`project_select_kernel` / `
     child[...]     int32    child node ids, ascending v per node
 
 Node 0 is the start symbol's node (`trie[2]`).  The edit distance runs on device too (`aocr_edit_distance`).
+
+`Lexicon` is the other dictionary mechanism, the lexicon-based recognition of the literature: the word list stays a list (one fixed-stride
+row of vocab ids per word, device resident) and every recognised line is snapped to the word at the smallest edit distance
+(`aocr_lexicon_nearest`), with that distance returned as a rejection signal.  It works at any beam width, takes a slice of the list per
+image and vocab ids up to 255.
 """
 from __future__ import annotations
 
@@ -19,7 +24,7 @@ from typing import Iterable, List, Optional
 import numpy as np
 import torch
 
-from ._lib import TrieDesc, check, lib, ptr
+from ._lib import LexiconDesc, TrieDesc, check, lib, ptr
 
 PAD, GO, EOS = 1, 2, 3
 MAX_VOCAB = 64
@@ -158,3 +163,97 @@ def edit_distance_device(labels: torch.Tensor, targets: torch.Tensor, stream=Non
     s = s if isinstance(s, C.c_void_p) else C.c_void_p(s)
     check(lib.aocr_edit_distance(s, ptr(labels), ptr(targets), B, L, ptr(dist), ptr(tlen)), "aocr_edit_distance")
     return dist, tlen
+
+
+_FIRST_CHAR_ID = 4           # ids 1..3 are PAD, GO, EOS
+
+
+class Lexicon:
+    """A word list for `aocr_lexicon_nearest`: `array` (n_words, stride) uint8 holds the vocab ids of word w (`char_id` per byte of the
+    stripped line, as `build_trie` maps it), then 0 up to `stride`.  A word is kept iff all its ids are in 4..255 and it fits the stride
+    (at most stride-1 ids); `words` lists the kept words in index order, `skipped` the dropped ones.  stride: a multiple of 16 in 16..256;
+    default: the smallest that holds the longest word with valid ids plus its 0."""
+
+    def __init__(self, words: Iterable[str], device=None, stride: Optional[int] = None):
+        if stride is not None and not (16 <= stride <= 256 and stride % 16 == 0):
+            raise ValueError(f"stride must be a multiple of 16 in 16..256, got {stride}")
+        cand, self.skipped = [], []
+        for line in words:
+            w = line.strip()
+            try:
+                ids = [char_id(c) for c in w.encode("latin-1")]
+            except UnicodeEncodeError:                       # no byte, no id
+                ids = [0]
+            if all(_FIRST_CHAR_ID <= v <= 255 for v in ids) and len(ids) < (stride or 256):
+                cand.append((w, ids))
+            else:
+                self.skipped.append(w)
+        if stride is None:
+            stride = max(16, -(-(max((len(ids) for _, ids in cand), default=0) + 1) // 16) * 16)
+        self.stride = int(stride)
+        self.words: List[str] = [w for w, _ in cand]
+        self.array = np.zeros((len(cand), self.stride), np.uint8)
+        for i, (_, ids) in enumerate(cand):
+            self.array[i, :len(ids)] = ids
+        self._dev = None
+        self._scratch = None
+        if device is not None:
+            self.to(device)
+
+    @property
+    def n_words(self) -> int:
+        return int(self.array.shape[0])
+
+    def __len__(self) -> int:
+        return self.n_words
+
+    def to(self, device) -> "Lexicon":
+        device = torch.device(device)
+        self._dev = torch.from_numpy(self.array if self.n_words else np.zeros((1, self.stride), np.uint8)).to(device)
+        self._scratch = None
+        return self
+
+    def desc(self) -> LexiconDesc:
+        """`aocr_lexicon` over the uploaded list (keep this Lexicon alive while the descriptor is in use)."""
+        if self._dev is None:
+            raise RuntimeError("Lexicon.to(device) has not been called")
+        return LexiconDesc(ptr(self._dev), self.n_words, self.stride)
+
+    def nearest(self, labels_dev: torch.Tensor, row_begin=None, stream=None):
+        """(index, dist), int32 device tensors of B elements: per row of labels_dev (B, L <= 64) int32, cut at its first EOS, the word at the
+        smallest edit distance (lowest index on ties) and that distance.  row_begin (B+1), non-decreasing: row b searches the words
+        [row_begin[b], row_begin[b+1]) (per-image lexicons); None: every row searches the whole list.  An empty range gives -1 / -1.
+        Enqueues only.  The scratch tensor is owned by this Lexicon and reused: calls on one Lexicon belong on one stream."""
+        desc = self.desc()
+        dev = self._dev.device
+        assert labels_dev.dim() == 2 and labels_dev.dtype == torch.int32 and labels_dev.device == dev
+        labels_dev = labels_dev.contiguous()
+        B, L = labels_dev.shape
+        if row_begin is not None:
+            if not isinstance(row_begin, torch.Tensor):
+                row_begin = torch.from_numpy(np.ascontiguousarray(row_begin, dtype=np.int32))
+            row_begin = row_begin.to(device=dev, dtype=torch.int32).contiguous()
+            if row_begin.shape != (B + 1,):
+                raise ValueError(f"row_begin must have B + 1 = {B + 1} entries, got {tuple(row_begin.shape)}")
+        index = torch.empty(B, dtype=torch.int32, device=dev)
+        dist = torch.empty(B, dtype=torch.int32, device=dev)
+        if B == 0:
+            return index, dist
+        need = int(lib.aocr_lexicon_scratch_bytes(B, self.n_words))
+        if need and (self._scratch is None or self._scratch.numel() * 8 < need):
+            self._scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+        s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        s = s if isinstance(s, C.c_void_p) else C.c_void_p(s)
+        check(lib.aocr_lexicon_nearest(s, ptr(labels_dev), B, L, C.byref(desc), ptr(row_begin), ptr(self._scratch) if need else None,
+                                       ptr(index), ptr(dist)), "aocr_lexicon_nearest")
+        return index, dist
+
+
+def load_lexicon(path: str, device=None) -> Lexicon:
+    """A `Lexicon` from a file with one word per line (encoding and errors as in `load_dictionary`)."""
+    try:
+        f = open(path, "r", encoding="latin-1")
+    except OSError as e:
+        raise FileNotFoundError(f"Error: Data file {path} not found") from e
+    with f:
+        return Lexicon(f, device)

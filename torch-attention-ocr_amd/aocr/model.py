@@ -399,11 +399,16 @@ class Model:
                                  ptr(clp), ptr(attn)), "aocr_recognize")
         return labels, scores, clp, attn
 
-    def recognize(self, images, beam_size=None, trie=None, attention=False, width=None):
+    def recognize(self, images, beam_size=None, trie=None, attention=False, width=None, lexicon=None, lexicon_rows=None):
         """Read images without labels.  images: a preprocessed (B,1,32,W) tensor, or a list of uint8 (H,W) / (H,W,3) arrays (load_image), which
         go through preprocess_batch at `width` (default max_img_w).  Returns a namespace: labels (B,max_decoder_l) int32, scores (B), text (per
         row, cut at the first EOS), char_logp (B,max_decoder_l), attention (B,max_decoder_l,T) when asked for (else None) and columns (T): the
-        image column every encoder step is centred on."""
+        image column every encoder step is centred on.
+        lexicon: an `aocr.Lexicon`; every row is also snapped to its nearest word (aocr_lexicon_nearest) and the namespace carries word (per row,
+        None for an empty range), word_index (B) and word_distance (B) int32.  lexicon_rows (B+1): row b searches the words
+        [lexicon_rows[b], lexicon_rows[b+1]) of the lexicon (per-image lexicons); None: the whole list."""
+        if lexicon is None and lexicon_rows is not None:
+            raise ValueError("lexicon_rows without a lexicon")
         if isinstance(images, (list, tuple)):
             from .data import preprocess_batch
             images = preprocess_batch(list(images), int(width or self.max_img_w), self.device, self._stream())
@@ -412,6 +417,11 @@ class Model:
         assert images.dim() == 4 and images.shape[1] == 1 and images.shape[2] == self.img_h
         beam_size = min(beam_size or 1, self.target_vocab_size)
         labels, scores, clp, attn = self.recognize_device(images, beam_size, trie, attention, True)
+        snapped = None
+        if lexicon is not None:
+            if lexicon._dev is None or lexicon._dev.device != self.device:
+                lexicon.to(self.device)
+            snapped = lexicon.nearest(labels, lexicon_rows, self._stream())
         labels_h = labels.cpu().numpy()
         text = []
         for row in labels_h:
@@ -422,8 +432,12 @@ class Model:
                 ids.append(int(v))
             text.append(numlist2str(ids))
         self.check_health()
-        return SimpleNamespace(labels=labels_h, scores=scores.cpu().numpy(), text=text, char_logp=clp.cpu().numpy(),
-                               attention=attn.cpu().numpy() if attn is not None else None, columns=encoder_columns(images.shape[3]))
+        res = SimpleNamespace(labels=labels_h, scores=scores.cpu().numpy(), text=text, char_logp=clp.cpu().numpy(),
+                              attention=attn.cpu().numpy() if attn is not None else None, columns=encoder_columns(images.shape[3]))
+        if snapped is not None:
+            res.word_index, res.word_distance = snapped[0].cpu().numpy(), snapped[1].cpu().numpy()
+            res.word = [lexicon.words[i] if i >= 0 else None for i in res.word_index.tolist()]
+        return res
 
     def profile_kernel(self, which=0, iters=20):
         """HIP-event timing of one hot kernel at the last step's shape: (ms per launch, flops per launch)."""

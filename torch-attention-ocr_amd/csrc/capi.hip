@@ -721,6 +721,28 @@ int aocr_edit_distance(void* stream, const int32_t* labels_dev, const int32_t* t
   return check_launch("aocr_edit_distance");
 }
 
+size_t aocr_lexicon_scratch_bytes(int32_t B, int32_t n_words) {
+  if (B <= 0 || n_words <= 0) return 0;
+  const int slices = lexicon_slices(n_words);
+  return slices > 1 ? (size_t)B * slices * sizeof(uint64_t) : 0;           // one key per (row, slice); a single slice writes the result itself
+}
+int aocr_lexicon_nearest(void* stream, const int32_t* labels_dev, int32_t B, int32_t L, const aocr_lexicon* lex, const int32_t* row_begin_dev,
+                         void* scratch_dev, int32_t* index_dev, int32_t* dist_dev) {
+  REQUIRE(lex, "lexicon is NULL");
+  REQUIRE(B >= 0 && L >= 1 && L <= 64, "bad sizes: B=%d L=%d (L must be 1..64)", B, L);
+  REQUIRE(index_dev && dist_dev && (labels_dev || B == 0), "NULL argument");
+  REQUIRE(lex->stride >= 16 && lex->stride <= 256 && lex->stride % 16 == 0, "bad stride %d: a multiple of 16 in 16..256", lex->stride);
+  REQUIRE(lex->n_words >= 0 && (lex->n_words == 0 || lex->words_dev), "bad lexicon: n_words=%d words_dev=%p", lex->n_words, (const void*)lex->words_dev);
+  REQUIRE(((uintptr_t)lex->words_dev & 15) == 0, "words_dev must be 16-byte aligned");
+  REQUIRE((int64_t)B * lexicon_slices(lex->n_words) <= INT32_MAX, "B=%d rows against n_words=%d words: too many workgroups", B, lex->n_words);
+  REQUIRE(scratch_dev || aocr_lexicon_scratch_bytes(B, lex->n_words) == 0, "scratch_dev is NULL: aocr_lexicon_scratch_bytes(%d, %d) bytes are needed",
+          B, lex->n_words);
+  REQUIRE(((uintptr_t)scratch_dev & 7) == 0, "scratch_dev must be 8-byte aligned");
+  if (B == 0) return 0;
+  lexicon_nearest((hipStream_t)stream, labels_dev, B, L, lex->words_dev, lex->n_words, lex->stride, row_begin_dev, scratch_dev, index_dev, dist_dev);
+  return check_launch("aocr_lexicon_nearest");
+}
+
 int aocr_preprocess_lines(void* stream, const uint8_t* src_dev, const aocr_image_desc* desc_dev, int32_t n_images, int32_t out_h,
                           int32_t out_w, float* out_dev) {
   REQUIRE(src_dev && desc_dev && out_dev, "NULL argument");

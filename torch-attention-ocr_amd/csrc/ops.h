@@ -246,6 +246,12 @@ void recognize_gather(hipStream_t s, const int32_t* labels, const int32_t* hist_
 void fill_i32(hipStream_t s, int32_t* p, int32_t v, int64_t n);
 // Levenshtein distance between two id rows cut at the first EOS (utils.lua:55-94 over the strings of utils.lua:136-168)
 void edit_distance(hipStream_t s, const int32_t* labels, const int32_t* targets, int B, int L, int32_t* dist, int32_t* target_len);
+// ---- lexicon snapping (lexicon.hip; include/aocr.h: aocr_lexicon_nearest): per label row cut at its first EOS, the word of
+// words [n_words][stride] (ids 1..255, zero filled) in [row_begin[b], row_begin[b+1]) (nullptr: the whole list) at the smallest
+// Levenshtein distance, lowest index on ties.  lexicon_slices: workgroups per row; scratch holds B * slices 64-bit keys when slices > 1.
+int lexicon_slices(int n_words);
+void lexicon_nearest(hipStream_t s, const int32_t* labels, int B, int L, const uint8_t* words, int n_words, int stride,
+                     const int32_t* row_begin, void* scratch, int32_t* index, int32_t* dist);
 
 // ---- whole-sequence encoder recurrence (rnn_seq.hip): one workgroup owns 16 batch rows of one direction for all T steps
 struct EncSeqDir {
