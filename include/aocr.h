@@ -449,6 +449,43 @@ typedef struct aocr_warp {
 int aocr_augment_lines(void* stream, const float* in_dev, const aocr_warp* warp_dev, int32_t n_images, int32_t H, int32_t W,
                        uint64_t seed, uint64_t counter, float* out_dev);
 
+/* ---- synthetic word lines: lexicon words rendered from a glyph atlas into a batch of line crops and its targets ---------
+ * The reference's training set (train.lua:21) is rendered dictionary words stretched to 32 x 100; this renders such crops where the
+ * train step reads them.  out_dev: (n_images, 1, H, W) fp32 in 0..255, the layout aocr_preprocess_lines writes and aocr_augment_lines
+ * reads.  style_dev[i]: the record of image i, drawn by the host like aocr_warp.  Every float operation below is one rounded
+ * single-precision op, in this order:
+ *   word: the ids of lexicon row `word` up to its first 0 (n <= stride-1 ids); `word` outside [0, n_words) or `face` outside
+ *         [0, n_faces) gives the empty word (paper only; its targets are those of the empty word);
+ *   an id outside 4..n_glyphs+3 draws nothing and advances by 0 (it still appears in the targets);
+ *   pens: sp = max(spacing, 0) (NaN -> 0); p_0 = 0, p_{k+1} = (p_k + adv_k) + sp, summed in this sequential order;
+ *   per output pixel (x, y): u = (x - x0)*sx, v = (y - y0)*sy, each clamped to [-1, 16384] (NaN -> -1);
+ *   glyph k = the largest k in [0, n) with p_k <= u (none if u < 0 or n = 0); lu = u - p_k;
+ *   xi = floor(lu), fx = lu - xi, yi = floor(v), fy = v - yi; the taps (xi,yi) (xi+1,yi) (xi,yi+1) (xi+1,yi+1) = a b c d read glyph
+ *   k's bitmap inside [0,gw) x [0,gh) and are 0 elsewhere or when there is no glyph;
+ *   top = (1-fx)*a + fx*b, bot = (1-fx)*c + fx*d, s = (1-fy)*top + fy*bot (the order of aocr_augment_lines);
+ *   out = min(max(bg + (fg - bg)*(s / 255), 0), 255), the division a true division: a 0/255 atlas blits exactly.
+ * targets_dev, targets_eval_dev: (n_images, L) int32, the rows DataGen builds: targets[j] = GO(2) at j = 0, id_{j-1} while j-1 < n,
+ * PAD(1) after; targets_eval[j] = id_j while j < n, EOS(3) at j = n, PAD after; a word longer than L-1 is cut by these rules.
+ * Both may be NULL together: only the images are written.
+ * n_images <= 65535; n_images == 0 is a no-op.  Enqueues only, never synchronises; the result does not depend on launch geometry. */
+typedef struct aocr_glyph_atlas {
+  const uint8_t* pixels_dev;    /* (n_faces, n_glyphs, gh, gw) ink coverage, 0 = paper, 255 = ink */
+  const uint8_t* advance_dev;   /* (n_faces, n_glyphs) pen advance in atlas pixels, 0..gw */
+  int32_t n_faces, n_glyphs, gh, gw;   /* glyph g draws vocab id g + 4; gh, gw in 1..64; n_glyphs in 1..252 */
+} aocr_glyph_atlas;
+
+typedef struct aocr_synth_style {      /* one per image, drawn by the host like aocr_warp */
+  int32_t word, face;           /* lexicon row, atlas face */
+  float spacing;                /* extra advance between glyphs, atlas pixels, >= 0 */
+  float sx, sy;                 /* atlas pixels per output pixel, x and y */
+  float x0, y0;                 /* output-pixel position of the text box's top-left corner */
+  float fg, bg;                 /* ink and paper gray, 0..255 */
+} aocr_synth_style;
+
+int aocr_synth_lines(void* stream, const aocr_lexicon* lex, const aocr_glyph_atlas* atlas,
+                     const aocr_synth_style* style_dev, int32_t n_images, int32_t H, int32_t W, int32_t L,
+                     float* out_dev, int32_t* targets_dev, int32_t* targets_eval_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,9 +12,11 @@ from . import data
 from .data import DataGen
 from . import augment
 from .augment import Augmenter
+from . import synth_lines
+from .synth_lines import GlyphAtlas, SynthGen
 from . import dictionary
 from . import t7, checkpoint
 from .dictionary import Trie, load_dictionary, build_trie, levenshtein, Lexicon, load_lexicon
 
-__all__ = ["Model", "DataGen", "Augmenter", "augment", "data", "dictionary", "t7", "checkpoint", "Trie", "load_dictionary", "build_trie", "levenshtein", "Lexicon", "load_lexicon", "AocrError", "Config", "COMPUTE_F32", "COMPUTE_BF16", "lib", "last_error", "check", "ptr",
+__all__ = ["Model", "DataGen", "Augmenter", "augment", "GlyphAtlas", "SynthGen", "synth_lines", "data", "dictionary", "t7", "checkpoint", "Trie", "load_dictionary", "build_trie", "levenshtein", "Lexicon", "load_lexicon", "AocrError", "Config", "COMPUTE_F32", "COMPUTE_BF16", "lib", "last_error", "check", "ptr",
            "param_table", "eval_word_err_rate", "numlist2str", "encoder_columns", "GROUPS", "synth"]

@@ -36,6 +36,17 @@ class LexiconDesc(C.Structure):
     _fields_ = [("words_dev", C.c_void_p), ("n_words", C.c_int32), ("stride", C.c_int32)]
 
 
+class GlyphAtlasDesc(C.Structure):
+    """mirror of `aocr_glyph_atlas` (include/aocr.h)."""
+    _fields_ = [("pixels_dev", C.c_void_p), ("advance_dev", C.c_void_p), ("n_faces", C.c_int32), ("n_glyphs", C.c_int32),
+                ("gh", C.c_int32), ("gw", C.c_int32)]
+
+
+class SynthStyle(C.Structure):
+    """mirror of `aocr_synth_style` (include/aocr.h)."""
+    _fields_ = [("word", C.c_int32), ("face", C.c_int32)] + [(n, C.c_float) for n in ("spacing", "sx", "sy", "x0", "y0", "fg", "bg")]
+
+
 class Config(C.Structure):
     """mirror of `aocr_config` (include/aocr.h)."""
     _fields_ = [(n, C.c_int32) for n in (
@@ -111,6 +122,7 @@ SIGNATURES = {
     "aocr_lexicon_nearest": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "aocr_preprocess_lines": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "aocr_augment_lines": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_uint64, C.c_uint64, _vp]),
+    "aocr_synth_lines": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "aocr_beam_select": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32]),
 }
 

@@ -761,4 +761,23 @@ int aocr_augment_lines(void* stream, const float* in_dev, const aocr_warp* warp_
   return check_launch("aocr_augment_lines");
 }
 
+int aocr_synth_lines(void* stream, const aocr_lexicon* lex, const aocr_glyph_atlas* atlas, const aocr_synth_style* style_dev, int32_t n_images,
+                     int32_t H, int32_t W, int32_t L, float* out_dev, int32_t* targets_dev, int32_t* targets_eval_dev) {
+  REQUIRE(lex, "lexicon is NULL");
+  REQUIRE(atlas, "atlas is NULL");
+  REQUIRE(n_images >= 0 && H >= 1 && W >= 1 && L >= 1 && (int64_t)H * W <= INT32_MAX, "bad sizes: n_images=%d H=%d W=%d L=%d", n_images, H, W, L);
+  REQUIRE(n_images <= 65535, "n_images=%d: at most 65535 images per call", n_images);
+  REQUIRE(lex->stride >= 16 && lex->stride <= 256 && lex->stride % 16 == 0, "bad stride %d: a multiple of 16 in 16..256", lex->stride);
+  REQUIRE(lex->n_words >= 0 && (lex->n_words == 0 || lex->words_dev), "bad lexicon: n_words=%d words_dev=%p", lex->n_words, (const void*)lex->words_dev);
+  REQUIRE(((uintptr_t)lex->words_dev & 15) == 0, "words_dev must be 16-byte aligned");
+  REQUIRE(atlas->n_faces >= 1 && atlas->n_glyphs >= 1 && atlas->n_glyphs <= 252 && atlas->gh >= 1 && atlas->gh <= 64 && atlas->gw >= 1 && atlas->gw <= 64,
+          "bad atlas: n_faces=%d n_glyphs=%d (1..252) gh=%d gw=%d (1..64)", atlas->n_faces, atlas->n_glyphs, atlas->gh, atlas->gw);
+  REQUIRE(atlas->pixels_dev && atlas->advance_dev, "bad atlas: pixels_dev or advance_dev is NULL");
+  REQUIRE(style_dev && out_dev, "NULL argument");
+  REQUIRE((targets_dev == nullptr) == (targets_eval_dev == nullptr), "targets_dev and targets_eval_dev must be given, or be NULL, together");
+  if (n_images == 0) return 0;
+  synth_lines((hipStream_t)stream, *lex, *atlas, style_dev, n_images, H, W, L, out_dev, targets_dev, targets_eval_dev);
+  return check_launch("aocr_synth_lines");
+}
+
 }  // extern "C"

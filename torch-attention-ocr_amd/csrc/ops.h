@@ -352,4 +352,8 @@ void preprocess_lines(hipStream_t s, const uint8_t* src, const aocr_image_desc* 
 // training augmentation (data.hip): affine warp + gain / offset + counter-based noise of n (1,H,W) images, in != out
 void augment_lines(hipStream_t s, const float* in, const aocr_warp* warp, int n_images, int H, int W, uint64_t seed, uint64_t counter,
                    float* out);
+// synthetic word lines (synth.hip; include/aocr.h: aocr_synth_lines): lexicon rows drawn from a glyph atlas into n (1,H,W) crops, and
+// their targets / targets_eval rows (n, L) unless both are nullptr
+void synth_lines(hipStream_t s, const aocr_lexicon& lex, const aocr_glyph_atlas& atlas, const aocr_synth_style* style, int n_images, int H,
+                 int W, int L, float* out, int32_t* targets, int32_t* targets_eval);
 }  // namespace aocr
