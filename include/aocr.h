@@ -486,6 +486,62 @@ int aocr_synth_lines(void* stream, const aocr_lexicon* lex, const aocr_glyph_atl
                      const aocr_synth_style* style_dev, int32_t n_images, int32_t H, int32_t W, int32_t L,
                      float* out_dev, int32_t* targets_dev, int32_t* targets_eval_dev);
 
+/* ---- page segmentation: from a scanned page to the word crops aocr_recognize reads ---------------------------------------
+ * The reference is fed cropped words (90kDICT32px); this finds them on a page by projection profiles and cuts them out, on the device.
+ * It assumes roughly horizontal lines in one column: skewed or multi-column pages are out of scope.
+ * page_dev: gray uint8, H rows of W pixels, rows `pitch` bytes apart (pitch >= W); any base address and any pitch, nothing need be aligned.
+ * 1 <= H, W <= 16384, H*W <= 2^26, 1 <= max_boxes <= 4096.  Steps, in order:
+ *   1 histogram  h[v], 256 bins, of the page (only the Otsu threshold reads it);
+ *   2 threshold  params.threshold when >= 0, else Otsu in double precision, every operation one rounded IEEE op: N = sum h, S = sum v*h[v]
+ *                (int64); for t = 0..254 ascending: n0 += h[t], s0 += t*h[t] (integers), n1 = N - n0; t is skipped when n0 == 0 or n1 == 0;
+ *                d = (double)s0*(double)n1 - (double)(S-s0)*(double)n0; score = (d*d) / ((double)n0*(double)n1); the first t with the strictly
+ *                largest score wins.  No t qualifies (one gray value): the threshold is -1, nothing is ink, zero boxes;
+ *                ink = (v <= threshold), or (v > threshold) with light_text;
+ *   3 rows       row_ink[y] = ink pixels of row y;
+ *   4 bands      maximal runs of rows with row_ink >= min_row_ink; neighbouring runs with <= merge_gap rows between them are one band (the gap
+ *                is measured between the original runs; merging chains); bands lower than min_line_h are dropped; the rest, top to bottom,
+ *                are lines 0, 1, ...;
+ *   5 words      per band, col_ink[x] = ink pixels of column x inside the band's rows; columns with col_ink >= 1 form runs; word_gap == 0: one
+ *                box from the band's first to its last ink column; else runs with fewer than word_gap empty columns between them are one
+ *                word; words narrower than min_word_w are dropped (a band that loses all its words keeps its line number);
+ *   6 boxes      a box spans its band's rows (not tightened per word: the words of a line keep their relative size and baseline); ink = the ink
+ *                pixels inside the unpadded box; then x grows by pad_x and y by pad_y, clamped to the page.  Order: line, then x0.  The first
+ *                max_boxes are written; rows of boxes_dev beyond them are untouched;
+ *   7 counts     counts_dev[0] = boxes found (it may exceed max_boxes: that is how the caller sees truncation), [1] = lines, [2] = the
+ *                threshold used, [3] = 0.
+ * scratch_dev: aocr_segment_scratch_bytes(H, W, max_boxes) bytes, 16-byte aligned, overwritten by the call (0 and an error for bad sizes).
+ * Enqueues only, never synchronises or allocates; the result does not depend on launch geometry, atomics order or run.  Invalid params or
+ * sizes return an error before anything is enqueued. */
+typedef struct aocr_segment_params {
+  int32_t threshold;     /* 0..254: ink = (v <= threshold); -1: Otsu (above) */
+  int32_t light_text;    /* 1: ink = (v > threshold) instead */
+  int32_t min_row_ink;   /* >= 1: a row is a text row when its ink count >= this */
+  int32_t merge_gap;     /* >= 0: text-row runs separated by <= merge_gap non-text rows are one band (0: never merges) */
+  int32_t min_line_h;    /* >= 1: bands lower than this are dropped */
+  int32_t word_gap;      /* 0: one box per band (first to last ink column); > 0: ink-column runs separated by fewer than
+                            word_gap empty columns are one word */
+  int32_t min_word_w;    /* >= 1: narrower words are dropped */
+  int32_t pad_x, pad_y;  /* >= 0: every box grows by this much, clamped to the page */
+  int32_t reserved;
+} aocr_segment_params;
+
+typedef struct aocr_box { int32_t x0, y0, x1, y1, line, ink; } aocr_box;   /* half-open [x0,x1) x [y0,y1) */
+
+size_t aocr_segment_scratch_bytes(int32_t H, int32_t W, int32_t max_boxes);
+int aocr_segment_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                      const aocr_segment_params* params, void* scratch_dev, int32_t max_boxes,
+                      aocr_box* boxes_dev, int32_t counts_dev[4]);
+
+/* The crops of a page: row i < n of out_dev (n_boxes, 1, out_h, out_w) fp32 is rectangle boxes_dev[i] of the page scaled to out_h x out_w with
+ * the arithmetic of aocr_preprocess_lines on a one-channel image, operation for operation (rows to out_w first, then columns to out_h): the
+ * result is bit-identical to aocr_preprocess_lines on a contiguous copy of the rectangle.  n = min(n_boxes, count_dev[0]) is read on the
+ * device (count_dev = the counts of aocr_segment_page: no host sync in between); count_dev == NULL: n = n_boxes.  Box coordinates are
+ * clamped to the page on the device before any read; a box that is empty after clamping gives a row of 255.0 (paper).  Rows >= n are
+ * untouched.  n_boxes <= 65535; n_boxes == 0 is a no-op.  The page follows the rules of aocr_segment_page.  Enqueues only. */
+int aocr_crop_lines(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                    const aocr_box* boxes_dev, const int32_t* count_dev, int32_t n_boxes,
+                    int32_t out_h, int32_t out_w, float* out_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,11 @@ int aocr_augment_lines(void* stream, const float* in_dev, const aocr_warp* warp_
 typedef struct aocr_glyph_atlas { const uint8_t* pixels_dev; const uint8_t* advance_dev; int32_t n_faces, n_glyphs, gh, gw; } aocr_glyph_atlas;
 typedef struct aocr_synth_style { int32_t word, face; float spacing; float sx, sy; float x0, y0; float fg, bg; } aocr_synth_style;
 int aocr_synth_lines(void* stream, const aocr_lexicon* lex, const aocr_glyph_atlas* atlas, const aocr_synth_style* style_dev, int32_t n_images, int32_t H, int32_t W, int32_t L, float* out_dev, int32_t* targets_dev, int32_t* targets_eval_dev);
+typedef struct aocr_segment_params { int32_t threshold; int32_t light_text; int32_t min_row_ink; int32_t merge_gap; int32_t min_line_h; int32_t word_gap; int32_t min_word_w; int32_t pad_x, pad_y; int32_t reserved; } aocr_segment_params;
+typedef struct aocr_box { int32_t x0, y0, x1, y1, line, ink; } aocr_box;
+size_t aocr_segment_scratch_bytes(int32_t H, int32_t W, int32_t max_boxes);
+int aocr_segment_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_segment_params* params, void* scratch_dev, int32_t max_boxes, aocr_box* boxes_dev, int32_t counts_dev[4]);
+int aocr_crop_lines(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_box* boxes_dev, const int32_t* count_dev, int32_t n_boxes, int32_t out_h, int32_t out_w, float* out_dev);
 ]]
 
 local M = {}

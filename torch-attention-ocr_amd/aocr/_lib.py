@@ -47,6 +47,21 @@ class SynthStyle(C.Structure):
     _fields_ = [("word", C.c_int32), ("face", C.c_int32)] + [(n, C.c_float) for n in ("spacing", "sx", "sy", "x0", "y0", "fg", "bg")]
 
 
+class SegmentParams(C.Structure):
+    """mirror of `aocr_segment_params` (include/aocr.h): how `aocr_segment_page` finds lines and words.  threshold -1: Otsu."""
+    _fields_ = [(n, C.c_int32) for n in ("threshold", "light_text", "min_row_ink", "merge_gap", "min_line_h", "word_gap", "min_word_w",
+                                         "pad_x", "pad_y", "reserved")]
+
+    def __init__(self, threshold=-1, light_text=0, min_row_ink=1, merge_gap=2, min_line_h=8, word_gap=12, min_word_w=4, pad_x=2, pad_y=2):
+        super().__init__(int(threshold), int(light_text), int(min_row_ink), int(merge_gap), int(min_line_h), int(word_gap), int(min_word_w),
+                         int(pad_x), int(pad_y), 0)
+
+
+class Box(C.Structure):
+    """mirror of `aocr_box` (include/aocr.h): half-open [x0,x1) x [y0,y1), line number, ink pixels."""
+    _fields_ = [(n, C.c_int32) for n in ("x0", "y0", "x1", "y1", "line", "ink")]
+
+
 class Config(C.Structure):
     """mirror of `aocr_config` (include/aocr.h)."""
     _fields_ = [(n, C.c_int32) for n in (
@@ -123,6 +138,9 @@ SIGNATURES = {
     "aocr_preprocess_lines": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "aocr_augment_lines": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_uint64, C.c_uint64, _vp]),
     "aocr_synth_lines": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "aocr_segment_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
+    "aocr_segment_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "aocr_crop_lines": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     "aocr_beam_select": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32]),
 }
 

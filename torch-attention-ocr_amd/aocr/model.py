@@ -439,6 +439,69 @@ class Model:
             res.word = [lexicon.words[i] if i >= 0 else None for i in res.word_index.tolist()]
         return res
 
+    def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024):
+        """Read a scanned page: segment it into word boxes (aocr_segment_page), crop them (aocr_crop_lines) and recognise the crops.
+        page: a uint8 (H,W) numpy array or tensor (gray; a 3-D array raises ValueError: colour pages are out of scope).  params: an
+        `aocr.SegmentParams` (default: Otsu threshold, dark text).  The counts and boxes are read back once (the one sync), then the boxes are
+        bucketed by crop width: `width` an int gives one bucket; otherwise each box gets DataGen's width rule (aocr.page.bucket_width with
+        width_step, capped at max_img_w).  Every bucket is cropped and recognised in chunks of at most batch_size rows through
+        recognize_device and, with a lexicon, Lexicon.nearest.
+        Returns a namespace in reading order (line, then x): boxes (n,4) int32 x0 y0 x1 y1, line (n), ink (n), text, labels (n,max_decoder_l),
+        scores (n), widths (n), threshold, n_found, n_lines, truncated (n_found > max_boxes), and word / word_index / word_distance with a
+        lexicon.  A page without boxes gives empty arrays."""
+        from .page import bucket_width, crop_lines_device, segment_page_device
+        if isinstance(page, np.ndarray):
+            if page.ndim != 2 or page.dtype != np.uint8:
+                raise ValueError(f"page must be a uint8 (H, W) array, got {page.dtype} {page.shape}: colour pages are out of scope")
+            page = torch.from_numpy(np.ascontiguousarray(page))
+        page = torch.as_tensor(page)
+        if page.dim() != 2 or page.dtype != torch.uint8:
+            raise ValueError(f"page must be a uint8 (H, W) tensor, got {page.dtype} {tuple(page.shape)}: colour pages are out of scope")
+        page = page.to(self.device)
+        beam_size = min(beam_size or 1, self.target_vocab_size)
+        stream = self._stream()
+        boxes_dev, counts_dev = segment_page_device(page, params, max_boxes, stream)
+        counts = counts_dev.cpu().numpy()
+        n = int(min(counts[0], max_boxes))
+        rows = boxes_dev[:n].cpu().numpy()
+        if width is not None:
+            widths = np.full(n, int(width), np.int64)
+        else:
+            widths = np.array([bucket_width(int(r[2] - r[0]), int(r[3] - r[1]), self.max_img_w, width_step) for r in rows], np.int64).reshape(n)
+        labels = np.full((n, self.max_decoder_l), PAD, np.int32)
+        scores = np.zeros(n, np.float32)
+        word_index, word_distance = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+        if lexicon is not None and (lexicon._dev is None or lexicon._dev.device != self.device):
+            lexicon.to(self.device)
+        for w in sorted(set(widths.tolist())):
+            members = np.nonzero(widths == w)[0]
+            for c0 in range(0, len(members), self.batch_size):
+                idx = members[c0:c0 + self.batch_size]
+                sel = boxes_dev[torch.from_numpy(idx).to(self.device)]
+                crops = crop_lines_device(page, sel, None, int(w), self.img_h, stream)
+                lab, sc, _, _ = self.recognize_device(crops, beam_size, trie)
+                if lexicon is not None:
+                    wi, wd = lexicon.nearest(lab, None, stream)
+                    word_index[idx], word_distance[idx] = wi.cpu().numpy(), wd.cpu().numpy()
+                labels[idx], scores[idx] = lab.cpu().numpy(), sc.cpu().numpy()
+        if n:
+            self.check_health()
+        text = []
+        for row in labels:
+            ids = []
+            for v in row:
+                if v == EOS:
+                    break
+                ids.append(int(v))
+            text.append(numlist2str(ids))
+        res = SimpleNamespace(boxes=rows[:, :4].copy(), line=rows[:, 4].copy(), ink=rows[:, 5].copy(), text=text, labels=labels, scores=scores,
+                              widths=widths, threshold=int(counts[2]), n_found=int(counts[0]), n_lines=int(counts[1]),
+                              truncated=bool(counts[0] > max_boxes))
+        if lexicon is not None:
+            res.word_index, res.word_distance = word_index, word_distance
+            res.word = [lexicon.words[i] if i >= 0 else None for i in word_index.tolist()]
+        return res
+
     def profile_kernel(self, which=0, iters=20):
         """HIP-event timing of one hot kernel at the last step's shape: (ms per launch, flops per launch)."""
         ms, fl = C.c_float(), C.c_double()

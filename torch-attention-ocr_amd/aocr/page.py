@@ -1,0 +1,91 @@
+"""Page segmentation on the device: `aocr_segment_page` (word boxes of a gray page by projection profiles) and `aocr_crop_lines` (the boxes
+cut out and scaled like `aocr_preprocess_lines`), the stage in front of `Model.recognize`.  Both calls only enqueue; nothing is read back
+here.  Projection profiles assume roughly horizontal lines in one column: skewed or multi-column pages are out of scope."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import torch
+
+from ._lib import Box, SegmentParams, check, lib, ptr
+
+IMG_H = 32
+MIN_ASPECT = 0.5
+
+
+def _stream(stream, device):
+    s = stream if stream is not None else torch.cuda.current_stream(device).cuda_stream
+    return s if isinstance(s, C.c_void_p) else C.c_void_p(s)
+
+
+def _page_view(page_dev):
+    """a 2-D uint8 device tensor whose rows are contiguous (a view of a larger image is taken as it is: its row stride is the pitch)."""
+    if not (isinstance(page_dev, torch.Tensor) and page_dev.dim() == 2 and page_dev.dtype == torch.uint8):
+        raise ValueError("page must be a 2-D uint8 tensor (H, W): colour pages are out of scope")
+    if not page_dev.is_cuda:
+        raise ValueError("page must be on the device")
+    H, W = page_dev.shape
+    if H < 1 or W < 1:
+        raise ValueError(f"empty page {tuple(page_dev.shape)}")
+    if W > 1 and page_dev.stride(1) != 1:
+        page_dev = page_dev.contiguous()
+    pitch = page_dev.stride(0) if H > 1 else W
+    if pitch < W:                                            # an expanded (stride 0) view
+        page_dev = page_dev.contiguous()
+        pitch = W
+    return page_dev, int(pitch)
+
+
+def segment_page_device(page_dev, params=None, max_boxes=1024, stream=None):
+    """(boxes (max_boxes, 6) int32 rows x0 y0 x1 y1 line ink, counts (4) int32: boxes found, lines, threshold, 0) as device tensors.
+    Rows of boxes beyond min(counts[0], max_boxes) are not written (they hold zeros).  Enqueues only.
+    stream: the raw handle of the CURRENT torch stream of the page's device (None takes it): the scratch and the outputs come from torch's
+    caching allocator, which orders the reuse of a freed block on the current stream only, and the scratch is freed when this returns."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    params = params if params is not None else SegmentParams()
+    dev = page_dev.device
+    need = int(lib.aocr_segment_scratch_bytes(H, W, max_boxes))
+    if need == 0:
+        check(1, "aocr_segment_scratch_bytes")
+    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    boxes = torch.zeros((max_boxes, 6), dtype=torch.int32, device=dev)
+    counts = torch.zeros(4, dtype=torch.int32, device=dev)
+    check(lib.aocr_segment_page(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), max_boxes, ptr(boxes),
+                                ptr(counts)), "aocr_segment_page")
+    return boxes, counts
+
+
+def crop_lines_device(page_dev, boxes, counts, out_w, out_h=IMG_H, stream=None):
+    """(n_boxes, 1, out_h, out_w) fp32 device tensor: row i < min(n_boxes, counts[0]) is box i of the page scaled as `aocr_preprocess_lines`
+    scales it; the other rows are paper (255).  boxes (n_boxes, 6) int32 and counts (>= 1) int32 device tensors as `segment_page_device`
+    returns them; counts None: every row of boxes is cropped.  Enqueues only.  stream: as for `segment_page_device`, the current torch stream
+    (the call reads boxes and counts, which the caller may drop right after it)."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    dev = page_dev.device
+    assert boxes.dim() == 2 and boxes.shape[1] == 6 and boxes.dtype == torch.int32 and boxes.device == dev
+    boxes = boxes.contiguous()
+    n = int(boxes.shape[0])
+    if counts is not None:
+        assert counts.dtype == torch.int32 and counts.device == dev and counts.numel() >= 1
+        counts = counts.contiguous()
+    out = torch.full((n, 1, int(out_h), int(out_w)), 255.0, dtype=torch.float32, device=dev)
+    if n:
+        check(lib.aocr_crop_lines(_stream(stream, dev), ptr(page_dev), pitch, H, W, ptr(boxes), ptr(counts), n, int(out_h), int(out_w),
+                                  ptr(out)), "aocr_crop_lines")
+    return out
+
+
+def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
+    """DataGen's width rule for a w x h box, ceil(clamp(w/h, 0.5, max_aspect) * 32), rounded up to a multiple of width_step and capped at
+    max_img_w.  max_aspect None: max_img_w / 32."""
+    max_aspect = max_aspect if max_aspect is not None else max_img_w / IMG_H
+    aspect = max(min(w / h, max_aspect), MIN_ASPECT)
+    img_w = int(math.ceil(aspect * IMG_H))
+    img_w = -(-img_w // width_step) * width_step
+    return min(img_w, int(max_img_w))
+
+
+__all__ = ["SegmentParams", "Box", "segment_page_device", "crop_lines_device", "bucket_width"]

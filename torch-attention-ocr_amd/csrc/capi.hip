@@ -780,4 +780,46 @@ int aocr_synth_lines(void* stream, const aocr_lexicon* lex, const aocr_glyph_atl
   return check_launch("aocr_synth_lines");
 }
 
+static int check_page(const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W) {
+  REQUIRE(page_dev, "page_dev is NULL");
+  REQUIRE(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26),
+          "bad page size H=%d W=%d: 1..16384 each, H*W <= 2^26", H, W);
+  REQUIRE(pitch >= W, "pitch=%lld is smaller than W=%d", (long long)pitch, W);
+  return 0;
+}
+
+size_t aocr_segment_scratch_bytes(int32_t H, int32_t W, int32_t max_boxes) {
+  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26) && max_boxes >= 1 && max_boxes <= 4096)) {
+    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26) max_boxes=%d (1..4096)", H, W, max_boxes);
+    return 0;
+  }
+  return segment_scratch_bytes(H, W, max_boxes);
+}
+
+int aocr_segment_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_segment_params* params,
+                      void* scratch_dev, int32_t max_boxes, aocr_box* boxes_dev, int32_t counts_dev[4]) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(params && scratch_dev && boxes_dev && counts_dev, "NULL argument");
+  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  REQUIRE(max_boxes >= 1 && max_boxes <= 4096, "max_boxes=%d: 1..4096", max_boxes);
+  REQUIRE(params->threshold >= -1 && params->threshold <= 254, "threshold=%d: 0..254, or -1 for Otsu", params->threshold);
+  REQUIRE(params->min_row_ink >= 1 && params->min_line_h >= 1 && params->min_word_w >= 1, "min_row_ink=%d min_line_h=%d min_word_w=%d must be >= 1",
+          params->min_row_ink, params->min_line_h, params->min_word_w);
+  REQUIRE(params->merge_gap >= 0 && params->word_gap >= 0, "merge_gap=%d word_gap=%d must be >= 0", params->merge_gap, params->word_gap);
+  REQUIRE(params->pad_x >= 0 && params->pad_y >= 0, "pad_x=%d pad_y=%d must be >= 0", params->pad_x, params->pad_y);
+  segment_page((hipStream_t)stream, page_dev, pitch, H, W, *params, scratch_dev, max_boxes, boxes_dev, counts_dev);
+  return check_launch("aocr_segment_page");
+}
+
+int aocr_crop_lines(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_box* boxes_dev,
+                    const int32_t* count_dev, int32_t n_boxes, int32_t out_h, int32_t out_w, float* out_dev) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(n_boxes >= 0 && n_boxes <= 65535 && out_h >= 1 && out_w >= 1 && (int64_t)out_h * out_w <= INT32_MAX,
+          "bad sizes: n_boxes=%d (0..65535) out_h=%d out_w=%d", n_boxes, out_h, out_w);
+  if (n_boxes == 0) return 0;
+  REQUIRE(boxes_dev && out_dev, "NULL argument");
+  crop_lines((hipStream_t)stream, page_dev, pitch, H, W, boxes_dev, count_dev, n_boxes, out_h, out_w, out_dev);
+  return check_launch("aocr_crop_lines");
+}
+
 }  // extern "C"

@@ -62,6 +62,27 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restri
   out[((int64_t)img * out_h + y) * out_w + x] = scale_elem(tmp, d.height, out_h, y);
 }
 
+// aocr_crop_lines: preprocess_kernel's arithmetic on a rectangle of a pitched one-channel page.  The box is clamped to the page before any
+// read; an empty box gives paper (255).  The number of boxes may come from the device (the counts of aocr_segment_page): no host sync.
+__global__ __launch_bounds__(256) void crop_kernel(const uint8_t* __restrict__ page, int64_t pitch, int H, int W, const aocr_box* __restrict__ boxes,
+                                                   const int32_t* __restrict__ count, int n_boxes, int out_h, int out_w, float* __restrict__ out) {
+  const int img = blockIdx.y;
+  const int id = blockIdx.x * 256 + threadIdx.x;
+  const int n = count ? min(n_boxes, count[0]) : n_boxes;
+  if (img >= n || id >= out_h * out_w) return;
+  const int y = id / out_w, x = id - y * out_w;
+  const aocr_box b = boxes[img];
+  const int x0 = min(max(b.x0, 0), W), x1 = min(max(b.x1, 0), W), y0 = min(max(b.y0, 0), H), y1 = min(max(b.y1, 0), H);
+  const int w = x1 - x0, h = y1 - y0;
+  float v = 255.0f;
+  if (w > 0 && h > 0) {
+    const uint8_t* src = page + (int64_t)y0 * pitch + x0;
+    auto tmp = [&](int row) { return scale_elem([&](int col) { return (float)src[(int64_t)row * pitch + col]; }, w, out_w, x); };
+    v = scale_elem(tmp, h, out_h, y);
+  }
+  out[((int64_t)img * out_h + y) * out_w + x] = v;
+}
+
 // Training augmentation behind preprocess_kernel (include/aocr.h: aocr_augment_lines): an affine warp with bilinear taps, gain / offset,
 // additive triangular noise, clamp to 0..255.  One thread per output pixel, four gathers and one store; every float operation is one
 // rounded single-precision op in the order of tests/augment_ref.py.  The noise is counter-based like the dropout masks (epilogues.h).
@@ -108,6 +129,13 @@ void augment_lines(hipStream_t s, const float* in, const aocr_warp* warp, int n_
 void preprocess_lines(hipStream_t s, const uint8_t* src, const aocr_image_desc* desc, int n_images, int out_h, int out_w, float* out) {
   if (n_images <= 0) return;
   hipLaunchKernelGGL(preprocess_kernel, dim3(cdiv(out_h * out_w, 256), n_images), dim3(256), 0, s, src, desc, out_h, out_w, out);
+}
+
+void crop_lines(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_box* boxes, const int32_t* count, int n_boxes,
+                int out_h, int out_w, float* out) {
+  if (n_boxes <= 0) return;
+  hipLaunchKernelGGL(crop_kernel, dim3(cdiv(out_h * out_w, 256), n_boxes), dim3(256), 0, s, page, pitch, H, W, boxes, count, n_boxes, out_h,
+                     out_w, out);
 }
 
 }  // namespace aocr

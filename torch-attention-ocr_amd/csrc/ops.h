@@ -356,4 +356,11 @@ void augment_lines(hipStream_t s, const float* in, const aocr_warp* warp, int n_
 // their targets / targets_eval rows (n, L) unless both are nullptr
 void synth_lines(hipStream_t s, const aocr_lexicon& lex, const aocr_glyph_atlas& atlas, const aocr_synth_style* style, int n_images, int H,
                  int W, int L, float* out, int32_t* targets, int32_t* targets_eval);
+// page segmentation (segment.hip; include/aocr.h: aocr_segment_page): word boxes of a pitched gray page by projection profiles
+size_t segment_scratch_bytes(int H, int W, int max_boxes);
+void segment_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_segment_params& p, void* scratch, int max_boxes,
+                  aocr_box* boxes, int32_t* counts);
+// crops (data.hip; aocr_crop_lines): preprocess_lines' scaling of n box rectangles of a pitched page, n = min(n_boxes, count[0]) on the device
+void crop_lines(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_box* boxes, const int32_t* count, int n_boxes,
+                int out_h, int out_w, float* out);
 }  // namespace aocr

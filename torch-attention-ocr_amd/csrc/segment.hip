@@ -1,0 +1,323 @@
+// segment.hip -- page segmentation by projection profiles (include/aocr.h: aocr_segment_page): a gray uint8 page becomes the word boxes
+// that aocr_crop_lines cuts out for the recogniser.  Everything is integer arithmetic except the Otsu scores, which are double precision
+// with every operation rounded on its own: this file is compiled with -ffp-contract=off (Makefile: FLAGS_segment), so the numpy
+// restatement (tests/segment_ref.py) matches exactly.
+//
+// Launches of one call, all on the caller's stream, intermediates in the caller's scratch:
+//   hist_kernel     (Otsu only) one wave per row, 16-byte loads over the aligned middle of the row and byte loads for the unaligned head
+//                   and tail; a 256-bin LDS histogram per wave, flushed with integer global atomics (order-independent: exact).
+//   otsu_kernel     one wave: lane l owns bins 4l..4l+3, int64 prefix sums over lanes, the 255 scores in parallel, then the argmax with
+//                   "larger score, then lower t" (= the first strictly largest of the serial loop).  Otsu only: a fixed threshold is a
+//                   launch argument of the kernels that need it.
+//   rowprof_kernel  one wave per row, the same loads, per-lane byte compares and a wave sum; Otsu's threshold is read from the device.
+//   bands_kernel    one workgroup: text-row flags in LDS -> bands (find_runs below).
+//   colprof_kernel  one thread per column per band: consecutive threads read consecutive bytes, row after row of the band.
+//   words_kernel    one workgroup per band: ink-column flags in LDS -> words (the same find_runs); the first `cap` words of each band are kept.
+//   offsets_kernel  one workgroup: exclusive prefix sum of the bands' word counts; writes counts_dev.
+//   emit_kernel     one wave per written box: finds its band by bisection of the offsets, sums the box's ink from the column profile,
+//                   pads, clamps and stores the box.
+// find_runs turns "flag[i], merge runs closer than gapmin, drop runs shorter than minlen" into three block scans: an element that is set
+// starts a run iff the previous set element is at least gapmin clear elements away (prefix max of set indices), ends one iff the next set
+// element is (suffix min), and the k-th start pairs with the k-th end (prefix sums).  No step depends on launch geometry or on atomics order.
+#include <algorithm>
+#include "ops.h"
+
+namespace aocr {
+
+namespace {
+
+constexpr int SEG_MAX_DIM = 16384;
+constexpr int SEG_THREADS = 1024;             // find_runs: 16 elements per thread cover SEG_MAX_DIM
+constexpr int SEG_WAVES = SEG_THREADS / 64;
+constexpr int SEG_NONE = 1 << 30;
+
+struct SegLayout {                             // byte offsets into scratch_dev
+  size_t hist, hdr, row_ink, bands, wcount, woffset, col, words, total;
+  int max_bands, cap;
+};
+
+SegLayout seg_layout(int H, int W, int max_boxes) {
+  SegLayout l;
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  l.max_bands = (H + 1) / 2;                   // bands are separated by at least one non-text row
+  l.cap = std::min(max_boxes, (W + 1) / 2);    // words of one band that can reach boxes_dev
+  size_t o = 0;
+  l.hist = o;    o = up(o + 256 * sizeof(uint32_t));
+  l.hdr = o;     o = up(o + 4 * sizeof(int32_t));                       // threshold, bands, boxes found
+  l.row_ink = o; o = up(o + (size_t)H * sizeof(int32_t));
+  l.bands = o;   o = up(o + (size_t)l.max_bands * sizeof(uint32_t));    // y0 | y1 << 16
+  l.wcount = o;  o = up(o + (size_t)l.max_bands * sizeof(int32_t));
+  l.woffset = o; o = up(o + (size_t)l.max_bands * sizeof(int32_t));
+  l.col = o;     o = up(o + (size_t)l.max_bands * W * sizeof(uint16_t));
+  l.words = o;   o = up(o + (size_t)l.max_bands * l.cap * sizeof(uint32_t));   // x0 | x1 << 16, unpadded
+  l.total = o;
+  return l;
+}
+
+// f(word, n): the low n bytes of word are n consecutive pixels of the row; every pixel of the row is visited exactly once by the wave
+template <class F> __device__ __forceinline__ void wave_row(const uint8_t* __restrict__ row, int W, int lane, F&& f) {
+  const int head = min(W, (int)((16u - (uint32_t)((uintptr_t)row & 15u)) & 15u));
+  const int nvec = (W - head) >> 4;
+  if (lane < head) f((uint32_t)row[lane], 1);
+  const uint4* v = reinterpret_cast<const uint4*>(row + head);
+  for (int i = lane; i < nvec; i += 64) {
+    const uint4 q = v[i];
+    f(q.x, 4); f(q.y, 4); f(q.z, 4); f(q.w, 4);
+  }
+  const int t = head + (nvec << 4) + lane;     // the tail is shorter than 16 bytes
+  if (t < W) f((uint32_t)row[t], 1);
+}
+
+__device__ __forceinline__ int ink_bytes(uint32_t w, int n, int thr, int light) {
+  int c = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int v = (int)((w >> (8 * j)) & 0xffu);
+    if (j < n) c += light ? (v > thr) : (v <= thr);
+  }
+  return c;
+}
+
+__global__ __launch_bounds__(256) void hist_kernel(const uint8_t* __restrict__ page, int64_t pitch, int H, int W, uint32_t* __restrict__ hist) {
+  __shared__ uint32_t sh[4][256];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int i = threadIdx.x; i < 4 * 256; i += 256) (&sh[0][0])[i] = 0;
+  __syncthreads();
+  uint32_t* h = sh[wave];
+  for (int y = blockIdx.x * 4 + wave; y < H; y += gridDim.x * 4) {
+    wave_row(page + (int64_t)y * pitch, W, lane, [&](uint32_t w, int n) {
+      const uint32_t b0 = w & 0xffu;
+      if (n == 1) { atomicAdd(&h[b0], 1u); return; }
+      if (w == b0 * 0x01010101u) { atomicAdd(&h[b0], 4u); return; }      // paper: four equal pixels, one add
+      atomicAdd(&h[b0], 1u); atomicAdd(&h[(w >> 8) & 0xffu], 1u); atomicAdd(&h[(w >> 16) & 0xffu], 1u); atomicAdd(&h[w >> 24], 1u);
+    });
+  }
+  __syncthreads();
+  const uint32_t s = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+  if (s) atomicAdd(&hist[threadIdx.x], s);
+}
+
+__global__ __launch_bounds__(64) void otsu_kernel(const uint32_t* __restrict__ hist, int32_t* __restrict__ hdr) {
+  const int lane = threadIdx.x;
+  long long h[4], ln = 0, ls = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { h[k] = hist[4 * lane + k]; ln += h[k]; ls += (long long)(4 * lane + k) * h[k]; }
+  long long pn = ln, ps = ls;                                               // inclusive prefix sums over lanes
+  for (int d = 1; d < 64; d <<= 1) {
+    const long long a = __shfl_up(pn, d), b = __shfl_up(ps, d);
+    if (lane >= d) { pn += a; ps += b; }
+  }
+  const long long N = __shfl(pn, 63), S = __shfl(ps, 63);
+  long long n0 = pn - ln, s0 = ps - ls;
+  double best = -1.0; int bt = -1;                                          // scores are >= 0
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int t = 4 * lane + k;
+    n0 += h[k]; s0 += (long long)t * h[k];
+    const long long n1 = N - n0;
+    if (t <= 254 && n0 > 0 && n1 > 0) {
+      const double d = (double)s0 * (double)n1 - (double)(S - s0) * (double)n0;
+      const double score = (d * d) / ((double)n0 * (double)n1);
+      if (score > best) { best = score; bt = t; }
+    }
+  }
+  for (int d = 32; d >= 1; d >>= 1) {
+    const double ob = __shfl_xor(best, d); const int ot = __shfl_xor(bt, d);
+    if (ob > best || (ob == best && ot < bt)) { best = ob; bt = ot; }
+  }
+  if (lane == 0) hdr[0] = bt;                                               // -1: one gray value only, no ink
+}
+
+__global__ __launch_bounds__(256) void rowprof_kernel(const uint8_t* __restrict__ page, int64_t pitch, int H, int W, int light, int fixed,
+                                                      const int32_t* __restrict__ hdr, int32_t* __restrict__ row_ink) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int thr = fixed >= 0 ? fixed : hdr[0];           // a fixed threshold is a launch argument; Otsu's was written by otsu_kernel just before
+  for (int y = blockIdx.x * 4 + wave; y < H; y += gridDim.x * 4) {
+    int c = 0;
+    if (thr >= 0) wave_row(page + (int64_t)y * pitch, W, lane, [&](uint32_t w, int n) { c += ink_bytes(w, n, thr, light); });
+    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
+    if (lane == 0) row_ink[y] = c;
+  }
+}
+
+struct RunsShared {
+  uint8_t flag[SEG_MAX_DIM];
+  uint16_t s[SEG_MAX_DIM / 2], e[SEG_MAX_DIM / 2];     // runs start at least two elements apart
+  int wtot[SEG_WAVES];
+};
+
+// exclusive scan of one value per thread over the workgroup (REV: from the last thread down); op commutative and associative
+template <bool REV, class Op> __device__ __forceinline__ int block_scan_excl(int v, int ident, Op op, int* wtot, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int inc = v;
+  for (int d = 1; d < 64; d <<= 1) {
+    const int o = REV ? __shfl_down(inc, d) : __shfl_up(inc, d);
+    if (REV ? (lane + d < 64) : (lane >= d)) inc = op(o, inc);
+  }
+  int ex = REV ? __shfl_down(inc, 1) : __shfl_up(inc, 1);
+  if (lane == (REV ? 63 : 0)) ex = ident;
+  __syncthreads();                                       // the previous scan's readers are done with wtot
+  if (lane == (REV ? 0 : 63)) wtot[wave] = inc;
+  __syncthreads();
+  int acc = ident, tot = ident;
+  for (int w = 0; w < SEG_WAVES; ++w) {
+    const int x = wtot[w];
+    tot = op(tot, x);
+    if (REV ? (w > wave) : (w < wave)) acc = op(acc, x);
+  }
+  *total = tot;
+  return op(acc, ex);
+}
+
+// sh.flag[0..n) is staged and a barrier has passed.  Set elements form runs; runs with fewer than gapmin clear elements between them are one
+// interval; intervals shorter than minlen are dropped; emit(k, start, end) is called for the k-th survivor, in order.  Returns their number.
+// Called by all SEG_THREADS threads.
+template <class Emit> __device__ __forceinline__ int find_runs(RunsShared& sh, int n, int gapmin, int minlen, Emit&& emit) {
+  const int tid = threadIdx.x;
+  const int ch = (n + SEG_THREADS - 1) / SEG_THREADS;    // <= 16 consecutive elements per thread
+  const int lo = min(n, tid * ch), hi = min(n, lo + ch);
+  auto imax = [](int a, int b) { return a > b ? a : b; };
+  auto imin = [](int a, int b) { return a < b ? a : b; };
+  auto iadd = [](int a, int b) { return a + b; };
+  int last = -1, first = SEG_NONE;
+  for (int i = lo; i < hi; ++i) if (sh.flag[i]) { if (first == SEG_NONE) first = i; last = i; }
+  int unused, K;
+  int p = block_scan_excl<false>(last, -1, imax, sh.wtot, &unused);         // the last set element before this thread's chunk
+  int q = block_scan_excl<true>(first, SEG_NONE, imin, sh.wtot, &unused);   // the first one after it
+  uint32_t smask = 0, emask = 0;
+  for (int i = lo; i < hi; ++i) if (sh.flag[i]) { if (p < 0 || i - p - 1 >= gapmin) smask |= 1u << (i - lo); p = i; }
+  for (int i = hi - 1; i >= lo; --i) if (sh.flag[i]) { if (q == SEG_NONE || q - i - 1 >= gapmin) emask |= 1u << (i - lo); q = i; }
+  int si = block_scan_excl<false>(__popc(smask), 0, iadd, sh.wtot, &K);
+  int ei = block_scan_excl<false>(__popc(emask), 0, iadd, sh.wtot, &unused);
+  for (; smask; smask &= smask - 1) sh.s[si++] = (uint16_t)(lo + __ffs(smask) - 1);
+  for (; emask; emask &= emask - 1) sh.e[ei++] = (uint16_t)(lo + __ffs(emask));          // exclusive end
+  __syncthreads();
+  const int ch2 = (K + SEG_THREADS - 1) / SEG_THREADS;
+  const int lo2 = min(K, tid * ch2), hi2 = min(K, lo2 + ch2);
+  int keep = 0;
+  for (int k = lo2; k < hi2; ++k) keep += ((int)sh.e[k] - (int)sh.s[k] >= minlen);
+  int total;
+  int o = block_scan_excl<false>(keep, 0, iadd, sh.wtot, &total);
+  for (int k = lo2; k < hi2; ++k) if ((int)sh.e[k] - (int)sh.s[k] >= minlen) emit(o++, (int)sh.s[k], (int)sh.e[k]);
+  return total;
+}
+
+__global__ __launch_bounds__(SEG_THREADS) void bands_kernel(const int32_t* __restrict__ row_ink, int H, int min_row_ink, int merge_gap,
+                                                            int min_line_h, uint32_t* __restrict__ bands, int32_t* __restrict__ hdr) {
+  __shared__ RunsShared sh;
+  for (int y = threadIdx.x; y < H; y += SEG_THREADS) sh.flag[y] = row_ink[y] >= min_row_ink;
+  __syncthreads();
+  const int n = find_runs(sh, H, merge_gap + 1, min_line_h, [&](int k, int y0, int y1) { bands[k] = (uint32_t)y0 | ((uint32_t)y1 << 16); });
+  if (threadIdx.x == 0) hdr[1] = n;
+}
+
+__global__ __launch_bounds__(256) void colprof_kernel(const uint8_t* __restrict__ page, int64_t pitch, int W, int light, int fixed, int max_bands,
+                                                      const int32_t* __restrict__ hdr, const uint32_t* __restrict__ bands,
+                                                      uint16_t* __restrict__ col) {
+  const int thr = fixed >= 0 ? fixed : hdr[0], nb = min(hdr[1], max_bands);
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  if (x >= W) return;
+  for (int b = blockIdx.y; b < nb; b += gridDim.y) {
+    const uint32_t yy = bands[b];
+    const int y0 = (int)(yy & 0xffffu), y1 = (int)(yy >> 16);
+    const uint8_t* p = page + (int64_t)y0 * pitch + x;
+    int c = 0;
+    for (int y = y0; y < y1; ++y, p += pitch) { const int v = *p; c += light ? (v > thr) : (v <= thr); }
+    col[(size_t)b * W + x] = (uint16_t)c;                 // <= SEG_MAX_DIM
+  }
+}
+
+__global__ __launch_bounds__(SEG_THREADS) void words_kernel(const uint16_t* __restrict__ col, int W, int word_gap, int min_word_w, int max_bands,
+                                                            int cap, const int32_t* __restrict__ hdr, uint32_t* __restrict__ words,
+                                                            int32_t* __restrict__ wcount) {
+  __shared__ RunsShared sh;
+  const int nb = min(hdr[1], max_bands);
+  const int gapmin = word_gap == 0 ? SEG_NONE : word_gap;                  // 0: nothing splits a band
+  for (int b = blockIdx.x; b < nb; b += gridDim.x) {
+    for (int x = threadIdx.x; x < W; x += SEG_THREADS) sh.flag[x] = col[(size_t)b * W + x] >= 1;
+    __syncthreads();
+    uint32_t* out = words + (size_t)b * cap;
+    const int n = find_runs(sh, W, gapmin, min_word_w, [&](int k, int x0, int x1) { if (k < cap) out[k] = (uint32_t)x0 | ((uint32_t)x1 << 16); });
+    if (threadIdx.x == 0) wcount[b] = n;
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(SEG_THREADS) void offsets_kernel(const int32_t* __restrict__ wcount, int max_bands, int fixed, int32_t* __restrict__ woffset,
+                                                              int32_t* __restrict__ hdr, int32_t* __restrict__ counts) {
+  __shared__ int wtot[SEG_WAVES];
+  const int nb = min(hdr[1], max_bands);
+  const int ch = (nb + SEG_THREADS - 1) / SEG_THREADS;
+  const int lo = min(nb, (int)threadIdx.x * ch), hi = min(nb, lo + ch);
+  int sum = 0;
+  for (int b = lo; b < hi; ++b) sum += wcount[b];
+  int total;
+  int o = block_scan_excl<false>(sum, 0, [](int a, int b) { return a + b; }, wtot, &total);
+  for (int b = lo; b < hi; ++b) { woffset[b] = o; o += wcount[b]; }
+  if (threadIdx.x == 0) { hdr[2] = total; counts[0] = total; counts[1] = nb; counts[2] = fixed >= 0 ? fixed : hdr[0]; counts[3] = 0; }
+}
+
+__global__ __launch_bounds__(256) void emit_kernel(const int32_t* __restrict__ hdr, const uint32_t* __restrict__ bands,
+                                                   const int32_t* __restrict__ woffset, const uint32_t* __restrict__ words,
+                                                   const uint16_t* __restrict__ col, int H, int W, int max_bands, int cap, int pad_x, int pad_y,
+                                                   int max_boxes, aocr_box* __restrict__ boxes) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int nb = min(hdr[1], max_bands);
+  if (i >= min(hdr[2], max_boxes)) return;
+  int lo = 0, hi = nb - 1;                                 // the last band whose offset is <= i (empty bands share their successor's offset)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (woffset[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  const int b = lo, j = i - woffset[b];
+  if (j < 0 || j >= cap) return;                           // cannot happen: j < the band's word count and j <= i < max_boxes
+  const uint32_t xx = words[(size_t)b * cap + j], yy = bands[b];
+  const int x0 = (int)(xx & 0xffffu), x1 = (int)(xx >> 16), y0 = (int)(yy & 0xffffu), y1 = (int)(yy >> 16);
+  int ink = 0;
+  for (int x = x0 + lane; x < x1; x += 64) ink += col[(size_t)b * W + x];
+  for (int d = 32; d >= 1; d >>= 1) ink += __shfl_xor(ink, d);
+  if (lane == 0) {
+    aocr_box bx;
+    bx.x0 = max(0, x0 - pad_x); bx.y0 = max(0, y0 - pad_y); bx.x1 = min(W, x1 + pad_x); bx.y1 = min(H, y1 + pad_y);
+    bx.line = b; bx.ink = ink;
+    boxes[i] = bx;
+  }
+}
+
+}  // namespace
+
+size_t segment_scratch_bytes(int H, int W, int max_boxes) { return seg_layout(H, W, max_boxes).total; }
+
+void segment_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_segment_params& p, void* scratch, int max_boxes,
+                  aocr_box* boxes, int32_t* counts) {
+  const SegLayout l = seg_layout(H, W, max_boxes);
+  char* base = static_cast<char*>(scratch);
+  uint32_t* hist = reinterpret_cast<uint32_t*>(base + l.hist);
+  int32_t* hdr = reinterpret_cast<int32_t*>(base + l.hdr);
+  int32_t* row_ink = reinterpret_cast<int32_t*>(base + l.row_ink);
+  uint32_t* bands = reinterpret_cast<uint32_t*>(base + l.bands);
+  int32_t* wcount = reinterpret_cast<int32_t*>(base + l.wcount);
+  int32_t* woffset = reinterpret_cast<int32_t*>(base + l.woffset);
+  uint16_t* col = reinterpret_cast<uint16_t*>(base + l.col);
+  uint32_t* words = reinterpret_cast<uint32_t*>(base + l.words);
+  const int light = p.light_text ? 1 : 0, fixed = p.threshold;    // >= 0: no histogram, no Otsu launch, hdr[0] unused
+  const int row_blocks = std::min(cdiv(H, 4), 2048);
+  if (p.threshold < 0) {
+    (void)hipMemsetAsync(hist, 0, 256 * sizeof(uint32_t), s);
+    hipLaunchKernelGGL(hist_kernel, dim3(row_blocks), dim3(256), 0, s, page, pitch, H, W, hist);
+    hipLaunchKernelGGL(otsu_kernel, dim3(1), dim3(64), 0, s, hist, hdr);
+  }
+  hipLaunchKernelGGL(rowprof_kernel, dim3(row_blocks), dim3(256), 0, s, page, pitch, H, W, light, fixed, hdr, row_ink);
+  hipLaunchKernelGGL(bands_kernel, dim3(1), dim3(SEG_THREADS), 0, s, row_ink, H, p.min_row_ink,
+                     std::min(p.merge_gap, SEG_MAX_DIM), p.min_line_h, bands, hdr);
+  hipLaunchKernelGGL(colprof_kernel, dim3(cdiv(W, 256), std::min(l.max_bands, 128)), dim3(256), 0, s, page, pitch, W, light, fixed, l.max_bands,
+                     hdr, bands, col);
+  hipLaunchKernelGGL(words_kernel, dim3(std::min(l.max_bands, 128)), dim3(SEG_THREADS), 0, s, col, W, p.word_gap, p.min_word_w, l.max_bands,
+                     l.cap, hdr, words, wcount);
+  hipLaunchKernelGGL(offsets_kernel, dim3(1), dim3(SEG_THREADS), 0, s, wcount, l.max_bands, fixed, woffset, hdr, counts);
+  hipLaunchKernelGGL(emit_kernel, dim3(cdiv(max_boxes, 4)), dim3(256), 0, s, hdr, bands, woffset, words, col, H, W, l.max_bands, l.cap, p.pad_x,
+                     p.pad_y, max_boxes, boxes);
+}
+
+}  // namespace aocr
