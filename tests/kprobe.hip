@@ -1,5 +1,6 @@
-// tests/libkprobe.so: extern "C" wrappers around the host launchers of the bf16-source conv / GEMM paths and of the fused recurrent-step
-// kernels (csrc/ops.h), for tests/test_kernels_bf16_gpu.py and tests/test_step_kernels_bf16_gpu.py.  Test infrastructure: no kernels of its own, not part of the product's C ABI (include/aocr.h).
+// tests/libkprobe.so: extern "C" wrappers around the host launchers of the bf16-source conv / GEMM paths, of the fused recurrent-step
+// kernels and of the attention kernels (csrc/ops.h), for tests/test_kernels_bf16_gpu.py, tests/test_step_kernels_bf16_gpu.py and
+// tests/test_attention_kernels_gpu.py.  Test infrastructure: no kernels of its own, not part of the product's C ABI (include/aocr.h).
 // Every wrapper enqueues on the given stream and returns hipGetLastError().  Pointers to bf16 data are passed as the raw addresses
 // of torch.bfloat16 tensors (the same bit layout as bf16_t).
 #include "ops.h"
@@ -83,6 +84,35 @@ size_t kp_bn_scratch_bytes(int C) { return aocr::bn_scratch_bytes(C); }
 
 int kp_bn_eval_prepare(hipStream_t s, const float* rm, const float* rv, float* save, int C) {
   aocr::bn_eval_prepare(s, rm, rv, save, C);
+  return (int)hipGetLastError();
+}
+
+// ---- the attention launchers (csrc/ops_misc.hip), for tests/test_attention_kernels_gpu.py: the launchers' own signatures (the forward query has ldu = Hd and
+// d q has ldo = Hd inside the launchers; no stride the product cannot pass is added here)
+int kp_attention_forward(hipStream_t s, const float* ctx, const float* q, float* a, float* c, int64_t ldc, int B, int T, int Hd, int ctx_div, void* cb,
+                         int64_t ldcb, const void* ctxb) {
+  aocr::attention_forward(s, ctx, q, a, c, ldc, B, T, Hd, ctx_div, W16(cb), ldcb, H16(ctxb));
+  return (int)hipGetLastError();
+}
+int kp_attention_backward(hipStream_t s, const float* ctx, const float* a, const float* dc, int64_t lddc, float* ds, float* dq, int B, int T, int Hd,
+                          void* dqb, const void* ctxb, const float* cfwd, int64_t ldcf) {
+  aocr::attention_backward(s, ctx, nullptr, a, dc, lddc, ds, dq, B, T, Hd, W16(dqb), H16(ctxb), cfwd, ldcf);
+  return (int)hipGetLastError();
+}
+int kp_attention_forward_dual(hipStream_t s, const float* h_top, int64_t ldh, float* a, float* c, int64_t ldc, int B, int T, int ctx_div, void* cb,
+                              int64_t ldcb, const void* ctxb, const void* ctxab) {
+  aocr::attention_forward_dual(s, h_top, ldh, a, c, ldc, B, T, ctx_div, W16(cb), ldcb, H16(ctxb), H16(ctxab));
+  return (int)hipGetLastError();
+}
+int kp_attention_backward_dual(hipStream_t s, const float* a, const float* dc, int64_t lddc, float* ds, float* dq, void* dqb, float* dh_attn, int B, int T,
+                               const void* ctxb, const void* ctxab) {
+  aocr::attention_backward_dual(s, a, dc, lddc, ds, dq, W16(dqb), dh_attn, B, T, H16(ctxb), H16(ctxab));
+  return (int)hipGetLastError();
+}
+int kp_attention_dual_ok(int T, int Hd, const void* ctxb, const void* ctxab) { return aocr::attention_dual_ok(T, Hd, H16(ctxb), H16(ctxab)) ? 1 : 0; }
+int kp_attention_dctx(hipStream_t s, const float* a_all, const float* ds_all, const float* dc_all, int64_t lddc, const float* q_all, float* dctx, int L, int B,
+                      int T, int Hd) {
+  aocr::attention_dctx(s, a_all, ds_all, dc_all, lddc, q_all, dctx, L, B, T, Hd);
   return (int)hipGetLastError();
 }
 

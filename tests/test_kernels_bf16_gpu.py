@@ -34,7 +34,9 @@ SWITCHES = ("AOCR_FORCE_DMA", "AOCR_HALO8", "AOCR_HALO4_STAGED", "AOCR_NO_HALO",
             "AOCR_WGRAD_DMA_WGS", "AOCR_BN_PARTIAL_OLD", "AOCR_UNPOOL4",
             # the recurrent-step launchers (tests/test_step_kernels_bf16_gpu.py shares this fixture)
             "AOCR_NO_HALF_TILES", "AOCR_HALF_TILES_MAXGRID", "AOCR_NO_STEP_MT2", "AOCR_STEP_MT2_MINK", "AOCR_NO_STEPL", "AOCR_STEPL_MIN_WGS",
-            "AOCR_STEP_WAVES4", "AOCR_STEP_WAVES16", "AOCR_BIG_STEP", "AOCR_BIG_STEP_MIN_ROWS")
+            "AOCR_STEP_WAVES4", "AOCR_STEP_WAVES16", "AOCR_BIG_STEP", "AOCR_BIG_STEP_MIN_ROWS",
+            # the attention launchers (tests/test_attention_kernels_gpu.py shares this fixture)
+            "AOCR_NO_ATTN_BF16", "AOCR_ATTN_NW16", "AOCR_NO_ATTN_BEAM_GROUP", "AOCR_ATTN_BWD_TWO_PASS", "AOCR_NO_CHAIN_CTXA")
 
 _KP = None
 vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
@@ -57,6 +59,12 @@ def kp():
             "kp_grouped_wgrad": [vp, i32, i32] + [vp] * 11 + [vp, sz],
             "kp_bn_relu_forward": [vp] * 9 + [i64, i32, i32, i32, i32],
             "kp_bn_eval_prepare": [vp, vp, vp, vp, i32],
+            "kp_attention_forward": [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, i64, vp],
+            "kp_attention_backward": [vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, vp, vp, vp, i64],
+            "kp_attention_forward_dual": [vp, vp, i64, vp, vp, i64, i32, i32, i32, vp, i64, vp, vp],
+            "kp_attention_backward_dual": [vp, vp, vp, i64, vp, vp, vp, vp, i32, i32, vp, vp],
+            "kp_attention_dual_ok": [i32, i32, vp, vp],
+            "kp_attention_dctx": [vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, i32],
         }
         for n, a in sig.items():
             getattr(lib, n).argtypes = a

@@ -39,7 +39,9 @@ def test_kprobe_symbols_resolve_in_libaocr(tmp_path):
     for name in ("conv_forward", "conv_backward_data", "conv_backward_filter", "conv_weight_shadows", "splitk_reduce", "gemm_hh",
                  "gemm_hh_shadow", "gemm_hh_cat", "grouped_wgrad", "bn_relu_forward",
                  "launch_small_gates_fwd_hh", "launch_small_gates_fwd_h", "launch_small_hh", "launch_small_h", "launch_small_gates_bwd_hh",
-                 "launch_small_gates_bwd_h", "gates_elem_bwd", "big_step_store", "big_step_gates_fwd"):
+                 "launch_small_gates_bwd_h", "gates_elem_bwd", "big_step_store", "big_step_gates_fwd",
+                 "attention_forward", "attention_backward", "attention_forward_dual", "attention_backward_dual", "attention_dual_ok",
+                 "attention_dctx"):
         assert any(f"{len(name)}{name}E" in s for s in wanted), f"the shim does not call aocr::{name}"
     defined = _symbols(LIB, "--defined-only")
     missing = sorted(wanted - defined)
@@ -47,5 +49,7 @@ def test_kprobe_symbols_resolve_in_libaocr(tmp_path):
     exported = _symbols(so, "--defined-only")
     for name in ("kp_conv_forward", "kp_conv_backward_data", "kp_conv_backward_filter", "kp_grouped_wgrad", "kp_gemm_hh_cat",
                  "kp_small_gates_fwd_hh", "kp_small_gates_fwd_h", "kp_small_hh", "kp_small_h", "kp_small_gates_bwd_hh", "kp_small_gates_bwd_h",
-                 "kp_gates_elem_bwd", "kp_big_step_store", "kp_big_step_gates_fwd"):
+                 "kp_gates_elem_bwd", "kp_big_step_store", "kp_big_step_gates_fwd",
+                 "kp_attention_forward", "kp_attention_backward", "kp_attention_forward_dual", "kp_attention_backward_dual",
+                 "kp_attention_dual_ok", "kp_attention_dctx"):
         assert name in exported

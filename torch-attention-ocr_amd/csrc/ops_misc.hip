@@ -1446,47 +1446,66 @@ __global__ __launch_bounds__(512) void attn_bf16_beam_kernel(const bf16_t* __res
 }
 
 constexpr int ATTN_NW = 16;
+// dispatch trace (AOCR_TRACE set, read per call; the format of ops_gemm.hip's lines): "[aocr] <function>: <kernel>[<instantiation>] B T Hd", one stderr line per
+// attention launch, so tests/test_attention_kernels_gpu.py can prove which instantiation a shape reached
+static void attn_trace(const char* fn, const char* kernel, const char* inst, int B, int T, int Hd) {
+  if (getenv("AOCR_TRACE")) fprintf(stderr, "[aocr] %s: %s[%s] %d %d %d\n", fn, kernel, inst, B, T, Hd);
+}
 template <bool BWD>
 static void attn_launch(hipStream_t s, const float* ctx, const float* u, int64_t ldu, const float* a_in, float* p_out, float* o,
                         int64_t ldo, int B, int T, int Hd, int ctx_div, bf16_t* ob, int64_t ldob, const bf16_t* ctxb, const float* cfwd = nullptr, int64_t ldcf = 0) {
   if (getenv("AOCR_ATTN_BWD_TWO_PASS")) cfwd = nullptr;          // A/B: the streamed backward kernel's two-pass form
+  const char* const fn = BWD ? "attention_backward" : "attention_forward";
 #define AOCR_ATTN_BF16(NC, RW, STREAM) do {                                                                                   \
+    attn_trace(fn, "attn_bf16_kernel", !(STREAM) ? #NC "," #RW ",reg,w16" : (!BWD || cfwd) ? #NC "," #RW ",stream,w16,onepass" : #NC "," #RW ",stream,w16,twopass", B, T, Hd); \
     if (64 * 1024 + (size_t)T * 4 > 64 * 1024)                                                                                  \
       (void)hipFuncSetAttribute((const void*)attn_bf16_kernel<BWD, NC, RW, STREAM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)T * 4)); \
     hipLaunchKernelGGL((attn_bf16_kernel<BWD, NC, RW, STREAM>), dim3(B), dim3(1024), (size_t)T * sizeof(float), s, ctxb, u, ldu, a_in, p_out, o, \
                        ldo, T, ctx_div, ob, ldob, (const bf16_t*)nullptr, (float*)nullptr, (int64_t)0, cfwd, ldcf); } while (0)
+  // AOCR_NO_ATTN_BF16=1 (A/B): the fp32-context kernels instead of attn_bf16_kernel / attn_bf16_beam_kernel.  It does NOT cover attn_reg_h512_kernel below, which
+  // a bf16 shadow at (Hd = 512, T <= 64) always reaches (tests/test_attention_kernels_gpu.py records it: no_attn_bf16_h512).
   const bool bf_ok = ctxb && ldu % 4 == 0 && !getenv("AOCR_NO_ATTN_BF16");
   if constexpr (!BWD) {
     // beam decode over a long context: one workgroup per IMAGE (its k hypotheses share every context row that is loaded); k <= 5, rows = images x k
     if (bf_ok && ctx_div > 1 && ctx_div <= 5 && B % ctx_div == 0 && T > 64 && (Hd == 1024 || Hd == 512) && (size_t)ctx_div * T * 4 <= 96 * 1024 && !getenv("AOCR_NO_ATTN_BEAM_GROUP")) {
       const size_t dyn = (size_t)ctx_div * T * sizeof(float);
       if (Hd == 1024) {
+        attn_trace(fn, "attn_bf16_beam_kernel", "2,4,5", B, T, Hd);
         if (dyn + 32 * 1024 > 64 * 1024) (void)hipFuncSetAttribute((const void*)attn_bf16_beam_kernel<2, 4, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         hipLaunchKernelGGL((attn_bf16_beam_kernel<2, 4, 5>), dim3(B / ctx_div), dim3(512), dyn, s, ctxb, u, ldu, p_out, o, ldo, T, ctx_div, ob, ldob);
       } else {
+        attn_trace(fn, "attn_bf16_beam_kernel", "1,8,5", B, T, Hd);
         if (dyn + 16 * 1024 > 64 * 1024) (void)hipFuncSetAttribute((const void*)attn_bf16_beam_kernel<1, 8, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         hipLaunchKernelGGL((attn_bf16_beam_kernel<1, 8, 5>), dim3(B / ctx_div), dim3(512), dyn, s, ctxb, u, ldu, p_out, o, ldo, T, ctx_div, ob, ldob);
       }
       return;
     }
   }
-  if (T <= 64 && Hd == 512 && ctxb && ldu % 4 == 0)
+  if (T <= 64 && Hd == 512 && ctxb && ldu % 4 == 0) {
+    attn_trace(fn, "attn_reg_h512_kernel", "w16", B, T, Hd);
     hipLaunchKernelGGL((attn_reg_h512_kernel<BWD, ATTN_NW>), dim3(B), dim3(64 * ATTN_NW), 0, s, ctxb, u, ldu, a_in, p_out, o, ldo, T, ctx_div, ob, ldob);
+  }
   else if (bf_ok && Hd == 512 && T <= 128) AOCR_ATTN_BF16(1, 8, false);
   else if (bf_ok && Hd == 512 && T <= 256) AOCR_ATTN_BF16(1, 16, false);
   else if (bf_ok && Hd == 512) AOCR_ATTN_BF16(1, 4, true);
-  else if (bf_ok && Hd == 1024 && T <= 32 && !getenv("AOCR_ATTN_NW16"))
+  else if (bf_ok && Hd == 1024 && T <= 32 && !getenv("AOCR_ATTN_NW16")) {
+    attn_trace(fn, "attn_bf16_kernel", "2,4,reg,w8", B, T, Hd);
     hipLaunchKernelGGL((attn_bf16_kernel<BWD, 2, 4, false, 8>), dim3(B), dim3(512), (size_t)T * sizeof(float), s, ctxb, u, ldu, a_in, p_out, o, ldo, T, ctx_div, ob, ldob);
+  }
   else if (bf_ok && Hd == 1024 && T <= 64) AOCR_ATTN_BF16(2, 4, false);
   else if (bf_ok && Hd == 1024 && T <= 128) AOCR_ATTN_BF16(2, 8, false);
   else if (bf_ok && Hd == 1024) AOCR_ATTN_BF16(2, 4, true);
-  else if (T <= 64 && Hd == 512)
+  else if (T <= 64 && Hd == 512) {
+    attn_trace(fn, "attn_reg_kernel", "2,f32", B, T, Hd);
     hipLaunchKernelGGL((attn_reg_kernel<2, BWD, float>), dim3(B), dim3(256), 0, s, ctx, u, ldu, a_in, p_out, o, ldo, T, ctx_div, ob, ldob);
-  else if (T <= 64 && Hd == 256)
+  } else if (T <= 64 && Hd == 256) {
+    attn_trace(fn, "attn_reg_kernel", "1,f32", B, T, Hd);
     hipLaunchKernelGGL((attn_reg_kernel<1, BWD, float>), dim3(B), dim3(256), 0, s, ctx, u, ldu, a_in, p_out, o, ldo, T, ctx_div, ob, ldob);
-  else
+  } else {
+    attn_trace(fn, "attn_core_kernel", "", B, T, Hd);
     hipLaunchKernelGGL((attn_core_kernel<BWD>), dim3(B), dim3(256), (size_t)(T + 8) * sizeof(float), s, ctx, u, ldu, a_in, p_out, o, ldo,
                        T, Hd, ctx_div, ob, ldob);
+  }
 }
 void attention_forward(hipStream_t s, const float* ctx, const float* q, float* a, float* c, int64_t ldc, int B, int T, int Hd,
                        int ctx_div, bf16_t* cb, int64_t ldcb, const bf16_t* ctxb) {
@@ -1502,11 +1521,13 @@ void attention_backward(hipStream_t s, const float* ctx, const float* q, const f
 bool attention_dual_ok(int T, int Hd, const bf16_t* ctxb, const bf16_t* ctxab) { return Hd == 1024 && T <= 64 && ctxb && ctxab && !getenv("AOCR_NO_CHAIN_CTXA"); }
 void attention_forward_dual(hipStream_t s, const float* h_top, int64_t ldh, float* a, float* c, int64_t ldc, int B, int T, int ctx_div, bf16_t* cb, int64_t ldcb,
                             const bf16_t* ctxb, const bf16_t* ctxab) {
+  attn_trace("attention_forward_dual", "attn_bf16_kernel", T <= 32 ? "2,4,reg,w8,dual" : "2,4,reg,w16,dual", B, T, 1024);
   if (T <= 32) hipLaunchKernelGGL((attn_bf16_kernel<false, 2, 4, false, 8, true>), dim3(B), dim3(512), (size_t)T * sizeof(float), s, ctxb, h_top, ldh, nullptr, a, c, ldc, T, ctx_div, cb, ldcb, ctxab, nullptr, (int64_t)0);
   else hipLaunchKernelGGL((attn_bf16_kernel<false, 2, 4, false, 16, true>), dim3(B), dim3(1024), (size_t)T * sizeof(float), s, ctxb, h_top, ldh, nullptr, a, c, ldc, T, ctx_div, cb, ldcb, ctxab, nullptr, (int64_t)0);
 }
 void attention_backward_dual(hipStream_t s, const float* a, const float* dc, int64_t lddc, float* ds, float* dq, bf16_t* dqb, float* dh_attn, int B, int T,
                              const bf16_t* ctxb, const bf16_t* ctxab) {
+  attn_trace("attention_backward_dual", "attn_bf16_kernel", T <= 32 ? "2,4,reg,w8,dual" : "2,4,reg,w16,dual", B, T, 1024);
   if (T <= 32) hipLaunchKernelGGL((attn_bf16_kernel<true, 2, 4, false, 8, true>), dim3(B), dim3(512), (size_t)T * sizeof(float), s, ctxb, dc, lddc, a, ds, dq, (int64_t)1024, T, 1, dqb, (int64_t)1024, ctxab, dh_attn, (int64_t)1024);
   else hipLaunchKernelGGL((attn_bf16_kernel<true, 2, 4, false, 16, true>), dim3(B), dim3(1024), (size_t)T * sizeof(float), s, ctxb, dc, lddc, a, ds, dq, (int64_t)1024, T, 1, dqb, (int64_t)1024, ctxab, dh_attn, (int64_t)1024);
 }
@@ -1559,6 +1580,7 @@ __global__ __launch_bounds__(256) void attn_dctx_kernel(const float* __restrict_
 }
 void attention_dctx(hipStream_t s, const float* a_all, const float* ds_all, const float* dc_all, int64_t lddc, const float* q_all,
                     float* dctx, int L, int B, int T, int Hd) {
+  attn_trace("attention_dctx", "attn_dctx_kernel", "", B, T, Hd);
   hipLaunchKernelGGL(attn_dctx_kernel, dim3((Hd + 63) / 64, B), dim3(256), 0, s, a_all, ds_all, dc_all, lddc, q_all, dctx, L, B, T, Hd);
 }
 
