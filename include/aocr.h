@@ -488,7 +488,8 @@ int aocr_synth_lines(void* stream, const aocr_lexicon* lex, const aocr_glyph_atl
 
 /* ---- page segmentation: from a scanned page to the word crops aocr_recognize reads ---------------------------------------
  * The reference is fed cropped words (90kDICT32px); this finds them on a page by projection profiles and cuts them out, on the device.
- * It assumes roughly horizontal lines in one column: skewed or multi-column pages are out of scope.
+ * It assumes horizontal lines in one column: a skewed page goes through aocr_estimate_skew and aocr_deskew_page (below) first; multi-column
+ * pages are out of scope.
  * page_dev: gray uint8, H rows of W pixels, rows `pitch` bytes apart (pitch >= W); any base address and any pitch, nothing need be aligned.
  * 1 <= H, W <= 16384, H*W <= 2^26, 1 <= max_boxes <= 4096.  Steps, in order:
  *   1 histogram  h[v], 256 bins, of the page (only the Otsu threshold reads it);
@@ -541,6 +542,48 @@ int aocr_segment_page(void* stream, const uint8_t* page_dev, int64_t pitch, int3
 int aocr_crop_lines(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
                     const aocr_box* boxes_dev, const int32_t* count_dev, int32_t n_boxes,
                     int32_t out_h, int32_t out_w, float* out_dev);
+
+/* ---- page deskew: the slope of the text lines, and the shear that removes it, in front of aocr_segment_page ---------------------------
+ * A scan is routinely off by a degree or two, and a skewed line smears its row profile into its neighbours.  aocr_estimate_skew finds the
+ * slope by a sweep of sheared projection profiles, aocr_deskew_page removes it; both are integer arithmetic, specified exactly.  Every >>
+ * is an arithmetic (floor) shift of a signed value; the limits keep every product inside int32.
+ * The page follows the rules of aocr_segment_page: any base address, any pitch >= W, 1 <= H, W <= 16384, H*W <= 2^26.
+ *   ink        the threshold is params.threshold when >= 0, else Otsu's: steps 1-2 of aocr_segment_page, bit for bit;
+ *              ink = (v <= threshold), or (v > threshold) with light_text; an Otsu threshold of -1 (one gray value): nothing is ink;
+ *   strips     columns in groups of 32: b = x >> 5, nb = ceil(W / 32) (the last strip may be narrower); R[b][y] = ink pixels of row y
+ *              inside strip b, 0..32;
+ *   offsets    candidates k = -K..K (K = n_steps), slope_k = k * step_q16 rows per column in Q16;  cx = W >> 1, c_b = 32*b + 16 (also for
+ *              a narrow last strip);  off_k(b) = ((c_b - cx) * slope_k + 32768) >> 16;  D_k = max over b of |off_k(b)|;
+ *   profile    P_k[r] = sum over b of R[b][r + off_k(b)] for r in [-D_k, H + D_k); a term whose row r + off_k(b) is outside [0, H) is 0:
+ *              every ink pixel lands in exactly one r, all candidates see the same total;
+ *   score      score_k = sum over r of P_k[r]^2, an exact unsigned 64-bit integer (at most about 2^43);
+ *   winner     candidates in the order 0, -1, +1, -2, +2, ...: the first with the strictly largest score.  A page without ink, an Otsu
+ *              threshold of -1 or K = 0 give k = 0;
+ *   outputs    skew_dev = [k, k * step_q16, the threshold used, 0];  scores_dev[k + K] = score_k for all 2K+1 candidates when not NULL.
+ * Limits: step_q16 in 1..4096, K in 0..256, K * step_q16 <= 16384 (slope 0.25, 14 degrees).
+ * scratch_dev: aocr_skew_scratch_bytes(H, W, n_steps) bytes, 16-byte aligned, overwritten by the call (0 and an error for bad sizes).
+ * Enqueues only, never synchronises or allocates; the result does not depend on launch geometry, atomics order or run (integer sums
+ * only).  Invalid params or sizes return an error before anything is enqueued. */
+typedef struct aocr_skew_params {
+  int32_t threshold;     /* 0..254: ink = (v <= threshold); -1: Otsu, steps 1-2 of aocr_segment_page, bit for bit */
+  int32_t light_text;    /* 1: ink = (v > threshold) instead */
+  int32_t step_q16;      /* 1..4096: slope difference between neighbouring candidates, rows per column, Q16 */
+  int32_t n_steps;       /* K in 0..256: candidates k = -K..K, slope_k = k*step_q16; K*step_q16 <= 16384 (slope 0.25) */
+} aocr_skew_params;
+
+size_t aocr_skew_scratch_bytes(int32_t H, int32_t W, int32_t n_steps);
+int aocr_estimate_skew(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                       const aocr_skew_params* params, void* scratch_dev, int32_t skew_dev[4], uint64_t* scores_dev);
+
+/* The page with the slope s taken out: a combined vertical and horizontal shear with nearest-neighbour sampling, integers only.
+ *   s = skew_dev[1], read on the device (skew_dev = the output of aocr_estimate_skew: no host read in between), or slope_q16 when skew_dev
+ *   is NULL; clamped to [-16384, 16384] on the device;  cx = W >> 1, cy = H >> 1;
+ *   per output pixel (x, y):  sy = y + (((x - cx) * s + 32768) >> 16),  sx = x - (((y - cy) * s + 32768) >> 16);
+ *   out[y][x] = page[sy][sx] when (sx, sy) is inside the page, else fill (0..255).
+ * s = 0 copies the page bit for bit.  out_dev: H rows of W bytes, out_pitch >= W apart, any alignment; bytes between W and out_pitch are
+ * untouched; it must not overlap the page.  Enqueues only. */
+int aocr_deskew_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                     const int32_t* skew_dev, int32_t slope_q16, int32_t fill, uint8_t* out_dev, int64_t out_pitch);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,15 @@ class SegmentParams(C.Structure):
                          int(pad_x), int(pad_y), 0)
 
 
+class SkewParams(C.Structure):
+    """mirror of `aocr_skew_params` (include/aocr.h): the candidates of `aocr_estimate_skew`, k = -n_steps..n_steps at k * step_q16 / 65536 rows
+    per column.  threshold -1: Otsu.  The defaults sweep +-5.4 degrees in steps of 0.056."""
+    _fields_ = [(n, C.c_int32) for n in ("threshold", "light_text", "step_q16", "n_steps")]
+
+    def __init__(self, threshold=-1, light_text=0, step_q16=64, n_steps=96):
+        super().__init__(int(threshold), int(light_text), int(step_q16), int(n_steps))
+
+
 class Box(C.Structure):
     """mirror of `aocr_box` (include/aocr.h): half-open [x0,x1) x [y0,y1), line number, ink pixels."""
     _fields_ = [(n, C.c_int32) for n in ("x0", "y0", "x1", "y1", "line", "ink")]
@@ -141,6 +150,9 @@ SIGNATURES = {
     "aocr_segment_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
     "aocr_segment_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "aocr_crop_lines": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "aocr_skew_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
+    "aocr_estimate_skew": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "aocr_deskew_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _i32, _i32, _vp, C.c_int64]),
     "aocr_beam_select": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32]),
 }
 

@@ -439,7 +439,7 @@ class Model:
             res.word = [lexicon.words[i] if i >= 0 else None for i in res.word_index.tolist()]
         return res
 
-    def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024):
+    def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None):
         """Read a scanned page: segment it into word boxes (aocr_segment_page), crop them (aocr_crop_lines) and recognise the crops.
         page: a uint8 (H,W) numpy array or tensor (gray; a 3-D array raises ValueError: colour pages are out of scope).  params: an
         `aocr.SegmentParams` (default: Otsu threshold, dark text).  The counts and boxes are read back once (the one sync), then the boxes are
@@ -448,8 +448,14 @@ class Model:
         recognize_device and, with a lexicon, Lexicon.nearest.
         Returns a namespace in reading order (line, then x): boxes (n,4) int32 x0 y0 x1 y1, line (n), ink (n), text, labels (n,max_decoder_l),
         scores (n), widths (n), threshold, n_found, n_lines, truncated (n_found > max_boxes), and word / word_index / word_distance with a
-        lexicon.  A page without boxes gives empty arrays."""
-        from .page import bucket_width, crop_lines_device, segment_page_device
+        lexicon.  A page without boxes gives empty arrays.
+        deskew: None (the default) segments the page as it is.  True or an `aocr.SkewParams` first estimates the slope of the lines
+        (aocr_estimate_skew; True: the default sweep with the threshold and light_text of `params`) and shears it out (aocr_deskew_page, filled
+        with paper: 0 with light_text, else 255), then segments, crops and recognises the deskewed page, all enqueued on the same stream; the
+        skew words come back with the counts (still one sync).  The namespace then also carries skew_steps, skew_slope_q16, skew_deg
+        (atan(slope / 65536) in degrees) and source_corners (n,4,2): the (x, y) of every box's corner pixels on the page as given
+        (aocr.page.source_corners); boxes are in deskewed-page coordinates."""
+        from .page import bucket_width, crop_lines_device, deskew_page_device, estimate_skew_device, segment_page_device, source_corners
         if isinstance(page, np.ndarray):
             if page.ndim != 2 or page.dtype != np.uint8:
                 raise ValueError(f"page must be a uint8 (H, W) array, got {page.dtype} {page.shape}: colour pages are out of scope")
@@ -460,8 +466,18 @@ class Model:
         page = page.to(self.device)
         beam_size = min(beam_size or 1, self.target_vocab_size)
         stream = self._stream()
+        skew_dev = None
+        if deskew is not None and deskew is not False:
+            seg = params if params is not None else _lib.SegmentParams()
+            sp = deskew if isinstance(deskew, _lib.SkewParams) else _lib.SkewParams(threshold=seg.threshold, light_text=seg.light_text)
+            skew_dev = estimate_skew_device(page, sp, stream)
+            page = deskew_page_device(page, skew_dev, 0 if seg.light_text else 255, stream)
         boxes_dev, counts_dev = segment_page_device(page, params, max_boxes, stream)
-        counts = counts_dev.cpu().numpy()
+        if skew_dev is None:
+            counts = counts_dev.cpu().numpy()
+        else:
+            both = torch.cat([counts_dev, skew_dev]).cpu().numpy()
+            counts, skew = both[:4], both[4:]
         n = int(min(counts[0], max_boxes))
         rows = boxes_dev[:n].cpu().numpy()
         if width is not None:
@@ -497,6 +513,10 @@ class Model:
         res = SimpleNamespace(boxes=rows[:, :4].copy(), line=rows[:, 4].copy(), ink=rows[:, 5].copy(), text=text, labels=labels, scores=scores,
                               widths=widths, threshold=int(counts[2]), n_found=int(counts[0]), n_lines=int(counts[1]),
                               truncated=bool(counts[0] > max_boxes))
+        if skew_dev is not None:
+            res.skew_steps, res.skew_slope_q16 = int(skew[0]), int(skew[1])
+            res.skew_deg = math.degrees(math.atan(res.skew_slope_q16 / 65536.0))
+            res.source_corners = source_corners(res.boxes, res.skew_slope_q16, page.shape[0], page.shape[1])
         if lexicon is not None:
             res.word_index, res.word_distance = word_index, word_distance
             res.word = [lexicon.words[i] if i >= 0 else None for i in word_index.tolist()]

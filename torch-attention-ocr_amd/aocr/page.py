@@ -1,14 +1,16 @@
 """Page segmentation on the device: `aocr_segment_page` (word boxes of a gray page by projection profiles) and `aocr_crop_lines` (the boxes
 cut out and scaled like `aocr_preprocess_lines`), the stage in front of `Model.recognize`.  Both calls only enqueue; nothing is read back
-here.  Projection profiles assume roughly horizontal lines in one column: skewed or multi-column pages are out of scope."""
+here.  Projection profiles assume horizontal lines in one column: a skewed page goes through `estimate_skew_device` and `deskew_page_device`
+(`aocr_estimate_skew`, `aocr_deskew_page`: a sweep of sheared profiles, then a shear) first; multi-column pages are out of scope."""
 from __future__ import annotations
 
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 
-from ._lib import Box, SegmentParams, check, lib, ptr
+from ._lib import Box, SegmentParams, SkewParams, check, lib, ptr
 
 IMG_H = 32
 MIN_ASPECT = 0.5
@@ -78,6 +80,58 @@ def crop_lines_device(page_dev, boxes, counts, out_w, out_h=IMG_H, stream=None):
     return out
 
 
+def estimate_skew_device(page_dev, params=None, stream=None, scores=False):
+    """skew (4) int32 device tensor: the winning candidate k, its slope k * step_q16 (rows per column, Q16), the threshold used, 0; with
+    scores=True (skew, scores (2 * n_steps + 1) int64: the score of every candidate, k = -n_steps first).  params: a `SkewParams` (default:
+    Otsu, +-96 steps of 1/1024 row per column).  Enqueues only.  stream: as for `segment_page_device`, the current torch stream."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    params = params if params is not None else SkewParams()
+    dev = page_dev.device
+    need = int(lib.aocr_skew_scratch_bytes(H, W, params.n_steps))
+    if need == 0:
+        check(1, "aocr_skew_scratch_bytes")
+    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    skew = torch.zeros(4, dtype=torch.int32, device=dev)
+    sc = torch.zeros(2 * params.n_steps + 1, dtype=torch.int64, device=dev) if scores else None
+    check(lib.aocr_estimate_skew(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), ptr(skew), ptr(sc)),
+          "aocr_estimate_skew")
+    return (skew, sc) if scores else skew
+
+
+def deskew_page_device(page_dev, skew, fill=255, stream=None):
+    """a new (H, W) uint8 device tensor: the page with the slope taken out by `aocr_deskew_page` (shear, nearest neighbour; `fill` where the
+    source is outside the page).  skew: the device tensor of `estimate_skew_device` (its slope is read on the device: no host sync), or a
+    Python int slope in Q16 rows per column.  Enqueues only.  stream: as for `segment_page_device`."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    dev = page_dev.device
+    skew_dev, slope = None, 0
+    if isinstance(skew, torch.Tensor):
+        assert skew.dtype == torch.int32 and skew.device == dev and skew.numel() >= 2
+        skew_dev = skew.contiguous()
+    else:
+        slope = int(skew)
+    out = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    check(lib.aocr_deskew_page(_stream(stream, dev), ptr(page_dev), pitch, H, W, ptr(skew_dev), slope, int(fill), ptr(out), W), "aocr_deskew_page")
+    return out
+
+
+def source_corners(boxes, slope_q16, H, W):
+    """(n, 4, 2) int64: for every box (x0 y0 x1 y1, half-open, deskewed-page coordinates) the source-page (x, y) of its corner pixels
+    (x0, y0), (x1-1, y0), (x1-1, y1-1), (x0, y1-1) under `aocr_deskew_page`'s mapping with slope_q16 (clamped like the device clamps it).
+    Host numpy; the corners of a box near the rim may lie outside the source page."""
+    b = np.asarray(boxes, np.int64)
+    b = b.reshape(-1, b.shape[-1] if b.ndim > 1 else 4)[:, :4]
+    s = min(max(int(slope_q16), -16384), 16384)
+    cx, cy = int(W) >> 1, int(H) >> 1
+    x = np.stack([b[:, 0], b[:, 2] - 1, b[:, 2] - 1, b[:, 0]], axis=1)
+    y = np.stack([b[:, 1], b[:, 1], b[:, 3] - 1, b[:, 3] - 1], axis=1)
+    sy = y + (((x - cx) * s + 32768) >> 16)
+    sx = x - (((y - cy) * s + 32768) >> 16)
+    return np.stack([sx, sy], axis=2)
+
+
 def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
     """DataGen's width rule for a w x h box, ceil(clamp(w/h, 0.5, max_aspect) * 32), rounded up to a multiple of width_step and capped at
     max_img_w.  max_aspect None: max_img_w / 32."""
@@ -88,4 +142,5 @@ def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
     return min(img_w, int(max_img_w))
 
 
-__all__ = ["SegmentParams", "Box", "segment_page_device", "crop_lines_device", "bucket_width"]
+__all__ = ["SegmentParams", "SkewParams", "Box", "segment_page_device", "crop_lines_device", "estimate_skew_device", "deskew_page_device",
+           "source_corners", "bucket_width"]

@@ -822,4 +822,44 @@ int aocr_crop_lines(void* stream, const uint8_t* page_dev, int64_t pitch, int32_
   return check_launch("aocr_crop_lines");
 }
 
+static int check_skew_params(const aocr_skew_params* p) {
+  REQUIRE(p, "params is NULL");
+  REQUIRE(p->threshold >= -1 && p->threshold <= 254, "threshold=%d: 0..254, or -1 for Otsu", p->threshold);
+  REQUIRE(p->step_q16 >= 1 && p->step_q16 <= 4096, "step_q16=%d: 1..4096", p->step_q16);
+  REQUIRE(p->n_steps >= 0 && p->n_steps <= 256, "n_steps=%d: 0..256", p->n_steps);
+  REQUIRE(p->n_steps * p->step_q16 <= 16384, "n_steps=%d * step_q16=%d exceeds 16384 (slope 0.25)", p->n_steps, p->step_q16);
+  return 0;
+}
+
+size_t aocr_skew_scratch_bytes(int32_t H, int32_t W, int32_t n_steps) {
+  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26) && n_steps >= 0 && n_steps <= 256)) {
+    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26) n_steps=%d (0..256)", H, W, n_steps);
+    return 0;
+  }
+  return skew_scratch_bytes(H, W, n_steps);
+}
+
+int aocr_estimate_skew(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_skew_params* params,
+                       void* scratch_dev, int32_t skew_dev[4], uint64_t* scores_dev) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  if (check_skew_params(params)) return 1;
+  REQUIRE(scratch_dev && skew_dev, "NULL argument");
+  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  REQUIRE(((uintptr_t)scores_dev & 7) == 0, "scores_dev must be 8-byte aligned");
+  estimate_skew((hipStream_t)stream, page_dev, pitch, H, W, *params, scratch_dev, skew_dev, scores_dev);
+  return check_launch("aocr_estimate_skew");
+}
+
+int aocr_deskew_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const int32_t* skew_dev, int32_t slope_q16,
+                     int32_t fill, uint8_t* out_dev, int64_t out_pitch) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(out_dev, "out_dev is NULL");
+  REQUIRE(out_pitch >= W, "out_pitch=%lld is smaller than W=%d", (long long)out_pitch, W);
+  REQUIRE(fill >= 0 && fill <= 255, "fill=%d: 0..255", fill);
+  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W, o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(H - 1) * out_pitch + W;
+  REQUIRE(o1 <= p0 || p1 <= o0, "out_dev overlaps the page");
+  deskew_page((hipStream_t)stream, page_dev, pitch, H, W, skew_dev, slope_q16, fill, out_dev, out_pitch);
+  return check_launch("aocr_deskew_page");
+}
+
 }  // extern "C"

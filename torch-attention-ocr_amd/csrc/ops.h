@@ -360,6 +360,14 @@ void synth_lines(hipStream_t s, const aocr_lexicon& lex, const aocr_glyph_atlas&
 size_t segment_scratch_bytes(int H, int W, int max_boxes);
 void segment_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_segment_params& p, void* scratch, int max_boxes,
                   aocr_box* boxes, int32_t* counts);
+// steps 1-2 of aocr_segment_page with Otsu (segment.hip): memset + histogram + Otsu; hist: 256 words, hdr[0] receives the threshold (-1: none)
+void otsu_threshold(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, uint32_t* hist, int32_t* hdr);
+// page deskew (skew.hip; include/aocr.h: aocr_estimate_skew, aocr_deskew_page): the sheared-profile sweep and the shear that removes the skew
+size_t skew_scratch_bytes(int H, int W, int n_steps);
+void estimate_skew(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_skew_params& p, void* scratch, int32_t* skew,
+                   uint64_t* scores);
+void deskew_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const int32_t* skew, int slope_q16, int fill, uint8_t* out,
+                 int64_t out_pitch);
 // crops (data.hip; aocr_crop_lines): preprocess_lines' scaling of n box rectangles of a pitched page, n = min(n_boxes, count[0]) on the device
 void crop_lines(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_box* boxes, const int32_t* count, int n_boxes,
                 int out_h, int out_w, float* out);

@@ -289,6 +289,13 @@ __global__ __launch_bounds__(256) void emit_kernel(const int32_t* __restrict__ h
 
 size_t segment_scratch_bytes(int H, int W, int max_boxes) { return seg_layout(H, W, max_boxes).total; }
 
+// steps 1-2 with Otsu: the histogram into hist (256 words), the threshold into hdr[0].  aocr_estimate_skew (skew.hip) enqueues the same three
+void otsu_threshold(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, uint32_t* hist, int32_t* hdr) {
+  (void)hipMemsetAsync(hist, 0, 256 * sizeof(uint32_t), s);
+  hipLaunchKernelGGL(hist_kernel, dim3(std::min(cdiv(H, 4), 2048)), dim3(256), 0, s, page, pitch, H, W, hist);
+  hipLaunchKernelGGL(otsu_kernel, dim3(1), dim3(64), 0, s, hist, hdr);
+}
+
 void segment_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_segment_params& p, void* scratch, int max_boxes,
                   aocr_box* boxes, int32_t* counts) {
   const SegLayout l = seg_layout(H, W, max_boxes);
@@ -303,11 +310,7 @@ void segment_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int 
   uint32_t* words = reinterpret_cast<uint32_t*>(base + l.words);
   const int light = p.light_text ? 1 : 0, fixed = p.threshold;    // >= 0: no histogram, no Otsu launch, hdr[0] unused
   const int row_blocks = std::min(cdiv(H, 4), 2048);
-  if (p.threshold < 0) {
-    (void)hipMemsetAsync(hist, 0, 256 * sizeof(uint32_t), s);
-    hipLaunchKernelGGL(hist_kernel, dim3(row_blocks), dim3(256), 0, s, page, pitch, H, W, hist);
-    hipLaunchKernelGGL(otsu_kernel, dim3(1), dim3(64), 0, s, hist, hdr);
-  }
+  if (p.threshold < 0) otsu_threshold(s, page, pitch, H, W, hist, hdr);
   hipLaunchKernelGGL(rowprof_kernel, dim3(row_blocks), dim3(256), 0, s, page, pitch, H, W, light, fixed, hdr, row_ink);
   hipLaunchKernelGGL(bands_kernel, dim3(1), dim3(SEG_THREADS), 0, s, row_ink, H, p.min_row_ink,
                      std::min(p.merge_gap, SEG_MAX_DIM), p.min_line_h, bands, hdr);
