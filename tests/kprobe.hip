@@ -1,6 +1,6 @@
 // tests/libkprobe.so: extern "C" wrappers around the host launchers of the bf16-source conv / GEMM paths, of the fused recurrent-step
-// kernels and of the attention kernels (csrc/ops.h), for tests/test_kernels_bf16_gpu.py, tests/test_step_kernels_bf16_gpu.py and
-// tests/test_attention_kernels_gpu.py.  Test infrastructure: no kernels of its own, not part of the product's C ABI (include/aocr.h).
+// kernels, of the attention kernels and of the BatchNorm / un-pool / conv1 / column-sum kernels (csrc/ops.h), for tests/test_kernels_bf16_gpu.py,
+// tests/test_step_kernels_bf16_gpu.py, tests/test_attention_kernels_gpu.py and tests/test_cnn_elementwise_kernels_gpu.py.  Test infrastructure: no kernels of its own, not part of the product's C ABI (include/aocr.h).
 // Every wrapper enqueues on the given stream and returns hipGetLastError().  Pointers to bf16 data are passed as the raw addresses
 // of torch.bfloat16 tensors (the same bit layout as bf16_t).
 #include "ops.h"
@@ -84,6 +84,65 @@ size_t kp_bn_scratch_bytes(int C) { return aocr::bn_scratch_bytes(C); }
 
 int kp_bn_eval_prepare(hipStream_t s, const float* rm, const float* rv, float* save, int C) {
   aocr::bn_eval_prepare(s, rm, rv, save, C);
+  return (int)hipGetLastError();
+}
+
+// ---- BatchNorm, un-pool, conv1 and the column sums (csrc/ops_misc.hip), for tests/test_cnn_elementwise_kernels_gpu.py: the launchers' full argument lists.
+// sync != 0: a BnSync whose all-reduce is the one-rank identity below (the launcher then takes its synchronised branch: bn_sums_kernel + bn_fwd_stats_kernel /
+// bn_bwd_scale_kernel).  defer != 0: the wrapper owns a ColsumJobs, hands it to the launcher and flushes it on the same stream before it returns.
+static int kp_allreduce_identity(void*, void*, int64_t, int, hipStream_t) { return 0; }
+static const aocr::BnSync kp_sync1 = {kp_allreduce_identity, nullptr};
+
+int kp_bn_relu_forward2(hipStream_t s, const float* x, float* y, const float* w, const float* b, float* rm, float* rv, float* save, void* scratch,
+                        int64_t rows, int C, int training, int update_running, int tb_rows, void* yb, int sync, int stats_chunks, const void* xh) {
+  aocr::bn_relu_forward(s, x, y, w, b, rm, rv, save, scratch, rows, C, training, update_running, tb_rows, W16(yb), sync ? &kp_sync1 : nullptr, stats_chunks,
+                        H16(xh));
+  return (int)hipGetLastError();
+}
+int kp_bn_relu_backward(hipStream_t s, const float* x, const float* y, const float* dA, const float* w, const float* save, float* dx, float* dw, float* db,
+                        void* scratch, int64_t rows, int C, int tb_rows, void* dxb, const void* yb, float* conv_dbias, float* partial, int sync, int defer,
+                        const void* xh, const void* dAh, int sums_chunks) {
+  aocr::ColsumJobs jobs = {};
+  aocr::bn_relu_backward(s, x, y, dA, w, save, dx, dw, db, scratch, rows, C, tb_rows, W16(dxb), H16(yb), conv_dbias, partial, sync ? &kp_sync1 : nullptr,
+                         defer ? &jobs : nullptr, H16(xh), H16(dAh), sums_chunks);
+  if (defer) aocr::colsum_flush(s, jobs);
+  return (int)hipGetLastError();
+}
+int kp_unpool_relu_backward(hipStream_t s, const float* dpooled, const float* pooled, const uint8_t* idx, float* dy, int B, int Ho, int Wo, int C, int pool,
+                            void* dyb, float* dbias, float* partial, const void* pooledb, int defer, const void* dpooled16) {
+  aocr::ColsumJobs jobs = {};
+  aocr::unpool_relu_backward(s, dpooled, pooled, idx, dy, B, Ho, Wo, C, pool, W16(dyb), dbias, partial, H16(pooledb), defer ? &jobs : nullptr, H16(dpooled16));
+  if (defer) aocr::colsum_flush(s, jobs);
+  return (int)hipGetLastError();
+}
+int kp_conv1_forward(hipStream_t s, const float* x, const float* w, const float* bias, float* y, int B, int H, int W, void* yb, uint16_t* route) {
+  aocr::conv1_forward(s, x, w, bias, y, B, H, W, W16(yb), route);
+  return (int)hipGetLastError();
+}
+size_t kp_conv1_route_elems(int B, int H, int W) { return aocr::conv1_route_elems(B, H, W); }
+int kp_conv1_backward(hipStream_t s, const float* x, const float* w, const float* bias, const float* dyp, float* dw, float* db, int B, int H, int W,
+                      float* scratch, int defer, const uint16_t* route) {
+  aocr::ColsumJobs jobs = {};
+  aocr::conv1_backward(s, x, w, bias, dyp, dw, db, B, H, W, scratch, defer ? &jobs : nullptr, route);
+  if (defer) aocr::colsum_flush(s, jobs);
+  return (int)hipGetLastError();
+}
+int kp_colsum_accum(hipStream_t s, const float* A, int64_t ld, int64_t rows, int N, float* out, float* out2) {
+  aocr::colsum_accum(s, A, ld, rows, N, out, out2);
+  return (int)hipGetLastError();
+}
+// n jobs (parallel arrays; out2 entries may be null) deferred in order, then ONE flush.  *dropped = the jobs colsum_defer did not take (its table holds 8).
+int kp_colsum_jobs(hipStream_t s, int n, const float* const* A, const int64_t* ld, const int64_t* rows, const int* N, float* const* out, float* const* out2,
+                   int* dropped) {
+  if (n < 0 || n > 16) return (int)hipErrorInvalidValue;
+  aocr::ColsumJobs jobs = {};
+  *dropped = 0;
+  for (int i = 0; i < n; ++i) {
+    const int before = jobs.n;
+    aocr::colsum_defer(jobs, A[i], ld[i], rows[i], N[i], out[i], out2[i]);
+    if (jobs.n == before) ++*dropped;
+  }
+  aocr::colsum_flush(s, jobs);
   return (int)hipGetLastError();
 }
 

@@ -31,7 +31,7 @@ SWITCHES = ("AOCR_FORCE_DMA", "AOCR_HALO8", "AOCR_HALO4_STAGED", "AOCR_NO_HALO",
             "AOCR_NO_WGRAD_HALO", "AOCR_WGRAD_HALO_RAGGED", "AOCR_NO_WGRAD_ISSUE_MID", "AOCR_WGRAD_ATOMIC", "AOCR_WGRAD_HALO_MINSTEPS",
             "AOCR_HH_NARROW_FULL_ONLY", "AOCR_NO_HH_CAT", "AOCR_NO_WGRAD_DMA_GROUPED", "AOCR_WGRAD_DMA_MINK", "AOCR_DX16", "AOCR_NO_DMA",
             "AOCR_NO_HH_NARROW", "AOCR_NO_NARROW_WIDE", "AOCR_WGRAD_HALO_MINN", "AOCR_BN_Y16", "AOCR_NO_BN_STATS_FUSE", "AOCR_BNB_FUSE",
-            "AOCR_WGRAD_DMA_WGS", "AOCR_BN_PARTIAL_OLD", "AOCR_UNPOOL4",
+            "AOCR_WGRAD_DMA_WGS", "AOCR_BN_PARTIAL_OLD", "AOCR_UNPOOL4", "AOCR_CONV1_SCALAR",
             # the recurrent-step launchers (tests/test_step_kernels_bf16_gpu.py shares this fixture)
             "AOCR_NO_HALF_TILES", "AOCR_HALF_TILES_MAXGRID", "AOCR_NO_STEP_MT2", "AOCR_STEP_MT2_MINK", "AOCR_NO_STEPL", "AOCR_STEPL_MIN_WGS",
             "AOCR_STEP_WAVES4", "AOCR_STEP_WAVES16", "AOCR_BIG_STEP", "AOCR_BIG_STEP_MIN_ROWS",

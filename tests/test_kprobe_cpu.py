@@ -41,7 +41,8 @@ def test_kprobe_symbols_resolve_in_libaocr(tmp_path):
                  "launch_small_gates_fwd_hh", "launch_small_gates_fwd_h", "launch_small_hh", "launch_small_h", "launch_small_gates_bwd_hh",
                  "launch_small_gates_bwd_h", "gates_elem_bwd", "big_step_store", "big_step_gates_fwd",
                  "attention_forward", "attention_backward", "attention_forward_dual", "attention_backward_dual", "attention_dual_ok",
-                 "attention_dctx"):
+                 "attention_dctx", "bn_relu_backward", "unpool_relu_backward", "conv1_forward", "conv1_route_elems", "conv1_backward",
+                 "colsum_accum", "colsum_defer", "colsum_flush"):
         assert any(f"{len(name)}{name}E" in s for s in wanted), f"the shim does not call aocr::{name}"
     defined = _symbols(LIB, "--defined-only")
     missing = sorted(wanted - defined)
@@ -51,5 +52,6 @@ def test_kprobe_symbols_resolve_in_libaocr(tmp_path):
                  "kp_small_gates_fwd_hh", "kp_small_gates_fwd_h", "kp_small_hh", "kp_small_h", "kp_small_gates_bwd_hh", "kp_small_gates_bwd_h",
                  "kp_gates_elem_bwd", "kp_big_step_store", "kp_big_step_gates_fwd",
                  "kp_attention_forward", "kp_attention_backward", "kp_attention_forward_dual", "kp_attention_backward_dual",
-                 "kp_attention_dual_ok", "kp_attention_dctx"):
+                 "kp_attention_dual_ok", "kp_attention_dctx", "kp_bn_relu_forward2", "kp_bn_relu_backward", "kp_unpool_relu_backward",
+                 "kp_conv1_forward", "kp_conv1_route_elems", "kp_conv1_backward", "kp_colsum_accum", "kp_colsum_jobs"):
         assert name in exported

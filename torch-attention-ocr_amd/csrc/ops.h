@@ -137,12 +137,14 @@ struct ColsumJobs;
 void conv1_backward(hipStream_t s, const float* x, const float* w, const float* bias, const float* dyp, float* dw, float* db,
                     int B, int H, int W, float* scratch = nullptr, ColsumJobs* defer = nullptr,
                     const uint16_t* route = nullptr /* conv1_forward's decisions for the SAME x, w, bias; null: re-evaluated here */);
+// scratch (min(ceil(strips / 4), 2048) * 640 floats, strips = B * (H/2) * ceil((W/2) / 32)): one partial row per workgroup, finished by two column sums (else fp32 atomics)
 void unpool_relu_backward(hipStream_t s, const float* dpooled, const float* pooled, const uint8_t* idx, float* dy, int B,
                           int Ho, int Wo, int C, int pool, bf16_t* dyb = nullptr, float* dbias = nullptr,
                           float* partial = nullptr, const bf16_t* pooledb = nullptr, ColsumJobs* defer = nullptr,
                           const bf16_t* dpooled16 = nullptr /* d(pooled) as bf16 instead of fp32 (bf16-mode 8-channel kernel only: conv_backward_data's dx16) */);
 // defer: the column sum that finishes a partial slab is queued (colsum_flush) instead of launched -- the slab must then stay untouched until the flush
-// dbias + partial (>= 2048*C floats scratch): fused bias gradient, dy may then be null; pooledb: bf16 shadow of pooled (mask source)
+// dbias + partial (>= 2048*C floats scratch; min(ceil(windows*C/4 / 256), 2048) * C are written) + dyb: fused bias gradient where 256 % (C/4) == 0, dy may then be null
+// (any other C: dy is required and dbias is left untouched); pooledb: bf16 shadow of pooled (mask source)
 void bf16_to_f32(hipStream_t s, const bf16_t* src, float* dst, int64_t n);
 size_t bn_scratch_bytes(int C);
 // synchronised BatchNorm: sums `count` elements (dtype 1 = fp64) of a device buffer over the data-parallel ranks, on stream s
@@ -150,14 +152,18 @@ struct BnSync { int (*allreduce)(void* ctx, void* buf, int64_t count, int dtype,
 void bn_relu_forward(hipStream_t s, const float* x, float* y, const float* w, const float* b, float* rm, float* rv,
                      float* save, void* scratch, int64_t rows, int C, int training, int update_running, int tb_rows,
                      bf16_t* yb = nullptr, const BnSync* sync = nullptr, int stats_chunks = 0 /* > 0: scratch already holds that many chunks of partial sums (conv_forward's bn_part) */,
-                     const bf16_t* xh = nullptr /* x as bf16 (conv_forward wrote it so: *y_bf16) */);
+                     const bf16_t* xh = nullptr /* x as bf16 (conv_forward wrote it so: *y_bf16), read instead of x by the statistics and the apply pass */);
+// xh (forward and backward) and dAh: where the launcher computes the sums itself (stats_chunks / sums_chunks == 0, training) they are legal only where the
+// 16-byte partial-sum kernel runs -- C / 4 a power of two <= 256 and AOCR_BN_PARTIAL_OLD unset (the generic partial-sum kernel reads fp32 only); with the
+// sums handed over, and in evaluation mode, only the apply kernels read them, for any C % 4 == 0
 void bn_relu_backward(hipStream_t s, const float* x, const float* y, const float* dA, const float* w, const float* save,
                       float* dx, float* dw, float* db, void* scratch, int64_t rows, int C, int tb_rows, bf16_t* dxb = nullptr,
                       const bf16_t* yb = nullptr, float* conv_dbias = nullptr, float* partial = nullptr, const BnSync* sync = nullptr,
                       ColsumJobs* defer = nullptr, const bf16_t* xh = nullptr /* x as bf16 */,
                       const bf16_t* dAh = nullptr /* d A as bf16 instead of fp32 (bn_partial4 path only) */,
                       int sums_chunks = 0 /* > 0: scratch already holds that many chunks of (sum d, sum d xhat) (conv_backward_data's bnb_chunks) */);
-// yb: bf16 shadow of y (ReLU mask source); conv_dbias + partial (>= 4096*256 floats): fused bias gradient of the preceding conv, dx may then be null
+// yb: bf16 shadow of y (ReLU mask source); conv_dbias + partial (min(ceil(rows*C/4 / 256), 2048) * 1024 floats) + dxb: fused bias gradient of the preceding conv
+// where 256 % (C/4) == 0, dx may then be null (any other C: dx is required and conv_dbias is left untouched)
 // ctx_div: rows r share context row r / ctx_div (beam search keeps one context per image, model.lua:373)
 void attention_forward(hipStream_t s, const float* ctx, const float* q, float* a, float* c, int64_t ldc, int B, int T, int Hd,
                        int ctx_div = 1, bf16_t* cb = nullptr, int64_t ldcb = 0, const bf16_t* ctxb = nullptr);

@@ -21,6 +21,16 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// dispatch trace (AOCR_TRACE set, read per call; the format of ops_gemm.hip's lines): "[aocr] <function>: <kernel>[<instantiation>] a b c", one stderr line per
+// launch decision, so the kernel tests can prove which instantiation a shape reached.  a b c: the launch's shape (attention: B T Hd; BatchNorm: rows C tb_rows;
+// un-pool: B*Ho Wo C; conv1: B H W)
+static void launch_trace(const char* fn, const char* kernel, const char* inst, int a, int b, int c) {
+  if (getenv("AOCR_TRACE")) fprintf(stderr, "[aocr] %s: %s[%s] %d %d %d\n", fn, kernel, inst, a, b, c);
+}
+static void chunks_trace(const char* fn, int n, int64_t rows, int C, int tb_rows) {     // the partial sums came from the producing conv: "chunks[n]"
+  char inst[16]; snprintf(inst, sizeof inst, "%d", n);
+  launch_trace(fn, "chunks", inst, (int)rows, C, tb_rows);
+}
 
 // =============================================================================================
 // conv1: cnn.lua:9-15.  x (B,H,W) raw 0..255 -> y (B,H/2,W/2,64) = maxpool2x2(relu(conv3x3((x-128)/128)+b)).
@@ -283,6 +293,7 @@ void conv1_forward(hipStream_t s, const float* x, const float* w, const float* b
   int Hp = H / 2, Wp = W / 2;
   int64_t strips = (int64_t)B * Hp * ((Wp + C1S - 1) / C1S);
   int blocks = (int)std::min<int64_t>((strips + 3) / 4, 4096);
+  launch_trace("conv1_forward", "conv1_fwd_kernel", route ? "1" : "0", B, H, W);
   if (route) hipLaunchKernelGGL(conv1_fwd_kernel<true>, dim3(blocks), dim3(256), 0, s, x, w, bias, y, yb, B, H, W, Hp, Wp, route);
   else hipLaunchKernelGGL(conv1_fwd_kernel<false>, dim3(blocks), dim3(256), 0, s, x, w, bias, y, yb, B, H, W, Hp, Wp, route);
 }
@@ -290,12 +301,19 @@ void conv1_backward(hipStream_t s, const float* x, const float* w, const float* 
                     int B, int H, int W, float* scratch, ColsumJobs* defer, const uint16_t* route) {
   int Hp = H / 2, Wp = W / 2;
   int64_t strips = (int64_t)B * Hp * ((Wp + C1S - 1) / C1S);
-  // with a scratch slab (>= 4096*640 floats) every workgroup writes its partial sums and two column sums finish the job:
-  // no contended global atomics, more workgroups
+  // with a scratch slab (blocks * 640 floats, at most 2048*640) every workgroup writes its partial sums and two column sums finish
+  // the job: no contended global atomics, more workgroups
   int blocks = (int)std::min<int64_t>((strips + 3) / 4, scratch ? 2048 : 1024);
-  if (getenv("AOCR_CONV1_SCALAR")) hipLaunchKernelGGL(conv1_bwd_kernel, dim3(blocks), dim3(256), 0, s, x, w, bias, dyp, dw, db, B, H, W, Hp, Wp, scratch);
-  else if (route) hipLaunchKernelGGL(conv1_bwd_pk_kernel<true>, dim3(blocks), dim3(256), 0, s, x, w, bias, dyp, dw, db, B, H, W, Hp, Wp, scratch, route);
-  else hipLaunchKernelGGL(conv1_bwd_pk_kernel<false>, dim3(blocks), dim3(256), 0, s, x, w, bias, dyp, dw, db, B, H, W, Hp, Wp, scratch, route);
+  if (getenv("AOCR_CONV1_SCALAR")) {
+    launch_trace("conv1_backward", "conv1_bwd_kernel", "", B, H, W);
+    hipLaunchKernelGGL(conv1_bwd_kernel, dim3(blocks), dim3(256), 0, s, x, w, bias, dyp, dw, db, B, H, W, Hp, Wp, scratch);
+  } else if (route) {
+    launch_trace("conv1_backward", "conv1_bwd_pk_kernel", "1", B, H, W);
+    hipLaunchKernelGGL(conv1_bwd_pk_kernel<true>, dim3(blocks), dim3(256), 0, s, x, w, bias, dyp, dw, db, B, H, W, Hp, Wp, scratch, route);
+  } else {
+    launch_trace("conv1_backward", "conv1_bwd_pk_kernel", "0", B, H, W);
+    hipLaunchKernelGGL(conv1_bwd_pk_kernel<false>, dim3(blocks), dim3(256), 0, s, x, w, bias, dyp, dw, db, B, H, W, Hp, Wp, scratch, route);
+  }
   if (scratch && defer) { colsum_defer(*defer, scratch, 640, blocks, 576, dw); colsum_defer(*defer, scratch + 576, 640, blocks, 64, db); }
   else if (scratch) {
     colsum_accum(s, scratch, 640, blocks, 576, dw);
@@ -527,16 +545,19 @@ void unpool_relu_backward(hipStream_t s, const float* dpooled, const float* pool
     int blocks = (int)std::min<int64_t>((total + 255) / 256, 2048);             // grid stride 2048*256 is a multiple of every C4 | 256
     if (!dy && pooledb && C % 8 == 0 && 256 % (C / 8) == 0 && !getenv("AOCR_UNPOOL4")) {
       const int64_t total8 = total / 2; const int blocks8 = (int)std::min<int64_t>((total8 + 255) / 256, 2048);
+      launch_trace("unpool_relu_backward", "unpool8_kernel", "", B * Ho, Wo, C);
       hipLaunchKernelGGL(unpool8_kernel, dim3(blocks8), dim3(256), 0, s, dpooled, idx, dyb, partial, B, Ho, Wo, C, pool, Hp, Wp, pooledb, dpooled16);
       if (defer) colsum_defer(*defer, partial, C, blocks8, C, dbias); else colsum_accum(s, partial, C, blocks8, C, dbias);
       return;
     }
+    launch_trace("unpool_relu_backward", "unpool_kernel", dy ? "1,1" : "0,1", B * Ho, Wo, C);
     if (dy) hipLaunchKernelGGL((unpool_kernel<true, true>), dim3(blocks), dim3(256), 0, s, dpooled, pooled, idx, dy, dyb, partial, B, Ho, Wo, C, pool, Hp, Wp, pooledb);
     else    hipLaunchKernelGGL((unpool_kernel<false, true>), dim3(blocks), dim3(256), 0, s, dpooled, pooled, idx, dy, dyb, partial, B, Ho, Wo, C, pool, Hp, Wp, pooledb);
     if (defer) colsum_defer(*defer, partial, C, blocks, C, dbias); else colsum_accum(s, partial, C, blocks, C, dbias);
     return;
   }
   int blocks = (int)std::min<int64_t>((total + 255) / 256, 16384);
+  launch_trace("unpool_relu_backward", "unpool_kernel", "1,0", B * Ho, Wo, C);
   hipLaunchKernelGGL((unpool_kernel<true, false>), dim3(blocks), dim3(256), 0, s, dpooled, pooled, idx, dy, dyb, nullptr, B, Ho, Wo, C, pool, Hp, Wp, pooledb);
 }
 
@@ -812,11 +833,15 @@ void bn_relu_forward(hipStream_t s, const float* x, float* y, const float* w, co
   if (training) {
     double* part = (double*)scratch;
     int nchunk = (int)std::min<int64_t>(BN_CHUNKS, (rows + 63) / 64);
-    if (stats_chunks > 0 && stats_chunks <= BN_CHUNKS) nchunk = stats_chunks;      // the producing conv's epilogue wrote the partial sums (EpConv::bn_part)
-    else
-    if (bn_partial4_ok(C)) hipLaunchKernelGGL(bn_partial4_kernel<0>, dim3(nchunk), dim3(1024), 0, s, x, nullptr, nullptr, nullptr, part, rows, C, 0, 0, nullptr);
-    else hipLaunchKernelGGL(bn_partial_kernel, dim3(cdiv(C, 64), nchunk), dim3(256), 0, s, x, nullptr, nullptr, nullptr, part, rows,
-                            C, 0, 0, 0, nullptr);
+    if (stats_chunks > 0 && stats_chunks <= BN_CHUNKS) { nchunk = stats_chunks; chunks_trace("bn_relu_forward", nchunk, rows, C, tb_rows); }   // the producing conv's epilogue wrote the partial sums (EpConv::bn_part)
+    else if (bn_partial4_ok(C)) {                         // xh: the statistics are those of the map the apply pass reads
+      launch_trace("bn_relu_forward", "bn_partial4_kernel", "0", (int)rows, C, tb_rows);
+      hipLaunchKernelGGL(bn_partial4_kernel<0>, dim3(nchunk), dim3(1024), 0, s, x, nullptr, nullptr, nullptr, part, rows, C, 0, 0, nullptr, xh);
+    } else {
+      launch_trace("bn_relu_forward", "bn_partial_kernel", "0", (int)rows, C, tb_rows);
+      hipLaunchKernelGGL(bn_partial_kernel, dim3(cdiv(C, 64), nchunk), dim3(256), 0, s, x, nullptr, nullptr, nullptr, part, rows,
+                         C, 0, 0, 0, nullptr);
+    }
     if (sync) {                                           // statistics of the GLOBAL batch: (sum x, sum x^2, rows) summed over the ranks
       double* fin = part + (size_t)BN_CHUNKS * C * 2;
       hipLaunchKernelGGL(bn_sums_kernel, dim3(cdiv(C, 16)), dim3(256), 0, s, part, nchunk, rows, C, fin, nullptr, nullptr);
@@ -839,10 +864,14 @@ void bn_relu_backward(hipStream_t s, const float* x, const float* y, const float
   double* part = (double*)scratch;
   double* fin = part + (size_t)BN_CHUNKS * C * 2;
   int nchunk = (int)std::min<int64_t>(BN_CHUNKS, (rows + 63) / 64);
-  if (sums_chunks > 0 && sums_chunks <= BN_CHUNKS) nchunk = sums_chunks;       // the producing data gradient's epilogue wrote the partial sums (EpStore::bnb_part)
-  else
-  if (bn_partial4_ok(C)) hipLaunchKernelGGL(bn_partial4_kernel<1>, dim3(nchunk), dim3(1024), 0, s, x, y, dA, save, part, rows, C, tb_rows, T, yb, xh, dAh);
-  else hipLaunchKernelGGL(bn_partial_kernel, dim3(cdiv(C, 64), nchunk), dim3(256), 0, s, x, y, dA, save, part, rows, C, 1, tb_rows, T, yb);
+  if (sums_chunks > 0 && sums_chunks <= BN_CHUNKS) { nchunk = sums_chunks; chunks_trace("bn_relu_backward", nchunk, rows, C, tb_rows); }   // the producing data gradient's epilogue wrote the partial sums (EpStore::bnb_part)
+  else if (bn_partial4_ok(C)) {
+    launch_trace("bn_relu_backward", "bn_partial4_kernel", "1", (int)rows, C, tb_rows);
+    hipLaunchKernelGGL(bn_partial4_kernel<1>, dim3(nchunk), dim3(1024), 0, s, x, y, dA, save, part, rows, C, tb_rows, T, yb, xh, dAh);
+  } else {
+    launch_trace("bn_relu_backward", "bn_partial_kernel", "1", (int)rows, C, tb_rows);
+    hipLaunchKernelGGL(bn_partial_kernel, dim3(cdiv(C, 64), nchunk), dim3(256), 0, s, x, y, dA, save, part, rows, C, 1, tb_rows, T, yb);
+  }
   if (sync) {                                             // mean(dy), mean(dy * xhat) over the GLOBAL batch
     hipLaunchKernelGGL(bn_sums_kernel, dim3(cdiv(C, 16)), dim3(256), 0, s, part, nchunk, rows, C, fin, dw, db);
     sync->allreduce(sync->ctx, fin, 2 * C + 1, 1, s);
@@ -856,11 +885,13 @@ void bn_relu_backward(hipStream_t s, const float* x, const float* y, const float
     // the grid stride (blocks * 256 quads) is a multiple of C4, so a thread keeps its channel quad: the flat partial slab
     // [blocks * 256][4] is a [blocks * 256 / C4][C] matrix whose column sums are the bias gradient
     int fb = (int)std::min<int64_t>((total + 255) / 256, 2048);
+    launch_trace("bn_relu_backward", "bn_bwd_apply_kernel", dx ? "1,1" : "0,1", (int)rows, C, tb_rows);
     if (dx) hipLaunchKernelGGL((bn_bwd_apply_kernel<true, true>), dim3(fb), dim3(256), 0, s, x, y, dA, w, save, fin, dx, rows, C, tb_rows, T, dxb, yb, partial, xh, dAh);
     else    hipLaunchKernelGGL((bn_bwd_apply_kernel<false, true>), dim3(fb), dim3(256), 0, s, x, y, dA, w, save, fin, dx, rows, C, tb_rows, T, dxb, yb, partial, xh, dAh);
     if (defer) colsum_defer(*defer, partial, C, (int64_t)fb * 256 / C4, C, conv_dbias); else colsum_accum(s, partial, C, (int64_t)fb * 256 / C4, C, conv_dbias);
     return;
   }
+  launch_trace("bn_relu_backward", "bn_bwd_apply_kernel", "1,0", (int)rows, C, tb_rows);
   hipLaunchKernelGGL((bn_bwd_apply_kernel<true, false>), dim3(blocks), dim3(256), 0, s, x, y, dA, w, save, fin, dx, rows, C, tb_rows, T, dxb, yb, nullptr, xh, dAh);
 }
 
@@ -1446,18 +1477,14 @@ __global__ __launch_bounds__(512) void attn_bf16_beam_kernel(const bf16_t* __res
 }
 
 constexpr int ATTN_NW = 16;
-// dispatch trace (AOCR_TRACE set, read per call; the format of ops_gemm.hip's lines): "[aocr] <function>: <kernel>[<instantiation>] B T Hd", one stderr line per
-// attention launch, so tests/test_attention_kernels_gpu.py can prove which instantiation a shape reached
-static void attn_trace(const char* fn, const char* kernel, const char* inst, int B, int T, int Hd) {
-  if (getenv("AOCR_TRACE")) fprintf(stderr, "[aocr] %s: %s[%s] %d %d %d\n", fn, kernel, inst, B, T, Hd);
-}
+// every attention launch prints its launch_trace line ("... B T Hd"): tests/test_attention_kernels_gpu.py proves from it which instantiation a shape reached
 template <bool BWD>
 static void attn_launch(hipStream_t s, const float* ctx, const float* u, int64_t ldu, const float* a_in, float* p_out, float* o,
                         int64_t ldo, int B, int T, int Hd, int ctx_div, bf16_t* ob, int64_t ldob, const bf16_t* ctxb, const float* cfwd = nullptr, int64_t ldcf = 0) {
   if (getenv("AOCR_ATTN_BWD_TWO_PASS")) cfwd = nullptr;          // A/B: the streamed backward kernel's two-pass form
   const char* const fn = BWD ? "attention_backward" : "attention_forward";
 #define AOCR_ATTN_BF16(NC, RW, STREAM) do {                                                                                   \
-    attn_trace(fn, "attn_bf16_kernel", !(STREAM) ? #NC "," #RW ",reg,w16" : (!BWD || cfwd) ? #NC "," #RW ",stream,w16,onepass" : #NC "," #RW ",stream,w16,twopass", B, T, Hd); \
+    launch_trace(fn, "attn_bf16_kernel", !(STREAM) ? #NC "," #RW ",reg,w16" : (!BWD || cfwd) ? #NC "," #RW ",stream,w16,onepass" : #NC "," #RW ",stream,w16,twopass", B, T, Hd); \
     if (64 * 1024 + (size_t)T * 4 > 64 * 1024)                                                                                  \
       (void)hipFuncSetAttribute((const void*)attn_bf16_kernel<BWD, NC, RW, STREAM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)T * 4)); \
     hipLaunchKernelGGL((attn_bf16_kernel<BWD, NC, RW, STREAM>), dim3(B), dim3(1024), (size_t)T * sizeof(float), s, ctxb, u, ldu, a_in, p_out, o, \
@@ -1470,11 +1497,11 @@ static void attn_launch(hipStream_t s, const float* ctx, const float* u, int64_t
     if (bf_ok && ctx_div > 1 && ctx_div <= 5 && B % ctx_div == 0 && T > 64 && (Hd == 1024 || Hd == 512) && (size_t)ctx_div * T * 4 <= 96 * 1024 && !getenv("AOCR_NO_ATTN_BEAM_GROUP")) {
       const size_t dyn = (size_t)ctx_div * T * sizeof(float);
       if (Hd == 1024) {
-        attn_trace(fn, "attn_bf16_beam_kernel", "2,4,5", B, T, Hd);
+        launch_trace(fn, "attn_bf16_beam_kernel", "2,4,5", B, T, Hd);
         if (dyn + 32 * 1024 > 64 * 1024) (void)hipFuncSetAttribute((const void*)attn_bf16_beam_kernel<2, 4, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         hipLaunchKernelGGL((attn_bf16_beam_kernel<2, 4, 5>), dim3(B / ctx_div), dim3(512), dyn, s, ctxb, u, ldu, p_out, o, ldo, T, ctx_div, ob, ldob);
       } else {
-        attn_trace(fn, "attn_bf16_beam_kernel", "1,8,5", B, T, Hd);
+        launch_trace(fn, "attn_bf16_beam_kernel", "1,8,5", B, T, Hd);
         if (dyn + 16 * 1024 > 64 * 1024) (void)hipFuncSetAttribute((const void*)attn_bf16_beam_kernel<1, 8, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         hipLaunchKernelGGL((attn_bf16_beam_kernel<1, 8, 5>), dim3(B / ctx_div), dim3(512), dyn, s, ctxb, u, ldu, p_out, o, ldo, T, ctx_div, ob, ldob);
       }
@@ -1482,27 +1509,27 @@ static void attn_launch(hipStream_t s, const float* ctx, const float* u, int64_t
     }
   }
   if (T <= 64 && Hd == 512 && ctxb && ldu % 4 == 0) {
-    attn_trace(fn, "attn_reg_h512_kernel", "w16", B, T, Hd);
+    launch_trace(fn, "attn_reg_h512_kernel", "w16", B, T, Hd);
     hipLaunchKernelGGL((attn_reg_h512_kernel<BWD, ATTN_NW>), dim3(B), dim3(64 * ATTN_NW), 0, s, ctxb, u, ldu, a_in, p_out, o, ldo, T, ctx_div, ob, ldob);
   }
   else if (bf_ok && Hd == 512 && T <= 128) AOCR_ATTN_BF16(1, 8, false);
   else if (bf_ok && Hd == 512 && T <= 256) AOCR_ATTN_BF16(1, 16, false);
   else if (bf_ok && Hd == 512) AOCR_ATTN_BF16(1, 4, true);
   else if (bf_ok && Hd == 1024 && T <= 32 && !getenv("AOCR_ATTN_NW16")) {
-    attn_trace(fn, "attn_bf16_kernel", "2,4,reg,w8", B, T, Hd);
+    launch_trace(fn, "attn_bf16_kernel", "2,4,reg,w8", B, T, Hd);
     hipLaunchKernelGGL((attn_bf16_kernel<BWD, 2, 4, false, 8>), dim3(B), dim3(512), (size_t)T * sizeof(float), s, ctxb, u, ldu, a_in, p_out, o, ldo, T, ctx_div, ob, ldob);
   }
   else if (bf_ok && Hd == 1024 && T <= 64) AOCR_ATTN_BF16(2, 4, false);
   else if (bf_ok && Hd == 1024 && T <= 128) AOCR_ATTN_BF16(2, 8, false);
   else if (bf_ok && Hd == 1024) AOCR_ATTN_BF16(2, 4, true);
   else if (T <= 64 && Hd == 512) {
-    attn_trace(fn, "attn_reg_kernel", "2,f32", B, T, Hd);
+    launch_trace(fn, "attn_reg_kernel", "2,f32", B, T, Hd);
     hipLaunchKernelGGL((attn_reg_kernel<2, BWD, float>), dim3(B), dim3(256), 0, s, ctx, u, ldu, a_in, p_out, o, ldo, T, ctx_div, ob, ldob);
   } else if (T <= 64 && Hd == 256) {
-    attn_trace(fn, "attn_reg_kernel", "1,f32", B, T, Hd);
+    launch_trace(fn, "attn_reg_kernel", "1,f32", B, T, Hd);
     hipLaunchKernelGGL((attn_reg_kernel<1, BWD, float>), dim3(B), dim3(256), 0, s, ctx, u, ldu, a_in, p_out, o, ldo, T, ctx_div, ob, ldob);
   } else {
-    attn_trace(fn, "attn_core_kernel", "", B, T, Hd);
+    launch_trace(fn, "attn_core_kernel", "", B, T, Hd);
     hipLaunchKernelGGL((attn_core_kernel<BWD>), dim3(B), dim3(256), (size_t)(T + 8) * sizeof(float), s, ctx, u, ldu, a_in, p_out, o, ldo,
                        T, Hd, ctx_div, ob, ldob);
   }
@@ -1521,13 +1548,13 @@ void attention_backward(hipStream_t s, const float* ctx, const float* q, const f
 bool attention_dual_ok(int T, int Hd, const bf16_t* ctxb, const bf16_t* ctxab) { return Hd == 1024 && T <= 64 && ctxb && ctxab && !getenv("AOCR_NO_CHAIN_CTXA"); }
 void attention_forward_dual(hipStream_t s, const float* h_top, int64_t ldh, float* a, float* c, int64_t ldc, int B, int T, int ctx_div, bf16_t* cb, int64_t ldcb,
                             const bf16_t* ctxb, const bf16_t* ctxab) {
-  attn_trace("attention_forward_dual", "attn_bf16_kernel", T <= 32 ? "2,4,reg,w8,dual" : "2,4,reg,w16,dual", B, T, 1024);
+  launch_trace("attention_forward_dual", "attn_bf16_kernel", T <= 32 ? "2,4,reg,w8,dual" : "2,4,reg,w16,dual", B, T, 1024);
   if (T <= 32) hipLaunchKernelGGL((attn_bf16_kernel<false, 2, 4, false, 8, true>), dim3(B), dim3(512), (size_t)T * sizeof(float), s, ctxb, h_top, ldh, nullptr, a, c, ldc, T, ctx_div, cb, ldcb, ctxab, nullptr, (int64_t)0);
   else hipLaunchKernelGGL((attn_bf16_kernel<false, 2, 4, false, 16, true>), dim3(B), dim3(1024), (size_t)T * sizeof(float), s, ctxb, h_top, ldh, nullptr, a, c, ldc, T, ctx_div, cb, ldcb, ctxab, nullptr, (int64_t)0);
 }
 void attention_backward_dual(hipStream_t s, const float* a, const float* dc, int64_t lddc, float* ds, float* dq, bf16_t* dqb, float* dh_attn, int B, int T,
                              const bf16_t* ctxb, const bf16_t* ctxab) {
-  attn_trace("attention_backward_dual", "attn_bf16_kernel", T <= 32 ? "2,4,reg,w8,dual" : "2,4,reg,w16,dual", B, T, 1024);
+  launch_trace("attention_backward_dual", "attn_bf16_kernel", T <= 32 ? "2,4,reg,w8,dual" : "2,4,reg,w16,dual", B, T, 1024);
   if (T <= 32) hipLaunchKernelGGL((attn_bf16_kernel<true, 2, 4, false, 8, true>), dim3(B), dim3(512), (size_t)T * sizeof(float), s, ctxb, dc, lddc, a, ds, dq, (int64_t)1024, T, 1, dqb, (int64_t)1024, ctxab, dh_attn, (int64_t)1024);
   else hipLaunchKernelGGL((attn_bf16_kernel<true, 2, 4, false, 16, true>), dim3(B), dim3(1024), (size_t)T * sizeof(float), s, ctxb, dc, lddc, a, ds, dq, (int64_t)1024, T, 1, dqb, (int64_t)1024, ctxab, dh_attn, (int64_t)1024);
 }
@@ -1580,7 +1607,7 @@ __global__ __launch_bounds__(256) void attn_dctx_kernel(const float* __restrict_
 }
 void attention_dctx(hipStream_t s, const float* a_all, const float* ds_all, const float* dc_all, int64_t lddc, const float* q_all,
                     float* dctx, int L, int B, int T, int Hd) {
-  attn_trace("attention_dctx", "attn_dctx_kernel", "", B, T, Hd);
+  launch_trace("attention_dctx", "attn_dctx_kernel", "", B, T, Hd);
   hipLaunchKernelGGL(attn_dctx_kernel, dim3((Hd + 63) / 64, B), dim3(256), 0, s, a_all, ds_all, dc_all, lddc, q_all, dctx, L, B, T, Hd);
 }
 
