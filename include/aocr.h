@@ -585,6 +585,34 @@ int aocr_estimate_skew(void* stream, const uint8_t* page_dev, int64_t pitch, int
 int aocr_deskew_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
                      const int32_t* skew_dev, int32_t slope_q16, int32_t fill, uint8_t* out_dev, int64_t out_pitch);
 
+/* ---- page background flattening: uneven lighting divided out, in front of aocr_estimate_skew and aocr_segment_page ----------------------
+ * One global threshold (Otsu's or a fixed one) separates ink from paper only when the paper has one brightness.  A photographed page, a book
+ * gutter or an open scanner lid gives paper that is darker on one side than the ink is on the other.  This estimates the paper brightness
+ * near every pixel and divides it out.  Integer arithmetic only, specified exactly; every / is a floor division of non-negative integers.
+ * The page and the output follow the rules of aocr_deskew_page: any base address, any pitch >= W, 1 <= H, W <= 16384, H*W <= 2^26; out_dev:
+ * H rows of W bytes, out_pitch >= W apart, any alignment; bytes between W and out_pitch are untouched; it must not overlap the page.
+ *   v           page[y][x], or 255 - page[y][x] with light_text: the paper is the bright side from here on;
+ *   window      of (x, y), r = radius: [max(x-r,0), min(x+r,W-1)] x [max(y-r,0), min(y+r,H-1)], clipped to the page, n(x,y) pixels;
+ *   background  M[y][x] = the max of v over the window: paper is the brightest thing near a pixel while the window is wider than a stroke;
+ *   smoothing   B[y][x] = (the sum of M over the window + (n >> 1)) / n: the rounded mean (the sum is < 2^24);
+ *   division    Bc = max(B, 1);  out = min(255, (v*255 + (Bc >> 1)) / Bc);  with light_text the byte written is 255 - out.
+ * Consequences: a pixel whose B is 255 is copied unchanged ((v*255 + 127) / 255 = v), so a clean page with paper at 255 comes back bit for
+ * bit; a constant page c >= 1 becomes 255 everywhere, c = 0 stays 0 (light_text: 255 - that); r larger than H or W is legal: the window is
+ * the whole page along that axis.  Limits: a bright speck lifts the background within r of it; solid ink wider than 2r+1 is read as dark
+ * paper; gray pages only; this divides out multiplicative shading, not an additive fog.
+ * scratch_dev: aocr_flatten_scratch_bytes(H, W, radius) bytes, 16-byte aligned, overwritten by the call (0 and an error for bad sizes).
+ * Enqueues only, never synchronises or allocates; the result does not depend on launch geometry or run (integer maxima and sums only, no
+ * atomics).  Invalid params, sizes or overlap return an error before anything is enqueued and leave out_dev untouched. */
+typedef struct aocr_flatten_params {
+  int32_t radius;        /* r in 1..127: windows are (2r+1) x (2r+1), clipped to the page; it must exceed the stroke width */
+  int32_t light_text;    /* 1: light ink on dark paper (the page is inverted, flattened, inverted back) */
+  int32_t reserved[2];   /* must be 0 */
+} aocr_flatten_params;
+
+size_t aocr_flatten_scratch_bytes(int32_t H, int32_t W, int32_t radius);
+int aocr_flatten_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                      const aocr_flatten_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch);
+
 #ifdef __cplusplus
 }
 #endif

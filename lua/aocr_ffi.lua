@@ -101,6 +101,9 @@ typedef struct aocr_skew_params { int32_t threshold; int32_t light_text; int32_t
 size_t aocr_skew_scratch_bytes(int32_t H, int32_t W, int32_t n_steps);
 int aocr_estimate_skew(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_skew_params* params, void* scratch_dev, int32_t skew_dev[4], uint64_t* scores_dev);
 int aocr_deskew_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const int32_t* skew_dev, int32_t slope_q16, int32_t fill, uint8_t* out_dev, int64_t out_pitch);
+typedef struct aocr_flatten_params { int32_t radius; int32_t light_text; int32_t reserved[2]; } aocr_flatten_params;
+size_t aocr_flatten_scratch_bytes(int32_t H, int32_t W, int32_t radius);
+int aocr_flatten_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_flatten_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch);
 ]]
 
 local M = {}

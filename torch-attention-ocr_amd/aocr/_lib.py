@@ -66,6 +66,15 @@ class SkewParams(C.Structure):
         super().__init__(int(threshold), int(light_text), int(step_q16), int(n_steps))
 
 
+class FlattenParams(C.Structure):
+    """mirror of `aocr_flatten_params` (include/aocr.h): the window radius of `aocr_flatten_page`.  The radius must exceed the stroke width
+    (solid ink wider than 2 * radius + 1 is read as dark paper); at 300 dpi 16 to 32 is typical."""
+    _fields_ = [("radius", C.c_int32), ("light_text", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+    def __init__(self, radius=16, light_text=0):
+        super().__init__(int(radius), int(light_text), (C.c_int32 * 2)(0, 0))
+
+
 class Box(C.Structure):
     """mirror of `aocr_box` (include/aocr.h): half-open [x0,x1) x [y0,y1), line number, ink pixels."""
     _fields_ = [(n, C.c_int32) for n in ("x0", "y0", "x1", "y1", "line", "ink")]
@@ -153,6 +162,8 @@ SIGNATURES = {
     "aocr_skew_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
     "aocr_estimate_skew": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "aocr_deskew_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _i32, _i32, _vp, C.c_int64]),
+    "aocr_flatten_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
+    "aocr_flatten_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, C.c_int64]),
     "aocr_beam_select": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32]),
 }
 

@@ -439,7 +439,7 @@ class Model:
             res.word = [lexicon.words[i] if i >= 0 else None for i in res.word_index.tolist()]
         return res
 
-    def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None):
+    def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None, flatten=None):
         """Read a scanned page: segment it into word boxes (aocr_segment_page), crop them (aocr_crop_lines) and recognise the crops.
         page: a uint8 (H,W) numpy array or tensor (gray; a 3-D array raises ValueError: colour pages are out of scope).  params: an
         `aocr.SegmentParams` (default: Otsu threshold, dark text).  The counts and boxes are read back once (the one sync), then the boxes are
@@ -454,8 +454,13 @@ class Model:
         with paper: 0 with light_text, else 255), then segments, crops and recognises the deskewed page, all enqueued on the same stream; the
         skew words come back with the counts (still one sync).  The namespace then also carries skew_steps, skew_slope_q16, skew_deg
         (atan(slope / 65536) in degrees) and source_corners (n,4,2): the (x, y) of every box's corner pixels on the page as given
-        (aocr.page.source_corners); boxes are in deskewed-page coordinates."""
-        from .page import bucket_width, crop_lines_device, deskew_page_device, estimate_skew_device, segment_page_device, source_corners
+        (aocr.page.source_corners); boxes are in deskewed-page coordinates.
+        flatten: None or False (the default) reads the page as it is.  True or an `aocr.FlattenParams` first divides the page's background out
+        (aocr_flatten_page; True: radius 16 with the light_text of `params`), for a page whose paper is not evenly lit; the skew estimate, the
+        deskew, the segmentation and the crops then all read the flattened page.  Enqueued on the same stream, still one sync.  The namespace
+        then also carries flatten_radius."""
+        from .page import (bucket_width, crop_lines_device, deskew_page_device, estimate_skew_device, flatten_page_device, segment_page_device,
+                           source_corners)
         if isinstance(page, np.ndarray):
             if page.ndim != 2 or page.dtype != np.uint8:
                 raise ValueError(f"page must be a uint8 (H, W) array, got {page.dtype} {page.shape}: colour pages are out of scope")
@@ -466,6 +471,11 @@ class Model:
         page = page.to(self.device)
         beam_size = min(beam_size or 1, self.target_vocab_size)
         stream = self._stream()
+        flat = None
+        if flatten is not None and flatten is not False:
+            seg = params if params is not None else _lib.SegmentParams()
+            flat = flatten if isinstance(flatten, _lib.FlattenParams) else _lib.FlattenParams(light_text=seg.light_text)
+            page = flatten_page_device(page, flat, stream)
         skew_dev = None
         if deskew is not None and deskew is not False:
             seg = params if params is not None else _lib.SegmentParams()
@@ -513,6 +523,8 @@ class Model:
         res = SimpleNamespace(boxes=rows[:, :4].copy(), line=rows[:, 4].copy(), ink=rows[:, 5].copy(), text=text, labels=labels, scores=scores,
                               widths=widths, threshold=int(counts[2]), n_found=int(counts[0]), n_lines=int(counts[1]),
                               truncated=bool(counts[0] > max_boxes))
+        if flat is not None:
+            res.flatten_radius = int(flat.radius)
         if skew_dev is not None:
             res.skew_steps, res.skew_slope_q16 = int(skew[0]), int(skew[1])
             res.skew_deg = math.degrees(math.atan(res.skew_slope_q16 / 65536.0))

@@ -1,7 +1,8 @@
 """Page segmentation on the device: `aocr_segment_page` (word boxes of a gray page by projection profiles) and `aocr_crop_lines` (the boxes
 cut out and scaled like `aocr_preprocess_lines`), the stage in front of `Model.recognize`.  Both calls only enqueue; nothing is read back
 here.  Projection profiles assume horizontal lines in one column: a skewed page goes through `estimate_skew_device` and `deskew_page_device`
-(`aocr_estimate_skew`, `aocr_deskew_page`: a sweep of sheared profiles, then a shear) first; multi-column pages are out of scope."""
+(`aocr_estimate_skew`, `aocr_deskew_page`: a sweep of sheared profiles, then a shear) first; multi-column pages are out of scope.  One global
+threshold assumes paper of one brightness: an unevenly lit page goes through `flatten_page_device` (`aocr_flatten_page`) before all of them."""
 from __future__ import annotations
 
 import ctypes as C
@@ -10,7 +11,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import Box, SegmentParams, SkewParams, check, lib, ptr
+from ._lib import Box, FlattenParams, SegmentParams, SkewParams, check, lib, ptr
 
 IMG_H = 32
 MIN_ASPECT = 0.5
@@ -117,6 +118,23 @@ def deskew_page_device(page_dev, skew, fill=255, stream=None):
     return out
 
 
+def flatten_page_device(page_dev, params=None, stream=None):
+    """a new (H, W) uint8 device tensor: the page with its background divided out by `aocr_flatten_page` (the paper brightness near every
+    pixel, a windowed max then a windowed mean, becomes 255).  params: a `FlattenParams` (default: radius 16, dark text).  Enqueues only.
+    stream: as for `segment_page_device`, the current torch stream; the scratch is freed when this returns."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    params = params if params is not None else FlattenParams()
+    dev = page_dev.device
+    need = int(lib.aocr_flatten_scratch_bytes(H, W, params.radius))
+    if need == 0:
+        check(1, "aocr_flatten_scratch_bytes")
+    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    out = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    check(lib.aocr_flatten_page(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), ptr(out), W), "aocr_flatten_page")
+    return out
+
+
 def source_corners(boxes, slope_q16, H, W):
     """(n, 4, 2) int64: for every box (x0 y0 x1 y1, half-open, deskewed-page coordinates) the source-page (x, y) of its corner pixels
     (x0, y0), (x1-1, y0), (x1-1, y1-1), (x0, y1-1) under `aocr_deskew_page`'s mapping with slope_q16 (clamped like the device clamps it).
@@ -142,5 +160,5 @@ def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
     return min(img_w, int(max_img_w))
 
 
-__all__ = ["SegmentParams", "SkewParams", "Box", "segment_page_device", "crop_lines_device", "estimate_skew_device", "deskew_page_device",
-           "source_corners", "bucket_width"]
+__all__ = ["SegmentParams", "SkewParams", "FlattenParams", "Box", "segment_page_device", "crop_lines_device", "estimate_skew_device",
+           "deskew_page_device", "flatten_page_device", "source_corners", "bucket_width"]

@@ -862,4 +862,27 @@ int aocr_deskew_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32
   return check_launch("aocr_deskew_page");
 }
 
+size_t aocr_flatten_scratch_bytes(int32_t H, int32_t W, int32_t radius) {
+  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26) && radius >= 1 && radius <= 127)) {
+    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26) radius=%d (1..127)", H, W, radius);
+    return 0;
+  }
+  return flatten_scratch_bytes(H, W);
+}
+
+int aocr_flatten_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_flatten_params* params,
+                      void* scratch_dev, uint8_t* out_dev, int64_t out_pitch) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(params, "params is NULL");
+  REQUIRE(params->radius >= 1 && params->radius <= 127, "radius=%d: 1..127", params->radius);
+  REQUIRE(params->reserved[0] == 0 && params->reserved[1] == 0, "reserved words must be 0");
+  REQUIRE(scratch_dev && out_dev, "NULL argument");
+  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  REQUIRE(out_pitch >= W, "out_pitch=%lld is smaller than W=%d", (long long)out_pitch, W);
+  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W, o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(H - 1) * out_pitch + W;
+  REQUIRE(o1 <= p0 || p1 <= o0, "out_dev overlaps the page");
+  flatten_page((hipStream_t)stream, page_dev, pitch, H, W, *params, scratch_dev, out_dev, out_pitch);
+  return check_launch("aocr_flatten_page");
+}
+
 }  // extern "C"

@@ -374,6 +374,10 @@ void estimate_skew(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int
                    uint64_t* scores);
 void deskew_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const int32_t* skew, int slope_q16, int fill, uint8_t* out,
                  int64_t out_pitch);
+// page background flattening (flatten.hip; include/aocr.h: aocr_flatten_page): windowed max, windowed mean, division, on a pitched gray page
+size_t flatten_scratch_bytes(int H, int W);
+void flatten_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_flatten_params& p, void* scratch, uint8_t* out,
+                  int64_t out_pitch);
 // crops (data.hip; aocr_crop_lines): preprocess_lines' scaling of n box rectangles of a pitched page, n = min(n_boxes, count[0]) on the device
 void crop_lines(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_box* boxes, const int32_t* count, int n_boxes,
                 int out_h, int out_w, float* out);
