@@ -488,8 +488,8 @@ int aocr_synth_lines(void* stream, const aocr_lexicon* lex, const aocr_glyph_atl
 
 /* ---- page segmentation: from a scanned page to the word crops aocr_recognize reads ---------------------------------------
  * The reference is fed cropped words (90kDICT32px); this finds them on a page by projection profiles and cuts them out, on the device.
- * It assumes horizontal lines in one column: a skewed page goes through aocr_estimate_skew and aocr_deskew_page (below) first; multi-column
- * pages are out of scope.
+ * It assumes horizontal lines in one column: a skewed page goes through aocr_estimate_skew and aocr_deskew_page (below) first; a multi-column
+ * page is first cut into blocks by aocr_ink_integral and aocr_layout_blocks (further below), and each block is segmented on its own.
  * page_dev: gray uint8, H rows of W pixels, rows `pitch` bytes apart (pitch >= W); any base address and any pitch, nothing need be aligned.
  * 1 <= H, W <= 16384, H*W <= 2^26, 1 <= max_boxes <= 4096.  Steps, in order:
  *   1 histogram  h[v], 256 bins, of the page (only the Otsu threshold reads it);
@@ -612,6 +612,66 @@ typedef struct aocr_flatten_params {
 size_t aocr_flatten_scratch_bytes(int32_t H, int32_t W, int32_t radius);
 int aocr_flatten_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
                       const aocr_flatten_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch);
+
+/* ---- page layout: the blocks of a multi-column page, in reading order, in front of aocr_segment_page -------------------------------------
+ * aocr_segment_page takes its row profiles across the whole width of the page: the lines of two columns fall into one band and their words
+ * come back interleaved.  These two calls cut the page into blocks (headline, columns, paragraphs) by a recursive XY cut; every block is
+ * then a one-column page for aocr_segment_page (a view: its row stride is the page's pitch).  Integer arithmetic only, specified exactly.
+ *
+ * aocr_ink_integral: the ink mask and its summed-area table.  The page follows the rules of aocr_segment_page: any base address, any
+ * pitch >= W, 1 <= H, W <= 16384, H*W <= 2^26.  threshold: 0..254, or -1 for Otsu: steps 1-2 of aocr_segment_page, bit for bit;
+ * ink = (v <= threshold), or (v > threshold) with light_text; an Otsu threshold of -1 (one gray value): nothing is ink.
+ *   sat_dev   (H+1) rows of (W+1) uint32, sat_pitch elements apart (sat_pitch >= W+1; the base 4-byte aligned).  Row 0 and column 0 are
+ *             zero; S[y+1][x+1] = the number of ink pixels in [0,x] x [0,y].  Elements between W+1 and sat_pitch are untouched.  It must
+ *             not overlap the page or the scratch.
+ *   info_dev  [the threshold used, the total ink (= S[H][W]), 0, 0].
+ * scratch_dev: aocr_integral_scratch_bytes(H, W) bytes, 16-byte aligned, overwritten by the call (0 and an error for bad sizes).
+ *
+ * aocr_layout_blocks: the recursive XY cut.  All ink counts come from the table, four reads per rectangle: the ink of [x0,x1) x [y0,y1) is
+ * S[y1][x1] - S[y0][x1] - S[y1][x0] + S[y0][x0].  For a region R = [x0,x1) x [y0,y1):
+ *   profiles  c[x] = the ink of column x within R's rows, r[y] = the ink of row y within R's columns; a column or row is occupied when its
+ *             count >= min_ink;
+ *   pieces    along an axis: the maximal runs of occupied elements; runs with fewer than `gap` unoccupied elements between them are one
+ *             piece (the gap is measured between the original runs; merging chains, as words are formed in step 5 of aocr_segment_page);
+ *             unoccupied elements before the first run and after the last belong to no piece;
+ *   tighten   first x0..x1 becomes the first to the last occupied column of R, then y0..y1 the first to the last occupied row of the
+ *             narrowed region: one pass each, no iteration.  No occupied column, or then no occupied row: R is empty and is dropped;
+ *   levels    L_0 = [tighten(page)] at depth 0, or the empty list.  For d = 0 .. max_depth-1 every region of L_d that is not yet a leaf is
+ *             cut: its column pieces with gap_x -- two or more: the children are piece.x x R.y, left to right; otherwise its row pieces
+ *             with gap_y over R's full columns -- two or more: the children are R.x x piece.y, top to bottom; otherwise R becomes a leaf
+ *             and keeps its place and its depth.  Columns first: a grid of four rectangles reads column by column.  Children are tightened
+ *             once, at creation; empty ones are dropped; the rest replace their parent in place at depth d+1, so the list is always in
+ *             reading order, the preorder of the cut tree.  If the list after level d would hold more than max_blocks regions, that
+ *             level's cuts are discarded, the list stays as it was before level d, counts[3] = 1 and cutting stops.  Cutting also stops
+ *             after a level that cut nothing;
+ *   output    every region of the final list with w >= min_block_w, h >= min_block_h and ink >= min_block_ink becomes, in list order, a
+ *             row {x0, y0, x1, y1, line = depth, ink} of blocks_dev; the others are dropped.  Rows beyond the written ones are untouched;
+ *   counts    counts_dev = [blocks written, levels in which something was cut and kept, regions dropped by size, overflow flag].
+ * sat_dev, sat_pitch, H, W: the table of aocr_ink_integral (any table with these properties).  1 <= max_blocks <= 1024.
+ * Limits: an XY cut cannot separate L-shaped or interleaved regions; a headline wider than one column but narrower than the page blocks
+ * the gutter beneath it only as far as it reaches; aligned word gaps on a page of very few lines can look like a gutter (gap_x is the
+ * control); paragraph gaps that line up across both columns are cut before the gutter is (the blocks then read row of paragraphs by row).
+ * scratch_dev: aocr_layout_scratch_bytes(H, W, max_blocks) bytes, 16-byte aligned, overwritten by the call (0 and an error for bad sizes).
+ * Both calls enqueue only, never synchronise or allocate; the results do not depend on launch geometry, atomics order or run.  Invalid
+ * params, sizes, NULLs or overlap return an error before anything is enqueued and leave the outputs untouched. */
+size_t aocr_integral_scratch_bytes(int32_t H, int32_t W);
+int aocr_ink_integral(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                      int32_t threshold, int32_t light_text, void* scratch_dev,
+                      uint32_t* sat_dev, int64_t sat_pitch, int32_t info_dev[4]);
+
+typedef struct aocr_layout_params {
+  int32_t min_ink;      /* >= 1: a column (row) of a region is occupied when its ink inside the region >= this */
+  int32_t gap_x;        /* >= 1: occupied-column runs with fewer than gap_x unoccupied columns between them are one piece */
+  int32_t gap_y;        /* >= 1: the same for rows */
+  int32_t max_depth;    /* 1..16 levels of cuts */
+  int32_t min_block_w, min_block_h, min_block_ink;   /* >= 1: smaller leaves are dropped at the end */
+  int32_t reserved;     /* must be 0 */
+} aocr_layout_params;
+
+size_t aocr_layout_scratch_bytes(int32_t H, int32_t W, int32_t max_blocks);
+int aocr_layout_blocks(void* stream, const uint32_t* sat_dev, int64_t sat_pitch, int32_t H, int32_t W,
+                       const aocr_layout_params* params, void* scratch_dev, int32_t max_blocks,
+                       aocr_box* blocks_dev, int32_t counts_dev[4]);
 
 #ifdef __cplusplus
 }

@@ -104,6 +104,11 @@ int aocr_deskew_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32
 typedef struct aocr_flatten_params { int32_t radius; int32_t light_text; int32_t reserved[2]; } aocr_flatten_params;
 size_t aocr_flatten_scratch_bytes(int32_t H, int32_t W, int32_t radius);
 int aocr_flatten_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_flatten_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch);
+size_t aocr_integral_scratch_bytes(int32_t H, int32_t W);
+int aocr_ink_integral(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t threshold, int32_t light_text, void* scratch_dev, uint32_t* sat_dev, int64_t sat_pitch, int32_t info_dev[4]);
+typedef struct aocr_layout_params { int32_t min_ink; int32_t gap_x; int32_t gap_y; int32_t max_depth; int32_t min_block_w, min_block_h, min_block_ink; int32_t reserved; } aocr_layout_params;
+size_t aocr_layout_scratch_bytes(int32_t H, int32_t W, int32_t max_blocks);
+int aocr_layout_blocks(void* stream, const uint32_t* sat_dev, int64_t sat_pitch, int32_t H, int32_t W, const aocr_layout_params* params, void* scratch_dev, int32_t max_blocks, aocr_box* blocks_dev, int32_t counts_dev[4]);
 ]]
 
 local M = {}

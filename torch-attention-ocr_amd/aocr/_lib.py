@@ -75,6 +75,15 @@ class FlattenParams(C.Structure):
         super().__init__(int(radius), int(light_text), (C.c_int32 * 2)(0, 0))
 
 
+class LayoutParams(C.Structure):
+    """mirror of `aocr_layout_params` (include/aocr.h): the recursive XY cut of `aocr_layout_blocks`.  gap_x is what a gutter must exceed and a
+    word gap must not; gap_y what a paragraph gap must exceed and a line gap must not."""
+    _fields_ = [(n, C.c_int32) for n in ("min_ink", "gap_x", "gap_y", "max_depth", "min_block_w", "min_block_h", "min_block_ink", "reserved")]
+
+    def __init__(self, min_ink=1, gap_x=24, gap_y=30, max_depth=8, min_block_w=8, min_block_h=8, min_block_ink=16):
+        super().__init__(int(min_ink), int(gap_x), int(gap_y), int(max_depth), int(min_block_w), int(min_block_h), int(min_block_ink), 0)
+
+
 class Box(C.Structure):
     """mirror of `aocr_box` (include/aocr.h): half-open [x0,x1) x [y0,y1), line number, ink pixels."""
     _fields_ = [(n, C.c_int32) for n in ("x0", "y0", "x1", "y1", "line", "ink")]
@@ -164,6 +173,10 @@ SIGNATURES = {
     "aocr_deskew_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _i32, _i32, _vp, C.c_int64]),
     "aocr_flatten_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
     "aocr_flatten_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, C.c_int64]),
+    "aocr_integral_scratch_bytes": (C.c_size_t, [_i32, _i32]),
+    "aocr_ink_integral": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _i32, _i32, _vp, _vp, C.c_int64, _vp]),
+    "aocr_layout_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
+    "aocr_layout_blocks": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
     "aocr_beam_select": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32]),
 }
 

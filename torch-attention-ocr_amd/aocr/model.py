@@ -439,7 +439,8 @@ class Model:
             res.word = [lexicon.words[i] if i >= 0 else None for i in res.word_index.tolist()]
         return res
 
-    def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None, flatten=None):
+    def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None, flatten=None,
+                       layout=None):
         """Read a scanned page: segment it into word boxes (aocr_segment_page), crop them (aocr_crop_lines) and recognise the crops.
         page: a uint8 (H,W) numpy array or tensor (gray; a 3-D array raises ValueError: colour pages are out of scope).  params: an
         `aocr.SegmentParams` (default: Otsu threshold, dark text).  The counts and boxes are read back once (the one sync), then the boxes are
@@ -458,9 +459,18 @@ class Model:
         flatten: None or False (the default) reads the page as it is.  True or an `aocr.FlattenParams` first divides the page's background out
         (aocr_flatten_page; True: radius 16 with the light_text of `params`), for a page whose paper is not evenly lit; the skew estimate, the
         deskew, the segmentation and the crops then all read the flattened page.  Enqueued on the same stream, still one sync.  The namespace
-        then also carries flatten_radius."""
-        from .page import (bucket_width, crop_lines_device, deskew_page_device, estimate_skew_device, flatten_page_device, segment_page_device,
-                           source_corners)
+        then also carries flatten_radius.
+        layout: None or False (the default) segments the page as one column.  True or an `aocr.LayoutParams` reads a multi-column page: after
+        flatten and deskew the page's ink table and its recursive XY cut are enqueued (aocr_ink_integral, aocr_layout_blocks, at most 256
+        blocks, with the threshold and light_text of `params`), and the blocks, their counts and the page threshold are read back (the skew
+        comes with them): the FIRST sync.  Every block is then segmented as a view of the page (aocr_segment_page with the page threshold, so
+        Otsu is not redone per block; max_boxes applies per block and the padding clamps to the block), the boxes are shifted to page
+        coordinates and the line numbers continued across blocks on the device, and all counts and boxes are read back together: the SECOND
+        sync (this path has two, the others one).  Crops are taken from the whole page.  The namespace is in reading order (block, then
+        line, then x) and also carries block (n): the block of every box, blocks (m,4) x0 y0 x1 y1, block_depth (m), n_blocks and
+        layout_overflow; truncated is true when any block truncated."""
+        from .page import (bucket_width, crop_lines_device, deskew_page_device, estimate_skew_device, flatten_page_device, layout_page_device,
+                           segment_page_device, source_corners)
         if isinstance(page, np.ndarray):
             if page.ndim != 2 or page.dtype != np.uint8:
                 raise ValueError(f"page must be a uint8 (H, W) array, got {page.dtype} {page.shape}: colour pages are out of scope")
@@ -482,14 +492,52 @@ class Model:
             sp = deskew if isinstance(deskew, _lib.SkewParams) else _lib.SkewParams(threshold=seg.threshold, light_text=seg.light_text)
             skew_dev = estimate_skew_device(page, sp, stream)
             page = deskew_page_device(page, skew_dev, 0 if seg.light_text else 255, stream)
-        boxes_dev, counts_dev = segment_page_device(page, params, max_boxes, stream)
-        if skew_dev is None:
-            counts = counts_dev.cpu().numpy()
+        lay = None
+        if layout is not None and layout is not False:
+            seg = params if params is not None else _lib.SegmentParams()
+            lay = layout if isinstance(layout, _lib.LayoutParams) else _lib.LayoutParams()
+            max_blocks = 256
+            blocks_dev, lcounts_dev, info_dev = layout_page_device(page, lay, seg.threshold, seg.light_text, max_blocks, stream)
+            head = torch.cat([lcounts_dev, info_dev, skew_dev if skew_dev is not None else lcounts_dev[:0], blocks_dev.reshape(-1)]).cpu().numpy()
+            lcounts, info = head[:4], head[4:8]                   # the first sync
+            if skew_dev is not None:
+                skew = head[8:12]
+            nb = int(lcounts[0])
+            blocks = head[-6 * max_blocks:].reshape(max_blocks, 6)[:nb]
+            block_seg = _lib.SegmentParams(*[getattr(seg, f) for f, _ in seg._fields_][:9])
+            block_seg.threshold = int(info[0])                    # the page's threshold: every block thresholds like the whole page
+            per = [segment_page_device(page[b[1]:b[3], b[0]:b[2]], block_seg, max_boxes, stream) for b in blocks.tolist()]
+            if nb:
+                all_boxes = torch.stack([bx for bx, _ in per])                          # (nb, max_boxes, 6)
+                all_counts = torch.stack([c for _, c in per])                           # (nb, 4)
+                all_boxes[:, :, :4] += blocks_dev[:nb][:, [0, 1, 0, 1]][:, None, :]
+                lines_dev = all_counts[:, 1]
+                all_boxes[:, :, 4] += (torch.cumsum(lines_dev, 0) - lines_dev).to(torch.int32)[:, None]
+                all_boxes = all_boxes.reshape(-1, 6)
+                back = torch.cat([all_counts.reshape(-1), all_boxes.reshape(-1)]).cpu().numpy()     # the second sync
+                bcounts = back[:4 * nb].reshape(nb, 4)
+                taken = np.minimum(bcounts[:, 0], max_boxes)
+                keep = np.concatenate([b * max_boxes + np.arange(t) for b, t in enumerate(taken.tolist())]).astype(np.int64)
+                rows = back[4 * nb:].reshape(-1, 6)[keep]
+                boxes_dev = all_boxes[torch.from_numpy(keep).to(self.device)]
+                block_id = np.repeat(np.arange(nb, dtype=np.int32), taken)
+            else:
+                bcounts = np.zeros((0, 4), np.int32)
+                rows, block_id = np.zeros((0, 6), np.int32), np.zeros(0, np.int32)
+                boxes_dev = torch.zeros((0, 6), dtype=torch.int32, device=self.device)
+            n = len(rows)
+            counts = np.array([bcounts[:, 0].sum(), bcounts[:, 1].sum(), info[0], 0], np.int64)
+            truncated = bool((bcounts[:, 0] > max_boxes).any())
         else:
-            both = torch.cat([counts_dev, skew_dev]).cpu().numpy()
-            counts, skew = both[:4], both[4:]
-        n = int(min(counts[0], max_boxes))
-        rows = boxes_dev[:n].cpu().numpy()
+            boxes_dev, counts_dev = segment_page_device(page, params, max_boxes, stream)
+            if skew_dev is None:
+                counts = counts_dev.cpu().numpy()
+            else:
+                both = torch.cat([counts_dev, skew_dev]).cpu().numpy()
+                counts, skew = both[:4], both[4:]
+            n = int(min(counts[0], max_boxes))
+            rows = boxes_dev[:n].cpu().numpy()
+            truncated = bool(counts[0] > max_boxes)
         if width is not None:
             widths = np.full(n, int(width), np.int64)
         else:
@@ -522,7 +570,10 @@ class Model:
             text.append(numlist2str(ids))
         res = SimpleNamespace(boxes=rows[:, :4].copy(), line=rows[:, 4].copy(), ink=rows[:, 5].copy(), text=text, labels=labels, scores=scores,
                               widths=widths, threshold=int(counts[2]), n_found=int(counts[0]), n_lines=int(counts[1]),
-                              truncated=bool(counts[0] > max_boxes))
+                              truncated=truncated)
+        if lay is not None:
+            res.block, res.blocks, res.block_depth = block_id, blocks[:, :4].copy(), blocks[:, 4].copy()
+            res.n_blocks, res.layout_overflow = nb, bool(lcounts[3])
         if flat is not None:
             res.flatten_radius = int(flat.radius)
         if skew_dev is not None:

@@ -1,8 +1,9 @@
 """Page segmentation on the device: `aocr_segment_page` (word boxes of a gray page by projection profiles) and `aocr_crop_lines` (the boxes
 cut out and scaled like `aocr_preprocess_lines`), the stage in front of `Model.recognize`.  Both calls only enqueue; nothing is read back
 here.  Projection profiles assume horizontal lines in one column: a skewed page goes through `estimate_skew_device` and `deskew_page_device`
-(`aocr_estimate_skew`, `aocr_deskew_page`: a sweep of sheared profiles, then a shear) first; multi-column pages are out of scope.  One global
-threshold assumes paper of one brightness: an unevenly lit page goes through `flatten_page_device` (`aocr_flatten_page`) before all of them."""
+(`aocr_estimate_skew`, `aocr_deskew_page`: a sweep of sheared profiles, then a shear) first; a multi-column page is first cut into blocks by
+`layout_page_device` (`aocr_ink_integral`, `aocr_layout_blocks`: a summed-area table of the ink, then a recursive XY cut) and each block is
+segmented as a view of the page.  One global threshold assumes paper of one brightness: an unevenly lit page goes through `flatten_page_device` (`aocr_flatten_page`) before all of them."""
 from __future__ import annotations
 
 import ctypes as C
@@ -11,7 +12,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import Box, FlattenParams, SegmentParams, SkewParams, check, lib, ptr
+from ._lib import Box, FlattenParams, LayoutParams, SegmentParams, SkewParams, check, lib, ptr
 
 IMG_H = 32
 MIN_ASPECT = 0.5
@@ -135,6 +136,53 @@ def flatten_page_device(page_dev, params=None, stream=None):
     return out
 
 
+def _ink_integral(page_dev, pitch, threshold, light_text, stream):
+    H, W = page_dev.shape
+    dev = page_dev.device
+    need = int(lib.aocr_integral_scratch_bytes(H, W))
+    if need == 0:
+        check(1, "aocr_integral_scratch_bytes")
+    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    sat_pitch = (W + 1 + 3) & ~3                             # rows of whole 16-byte words
+    sat = torch.empty((H + 1, sat_pitch), dtype=torch.int32, device=dev)
+    info = torch.zeros(4, dtype=torch.int32, device=dev)
+    check(lib.aocr_ink_integral(_stream(stream, dev), ptr(page_dev), pitch, H, W, int(threshold), int(light_text), ptr(scratch), ptr(sat),
+                                sat_pitch, ptr(info)), "aocr_ink_integral")
+    return sat, info
+
+
+def ink_integral_device(page_dev, threshold=-1, light_text=0, stream=None):
+    """(sat, info): sat an (H+1, W+1) int32 view of a table whose rows are `sat.stride(0)` elements apart -- sat[y+1, x+1] is the number of
+    ink pixels in [0,x] x [0,y], row 0 and column 0 are zero (counts are at most 2^26: int32 holds them) -- and info (4) int32: the threshold
+    used, the total ink, 0, 0 (`aocr_ink_integral`).  threshold -1: Otsu.  Enqueues only.  stream: as for `segment_page_device`, the current
+    torch stream; the scratch is freed when this returns."""
+    page_dev, pitch = _page_view(page_dev)
+    sat, info = _ink_integral(page_dev, pitch, threshold, light_text, stream)
+    return sat[:, :page_dev.shape[1] + 1], info
+
+
+def layout_page_device(page_dev, params=None, threshold=-1, light_text=0, max_blocks=256, stream=None):
+    """(blocks (max_blocks, 6) int32 rows x0 y0 x1 y1 depth ink in reading order, counts (4) int32: blocks written, levels cut, regions
+    dropped by size, overflow flag, info (4) int32: threshold, total ink, 0, 0) as device tensors: the page's ink table (`aocr_ink_integral`)
+    and the recursive XY cut on it (`aocr_layout_blocks`).  Rows of blocks beyond counts[0] are not written (they hold zeros).  params: a
+    `LayoutParams` (default: gaps of 24 columns and 30 rows).  Enqueues only.  stream: as for `segment_page_device`; the table and the scratch
+    are freed when this returns."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    params = params if params is not None else LayoutParams()
+    dev = page_dev.device
+    need = int(lib.aocr_layout_scratch_bytes(H, W, max_blocks))
+    if need == 0:
+        check(1, "aocr_layout_scratch_bytes")
+    sat, info = _ink_integral(page_dev, pitch, threshold, light_text, stream)
+    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    blocks = torch.zeros((max_blocks, 6), dtype=torch.int32, device=dev)
+    counts = torch.zeros(4, dtype=torch.int32, device=dev)
+    check(lib.aocr_layout_blocks(_stream(stream, dev), ptr(sat), sat.stride(0), H, W, C.byref(params), ptr(scratch), max_blocks, ptr(blocks),
+                                 ptr(counts)), "aocr_layout_blocks")
+    return blocks, counts, info
+
+
 def source_corners(boxes, slope_q16, H, W):
     """(n, 4, 2) int64: for every box (x0 y0 x1 y1, half-open, deskewed-page coordinates) the source-page (x, y) of its corner pixels
     (x0, y0), (x1-1, y0), (x1-1, y1-1), (x0, y1-1) under `aocr_deskew_page`'s mapping with slope_q16 (clamped like the device clamps it).
@@ -160,5 +208,6 @@ def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
     return min(img_w, int(max_img_w))
 
 
-__all__ = ["SegmentParams", "SkewParams", "FlattenParams", "Box", "segment_page_device", "crop_lines_device", "estimate_skew_device",
-           "deskew_page_device", "flatten_page_device", "source_corners", "bucket_width"]
+__all__ = ["SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "Box", "segment_page_device", "crop_lines_device",
+           "estimate_skew_device", "deskew_page_device", "flatten_page_device", "ink_integral_device", "layout_page_device", "source_corners",
+           "bucket_width"]

@@ -885,4 +885,64 @@ int aocr_flatten_page(void* stream, const uint8_t* page_dev, int64_t pitch, int3
   return check_launch("aocr_flatten_page");
 }
 
+size_t aocr_integral_scratch_bytes(int32_t H, int32_t W) {
+  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26))) {
+    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26)", H, W);
+    return 0;
+  }
+  return integral_scratch_bytes(H, W);
+}
+
+static int check_sat(const uint32_t* sat_dev, int64_t sat_pitch, int32_t H, int32_t W) {
+  REQUIRE(sat_dev, "sat_dev is NULL");
+  REQUIRE(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26),
+          "bad page size H=%d W=%d: 1..16384 each, H*W <= 2^26", H, W);
+  REQUIRE(sat_pitch >= (int64_t)W + 1, "sat_pitch=%lld is smaller than W+1=%d", (long long)sat_pitch, W + 1);
+  REQUIRE(((uintptr_t)sat_dev & 3) == 0, "sat_dev must be 4-byte aligned");
+  return 0;
+}
+
+int aocr_ink_integral(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t threshold, int32_t light_text,
+                      void* scratch_dev, uint32_t* sat_dev, int64_t sat_pitch, int32_t info_dev[4]) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(threshold >= -1 && threshold <= 254, "threshold=%d: 0..254, or -1 for Otsu", threshold);
+  REQUIRE(scratch_dev && info_dev, "NULL argument");
+  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  if (check_sat(sat_dev, sat_pitch, H, W)) return 1;
+  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W;
+  const uintptr_t t0 = (uintptr_t)sat_dev, t1 = t0 + ((uintptr_t)H * sat_pitch + W + 1) * sizeof(uint32_t);
+  const uintptr_t s0 = (uintptr_t)scratch_dev, s1 = s0 + integral_scratch_bytes(H, W);
+  REQUIRE(t1 <= p0 || p1 <= t0, "sat_dev overlaps the page");
+  REQUIRE(t1 <= s0 || s1 <= t0, "sat_dev overlaps the scratch");
+  ink_integral((hipStream_t)stream, page_dev, pitch, H, W, threshold, light_text, scratch_dev, sat_dev, sat_pitch, info_dev);
+  return check_launch("aocr_ink_integral");
+}
+
+size_t aocr_layout_scratch_bytes(int32_t H, int32_t W, int32_t max_blocks) {
+  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26) && max_blocks >= 1 && max_blocks <= 1024)) {
+    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26) max_blocks=%d (1..1024)", H, W, max_blocks);
+    return 0;
+  }
+  return layout_scratch_bytes(max_blocks);
+}
+
+int aocr_layout_blocks(void* stream, const uint32_t* sat_dev, int64_t sat_pitch, int32_t H, int32_t W, const aocr_layout_params* params,
+                       void* scratch_dev, int32_t max_blocks, aocr_box* blocks_dev, int32_t counts_dev[4]) {
+  if (check_sat(sat_dev, sat_pitch, H, W)) return 1;
+  REQUIRE(params && scratch_dev && blocks_dev && counts_dev, "NULL argument");
+  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  REQUIRE(max_blocks >= 1 && max_blocks <= 1024, "max_blocks=%d: 1..1024", max_blocks);
+  REQUIRE(params->min_ink >= 1 && params->gap_x >= 1 && params->gap_y >= 1, "min_ink=%d gap_x=%d gap_y=%d must be >= 1", params->min_ink,
+          params->gap_x, params->gap_y);
+  REQUIRE(params->max_depth >= 1 && params->max_depth <= 16, "max_depth=%d: 1..16", params->max_depth);
+  REQUIRE(params->min_block_w >= 1 && params->min_block_h >= 1 && params->min_block_ink >= 1,
+          "min_block_w=%d min_block_h=%d min_block_ink=%d must be >= 1", params->min_block_w, params->min_block_h, params->min_block_ink);
+  REQUIRE(params->reserved == 0, "reserved word must be 0");
+  const uintptr_t t0 = (uintptr_t)sat_dev, t1 = t0 + ((uintptr_t)H * sat_pitch + W + 1) * sizeof(uint32_t);
+  const uintptr_t s0 = (uintptr_t)scratch_dev, s1 = s0 + layout_scratch_bytes(max_blocks);
+  REQUIRE(t1 <= s0 || s1 <= t0, "sat_dev overlaps the scratch");
+  layout_blocks((hipStream_t)stream, sat_dev, sat_pitch, H, W, *params, scratch_dev, max_blocks, blocks_dev, counts_dev);
+  return check_launch("aocr_layout_blocks");
+}
+
 }  // extern "C"

@@ -378,6 +378,13 @@ void deskew_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W
 size_t flatten_scratch_bytes(int H, int W);
 void flatten_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_flatten_params& p, void* scratch, uint8_t* out,
                   int64_t out_pitch);
+// page layout (layout.hip; include/aocr.h: aocr_ink_integral, aocr_layout_blocks): the summed-area table of the ink mask and the XY cut on it
+size_t integral_scratch_bytes(int H, int W);
+void ink_integral(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, int threshold, int light_text, void* scratch, uint32_t* sat,
+                  int64_t sat_pitch, int32_t* info);
+size_t layout_scratch_bytes(int max_blocks);
+void layout_blocks(hipStream_t s, const uint32_t* sat, int64_t sat_pitch, int H, int W, const aocr_layout_params& p, void* scratch, int max_blocks,
+                   aocr_box* blocks, int32_t* counts);
 // crops (data.hip; aocr_crop_lines): preprocess_lines' scaling of n box rectangles of a pitched page, n = min(n_boxes, count[0]) on the device
 void crop_lines(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_box* boxes, const int32_t* count, int n_boxes,
                 int out_h, int out_w, float* out);
