@@ -673,6 +673,69 @@ int aocr_layout_blocks(void* stream, const uint32_t* sat_dev, int64_t sat_pitch,
                        const aocr_layout_params* params, void* scratch_dev, int32_t max_blocks,
                        aocr_box* blocks_dev, int32_t counts_dev[4]);
 
+/* ---- page cleaning: connected components of the ink; specks and rules painted over, in front of aocr_estimate_skew and aocr_segment_page --
+ * Everything above reads projection profiles of the thresholded page, and a profile cannot tell a word from a speck or a ruled line: one
+ * dark pixel makes a text row (min_row_ink = 1) and an occupied column (step 5), one vertical rule joins every line it passes into one band,
+ * one underline joins the words of its line into one box.  These two calls label the ink, measure every component and delete the ones that
+ * cannot be text.  Integer arithmetic only, specified exactly.
+ *
+ * aocr_label_components.  The page follows the rules of aocr_segment_page: any base address, any pitch >= W, 1 <= H, W <= 16384,
+ * H*W <= 2^26.  threshold: 0..254, or -1 for Otsu: steps 1-2 of aocr_segment_page, bit for bit; ink = (v <= threshold), or (v > threshold)
+ * with light_text; an Otsu threshold of -1 (one gray value): nothing is ink.
+ *   neighbours  connectivity is 4 or 8: two ink pixels are neighbours when they differ by 1 in x or in y (4), or by at most 1 in both and
+ *               are not the same pixel (8).  A component is a maximal set of ink pixels connected through neighbours;
+ *   labels_dev  H rows of W int32, labels_pitch elements apart (labels_pitch >= W; the base 4-byte aligned); elements between W and
+ *               labels_pitch are untouched.  Paper is -1; an ink pixel carries the smallest y*W + x of any pixel of its component: the
+ *               component's first pixel in raster order (W, not the pitch: indices fit int32 because H*W <= 2^26).  It must not overlap
+ *               the page or the scratch;
+ *   comps_dev   may be NULL.  Otherwise the components in ascending label order (the raster order of their first pixels) as rows
+ *               {x0, y0, x1, y1, line = label, ink = area}: the half-open tight box and the number of pixels.  Only the first
+ *               max_components are written (1 <= max_components <= 65536); rows beyond them are untouched;
+ *   info_dev    [the threshold used, the total ink, components found, 0].  Components found may exceed max_components: that is how the
+ *               caller sees truncation.
+ * scratch_dev: aocr_components_scratch_bytes(H, W) bytes, 16-byte aligned, overwritten by the call (0 and an error for bad sizes): about
+ * 8 bytes per pixel (one 16-byte record per pixel pair), 516 MiB at H*W = 2^26, 67 MiB for A4 at 300 dpi.
+ *
+ * aocr_clean_page: the page with its specks and rules painted over.  Components as above (params.threshold, light_text, connectivity), each
+ * with its area and its tight box of w x h pixels:
+ *   speck       area < min_area (min_area = 1: nothing is a speck);
+ *   rule        not a speck, and w > max_w or h > max_h (a limit of 0 switches that test off).  Specks are tested first: a short dash is a
+ *               speck, never a rule;
+ *   output      out[y][x] = fill when the pixel is ink and its component is a speck or a rule, fill = 255, or 0 with light_text; every
+ *               other byte is copied bit for bit.  A page with nothing to remove comes back identical; an Otsu threshold of -1 copies it;
+ *   counts      counts_dev = [components, specks removed, rules removed, the threshold used, the total ink, ink pixels removed, 0, 0]
+ *               (4-byte aligned).
+ * out_dev follows the rules of aocr_deskew_page: H rows of W bytes, out_pitch >= W apart, any alignment; bytes between W and out_pitch are
+ * untouched; it must not overlap the page (or the scratch).  The labels live in the scratch; this call does not expose them.
+ * Limits: a character that touches a rule goes with it (an underline through descenders takes them along); min_area above the area of an
+ * i-dot or a full stop deletes those; a figure is one big component and is removed by max_w / max_h, which is intended: what is left is
+ * what the recogniser can read.
+ * scratch_dev: aocr_clean_scratch_bytes(H, W) bytes, 16-byte aligned, overwritten by the call (0 and an error for bad sizes): the above
+ * plus the labels, about 12 bytes per pixel, 772 MiB at H*W = 2^26, 100 MiB for A4 at 300 dpi.
+ * Both calls enqueue only, never synchronise or allocate; the results do not depend on launch geometry, atomics order or run (the labels
+ * are canonical; sums, minima and maxima of integers).  Invalid params, sizes, NULLs, a bad connectivity or overlap return an error before
+ * anything is enqueued and leave the outputs untouched. */
+size_t aocr_components_scratch_bytes(int32_t H, int32_t W);
+int aocr_label_components(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                          int32_t threshold, int32_t light_text, int32_t connectivity, void* scratch_dev,
+                          int32_t* labels_dev, int64_t labels_pitch,
+                          int32_t max_components, aocr_box* comps_dev, int32_t info_dev[4]);
+
+typedef struct aocr_clean_params {
+  int32_t threshold;     /* 0..254: ink = (v <= threshold); -1: Otsu, steps 1-2 of aocr_segment_page, bit for bit */
+  int32_t light_text;    /* 1: ink = (v > threshold) instead; removed pixels become 0 instead of 255 */
+  int32_t connectivity;  /* 4 or 8 */
+  int32_t min_area;      /* >= 1: a component with area < min_area is a speck (1: none is) */
+  int32_t max_w, max_h;  /* >= 0: a component that is no speck and whose box is wider than max_w or higher than max_h is a rule
+                            (0: that test is off) */
+  int32_t reserved[2];   /* must be 0 */
+} aocr_clean_params;
+
+size_t aocr_clean_scratch_bytes(int32_t H, int32_t W);
+int aocr_clean_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                    const aocr_clean_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch,
+                    int32_t counts_dev[8]);
+
 #ifdef __cplusplus
 }
 #endif

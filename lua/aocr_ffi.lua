@@ -109,6 +109,11 @@ int aocr_ink_integral(void* stream, const uint8_t* page_dev, int64_t pitch, int3
 typedef struct aocr_layout_params { int32_t min_ink; int32_t gap_x; int32_t gap_y; int32_t max_depth; int32_t min_block_w, min_block_h, min_block_ink; int32_t reserved; } aocr_layout_params;
 size_t aocr_layout_scratch_bytes(int32_t H, int32_t W, int32_t max_blocks);
 int aocr_layout_blocks(void* stream, const uint32_t* sat_dev, int64_t sat_pitch, int32_t H, int32_t W, const aocr_layout_params* params, void* scratch_dev, int32_t max_blocks, aocr_box* blocks_dev, int32_t counts_dev[4]);
+size_t aocr_components_scratch_bytes(int32_t H, int32_t W);
+int aocr_label_components(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t threshold, int32_t light_text, int32_t connectivity, void* scratch_dev, int32_t* labels_dev, int64_t labels_pitch, int32_t max_components, aocr_box* comps_dev, int32_t info_dev[4]);
+typedef struct aocr_clean_params { int32_t threshold; int32_t light_text; int32_t connectivity; int32_t min_area; int32_t max_w, max_h; int32_t reserved[2]; } aocr_clean_params;
+size_t aocr_clean_scratch_bytes(int32_t H, int32_t W);
+int aocr_clean_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_clean_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch, int32_t counts_dev[8]);
 ]]
 
 local M = {}

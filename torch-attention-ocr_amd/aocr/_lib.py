@@ -84,6 +84,17 @@ class LayoutParams(C.Structure):
         super().__init__(int(min_ink), int(gap_x), int(gap_y), int(max_depth), int(min_block_w), int(min_block_h), int(min_block_ink), 0)
 
 
+class CleanParams(C.Structure):
+    """mirror of `aocr_clean_params` (include/aocr.h): which connected components `aocr_clean_page` paints over.  A component with fewer than
+    min_area pixels is a speck; one that is no speck and whose box is wider than max_w or higher than max_h is a rule (0: that test is off).
+    threshold -1: Otsu.  The defaults are a judgement for text at 300 dpi -- dust is a few pixels, an i-dot a dozen or more, no glyph is 200
+    rows high, and a long word can be as wide as a short rule, so the width test is off -- and nobody has tuned them on real scans."""
+    _fields_ = [(n, C.c_int32) for n in ("threshold", "light_text", "connectivity", "min_area", "max_w", "max_h")] + [("reserved", C.c_int32 * 2)]
+
+    def __init__(self, threshold=-1, light_text=0, connectivity=8, min_area=6, max_w=0, max_h=200):
+        super().__init__(int(threshold), int(light_text), int(connectivity), int(min_area), int(max_w), int(max_h), (C.c_int32 * 2)(0, 0))
+
+
 class Box(C.Structure):
     """mirror of `aocr_box` (include/aocr.h): half-open [x0,x1) x [y0,y1), line number, ink pixels."""
     _fields_ = [(n, C.c_int32) for n in ("x0", "y0", "x1", "y1", "line", "ink")]
@@ -177,6 +188,10 @@ SIGNATURES = {
     "aocr_ink_integral": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _i32, _i32, _vp, _vp, C.c_int64, _vp]),
     "aocr_layout_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
     "aocr_layout_blocks": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "aocr_components_scratch_bytes": (C.c_size_t, [_i32, _i32]),
+    "aocr_label_components": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, C.c_int64, _i32, _vp, _vp]),
+    "aocr_clean_scratch_bytes": (C.c_size_t, [_i32, _i32]),
+    "aocr_clean_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, C.c_int64, _vp]),
     "aocr_beam_select": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32]),
 }
 

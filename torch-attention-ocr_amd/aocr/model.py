@@ -440,7 +440,7 @@ class Model:
         return res
 
     def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None, flatten=None,
-                       layout=None):
+                       layout=None, clean=None):
         """Read a scanned page: segment it into word boxes (aocr_segment_page), crop them (aocr_crop_lines) and recognise the crops.
         page: a uint8 (H,W) numpy array or tensor (gray; a 3-D array raises ValueError: colour pages are out of scope).  params: an
         `aocr.SegmentParams` (default: Otsu threshold, dark text).  The counts and boxes are read back once (the one sync), then the boxes are
@@ -468,8 +468,13 @@ class Model:
         coordinates and the line numbers continued across blocks on the device, and all counts and boxes are read back together: the SECOND
         sync (this path has two, the others one).  Crops are taken from the whole page.  The namespace is in reading order (block, then
         line, then x) and also carries block (n): the block of every box, blocks (m,4) x0 y0 x1 y1, block_depth (m), n_blocks and
-        layout_overflow; truncated is true when any block truncated."""
-        from .page import (bucket_width, crop_lines_device, deskew_page_device, estimate_skew_device, flatten_page_device, layout_page_device,
+        layout_overflow; truncated is true when any block truncated.
+        clean: None or False (the default) reads the page as it is.  True or an `aocr.CleanParams` first paints over the connected components of
+        the ink that cannot be text (aocr_clean_page: specks and rules; True: the defaults with the threshold and light_text of `params`),
+        after flatten and before deskew; everything after it reads the cleaned page.  Enqueued on the same stream; its eight counts come back
+        with the existing readback (one sync, two with layout).  The namespace then also carries clean_components, clean_specks, clean_rules
+        and clean_ink_removed."""
+        from .page import (bucket_width, clean_page_device, crop_lines_device, deskew_page_device, estimate_skew_device, flatten_page_device, layout_page_device,
                            segment_page_device, source_corners)
         if isinstance(page, np.ndarray):
             if page.ndim != 2 or page.dtype != np.uint8:
@@ -486,6 +491,11 @@ class Model:
             seg = params if params is not None else _lib.SegmentParams()
             flat = flatten if isinstance(flatten, _lib.FlattenParams) else _lib.FlattenParams(light_text=seg.light_text)
             page = flatten_page_device(page, flat, stream)
+        clean_dev = None
+        if clean is not None and clean is not False:
+            seg = params if params is not None else _lib.SegmentParams()
+            cp = clean if isinstance(clean, _lib.CleanParams) else _lib.CleanParams(threshold=seg.threshold, light_text=seg.light_text)
+            page, clean_dev = clean_page_device(page, cp, stream)
         skew_dev = None
         if deskew is not None and deskew is not False:
             seg = params if params is not None else _lib.SegmentParams()
@@ -498,10 +508,13 @@ class Model:
             lay = layout if isinstance(layout, _lib.LayoutParams) else _lib.LayoutParams()
             max_blocks = 256
             blocks_dev, lcounts_dev, info_dev = layout_page_device(page, lay, seg.threshold, seg.light_text, max_blocks, stream)
-            head = torch.cat([lcounts_dev, info_dev, skew_dev if skew_dev is not None else lcounts_dev[:0], blocks_dev.reshape(-1)]).cpu().numpy()
+            head = torch.cat([lcounts_dev, info_dev, skew_dev if skew_dev is not None else lcounts_dev[:0],
+                              clean_dev if clean_dev is not None else lcounts_dev[:0], blocks_dev.reshape(-1)]).cpu().numpy()
             lcounts, info = head[:4], head[4:8]                   # the first sync
             if skew_dev is not None:
                 skew = head[8:12]
+            if clean_dev is not None:
+                cleaned = head[12:20] if skew_dev is not None else head[8:16]
             nb = int(lcounts[0])
             blocks = head[-6 * max_blocks:].reshape(max_blocks, 6)[:nb]
             block_seg = _lib.SegmentParams(*[getattr(seg, f) for f, _ in seg._fields_][:9])
@@ -530,11 +543,16 @@ class Model:
             truncated = bool((bcounts[:, 0] > max_boxes).any())
         else:
             boxes_dev, counts_dev = segment_page_device(page, params, max_boxes, stream)
-            if skew_dev is None:
+            if skew_dev is None and clean_dev is None:
                 counts = counts_dev.cpu().numpy()
             else:
-                both = torch.cat([counts_dev, skew_dev]).cpu().numpy()
-                counts, skew = both[:4], both[4:]
+                both = torch.cat([counts_dev, skew_dev if skew_dev is not None else counts_dev[:0],
+                                  clean_dev if clean_dev is not None else counts_dev[:0]]).cpu().numpy()
+                counts = both[:4]
+                if skew_dev is not None:
+                    skew = both[4:8]
+                if clean_dev is not None:
+                    cleaned = both[-8:]
             n = int(min(counts[0], max_boxes))
             rows = boxes_dev[:n].cpu().numpy()
             truncated = bool(counts[0] > max_boxes)
@@ -576,6 +594,9 @@ class Model:
             res.n_blocks, res.layout_overflow = nb, bool(lcounts[3])
         if flat is not None:
             res.flatten_radius = int(flat.radius)
+        if clean_dev is not None:
+            res.clean_components, res.clean_specks, res.clean_rules, res.clean_ink_removed = (int(cleaned[0]), int(cleaned[1]), int(cleaned[2]),
+                                                                                              int(cleaned[5]))
         if skew_dev is not None:
             res.skew_steps, res.skew_slope_q16 = int(skew[0]), int(skew[1])
             res.skew_deg = math.degrees(math.atan(res.skew_slope_q16 / 65536.0))

@@ -3,7 +3,8 @@ cut out and scaled like `aocr_preprocess_lines`), the stage in front of `Model.r
 here.  Projection profiles assume horizontal lines in one column: a skewed page goes through `estimate_skew_device` and `deskew_page_device`
 (`aocr_estimate_skew`, `aocr_deskew_page`: a sweep of sheared profiles, then a shear) first; a multi-column page is first cut into blocks by
 `layout_page_device` (`aocr_ink_integral`, `aocr_layout_blocks`: a summed-area table of the ink, then a recursive XY cut) and each block is
-segmented as a view of the page.  One global threshold assumes paper of one brightness: an unevenly lit page goes through `flatten_page_device` (`aocr_flatten_page`) before all of them."""
+segmented as a view of the page.  A profile cannot tell a word from a speck or a ruled line: `clean_page_device` (`aocr_clean_page`: connected
+components of the ink, `label_components_device`) paints over the components that cannot be text before any profile is taken.  One global threshold assumes paper of one brightness: an unevenly lit page goes through `flatten_page_device` (`aocr_flatten_page`) before all of them."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,7 +13,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import Box, FlattenParams, LayoutParams, SegmentParams, SkewParams, check, lib, ptr
+from ._lib import Box, CleanParams, FlattenParams, LayoutParams, SegmentParams, SkewParams, check, lib, ptr
 
 IMG_H = 32
 MIN_ASPECT = 0.5
@@ -183,6 +184,47 @@ def layout_page_device(page_dev, params=None, threshold=-1, light_text=0, max_bl
     return blocks, counts, info
 
 
+def label_components_device(page_dev, threshold=-1, light_text=0, connectivity=8, max_components=4096, stream=None):
+    """(labels (H, W) int32: -1 on paper, on ink the smallest y*W + x of the pixel's connected component; comps (max_components, 6) int32 rows
+    x0 y0 x1 y1 label area in ascending label order, the box half-open and tight; info (4) int32: threshold, total ink, components found, 0)
+    as device tensors (`aocr_label_components`).  Rows of comps beyond min(info[2], max_components) are not written (they hold zeros).
+    threshold -1: Otsu; connectivity 4 or 8.  Enqueues only.  stream: as for `segment_page_device`, the current torch stream; the scratch is
+    freed when this returns."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    dev = page_dev.device
+    need = int(lib.aocr_components_scratch_bytes(H, W))
+    if need == 0:
+        check(1, "aocr_components_scratch_bytes")
+    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    labels = torch.empty((H, W), dtype=torch.int32, device=dev)
+    comps = torch.zeros((max(int(max_components), 1), 6), dtype=torch.int32, device=dev)
+    info = torch.zeros(4, dtype=torch.int32, device=dev)
+    check(lib.aocr_label_components(_stream(stream, dev), ptr(page_dev), pitch, H, W, int(threshold), int(light_text), int(connectivity),
+                                    ptr(scratch), ptr(labels), W, int(max_components), ptr(comps), ptr(info)), "aocr_label_components")
+    return labels, comps, info
+
+
+def clean_page_device(page_dev, params=None, stream=None):
+    """(out, counts): out a new (H, W) uint8 device tensor, the page with its specks and rules painted over by `aocr_clean_page` (every other
+    byte copied), and counts (8) int32: components, specks removed, rules removed, threshold, total ink, ink pixels removed, 0, 0.  params: a
+    `CleanParams` (default: Otsu, 8-connectivity, specks under 6 pixels, rules higher than 200 rows).  Enqueues only.  stream: as for
+    `segment_page_device`, the current torch stream; the scratch (about 12 bytes per pixel) is freed when this returns."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    params = params if params is not None else CleanParams()
+    dev = page_dev.device
+    need = int(lib.aocr_clean_scratch_bytes(H, W))
+    if need == 0:
+        check(1, "aocr_clean_scratch_bytes")
+    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    out = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    counts = torch.zeros(8, dtype=torch.int32, device=dev)
+    check(lib.aocr_clean_page(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), ptr(out), W, ptr(counts)),
+          "aocr_clean_page")
+    return out, counts
+
+
 def source_corners(boxes, slope_q16, H, W):
     """(n, 4, 2) int64: for every box (x0 y0 x1 y1, half-open, deskewed-page coordinates) the source-page (x, y) of its corner pixels
     (x0, y0), (x1-1, y0), (x1-1, y1-1), (x0, y1-1) under `aocr_deskew_page`'s mapping with slope_q16 (clamped like the device clamps it).
@@ -208,6 +250,6 @@ def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
     return min(img_w, int(max_img_w))
 
 
-__all__ = ["SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "Box", "segment_page_device", "crop_lines_device",
+__all__ = ["SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "CleanParams", "Box", "label_components_device", "clean_page_device", "segment_page_device", "crop_lines_device",
            "estimate_skew_device", "deskew_page_device", "flatten_page_device", "ink_integral_device", "layout_page_device", "source_corners",
            "bucket_width"]

@@ -945,4 +945,64 @@ int aocr_layout_blocks(void* stream, const uint32_t* sat_dev, int64_t sat_pitch,
   return check_launch("aocr_layout_blocks");
 }
 
+size_t aocr_components_scratch_bytes(int32_t H, int32_t W) {
+  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26))) {
+    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26)", H, W);
+    return 0;
+  }
+  return components_scratch_bytes(H, W);
+}
+
+static bool disjoint(uintptr_t a0, uintptr_t a1, uintptr_t b0, uintptr_t b1) { return a1 <= b0 || b1 <= a0; }
+
+int aocr_label_components(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t threshold, int32_t light_text,
+                          int32_t connectivity, void* scratch_dev, int32_t* labels_dev, int64_t labels_pitch, int32_t max_components,
+                          aocr_box* comps_dev, int32_t info_dev[4]) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(threshold >= -1 && threshold <= 254, "threshold=%d: 0..254, or -1 for Otsu", threshold);
+  REQUIRE(connectivity == 4 || connectivity == 8, "connectivity=%d: 4 or 8", connectivity);
+  REQUIRE(scratch_dev && labels_dev && info_dev, "NULL argument");
+  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  REQUIRE(((uintptr_t)labels_dev & 3) == 0, "labels_dev must be 4-byte aligned");
+  REQUIRE(labels_pitch >= W, "labels_pitch=%lld is smaller than W=%d", (long long)labels_pitch, W);
+  REQUIRE(max_components >= 1 && max_components <= 65536, "max_components=%d: 1..65536", max_components);
+  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W;
+  const uintptr_t l0 = (uintptr_t)labels_dev, l1 = l0 + ((uintptr_t)(H - 1) * labels_pitch + W) * sizeof(int32_t);
+  const uintptr_t s0 = (uintptr_t)scratch_dev, s1 = s0 + components_scratch_bytes(H, W);
+  REQUIRE(disjoint(l0, l1, p0, p1), "labels_dev overlaps the page");
+  REQUIRE(disjoint(l0, l1, s0, s1), "labels_dev overlaps the scratch");
+  label_components((hipStream_t)stream, page_dev, pitch, H, W, threshold, light_text, connectivity, scratch_dev, labels_dev, labels_pitch,
+                   max_components, comps_dev, info_dev);
+  return check_launch("aocr_label_components");
+}
+
+size_t aocr_clean_scratch_bytes(int32_t H, int32_t W) {
+  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26))) {
+    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26)", H, W);
+    return 0;
+  }
+  return clean_scratch_bytes(H, W);
+}
+
+int aocr_clean_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_clean_params* params,
+                    void* scratch_dev, uint8_t* out_dev, int64_t out_pitch, int32_t counts_dev[8]) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(params, "params is NULL");
+  REQUIRE(params->threshold >= -1 && params->threshold <= 254, "threshold=%d: 0..254, or -1 for Otsu", params->threshold);
+  REQUIRE(params->connectivity == 4 || params->connectivity == 8, "connectivity=%d: 4 or 8", params->connectivity);
+  REQUIRE(params->min_area >= 1, "min_area=%d must be >= 1", params->min_area);
+  REQUIRE(params->max_w >= 0 && params->max_h >= 0, "max_w=%d max_h=%d must be >= 0", params->max_w, params->max_h);
+  REQUIRE(params->reserved[0] == 0 && params->reserved[1] == 0, "reserved words must be 0");
+  REQUIRE(scratch_dev && out_dev && counts_dev, "NULL argument");
+  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  REQUIRE(((uintptr_t)counts_dev & 3) == 0, "counts_dev must be 4-byte aligned");
+  REQUIRE(out_pitch >= W, "out_pitch=%lld is smaller than W=%d", (long long)out_pitch, W);
+  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W, o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(H - 1) * out_pitch + W;
+  const uintptr_t s0 = (uintptr_t)scratch_dev, s1 = s0 + clean_scratch_bytes(H, W);
+  REQUIRE(disjoint(o0, o1, p0, p1), "out_dev overlaps the page");
+  REQUIRE(disjoint(o0, o1, s0, s1), "out_dev overlaps the scratch");
+  clean_page((hipStream_t)stream, page_dev, pitch, H, W, *params, scratch_dev, out_dev, out_pitch, counts_dev);
+  return check_launch("aocr_clean_page");
+}
+
 }  // extern "C"

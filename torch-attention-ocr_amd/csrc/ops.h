@@ -385,6 +385,14 @@ void ink_integral(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int 
 size_t layout_scratch_bytes(int max_blocks);
 void layout_blocks(hipStream_t s, const uint32_t* sat, int64_t sat_pitch, int H, int W, const aocr_layout_params& p, void* scratch, int max_blocks,
                    aocr_box* blocks, int32_t* counts);
+// connected components (components.hip; include/aocr.h: aocr_label_components, aocr_clean_page): canonical labels, area and box per component,
+// and the page with its specks and rules painted over
+size_t components_scratch_bytes(int H, int W);
+void label_components(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, int threshold, int light_text, int connectivity,
+                      void* scratch, int32_t* labels, int64_t labels_pitch, int max_components, aocr_box* comps, int32_t* info);
+size_t clean_scratch_bytes(int H, int W);
+void clean_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_clean_params& p, void* scratch, uint8_t* out,
+                int64_t out_pitch, int32_t* counts);
 // crops (data.hip; aocr_crop_lines): preprocess_lines' scaling of n box rectangles of a pitched page, n = min(n_boxes, count[0]) on the device
 void crop_lines(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_box* boxes, const int32_t* count, int n_boxes,
                 int out_h, int out_w, float* out);
