@@ -736,6 +736,43 @@ int aocr_clean_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_
                     const aocr_clean_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch,
                     int32_t counts_dev[8]);
 
+/* ---- page orientation: quarter turns, and which way the text lines run, in front of aocr_estimate_skew ------------------------------------
+ * Every stage above reads row profiles and assumes that the lines run along x; aocr_estimate_skew sweeps slopes up to 0.25 only.  A page
+ * fed sideways or upside down is turned here, on the device.  Integer arithmetic only, specified exactly.
+ *
+ * aocr_rotate_page: the page turned by q clockwise quarter turns, exactly numpy.rot90(page, -q):
+ *   q        = (quarter + (orient_dev ? (orient_dev[0] & 2) : 0)) & 3.  quarter is 0..3: the host fixes the odd part, because it changes the
+ *            output's shape; the device may add a half turn, which does not: orient_dev[0] is read on the device (no host read in
+ *            between, as aocr_deskew_page reads skew_dev); its odd bit is ignored;
+ *   shape    the output has Ho x Wo pixels, out_pitch >= Wo:  Ho, Wo = H, W for an even quarter, W, H for an odd one;
+ *   q = 0    out[y][x] = page[y][x]                 q = 1    out[y][x] = page[H-1-x][y]
+ *   q = 2    out[y][x] = page[H-1-y][W-1-x]         q = 3    out[y][x] = page[x][W-1-y]
+ * The page follows the rules of aocr_deskew_page: any base address, any pitch >= W, 1 <= H, W <= 16384, H*W <= 2^26; out_dev: Ho rows of Wo
+ * bytes, out_pitch >= Wo apart, any alignment; bytes between Wo and out_pitch are untouched; it must not overlap the page.  No scratch.
+ * Enqueues only; the result does not depend on launch geometry.  Invalid sizes, NULLs, a quarter outside 0..3 or overlap return an error
+ * before anything is enqueued.
+ *
+ * aocr_estimate_orientation: which way the lines run, from where ink runs start.
+ *   ink      the threshold is `threshold` when 0..254, else (-1) Otsu's: steps 1-2 of aocr_segment_page, bit for bit; ink = (v <= threshold),
+ *            or (v > threshold) with light_text; an Otsu threshold of -1 (one gray value): nothing is ink;
+ *   N_h      the number of ink pixels whose left neighbour (x-1, y) is paper or off the page: the starts of the runs along x;
+ *   N_v      the number of ink pixels whose upper neighbour (x, y-1) is paper or off the page: the starts of the runs along y;
+ *   axis     1 when N_v > N_h, else 0 (a tie keeps the page): the clockwise quarter turns proposed.  Latin text is mostly vertical strokes: a
+ *            stroke h rows high starts h runs along x and one along y, so N_h > N_v when the lines run along x;
+ *   output   orient_dev = [axis, N_h, N_v, the threshold used, the total ink, 0, 0, 0] (4-byte aligned).
+ * All sums are exact integers, at most 2^26.  A quarter turn of the page swaps N_h and N_v exactly, a half turn leaves both unchanged: the
+ * call cannot tell an upright page from one upside down, and the caller chooses between axis and axis + 2 by other means (Model.recognize_page
+ * in the Python host asks the recogniser).  Limits: the margin is thin -- on rendered lowercase text max(N_h, N_v) / min(N_h, N_v) goes down to
+ * 1.03 -- and a page of digits alone decides wrongly (digits are round); N_h and N_v are returned so that a caller can reject a thin margin.
+ * scratch_dev: aocr_orient_scratch_bytes(H, W) bytes, 16-byte aligned, overwritten by the call (0 and an error for bad sizes).
+ * Enqueues only, never synchronises or allocates; the result does not depend on launch geometry, atomics order or run (integer sums
+ * only).  Invalid sizes, a bad threshold or NULLs return an error before anything is enqueued. */
+int aocr_rotate_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                     const int32_t* orient_dev, int32_t quarter, uint8_t* out_dev, int64_t out_pitch);
+size_t aocr_orient_scratch_bytes(int32_t H, int32_t W);
+int aocr_estimate_orientation(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                              int32_t threshold, int32_t light_text, void* scratch_dev, int32_t orient_dev[8]);
+
 #ifdef __cplusplus
 }
 #endif

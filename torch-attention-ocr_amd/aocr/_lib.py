@@ -192,6 +192,9 @@ SIGNATURES = {
     "aocr_label_components": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, C.c_int64, _i32, _vp, _vp]),
     "aocr_clean_scratch_bytes": (C.c_size_t, [_i32, _i32]),
     "aocr_clean_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, C.c_int64, _vp]),
+    "aocr_rotate_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _i32, _vp, C.c_int64]),
+    "aocr_orient_scratch_bytes": (C.c_size_t, [_i32, _i32]),
+    "aocr_estimate_orientation": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _i32, _i32, _vp, _vp]),
     "aocr_beam_select": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32]),
 }
 

@@ -439,63 +439,11 @@ class Model:
             res.word = [lexicon.words[i] if i >= 0 else None for i in res.word_index.tolist()]
         return res
 
-    def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None, flatten=None,
-                       layout=None, clean=None):
-        """Read a scanned page: segment it into word boxes (aocr_segment_page), crop them (aocr_crop_lines) and recognise the crops.
-        page: a uint8 (H,W) numpy array or tensor (gray; a 3-D array raises ValueError: colour pages are out of scope).  params: an
-        `aocr.SegmentParams` (default: Otsu threshold, dark text).  The counts and boxes are read back once (the one sync), then the boxes are
-        bucketed by crop width: `width` an int gives one bucket; otherwise each box gets DataGen's width rule (aocr.page.bucket_width with
-        width_step, capped at max_img_w).  Every bucket is cropped and recognised in chunks of at most batch_size rows through
-        recognize_device and, with a lexicon, Lexicon.nearest.
-        Returns a namespace in reading order (line, then x): boxes (n,4) int32 x0 y0 x1 y1, line (n), ink (n), text, labels (n,max_decoder_l),
-        scores (n), widths (n), threshold, n_found, n_lines, truncated (n_found > max_boxes), and word / word_index / word_distance with a
-        lexicon.  A page without boxes gives empty arrays.
-        deskew: None (the default) segments the page as it is.  True or an `aocr.SkewParams` first estimates the slope of the lines
-        (aocr_estimate_skew; True: the default sweep with the threshold and light_text of `params`) and shears it out (aocr_deskew_page, filled
-        with paper: 0 with light_text, else 255), then segments, crops and recognises the deskewed page, all enqueued on the same stream; the
-        skew words come back with the counts (still one sync).  The namespace then also carries skew_steps, skew_slope_q16, skew_deg
-        (atan(slope / 65536) in degrees) and source_corners (n,4,2): the (x, y) of every box's corner pixels on the page as given
-        (aocr.page.source_corners); boxes are in deskewed-page coordinates.
-        flatten: None or False (the default) reads the page as it is.  True or an `aocr.FlattenParams` first divides the page's background out
-        (aocr_flatten_page; True: radius 16 with the light_text of `params`), for a page whose paper is not evenly lit; the skew estimate, the
-        deskew, the segmentation and the crops then all read the flattened page.  Enqueued on the same stream, still one sync.  The namespace
-        then also carries flatten_radius.
-        layout: None or False (the default) segments the page as one column.  True or an `aocr.LayoutParams` reads a multi-column page: after
-        flatten and deskew the page's ink table and its recursive XY cut are enqueued (aocr_ink_integral, aocr_layout_blocks, at most 256
-        blocks, with the threshold and light_text of `params`), and the blocks, their counts and the page threshold are read back (the skew
-        comes with them): the FIRST sync.  Every block is then segmented as a view of the page (aocr_segment_page with the page threshold, so
-        Otsu is not redone per block; max_boxes applies per block and the padding clamps to the block), the boxes are shifted to page
-        coordinates and the line numbers continued across blocks on the device, and all counts and boxes are read back together: the SECOND
-        sync (this path has two, the others one).  Crops are taken from the whole page.  The namespace is in reading order (block, then
-        line, then x) and also carries block (n): the block of every box, blocks (m,4) x0 y0 x1 y1, block_depth (m), n_blocks and
-        layout_overflow; truncated is true when any block truncated.
-        clean: None or False (the default) reads the page as it is.  True or an `aocr.CleanParams` first paints over the connected components of
-        the ink that cannot be text (aocr_clean_page: specks and rules; True: the defaults with the threshold and light_text of `params`),
-        after flatten and before deskew; everything after it reads the cleaned page.  Enqueued on the same stream; its eight counts come back
-        with the existing readback (one sync, two with layout).  The namespace then also carries clean_components, clean_specks, clean_rules
-        and clean_ink_removed."""
-        from .page import (bucket_width, clean_page_device, crop_lines_device, deskew_page_device, estimate_skew_device, flatten_page_device, layout_page_device,
-                           segment_page_device, source_corners)
-        if isinstance(page, np.ndarray):
-            if page.ndim != 2 or page.dtype != np.uint8:
-                raise ValueError(f"page must be a uint8 (H, W) array, got {page.dtype} {page.shape}: colour pages are out of scope")
-            page = torch.from_numpy(np.ascontiguousarray(page))
-        page = torch.as_tensor(page)
-        if page.dim() != 2 or page.dtype != torch.uint8:
-            raise ValueError(f"page must be a uint8 (H, W) tensor, got {page.dtype} {tuple(page.shape)}: colour pages are out of scope")
-        page = page.to(self.device)
-        beam_size = min(beam_size or 1, self.target_vocab_size)
-        stream = self._stream()
-        flat = None
-        if flatten is not None and flatten is not False:
-            seg = params if params is not None else _lib.SegmentParams()
-            flat = flatten if isinstance(flatten, _lib.FlattenParams) else _lib.FlattenParams(light_text=seg.light_text)
-            page = flatten_page_device(page, flat, stream)
-        clean_dev = None
-        if clean is not None and clean is not False:
-            seg = params if params is not None else _lib.SegmentParams()
-            cp = clean if isinstance(clean, _lib.CleanParams) else _lib.CleanParams(threshold=seg.threshold, light_text=seg.light_text)
-            page, clean_dev = clean_page_device(page, cp, stream)
+    def _page_boxes(self, page, params, max_boxes, deskew, layout, clean_dev, stream):
+        """the middle of recognize_page, from the deskew to the boxes on the host: everything that reads the page in its final orientation and
+        has to be redone when recognize_page(orient=True) turns the page by another half turn.  Returns its locals as a namespace."""
+        from .page import deskew_page_device, estimate_skew_device, layout_page_device, segment_page_device
+        skew = cleaned = blocks = block_id = nb = lcounts = None
         skew_dev = None
         if deskew is not None and deskew is not False:
             seg = params if params is not None else _lib.SegmentParams()
@@ -556,6 +504,108 @@ class Model:
             n = int(min(counts[0], max_boxes))
             rows = boxes_dev[:n].cpu().numpy()
             truncated = bool(counts[0] > max_boxes)
+        return SimpleNamespace(page=page, skew_dev=skew_dev, skew=skew, cleaned=cleaned, lay=lay, blocks=blocks, block_id=block_id, nb=nb,
+                               lcounts=lcounts, boxes_dev=boxes_dev, rows=rows, counts=counts, n=n, truncated=truncated)
+
+    def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None, flatten=None,
+                       layout=None, clean=None, orient=None):
+        """Read a scanned page: segment it into word boxes (aocr_segment_page), crop them (aocr_crop_lines) and recognise the crops.
+        page: a uint8 (H,W) numpy array or tensor (gray; a 3-D array raises ValueError: colour pages are out of scope).  params: an
+        `aocr.SegmentParams` (default: Otsu threshold, dark text).  The counts and boxes are read back once (the one sync), then the boxes are
+        bucketed by crop width: `width` an int gives one bucket; otherwise each box gets DataGen's width rule (aocr.page.bucket_width with
+        width_step, capped at max_img_w).  Every bucket is cropped and recognised in chunks of at most batch_size rows through
+        recognize_device and, with a lexicon, Lexicon.nearest.
+        Returns a namespace in reading order (line, then x): boxes (n,4) int32 x0 y0 x1 y1, line (n), ink (n), text, labels (n,max_decoder_l),
+        scores (n), widths (n), threshold, n_found, n_lines, truncated (n_found > max_boxes), and word / word_index / word_distance with a
+        lexicon.  A page without boxes gives empty arrays.
+        deskew: None (the default) segments the page as it is.  True or an `aocr.SkewParams` first estimates the slope of the lines
+        (aocr_estimate_skew; True: the default sweep with the threshold and light_text of `params`) and shears it out (aocr_deskew_page, filled
+        with paper: 0 with light_text, else 255), then segments, crops and recognises the deskewed page, all enqueued on the same stream; the
+        skew words come back with the counts (still one sync).  The namespace then also carries skew_steps, skew_slope_q16, skew_deg
+        (atan(slope / 65536) in degrees) and source_corners (n,4,2): the (x, y) of every box's corner pixels on the page as given
+        (aocr.page.source_corners); boxes are in deskewed-page coordinates.
+        flatten: None or False (the default) reads the page as it is.  True or an `aocr.FlattenParams` first divides the page's background out
+        (aocr_flatten_page; True: radius 16 with the light_text of `params`), for a page whose paper is not evenly lit; the skew estimate, the
+        deskew, the segmentation and the crops then all read the flattened page.  Enqueued on the same stream, still one sync.  The namespace
+        then also carries flatten_radius.
+        layout: None or False (the default) segments the page as one column.  True or an `aocr.LayoutParams` reads a multi-column page: after
+        flatten and deskew the page's ink table and its recursive XY cut are enqueued (aocr_ink_integral, aocr_layout_blocks, at most 256
+        blocks, with the threshold and light_text of `params`), and the blocks, their counts and the page threshold are read back (the skew
+        comes with them): the FIRST sync.  Every block is then segmented as a view of the page (aocr_segment_page with the page threshold, so
+        Otsu is not redone per block; max_boxes applies per block and the padding clamps to the block), the boxes are shifted to page
+        coordinates and the line numbers continued across blocks on the device, and all counts and boxes are read back together: the SECOND
+        sync (this path has two, the others one).  Crops are taken from the whole page.  The namespace is in reading order (block, then
+        line, then x) and also carries block (n): the block of every box, blocks (m,4) x0 y0 x1 y1, block_depth (m), n_blocks and
+        layout_overflow; truncated is true when any block truncated.
+        clean: None or False (the default) reads the page as it is.  True or an `aocr.CleanParams` first paints over the connected components of
+        the ink that cannot be text (aocr_clean_page: specks and rules; True: the defaults with the threshold and light_text of `params`),
+        after flatten and before deskew; everything after it reads the cleaned page.  Enqueued on the same stream; its eight counts come back
+        with the existing readback (one sync, two with layout).  The namespace then also carries clean_components, clean_specks, clean_rules
+        and clean_ink_removed.
+        orient: None or False (the default) reads the page as it is.  An int 0..3 first turns the page by that many clockwise quarter turns
+        (aocr_rotate_page), after flatten and clean and before deskew: no estimate and no extra sync.  True is automatic: the run starts of
+        the ink are counted along x and along y (aocr_estimate_orientation, with the threshold and light_text of `params`) and read back -- ONE
+        ADDITIONAL sync, which cannot be avoided because the page's shape may change -- and the page is turned by the quarter turn they
+        propose.  The counts cannot tell a page from the same page upside down, so the recogniser is asked: after deskew, layout and
+        segmentation the first min(n, batch_size) boxes are cropped at one width (`width`, or the widest bucket among them) and recognised
+        twice, as cropped and turned by a half turn (torch.flip of the crop batch: a few small crops, not the page); when the flipped crops'
+        mean score is strictly higher, the page is turned by a further half turn and deskew, layout, segmentation and recognition start over
+        on it.  The namespace then also carries orientation (the clockwise quarter turns applied in all), orient_runs ((N_h, N_v); None
+        unless automatic), orient_scores ((mean score as cropped, flipped) of the probe, (0.0, 0.0) for a page without boxes; None unless
+        automatic) and source_boxes (n,4): the boxes on the page as given (aocr.page.unrotate_boxes); boxes are in the coordinates of the
+        page that was segmented, and with deskew source_corners goes through the shear and then the rotation back to the page as given.
+        Limits of the estimate (thin margins, pages of digits): DESIGN.md section 17."""
+        from .page import (bucket_width, clean_page_device, crop_lines_device, estimate_orientation_device, flatten_page_device, rotate_page_device,
+                           source_corners, unrotate_boxes, unrotate_points)
+        if isinstance(page, np.ndarray):
+            if page.ndim != 2 or page.dtype != np.uint8:
+                raise ValueError(f"page must be a uint8 (H, W) array, got {page.dtype} {page.shape}: colour pages are out of scope")
+            page = torch.from_numpy(np.ascontiguousarray(page))
+        page = torch.as_tensor(page)
+        if page.dim() != 2 or page.dtype != torch.uint8:
+            raise ValueError(f"page must be a uint8 (H, W) tensor, got {page.dtype} {tuple(page.shape)}: colour pages are out of scope")
+        page = page.to(self.device)
+        beam_size = min(beam_size or 1, self.target_vocab_size)
+        stream = self._stream()
+        flat = None
+        if flatten is not None and flatten is not False:
+            seg = params if params is not None else _lib.SegmentParams()
+            flat = flatten if isinstance(flatten, _lib.FlattenParams) else _lib.FlattenParams(light_text=seg.light_text)
+            page = flatten_page_device(page, flat, stream)
+        clean_dev = None
+        if clean is not None and clean is not False:
+            seg = params if params is not None else _lib.SegmentParams()
+            cp = clean if isinstance(clean, _lib.CleanParams) else _lib.CleanParams(threshold=seg.threshold, light_text=seg.light_text)
+            page, clean_dev = clean_page_device(page, cp, stream)
+        quarter, page0, orient_runs, orient_scores = None, page, None, None
+        if orient is not None and orient is not False:
+            if orient is True:
+                seg = params if params is not None else _lib.SegmentParams()
+                words = estimate_orientation_device(page, seg.threshold, seg.light_text, stream).cpu().numpy()    # the additional sync
+                quarter, orient_runs = int(words[0]), (int(words[1]), int(words[2]))
+            else:
+                quarter = int(orient)
+                if not 0 <= quarter <= 3:
+                    raise ValueError(f"orient={orient!r}: None, False, True or 0..3 clockwise quarter turns")
+            page = rotate_page_device(page0, quarter, None, stream)
+        st = self._page_boxes(page, params, max_boxes, deskew, layout, clean_dev, stream)
+        if orient is True:
+            m = min(st.n, self.batch_size)                          # which way up: the recogniser reads the first boxes both ways
+            orient_scores = (0.0, 0.0)
+            if m:
+                r = st.rows[:m]
+                pw = int(width) if width is not None else max(bucket_width(int(b[2] - b[0]), int(b[3] - b[1]), self.max_img_w, width_step) for b in r)
+                crops = crop_lines_device(st.page, st.boxes_dev[:m], None, pw, self.img_h, stream)
+                up = self.recognize_device(crops, beam_size, trie)[1].mean()
+                down = self.recognize_device(torch.flip(crops, (2, 3)).contiguous(), beam_size, trie)[1].mean()
+                orient_scores = tuple(float(v) for v in torch.stack([up, down]).cpu().numpy())
+            if orient_scores[1] > orient_scores[0]:
+                quarter = (quarter + 2) & 3
+                page = rotate_page_device(page0, quarter, None, stream)
+                st = self._page_boxes(page, params, max_boxes, deskew, layout, clean_dev, stream)
+        page, skew_dev, skew, cleaned, lay = st.page, st.skew_dev, st.skew, st.cleaned, st.lay
+        blocks, block_id, nb, lcounts = st.blocks, st.block_id, st.nb, st.lcounts
+        boxes_dev, rows, counts, n, truncated = st.boxes_dev, st.rows, st.counts, st.n, st.truncated
         if width is not None:
             widths = np.full(n, int(width), np.int64)
         else:
@@ -601,6 +651,13 @@ class Model:
             res.skew_steps, res.skew_slope_q16 = int(skew[0]), int(skew[1])
             res.skew_deg = math.degrees(math.atan(res.skew_slope_q16 / 65536.0))
             res.source_corners = source_corners(res.boxes, res.skew_slope_q16, page.shape[0], page.shape[1])
+        if quarter is not None:
+            H0, W0 = int(page0.shape[0]), int(page0.shape[1])
+            res.orientation, res.orient_runs, res.orient_scores = quarter, orient_runs, orient_scores
+            res.source_boxes = unrotate_boxes(res.boxes, quarter, H0, W0)
+            if skew_dev is not None:
+                sx, sy = unrotate_points(res.source_corners[:, :, 0], res.source_corners[:, :, 1], quarter, H0, W0)
+                res.source_corners = np.stack([sx, sy], axis=2)
         if lexicon is not None:
             res.word_index, res.word_distance = word_index, word_distance
             res.word = [lexicon.words[i] if i >= 0 else None for i in word_index.tolist()]

@@ -4,7 +4,9 @@ here.  Projection profiles assume horizontal lines in one column: a skewed page 
 (`aocr_estimate_skew`, `aocr_deskew_page`: a sweep of sheared profiles, then a shear) first; a multi-column page is first cut into blocks by
 `layout_page_device` (`aocr_ink_integral`, `aocr_layout_blocks`: a summed-area table of the ink, then a recursive XY cut) and each block is
 segmented as a view of the page.  A profile cannot tell a word from a speck or a ruled line: `clean_page_device` (`aocr_clean_page`: connected
-components of the ink, `label_components_device`) paints over the components that cannot be text before any profile is taken.  One global threshold assumes paper of one brightness: an unevenly lit page goes through `flatten_page_device` (`aocr_flatten_page`) before all of them."""
+components of the ink, `label_components_device`) paints over the components that cannot be text before any profile is taken.  One global threshold assumes paper of one brightness: an unevenly lit page goes through `flatten_page_device` (`aocr_flatten_page`) before all of them.  All of them assume that the lines run along x, the right way up: a page
+fed sideways goes through `estimate_orientation_device` (`aocr_estimate_orientation`: where ink runs start along x and along y) and
+`rotate_page_device` (`aocr_rotate_page`: quarter turns) before the deskew; `unrotate_boxes` takes boxes back to the page as given."""
 from __future__ import annotations
 
 import ctypes as C
@@ -225,6 +227,76 @@ def clean_page_device(page_dev, params=None, stream=None):
     return out, counts
 
 
+def rotate_page_device(page_dev, quarter, orient_dev=None, stream=None):
+    """a new uint8 device tensor: the page turned by `aocr_rotate_page`, numpy.rot90(page, -q) with q = (quarter + (orient_dev[0] & 2)) & 3
+    clockwise quarter turns: (H, W) for an even `quarter`, (W, H) for an odd one.  quarter: a Python int 0..3 (it sets the shape).  orient_dev:
+    None, or an int32 device tensor whose first word may add a half turn (bit 1; read on the device: no host sync; the odd bit is ignored).
+    Enqueues only.  stream: as for `segment_page_device`."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    dev = page_dev.device
+    quarter = int(quarter)
+    if not 0 <= quarter <= 3:
+        raise ValueError(f"quarter={quarter}: 0..3")
+    if orient_dev is not None:
+        assert orient_dev.dtype == torch.int32 and orient_dev.device == dev and orient_dev.numel() >= 1
+        orient_dev = orient_dev.contiguous()
+    Ho, Wo = (W, H) if quarter & 1 else (H, W)
+    out = torch.empty((Ho, Wo), dtype=torch.uint8, device=dev)
+    check(lib.aocr_rotate_page(_stream(stream, dev), ptr(page_dev), pitch, H, W, ptr(orient_dev), quarter, ptr(out), Wo), "aocr_rotate_page")
+    return out
+
+
+def estimate_orientation_device(page_dev, threshold=-1, light_text=0, stream=None):
+    """orient (8) int32 device tensor: axis, N_h, N_v, the threshold used, the total ink, 0, 0, 0 (`aocr_estimate_orientation`).  N_h / N_v:
+    the ink pixels whose left / upper neighbour is paper; axis = 1 when N_v > N_h: the lines run along y and the page wants one clockwise
+    quarter turn (or three: the counts cannot tell up from down).  threshold -1: Otsu.  Enqueues only.  stream: as for
+    `segment_page_device`, the current torch stream; the scratch is freed when this returns."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    dev = page_dev.device
+    need = int(lib.aocr_orient_scratch_bytes(H, W))
+    if need == 0:
+        check(1, "aocr_orient_scratch_bytes")
+    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    orient = torch.zeros(8, dtype=torch.int32, device=dev)
+    check(lib.aocr_estimate_orientation(_stream(stream, dev), ptr(page_dev), pitch, H, W, int(threshold), int(light_text), ptr(scratch),
+                                        ptr(orient)), "aocr_estimate_orientation")
+    return orient
+
+
+def unrotate_points(x, y, quarter, H, W):
+    """pixel (x, y) of the page turned by `quarter` clockwise quarter turns -> the pixel (x, y) of the (H, W) page it came from
+    (`aocr_rotate_page`'s mapping); numpy arrays or ints."""
+    q = int(quarter) & 3
+    if q == 1:
+        return y, H - 1 - x
+    if q == 2:
+        return W - 1 - x, H - 1 - y
+    if q == 3:
+        return W - 1 - y, x
+    return x, y
+
+
+def unrotate_boxes(boxes, quarter, H, W):
+    """(n, 4) int64: half-open boxes x0 y0 x1 y1 on the page turned by `quarter` clockwise quarter turns (`aocr_rotate_page`), mapped back
+    to the page as given; H, W: the shape of the page as given.  Host numpy."""
+    b = np.asarray(boxes, np.int64)
+    b = b.reshape(-1, b.shape[-1] if b.ndim > 1 else 4)[:, :4]
+    x0, y0, x1, y1 = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
+    q = int(quarter) & 3
+    H, W = int(H), int(W)
+    if q == 1:
+        out = [y0, H - x1, y1, H - x0]
+    elif q == 2:
+        out = [W - x1, H - y1, W - x0, H - y0]
+    elif q == 3:
+        out = [W - y1, x0, W - y0, x1]
+    else:
+        out = [x0, y0, x1, y1]
+    return np.stack(out, axis=1).reshape(-1, 4)
+
+
 def source_corners(boxes, slope_q16, H, W):
     """(n, 4, 2) int64: for every box (x0 y0 x1 y1, half-open, deskewed-page coordinates) the source-page (x, y) of its corner pixels
     (x0, y0), (x1-1, y0), (x1-1, y1-1), (x0, y1-1) under `aocr_deskew_page`'s mapping with slope_q16 (clamped like the device clamps it).
@@ -252,4 +324,4 @@ def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
 
 __all__ = ["SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "CleanParams", "Box", "label_components_device", "clean_page_device", "segment_page_device", "crop_lines_device",
            "estimate_skew_device", "deskew_page_device", "flatten_page_device", "ink_integral_device", "layout_page_device", "source_corners",
-           "bucket_width"]
+           "rotate_page_device", "estimate_orientation_device", "unrotate_boxes", "unrotate_points", "bucket_width"]

@@ -1005,4 +1005,37 @@ int aocr_clean_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_
   return check_launch("aocr_clean_page");
 }
 
+int aocr_rotate_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const int32_t* orient_dev, int32_t quarter,
+                     uint8_t* out_dev, int64_t out_pitch) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(quarter >= 0 && quarter <= 3, "quarter=%d: 0..3", quarter);
+  REQUIRE(out_dev, "out_dev is NULL");
+  REQUIRE(((uintptr_t)orient_dev & 3) == 0, "orient_dev must be 4-byte aligned");
+  const int32_t Ho = (quarter & 1) ? W : H, Wo = (quarter & 1) ? H : W;
+  REQUIRE(out_pitch >= Wo, "out_pitch=%lld is smaller than the output's width %d", (long long)out_pitch, Wo);
+  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W, o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(Ho - 1) * out_pitch + Wo;
+  REQUIRE(disjoint(o0, o1, p0, p1), "out_dev overlaps the page");
+  rotate_page((hipStream_t)stream, page_dev, pitch, H, W, orient_dev, quarter, out_dev, out_pitch);
+  return check_launch("aocr_rotate_page");
+}
+
+size_t aocr_orient_scratch_bytes(int32_t H, int32_t W) {
+  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26))) {
+    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26)", H, W);
+    return 0;
+  }
+  return orient_scratch_bytes(H, W);
+}
+
+int aocr_estimate_orientation(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t threshold, int32_t light_text,
+                              void* scratch_dev, int32_t orient_dev[8]) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(threshold >= -1 && threshold <= 254, "threshold=%d: 0..254, or -1 for Otsu", threshold);
+  REQUIRE(scratch_dev && orient_dev, "NULL argument");
+  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  REQUIRE(((uintptr_t)orient_dev & 3) == 0, "orient_dev must be 4-byte aligned");
+  estimate_orientation((hipStream_t)stream, page_dev, pitch, H, W, threshold, light_text, scratch_dev, orient_dev);
+  return check_launch("aocr_estimate_orientation");
+}
+
 }  // extern "C"

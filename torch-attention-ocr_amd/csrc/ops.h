@@ -393,6 +393,13 @@ void label_components(hipStream_t s, const uint8_t* page, int64_t pitch, int H, 
 size_t clean_scratch_bytes(int H, int W);
 void clean_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_clean_params& p, void* scratch, uint8_t* out,
                 int64_t out_pitch, int32_t* counts);
+// page orientation (orient.hip; include/aocr.h: aocr_rotate_page, aocr_estimate_orientation): quarter turns of a pitched page, and the run-start
+// counts that say which way the text lines run
+void rotate_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const int32_t* orient, int quarter, uint8_t* out,
+                 int64_t out_pitch);
+size_t orient_scratch_bytes(int H, int W);
+void estimate_orientation(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, int threshold, int light_text, void* scratch,
+                          int32_t* orient);
 // crops (data.hip; aocr_crop_lines): preprocess_lines' scaling of n box rectangles of a pitched page, n = min(n_boxes, count[0]) on the device
 void crop_lines(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_box* boxes, const int32_t* count, int n_boxes,
                 int out_h, int out_w, float* out);
