@@ -773,6 +773,68 @@ size_t aocr_orient_scratch_bytes(int32_t H, int32_t W);
 int aocr_estimate_orientation(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
                               int32_t threshold, int32_t light_text, void* scratch_dev, int32_t orient_dev[8]);
 
+/* ---- page rectification: the paper's four corners on a photograph, and the projective warp to the upright page, in front of everything ------
+ * A photographed page is a quadrilateral on a darker (or lighter) desk, seen in perspective: the lines converge (keystone), which no shear
+ * removes, and aocr_flatten_page would divide the desk out to paper.  These three calls find the paper, plan the map and resample.  The
+ * page follows the rules of aocr_segment_page: gray uint8, any base address, any pitch >= W, 1 <= H, W <= 16384, H*W <= 2^26.
+ *
+ * aocr_find_page_quad (device): the four corners of the paper.  Integer arithmetic only, specified exactly.
+ *   threshold  `threshold` when 0..254, else (-1) Otsu's: steps 1-2 of aocr_segment_page, bit for bit;
+ *   paper      (v > threshold), or (v <= threshold) with dark_paper; an Otsu threshold of -1 (one gray value): nothing is paper;
+ *   sheet      the 8-connected components of the paper mask as aocr_label_components defines them (label = the smallest y*W + x); the sheet
+ *              is the component of the largest area, a tie goes to the smallest label.  Text holes in the sheet do not matter;
+ *   corners    over the sheet's pixels (x, y), exact integer keys with exact ties:
+ *                TL minimises (x+y, then y);    TR maximises (x-y, then -y);
+ *                BR maximises (x+y, then y);    BL minimises (x-y, then -y);
+ *   valid      with P0..P3 = TL, TR, BR, BL: 1 when a sheet exists and all four cross products (P[i+1]-P[i]) x (P[i+2]-P[i+1]), indices
+ *              mod 4, in int64, are > 0 (y points down: the order is clockwise); else 0;
+ *   output     quad_dev = [x_tl, y_tl, x_tr, y_tr, x_br, y_br, x_bl, y_bl, the threshold used, the sheet's area, components found, valid,
+ *              0, 0, 0, 0] (4-byte aligned); with no sheet the eight coordinates are 0.
+ * Limits: the sheet must be turned by less than about 45 degrees, so that each corner is the extreme along its diagonal; rounded or
+ * dog-eared corners move the estimate; a page that fills the frame yields the image corners, and rectifying it is then close to a copy; the
+ * desk must fall on the other side of the threshold from the paper (a desk as bright as the paper joins the sheet).
+ * scratch_dev: aocr_quad_scratch_bytes(H, W) bytes, 16-byte aligned, overwritten by the call (0 and an error for bad sizes): that of
+ * aocr_clean_page, about 12 bytes per pixel.  It and quad_dev must not overlap the page or each other.
+ *
+ * aocr_rectify_plan (host only, plain C++, no device work): the output size and the warp coefficients of a quad x0 y0 .. x3 y3 = TL, TR,
+ * BR, BL (host memory; every coordinate within +-2^20).
+ *   checks     the quad must pass the valid test above, else an error;
+ *   size       Wo = Wo_in when > 0, else isqrt(max(|TR-TL|^2, |BR-BL|^2)) + 1;  Ho = Ho_in when > 0, else
+ *              isqrt(max(|BL-TL|^2, |BR-TR|^2)) + 1;  isqrt is the floor integer square root of an int64.  Wo or Ho > 16384, or
+ *              Wo*Ho > 2^26, is an error naming the size: the caller passes a smaller one.  size = [Wo, Ho];
+ *   map        Heckbert's square-to-quad map; it maps output to source, so no matrix is inverted.  Integers first, in int64:
+ *                dx1 = x1-x2, dx2 = x3-x2, dx3 = x0-x1+x2-x3, the same for y;
+ *                den = dx1*dy2 - dy1*dx2,  gn = dx3*dy2 - dy3*dx2,  hn = dx1*dy3 - dy1*dx3;
+ *              then doubles, each operation rounded on its own, in this order:
+ *                g = gn/den, h = hn/den;
+ *                a = (x1-x0) + g*x1,  b = (x3-x0) + h*x3,  c = x0;    d = (y1-y0) + g*y1,  e = (y3-y0) + h*y3,  f = y0;
+ *                U = max(Wo-1, 1), V = max(Ho-1, 1);
+ *                coef = [a*V, b*U, c*(U*V), d*V, e*U, f*(U*V), g*V, h*U, U*V].
+ * Consequence: the axis-aligned rectangle (x0,y0)..(x0+w, y0+h) with Wo = w+1, Ho = h+1 gives g = h = 0 and products that are exact
+ * integers below 2^53: aocr_warp_page then maps (x, y) to (x+x0, y+y0) exactly and copies the rectangle bit for bit.
+ *
+ * aocr_warp_page (device): the projective resample, bilinear with 8 fractional bits.  coef is a HOST pointer, copied into the kernel's
+ * arguments (the host has read the quad anyway, to learn the output's shape).  Per output pixel (x, y), in double, each operation
+ * rounded on its own, left to right:
+ *   nx = (c0*x + c1*y) + c2;   ny = (c3*x + c4*y) + c5;   dn = (c6*x + c7*y) + c8;
+ *   the pixel is fill (0..255) when !(dn > 0), or X = nx/dn is not within [-1, W], or Y = ny/dn is not within [-1, H] (negated
+ *   comparisons: a NaN falls to fill); otherwise
+ *   qx = (int64)floor(X*256.0 + 0.5), ix = qx >> 8, fx = qx & 255 (arithmetic shift), the same for y;
+ *   taps p00 = (ix,iy), p10 = (ix+1,iy), p01 = (ix,iy+1), p11 = (ix+1,iy+1); a tap off the page reads fill;
+ *   top = p00*(256-fx) + p10*fx;   bot = p01*(256-fx) + p11*fx;   out = (top*(256-fy) + bot*fy + 32768) >> 16.
+ * The divisions are correctly rounded.  out_dev follows the rules of aocr_deskew_page: Ho rows of Wo bytes (1 <= Ho, Wo <= 16384,
+ * Ho*Wo <= 2^26), out_pitch >= Wo apart, any alignment; bytes between Wo and out_pitch are untouched; it must not overlap the page.  No
+ * scratch.
+ * The device calls enqueue only, never synchronise or allocate; the results do not depend on launch geometry, atomics order or run (integer
+ * maxima; one thread per output byte).  Invalid sizes, a bad threshold or fill, NULLs or overlap return an error before anything is
+ * enqueued and leave the outputs untouched. */
+size_t aocr_quad_scratch_bytes(int32_t H, int32_t W);
+int aocr_find_page_quad(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                        int32_t threshold, int32_t dark_paper, void* scratch_dev, int32_t quad_dev[16]);
+int aocr_rectify_plan(const int32_t quad[8], int32_t Wo_in, int32_t Ho_in, int32_t size[2], double coef[9]);
+int aocr_warp_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                   const double coef[9], int32_t fill, uint8_t* out_dev, int64_t out_pitch, int32_t Ho, int32_t Wo);
+
 #ifdef __cplusplus
 }
 #endif

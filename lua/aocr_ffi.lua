@@ -117,6 +117,10 @@ int aocr_clean_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_
 int aocr_rotate_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const int32_t* orient_dev, int32_t quarter, uint8_t* out_dev, int64_t out_pitch);
 size_t aocr_orient_scratch_bytes(int32_t H, int32_t W);
 int aocr_estimate_orientation(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t threshold, int32_t light_text, void* scratch_dev, int32_t orient_dev[8]);
+size_t aocr_quad_scratch_bytes(int32_t H, int32_t W);
+int aocr_find_page_quad(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t threshold, int32_t dark_paper, void* scratch_dev, int32_t quad_dev[16]);
+int aocr_rectify_plan(const int32_t quad[8], int32_t Wo_in, int32_t Ho_in, int32_t size[2], double coef[9]);
+int aocr_warp_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const double coef[9], int32_t fill, uint8_t* out_dev, int64_t out_pitch, int32_t Ho, int32_t Wo);
 ]]
 
 local M = {}

@@ -95,6 +95,18 @@ class CleanParams(C.Structure):
         super().__init__(int(threshold), int(light_text), int(connectivity), int(min_area), int(max_w), int(max_h), (C.c_int32 * 2)(0, 0))
 
 
+class RectifyParams:
+    """how `Model.recognize_page(rectify=...)` finds and straightens a photographed page (`aocr_find_page_quad`, `aocr_rectify_plan`,
+    `aocr_warp_page`; plain Python: there is no C struct behind it).  threshold -1: Otsu; dark_paper 1: the paper is the dark side of the threshold
+    (rectify=True takes the segment params' light_text for it); width / height 0: the lengths of the quad's longer sides; the quad is used only when it is valid and the sheet covers at least
+    min_area_percent of the photograph; fill None: the paper colour, as for deskew."""
+
+    def __init__(self, threshold=-1, dark_paper=0, width=0, height=0, min_area_percent=10, fill=None):
+        self.threshold, self.dark_paper = int(threshold), int(dark_paper)
+        self.width, self.height, self.min_area_percent = int(width), int(height), int(min_area_percent)
+        self.fill = None if fill is None else int(fill)
+
+
 class Box(C.Structure):
     """mirror of `aocr_box` (include/aocr.h): half-open [x0,x1) x [y0,y1), line number, ink pixels."""
     _fields_ = [(n, C.c_int32) for n in ("x0", "y0", "x1", "y1", "line", "ink")]
@@ -195,6 +207,10 @@ SIGNATURES = {
     "aocr_rotate_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _i32, _vp, C.c_int64]),
     "aocr_orient_scratch_bytes": (C.c_size_t, [_i32, _i32]),
     "aocr_estimate_orientation": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "aocr_quad_scratch_bytes": (C.c_size_t, [_i32, _i32]),
+    "aocr_find_page_quad": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "aocr_rectify_plan": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    "aocr_warp_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _i32, _vp, C.c_int64, _i32, _i32]),
     "aocr_beam_select": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32]),
 }
 

@@ -508,7 +508,7 @@ class Model:
                                lcounts=lcounts, boxes_dev=boxes_dev, rows=rows, counts=counts, n=n, truncated=truncated)
 
     def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None, flatten=None,
-                       layout=None, clean=None, orient=None):
+                       layout=None, clean=None, orient=None, rectify=None):
         """Read a scanned page: segment it into word boxes (aocr_segment_page), crop them (aocr_crop_lines) and recognise the crops.
         page: a uint8 (H,W) numpy array or tensor (gray; a 3-D array raises ValueError: colour pages are out of scope).  params: an
         `aocr.SegmentParams` (default: Otsu threshold, dark text).  The counts and boxes are read back once (the one sync), then the boxes are
@@ -554,9 +554,23 @@ class Model:
         unless automatic), orient_scores ((mean score as cropped, flipped) of the probe, (0.0, 0.0) for a page without boxes; None unless
         automatic) and source_boxes (n,4): the boxes on the page as given (aocr.page.unrotate_boxes); boxes are in the coordinates of the
         page that was segmented, and with deskew source_corners goes through the shear and then the rotation back to the page as given.
-        Limits of the estimate (thin margins, pages of digits): DESIGN.md section 17."""
-        from .page import (bucket_width, clean_page_device, crop_lines_device, estimate_orientation_device, flatten_page_device, rotate_page_device,
-                           source_corners, unrotate_boxes, unrotate_points)
+        Limits of the estimate (thin margins, pages of digits): DESIGN.md section 17.
+        rectify: None or False (the default) reads the page as it is.  Anything else treats the page as a photograph, a sheet of paper lying
+        on a desk and seen in perspective, and straightens it FIRST, before flatten: flatten would divide the desk out to paper, and no later
+        stage could then tell the two apart.  True or an `aocr.RectifyParams` finds the paper's corners on the device (aocr_find_page_quad:
+        the extremes along the diagonals of the largest component on the paper side of an Otsu threshold; True: dark_paper = the light_text
+        of `params`) and reads the 16 words back -- ONE ADDITIONAL sync, which cannot be avoided because the corners set the shape of the
+        page that every later stage reads.  When the quad is valid and the sheet covers at least min_area_percent of the photograph, the
+        output size and the coefficients are planned on the host (aocr_rectify_plan) and the page is resampled (aocr_warp_page, filled with
+        paper: 0 with light_text, else 255); otherwise the page is used as it is.  A sequence of four (x, y) corners in the order TL, TR,
+        BR, BL is used as given: no estimate and no extra sync; a quad that is not convex and clockwise raises ValueError.  The namespace
+        then also carries rectified (bool), rectify_quad ((4,2) int, None when no sheet was found), rectify_size ((Wo, Ho), None unless
+        rectified), rectify_area (the sheet's pixels, None for corners given) and photo_corners (n,4,2) float64: the corner pixels of every
+        box -- source_corners with deskew, those of source_boxes with orient, else those of boxes -- carried back onto the photograph
+        (aocr.page.warp_points).  Limits (sheets turned by 45 degrees or more, dog ears, a desk as bright as the paper): DESIGN.md
+        section 18."""
+        from .page import (bucket_width, clean_page_device, crop_lines_device, estimate_orientation_device, find_page_quad_device, flatten_page_device,
+                           rectify_plan, rotate_page_device, source_corners, unrotate_boxes, unrotate_points, warp_page_device, warp_points)
         if isinstance(page, np.ndarray):
             if page.ndim != 2 or page.dtype != np.uint8:
                 raise ValueError(f"page must be a uint8 (H, W) array, got {page.dtype} {page.shape}: colour pages are out of scope")
@@ -567,6 +581,27 @@ class Model:
         page = page.to(self.device)
         beam_size = min(beam_size or 1, self.target_vocab_size)
         stream = self._stream()
+        rect = None
+        if rectify is not None and rectify is not False:
+            seg = params if params is not None else _lib.SegmentParams()
+            rect = SimpleNamespace(used=False, quad=None, size=None, area=None, coef=None)
+            if rectify is True or isinstance(rectify, _lib.RectifyParams):
+                rp = rectify if isinstance(rectify, _lib.RectifyParams) else _lib.RectifyParams(dark_paper=seg.light_text)
+                words = find_page_quad_device(page, rp.threshold, rp.dark_paper, stream).cpu().numpy()         # the additional sync
+                rect.area = int(words[9])
+                if rect.area > 0:
+                    rect.quad = words[:8].reshape(4, 2).astype(np.int64)
+                rect.used = bool(words[11]) and rect.area * 100 >= rp.min_area_percent * int(page.shape[0]) * int(page.shape[1])
+            else:
+                rp = _lib.RectifyParams(dark_paper=seg.light_text)
+                q = np.asarray(rectify)
+                if q.shape != (4, 2) or not np.all(q == np.round(q)):
+                    raise ValueError(f"rectify={rectify!r}: None, False, True, an aocr.RectifyParams or four integer (x, y) corners TL, TR, BR, BL")
+                rect.quad, rect.used = q.astype(np.int64), True
+            if rect.used:
+                rect.size, rect.coef = rectify_plan(rect.quad, rp.width, rp.height)
+                fill = rp.fill if rp.fill is not None else (0 if seg.light_text else 255)
+                page = warp_page_device(page, rect.coef, rect.size, fill, stream)
         flat = None
         if flatten is not None and flatten is not False:
             seg = params if params is not None else _lib.SegmentParams()
@@ -658,6 +693,19 @@ class Model:
             if skew_dev is not None:
                 sx, sy = unrotate_points(res.source_corners[:, :, 0], res.source_corners[:, :, 1], quarter, H0, W0)
                 res.source_corners = np.stack([sx, sy], axis=2)
+        if rect is not None:
+            res.rectified, res.rectify_quad, res.rectify_size, res.rectify_area = rect.used, rect.quad, rect.size, rect.area
+            if skew_dev is not None:
+                pc = res.source_corners
+            else:
+                b = (res.source_boxes if quarter is not None else res.boxes).astype(np.int64).reshape(-1, 4)
+                pc = np.stack([np.stack([b[:, 0], b[:, 2] - 1, b[:, 2] - 1, b[:, 0]], axis=1),
+                               np.stack([b[:, 1], b[:, 1], b[:, 3] - 1, b[:, 3] - 1], axis=1)], axis=2)
+            pc = pc.astype(np.float64)
+            if rect.used:
+                px, py = warp_points(rect.coef, pc[:, :, 0], pc[:, :, 1])
+                pc = np.stack([px, py], axis=2)
+            res.photo_corners = pc
         if lexicon is not None:
             res.word_index, res.word_distance = word_index, word_distance
             res.word = [lexicon.words[i] if i >= 0 else None for i in word_index.tolist()]

@@ -6,7 +6,10 @@ here.  Projection profiles assume horizontal lines in one column: a skewed page 
 segmented as a view of the page.  A profile cannot tell a word from a speck or a ruled line: `clean_page_device` (`aocr_clean_page`: connected
 components of the ink, `label_components_device`) paints over the components that cannot be text before any profile is taken.  One global threshold assumes paper of one brightness: an unevenly lit page goes through `flatten_page_device` (`aocr_flatten_page`) before all of them.  All of them assume that the lines run along x, the right way up: a page
 fed sideways goes through `estimate_orientation_device` (`aocr_estimate_orientation`: where ink runs start along x and along y) and
-`rotate_page_device` (`aocr_rotate_page`: quarter turns) before the deskew; `unrotate_boxes` takes boxes back to the page as given."""
+`rotate_page_device` (`aocr_rotate_page`: quarter turns) before the deskew; `unrotate_boxes` takes boxes back to the page as given.  A
+photographed page, a quadrilateral on a desk seen in perspective, goes through `find_page_quad_device` (`aocr_find_page_quad`: the corners
+of the largest paper component), `rectify_plan` (`aocr_rectify_plan`, host only) and `warp_page_device` (`aocr_warp_page`: the projective
+resample) before all of them; `warp_points` takes points of the rectified page back to the photograph."""
 from __future__ import annotations
 
 import ctypes as C
@@ -15,7 +18,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import Box, CleanParams, FlattenParams, LayoutParams, SegmentParams, SkewParams, check, lib, ptr
+from ._lib import Box, CleanParams, FlattenParams, LayoutParams, RectifyParams, SegmentParams, SkewParams, check, lib, ptr
 
 IMG_H = 32
 MIN_ASPECT = 0.5
@@ -312,6 +315,70 @@ def source_corners(boxes, slope_q16, H, W):
     return np.stack([sx, sy], axis=2)
 
 
+def find_page_quad_device(page_dev, threshold=-1, dark_paper=0, stream=None):
+    """quad (16) int32 device tensor: x y of the corners TL, TR, BR, BL of the paper, the threshold used, the sheet's area, components found,
+    valid, 0, 0, 0, 0 (`aocr_find_page_quad`): the extremes along the diagonals of the largest 8-connected component of (v > threshold), or
+    of (v <= threshold) with dark_paper.  threshold -1: Otsu.  Enqueues only.  stream: as for `segment_page_device`, the current torch
+    stream; the scratch (about 12 bytes per pixel) is freed when this returns."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    dev = page_dev.device
+    need = int(lib.aocr_quad_scratch_bytes(H, W))
+    if need == 0:
+        check(1, "aocr_quad_scratch_bytes")
+    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    quad = torch.zeros(16, dtype=torch.int32, device=dev)
+    check(lib.aocr_find_page_quad(_stream(stream, dev), ptr(page_dev), pitch, H, W, int(threshold), int(dark_paper), ptr(scratch), ptr(quad)),
+          "aocr_find_page_quad")
+    return quad
+
+
+def rectify_plan(quad, width=0, height=0):
+    """((Wo, Ho), coef (9) float64) of `aocr_rectify_plan` for the corners TL, TR, BR, BL: quad is eight ints x0 y0 .. x3 y3 or a (4, 2)
+    array.  width / height 0: the lengths of the quad's longer sides.  Host only.  A quad that is not convex and clockwise, or an output
+    that would be too large, raises ValueError."""
+    q = np.asarray(quad).reshape(-1)
+    if q.size != 8 or not np.all(q == np.round(q)) or np.any(np.abs(q) > (1 << 20)):
+        raise ValueError(f"quad must be four integer (x, y) corners within +-2^20, got {quad!r}")
+    q = (C.c_int32 * 8)(*[int(v) for v in q])
+    size, coef = (C.c_int32 * 2)(), (C.c_double * 9)()
+    if lib.aocr_rectify_plan(q, int(width), int(height), size, coef) != 0:
+        from ._lib import last_error
+        raise ValueError(f"aocr_rectify_plan: {last_error()}")
+    return (int(size[0]), int(size[1])), np.array(list(coef), np.float64)
+
+
+def warp_page_device(page_dev, coef, size, fill=255, stream=None):
+    """a new (Ho, Wo) uint8 device tensor, size = (Wo, Ho): the page resampled by `aocr_warp_page` through the nine coefficients of
+    `rectify_plan` (a host array: they travel in the kernel's arguments); `fill` where the source is outside the page.  Enqueues only.
+    stream: as for `segment_page_device`."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    dev = page_dev.device
+    c = np.ascontiguousarray(np.asarray(coef, np.float64).reshape(-1))
+    if c.size != 9:
+        raise ValueError("coef must hold nine doubles")
+    Wo, Ho = int(size[0]), int(size[1])
+    if Wo < 1 or Ho < 1:
+        raise ValueError(f"bad output size {size!r}")
+    out = torch.empty((Ho, Wo), dtype=torch.uint8, device=dev)
+    check(lib.aocr_warp_page(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.c_void_p(c.ctypes.data), int(fill), ptr(out), Wo, Ho, Wo),
+          "aocr_warp_page")
+    return out
+
+
+def warp_points(coef, x, y):
+    """(X, Y) float64: where `aocr_warp_page` with these coefficients samples the photograph for the pixel (x, y) of the rectified page -- the
+    same expression, one numpy operation per operation (no range test: the caller sees infinities and NaNs as they come).  Host numpy."""
+    c = np.asarray(coef, np.float64).reshape(-1)
+    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+    with np.errstate(all="ignore"):
+        nx = (c[0] * x + c[1] * y) + c[2]
+        ny = (c[3] * x + c[4] * y) + c[5]
+        dn = (c[6] * x + c[7] * y) + c[8]
+        return nx / dn, ny / dn
+
+
 def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
     """DataGen's width rule for a w x h box, ceil(clamp(w/h, 0.5, max_aspect) * 32), rounded up to a multiple of width_step and capped at
     max_img_w.  max_aspect None: max_img_w / 32."""
@@ -322,6 +389,6 @@ def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
     return min(img_w, int(max_img_w))
 
 
-__all__ = ["SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "CleanParams", "Box", "label_components_device", "clean_page_device", "segment_page_device", "crop_lines_device",
+__all__ = ["RectifyParams", "find_page_quad_device", "rectify_plan", "warp_page_device", "warp_points", "SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "CleanParams", "Box", "label_components_device", "clean_page_device", "segment_page_device", "crop_lines_device",
            "estimate_skew_device", "deskew_page_device", "flatten_page_device", "ink_integral_device", "layout_page_device", "source_corners",
            "rotate_page_device", "estimate_orientation_device", "unrotate_boxes", "unrotate_points", "bucket_width"]

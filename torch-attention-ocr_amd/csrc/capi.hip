@@ -1038,4 +1038,55 @@ int aocr_estimate_orientation(void* stream, const uint8_t* page_dev, int64_t pit
   return check_launch("aocr_estimate_orientation");
 }
 
+size_t aocr_quad_scratch_bytes(int32_t H, int32_t W) {
+  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26))) {
+    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26)", H, W);
+    return 0;
+  }
+  return quad_scratch_bytes(H, W);
+}
+
+int aocr_find_page_quad(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t threshold, int32_t dark_paper,
+                        void* scratch_dev, int32_t quad_dev[16]) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(threshold >= -1 && threshold <= 254, "threshold=%d: 0..254, or -1 for Otsu", threshold);
+  REQUIRE(scratch_dev && quad_dev, "NULL argument");
+  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  REQUIRE(((uintptr_t)quad_dev & 3) == 0, "quad_dev must be 4-byte aligned");
+  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W;
+  const uintptr_t s0 = (uintptr_t)scratch_dev, s1 = s0 + quad_scratch_bytes(H, W);
+  const uintptr_t q0 = (uintptr_t)quad_dev, q1 = q0 + 16 * sizeof(int32_t);
+  REQUIRE(disjoint(s0, s1, p0, p1), "scratch_dev overlaps the page");
+  REQUIRE(disjoint(q0, q1, p0, p1), "quad_dev overlaps the page");
+  REQUIRE(disjoint(q0, q1, s0, s1), "quad_dev overlaps the scratch");
+  find_page_quad((hipStream_t)stream, page_dev, pitch, H, W, threshold, dark_paper, scratch_dev, quad_dev);
+  return check_launch("aocr_find_page_quad");
+}
+
+int aocr_rectify_plan(const int32_t quad[8], int32_t Wo_in, int32_t Ho_in, int32_t size[2], double coef[9]) {
+  REQUIRE(quad && size && coef, "NULL argument");
+  char msg[256] = "";
+  int32_t sz[2];
+  double c[9];
+  if (rectify_plan(quad, Wo_in, Ho_in, sz, c, msg, sizeof msg)) return fail("%s", msg);
+  size[0] = sz[0]; size[1] = sz[1];
+  for (int i = 0; i < 9; ++i) coef[i] = c[i];
+  return 0;
+}
+
+int aocr_warp_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const double coef[9], int32_t fill,
+                   uint8_t* out_dev, int64_t out_pitch, int32_t Ho, int32_t Wo) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(coef, "coef is NULL");
+  REQUIRE(out_dev, "out_dev is NULL");
+  REQUIRE(Ho >= 1 && Wo >= 1 && Ho <= 16384 && Wo <= 16384 && (int64_t)Ho * Wo <= ((int64_t)1 << 26),
+          "bad output size Ho=%d Wo=%d: 1..16384 each, Ho*Wo <= 2^26", Ho, Wo);
+  REQUIRE(out_pitch >= Wo, "out_pitch=%lld is smaller than Wo=%d", (long long)out_pitch, Wo);
+  REQUIRE(fill >= 0 && fill <= 255, "fill=%d: 0..255", fill);
+  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W, o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(Ho - 1) * out_pitch + Wo;
+  REQUIRE(disjoint(o0, o1, p0, p1), "out_dev overlaps the page");
+  warp_page((hipStream_t)stream, page_dev, pitch, H, W, coef, fill, out_dev, out_pitch, Ho, Wo);
+  return check_launch("aocr_warp_page");
+}
+
 }  // extern "C"

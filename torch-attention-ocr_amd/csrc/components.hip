@@ -29,6 +29,7 @@
 // No workgroup ever waits on another: no look-back, no flags, no grid barrier.  Every loop is bounded by the data (DESIGN.md section 16
 // gives each termination argument).  Integer atomics only: sums, minima and maxima do not depend on their order.
 #include <algorithm>
+#include <cstddef>
 #include "ops.h"
 #include "runs.h"
 
@@ -373,6 +374,12 @@ void label_launches(hipStream_t s, const uint8_t* page, int64_t pitch, int H, in
 
 size_t components_scratch_bytes(int H, int W) { return cc_layout(H, W, false).total; }
 size_t clean_scratch_bytes(int H, int W) { return cc_layout(H, W, true).total; }
+
+static_assert(sizeof(CompStat) == 4 * sizeof(int32_t) && offsetof(CompStat, area) == 0, "ops.h describes the record to rectify.hip");
+ComponentAreas component_areas(int H, int W, void* scratch) {
+  const CcLayout l = cc_layout(H, W, false);
+  return ComponentAreas{reinterpret_cast<const int32_t*>(static_cast<char*>(scratch) + l.stats), l.sw};
+}
 
 void label_components(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, int threshold, int light_text, int connectivity,
                       void* scratch, int32_t* labels, int64_t labels_pitch, int max_components, aocr_box* comps, int32_t* info) {

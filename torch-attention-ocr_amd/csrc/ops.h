@@ -393,6 +393,10 @@ void label_components(hipStream_t s, const uint8_t* page, int64_t pitch, int H, 
 size_t clean_scratch_bytes(int H, int W);
 void clean_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_clean_params& p, void* scratch, uint8_t* out,
                 int64_t out_pitch, int32_t* counts);
+// where the launches of label_components leave every component's area (components.hip): the record of the component whose first pixel in
+// raster order is (rx, ry) is the four words at rec + 4 * (ry * sw + (rx >> 1)): area, min x, max x, max y.  scratch: label_components' own
+struct ComponentAreas { const int32_t* rec; int sw; };
+ComponentAreas component_areas(int H, int W, void* scratch);
 // page orientation (orient.hip; include/aocr.h: aocr_rotate_page, aocr_estimate_orientation): quarter turns of a pitched page, and the run-start
 // counts that say which way the text lines run
 void rotate_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const int32_t* orient, int quarter, uint8_t* out,
@@ -400,6 +404,15 @@ void rotate_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W
 size_t orient_scratch_bytes(int H, int W);
 void estimate_orientation(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, int threshold, int light_text, void* scratch,
                           int32_t* orient);
+// page rectification (rectify.hip; include/aocr.h: aocr_find_page_quad, aocr_rectify_plan, aocr_warp_page): the corners of the paper on a
+// photograph, the output size and coefficients of the projective map (host only; 1 and a message in err_buf on error), and the resample
+constexpr int RECTIFY_COORD_MAX = 1 << 20;
+size_t quad_scratch_bytes(int H, int W);
+void find_page_quad(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, int threshold, int dark_paper, void* scratch,
+                    int32_t* quad);
+int rectify_plan(const int32_t* quad, int Wo_in, int Ho_in, int32_t* size, double* coef, char* err_buf, size_t err_len);
+void warp_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const double* coef, int fill, uint8_t* out, int64_t out_pitch,
+               int Ho, int Wo);
 // crops (data.hip; aocr_crop_lines): preprocess_lines' scaling of n box rectangles of a pitched page, n = min(n_boxes, count[0]) on the device
 void crop_lines(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_box* boxes, const int32_t* count, int n_boxes,
                 int out_h, int out_w, float* out);
