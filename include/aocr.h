@@ -835,6 +835,57 @@ int aocr_rectify_plan(const int32_t quad[8], int32_t Wo_in, int32_t Ho_in, int32
 int aocr_warp_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
                    const double coef[9], int32_t fill, uint8_t* out_dev, int64_t out_pitch, int32_t Ho, int32_t Wo);
 
+/* ---- page scale normalisation: the size of the glyphs, and exact area resampling, between aocr_flatten_page and aocr_clean_page ----------
+ * Every stage above counts in pixels (min_line_h, word_gap, gap_x, min_area, radius ...), and every default is a judgement for text at
+ * 300 dpi.  A page scanned at 150 or 600 dpi breaks them all at once.  These two calls measure how large the glyphs are and resample the
+ * page so that the text has the size the defaults were written for.  Integer arithmetic only, specified exactly.  The page follows the
+ * rules of aocr_segment_page: gray uint8, any base address, any pitch >= W, 1 <= H, W <= 16384, H*W <= 2^26.
+ *
+ * aocr_estimate_glyph_size (device): the quartiles of the glyph size.
+ *   components as aocr_label_components defines them, with params.threshold (0..254, or -1 for Otsu: steps 1-2 of aocr_segment_page, bit
+ *              for bit), light_text and connectivity (4 or 8); an Otsu threshold of -1 (one gray value): there are none;
+ *   size       of a component with the tight box w x h: a = min(w, h), b = max(w, h).  The component qualifies when
+ *              min_size <= a <= max_size and b <= max_aspect * a (in int64); a qualifying component adds one to hist[a];
+ *   quartiles  with n the number of qualifying components, q_k (k = 1, 2, 3) is the element at index floor(k * (n - 1) / 4) of the
+ *              ascending list of their a: the smallest s whose running sum hist[1] + .. + hist[s] exceeds that index;
+ *   output     glyph_dev = [q_2 (the size), q_1, q_3, n, components found, the threshold used, the total ink, 0] (4-byte aligned); the three
+ *              quartiles are 0 when n == 0.
+ * min(w, h) does not change under quarter turns (the call may run before aocr_estimate_orientation) and ignores glyphs merged along the
+ * line, whose box grows along one axis only; max_aspect drops rules and the stems of l and 1.
+ * Limits: the size is a median of component boxes, not an x-height; all-caps text reads larger; touching or broken glyphs move it; below
+ * about 4 pixels it is noise (read n and the quartiles before trusting it).
+ * scratch_dev: aocr_glyph_scratch_bytes(H, W) bytes, 16-byte aligned, overwritten by the call (0 and an error for bad sizes): that of
+ * aocr_clean_page plus a histogram, about 12 bytes per pixel.  It and glyph_dev must not overlap the page or each other.
+ *
+ * aocr_resize_page (device): exact pixel-area resampling of the H x W page to Ho x Wo.  Along x, source pixel x covers [x*Wo, (x+1)*Wo)
+ * and output pixel X covers [X*W, (X+1)*W) on a common axis of W*Wo units:
+ *   wx(x, X) = max(0, min((x+1)*Wo, (X+1)*W) - max(x*Wo, X*W)), which sums to W over x; wy(y, Y) likewise with H and Ho, summing to H;
+ *   S        = sum over y, x of wy(y, Y) * wx(x, X) * page[y][x]                  (<= 255*H*W < 2^34: 64 bits);
+ *   out[Y][X] = floor((S + floor(H*W / 2)) / (H*W)).
+ * Consequences: equal sizes copy the page byte for byte; shrinking by an integer k gives the rounded mean of every k x k block; growing by
+ * an integer k repeats every pixel k x k times; a constant page stays constant.
+ * The page and the output each follow the size rules of aocr_deskew_page (1 <= Ho, Wo <= 16384, Ho*Wo <= 2^26, out_pitch >= Wo, any
+ * alignment; bytes between Wo and out_pitch are untouched), and W <= 8*Wo, Wo <= 8*W, H <= 8*Ho, Ho <= 8*H: at most 9 taps per axis.  The
+ * output must not overlap the page.  No scratch.
+ * Both calls enqueue only, never synchronise or allocate; the results do not depend on launch geometry, atomics order or run (integer sums;
+ * one thread per output byte).  Invalid params or sizes, non-zero reserved words, NULLs or overlap return an error before anything is
+ * enqueued and leave the outputs untouched. */
+typedef struct aocr_glyph_params {
+  int32_t threshold;     /* 0..254: ink = (v <= threshold); -1: Otsu, steps 1-2 of aocr_segment_page, bit for bit */
+  int32_t light_text;    /* 1: ink = (v > threshold) instead */
+  int32_t connectivity;  /* 4 or 8 */
+  int32_t min_size;      /* >= 1: a component whose min(w, h) is smaller does not count */
+  int32_t max_size;      /* min_size..1024: nor one whose min(w, h) is larger */
+  int32_t max_aspect;    /* >= 1: nor one with max(w, h) > max_aspect * min(w, h) */
+  int32_t reserved[2];   /* must be 0 */
+} aocr_glyph_params;
+
+size_t aocr_glyph_scratch_bytes(int32_t H, int32_t W);
+int aocr_estimate_glyph_size(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                             const aocr_glyph_params* params, void* scratch_dev, int32_t glyph_dev[8]);
+int aocr_resize_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                     uint8_t* out_dev, int64_t out_pitch, int32_t Ho, int32_t Wo);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,10 @@ size_t aocr_quad_scratch_bytes(int32_t H, int32_t W);
 int aocr_find_page_quad(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t threshold, int32_t dark_paper, void* scratch_dev, int32_t quad_dev[16]);
 int aocr_rectify_plan(const int32_t quad[8], int32_t Wo_in, int32_t Ho_in, int32_t size[2], double coef[9]);
 int aocr_warp_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const double coef[9], int32_t fill, uint8_t* out_dev, int64_t out_pitch, int32_t Ho, int32_t Wo);
+typedef struct aocr_glyph_params { int32_t threshold; int32_t light_text; int32_t connectivity; int32_t min_size; int32_t max_size; int32_t max_aspect; int32_t reserved[2]; } aocr_glyph_params;
+size_t aocr_glyph_scratch_bytes(int32_t H, int32_t W);
+int aocr_estimate_glyph_size(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_glyph_params* params, void* scratch_dev, int32_t glyph_dev[8]);
+int aocr_resize_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, uint8_t* out_dev, int64_t out_pitch, int32_t Ho, int32_t Wo);
 ]]
 
 local M = {}

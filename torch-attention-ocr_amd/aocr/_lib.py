@@ -107,6 +107,28 @@ class RectifyParams:
         self.fill = None if fill is None else int(fill)
 
 
+class GlyphParams(C.Structure):
+    """mirror of `aocr_glyph_params` (include/aocr.h): which connected components `aocr_estimate_glyph_size` counts as glyphs.  The size of a
+    component is a = min(w, h) of its tight box; it counts when min_size <= a <= max_size and max(w, h) <= max_aspect * a (rules and the
+    stems of l and 1 do not).  threshold -1: Otsu."""
+    _fields_ = [(n, C.c_int32) for n in ("threshold", "light_text", "connectivity", "min_size", "max_size", "max_aspect")] + [("reserved", C.c_int32 * 2)]
+
+    def __init__(self, threshold=-1, light_text=0, connectivity=8, min_size=2, max_size=512, max_aspect=8):
+        super().__init__(int(threshold), int(light_text), int(connectivity), int(min_size), int(max_size), int(max_aspect), (C.c_int32 * 2)(0, 0))
+
+
+class ScaleParams:
+    """how `Model.recognize_page(scale=...)` brings the text of a page to the size the other stages' defaults were written for
+    (`aocr_estimate_glyph_size`, `aocr.scale_plan`, `aocr_resize_page`; plain Python: there is no C struct behind it).  glyph: the
+    `GlyphParams` of the estimate; target: the glyph size to resample to (16: what the estimate reads on the glyph atlas at its native size,
+    the size every default was judged on); the page is left alone when target / size lies within [1 / tolerance, tolerance], or when fewer
+    than min_glyphs components qualified."""
+
+    def __init__(self, glyph=None, target=16, tolerance=1.25, min_glyphs=8):
+        self.glyph = glyph if glyph is not None else GlyphParams()
+        self.target, self.tolerance, self.min_glyphs = int(target), float(tolerance), int(min_glyphs)
+
+
 class Box(C.Structure):
     """mirror of `aocr_box` (include/aocr.h): half-open [x0,x1) x [y0,y1), line number, ink pixels."""
     _fields_ = [(n, C.c_int32) for n in ("x0", "y0", "x1", "y1", "line", "ink")]
@@ -211,6 +233,9 @@ SIGNATURES = {
     "aocr_find_page_quad": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _i32, _i32, _vp, _vp]),
     "aocr_rectify_plan": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "aocr_warp_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _i32, _vp, C.c_int64, _i32, _i32]),
+    "aocr_glyph_scratch_bytes": (C.c_size_t, [_i32, _i32]),
+    "aocr_estimate_glyph_size": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp]),
+    "aocr_resize_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, C.c_int64, _i32, _i32]),
     "aocr_beam_select": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32]),
 }
 

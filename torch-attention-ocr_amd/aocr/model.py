@@ -508,7 +508,7 @@ class Model:
                                lcounts=lcounts, boxes_dev=boxes_dev, rows=rows, counts=counts, n=n, truncated=truncated)
 
     def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None, flatten=None,
-                       layout=None, clean=None, orient=None, rectify=None):
+                       layout=None, clean=None, orient=None, rectify=None, scale=None):
         """Read a scanned page: segment it into word boxes (aocr_segment_page), crop them (aocr_crop_lines) and recognise the crops.
         page: a uint8 (H,W) numpy array or tensor (gray; a 3-D array raises ValueError: colour pages are out of scope).  params: an
         `aocr.SegmentParams` (default: Otsu threshold, dark text).  The counts and boxes are read back once (the one sync), then the boxes are
@@ -568,9 +568,22 @@ class Model:
         rectified), rectify_area (the sheet's pixels, None for corners given) and photo_corners (n,4,2) float64: the corner pixels of every
         box -- source_corners with deskew, those of source_boxes with orient, else those of boxes -- carried back onto the photograph
         (aocr.page.warp_points).  Limits (sheets turned by 45 degrees or more, dog ears, a desk as bright as the paper): DESIGN.md
-        section 18."""
-        from .page import (bucket_width, clean_page_device, crop_lines_device, estimate_orientation_device, find_page_quad_device, flatten_page_device,
-                           rectify_plan, rotate_page_device, source_corners, unrotate_boxes, unrotate_points, warp_page_device, warp_points)
+        section 18.
+        scale: None or False (the default) reads the page at the resolution it has.  Anything else resamples it, after flatten and before
+        clean, so that its text has the size the other stages' pixel defaults were written for (min_line_h, word_gap, gap_x, min_area ...:
+        text at 300 dpi).  True or an `aocr.ScaleParams` measures the glyphs on the device (aocr_estimate_glyph_size: the median of min(w, h)
+        over the component boxes; True: the threshold and light_text of `params`) and reads the 8 words back -- ONE ADDITIONAL sync, which
+        cannot be avoided because the size sets the shape of the page that every later stage reads; aocr.scale_plan then picks the output size
+        (none when the text is within the tolerance of the target, or too few glyphs qualified) and aocr_resize_page resamples by exact pixel
+        areas.  A positive number is the ratio to resample by (0.5 halves both sides): no estimate and no extra sync.  The namespace then also
+        carries scaled (bool), scale_size (the median, None for a ratio given), scale_quartiles ((q_1, q_3), None likewise), scale_glyphs
+        (how many components qualified, None likewise), scale_shape ((Wo, Ho), None unless scaled) and unscaled_corners (n,4,2) float64: the
+        corner pixels of every box -- source_corners with deskew, those of source_boxes with orient, else those of boxes -- on the page as it
+        was before resizing, xs = (x + 0.5) * W / Wo - 0.5 (aocr.page.unscale_points); with rectify, photo_corners goes through this map
+        first.  Limits (a median of boxes, not an x-height; below about 4 pixels the estimate is noise): DESIGN.md section 19."""
+        from .page import (bucket_width, clean_page_device, crop_lines_device, estimate_glyph_size_device, estimate_orientation_device,
+                           find_page_quad_device, flatten_page_device, rectify_plan, resize_page_device, rotate_page_device, scale_plan,
+                           source_corners, unrotate_boxes, unrotate_points, unscale_points, warp_page_device, warp_points)
         if isinstance(page, np.ndarray):
             if page.ndim != 2 or page.dtype != np.uint8:
                 raise ValueError(f"page must be a uint8 (H, W) array, got {page.dtype} {page.shape}: colour pages are out of scope")
@@ -607,6 +620,23 @@ class Model:
             seg = params if params is not None else _lib.SegmentParams()
             flat = flatten if isinstance(flatten, _lib.FlattenParams) else _lib.FlattenParams(light_text=seg.light_text)
             page = flatten_page_device(page, flat, stream)
+        scl = None
+        if scale is not None and scale is not False:
+            seg = params if params is not None else _lib.SegmentParams()
+            H1, W1 = int(page.shape[0]), int(page.shape[1])
+            scl = SimpleNamespace(shape=None, size=None, quartiles=None, glyphs=None, H=H1, W=W1)
+            if scale is True or isinstance(scale, _lib.ScaleParams):
+                sp = scale if isinstance(scale, _lib.ScaleParams) else _lib.ScaleParams(_lib.GlyphParams(threshold=seg.threshold, light_text=seg.light_text))
+                words = estimate_glyph_size_device(page, sp.glyph, stream).cpu().numpy()                      # the additional sync
+                scl.size, scl.quartiles, scl.glyphs = int(words[0]), (int(words[1]), int(words[2])), int(words[3])
+                scl.shape = scale_plan(scl.size, scl.glyphs, H1, W1, sp)
+            else:
+                ok = isinstance(scale, (int, float, np.integer, np.floating)) and not isinstance(scale, bool)
+                if not (ok and math.isfinite(float(scale)) and float(scale) > 0):
+                    raise ValueError(f"scale={scale!r}: None, False, True, an aocr.ScaleParams or a positive ratio")
+                scl.shape = (max(int(math.floor(W1 * float(scale) + 0.5)), 1), max(int(math.floor(H1 * float(scale) + 0.5)), 1))
+            if scl.shape is not None:
+                page = resize_page_device(page, scl.shape, stream)
         clean_dev = None
         if clean is not None and clean is not False:
             seg = params if params is not None else _lib.SegmentParams()
@@ -693,8 +723,7 @@ class Model:
             if skew_dev is not None:
                 sx, sy = unrotate_points(res.source_corners[:, :, 0], res.source_corners[:, :, 1], quarter, H0, W0)
                 res.source_corners = np.stack([sx, sy], axis=2)
-        if rect is not None:
-            res.rectified, res.rectify_quad, res.rectify_size, res.rectify_area = rect.used, rect.quad, rect.size, rect.area
+        if rect is not None or scl is not None:
             if skew_dev is not None:
                 pc = res.source_corners
             else:
@@ -702,6 +731,15 @@ class Model:
                 pc = np.stack([np.stack([b[:, 0], b[:, 2] - 1, b[:, 2] - 1, b[:, 0]], axis=1),
                                np.stack([b[:, 1], b[:, 1], b[:, 3] - 1, b[:, 3] - 1], axis=1)], axis=2)
             pc = pc.astype(np.float64)
+        if scl is not None:
+            res.scaled, res.scale_size, res.scale_quartiles, res.scale_glyphs, res.scale_shape = (scl.shape is not None, scl.size, scl.quartiles,
+                                                                                                  scl.glyphs, scl.shape)
+            if scl.shape is not None:
+                ux, uy = unscale_points(pc[:, :, 0], pc[:, :, 1], scl.H, scl.W, scl.shape[1], scl.shape[0])
+                pc = np.stack([ux, uy], axis=2)
+            res.unscaled_corners = pc
+        if rect is not None:
+            res.rectified, res.rectify_quad, res.rectify_size, res.rectify_area = rect.used, rect.quad, rect.size, rect.area
             if rect.used:
                 px, py = warp_points(rect.coef, pc[:, :, 0], pc[:, :, 1])
                 pc = np.stack([px, py], axis=2)

@@ -9,7 +9,10 @@ fed sideways goes through `estimate_orientation_device` (`aocr_estimate_orientat
 `rotate_page_device` (`aocr_rotate_page`: quarter turns) before the deskew; `unrotate_boxes` takes boxes back to the page as given.  A
 photographed page, a quadrilateral on a desk seen in perspective, goes through `find_page_quad_device` (`aocr_find_page_quad`: the corners
 of the largest paper component), `rectify_plan` (`aocr_rectify_plan`, host only) and `warp_page_device` (`aocr_warp_page`: the projective
-resample) before all of them; `warp_points` takes points of the rectified page back to the photograph."""
+resample) before all of them; `warp_points` takes points of the rectified page back to the photograph.  Every one of them counts in
+pixels of text at 300 dpi: a page scanned at another resolution goes through `estimate_glyph_size_device` (`aocr_estimate_glyph_size`: the
+median of min(w, h) over the component boxes), `scale_plan` (host only) and `resize_page_device` (`aocr_resize_page`: exact area
+resampling) after the flattening; `unscale_points` takes points back to the page before resizing."""
 from __future__ import annotations
 
 import ctypes as C
@@ -18,7 +21,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import Box, CleanParams, FlattenParams, LayoutParams, RectifyParams, SegmentParams, SkewParams, check, lib, ptr
+from ._lib import Box, CleanParams, FlattenParams, GlyphParams, LayoutParams, RectifyParams, ScaleParams, SegmentParams, SkewParams, check, lib, ptr
 
 IMG_H = 32
 MIN_ASPECT = 0.5
@@ -379,6 +382,77 @@ def warp_points(coef, x, y):
         return nx / dn, ny / dn
 
 
+def estimate_glyph_size_device(page_dev, params=None, stream=None):
+    """glyph (8) int32 device tensor: the median q_2 of min(w, h) over the tight boxes of the components that qualify as glyphs, the
+    quartiles q_1 and q_3, how many qualified, components found, the threshold used, the total ink, 0 (`aocr_estimate_glyph_size`).  params:
+    a `GlyphParams` (default: Otsu, dark text, 8-connectivity, sizes 2..512, aspect up to 8).  Enqueues only.  stream: as for
+    `segment_page_device`, the current torch stream; the scratch (about 12 bytes per pixel) is freed when this returns."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    params = params if params is not None else GlyphParams()
+    dev = page_dev.device
+    need = int(lib.aocr_glyph_scratch_bytes(H, W))
+    if need == 0:
+        check(1, "aocr_glyph_scratch_bytes")
+    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    glyph = torch.zeros(8, dtype=torch.int32, device=dev)
+    check(lib.aocr_estimate_glyph_size(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), ptr(glyph)),
+          "aocr_estimate_glyph_size")
+    return glyph
+
+
+def resize_page_device(page_dev, size, stream=None):
+    """a new (Ho, Wo) uint8 device tensor, size = (Wo, Ho): the page resampled by exact pixel areas (`aocr_resize_page`); each axis may
+    shrink or grow by a factor of up to 8.  Enqueues only.  stream: as for `segment_page_device`."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    dev = page_dev.device
+    Wo, Ho = int(size[0]), int(size[1])
+    if Wo < 1 or Ho < 1:
+        raise ValueError(f"bad output size {size!r}")
+    out = torch.empty((Ho, Wo), dtype=torch.uint8, device=dev)
+    check(lib.aocr_resize_page(_stream(stream, dev), ptr(page_dev), pitch, H, W, ptr(out), Wo, Ho, Wo), "aocr_resize_page")
+    return out
+
+
+def scale_plan(size, n, H, W, params=None):
+    """(Wo, Ho), the size to resample an H x W page to so that glyphs of `size` pixels (`estimate_glyph_size_device`'s first word, from `n`
+    qualifying components) come out at params.target pixels; None when the page is to be left alone: n < params.min_glyphs, size == 0, or
+    target / size within [1 / tolerance, tolerance].  Wo = round(W * target / size) in integers, (2*W*target + size) // (2*size), and Ho
+    likewise; both are then clamped to what `aocr_resize_page` takes: a factor of 8 either way, 1..16384, and Ho*Wo <= 2^26 (both sides are
+    shrunk by the same factor).  params: a `ScaleParams`.  Host only."""
+    params = params if params is not None else ScaleParams()
+    size, n, H, W = int(size), int(n), int(H), int(W)
+    if n < params.min_glyphs or size <= 0:
+        return None
+    t = params.target
+    if t <= params.tolerance * size and size <= params.tolerance * t:
+        return None
+
+    def side(L):
+        v = (2 * L * t + size) // (2 * size)
+        v = min(max(v, -(-L // 8)), 8 * L)
+        return min(max(v, 1), 16384)
+
+    Wo, Ho = side(W), side(H)
+    if Ho * Wo > 1 << 26:
+        f = math.sqrt((1 << 26) / (Ho * Wo))
+        Wo, Ho = max(int(Wo * f), -(-W // 8)), max(int(Ho * f), -(-H // 8))
+        while Ho * Wo > 1 << 26:                             # only when a lower bound lifted one side: take it off the longer one
+            if Ho >= Wo:
+                Ho -= 1
+            else:
+                Wo -= 1
+    return Wo, Ho
+
+
+def unscale_points(x, y, H, W, Ho, Wo):
+    """(xs, ys) float64: the centre of pixel (x, y) of the Ho x Wo page `aocr_resize_page` made, on the H x W page it was made from:
+    xs = (x + 0.5) * W / Wo - 0.5, and likewise for y.  Host numpy."""
+    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+    return (x + 0.5) * W / Wo - 0.5, (y + 0.5) * H / Ho - 0.5
+
+
 def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
     """DataGen's width rule for a w x h box, ceil(clamp(w/h, 0.5, max_aspect) * 32), rounded up to a multiple of width_step and capped at
     max_img_w.  max_aspect None: max_img_w / 32."""
@@ -389,6 +463,6 @@ def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
     return min(img_w, int(max_img_w))
 
 
-__all__ = ["RectifyParams", "find_page_quad_device", "rectify_plan", "warp_page_device", "warp_points", "SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "CleanParams", "Box", "label_components_device", "clean_page_device", "segment_page_device", "crop_lines_device",
+__all__ = ["GlyphParams", "ScaleParams", "estimate_glyph_size_device", "resize_page_device", "scale_plan", "unscale_points", "RectifyParams", "find_page_quad_device", "rectify_plan", "warp_page_device", "warp_points", "SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "CleanParams", "Box", "label_components_device", "clean_page_device", "segment_page_device", "crop_lines_device",
            "estimate_skew_device", "deskew_page_device", "flatten_page_device", "ink_integral_device", "layout_page_device", "source_corners",
            "rotate_page_device", "estimate_orientation_device", "unrotate_boxes", "unrotate_points", "bucket_width"]

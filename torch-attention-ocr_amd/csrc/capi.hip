@@ -1089,4 +1089,51 @@ int aocr_warp_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t
   return check_launch("aocr_warp_page");
 }
 
+size_t aocr_glyph_scratch_bytes(int32_t H, int32_t W) {
+  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26))) {
+    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26)", H, W);
+    return 0;
+  }
+  return glyph_scratch_bytes(H, W);
+}
+
+int aocr_estimate_glyph_size(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_glyph_params* params,
+                             void* scratch_dev, int32_t glyph_dev[8]) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(params, "params is NULL");
+  REQUIRE(params->threshold >= -1 && params->threshold <= 254, "threshold=%d: 0..254, or -1 for Otsu", params->threshold);
+  REQUIRE(params->connectivity == 4 || params->connectivity == 8, "connectivity=%d: 4 or 8", params->connectivity);
+  REQUIRE(params->min_size >= 1, "min_size=%d must be >= 1", params->min_size);
+  REQUIRE(params->max_size >= params->min_size && params->max_size <= GLYPH_SIZE_MAX, "max_size=%d: min_size=%d..%d", params->max_size,
+          params->min_size, GLYPH_SIZE_MAX);
+  REQUIRE(params->max_aspect >= 1, "max_aspect=%d must be >= 1", params->max_aspect);
+  REQUIRE(params->reserved[0] == 0 && params->reserved[1] == 0, "reserved words must be 0");
+  REQUIRE(scratch_dev && glyph_dev, "NULL argument");
+  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  REQUIRE(((uintptr_t)glyph_dev & 3) == 0, "glyph_dev must be 4-byte aligned");
+  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W;
+  const uintptr_t s0 = (uintptr_t)scratch_dev, s1 = s0 + glyph_scratch_bytes(H, W);
+  const uintptr_t g0 = (uintptr_t)glyph_dev, g1 = g0 + 8 * sizeof(int32_t);
+  REQUIRE(disjoint(s0, s1, p0, p1), "scratch_dev overlaps the page");
+  REQUIRE(disjoint(g0, g1, p0, p1), "glyph_dev overlaps the page");
+  REQUIRE(disjoint(g0, g1, s0, s1), "glyph_dev overlaps the scratch");
+  estimate_glyph_size((hipStream_t)stream, page_dev, pitch, H, W, *params, scratch_dev, glyph_dev);
+  return check_launch("aocr_estimate_glyph_size");
+}
+
+int aocr_resize_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, uint8_t* out_dev, int64_t out_pitch,
+                     int32_t Ho, int32_t Wo) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(out_dev, "out_dev is NULL");
+  REQUIRE(Ho >= 1 && Wo >= 1 && Ho <= 16384 && Wo <= 16384 && (int64_t)Ho * Wo <= ((int64_t)1 << 26),
+          "bad output size Ho=%d Wo=%d: 1..16384 each, Ho*Wo <= 2^26", Ho, Wo);
+  REQUIRE(out_pitch >= Wo, "out_pitch=%lld is smaller than Wo=%d", (long long)out_pitch, Wo);
+  REQUIRE(W <= 8 * (int64_t)Wo && Wo <= 8 * (int64_t)W && H <= 8 * (int64_t)Ho && Ho <= 8 * (int64_t)H,
+          "H=%d W=%d to Ho=%d Wo=%d: a ratio of at most 8 either way on each axis", H, W, Ho, Wo);
+  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W, o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(Ho - 1) * out_pitch + Wo;
+  REQUIRE(disjoint(o0, o1, p0, p1), "out_dev overlaps the page");
+  resize_page((hipStream_t)stream, page_dev, pitch, H, W, out_dev, out_pitch, Ho, Wo);
+  return check_launch("aocr_resize_page");
+}
+
 }  // extern "C"

@@ -413,6 +413,13 @@ void find_page_quad(hipStream_t s, const uint8_t* page, int64_t pitch, int H, in
 int rectify_plan(const int32_t* quad, int Wo_in, int Ho_in, int32_t* size, double* coef, char* err_buf, size_t err_len);
 void warp_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const double* coef, int fill, uint8_t* out, int64_t out_pitch,
                int Ho, int Wo);
+// page scale normalisation (scale.hip; include/aocr.h: aocr_estimate_glyph_size, aocr_resize_page): the quartiles of min(w, h) over the
+// components that can be glyphs, and exact pixel-area resampling to any size
+constexpr int GLYPH_SIZE_MAX = 1024;           // the largest max_size: the histogram's bins
+size_t glyph_scratch_bytes(int H, int W);
+void estimate_glyph_size(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_glyph_params& p, void* scratch,
+                         int32_t* glyph);
+void resize_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, uint8_t* out, int64_t out_pitch, int Ho, int Wo);
 // crops (data.hip; aocr_crop_lines): preprocess_lines' scaling of n box rectangles of a pitched page, n = min(n_boxes, count[0]) on the device
 void crop_lines(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_box* boxes, const int32_t* count, int n_boxes,
                 int out_h, int out_w, float* out);
