@@ -64,6 +64,12 @@ RESIZE_SHAPES = [
     ((257, 129, 134, 3), (300, 97), (101, 1)),          # up in y, down in x, misaligned; the same on the output
     ((130, 1100, 1100, 0), (61, 1009), (None, 0)),      # more than one wave chunk per row
     ((2048, 8192, 8192, 0), (256, 1024), (None, 0)),    # bytes 254 and 255 only: the divisor is 2^24, the numerator near its top
+    # output rows around one 16-byte store at an unaligned base: a row that is all head, a head and a tail, one and two whole stores
+    ((7, 3, 3, 0), (5, 1), (8, 5)),
+    ((7, 29, 29, 0), (5, 15), (22, 5)),
+    ((7, 16, 16, 0), (5, 16), (23, 5)),
+    ((7, 23, 23, 0), (5, 17), (24, 5)),
+    ((7, 20, 20, 0), (8, 33), (40, 5)),
 ]
 
 

@@ -3,6 +3,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include "model.h"
@@ -780,16 +781,55 @@ int aocr_synth_lines(void* stream, const aocr_lexicon* lex, const aocr_glyph_atl
   return check_launch("aocr_synth_lines");
 }
 
+// ---- the page stages: what every one of them checks ---------------------------------------------------------------------------------------
+
+static bool page_size_ok(int64_t H, int64_t W) { return H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && H * W <= ((int64_t)1 << 26); }
+
 static int check_page(const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W) {
   REQUIRE(page_dev, "page_dev is NULL");
-  REQUIRE(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26),
-          "bad page size H=%d W=%d: 1..16384 each, H*W <= 2^26", H, W);
+  REQUIRE(page_size_ok(H, W), "bad page size H=%d W=%d: 1..16384 each, H*W <= 2^26", H, W);
   REQUIRE(pitch >= W, "pitch=%lld is smaller than W=%d", (long long)pitch, W);
   return 0;
 }
 
+// for the aocr_*_scratch_bytes that take a page size only: they return 0 on failure
+static bool scratch_size_ok(int32_t H, int32_t W) {
+  if (!page_size_ok(H, W)) fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26)", H, W);
+  return page_size_ok(H, W);
+}
+
+static int check_threshold(int32_t threshold) {
+  REQUIRE(threshold >= -1 && threshold <= 254, "threshold=%d: 0..254, or -1 for Otsu", threshold);
+  return 0;
+}
+
+// others: the call's other pointers that must not be NULL, reported together with scratch_dev
+static int check_scratch(const void* scratch_dev, bool others) {
+  REQUIRE(scratch_dev && others, "NULL argument");
+  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  return 0;
+}
+
+// the bytes of H rows of W elements, pitch elements apart; or of n bytes
+struct Span { uintptr_t lo, hi; };
+static Span span_rows(const void* p, int64_t pitch, int64_t H, int64_t W, size_t elem = 1) {
+  return Span{(uintptr_t)p, (uintptr_t)p + ((uintptr_t)(H - 1) * pitch + W) * elem};
+}
+static Span span_bytes(const void* p, size_t n) { return Span{(uintptr_t)p, (uintptr_t)p + n}; }
+static bool disjoint(Span a, Span b) { return a.hi <= b.lo || b.hi <= a.lo; }
+
+// the output page of a stage, Ho x Wo (width: how the message names Wo).  between: the checks that the call reports after the pitch and
+// before the overlap
+static int check_out(const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const uint8_t* out_dev, int64_t out_pitch, int32_t Ho, int32_t Wo,
+                     const char* width = "W=", const std::function<int()>& between = nullptr) {
+  REQUIRE(out_pitch >= Wo, "out_pitch=%lld is smaller than %s%d", (long long)out_pitch, width, Wo);
+  if (between && between()) return 1;
+  REQUIRE(disjoint(span_rows(out_dev, out_pitch, Ho, Wo), span_rows(page_dev, pitch, H, W)), "out_dev overlaps the page");
+  return 0;
+}
+
 size_t aocr_segment_scratch_bytes(int32_t H, int32_t W, int32_t max_boxes) {
-  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26) && max_boxes >= 1 && max_boxes <= 4096)) {
+  if (!(page_size_ok(H, W) && max_boxes >= 1 && max_boxes <= 4096)) {
     fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26) max_boxes=%d (1..4096)", H, W, max_boxes);
     return 0;
   }
@@ -799,10 +839,9 @@ size_t aocr_segment_scratch_bytes(int32_t H, int32_t W, int32_t max_boxes) {
 int aocr_segment_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_segment_params* params,
                       void* scratch_dev, int32_t max_boxes, aocr_box* boxes_dev, int32_t counts_dev[4]) {
   if (check_page(page_dev, pitch, H, W)) return 1;
-  REQUIRE(params && scratch_dev && boxes_dev && counts_dev, "NULL argument");
-  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  if (check_scratch(scratch_dev, params && boxes_dev && counts_dev)) return 1;
   REQUIRE(max_boxes >= 1 && max_boxes <= 4096, "max_boxes=%d: 1..4096", max_boxes);
-  REQUIRE(params->threshold >= -1 && params->threshold <= 254, "threshold=%d: 0..254, or -1 for Otsu", params->threshold);
+  if (check_threshold(params->threshold)) return 1;
   REQUIRE(params->min_row_ink >= 1 && params->min_line_h >= 1 && params->min_word_w >= 1, "min_row_ink=%d min_line_h=%d min_word_w=%d must be >= 1",
           params->min_row_ink, params->min_line_h, params->min_word_w);
   REQUIRE(params->merge_gap >= 0 && params->word_gap >= 0, "merge_gap=%d word_gap=%d must be >= 0", params->merge_gap, params->word_gap);
@@ -824,7 +863,7 @@ int aocr_crop_lines(void* stream, const uint8_t* page_dev, int64_t pitch, int32_
 
 static int check_skew_params(const aocr_skew_params* p) {
   REQUIRE(p, "params is NULL");
-  REQUIRE(p->threshold >= -1 && p->threshold <= 254, "threshold=%d: 0..254, or -1 for Otsu", p->threshold);
+  if (check_threshold(p->threshold)) return 1;
   REQUIRE(p->step_q16 >= 1 && p->step_q16 <= 4096, "step_q16=%d: 1..4096", p->step_q16);
   REQUIRE(p->n_steps >= 0 && p->n_steps <= 256, "n_steps=%d: 0..256", p->n_steps);
   REQUIRE(p->n_steps * p->step_q16 <= 16384, "n_steps=%d * step_q16=%d exceeds 16384 (slope 0.25)", p->n_steps, p->step_q16);
@@ -832,7 +871,7 @@ static int check_skew_params(const aocr_skew_params* p) {
 }
 
 size_t aocr_skew_scratch_bytes(int32_t H, int32_t W, int32_t n_steps) {
-  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26) && n_steps >= 0 && n_steps <= 256)) {
+  if (!(page_size_ok(H, W) && n_steps >= 0 && n_steps <= 256)) {
     fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26) n_steps=%d (0..256)", H, W, n_steps);
     return 0;
   }
@@ -843,8 +882,7 @@ int aocr_estimate_skew(void* stream, const uint8_t* page_dev, int64_t pitch, int
                        void* scratch_dev, int32_t skew_dev[4], uint64_t* scores_dev) {
   if (check_page(page_dev, pitch, H, W)) return 1;
   if (check_skew_params(params)) return 1;
-  REQUIRE(scratch_dev && skew_dev, "NULL argument");
-  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  if (check_scratch(scratch_dev, skew_dev)) return 1;
   REQUIRE(((uintptr_t)scores_dev & 7) == 0, "scores_dev must be 8-byte aligned");
   estimate_skew((hipStream_t)stream, page_dev, pitch, H, W, *params, scratch_dev, skew_dev, scores_dev);
   return check_launch("aocr_estimate_skew");
@@ -854,16 +892,14 @@ int aocr_deskew_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32
                      int32_t fill, uint8_t* out_dev, int64_t out_pitch) {
   if (check_page(page_dev, pitch, H, W)) return 1;
   REQUIRE(out_dev, "out_dev is NULL");
-  REQUIRE(out_pitch >= W, "out_pitch=%lld is smaller than W=%d", (long long)out_pitch, W);
-  REQUIRE(fill >= 0 && fill <= 255, "fill=%d: 0..255", fill);
-  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W, o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(H - 1) * out_pitch + W;
-  REQUIRE(o1 <= p0 || p1 <= o0, "out_dev overlaps the page");
+  if (check_out(page_dev, pitch, H, W, out_dev, out_pitch, H, W, "W=", [&] { REQUIRE(fill >= 0 && fill <= 255, "fill=%d: 0..255", fill); return 0; }))
+    return 1;
   deskew_page((hipStream_t)stream, page_dev, pitch, H, W, skew_dev, slope_q16, fill, out_dev, out_pitch);
   return check_launch("aocr_deskew_page");
 }
 
 size_t aocr_flatten_scratch_bytes(int32_t H, int32_t W, int32_t radius) {
-  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26) && radius >= 1 && radius <= 127)) {
+  if (!(page_size_ok(H, W) && radius >= 1 && radius <= 127)) {
     fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26) radius=%d (1..127)", H, W, radius);
     return 0;
   }
@@ -876,27 +912,17 @@ int aocr_flatten_page(void* stream, const uint8_t* page_dev, int64_t pitch, int3
   REQUIRE(params, "params is NULL");
   REQUIRE(params->radius >= 1 && params->radius <= 127, "radius=%d: 1..127", params->radius);
   REQUIRE(params->reserved[0] == 0 && params->reserved[1] == 0, "reserved words must be 0");
-  REQUIRE(scratch_dev && out_dev, "NULL argument");
-  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
-  REQUIRE(out_pitch >= W, "out_pitch=%lld is smaller than W=%d", (long long)out_pitch, W);
-  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W, o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(H - 1) * out_pitch + W;
-  REQUIRE(o1 <= p0 || p1 <= o0, "out_dev overlaps the page");
+  if (check_scratch(scratch_dev, out_dev)) return 1;
+  if (check_out(page_dev, pitch, H, W, out_dev, out_pitch, H, W)) return 1;
   flatten_page((hipStream_t)stream, page_dev, pitch, H, W, *params, scratch_dev, out_dev, out_pitch);
   return check_launch("aocr_flatten_page");
 }
 
-size_t aocr_integral_scratch_bytes(int32_t H, int32_t W) {
-  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26))) {
-    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26)", H, W);
-    return 0;
-  }
-  return integral_scratch_bytes(H, W);
-}
+size_t aocr_integral_scratch_bytes(int32_t H, int32_t W) { return scratch_size_ok(H, W) ? integral_scratch_bytes(H, W) : 0; }
 
 static int check_sat(const uint32_t* sat_dev, int64_t sat_pitch, int32_t H, int32_t W) {
   REQUIRE(sat_dev, "sat_dev is NULL");
-  REQUIRE(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26),
-          "bad page size H=%d W=%d: 1..16384 each, H*W <= 2^26", H, W);
+  REQUIRE(page_size_ok(H, W), "bad page size H=%d W=%d: 1..16384 each, H*W <= 2^26", H, W);
   REQUIRE(sat_pitch >= (int64_t)W + 1, "sat_pitch=%lld is smaller than W+1=%d", (long long)sat_pitch, W + 1);
   REQUIRE(((uintptr_t)sat_dev & 3) == 0, "sat_dev must be 4-byte aligned");
   return 0;
@@ -905,21 +931,18 @@ static int check_sat(const uint32_t* sat_dev, int64_t sat_pitch, int32_t H, int3
 int aocr_ink_integral(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t threshold, int32_t light_text,
                       void* scratch_dev, uint32_t* sat_dev, int64_t sat_pitch, int32_t info_dev[4]) {
   if (check_page(page_dev, pitch, H, W)) return 1;
-  REQUIRE(threshold >= -1 && threshold <= 254, "threshold=%d: 0..254, or -1 for Otsu", threshold);
-  REQUIRE(scratch_dev && info_dev, "NULL argument");
-  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  if (check_threshold(threshold)) return 1;
+  if (check_scratch(scratch_dev, info_dev)) return 1;
   if (check_sat(sat_dev, sat_pitch, H, W)) return 1;
-  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W;
-  const uintptr_t t0 = (uintptr_t)sat_dev, t1 = t0 + ((uintptr_t)H * sat_pitch + W + 1) * sizeof(uint32_t);
-  const uintptr_t s0 = (uintptr_t)scratch_dev, s1 = s0 + integral_scratch_bytes(H, W);
-  REQUIRE(t1 <= p0 || p1 <= t0, "sat_dev overlaps the page");
-  REQUIRE(t1 <= s0 || s1 <= t0, "sat_dev overlaps the scratch");
+  const Span sat = span_rows(sat_dev, sat_pitch, H + 1, W + 1, sizeof(uint32_t));
+  REQUIRE(disjoint(sat, span_rows(page_dev, pitch, H, W)), "sat_dev overlaps the page");
+  REQUIRE(disjoint(sat, span_bytes(scratch_dev, integral_scratch_bytes(H, W))), "sat_dev overlaps the scratch");
   ink_integral((hipStream_t)stream, page_dev, pitch, H, W, threshold, light_text, scratch_dev, sat_dev, sat_pitch, info_dev);
   return check_launch("aocr_ink_integral");
 }
 
 size_t aocr_layout_scratch_bytes(int32_t H, int32_t W, int32_t max_blocks) {
-  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26) && max_blocks >= 1 && max_blocks <= 1024)) {
+  if (!(page_size_ok(H, W) && max_blocks >= 1 && max_blocks <= 1024)) {
     fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26) max_blocks=%d (1..1024)", H, W, max_blocks);
     return 0;
   }
@@ -929,8 +952,7 @@ size_t aocr_layout_scratch_bytes(int32_t H, int32_t W, int32_t max_blocks) {
 int aocr_layout_blocks(void* stream, const uint32_t* sat_dev, int64_t sat_pitch, int32_t H, int32_t W, const aocr_layout_params* params,
                        void* scratch_dev, int32_t max_blocks, aocr_box* blocks_dev, int32_t counts_dev[4]) {
   if (check_sat(sat_dev, sat_pitch, H, W)) return 1;
-  REQUIRE(params && scratch_dev && blocks_dev && counts_dev, "NULL argument");
-  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  if (check_scratch(scratch_dev, params && blocks_dev && counts_dev)) return 1;
   REQUIRE(max_blocks >= 1 && max_blocks <= 1024, "max_blocks=%d: 1..1024", max_blocks);
   REQUIRE(params->min_ink >= 1 && params->gap_x >= 1 && params->gap_y >= 1, "min_ink=%d gap_x=%d gap_y=%d must be >= 1", params->min_ink,
           params->gap_x, params->gap_y);
@@ -938,69 +960,47 @@ int aocr_layout_blocks(void* stream, const uint32_t* sat_dev, int64_t sat_pitch,
   REQUIRE(params->min_block_w >= 1 && params->min_block_h >= 1 && params->min_block_ink >= 1,
           "min_block_w=%d min_block_h=%d min_block_ink=%d must be >= 1", params->min_block_w, params->min_block_h, params->min_block_ink);
   REQUIRE(params->reserved == 0, "reserved word must be 0");
-  const uintptr_t t0 = (uintptr_t)sat_dev, t1 = t0 + ((uintptr_t)H * sat_pitch + W + 1) * sizeof(uint32_t);
-  const uintptr_t s0 = (uintptr_t)scratch_dev, s1 = s0 + layout_scratch_bytes(max_blocks);
-  REQUIRE(t1 <= s0 || s1 <= t0, "sat_dev overlaps the scratch");
+  REQUIRE(disjoint(span_rows(sat_dev, sat_pitch, H + 1, W + 1, sizeof(uint32_t)), span_bytes(scratch_dev, layout_scratch_bytes(max_blocks))),
+          "sat_dev overlaps the scratch");
   layout_blocks((hipStream_t)stream, sat_dev, sat_pitch, H, W, *params, scratch_dev, max_blocks, blocks_dev, counts_dev);
   return check_launch("aocr_layout_blocks");
 }
 
-size_t aocr_components_scratch_bytes(int32_t H, int32_t W) {
-  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26))) {
-    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26)", H, W);
-    return 0;
-  }
-  return components_scratch_bytes(H, W);
-}
-
-static bool disjoint(uintptr_t a0, uintptr_t a1, uintptr_t b0, uintptr_t b1) { return a1 <= b0 || b1 <= a0; }
+size_t aocr_components_scratch_bytes(int32_t H, int32_t W) { return scratch_size_ok(H, W) ? components_scratch_bytes(H, W) : 0; }
 
 int aocr_label_components(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t threshold, int32_t light_text,
                           int32_t connectivity, void* scratch_dev, int32_t* labels_dev, int64_t labels_pitch, int32_t max_components,
                           aocr_box* comps_dev, int32_t info_dev[4]) {
   if (check_page(page_dev, pitch, H, W)) return 1;
-  REQUIRE(threshold >= -1 && threshold <= 254, "threshold=%d: 0..254, or -1 for Otsu", threshold);
+  if (check_threshold(threshold)) return 1;
   REQUIRE(connectivity == 4 || connectivity == 8, "connectivity=%d: 4 or 8", connectivity);
-  REQUIRE(scratch_dev && labels_dev && info_dev, "NULL argument");
-  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  if (check_scratch(scratch_dev, labels_dev && info_dev)) return 1;
   REQUIRE(((uintptr_t)labels_dev & 3) == 0, "labels_dev must be 4-byte aligned");
   REQUIRE(labels_pitch >= W, "labels_pitch=%lld is smaller than W=%d", (long long)labels_pitch, W);
   REQUIRE(max_components >= 1 && max_components <= 65536, "max_components=%d: 1..65536", max_components);
-  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W;
-  const uintptr_t l0 = (uintptr_t)labels_dev, l1 = l0 + ((uintptr_t)(H - 1) * labels_pitch + W) * sizeof(int32_t);
-  const uintptr_t s0 = (uintptr_t)scratch_dev, s1 = s0 + components_scratch_bytes(H, W);
-  REQUIRE(disjoint(l0, l1, p0, p1), "labels_dev overlaps the page");
-  REQUIRE(disjoint(l0, l1, s0, s1), "labels_dev overlaps the scratch");
+  const Span labels = span_rows(labels_dev, labels_pitch, H, W, sizeof(int32_t));
+  REQUIRE(disjoint(labels, span_rows(page_dev, pitch, H, W)), "labels_dev overlaps the page");
+  REQUIRE(disjoint(labels, span_bytes(scratch_dev, components_scratch_bytes(H, W))), "labels_dev overlaps the scratch");
   label_components((hipStream_t)stream, page_dev, pitch, H, W, threshold, light_text, connectivity, scratch_dev, labels_dev, labels_pitch,
                    max_components, comps_dev, info_dev);
   return check_launch("aocr_label_components");
 }
 
-size_t aocr_clean_scratch_bytes(int32_t H, int32_t W) {
-  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26))) {
-    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26)", H, W);
-    return 0;
-  }
-  return clean_scratch_bytes(H, W);
-}
+size_t aocr_clean_scratch_bytes(int32_t H, int32_t W) { return scratch_size_ok(H, W) ? clean_scratch_bytes(H, W) : 0; }
 
 int aocr_clean_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_clean_params* params,
                     void* scratch_dev, uint8_t* out_dev, int64_t out_pitch, int32_t counts_dev[8]) {
   if (check_page(page_dev, pitch, H, W)) return 1;
   REQUIRE(params, "params is NULL");
-  REQUIRE(params->threshold >= -1 && params->threshold <= 254, "threshold=%d: 0..254, or -1 for Otsu", params->threshold);
+  if (check_threshold(params->threshold)) return 1;
   REQUIRE(params->connectivity == 4 || params->connectivity == 8, "connectivity=%d: 4 or 8", params->connectivity);
   REQUIRE(params->min_area >= 1, "min_area=%d must be >= 1", params->min_area);
   REQUIRE(params->max_w >= 0 && params->max_h >= 0, "max_w=%d max_h=%d must be >= 0", params->max_w, params->max_h);
   REQUIRE(params->reserved[0] == 0 && params->reserved[1] == 0, "reserved words must be 0");
-  REQUIRE(scratch_dev && out_dev && counts_dev, "NULL argument");
-  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  if (check_scratch(scratch_dev, out_dev && counts_dev)) return 1;
   REQUIRE(((uintptr_t)counts_dev & 3) == 0, "counts_dev must be 4-byte aligned");
-  REQUIRE(out_pitch >= W, "out_pitch=%lld is smaller than W=%d", (long long)out_pitch, W);
-  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W, o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(H - 1) * out_pitch + W;
-  const uintptr_t s0 = (uintptr_t)scratch_dev, s1 = s0 + clean_scratch_bytes(H, W);
-  REQUIRE(disjoint(o0, o1, p0, p1), "out_dev overlaps the page");
-  REQUIRE(disjoint(o0, o1, s0, s1), "out_dev overlaps the scratch");
+  if (check_out(page_dev, pitch, H, W, out_dev, out_pitch, H, W)) return 1;
+  REQUIRE(disjoint(span_rows(out_dev, out_pitch, H, W), span_bytes(scratch_dev, clean_scratch_bytes(H, W))), "out_dev overlaps the scratch");
   clean_page((hipStream_t)stream, page_dev, pitch, H, W, *params, scratch_dev, out_dev, out_pitch, counts_dev);
   return check_launch("aocr_clean_page");
 }
@@ -1012,53 +1012,43 @@ int aocr_rotate_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32
   REQUIRE(out_dev, "out_dev is NULL");
   REQUIRE(((uintptr_t)orient_dev & 3) == 0, "orient_dev must be 4-byte aligned");
   const int32_t Ho = (quarter & 1) ? W : H, Wo = (quarter & 1) ? H : W;
-  REQUIRE(out_pitch >= Wo, "out_pitch=%lld is smaller than the output's width %d", (long long)out_pitch, Wo);
-  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W, o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(Ho - 1) * out_pitch + Wo;
-  REQUIRE(disjoint(o0, o1, p0, p1), "out_dev overlaps the page");
+  if (check_out(page_dev, pitch, H, W, out_dev, out_pitch, Ho, Wo, "the output's width ")) return 1;
   rotate_page((hipStream_t)stream, page_dev, pitch, H, W, orient_dev, quarter, out_dev, out_pitch);
   return check_launch("aocr_rotate_page");
 }
 
-size_t aocr_orient_scratch_bytes(int32_t H, int32_t W) {
-  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26))) {
-    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26)", H, W);
-    return 0;
-  }
-  return orient_scratch_bytes(H, W);
-}
+size_t aocr_orient_scratch_bytes(int32_t H, int32_t W) { return scratch_size_ok(H, W) ? orient_scratch_bytes(H, W) : 0; }
 
 int aocr_estimate_orientation(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t threshold, int32_t light_text,
                               void* scratch_dev, int32_t orient_dev[8]) {
   if (check_page(page_dev, pitch, H, W)) return 1;
-  REQUIRE(threshold >= -1 && threshold <= 254, "threshold=%d: 0..254, or -1 for Otsu", threshold);
-  REQUIRE(scratch_dev && orient_dev, "NULL argument");
-  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  if (check_threshold(threshold)) return 1;
+  if (check_scratch(scratch_dev, orient_dev)) return 1;
   REQUIRE(((uintptr_t)orient_dev & 3) == 0, "orient_dev must be 4-byte aligned");
   estimate_orientation((hipStream_t)stream, page_dev, pitch, H, W, threshold, light_text, scratch_dev, orient_dev);
   return check_launch("aocr_estimate_orientation");
 }
 
-size_t aocr_quad_scratch_bytes(int32_t H, int32_t W) {
-  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26))) {
-    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26)", H, W);
-    return 0;
-  }
-  return quad_scratch_bytes(H, W);
+size_t aocr_quad_scratch_bytes(int32_t H, int32_t W) { return scratch_size_ok(H, W) ? quad_scratch_bytes(H, W) : 0; }
+
+// a stage that writes a few words: the scratch, the page and the words lie apart.  name_dev: the words' name in the messages
+static int check_words(const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const void* scratch_dev, size_t scratch_bytes,
+                       const int32_t* words_dev, int n_words, const char* name_dev) {
+  const Span page = span_rows(page_dev, pitch, H, W), scratch = span_bytes(scratch_dev, scratch_bytes);
+  const Span words = span_bytes(words_dev, n_words * sizeof(int32_t));
+  REQUIRE(disjoint(scratch, page), "scratch_dev overlaps the page");
+  REQUIRE(disjoint(words, page), "%s overlaps the page", name_dev);
+  REQUIRE(disjoint(words, scratch), "%s overlaps the scratch", name_dev);
+  return 0;
 }
 
 int aocr_find_page_quad(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t threshold, int32_t dark_paper,
                         void* scratch_dev, int32_t quad_dev[16]) {
   if (check_page(page_dev, pitch, H, W)) return 1;
-  REQUIRE(threshold >= -1 && threshold <= 254, "threshold=%d: 0..254, or -1 for Otsu", threshold);
-  REQUIRE(scratch_dev && quad_dev, "NULL argument");
-  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  if (check_threshold(threshold)) return 1;
+  if (check_scratch(scratch_dev, quad_dev)) return 1;
   REQUIRE(((uintptr_t)quad_dev & 3) == 0, "quad_dev must be 4-byte aligned");
-  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W;
-  const uintptr_t s0 = (uintptr_t)scratch_dev, s1 = s0 + quad_scratch_bytes(H, W);
-  const uintptr_t q0 = (uintptr_t)quad_dev, q1 = q0 + 16 * sizeof(int32_t);
-  REQUIRE(disjoint(s0, s1, p0, p1), "scratch_dev overlaps the page");
-  REQUIRE(disjoint(q0, q1, p0, p1), "quad_dev overlaps the page");
-  REQUIRE(disjoint(q0, q1, s0, s1), "quad_dev overlaps the scratch");
+  if (check_words(page_dev, pitch, H, W, scratch_dev, quad_scratch_bytes(H, W), quad_dev, 16, "quad_dev")) return 1;
   find_page_quad((hipStream_t)stream, page_dev, pitch, H, W, threshold, dark_paper, scratch_dev, quad_dev);
   return check_launch("aocr_find_page_quad");
 }
@@ -1079,44 +1069,29 @@ int aocr_warp_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t
   if (check_page(page_dev, pitch, H, W)) return 1;
   REQUIRE(coef, "coef is NULL");
   REQUIRE(out_dev, "out_dev is NULL");
-  REQUIRE(Ho >= 1 && Wo >= 1 && Ho <= 16384 && Wo <= 16384 && (int64_t)Ho * Wo <= ((int64_t)1 << 26),
-          "bad output size Ho=%d Wo=%d: 1..16384 each, Ho*Wo <= 2^26", Ho, Wo);
-  REQUIRE(out_pitch >= Wo, "out_pitch=%lld is smaller than Wo=%d", (long long)out_pitch, Wo);
-  REQUIRE(fill >= 0 && fill <= 255, "fill=%d: 0..255", fill);
-  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W, o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(Ho - 1) * out_pitch + Wo;
-  REQUIRE(disjoint(o0, o1, p0, p1), "out_dev overlaps the page");
+  REQUIRE(page_size_ok(Ho, Wo), "bad output size Ho=%d Wo=%d: 1..16384 each, Ho*Wo <= 2^26", Ho, Wo);
+  if (check_out(page_dev, pitch, H, W, out_dev, out_pitch, Ho, Wo, "Wo=", [&] { REQUIRE(fill >= 0 && fill <= 255, "fill=%d: 0..255", fill); return 0; }))
+    return 1;
   warp_page((hipStream_t)stream, page_dev, pitch, H, W, coef, fill, out_dev, out_pitch, Ho, Wo);
   return check_launch("aocr_warp_page");
 }
 
-size_t aocr_glyph_scratch_bytes(int32_t H, int32_t W) {
-  if (!(H >= 1 && W >= 1 && H <= 16384 && W <= 16384 && (int64_t)H * W <= ((int64_t)1 << 26))) {
-    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26)", H, W);
-    return 0;
-  }
-  return glyph_scratch_bytes(H, W);
-}
+size_t aocr_glyph_scratch_bytes(int32_t H, int32_t W) { return scratch_size_ok(H, W) ? glyph_scratch_bytes(H, W) : 0; }
 
 int aocr_estimate_glyph_size(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_glyph_params* params,
                              void* scratch_dev, int32_t glyph_dev[8]) {
   if (check_page(page_dev, pitch, H, W)) return 1;
   REQUIRE(params, "params is NULL");
-  REQUIRE(params->threshold >= -1 && params->threshold <= 254, "threshold=%d: 0..254, or -1 for Otsu", params->threshold);
+  if (check_threshold(params->threshold)) return 1;
   REQUIRE(params->connectivity == 4 || params->connectivity == 8, "connectivity=%d: 4 or 8", params->connectivity);
   REQUIRE(params->min_size >= 1, "min_size=%d must be >= 1", params->min_size);
   REQUIRE(params->max_size >= params->min_size && params->max_size <= GLYPH_SIZE_MAX, "max_size=%d: min_size=%d..%d", params->max_size,
           params->min_size, GLYPH_SIZE_MAX);
   REQUIRE(params->max_aspect >= 1, "max_aspect=%d must be >= 1", params->max_aspect);
   REQUIRE(params->reserved[0] == 0 && params->reserved[1] == 0, "reserved words must be 0");
-  REQUIRE(scratch_dev && glyph_dev, "NULL argument");
-  REQUIRE(((uintptr_t)scratch_dev & 15) == 0, "scratch_dev must be 16-byte aligned");
+  if (check_scratch(scratch_dev, glyph_dev)) return 1;
   REQUIRE(((uintptr_t)glyph_dev & 3) == 0, "glyph_dev must be 4-byte aligned");
-  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W;
-  const uintptr_t s0 = (uintptr_t)scratch_dev, s1 = s0 + glyph_scratch_bytes(H, W);
-  const uintptr_t g0 = (uintptr_t)glyph_dev, g1 = g0 + 8 * sizeof(int32_t);
-  REQUIRE(disjoint(s0, s1, p0, p1), "scratch_dev overlaps the page");
-  REQUIRE(disjoint(g0, g1, p0, p1), "glyph_dev overlaps the page");
-  REQUIRE(disjoint(g0, g1, s0, s1), "glyph_dev overlaps the scratch");
+  if (check_words(page_dev, pitch, H, W, scratch_dev, glyph_scratch_bytes(H, W), glyph_dev, 8, "glyph_dev")) return 1;
   estimate_glyph_size((hipStream_t)stream, page_dev, pitch, H, W, *params, scratch_dev, glyph_dev);
   return check_launch("aocr_estimate_glyph_size");
 }
@@ -1125,13 +1100,13 @@ int aocr_resize_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32
                      int32_t Ho, int32_t Wo) {
   if (check_page(page_dev, pitch, H, W)) return 1;
   REQUIRE(out_dev, "out_dev is NULL");
-  REQUIRE(Ho >= 1 && Wo >= 1 && Ho <= 16384 && Wo <= 16384 && (int64_t)Ho * Wo <= ((int64_t)1 << 26),
-          "bad output size Ho=%d Wo=%d: 1..16384 each, Ho*Wo <= 2^26", Ho, Wo);
-  REQUIRE(out_pitch >= Wo, "out_pitch=%lld is smaller than Wo=%d", (long long)out_pitch, Wo);
-  REQUIRE(W <= 8 * (int64_t)Wo && Wo <= 8 * (int64_t)W && H <= 8 * (int64_t)Ho && Ho <= 8 * (int64_t)H,
-          "H=%d W=%d to Ho=%d Wo=%d: a ratio of at most 8 either way on each axis", H, W, Ho, Wo);
-  const uintptr_t p0 = (uintptr_t)page_dev, p1 = p0 + (uintptr_t)(H - 1) * pitch + W, o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)(Ho - 1) * out_pitch + Wo;
-  REQUIRE(disjoint(o0, o1, p0, p1), "out_dev overlaps the page");
+  REQUIRE(page_size_ok(Ho, Wo), "bad output size Ho=%d Wo=%d: 1..16384 each, Ho*Wo <= 2^26", Ho, Wo);
+  if (check_out(page_dev, pitch, H, W, out_dev, out_pitch, Ho, Wo, "Wo=", [&] {
+        REQUIRE(W <= 8 * (int64_t)Wo && Wo <= 8 * (int64_t)W && H <= 8 * (int64_t)Ho && Ho <= 8 * (int64_t)H,
+                "H=%d W=%d to Ho=%d Wo=%d: a ratio of at most 8 either way on each axis", H, W, Ho, Wo);
+        return 0;
+      }))
+    return 1;
   resize_page((hipStream_t)stream, page_dev, pitch, H, W, out_dev, out_pitch, Ho, Wo);
   return check_launch("aocr_resize_page");
 }

@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <cstddef>
 #include "ops.h"
+#include "page_common.h"
 #include "runs.h"
 
 namespace aocr {
@@ -57,17 +58,16 @@ struct CcLayout {                              // byte offsets into scratch_dev
 
 CcLayout cc_layout(int H, int W, bool with_labels) {
   CcLayout l;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  ScratchCursor c;
   l.ntx = cdiv(W, CC_TILE_W);
   l.nty = cdiv(H, CC_TILE_H);
   l.sw = (W + 1) / 2;                          // a root has paper (or the page's edge) to its left: at most one per pixel pair of a row
-  size_t o = 0;
-  l.hist = o;   o = up(o + 256 * sizeof(uint32_t));
-  l.hdr = o;    o = up(o + HDR_WORDS * sizeof(int32_t));
-  l.stats = o;  o = up(o + (size_t)H * l.sw * sizeof(CompStat));
-  l.segs = o;   o = up(o + (size_t)H * l.ntx * sizeof(int32_t));
-  l.labels = o; if (with_labels) o = up(o + (size_t)H * W * sizeof(int32_t));
-  l.total = o;
+  l.hist = c.take(256 * sizeof(uint32_t));
+  l.hdr = c.take(HDR_WORDS * sizeof(int32_t));
+  l.stats = c.take((size_t)H * l.sw * sizeof(CompStat));
+  l.segs = c.take((size_t)H * l.ntx * sizeof(int32_t));
+  l.labels = c.take(with_labels ? (size_t)H * W * sizeof(int32_t) : 0);
+  l.total = c.total();
   return l;
 }
 
@@ -103,15 +103,12 @@ __global__ __launch_bounds__(CC_THREADS) void cc_local_kernel(const uint8_t* __r
   __shared__ uint64_t rowmask[CC_TILE_H];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int x0 = blockIdx.x * CC_TILE_W, y0 = blockIdx.y * CC_TILE_H;
-  const int thr = fixed >= 0 ? fixed : hdr[HDR_THR];     // Otsu's was written by otsu_kernel just before; -1: nothing is ink
+  const int thr = ink_thr(fixed, hdr + HDR_THR);
   const int x = x0 + lane;
   for (int r = wave; r < CC_TILE_H; r += CC_WAVES) {
     const int y = y0 + r;
     bool ink = false;
-    if (y < H && x < W && thr >= 0) {
-      const int v = page[(int64_t)y * pitch + x];
-      ink = light ? (v > thr) : (v <= thr);
-    }
+    if (y < H && x < W && thr >= 0) ink = is_ink(page[(int64_t)y * pitch + x], thr, light);
     const uint64_t m = __ballot(ink);
     if (lane == 0) rowmask[r] = m;
     const uint64_t z = ~m & below(lane);                 // paper left of this pixel: the run starts after the last of it
@@ -229,11 +226,6 @@ __global__ __launch_bounds__(CC_THREADS) void cc_flatten_kernel(int32_t* labels,
   if (r == i) stats[(size_t)y * sw + (x >> 1)] = CompStat{0, CC_BIG, -1, -1};
 }
 
-__device__ __forceinline__ int wave_sum_int(int v) {
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-
 __global__ __launch_bounds__(CC_THREADS) void cc_stats_kernel(const int32_t* __restrict__ labels, int64_t lp, int H, int W, CompStat* stats, int sw,
                                                               int32_t* __restrict__ segs, int ntx, int32_t* hdr) {
   __shared__ int key[CC_HASH], area[CC_HASH], mnx[CC_HASH], mxx[CC_HASH], mxy[CC_HASH];
@@ -277,7 +269,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_stats_kernel(const int32_t* __r
     atomicMax(s + 3, mxy[i]);
     ink += area[i];
   }
-  ink = wave_sum_int(ink);
+  ink = wave_sum(ink);
   if (lane == 0 && ink) atomicAdd(&tile_ink, ink);
   __syncthreads();
   if (threadIdx.x == 0 && tile_ink) atomicAdd(&hdr[HDR_INK], tile_ink);
@@ -295,7 +287,7 @@ __global__ __launch_bounds__(SEG_THREADS) void cc_scan_kernel(int32_t* __restric
   int o = block_scan_excl<false>(sum, 0, [](int a, int b) { return a + b; }, wtot, &total);
   for (int i = lo; i < hi; ++i) { const int c = segs[i]; segs[i] = o; o += c; }
   if (threadIdx.x == 0) {
-    const int thr = fixed >= 0 ? fixed : hdr[HDR_THR];
+    const int thr = ink_thr(fixed, hdr + HDR_THR);
     if (clean) { out[0] = total; out[1] = 0; out[2] = 0; out[3] = thr; out[4] = hdr[HDR_INK]; out[5] = 0; out[6] = 0; out[7] = 0; }
     else { out[0] = thr; out[1] = hdr[HDR_INK]; out[2] = total; out[3] = 0; }
   }
@@ -351,15 +343,15 @@ __global__ __launch_bounds__(CC_THREADS) void cc_apply_kernel(const uint8_t* __r
 
 // the launches both calls share: labels of the page (lp elements a row), statistics and root offsets in scratch, info / counts header in out
 void label_launches(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, int threshold, int light_text, int connectivity,
-                    const CcLayout& l, char* base, int32_t* labels, int64_t lp, int clean, int32_t* out) {
-  uint32_t* hist = reinterpret_cast<uint32_t*>(base + l.hist);
-  int32_t* hdr = reinterpret_cast<int32_t*>(base + l.hdr);
-  CompStat* stats = reinterpret_cast<CompStat*>(base + l.stats);
-  int32_t* segs = reinterpret_cast<int32_t*>(base + l.segs);
+                    const CcLayout& l, void* scratch, int32_t* labels, int64_t lp, int clean, int32_t* out) {
+  uint32_t* hist = scratch_at<uint32_t>(scratch, l.hist);
+  int32_t* hdr = scratch_at<int32_t>(scratch, l.hdr);
+  CompStat* stats = scratch_at<CompStat>(scratch, l.stats);
+  int32_t* segs = scratch_at<int32_t>(scratch, l.segs);
   const int light = light_text ? 1 : 0, fixed = threshold, conn8 = connectivity == 8;
   const dim3 tiles(l.ntx, l.nty), rows(cdiv(W, CC_THREADS), H);
   (void)hipMemsetAsync(hdr, 0, HDR_WORDS * sizeof(int32_t), s);
-  if (fixed < 0) otsu_threshold(s, page, pitch, H, W, hist, hdr);
+  page_threshold(s, page, pitch, H, W, fixed, hist, hdr + HDR_THR);
   hipLaunchKernelGGL(cc_local_kernel, tiles, dim3(CC_THREADS), 0, s, page, pitch, H, W, light, fixed, hdr, conn8, labels, lp);
   const int n_rows = l.nty - 1, n_cols = l.ntx - 1;
   const int64_t border = (int64_t)n_rows * W + (int64_t)n_cols * H;
@@ -378,28 +370,26 @@ size_t clean_scratch_bytes(int H, int W) { return cc_layout(H, W, true).total; }
 static_assert(sizeof(CompStat) == 4 * sizeof(int32_t) && offsetof(CompStat, area) == 0, "ops.h describes the record to rectify.hip");
 ComponentAreas component_areas(int H, int W, void* scratch) {
   const CcLayout l = cc_layout(H, W, false);
-  return ComponentAreas{reinterpret_cast<const int32_t*>(static_cast<char*>(scratch) + l.stats), l.sw};
+  return ComponentAreas{scratch_at<const int32_t>(scratch, l.stats), l.sw};
 }
 
 void label_components(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, int threshold, int light_text, int connectivity,
                       void* scratch, int32_t* labels, int64_t labels_pitch, int max_components, aocr_box* comps, int32_t* info) {
   const CcLayout l = cc_layout(H, W, false);
-  char* base = static_cast<char*>(scratch);
-  label_launches(s, page, pitch, H, W, threshold, light_text, connectivity, l, base, labels, labels_pitch, 0, info);
+  label_launches(s, page, pitch, H, W, threshold, light_text, connectivity, l, scratch, labels, labels_pitch, 0, info);
   if (comps)
     hipLaunchKernelGGL(cc_emit_kernel, dim3(l.ntx, cdiv(H, CC_WAVES)), dim3(CC_THREADS), 0, s, labels, labels_pitch, H, W,
-                       reinterpret_cast<const CompStat*>(base + l.stats), l.sw, reinterpret_cast<const int32_t*>(base + l.segs), l.ntx,
+                       scratch_at<const CompStat>(scratch, l.stats), l.sw, scratch_at<const int32_t>(scratch, l.segs), l.ntx,
                        max_components, comps);
 }
 
 void clean_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_clean_params& p, void* scratch, uint8_t* out,
                 int64_t out_pitch, int32_t* counts) {
   const CcLayout l = cc_layout(H, W, true);
-  char* base = static_cast<char*>(scratch);
-  int32_t* labels = reinterpret_cast<int32_t*>(base + l.labels);
-  label_launches(s, page, pitch, H, W, p.threshold, p.light_text, p.connectivity, l, base, labels, W, 1, counts);
+  int32_t* labels = scratch_at<int32_t>(scratch, l.labels);
+  label_launches(s, page, pitch, H, W, p.threshold, p.light_text, p.connectivity, l, scratch, labels, W, 1, counts);
   hipLaunchKernelGGL(cc_apply_kernel, dim3(cdiv(W, CC_THREADS), H), dim3(CC_THREADS), 0, s, page, pitch, H, W, labels,
-                     reinterpret_cast<const CompStat*>(base + l.stats), l.sw, p.min_area, p.max_w, p.max_h, p.light_text ? 0 : 255, out,
+                     scratch_at<const CompStat>(scratch, l.stats), l.sw, p.min_area, p.max_w, p.max_h, p.light_text ? 0 : 255, out,
                      out_pitch, counts);
 }
 

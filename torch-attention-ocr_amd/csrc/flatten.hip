@@ -16,11 +16,12 @@
 //                      registers as 16-bit halves (add before subtract: no half exceeds 65025 + 255).
 //   flat_div_kernel    S, page -> out.  A workgroup owns 4 rows of one segment of HSEG columns, one wave per row: the row of S with its halo
 //                      becomes an exclusive prefix sum in LDS (each lane scans PCH consecutive entries, the lane totals are scanned with
-//                      shuffles), so B is a difference of two entries; then the rounding, the two integer divisions and deskew_kernel's store
-//                      pattern: 16 bytes per lane where the output row is aligned, bytes at its ragged ends.
+//                      shuffles), so B is a difference of two entries; then the rounding, the two integer divisions and the row store of
+//                      page_common.h (wave_store_row) over the segment.
 // Integer sums and maxima do not depend on their order: the result does not depend on the launch geometry.  No atomics, no floats.
 #include <algorithm>
 #include "ops.h"
+#include "page_common.h"
 
 namespace aocr {
 
@@ -45,8 +46,12 @@ struct FlatLayout {                            // byte offsets into scratch_dev;
 FlatLayout flat_layout(int H, int W) {
   FlatLayout l;
   l.pa4 = ((W + VT_COLS - 1) / VT_COLS) * (VT_COLS / 4);
-  const size_t plane = ((size_t)H * l.pa4 * 4 + 255) & ~(size_t)255;
-  l.a = 0; l.s = 0; l.m = 2 * plane; l.total = 3 * plane;
+  const size_t plane = (size_t)H * l.pa4 * 4;            // one byte per column
+  ScratchCursor c;
+  l.s = c.take(plane); c.take(plane);                    // two bytes per column: two planes
+  l.a = l.s;
+  l.m = c.take(plane);
+  l.total = c.total();
   return l;
 }
 
@@ -196,28 +201,15 @@ __global__ __launch_bounds__(256) void flat_div_kernel(const uint8_t* __restrict
   if (!live) return;
   const uint32_t ny = (uint32_t)(min(y + r, H - 1) - max(y - r, 0) + 1), inv8 = inv & 0xffu;
   const uint8_t* prow = page + (int64_t)y * pitch;
-  auto px = [&](int x) -> uint32_t {                     // X0 <= x < X1
+  auto px = [&](int u) -> uint32_t {                     // column X0 + u of the page, 0 <= u < X1 - X0
+    const int x = X0 + u;
     const int lo = max(x - r, 0), hi = min(x + r, W - 1);
     const uint32_t n = (uint32_t)(hi - lo + 1) * ny;
     const uint32_t B = (Pw[hi + 1 - xb] - Pw[lo - xb] + (n >> 1)) / n;
     const uint32_t Bc = max(B, 1u), v = (uint32_t)prow[x] ^ inv8;
     return min(255u, (v * 255u + (Bc >> 1)) / Bc) ^ inv8;
   };
-  auto px4 = [&](int x) -> uint32_t { return px(x) | (px(x + 1) << 8) | (px(x + 2) << 16) | (px(x + 3) << 24); };
-  uint8_t* o = out + (int64_t)y * out_pitch + X0;
-  const int n = X1 - X0;
-  const int head = min(n, (int)((16u - (uint32_t)((uintptr_t)o & 15u)) & 15u));
-  const int nvec = (n - head) >> 4;                      // <= 64
-  if (lane < head) o[lane] = (uint8_t)px(X0 + lane);
-  uint4* vec = reinterpret_cast<uint4*>(o + head);
-  for (int i = lane; i < nvec; i += 64) {
-    const int x = X0 + head + (i << 4);
-    uint4 q;
-    q.x = px4(x); q.y = px4(x + 4); q.z = px4(x + 8); q.w = px4(x + 12);
-    vec[i] = q;
-  }
-  const int t = head + (nvec << 4) + lane;               // the tail is shorter than 16 bytes
-  if (t < n) o[t] = (uint8_t)px(X0 + t);
+  wave_store_row(out + (int64_t)y * out_pitch + X0, X1 - X0, lane, px, px16_of(px));
 }
 
 }  // namespace
@@ -227,10 +219,9 @@ size_t flatten_scratch_bytes(int H, int W) { return flat_layout(H, W).total; }
 void flatten_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_flatten_params& fp, void* scratch, uint8_t* out,
                   int64_t out_pitch) {
   const FlatLayout l = flat_layout(H, W);
-  char* base = static_cast<char*>(scratch);
-  uint32_t* A = reinterpret_cast<uint32_t*>(base + l.a);
-  uint32_t* M = reinterpret_cast<uint32_t*>(base + l.m);
-  uint2* S = reinterpret_cast<uint2*>(base + l.s);
+  uint32_t* A = scratch_at<uint32_t>(scratch, l.a);
+  uint32_t* M = scratch_at<uint32_t>(scratch, l.m);
+  uint2* S = scratch_at<uint2>(scratch, l.s);
   const int r = fp.radius, nw4 = (W + 3) / 4;
   const uint32_t inv = fp.light_text ? 0xffffffffu : 0u;
   int p = 1;                                             // the largest power of two <= 2r + 1

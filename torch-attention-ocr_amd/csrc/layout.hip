@@ -14,7 +14,7 @@
 //   sat_tile_kernel      one wave per tile.  Top carry: S[y0][x+1] is the prefix over x of the column counts above the segment (a wave sum of
 //                        the columns left of the chunk, then 16 wave prefixes), kept in 16 registers per lane, lane l owning the columns
 //                        64k + l of the chunk.  Left carry of row y: the row counts of the chunks to its left, in lane y - y0.  Then row after
-//                        row: the 16-byte load pattern of wave_row (segment.hip), cut to the chunk -- a chunk is 63 words wide, so the at most
+//                        row: the 16-byte load pattern of wave_row (page_common.h), cut to the chunk -- a chunk is 63 words wide, so the at most
 //                        64 aligned words that cover it are one load per lane, a row whose word straddles the page's ends takes byte loads,
 //                        and all SAT_ROWS loads are issued before the first is used -- a 16-bit ink mask per lane, a wave prefix of the
 //                        popcounts, the row's prefix to LDS (padded by one word in 16: the lanes' 16-word runs start on distinct banks), and
@@ -28,6 +28,7 @@
 // appended, so the list is in reading order by construction.  Every thread follows the same control flow; thread 0 writes the lists.
 #include <algorithm>
 #include "ops.h"
+#include "page_common.h"
 #include "runs.h"
 
 namespace aocr {
@@ -47,26 +48,15 @@ struct SatLayout {                             // byte offsets into scratch_dev
 
 SatLayout sat_layout(int H, int W) {
   SatLayout l;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  ScratchCursor c;
   l.nseg = cdiv(H, SAT_ROWS);
   l.nch = cdiv(W, SAT_COLS);
-  size_t o = 0;
-  l.hist = o; o = up(o + 256 * sizeof(uint32_t));
-  l.hdr = o;  o = up(o + 4 * sizeof(int32_t));
-  l.cc = o;   o = up(o + (size_t)l.nseg * W * sizeof(uint32_t));      // column counts per segment, then their prefix down the page
-  l.rc = o;   o = up(o + (size_t)H * l.nch * sizeof(uint32_t));       // row counts per chunk
-  l.total = o;
+  l.hist = c.take(256 * sizeof(uint32_t));
+  l.hdr = c.take(4 * sizeof(int32_t));
+  l.cc = c.take((size_t)l.nseg * W * sizeof(uint32_t));               // column counts per segment, then their prefix down the page
+  l.rc = c.take((size_t)H * l.nch * sizeof(uint32_t));                // row counts per chunk
+  l.total = c.total();
   return l;
-}
-
-__device__ __forceinline__ uint32_t ink_mask4(uint32_t w, int thr, int light) {      // bit j: byte j of w is ink
-  uint32_t m = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int v = (int)((w >> (8 * j)) & 0xffu);
-    m |= (uint32_t)(light ? (v > thr) : (v <= thr)) << j;
-  }
-  return m;
 }
 
 // bit j: column xq + j of the row is ink and lies in [X0, X1); row + xq is 16-byte aligned; thr >= 0.  Every read is inside [0, W).
@@ -75,13 +65,9 @@ __device__ __forceinline__ uint32_t tile_mask(const uint8_t* __restrict__ row, i
   if (lo >= hi) return 0u;
   uint32_t m = 0;
   if (xq >= 0 && xq + 16 <= W) {                         // a whole aligned word inside the row
-    const uint4 q = *reinterpret_cast<const uint4*>(row + xq);
-    m = ink_mask4(q.x, thr, light) | (ink_mask4(q.y, thr, light) << 4) | (ink_mask4(q.z, thr, light) << 8) | (ink_mask4(q.w, thr, light) << 12);
+    m = ink_mask16(*reinterpret_cast<const uint4*>(row + xq), thr, light);
   } else {
-    for (int j = lo; j < hi; ++j) {                      // X0 <= xq + j < X1 <= W
-      const int v = row[xq + j];
-      m |= (uint32_t)(light ? (v > thr) : (v <= thr)) << j;
-    }
+    for (int j = lo; j < hi; ++j) m |= (uint32_t)is_ink(row[xq + j], thr, light) << j;       // X0 <= xq + j < X1 <= W
   }
   return m & ((1u << hi) - 1u) & ~((1u << lo) - 1u);
 }
@@ -89,11 +75,6 @@ __device__ __forceinline__ uint32_t tile_mask(const uint8_t* __restrict__ row, i
 // the first column of lane `lane`'s word for the chunk that starts at column X0 of `row`
 __device__ __forceinline__ int tile_word(const uint8_t* row, int X0, int lane) {
   return X0 - (int)((uintptr_t)(row + X0) & 15u) + 16 * lane;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
 }
 
 __device__ __forceinline__ uint32_t wave_prefix_incl(uint32_t v, int lane) {
@@ -106,14 +87,14 @@ __device__ __forceinline__ uint32_t wave_prefix_incl(uint32_t v, int lane) {
 
 __global__ __launch_bounds__(256) void sat_colcount_kernel(const uint8_t* __restrict__ page, int64_t pitch, int H, int W, int light, int fixed,
                                                            const int32_t* __restrict__ hdr, uint32_t* __restrict__ cc) {
-  const int thr = fixed >= 0 ? fixed : hdr[0];           // Otsu's was written by otsu_kernel just before; -1: nothing is ink
+  const int thr = ink_thr(fixed, hdr);
   const int x = blockIdx.x * 256 + threadIdx.x, seg = blockIdx.y;
   if (x >= W) return;
   const int y0 = seg * SAT_ROWS, y1 = min(y0 + SAT_ROWS, H);
   const uint8_t* p = page + (int64_t)y0 * pitch + x;
   uint32_t c = 0;
   if (thr >= 0)
-    for (int y = y0; y < y1; ++y, p += pitch) { const int v = *p; c += light ? (v > thr) : (v <= thr); }
+    for (int y = y0; y < y1; ++y, p += pitch) c += is_ink(*p, thr, light);
   cc[(size_t)seg * W + x] = c;
 }
 
@@ -121,7 +102,7 @@ __global__ __launch_bounds__(256) void sat_rowcount_kernel(const uint8_t* __rest
                                                            const int32_t* __restrict__ hdr, int nseg, int nch, uint32_t* __restrict__ rc) {
   const int lane = threadIdx.x & 63, seg = blockIdx.x * 4 + (threadIdx.x >> 6), chunk = blockIdx.y;
   if (seg >= nseg) return;
-  const int thr = fixed >= 0 ? fixed : hdr[0];
+  const int thr = ink_thr(fixed, hdr);
   const int X0 = chunk * SAT_COLS, X1 = min(X0 + SAT_COLS, W), y0 = seg * SAT_ROWS;
   uint32_t m[SAT_ROWS];
 #pragma unroll
@@ -167,7 +148,7 @@ __global__ __launch_bounds__(256) void sat_tile_kernel(const uint8_t* __restrict
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int seg = blockIdx.x * 4 + wave, chunk = blockIdx.y;
   const bool live = seg < nseg;                          // every wave takes every barrier
-  const int thr = fixed >= 0 ? fixed : hdr[0];
+  const int thr = ink_thr(fixed, hdr);
   const int X0 = chunk * SAT_COLS, X1 = min(X0 + SAT_COLS, W), y0 = seg * SAT_ROWS;
   const int nr = live ? min(SAT_ROWS, H - y0) : 0;
   uint32_t* st = stage[wave];
@@ -355,13 +336,12 @@ size_t integral_scratch_bytes(int H, int W) { return sat_layout(H, W).total; }
 void ink_integral(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, int threshold, int light_text, void* scratch, uint32_t* sat,
                   int64_t sat_pitch, int32_t* info) {
   const SatLayout l = sat_layout(H, W);
-  char* base = static_cast<char*>(scratch);
-  uint32_t* hist = reinterpret_cast<uint32_t*>(base + l.hist);
-  int32_t* hdr = reinterpret_cast<int32_t*>(base + l.hdr);
-  uint32_t* cc = reinterpret_cast<uint32_t*>(base + l.cc);
-  uint32_t* rc = reinterpret_cast<uint32_t*>(base + l.rc);
+  uint32_t* hist = scratch_at<uint32_t>(scratch, l.hist);
+  int32_t* hdr = scratch_at<int32_t>(scratch, l.hdr);
+  uint32_t* cc = scratch_at<uint32_t>(scratch, l.cc);
+  uint32_t* rc = scratch_at<uint32_t>(scratch, l.rc);
   const int light = light_text ? 1 : 0, fixed = threshold;
-  if (fixed < 0) otsu_threshold(s, page, pitch, H, W, hist, hdr);
+  page_threshold(s, page, pitch, H, W, fixed, hist, hdr);
   const dim3 tiles(cdiv(l.nseg, 4), l.nch);
   hipLaunchKernelGGL(sat_colcount_kernel, dim3(cdiv(W, 256), l.nseg), dim3(256), 0, s, page, pitch, H, W, light, fixed, hdr, cc);
   hipLaunchKernelGGL(sat_rowcount_kernel, tiles, dim3(256), 0, s, page, pitch, H, W, light, fixed, hdr, l.nseg, l.nch, rc);
@@ -369,13 +349,17 @@ void ink_integral(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int 
   hipLaunchKernelGGL(sat_tile_kernel, tiles, dim3(256), 0, s, page, pitch, H, W, light, fixed, hdr, l.nseg, l.nch, cc, rc, sat, sat_pitch, info);
 }
 
-size_t layout_scratch_bytes(int max_blocks) { return 2 * (((size_t)max_blocks * sizeof(Region) + 255) & ~(size_t)255); }
+size_t layout_scratch_bytes(int max_blocks) {            // the two level lists
+  ScratchCursor c;
+  c.take((size_t)max_blocks * sizeof(Region));
+  c.take((size_t)max_blocks * sizeof(Region));
+  return c.total();
+}
 
 void layout_blocks(hipStream_t s, const uint32_t* sat, int64_t sat_pitch, int H, int W, const aocr_layout_params& p, void* scratch, int max_blocks,
                    aocr_box* blocks, int32_t* counts) {
-  char* base = static_cast<char*>(scratch);
-  Region* la = reinterpret_cast<Region*>(base);
-  Region* lb = reinterpret_cast<Region*>(base + layout_scratch_bytes(max_blocks) / 2);
+  Region* la = scratch_at<Region>(scratch, 0);
+  Region* lb = scratch_at<Region>(scratch, layout_scratch_bytes(max_blocks) / 2);
   hipLaunchKernelGGL(xycut_kernel, dim3(1), dim3(SEG_THREADS), 0, s, sat, sat_pitch, H, W, p, la, lb, max_blocks, blocks, counts);
 }
 

@@ -5,8 +5,7 @@
 //
 // aocr_rotate_page is one launch.  The odd part of the turn comes from the host (it sets the output's shape), a half turn may be added
 // from orient_dev[0] on the device:
-//   rotate_rows_kernel  q = 0 or 2.  One wave per output row: 16 output bytes per lane where the output row is aligned, byte stores at its
-//                       ragged ends (deskew_kernel's pattern).  The 16 source bytes of a store are four words when the source run is 4-byte
+//   rotate_rows_kernel  q = 0 or 2.  One wave per output row (wave_store_row of page_common.h).  The 16 source bytes of a store are four words when the source run is 4-byte
 //                       aligned (one decision per row: all runs of a row are 16 bytes apart), else 16 byte loads; the half turn takes the
 //                       words in reverse order and reverses the bytes within each.  No LDS.
 //   rotate_tile_kernel  q = 1 or 3.  A workgroup owns a TILE x TILE block of the output.  Its source block goes into LDS row by row, 16
@@ -31,6 +30,7 @@
 // geometry.
 #include <algorithm>
 #include "ops.h"
+#include "page_common.h"
 
 namespace aocr {
 
@@ -48,14 +48,13 @@ struct OrientLayout {                          // byte offsets into scratch_dev
 
 OrientLayout orient_layout(int H, int W) {
   OrientLayout l;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  ScratchCursor c;
   l.gx = cdiv(W, 64);
   l.gy = cdiv(H, 4 * RUN_ROWS);
-  size_t o = 0;
-  l.hist = o; o = up(o + 256 * sizeof(uint32_t));
-  l.hdr = o;  o = up(o + 4 * sizeof(int32_t));
-  l.sums = o; o = up(o + (size_t)l.gx * l.gy * sizeof(uint4));        // N_h, N_v, the ink, 0 per workgroup
-  l.total = o;
+  l.hist = c.take(256 * sizeof(uint32_t));
+  l.hdr = c.take(4 * sizeof(int32_t));
+  l.sums = c.take((size_t)l.gx * l.gy * sizeof(uint4));               // N_h, N_v, the ink, 0 per workgroup
+  l.total = c.total();
   return l;
 }
 
@@ -69,14 +68,11 @@ __global__ __launch_bounds__(256) void rotate_rows_kernel(const uint8_t* __restr
   for (int y = blockIdx.x * 4 + wave; y < H; y += gridDim.x * 4) {
     const uint8_t* src = page + (int64_t)(rev ? H - 1 - y : y) * pitch;
     uint8_t* o = out + (int64_t)y * out_pitch;
-    const int head = min(W, (int)((16u - (uint32_t)((uintptr_t)o & 15u)) & 15u));
-    const int nvec = (W - head) >> 4;
-    if (lane < head) o[lane] = src[rev ? W - 1 - lane : lane];
+    const int head = row_head(o, W);                       // the first column of the row's first 16-byte store
     // output columns x .. x+15 come from source columns x .. x+15, or W-16-x .. W-1-x backwards; every run of the row has the same alignment
     const bool words = (((uintptr_t)src + (uintptr_t)(int64_t)(rev ? W - 16 - head : head)) & 3u) == 0;
-    uint4* vec = reinterpret_cast<uint4*>(o + head);
-    for (int i = lane; i < nvec; i += 64) {
-      const int x = head + (i << 4);
+    auto px1 = [&](int x) -> uint8_t { return src[rev ? W - 1 - x : x]; };
+    auto px16 = [&](int x) -> uint4 {
       const uint8_t* p = src + (rev ? W - 16 - x : x);
       uint32_t w[4];
       if (words) {
@@ -90,10 +86,9 @@ __global__ __launch_bounds__(256) void rotate_rows_kernel(const uint8_t* __restr
       uint4 q;
       if (rev) { q.x = bytes_rev(w[3]); q.y = bytes_rev(w[2]); q.z = bytes_rev(w[1]); q.w = bytes_rev(w[0]); }
       else { q.x = w[0]; q.y = w[1]; q.z = w[2]; q.w = w[3]; }
-      vec[i] = q;
-    }
-    const int t = head + (nvec << 4) + lane;               // the tail is shorter than 16 bytes
-    if (t < W) o[t] = src[rev ? W - 1 - t : t];
+      return q;
+    };
+    wave_store_row(o, W, lane, px1, px16);
   }
 }
 
@@ -160,14 +155,13 @@ __global__ __launch_bounds__(256) void runs_kernel(const uint8_t* __restrict__ p
                                                    const int32_t* __restrict__ hdr, uint4* __restrict__ sums) {
   __shared__ uint32_t wsum[4][3];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int thr = fixed >= 0 ? fixed : hdr[0];           // Otsu's was written by otsu_kernel just before; -1: nothing is ink
+  const int thr = ink_thr(fixed, hdr);
   const int x0 = blockIdx.x * 64, x = x0 + lane;
   const int y0 = (blockIdx.y * 4 + wave) * RUN_ROWS, y1 = thr < 0 ? y0 : min(H, y0 + RUN_ROWS);       // no threshold, or past the page: no rows
   const bool inside = x < W, left = lane == 0 && x0 > 0;
-  auto ink = [&](int v) -> bool { return light ? (v > thr) : (v <= thr); };
   const uint8_t* col = page + x;                         // read where inside; col[-1] where left
   uint64_t prev = 0;                                     // the mask of the row above: paper off the page
-  if (y0 > 0 && y0 < y1) prev = __ballot(inside && ink(col[(int64_t)(y0 - 1) * pitch]));
+  if (y0 > 0 && y0 < y1) prev = __ballot(inside && is_ink(col[(int64_t)(y0 - 1) * pitch], thr, light));
   uint32_t nh = 0, nv = 0, total = 0;
   for (int y = y0; y < y1; y += RUN_UNROLL) {
     int v[RUN_UNROLL], c[RUN_UNROLL];
@@ -181,8 +175,8 @@ __global__ __launch_bounds__(256) void runs_kernel(const uint8_t* __restrict__ p
 #pragma unroll
     for (int j = 0; j < RUN_UNROLL; ++j) {
       if (y + j >= y1) break;                            // uniform
-      const uint64_t m = __ballot(v[j] >= 0 && ink(v[j]));
-      const uint64_t carry = __ballot(c[j] >= 0 && ink(c[j]));       // bit 0, or nothing
+      const uint64_t m = __ballot(v[j] >= 0 && is_ink(v[j], thr, light));
+      const uint64_t carry = __ballot(c[j] >= 0 && is_ink(c[j], thr, light));       // bit 0, or nothing
       nh += (uint32_t)__popcll(m & ~((m << 1) | carry));
       nv += (uint32_t)__popcll(m & ~prev);
       total += (uint32_t)__popcll(m);
@@ -216,7 +210,7 @@ __global__ __launch_bounds__(256) void decide_kernel(const uint4* __restrict__ s
   if (threadIdx.x == 0) {
     orient[0] = part[0][1] > part[0][0] ? 1 : 0;         // a tie keeps the page
     orient[1] = (int32_t)part[0][0]; orient[2] = (int32_t)part[0][1];
-    orient[3] = fixed >= 0 ? fixed : hdr[0];
+    orient[3] = ink_thr(fixed, hdr);
     orient[4] = (int32_t)part[0][2];
     orient[5] = 0; orient[6] = 0; orient[7] = 0;
   }
@@ -237,11 +231,10 @@ size_t orient_scratch_bytes(int H, int W) { return orient_layout(H, W).total; }
 void estimate_orientation(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, int threshold, int light_text, void* scratch,
                           int32_t* orient) {
   const OrientLayout l = orient_layout(H, W);
-  char* base = static_cast<char*>(scratch);
-  uint32_t* hist = reinterpret_cast<uint32_t*>(base + l.hist);
-  int32_t* hdr = reinterpret_cast<int32_t*>(base + l.hdr);
-  uint4* sums = reinterpret_cast<uint4*>(base + l.sums);
-  if (threshold < 0) otsu_threshold(s, page, pitch, H, W, hist, hdr);
+  uint32_t* hist = scratch_at<uint32_t>(scratch, l.hist);
+  int32_t* hdr = scratch_at<int32_t>(scratch, l.hdr);
+  uint4* sums = scratch_at<uint4>(scratch, l.sums);
+  page_threshold(s, page, pitch, H, W, threshold, hist, hdr);
   hipLaunchKernelGGL(runs_kernel, dim3(l.gx, l.gy), dim3(256), 0, s, page, pitch, H, W, light_text ? 1 : 0, threshold, hdr, sums);
   hipLaunchKernelGGL(decide_kernel, dim3(1), dim3(256), 0, s, sums, l.gx * l.gy, threshold, hdr, orient);
 }

@@ -17,8 +17,7 @@
 //   quad_final_kernel  one thread unpacks the keys, takes the four cross products in int64 and writes the 16 words.
 // Integer maxima do not depend on their order: the words do not depend on the launch geometry or on the order of the atomics.
 //
-// aocr_warp_page is one launch: warp_kernel, one wave per output row, 16 output bytes per lane where the output row is aligned and byte
-// stores at its ragged ends (deskew_kernel's pattern).  A lane's 16 pixels are 16 neighbouring source positions, the lanes of a wave
+// aocr_warp_page is one launch: warp_kernel, one wave per output row (wave_store_row of page_common.h).  A lane's 16 pixels are 16 neighbouring source positions, the lanes of a wave
 // continue them along the row: the four taps of a wave's pixels lie in two (for a keystone a few) source rows and stay in the same cache
 // lines from lane to lane.  The products c1*y, c4*y, c7*y are taken once per row: (c0*x + c1*y) + c2 rounds the same whether c1*y was
 // rounded now or before.  Two correctly rounded fp64 divisions per pixel (hipcc's default: no fast-math, no reciprocal shortcut).
@@ -27,6 +26,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include "ops.h"
+#include "page_common.h"
 
 namespace aocr {
 
@@ -43,18 +43,12 @@ struct QuadLayout {                            // byte offsets into scratch_dev
 
 QuadLayout quad_layout(int H, int W) {
   QuadLayout l;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t o = 0;
-  l.cc = o;     o = up(o + components_scratch_bytes(H, W));
-  l.labels = o; o = up(o + (size_t)H * W * sizeof(int32_t));
-  l.hdr = o;    o = up(o + 64 + KEY_COUNT * sizeof(uint64_t));         // info (4 words, padded to 64 bytes), then the keys
-  l.total = o;
+  ScratchCursor c;
+  l.cc = c.take(components_scratch_bytes(H, W));
+  l.labels = c.take((size_t)H * W * sizeof(int32_t));
+  l.hdr = c.take(64 + KEY_COUNT * sizeof(uint64_t));                   // info (4 words, padded to 64 bytes), then the keys
+  l.total = c.total();
   return l;
-}
-
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-  for (int d = 32; d >= 1; d >>= 1) { const uint64_t o = __shfl_xor(v, d); v = o > v ? o : v; }
-  return v;
 }
 
 // one lane of a wave: the word only ever grows, so a key that does not beat a (possibly stale) read of it cannot beat its true value
@@ -75,7 +69,7 @@ __global__ __launch_bounds__(QUAD_THREADS) void quad_sheet_kernel(const int32_t*
       const uint64_t key = (area << 32) | (uint64_t)(0xffffffffu - (uint32_t)i);
       best = key > best ? key : best;
     }
-  best = wave_max_u64(best);
+  best = wave_max(best);
   if ((threadIdx.x & 63) == 0 && best) offer(&keys[KEY_SHEET], best);
 }
 
@@ -97,7 +91,7 @@ __global__ __launch_bounds__(QUAD_THREADS) void quad_corner_kernel(const int32_t
       tl = k0 > tl ? k0 : tl; tr = k1 > tr ? k1 : tr; br = k2 > br ? k2 : br; bl = k3 > bl ? k3 : bl;
     }
   if (!__ballot(tl != 0)) return;                          // every key of a sheet pixel is non-zero
-  tl = wave_max_u64(tl); tr = wave_max_u64(tr); br = wave_max_u64(br); bl = wave_max_u64(bl);
+  tl = wave_max(tl); tr = wave_max(tr); br = wave_max(br); bl = wave_max(bl);
   if ((threadIdx.x & 63) == 0) { offer(&keys[KEY_TL], tl); offer(&keys[KEY_TR], tr); offer(&keys[KEY_BR], br); offer(&keys[KEY_BL], bl); }
 }
 
@@ -155,20 +149,7 @@ __global__ __launch_bounds__(256) void warp_kernel(const uint8_t* __restrict__ p
       const uint32_t bot = tap(ix, iy + 1) * (256u - fx) + tap(ix + 1, iy + 1) * fx;
       return (top * (256u - fy) + bot * fy + 32768u) >> 16;                                      // <= 255
     };
-    auto px4 = [&](int x) -> uint32_t { return px(x) | (px(x + 1) << 8) | (px(x + 2) << 16) | (px(x + 3) << 24); };
-    uint8_t* o = out + (int64_t)y * out_pitch;
-    const int head = min(Wo, (int)((16u - (uint32_t)((uintptr_t)o & 15u)) & 15u));
-    const int nvec = (Wo - head) >> 4;
-    if (lane < head) o[lane] = (uint8_t)px(lane);
-    uint4* vec = reinterpret_cast<uint4*>(o + head);
-    for (int i = lane; i < nvec; i += 64) {
-      const int x = head + (i << 4);
-      uint4 q;
-      q.x = px4(x); q.y = px4(x + 4); q.z = px4(x + 8); q.w = px4(x + 12);
-      vec[i] = q;
-    }
-    const int t = head + (nvec << 4) + lane;               // the tail is shorter than 16 bytes
-    if (t < Wo) o[t] = (uint8_t)px(t);
+    wave_store_row(out + (int64_t)y * out_pitch, Wo, lane, px, px16_of(px));
   }
 }
 
@@ -198,12 +179,12 @@ size_t quad_scratch_bytes(int H, int W) { return quad_layout(H, W).total; }
 void find_page_quad(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, int threshold, int dark_paper, void* scratch,
                     int32_t* quad) {
   const QuadLayout l = quad_layout(H, W);
-  char* base = static_cast<char*>(scratch);
-  int32_t* labels = reinterpret_cast<int32_t*>(base + l.labels);
-  int32_t* info = reinterpret_cast<int32_t*>(base + l.hdr);
-  uint64_t* keys = reinterpret_cast<uint64_t*>(base + l.hdr + 64);
-  label_components(s, page, pitch, H, W, threshold, dark_paper ? 0 : 1, 8, base + l.cc, labels, W, 1, nullptr, info);
-  const ComponentAreas a = component_areas(H, W, base + l.cc);
+  void* cc = scratch_at<char>(scratch, l.cc);
+  int32_t* labels = scratch_at<int32_t>(scratch, l.labels);
+  int32_t* info = scratch_at<int32_t>(scratch, l.hdr);
+  uint64_t* keys = scratch_at<uint64_t>(scratch, l.hdr + 64);
+  label_components(s, page, pitch, H, W, threshold, dark_paper ? 0 : 1, 8, cc, labels, W, 1, nullptr, info);
+  const ComponentAreas a = component_areas(H, W, cc);
   (void)hipMemsetAsync(keys, 0, KEY_COUNT * sizeof(uint64_t), s);
   const dim3 grid(cdiv(W, QUAD_THREADS), cdiv(H, QUAD_ROWS));
   hipLaunchKernelGGL(quad_sheet_kernel, grid, dim3(QUAD_THREADS), 0, s, labels, H, W, a.rec, a.sw, keys);

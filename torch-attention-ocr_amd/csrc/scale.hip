@@ -15,8 +15,7 @@
 //                      offset, and the lane whose bins contain a quartile's index finds the bin.  Lane 0 writes the other five words.
 // Integer sums do not depend on their order: the words do not depend on the launch geometry or on the order of the atomics.
 //
-// aocr_resize_page is one launch: resize_kernel, one wave per output row, 16 output bytes per lane where the output row is aligned and byte
-// stores at its ragged ends (deskew_kernel's pattern).  With a = X*W, b = a + W the source columns of output pixel X are a / Wo ..
+// aocr_resize_page is one launch: resize_kernel, one wave per output row (wave_store_row of page_common.h).  With a = X*W, b = a + W the source columns of output pixel X are a / Wo ..
 // (b - 1) / Wo: a lane takes one 32-bit division for its first pixel and then steps quotient and remainder by W / Wo and W % Wo.  The row's
 // source rows and their weights are the same for the whole wave (scalar registers).  Per pixel: for each source column the weighted
 // column sum over the rows (below 2^22, 32 bits), times the column's weight into a 64-bit sum (one v_mad_u64_u32), then the division by H*W.
@@ -25,6 +24,7 @@
 // adds less than 1/d.  d = 1 (a page of one pixel) has no such m and takes n itself.
 #include <algorithm>
 #include "ops.h"
+#include "page_common.h"
 
 namespace aocr {
 
@@ -40,13 +40,12 @@ struct GlyphLayout {                           // byte offsets into scratch_dev
 
 GlyphLayout glyph_layout(int H, int W) {
   GlyphLayout l;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  size_t o = 0;
-  l.cc = o;     o = up(o + components_scratch_bytes(H, W));
-  l.labels = o; o = up(o + (size_t)H * W * sizeof(int32_t));
-  l.hist = o;   o = up(o + GLYPH_BINS * sizeof(uint32_t));
-  l.hdr = o;    o = up(o + 64);                                        // info (4 words, padded to 64 bytes)
-  l.total = o;
+  ScratchCursor c;
+  l.cc = c.take(components_scratch_bytes(H, W));
+  l.labels = c.take((size_t)H * W * sizeof(int32_t));
+  l.hist = c.take(GLYPH_BINS * sizeof(uint32_t));
+  l.hdr = c.take(64);                                                  // info (4 words, padded to 64 bytes)
+  l.total = c.total();
   return l;
 }
 
@@ -151,21 +150,15 @@ __global__ __launch_bounds__(256) void resize_kernel(const uint8_t* __restrict__
       return p0 | (p1 << 8) | (p2 << 16) | (p3 << 24);
     };
     auto start = [&](int X, int& q, int& r) { const int a = X * W; q = a / Wo; r = a - q * Wo; };
-    uint8_t* o = out + (int64_t)Y * out_pitch;
-    const int head = min(Wo, (int)((16u - (uint32_t)((uintptr_t)o & 15u)) & 15u));
-    const int nvec = (Wo - head) >> 4;
-    int q, r;
-    if (lane < head) { start(lane, q, r); o[lane] = (uint8_t)px(lane, q, r); }
-    uint4* vec = reinterpret_cast<uint4*>(o + head);
-    for (int i = lane; i < nvec; i += 64) {
-      const int X = head + (i << 4);
+    auto px1 = [&](int X) -> uint32_t { int q, r; start(X, q, r); return px(X, q, r); };
+    auto px16 = [&](int X) -> uint4 {                      // one division for the 16 pixels of a store
+      int q, r;
       start(X, q, r);
       uint4 v;
       v.x = px4(X, q, r); v.y = px4(X + 4, q, r); v.z = px4(X + 8, q, r); v.w = px4(X + 12, q, r);
-      vec[i] = v;
-    }
-    const int t = head + (nvec << 4) + lane;               // the tail is shorter than 16 bytes
-    if (t < Wo) { start(t, q, r); o[t] = (uint8_t)px(t, q, r); }
+      return v;
+    };
+    wave_store_row(out + (int64_t)Y * out_pitch, Wo, lane, px1, px16);
   }
 }
 
@@ -176,12 +169,12 @@ size_t glyph_scratch_bytes(int H, int W) { return glyph_layout(H, W).total; }
 void estimate_glyph_size(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_glyph_params& p, void* scratch,
                          int32_t* glyph) {
   const GlyphLayout l = glyph_layout(H, W);
-  char* base = static_cast<char*>(scratch);
-  int32_t* labels = reinterpret_cast<int32_t*>(base + l.labels);
-  uint32_t* hist = reinterpret_cast<uint32_t*>(base + l.hist);
-  int32_t* info = reinterpret_cast<int32_t*>(base + l.hdr);
-  label_components(s, page, pitch, H, W, p.threshold, p.light_text, p.connectivity, base + l.cc, labels, W, 1, nullptr, info);
-  const ComponentAreas a = component_areas(H, W, base + l.cc);
+  void* cc = scratch_at<char>(scratch, l.cc);
+  int32_t* labels = scratch_at<int32_t>(scratch, l.labels);
+  uint32_t* hist = scratch_at<uint32_t>(scratch, l.hist);
+  int32_t* info = scratch_at<int32_t>(scratch, l.hdr);
+  label_components(s, page, pitch, H, W, p.threshold, p.light_text, p.connectivity, cc, labels, W, 1, nullptr, info);
+  const ComponentAreas a = component_areas(H, W, cc);
   (void)hipMemsetAsync(hist, 0, GLYPH_BINS * sizeof(uint32_t), s);
   hipLaunchKernelGGL(glyph_hist_kernel, dim3(cdiv(W, GLYPH_THREADS), cdiv(H, GLYPH_ROWS)), dim3(GLYPH_THREADS), 0, s, labels, H, W, a.rec, a.sw,
                      p.min_size, p.max_size, p.max_aspect, hist);

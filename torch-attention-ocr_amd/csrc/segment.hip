@@ -4,8 +4,9 @@
 // restatement (tests/segment_ref.py) matches exactly.
 //
 // Launches of one call, all on the caller's stream, intermediates in the caller's scratch:
-//   hist_kernel     (Otsu only) one wave per row, 16-byte loads over the aligned middle of the row and byte loads for the unaligned head
-//                   and tail; a 256-bin LDS histogram per wave, flushed with integer global atomics (order-independent: exact).
+//   hist_kernel     (Otsu only) one wave per row (wave_row of page_common.h, which holds the row walks, the ink test and the scratch
+//                   layout of all the page kernels); a 256-bin LDS histogram per wave, flushed with integer global atomics
+//                   (order-independent: exact).
 //   otsu_kernel     one wave: lane l owns bins 4l..4l+3, int64 prefix sums over lanes, the 255 scores in parallel, then the argmax with
 //                   "larger score, then lower t" (= the first strictly largest of the serial loop).  Otsu only: a fixed threshold is a
 //                   launch argument of the kernels that need it.
@@ -21,6 +22,7 @@
 // element is (suffix min), and the k-th start pairs with the k-th end (prefix sums).  No step depends on launch geometry or on atomics order.
 #include <algorithm>
 #include "ops.h"
+#include "page_common.h"
 #include "runs.h"
 
 namespace aocr {
@@ -34,44 +36,19 @@ struct SegLayout {                             // byte offsets into scratch_dev
 
 SegLayout seg_layout(int H, int W, int max_boxes) {
   SegLayout l;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  ScratchCursor c;
   l.max_bands = (H + 1) / 2;                   // bands are separated by at least one non-text row
   l.cap = std::min(max_boxes, (W + 1) / 2);    // words of one band that can reach boxes_dev
-  size_t o = 0;
-  l.hist = o;    o = up(o + 256 * sizeof(uint32_t));
-  l.hdr = o;     o = up(o + 4 * sizeof(int32_t));                       // threshold, bands, boxes found
-  l.row_ink = o; o = up(o + (size_t)H * sizeof(int32_t));
-  l.bands = o;   o = up(o + (size_t)l.max_bands * sizeof(uint32_t));    // y0 | y1 << 16
-  l.wcount = o;  o = up(o + (size_t)l.max_bands * sizeof(int32_t));
-  l.woffset = o; o = up(o + (size_t)l.max_bands * sizeof(int32_t));
-  l.col = o;     o = up(o + (size_t)l.max_bands * W * sizeof(uint16_t));
-  l.words = o;   o = up(o + (size_t)l.max_bands * l.cap * sizeof(uint32_t));   // x0 | x1 << 16, unpadded
-  l.total = o;
+  l.hist = c.take(256 * sizeof(uint32_t));
+  l.hdr = c.take(4 * sizeof(int32_t));                                  // threshold, bands, boxes found
+  l.row_ink = c.take((size_t)H * sizeof(int32_t));
+  l.bands = c.take((size_t)l.max_bands * sizeof(uint32_t));             // y0 | y1 << 16
+  l.wcount = c.take((size_t)l.max_bands * sizeof(int32_t));
+  l.woffset = c.take((size_t)l.max_bands * sizeof(int32_t));
+  l.col = c.take((size_t)l.max_bands * W * sizeof(uint16_t));
+  l.words = c.take((size_t)l.max_bands * l.cap * sizeof(uint32_t));     // x0 | x1 << 16, unpadded
+  l.total = c.total();
   return l;
-}
-
-// f(word, n): the low n bytes of word are n consecutive pixels of the row; every pixel of the row is visited exactly once by the wave
-template <class F> __device__ __forceinline__ void wave_row(const uint8_t* __restrict__ row, int W, int lane, F&& f) {
-  const int head = min(W, (int)((16u - (uint32_t)((uintptr_t)row & 15u)) & 15u));
-  const int nvec = (W - head) >> 4;
-  if (lane < head) f((uint32_t)row[lane], 1);
-  const uint4* v = reinterpret_cast<const uint4*>(row + head);
-  for (int i = lane; i < nvec; i += 64) {
-    const uint4 q = v[i];
-    f(q.x, 4); f(q.y, 4); f(q.z, 4); f(q.w, 4);
-  }
-  const int t = head + (nvec << 4) + lane;     // the tail is shorter than 16 bytes
-  if (t < W) f((uint32_t)row[t], 1);
-}
-
-__device__ __forceinline__ int ink_bytes(uint32_t w, int n, int thr, int light) {
-  int c = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int v = (int)((w >> (8 * j)) & 0xffu);
-    if (j < n) c += light ? (v > thr) : (v <= thr);
-  }
-  return c;
 }
 
 __global__ __launch_bounds__(256) void hist_kernel(const uint8_t* __restrict__ page, int64_t pitch, int H, int W, uint32_t* __restrict__ hist) {
@@ -127,11 +104,11 @@ __global__ __launch_bounds__(64) void otsu_kernel(const uint32_t* __restrict__ h
 __global__ __launch_bounds__(256) void rowprof_kernel(const uint8_t* __restrict__ page, int64_t pitch, int H, int W, int light, int fixed,
                                                       const int32_t* __restrict__ hdr, int32_t* __restrict__ row_ink) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int thr = fixed >= 0 ? fixed : hdr[0];           // a fixed threshold is a launch argument; Otsu's was written by otsu_kernel just before
+  const int thr = ink_thr(fixed, hdr);
   for (int y = blockIdx.x * 4 + wave; y < H; y += gridDim.x * 4) {
     int c = 0;
     if (thr >= 0) wave_row(page + (int64_t)y * pitch, W, lane, [&](uint32_t w, int n) { c += ink_bytes(w, n, thr, light); });
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
+    c = wave_sum(c);
     if (lane == 0) row_ink[y] = c;
   }
 }
@@ -148,7 +125,7 @@ __global__ __launch_bounds__(SEG_THREADS) void bands_kernel(const int32_t* __res
 __global__ __launch_bounds__(256) void colprof_kernel(const uint8_t* __restrict__ page, int64_t pitch, int W, int light, int fixed, int max_bands,
                                                       const int32_t* __restrict__ hdr, const uint32_t* __restrict__ bands,
                                                       uint16_t* __restrict__ col) {
-  const int thr = fixed >= 0 ? fixed : hdr[0], nb = min(hdr[1], max_bands);
+  const int thr = ink_thr(fixed, hdr), nb = min(hdr[1], max_bands);
   const int x = blockIdx.x * 256 + threadIdx.x;
   if (x >= W) return;
   for (int b = blockIdx.y; b < nb; b += gridDim.y) {
@@ -156,7 +133,7 @@ __global__ __launch_bounds__(256) void colprof_kernel(const uint8_t* __restrict_
     const int y0 = (int)(yy & 0xffffu), y1 = (int)(yy >> 16);
     const uint8_t* p = page + (int64_t)y0 * pitch + x;
     int c = 0;
-    for (int y = y0; y < y1; ++y, p += pitch) { const int v = *p; c += light ? (v > thr) : (v <= thr); }
+    for (int y = y0; y < y1; ++y, p += pitch) c += is_ink(*p, thr, light);
     col[(size_t)b * W + x] = (uint16_t)c;                 // <= SEG_MAX_DIM
   }
 }
@@ -188,7 +165,7 @@ __global__ __launch_bounds__(SEG_THREADS) void offsets_kernel(const int32_t* __r
   int total;
   int o = block_scan_excl<false>(sum, 0, [](int a, int b) { return a + b; }, wtot, &total);
   for (int b = lo; b < hi; ++b) { woffset[b] = o; o += wcount[b]; }
-  if (threadIdx.x == 0) { hdr[2] = total; counts[0] = total; counts[1] = nb; counts[2] = fixed >= 0 ? fixed : hdr[0]; counts[3] = 0; }
+  if (threadIdx.x == 0) { hdr[2] = total; counts[0] = total; counts[1] = nb; counts[2] = ink_thr(fixed, hdr); counts[3] = 0; }
 }
 
 __global__ __launch_bounds__(256) void emit_kernel(const int32_t* __restrict__ hdr, const uint32_t* __restrict__ bands,
@@ -210,7 +187,7 @@ __global__ __launch_bounds__(256) void emit_kernel(const int32_t* __restrict__ h
   const int x0 = (int)(xx & 0xffffu), x1 = (int)(xx >> 16), y0 = (int)(yy & 0xffffu), y1 = (int)(yy >> 16);
   int ink = 0;
   for (int x = x0 + lane; x < x1; x += 64) ink += col[(size_t)b * W + x];
-  for (int d = 32; d >= 1; d >>= 1) ink += __shfl_xor(ink, d);
+  ink = wave_sum(ink);
   if (lane == 0) {
     aocr_box bx;
     bx.x0 = max(0, x0 - pad_x); bx.y0 = max(0, y0 - pad_y); bx.x1 = min(W, x1 + pad_x); bx.y1 = min(H, y1 + pad_y);
@@ -233,18 +210,17 @@ void otsu_threshold(hipStream_t s, const uint8_t* page, int64_t pitch, int H, in
 void segment_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_segment_params& p, void* scratch, int max_boxes,
                   aocr_box* boxes, int32_t* counts) {
   const SegLayout l = seg_layout(H, W, max_boxes);
-  char* base = static_cast<char*>(scratch);
-  uint32_t* hist = reinterpret_cast<uint32_t*>(base + l.hist);
-  int32_t* hdr = reinterpret_cast<int32_t*>(base + l.hdr);
-  int32_t* row_ink = reinterpret_cast<int32_t*>(base + l.row_ink);
-  uint32_t* bands = reinterpret_cast<uint32_t*>(base + l.bands);
-  int32_t* wcount = reinterpret_cast<int32_t*>(base + l.wcount);
-  int32_t* woffset = reinterpret_cast<int32_t*>(base + l.woffset);
-  uint16_t* col = reinterpret_cast<uint16_t*>(base + l.col);
-  uint32_t* words = reinterpret_cast<uint32_t*>(base + l.words);
+  uint32_t* hist = scratch_at<uint32_t>(scratch, l.hist);
+  int32_t* hdr = scratch_at<int32_t>(scratch, l.hdr);
+  int32_t* row_ink = scratch_at<int32_t>(scratch, l.row_ink);
+  uint32_t* bands = scratch_at<uint32_t>(scratch, l.bands);
+  int32_t* wcount = scratch_at<int32_t>(scratch, l.wcount);
+  int32_t* woffset = scratch_at<int32_t>(scratch, l.woffset);
+  uint16_t* col = scratch_at<uint16_t>(scratch, l.col);
+  uint32_t* words = scratch_at<uint32_t>(scratch, l.words);
   const int light = p.light_text ? 1 : 0, fixed = p.threshold;    // >= 0: no histogram, no Otsu launch, hdr[0] unused
   const int row_blocks = std::min(cdiv(H, 4), 2048);
-  if (p.threshold < 0) otsu_threshold(s, page, pitch, H, W, hist, hdr);
+  page_threshold(s, page, pitch, H, W, fixed, hist, hdr);
   hipLaunchKernelGGL(rowprof_kernel, dim3(row_blocks), dim3(256), 0, s, page, pitch, H, W, light, fixed, hdr, row_ink);
   hipLaunchKernelGGL(bands_kernel, dim3(1), dim3(SEG_THREADS), 0, s, row_ink, H, p.min_row_ink,
                      std::min(p.merge_gap, SEG_MAX_DIM), p.min_line_h, bands, hdr);

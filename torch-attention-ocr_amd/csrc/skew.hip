@@ -4,18 +4,19 @@
 //
 // Launches of one aocr_estimate_skew, all on the caller's stream, intermediates in the caller's scratch:
 //   (Otsu only) otsu_threshold of segment.hip: memset, hist_kernel, otsu_kernel -- what aocr_segment_page enqueues for its steps 1-2.
-//   strips_kernel    the one page read.  A workgroup owns STRIP_ROWS consecutive rows, one wave per row at a time: 16-byte loads over the
-//                    aligned middle of the row, byte loads for the head and tail, a 16-bit ink mask per load split at the strip boundary
-//                    (a load starts anywhere in its 32-column strip: the row's base address is arbitrary) and added to the per-strip
-//                    counters in LDS with integer atomics.  R is written as uint8 [strip][row], 8 rows per store.
+//   strips_kernel    the one page read.  A workgroup owns STRIP_ROWS consecutive rows, one wave per row at a time (wave_row16 of
+//                    page_common.h): a 16-bit ink mask per 16-byte load split at the strip boundary (a load starts anywhere in its
+//                    32-column strip: the row's base address is arbitrary) and added to the per-strip counters in LDS with integer
+//                    atomics.  R is written as uint8 [strip][row], 8 rows per store.
 //   sweep_kernel     grid (row chunk, candidate): one thread per profile row r walks the strips (consecutive threads read consecutive
 //                    bytes of R), squares its sum and the workgroup adds the squares in uint64: one partial per (candidate, chunk).
 //   pick_kernel      one workgroup: the partials of a candidate are added in chunk order, the scores written, the winner taken by the
 //                    total order "larger score, then earlier in 0, -1, +1, -2, +2, ...".
-// aocr_deskew_page is one launch: deskew_kernel, one wave per output row, 16 output bytes per lane where the output row is aligned and
-// byte stores at its ragged ends; the source of a row is one run of the page per 16-pixel group, shifted by the row's horizontal offset.
+// aocr_deskew_page is one launch: deskew_kernel, one wave per output row (wave_store_row of page_common.h); the source of a row is one
+// run of the page per 16-pixel group, shifted by the row's horizontal offset.
 #include <algorithm>
 #include "ops.h"
+#include "page_common.h"
 
 namespace aocr {
 
@@ -41,66 +42,40 @@ __host__ __device__ inline int max_off(int nb, int cx, int slope) {
 
 SkewLayout skew_layout(int H, int W, int n_steps) {
   SkewLayout l;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  ScratchCursor c;
   l.nb = (W + 31) / 32;
   l.hs = (H + 15) & ~15;                       // rows of one strip of R, padded so that every 8-row store is aligned and inside
   const int dmax = std::max(max_off(l.nb, W >> 1, SLOPE_MAX), max_off(l.nb, W >> 1, -SLOPE_MAX));
   l.max_chunks = cdiv(H + 2 * dmax, SWEEP_THREADS);
-  size_t o = 0;
-  l.hist = o;     o = up(o + 256 * sizeof(uint32_t));
-  l.hdr = o;      o = up(o + 4 * sizeof(int32_t));
-  l.strips = o;   o = up(o + (size_t)l.nb * l.hs);
-  l.partials = o; o = up(o + (size_t)(2 * n_steps + 1) * l.max_chunks * sizeof(uint64_t));
-  l.total = o;
+  l.hist = c.take(256 * sizeof(uint32_t));
+  l.hdr = c.take(4 * sizeof(int32_t));
+  l.strips = c.take((size_t)l.nb * l.hs);
+  l.partials = c.take((size_t)(2 * n_steps + 1) * l.max_chunks * sizeof(uint64_t));
+  l.total = c.total();
   return l;
-}
-
-// bit j of the result: byte j of w is ink
-__device__ __forceinline__ uint32_t ink_mask4(uint32_t w, int thr, int light) {
-  uint32_t m = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int v = (int)((w >> (8 * j)) & 0xffu);
-    m |= (uint32_t)(light ? (v > thr) : (v <= thr)) << j;
-  }
-  return m;
 }
 
 __global__ __launch_bounds__(256) void strips_kernel(const uint8_t* __restrict__ page, int64_t pitch, int H, int W, int light, int fixed,
                                                      const int32_t* __restrict__ hdr, int nb, int hs, uint8_t* __restrict__ R) {
   __shared__ uint32_t cnt[STRIP_ROWS][MAX_STRIPS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int thr = fixed >= 0 ? fixed : hdr[0];           // Otsu's was written by otsu_kernel just before; -1: nothing is ink
+  const int thr = ink_thr(fixed, hdr);
   const int y0 = blockIdx.x * STRIP_ROWS;
   for (int i = threadIdx.x; i < STRIP_ROWS * MAX_STRIPS; i += 256) (&cnt[0][0])[i] = 0;
   __syncthreads();
   for (int j = wave; j < STRIP_ROWS; j += 4) {
     const int y = y0 + j;
     if (y >= H || thr < 0) continue;
-    const uint8_t* row = page + (int64_t)y * pitch;
     uint32_t* c = cnt[j];
-    const int head = min(W, (int)((16u - (uint32_t)((uintptr_t)row & 15u)) & 15u));
-    const int nvec = (W - head) >> 4;
-    if (lane < head) {                                   // head < 16: strip 0
-      const int v = row[lane];
-      if (light ? (v > thr) : (v <= thr)) atomicAdd(&c[0], 1u);
-    }
-    const uint4* vec = reinterpret_cast<const uint4*>(row + head);
-    for (int i = lane; i < nvec; i += 64) {
-      const uint4 q = vec[i];
-      const uint32_t m = ink_mask4(q.x, thr, light) | (ink_mask4(q.y, thr, light) << 4) | (ink_mask4(q.z, thr, light) << 8) |
-                         (ink_mask4(q.w, thr, light) << 12);
-      const int x = head + (i << 4);                     // columns x .. x+15 < W
-      const int first = min(16, 32 - (x & 31));          // of them in strip x >> 5, the others in the next one
-      const int c0 = __popc(m & ((1u << first) - 1u)), c1 = __popc(m >> first);
-      if (c0) atomicAdd(&c[x >> 5], (uint32_t)c0);
-      if (c1) atomicAdd(&c[(x >> 5) + 1], (uint32_t)c1);  // c1 > 0: column x + first < W lies in that strip
-    }
-    const int t = head + (nvec << 4) + lane;             // the tail is shorter than 16 bytes
-    if (t < W) {
-      const int v = row[t];
-      if (light ? (v > thr) : (v <= thr)) atomicAdd(&c[t >> 5], 1u);
-    }
+    wave_row16(page + (int64_t)y * pitch, W, lane,
+               [&](int x, uint32_t v) { if (is_ink((int)v, thr, light)) atomicAdd(&c[x >> 5], 1u); },
+               [&](int x, const uint4& q) {                // columns x .. x+15 < W
+                 const uint32_t m = ink_mask16(q, thr, light);
+                 const int first = min(16, 32 - (x & 31)); // of them in strip x >> 5, the others in the next one
+                 const int c0 = __popc(m & ((1u << first) - 1u)), c1 = __popc(m >> first);
+                 if (c0) atomicAdd(&c[x >> 5], (uint32_t)c0);
+                 if (c1) atomicAdd(&c[(x >> 5) + 1], (uint32_t)c1);      // c1 > 0: column x + first < W lies in that strip
+               });
   }
   __syncthreads();
   for (int b = threadIdx.x; b < nb; b += 256) {          // rows >= H of the last workgroup are zero: y0 + 8 <= hs
@@ -126,7 +101,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) void sweep_kernel(const uint8_t* __r
     }
   }
   uint64_t v = (uint64_t)P * P;                                           // P <= W <= 2^14
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
@@ -157,7 +132,7 @@ __global__ __launch_bounds__(256) void pick_kernel(const uint64_t* __restrict__ 
   if (threadIdx.x == 0) {
     const int rk = br[0];                                // candidate 0 always exists: rk <= 2K
     const int k = (rk & 1) ? -((rk + 1) >> 1) : (rk >> 1);
-    skew[0] = k; skew[1] = k * step; skew[2] = fixed >= 0 ? fixed : hdr[0]; skew[3] = 0;
+    skew[0] = k; skew[1] = k * step; skew[2] = ink_thr(fixed, hdr); skew[3] = 0;
   }
 }
 
@@ -172,20 +147,7 @@ __global__ __launch_bounds__(256) void deskew_kernel(const uint8_t* __restrict__
       const int sy = y + (((x - cx) * s + 32768) >> 16), sx = x - dx;
       return ((unsigned)sy < (unsigned)H && (unsigned)sx < (unsigned)W) ? (uint32_t)page[(int64_t)sy * pitch + sx] : fill;
     };
-    auto px4 = [&](int x) -> uint32_t { return px(x) | (px(x + 1) << 8) | (px(x + 2) << 16) | (px(x + 3) << 24); };
-    uint8_t* o = out + (int64_t)y * out_pitch;
-    const int head = min(W, (int)((16u - (uint32_t)((uintptr_t)o & 15u)) & 15u));
-    const int nvec = (W - head) >> 4;
-    if (lane < head) o[lane] = (uint8_t)px(lane);
-    uint4* vec = reinterpret_cast<uint4*>(o + head);
-    for (int i = lane; i < nvec; i += 64) {
-      const int x = head + (i << 4);
-      uint4 q;
-      q.x = px4(x); q.y = px4(x + 4); q.z = px4(x + 8); q.w = px4(x + 12);
-      vec[i] = q;
-    }
-    const int t = head + (nvec << 4) + lane;             // the tail is shorter than 16 bytes
-    if (t < W) o[t] = (uint8_t)px(t);
+    wave_store_row(out + (int64_t)y * out_pitch, W, lane, px, px16_of(px));
   }
 }
 
@@ -196,15 +158,14 @@ size_t skew_scratch_bytes(int H, int W, int n_steps) { return skew_layout(H, W, 
 void estimate_skew(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_skew_params& p, void* scratch, int32_t* skew,
                    uint64_t* scores) {
   const SkewLayout l = skew_layout(H, W, p.n_steps);
-  char* base = static_cast<char*>(scratch);
-  uint32_t* hist = reinterpret_cast<uint32_t*>(base + l.hist);
-  int32_t* hdr = reinterpret_cast<int32_t*>(base + l.hdr);
-  uint8_t* R = reinterpret_cast<uint8_t*>(base + l.strips);
-  uint64_t* partials = reinterpret_cast<uint64_t*>(base + l.partials);
+  uint32_t* hist = scratch_at<uint32_t>(scratch, l.hist);
+  int32_t* hdr = scratch_at<int32_t>(scratch, l.hdr);
+  uint8_t* R = scratch_at<uint8_t>(scratch, l.strips);
+  uint64_t* partials = scratch_at<uint64_t>(scratch, l.partials);
   const int light = p.light_text ? 1 : 0, fixed = p.threshold, K = p.n_steps;
   const int dmax = std::max(max_off(l.nb, W >> 1, K * p.step_q16), max_off(l.nb, W >> 1, -K * p.step_q16));
   const int nchunks = cdiv(H + 2 * dmax, SWEEP_THREADS);                  // <= l.max_chunks: K * step_q16 <= SLOPE_MAX
-  if (fixed < 0) otsu_threshold(s, page, pitch, H, W, hist, hdr);
+  page_threshold(s, page, pitch, H, W, fixed, hist, hdr);
   hipLaunchKernelGGL(strips_kernel, dim3(cdiv(H, STRIP_ROWS)), dim3(256), 0, s, page, pitch, H, W, light, fixed, hdr, l.nb, l.hs, R);
   hipLaunchKernelGGL(sweep_kernel, dim3(nchunks, 2 * K + 1), dim3(SWEEP_THREADS), 0, s, R, H, W, l.nb, l.hs, K, p.step_q16, partials);
   hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(256), 0, s, partials, nchunks, K, p.step_q16, fixed, hdr, skew, scores);
