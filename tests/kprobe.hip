@@ -1,6 +1,7 @@
 // tests/libkprobe.so: extern "C" wrappers around the host launchers of the bf16-source conv / GEMM paths, of the fused recurrent-step
-// kernels, of the attention kernels and of the BatchNorm / un-pool / conv1 / column-sum kernels (csrc/ops.h), for tests/test_kernels_bf16_gpu.py,
-// tests/test_step_kernels_bf16_gpu.py, tests/test_attention_kernels_gpu.py and tests/test_cnn_elementwise_kernels_gpu.py.  Test infrastructure: no kernels of its own, not part of the product's C ABI (include/aocr.h).
+// kernels, of the attention kernels, of the BatchNorm / un-pool / conv1 / column-sum kernels and of the loss, token-sum, optimizer, beam-search and small
+// elementwise kernels (csrc/ops.h), for tests/test_kernels_bf16_gpu.py, tests/test_step_kernels_bf16_gpu.py, tests/test_attention_kernels_gpu.py,
+// tests/test_cnn_elementwise_kernels_gpu.py and tests/test_tail_kernels_gpu.py.  Test infrastructure: no kernels of its own, not part of the product's C ABI (include/aocr.h).
 // Every wrapper enqueues on the given stream and returns hipGetLastError().  Pointers to bf16 data are passed as the raw addresses
 // of torch.bfloat16 tensors (the same bit layout as bf16_t).
 #include "ops.h"
@@ -273,6 +274,174 @@ int kp_big_step_store(hipStream_t s, const KpStore* p, int M, int N, int* taken)
 }
 int kp_big_step_gates_fwd(hipStream_t s, const KpGatesFwd* p, int M, int H, float* zbuf, size_t zbuf_floats, int* taken) {
   *taken = aocr::big_step_gates_fwd(s, kh(p->a), kh(p->b), ep_of(*p, M, H), M, H, zbuf, zbuf_floats) ? 1 : 0;
+  return (int)hipGetLastError();
+}
+
+// ---- loss, sums by token, optimizer, weight shadows, beam search and the small elementwise kernels (csrc/ops_misc.hip; project_loss: csrc/ops_gemm.hip), for
+// tests/test_tail_kernels_gpu.py: the launchers' own argument lists.  Structs passed by pointer mirror the C++ ones field by field (KpTrie = TrieView,
+// KpDecInit = DecInitArgs, KpDrop = DropSpec; a null KpDrop pointer / a null KpTrie pointer = the launcher's default).
+struct KpTrie { const unsigned long long* mask; const int32_t* base; const int32_t* child; const int32_t* loc_in; int32_t* loc_out; };
+struct KpDecInit { float* c0[4]; float* h0[4]; void* hb[4]; float* feed0; void* outb; const float *cfw, *cbw, *hfw, *hbw; int B, He, Hd, Ld, copy_h; };
+
+int kp_logsoftmax_nll(hipStream_t s, const float* logits, int64_t ld, const int32_t* tgt, int64_t st, int64_t sb, int Bt, float* logp, float* dlogits,
+                      float* nll_rows, int64_t rows, int V, float grad_scale) {
+  aocr::logsoftmax_nll(s, logits, ld, tgt, st, sb, Bt, logp, dlogits, nll_rows, rows, V, grad_scale);
+  return (int)hipGetLastError();
+}
+int kp_project_loss_ok(int rows, int V, int Hd) { return aocr::project_loss_ok(rows, V, Hd) ? 1 : 0; }
+int kp_project_loss(hipStream_t s, const float* out, int64_t ldo, const float* wo, const float* bo, float* logits, float* dlogits, int64_t ld, float* nll,
+                    float* dout, const int32_t* tgt, int64_t st, int64_t sb, int Bt, int rows, int V, int Hd, float scale) {
+  aocr::project_loss(s, out, ldo, wo, bo, logits, dlogits, ld, nll, dout, tgt, st, sb, Bt, rows, V, Hd, scale);
+  return (int)hipGetLastError();
+}
+// the generic product project_loss documents itself against (*rc = gemm's own return value)
+int kp_gemm(hipStream_t s, int bf16, const float* A, int64_t lda, int a_kmajor, const float* B, int64_t ldb, int b_kmajor, float* C, int64_t ldc, int M, int N,
+            int K, const float* bias, const float* bias2, int flags, int* rc) {
+  *rc = aocr::gemm(s, bf16 != 0, A, lda, a_kmajor != 0, B, ldb, b_kmajor != 0, C, ldc, M, N, K, bias, bias2, flags);
+  return (int)hipGetLastError();
+}
+int kp_sum_to_scalar(hipStream_t s, const float* x, int64_t n, float* out) {
+  aocr::sum_to_scalar(s, x, n, out);
+  return (int)hipGetLastError();
+}
+int kp_gold_scores(hipStream_t s, const float* nll_rows, float* gold, int L, int B) {
+  aocr::gold_scores(s, nll_rows, gold, L, B);
+  return (int)hipGetLastError();
+}
+
+int kp_segsum_supported(int ncols, int V, int E) { return aocr::segsum_supported(ncols, V, E) ? 1 : 0; }
+size_t kp_segsum_index_ints(int rows, int V) { return aocr::segsum_index_ints(rows, V); }
+int kp_segsum_by_token(hipStream_t s, const float* dz, int64_t ld, const int32_t* tok, int64_t st, int64_t sb, int L, int B, int ncols, int V, float* S,
+                       int* index, float* db1, float* db2, const float* W, int64_t ldw, const float* lookup, int E, float* dlookup, float* dW) {
+  aocr::segsum_by_token(s, dz, ld, tok, st, sb, L, B, ncols, V, S, index, db1, db2, W, ldw, lookup, E, dlookup, dW);
+  return (int)hipGetLastError();
+}
+int kp_embedding_gather(hipStream_t s, const float* table, const int32_t* tok, int64_t st, int64_t sb, float* out, int L, int B, int E) {
+  aocr::embedding_gather(s, table, tok, st, sb, out, L, B, E);
+  return (int)hipGetLastError();
+}
+int kp_embedding_scatter_accum(hipStream_t s, const float* demb, const int32_t* tok, int64_t st, int64_t sb, float* dtable, int L, int B, int E, int V) {
+  aocr::embedding_scatter_accum(s, demb, tok, st, sb, dtable, L, B, E, V);
+  return (int)hipGetLastError();
+}
+
+size_t kp_sgd_scratch_bytes() { return aocr::sgd_scratch_bytes(); }
+int kp_cl_err_latch() { return aocr::CL_ERR_LATCH; }
+int kp_cl_err_sticky() { return aocr::CL_ERR_STICKY; }
+int kp_sgd_clip_update(hipStream_t s, float* params, float* grads, const int64_t* group_off, float lr, float clip, float* norms_out, void* scratch, int* err,
+                       float* bn_state, const float* bn_snap, int bn_n) {
+  aocr::sgd_clip_update(s, params, grads, group_off, lr, clip, norms_out, scratch, err, bn_state, bn_snap, bn_n);
+  return (int)hipGetLastError();
+}
+int kp_adadelta_update(hipStream_t s, float* params, float* grads, float* var, float* acc, int64_t n, float rho, float eps, float wd, int* err, float* bn_state,
+                       const float* bn_snap, int bn_n) {
+  aocr::adadelta_update(s, params, grads, var, acc, n, rho, eps, wd, err, bn_state, bn_snap, bn_n);
+  return (int)hipGetLastError();
+}
+int kp_step_snapshot(hipStream_t s, const float* bn_state, float* bn_snap, int n, int* err) {
+  aocr::step_snapshot(s, bn_state, bn_snap, n, err);
+  return (int)hipGetLastError();
+}
+
+// n pieces (parallel host arrays) -> the ShadowJob table as build_shadow_jobs lays it out (tile0 ascending, tx = tiles per row), copied to jobs_dev (n
+// ShadowJob of device memory, kp_shadow_job_bytes() each) on the stream; then tiles [tile_off, tile_off + ntiles) are launched (ntiles < 0: all from tile_off).
+// *total = the table's tile count.
+size_t kp_shadow_job_bytes() { return sizeof(aocr::ShadowJob); }
+int kp_shadow_jobs(hipStream_t s, int n, const float* const* w, void* const* wb, void* const* wtb, const int64_t* ld, const int64_t* ldb, const int64_t* ldt,
+                   const int* R, const int* C, void* jobs_dev, int tile_off, int ntiles, int* total) {
+  if (n < 1 || n > 16) return (int)hipErrorInvalidValue;
+  aocr::ShadowJob j[16];
+  int tiles = 0;
+  for (int i = 0; i < n; ++i) {
+    j[i] = aocr::ShadowJob{w[i], W16(wb[i]), W16(wtb[i]), ld[i], ldb[i], ldt[i], R[i], C[i], tiles, aocr::cdiv(C[i], 32)};
+    tiles += aocr::cdiv(C[i], 32) * aocr::cdiv(R[i], 32);
+  }
+  *total = tiles;
+  if (tile_off < 0 || tile_off > tiles) return (int)hipErrorInvalidValue;
+  if (ntiles < 0) ntiles = tiles - tile_off;
+  if (tile_off + ntiles > tiles) return (int)hipErrorInvalidValue;
+  if (hipError_t e = hipMemcpyAsync(jobs_dev, j, n * sizeof(aocr::ShadowJob), hipMemcpyHostToDevice, s)) return (int)e;
+  if (hipError_t e = hipStreamSynchronize(s)) return (int)e;      // (the table is on this stack frame)
+  aocr::shadow_jobs(s, static_cast<const aocr::ShadowJob*>(jobs_dev), n, ntiles, tile_off);
+  return (int)hipGetLastError();
+}
+
+static aocr::TrieView trie_of(const KpTrie& t) { aocr::TrieView v; v.mask = t.mask; v.base = t.base; v.child = t.child; v.loc_in = t.loc_in; v.loc_out = t.loc_out; return v; }
+int kp_beam_select(hipStream_t s, const float* logp, const int32_t* prev_tok, float* beam_scores, int32_t* tokens, int32_t* parents, int B, int kin, int kout,
+                   int V, const float* logits, int64_t ldl, const KpTrie* tv, float* sc_out) {
+  aocr::TrieView v; if (tv) v = trie_of(*tv);
+  aocr::beam_select(s, logp, prev_tok, beam_scores, tokens, parents, B, kin, kout, V, logits, ldl, tv ? &v : nullptr, sc_out);
+  return (int)hipGetLastError();
+}
+int kp_project_select(hipStream_t s, const float* h, int64_t ldh, const float* wo, const float* bo, int Hd, const int32_t* prev_tok, float* beam_scores,
+                      int32_t* tokens, int32_t* parents, int B, int kin, int kout, int V, const KpTrie* tv, float* sc_out) {
+  aocr::TrieView v; if (tv) v = trie_of(*tv);
+  aocr::project_select(s, h, ldh, wo, bo, Hd, prev_tok, beam_scores, tokens, parents, B, kin, kout, V, tv ? &v : nullptr, sc_out);
+  return (int)hipGetLastError();
+}
+// n tensors (parallel host arrays of device pointers; dstb null or with null entries: no bf16 copy)
+int kp_gather_beam_rows_many(hipStream_t s, int n, const float* const* src, float* const* dst, int64_t ld, const int32_t* parents, int B, int kin, int kout,
+                             int width, void* const* dstb) {
+  if (n < 0 || n > 16) return (int)hipErrorInvalidValue;
+  aocr::bf16_t* db[16];
+  for (int i = 0; i < n; ++i) db[i] = dstb ? W16(dstb[i]) : nullptr;
+  aocr::gather_beam_rows_many(s, n, src, dst, ld, parents, B, kin, kout, width, dstb ? db : nullptr);
+  return (int)hipGetLastError();
+}
+int kp_gather_beam_rows(hipStream_t s, const float* src, int64_t lds, float* dst, int64_t ldd, const int32_t* parents, int B, int kin, int kout, int width) {
+  aocr::gather_beam_rows(s, src, lds, dst, ldd, parents, B, kin, kout, width);
+  return (int)hipGetLastError();
+}
+int kp_token_rows(hipStream_t s, const float* table, const int32_t* tok, int64_t stride, float* dst, int R, int width) {
+  aocr::token_rows(s, table, tok, stride, dst, R, width);
+  return (int)hipGetLastError();
+}
+int kp_beam_backtrace(hipStream_t s, const int32_t* hist_tok, const int32_t* hist_par, const float* beam_scores, int32_t* labels, float* scores, int Lt, int B,
+                      int k) {
+  aocr::beam_backtrace(s, hist_tok, hist_par, beam_scores, labels, scores, Lt, B, k);
+  return (int)hipGetLastError();
+}
+int kp_recognize_gather(hipStream_t s, const int32_t* labels, const int32_t* hist_par, const float* beam_scores, const float* sc_hist, const float* attn_hist,
+                        float* char_logp, float* attn, int Lt, int B, int k, int T) {
+  aocr::recognize_gather(s, labels, hist_par, beam_scores, sc_hist, attn_hist, char_logp, attn, Lt, B, k, T);
+  return (int)hipGetLastError();
+}
+
+int kp_dec_init(hipStream_t s, const KpDecInit* p) {
+  aocr::DecInitArgs a;
+  for (int l = 0; l < 4; ++l) { a.c0[l] = p->c0[l]; a.h0[l] = p->h0[l]; a.hb[l] = W16(p->hb[l]); }
+  a.feed0 = p->feed0; a.outb = W16(p->outb); a.cfw = p->cfw; a.cbw = p->cbw; a.hfw = p->hfw; a.hbw = p->hbw;
+  a.B = p->B; a.He = p->He; a.Hd = p->Hd; a.Ld = p->Ld; a.copy_h = p->copy_h;
+  aocr::dec_init(s, a);
+  return (int)hipGetLastError();
+}
+int kp_dpre_tanh(hipStream_t s, const float* g1, const float* g2, const float* out, float* dpre, int64_t n, void* dpreb, const KpDrop* drop) {
+  aocr::DropSpec d; if (drop) d = drop_of(*drop);
+  aocr::dpre_tanh(s, g1, g2, out, dpre, n, W16(dpreb), drop ? &d : nullptr);
+  return (int)hipGetLastError();
+}
+int kp_dropout_apply(hipStream_t s, const float* src, float* dst, void* dstb, int64_t n, const KpDrop* drop) {
+  aocr::dropout_apply(s, src, dst, W16(dstb), n, drop_of(*drop));
+  return (int)hipGetLastError();
+}
+int kp_dropout_apply_b(hipStream_t s, const void* src, float* dst, void* dstb, int64_t n, const KpDrop* drop) {
+  aocr::dropout_apply_b(s, H16(src), dst, W16(dstb), n, drop_of(*drop));
+  return (int)hipGetLastError();
+}
+// n regions (parallel host arrays) through ZeroList::add (which drops empty regions), one launch
+int kp_zero_many(hipStream_t s, int n, void* const* p, const size_t* bytes) {
+  if (n < 0 || n > 16) return (int)hipErrorInvalidValue;
+  aocr::ZeroList z;
+  for (int i = 0; i < n; ++i) z.add(p[i], bytes[i]);
+  aocr::zero_many(s, z);
+  return (int)hipGetLastError();
+}
+int kp_copy2d_bf16(hipStream_t s, const float* src, int64_t lds, void* dst, int64_t ldd, int rows, int cols) {
+  aocr::copy2d_bf16(s, src, lds, W16(dst), ldd, rows, cols);
+  return (int)hipGetLastError();
+}
+int kp_edit_distance(hipStream_t s, const int32_t* labels, const int32_t* targets, int B, int L, int32_t* dist, int32_t* target_len) {
+  aocr::edit_distance(s, labels, targets, B, L, dist, target_len);
   return (int)hipGetLastError();
 }
 

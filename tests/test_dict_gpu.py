@@ -93,7 +93,7 @@ def test_beam_select_dict_rejects_bad_arguments(cuda):
     assert b"64" in lib.aocr_last_error()
 
 
-@pytest.mark.parametrize("B,L", [(1, 1), (70, 10), (256, 50), (3, 200)])
+@pytest.mark.parametrize("B,L", [(1, 1), (70, 10), (256, 50), (3, 200), (3, 300)])      # L = 300: above the default dynamic-LDS limit
 def test_edit_distance_kernel(cuda, B, L):
     import dict_oracle as DO
     from aocr.dictionary import edit_distance_device

@@ -42,7 +42,11 @@ def test_kprobe_symbols_resolve_in_libaocr(tmp_path):
                  "launch_small_gates_bwd_h", "gates_elem_bwd", "big_step_store", "big_step_gates_fwd",
                  "attention_forward", "attention_backward", "attention_forward_dual", "attention_backward_dual", "attention_dual_ok",
                  "attention_dctx", "bn_relu_backward", "unpool_relu_backward", "conv1_forward", "conv1_route_elems", "conv1_backward",
-                 "colsum_accum", "colsum_defer", "colsum_flush"):
+                 "colsum_accum", "colsum_defer", "colsum_flush",
+                 "logsoftmax_nll", "project_loss", "project_loss_ok", "segsum_by_token", "segsum_supported", "segsum_index_ints", "embedding_gather",
+                 "embedding_scatter_accum", "sgd_clip_update", "sgd_scratch_bytes", "adadelta_update", "step_snapshot", "shadow_jobs", "beam_select",
+                 "project_select", "gather_beam_rows_many", "gather_beam_rows", "token_rows", "beam_backtrace", "recognize_gather", "dec_init",
+                 "dpre_tanh", "dropout_apply", "dropout_apply_b", "zero_many", "copy2d_bf16", "sum_to_scalar", "gold_scores", "edit_distance"):
         assert any(f"{len(name)}{name}E" in s for s in wanted), f"the shim does not call aocr::{name}"
     defined = _symbols(LIB, "--defined-only")
     missing = sorted(wanted - defined)
@@ -53,5 +57,10 @@ def test_kprobe_symbols_resolve_in_libaocr(tmp_path):
                  "kp_gates_elem_bwd", "kp_big_step_store", "kp_big_step_gates_fwd",
                  "kp_attention_forward", "kp_attention_backward", "kp_attention_forward_dual", "kp_attention_backward_dual",
                  "kp_attention_dual_ok", "kp_attention_dctx", "kp_bn_relu_forward2", "kp_bn_relu_backward", "kp_unpool_relu_backward",
-                 "kp_conv1_forward", "kp_conv1_route_elems", "kp_conv1_backward", "kp_colsum_accum", "kp_colsum_jobs"):
+                 "kp_conv1_forward", "kp_conv1_route_elems", "kp_conv1_backward", "kp_colsum_accum", "kp_colsum_jobs",
+                 "kp_logsoftmax_nll", "kp_project_loss", "kp_project_loss_ok", "kp_gemm", "kp_segsum_by_token", "kp_segsum_supported",
+                 "kp_segsum_index_ints", "kp_embedding_gather", "kp_embedding_scatter_accum", "kp_sgd_clip_update", "kp_sgd_scratch_bytes",
+                 "kp_adadelta_update", "kp_step_snapshot", "kp_shadow_jobs", "kp_beam_select", "kp_project_select", "kp_gather_beam_rows_many",
+                 "kp_gather_beam_rows", "kp_token_rows", "kp_beam_backtrace", "kp_recognize_gather", "kp_dec_init", "kp_dpre_tanh",
+                 "kp_dropout_apply", "kp_dropout_apply_b", "kp_zero_many", "kp_copy2d_bf16", "kp_sum_to_scalar", "kp_gold_scores"):
         assert name in exported
