@@ -1,7 +1,7 @@
 // tests/libkprobe.so: extern "C" wrappers around the host launchers of the bf16-source conv / GEMM paths, of the fused recurrent-step
 // kernels, of the attention kernels, of the BatchNorm / un-pool / conv1 / column-sum kernels and of the loss, token-sum, optimizer, beam-search and small
-// elementwise kernels (csrc/ops.h), for tests/test_kernels_bf16_gpu.py, tests/test_step_kernels_bf16_gpu.py, tests/test_attention_kernels_gpu.py,
-// tests/test_cnn_elementwise_kernels_gpu.py and tests/test_tail_kernels_gpu.py.  Test infrastructure: no kernels of its own, not part of the product's C ABI (include/aocr.h).
+// elementwise kernels, and of the whole-sequence encoder recurrences (csrc/ops.h), for tests/test_kernels_bf16_gpu.py, tests/test_step_kernels_bf16_gpu.py,
+// tests/test_attention_kernels_gpu.py, tests/test_cnn_elementwise_kernels_gpu.py, tests/test_tail_kernels_gpu.py and tests/test_encoder_seq_kernels_gpu.py.  Test infrastructure: no kernels of its own, not part of the product's C ABI (include/aocr.h).
 // Every wrapper enqueues on the given stream and returns hipGetLastError().  Pointers to bf16 data are passed as the raw addresses
 // of torch.bfloat16 tensors (the same bit layout as bf16_t).
 #include "ops.h"
@@ -442,6 +442,105 @@ int kp_copy2d_bf16(hipStream_t s, const float* src, int64_t lds, void* dst, int6
 }
 int kp_edit_distance(hipStream_t s, const int32_t* labels, const int32_t* targets, int B, int L, int32_t* dist, int32_t* target_len) {
   aocr::edit_distance(s, labels, targets, B, L, dist, target_len);
+  return (int)hipGetLastError();
+}
+
+// ---- the whole-sequence encoder recurrences (csrc/rnn_seq.hip, csrc/rnn_cluster.hip), for tests/test_encoder_seq_kernels_gpu.py.  One flat struct per problem
+// (mirrored there as ctypes.Structure): KpEncDir = EncSeqDir, KpEncBwdDir = EncSeqBwdDir field by field, then what the host sets of the launch arguments.
+// A wrapper REFUSES -- returns one of the KP_ENC_* codes below (above every hipError_t) and launches nothing -- whatever the model would not launch either:
+// the cluster kernels wait for each other, so every workgroup of a launch must be resident at once, which is what enc_cluster_plan decides.
+struct KpEncDir { const void* w; const float* zx; float* hs; float* cs; void* hsb; float* gates; float* ctx; int reverse; };
+struct KpEncBwdDir {
+  const void* wt; const float* dh1; int64_t dh1_row, dh1_t; const float* dh2; int64_t dh2_row; float* dc; const float* dc_in; int64_t dc_in_row;
+  const float* gates; const float* cs; float* dz; void* dzb; float* dbi; float* dbh; int forward_dir;
+};
+struct KpEncSeqFwd { KpEncDir d[2]; int B, T, He, Hd; };
+struct KpEncSeqBwd { KpEncBwdDir d[2]; int B, T, He; };
+// buf = xbuf (forward) / pbuf (backward); *_bytes / err_ints: what the caller allocated; layers: the sets of group slots the buffers were sized for (model.hip: Le)
+struct KpEncCl {
+  int B, T, He, Hd, groups; unsigned epoch; int it0, it1, gslot;
+  unsigned long long* buf; size_t buf_bytes; unsigned long long* xtab; size_t xtab_bytes; int* err; size_t err_ints; int layers;
+  int G, RT, reserve_cus, concurrent;
+};
+struct KpEncClFwd { KpEncDir d[2]; KpEncCl c; };
+struct KpEncClBwd { KpEncBwdDir d[2]; KpEncCl c; };
+enum { KP_ENC_UNSUPPORTED = 2001, KP_ENC_PLAN_MISMATCH = 2002, KP_ENC_BUF_SMALL = 2003, KP_ENC_XTAB_SMALL = 2004, KP_ENC_ERR_SMALL = 2005, KP_ENC_BAD_ARGS = 2006 };
+
+}  // extern "C"
+
+namespace {
+int kp_cus() { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }
+aocr::EncSeqDir enc_dir(const KpEncDir& d) {
+  aocr::EncSeqDir e; e.w = H16(d.w); e.zx = d.zx; e.hs = d.hs; e.cs = d.cs; e.hsb = W16(d.hsb); e.gates = d.gates; e.ctx = d.ctx; e.reverse = d.reverse;
+  return e;
+}
+aocr::EncSeqBwdDir enc_bwd_dir(const KpEncBwdDir& d) {
+  aocr::EncSeqBwdDir e; e.wt = H16(d.wt); e.dh1 = d.dh1; e.dh1_row = d.dh1_row; e.dh1_t = d.dh1_t; e.dh2 = d.dh2; e.dh2_row = d.dh2_row; e.dc = d.dc;
+  e.dc_in = d.dc_in; e.dc_in_row = d.dc_in_row; e.gates = d.gates; e.cs = d.cs; e.dz = d.dz; e.dzb = W16(d.dzb); e.dbi = d.dbi; e.dbh = d.dbh;
+  e.forward_dir = d.forward_dir;
+  return e;
+}
+// What model.hip checks and allocates before it launches a cluster kernel, as refusals.  The sizes:
+//   xbuf / pbuf  layers * enc_cluster_xbuf_bytes / enc_cluster_pbuf_bytes (model.hip: cl_xbytes, cl_pbytes: one set of group slots per layer)
+//   xtab         (layers * 4 * ceil(B / 16) * 8 + 64) * 8 bytes (model.hip: cl_tbytes -- a layer's 8-row launches start at slot l * 4 * ceil(B / 16))
+//   err          16 + 256 * 8 + 4096 ints (model.hip: cl_err): the error record, then the TRASH SLOTS the kernels' lanes of rows >= B store to
+//                (p.err + 16, 256 lanes x 4 floats; the model leaves room for 8), then the debugging timeline of the stamps builds
+// gslot is a layer's first slot, l * 2 * groups with l < layers (model.hip: encoder_forward_pipe).
+int enc_cl_check(const KpEncCl& c, size_t layer_bytes) {
+  if (c.reserve_cus < 0 || c.concurrent < 1 || c.layers < 1 || c.it0 < 0 || c.it1 < 0 || c.it1 > c.T || (c.it1 > 0 && c.it0 >= c.it1) || c.it0 >= c.T || c.epoch == 0 ||
+      c.epoch >= (1u << 20))
+    return KP_ENC_BAD_ARGS;
+  int G = 0, RT = 0, groups = 0;
+  if (!aocr::enc_cluster_plan(c.B, c.He, c.T, kp_cus() - c.reserve_cus, G, RT, groups)) return KP_ENC_UNSUPPORTED;
+  if (G != c.G || RT != c.RT || groups != c.groups) return KP_ENC_PLAN_MISMATCH;
+  if (c.gslot < 0 || c.gslot % (2 * groups) != 0 || c.gslot / (2 * groups) >= c.layers) return KP_ENC_BAD_ARGS;
+  if (!c.buf || c.buf_bytes < (size_t)c.layers * layer_bytes) return KP_ENC_BUF_SMALL;
+  if (!c.xtab || c.xtab_bytes < ((size_t)c.layers * 4 * ((c.B + 15) / 16) * 8 + 64) * 8) return KP_ENC_XTAB_SMALL;
+  if (!c.err || c.err_ints < 16 + 256 * 8 + 4096) return KP_ENC_ERR_SMALL;
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int kp_enc_seq_supported(int B, int He) { return aocr::enc_seq_supported(B, He, kp_cus()) ? 1 : 0; }       // (blocks_limit = the compute units, as model.hip passes it)
+int kp_enc_seq_forward(hipStream_t s, const KpEncSeqFwd* p) {
+  if (p->T < 1 || !aocr::enc_seq_supported(p->B, p->He, kp_cus())) return KP_ENC_UNSUPPORTED;
+  aocr::EncSeqFwdArgs a; a.B = p->B; a.T = p->T; a.He = p->He; a.Hd = p->Hd;
+  for (int dir = 0; dir < 2; ++dir) a.d[dir] = enc_dir(p->d[dir]);
+  aocr::enc_seq_forward(s, a);
+  return (int)hipGetLastError();
+}
+int kp_enc_seq_backward(hipStream_t s, const KpEncSeqBwd* p) {
+  if (p->T < 1 || !aocr::enc_seq_supported(p->B, p->He, kp_cus())) return KP_ENC_UNSUPPORTED;
+  aocr::EncSeqBwdArgs a; a.B = p->B; a.T = p->T; a.He = p->He;
+  for (int dir = 0; dir < 2; ++dir) a.d[dir] = enc_bwd_dir(p->d[dir]);
+  aocr::enc_seq_backward(s, a);
+  return (int)hipGetLastError();
+}
+
+// -> 1 and *G, *RT, *groups when the cluster kernels take the shape on this device with reserve_cus compute units left out (0: they do not)
+int kp_enc_cluster_plan(int B, int He, int T, int reserve_cus, int* G, int* RT, int* groups) {
+  return reserve_cus >= 0 && aocr::enc_cluster_plan(B, He, T, kp_cus() - reserve_cus, *G, *RT, *groups) ? 1 : 0;
+}
+size_t kp_enc_cluster_xbuf_bytes(int B, int He) { return aocr::enc_cluster_xbuf_bytes(B, He); }
+size_t kp_enc_cluster_pbuf_bytes(int B, int He) { return aocr::enc_cluster_pbuf_bytes(B, He); }
+int kp_enc_cluster_forward(hipStream_t s, const KpEncClFwd* p) {
+  const KpEncCl& c = p->c;
+  if (int rc = enc_cl_check(c, aocr::enc_cluster_xbuf_bytes(c.B, c.He))) return rc;
+  aocr::EncClFwdArgs a; a.B = c.B; a.T = c.T; a.He = c.He; a.Hd = c.Hd; a.groups = c.groups; a.epoch = c.epoch; a.xbuf = c.buf; a.err = c.err; a.xtab = c.xtab;
+  a.it0 = c.it0; a.it1 = c.it1; a.gslot = c.gslot;
+  for (int dir = 0; dir < 2; ++dir) a.d[dir] = enc_dir(p->d[dir]);
+  aocr::enc_cluster_forward(s, a, c.G, c.RT, c.reserve_cus, c.concurrent);
+  return (int)hipGetLastError();
+}
+int kp_enc_cluster_backward(hipStream_t s, const KpEncClBwd* p) {
+  const KpEncCl& c = p->c;
+  if (int rc = enc_cl_check(c, aocr::enc_cluster_pbuf_bytes(c.B, c.He))) return rc;
+  aocr::EncClBwdArgs a; a.B = c.B; a.T = c.T; a.He = c.He; a.groups = c.groups; a.epoch = c.epoch; a.pbuf = c.buf; a.err = c.err; a.xtab = c.xtab;
+  a.it0 = c.it0; a.it1 = c.it1; a.gslot = c.gslot;
+  for (int dir = 0; dir < 2; ++dir) a.d[dir] = enc_bwd_dir(p->d[dir]);
+  aocr::enc_cluster_backward(s, a, c.G, c.RT, c.reserve_cus, c.concurrent);
   return (int)hipGetLastError();
 }
 

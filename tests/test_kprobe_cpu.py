@@ -46,7 +46,9 @@ def test_kprobe_symbols_resolve_in_libaocr(tmp_path):
                  "logsoftmax_nll", "project_loss", "project_loss_ok", "segsum_by_token", "segsum_supported", "segsum_index_ints", "embedding_gather",
                  "embedding_scatter_accum", "sgd_clip_update", "sgd_scratch_bytes", "adadelta_update", "step_snapshot", "shadow_jobs", "beam_select",
                  "project_select", "gather_beam_rows_many", "gather_beam_rows", "token_rows", "beam_backtrace", "recognize_gather", "dec_init",
-                 "dpre_tanh", "dropout_apply", "dropout_apply_b", "zero_many", "copy2d_bf16", "sum_to_scalar", "gold_scores", "edit_distance"):
+                 "dpre_tanh", "dropout_apply", "dropout_apply_b", "zero_many", "copy2d_bf16", "sum_to_scalar", "gold_scores", "edit_distance",
+                 "enc_seq_supported", "enc_seq_forward", "enc_seq_backward", "enc_cluster_plan", "enc_cluster_xbuf_bytes", "enc_cluster_pbuf_bytes",
+                 "enc_cluster_forward", "enc_cluster_backward"):
         assert any(f"{len(name)}{name}E" in s for s in wanted), f"the shim does not call aocr::{name}"
     defined = _symbols(LIB, "--defined-only")
     missing = sorted(wanted - defined)
@@ -62,5 +64,7 @@ def test_kprobe_symbols_resolve_in_libaocr(tmp_path):
                  "kp_segsum_index_ints", "kp_embedding_gather", "kp_embedding_scatter_accum", "kp_sgd_clip_update", "kp_sgd_scratch_bytes",
                  "kp_adadelta_update", "kp_step_snapshot", "kp_shadow_jobs", "kp_beam_select", "kp_project_select", "kp_gather_beam_rows_many",
                  "kp_gather_beam_rows", "kp_token_rows", "kp_beam_backtrace", "kp_recognize_gather", "kp_dec_init", "kp_dpre_tanh",
-                 "kp_dropout_apply", "kp_dropout_apply_b", "kp_zero_many", "kp_copy2d_bf16", "kp_sum_to_scalar", "kp_gold_scores"):
+                 "kp_dropout_apply", "kp_dropout_apply_b", "kp_zero_many", "kp_copy2d_bf16", "kp_sum_to_scalar", "kp_gold_scores",
+                 "kp_enc_seq_supported", "kp_enc_seq_forward", "kp_enc_seq_backward", "kp_enc_cluster_plan", "kp_enc_cluster_xbuf_bytes",
+                 "kp_enc_cluster_pbuf_bytes", "kp_enc_cluster_forward", "kp_enc_cluster_backward"):
         assert name in exported

@@ -575,12 +575,15 @@ def test_beam_decode_chain_kernel_matches_launch_chain(cuda, monkeypatch, B, W, 
 
 
 @pytest.mark.parametrize("B,W,He", [(48, 100, 256), (21, 72, 256), (24, 160, 512)])
-def test_encoder_half_tiles_match_full_tiles(cuda, monkeypatch, B, W, He):
+def test_encoder_half_tiles_match_full_tiles(cuda, monkeypatch, capfd, B, W, He):
     """Round 5: the encoder cluster kernels give a group 8 batch rows instead of 16 when twice the groups fit the chip (half the output bytes per compute unit;
     columns 8..15 of every MFMA tile repeat column 7 and are neither stored nor published).  Same arithmetic per row: against 16-row groups (AOCR_ENC_RH16=1,
     AOCR_ENC_BWD_RH=16) the encoder output, the logits and the loss must be BIT-identical, the gradients equal up to the order in which the bias sums and the
-    split-K partial sums meet; ragged last groups (B = 21) and He = 512 (8 members per group) included."""
+    split-K partial sums meet; ragged last groups (B = 21) and He = 512 (8 members per group) included.
+    The configuration each run reached is asserted from the launchers' AOCR_TRACE lines (rh=8 / rh=16 in the forward AND the backward call): the two switches
+    were once cached in function-local statics, both runs took the same kernels and the comparison held trivially."""
     cfg = dict(enc_hidden=He, enc_layers=1, dec_layers=2, input_feed=True)
+    monkeypatch.setenv("AOCR_TRACE", "1")
     out = {}
     for knob in ("half", "full"):
         monkeypatch.delenv("AOCR_ENC_RH16", raising=False); monkeypatch.delenv("AOCR_ENC_BWD_RH", raising=False)
@@ -589,8 +592,15 @@ def test_encoder_half_tiles_match_full_tiles(cuda, monkeypatch, B, W, He):
         else:
             monkeypatch.setenv("AOCR_ENC_BWD_RH", "8")
         m, O, ocfg, P, st, batch = make(cfg, B=B, W=W, maxlen=7, compute="bf16", max_decoder_l=8, max_beam=1)
+        capfd.readouterr()
         loss = m.train_forward_backward(batch)
         assert m.cluster_status() == 0
+        err = capfd.readouterr().err
+        for fn in ("enc_cluster_forward", "enc_cluster_backward"):
+            lines = [ln for ln in err.splitlines() if ln.startswith(f"[aocr] {fn}: ")]
+            assert lines, f"{knob}: no {fn} trace line (AOCR_TRACE)"
+            want = " rh=8 " if knob == "half" else " rh=16 "
+            assert all(want in ln for ln in lines), (knob, fn, lines)
         out[knob] = dict(loss=loss, ctx=m.get_tensor("context").clone(), logits=m.get_tensor("logits")[:, :, :ocfg.vocab].clone(),
                          grads={k: v.clone() for k, v in m.get_gradients().items()})
         m.shutdown()
