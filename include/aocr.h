@@ -886,6 +886,62 @@ int aocr_estimate_glyph_size(void* stream, const uint8_t* page_dev, int64_t pitc
 int aocr_resize_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
                      uint8_t* out_dev, int64_t out_pitch, int32_t Ho, int32_t Wo);
 
+/* ---- page dewarp: the curl of the text lines, and the column shifts that remove it, after aocr_deskew_page and in front of aocr_segment_page --
+ * On a book page bending into the gutter, or a sheet lifting at one edge, the text lines are curves.  aocr_deskew_page removes the best
+ * single slope; what is left smears the whole-width row profiles of aocr_segment_page as skew did.  aocr_estimate_curl finds, for groups of
+ * columns, how many rows the text of a group sits below that of the middle group; aocr_dewarp_page shifts every column back.  Both are
+ * integer arithmetic, specified exactly.  The page follows the rules of aocr_segment_page: any base address, any pitch >= W,
+ * 1 <= H, W <= 16384, H*W <= 2^26.
+ *
+ * aocr_estimate_curl (device):
+ *   ink        the threshold is params.threshold when >= 0, else Otsu's: steps 1-2 of aocr_segment_page, bit for bit;
+ *              ink = (v <= threshold), or (v > threshold) with light_text; an Otsu threshold of -1 (one gray value): nothing is ink;
+ *   strips     R[b][y], b = x >> 5, nb = ceil(W / 32): exactly as in aocr_estimate_skew;
+ *   groups     g = params.group strips each: ng = ceil(nb / g);  G[j][y] = sum of R[b][y] over b in [j*g, min((j+1)*g, nb)), at most 512;
+ *              I_j = sum over y of G[j][y];
+ *   scores     D = params.max_shift; for every pair j in [0, ng-1) and every d in [-D, D]:  C_j(d) = sum over y of G[j][y] * G[j+1][y+d];
+ *              a term whose row y+d is outside [0, H) is 0; the sums are exact unsigned 64-bit integers.  D >= H is legal: those scores are 0;
+ *   pair       delta_j = 0 when I_j < min_ink or I_{j+1} < min_ink; otherwise candidates in the order 0, -1, +1, -2, +2, ...: the first
+ *              with the strictly largest score.  All scores 0 gives 0;
+ *   chain      jc = ng >> 1, s[jc] = 0;  s[j+1] = s[j] + delta_j upward, s[j] = s[j+1] - delta_j downward: what is on row y of group jc
+ *              is on row y + s[j] of group j;
+ *   outputs    shifts_dev[j] = s[j] for j < ng;  curl_dev = [ng, max over j of |s[j]|, the threshold used, the number of pairs with
+ *              delta_j != 0];  scores_dev[j*(2D+1) + d + D] = C_j(d) for every pair, gated ones included, when not NULL.
+ * ng == 1 gives s = [0] and no scores; a page without ink, or an Otsu threshold of -1, gives all zeros.
+ * Limits: D must stay below half the line pitch, or a pair locks onto the neighbouring line; the errors of the pairs add up along the
+ * chain; a group in an empty margin (gated) continues its neighbour's shift flat.
+ * scratch_dev: aocr_curl_scratch_bytes(H, W, group, max_shift) bytes, 16-byte aligned, overwritten by the call (0 and an error for bad
+ * sizes).  curl_dev, shifts_dev (4-byte aligned) and scores_dev (8-byte aligned) must not overlap the page or the scratch.
+ *
+ * aocr_dewarp_page (device): every column resampled along y by its shift, linearly interpolated between the group centres.
+ *   w = 32*group, h = 16*group, ng = ceil(ceil(W / 32) / group), c_j = j*w + h (also for a narrow last group);  s[j] = shifts_dev[j], read
+ *   on the device (shifts_dev = the output of aocr_estimate_curl: no host read in between) and clamped to [-16384, 16384];
+ *   shift      in Q8:  q(x) = 256*s[0] for x <= c_0;  q(x) = 256*s[ng-1] for x >= c_{ng-1};  otherwise j = (x - h) / w, t = x - c_j and
+ *              q(x) = 256*s[j] + floor(((s[j+1] - s[j]) * t * 256 + h) / w): a floor division of a signed value, the product in 64 bits;
+ *   pixel      p = 256*y + q(x), sy = p >> 8 (arithmetic shift), f = p & 255;  a = page[sy][x], b = page[sy+1][x], either one `fill`
+ *              (0..255) when its row is outside [0, H);  out[y][x] = (a*(256 - f) + b*f + 128) >> 8.
+ * All-zero shifts copy the page bit for bit; no read leaves the page.  Vertical displacement only: the foreshortening of the columns
+ * toward a gutter stays.  out_dev follows the rules of aocr_deskew_page: H rows of W bytes, out_pitch >= W apart, any alignment; bytes
+ * between W and out_pitch are untouched; it must not overlap the page (or shifts_dev).  No scratch.
+ * All three calls enqueue only, never synchronise or allocate; the results do not depend on launch geometry, atomics order or run (integer
+ * sums only).  Invalid params, sizes, non-zero reserved words, NULLs or overlap return an error before anything is enqueued and leave the
+ * outputs untouched. */
+typedef struct aocr_curl_params {
+  int32_t threshold;     /* 0..254: ink = (v <= threshold); -1: Otsu, steps 1-2 of aocr_segment_page, bit for bit */
+  int32_t light_text;    /* 1: ink = (v > threshold) instead */
+  int32_t group;         /* g in 1..16: column groups of 32*g columns */
+  int32_t max_shift;     /* D in 0..64: candidate row shifts -D..D between neighbouring groups */
+  int32_t min_ink;       /* 0..2^20: a pair with a group holding fewer ink pixels than this gets shift 0 */
+  int32_t reserved[3];   /* must be 0 */
+} aocr_curl_params;
+
+size_t aocr_curl_scratch_bytes(int32_t H, int32_t W, int32_t group, int32_t max_shift);
+int aocr_estimate_curl(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                       const aocr_curl_params* params, void* scratch_dev, int32_t curl_dev[4],
+                       int32_t* shifts_dev, uint64_t* scores_dev);
+int aocr_dewarp_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t group,
+                     const int32_t* shifts_dev, int32_t fill, uint8_t* out_dev, int64_t out_pitch);
+
 #ifdef __cplusplus
 }
 #endif

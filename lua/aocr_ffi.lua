@@ -125,6 +125,10 @@ typedef struct aocr_glyph_params { int32_t threshold; int32_t light_text; int32_
 size_t aocr_glyph_scratch_bytes(int32_t H, int32_t W);
 int aocr_estimate_glyph_size(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_glyph_params* params, void* scratch_dev, int32_t glyph_dev[8]);
 int aocr_resize_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, uint8_t* out_dev, int64_t out_pitch, int32_t Ho, int32_t Wo);
+typedef struct aocr_curl_params { int32_t threshold; int32_t light_text; int32_t group; int32_t max_shift; int32_t min_ink; int32_t reserved[3]; } aocr_curl_params;
+size_t aocr_curl_scratch_bytes(int32_t H, int32_t W, int32_t group, int32_t max_shift);
+int aocr_estimate_curl(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_curl_params* params, void* scratch_dev, int32_t curl_dev[4], int32_t* shifts_dev, uint64_t* scores_dev);
+int aocr_dewarp_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t group, const int32_t* shifts_dev, int32_t fill, uint8_t* out_dev, int64_t out_pitch);
 ]]
 
 local M = {}

@@ -117,6 +117,16 @@ class GlyphParams(C.Structure):
         super().__init__(int(threshold), int(light_text), int(connectivity), int(min_size), int(max_size), int(max_aspect), (C.c_int32 * 2)(0, 0))
 
 
+class CurlParams(C.Structure):
+    """mirror of `aocr_curl_params` (include/aocr.h): how `aocr_estimate_curl` measures page curl.  Columns are taken in groups of 32 * group;
+    neighbouring groups are tried at row shifts -max_shift..max_shift (keep it below half the line pitch); a pair with a group of fewer than
+    min_ink ink pixels gets shift 0.  threshold -1: Otsu."""
+    _fields_ = [(n, C.c_int32) for n in ("threshold", "light_text", "group", "max_shift", "min_ink")] + [("reserved", C.c_int32 * 3)]
+
+    def __init__(self, threshold=-1, light_text=0, group=4, max_shift=8, min_ink=64):
+        super().__init__(int(threshold), int(light_text), int(group), int(max_shift), int(min_ink), (C.c_int32 * 3)(0, 0, 0))
+
+
 class ScaleParams:
     """how `Model.recognize_page(scale=...)` brings the text of a page to the size the other stages' defaults were written for
     (`aocr_estimate_glyph_size`, `aocr.scale_plan`, `aocr_resize_page`; plain Python: there is no C struct behind it).  glyph: the
@@ -236,6 +246,9 @@ SIGNATURES = {
     "aocr_glyph_scratch_bytes": (C.c_size_t, [_i32, _i32]),
     "aocr_estimate_glyph_size": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp]),
     "aocr_resize_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, C.c_int64, _i32, _i32]),
+    "aocr_curl_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32]),
+    "aocr_estimate_curl": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "aocr_dewarp_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _i32, _vp, _i32, _vp, C.c_int64]),
     "aocr_beam_select": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32]),
 }
 

@@ -439,10 +439,11 @@ class Model:
             res.word = [lexicon.words[i] if i >= 0 else None for i in res.word_index.tolist()]
         return res
 
-    def _page_boxes(self, page, params, max_boxes, deskew, layout, clean_dev, stream):
+    def _page_boxes(self, page, params, max_boxes, deskew, layout, clean_dev, stream, dewarp=None):
         """the middle of recognize_page, from the deskew to the boxes on the host: everything that reads the page in its final orientation and
         has to be redone when recognize_page(orient=True) turns the page by another half turn.  Returns its locals as a namespace."""
-        from .page import deskew_page_device, estimate_skew_device, layout_page_device, segment_page_device
+        from .page import (deskew_page_device, dewarp_page_device, estimate_curl_device, estimate_skew_device, layout_page_device,
+                           segment_page_device)
         skew = cleaned = blocks = block_id = nb = lcounts = None
         skew_dev = None
         if deskew is not None and deskew is not False:
@@ -450,6 +451,13 @@ class Model:
             sp = deskew if isinstance(deskew, _lib.SkewParams) else _lib.SkewParams(threshold=seg.threshold, light_text=seg.light_text)
             skew_dev = estimate_skew_device(page, sp, stream)
             page = deskew_page_device(page, skew_dev, 0 if seg.light_text else 255, stream)
+        curl = curl_dev = curl_group = None                       # curl_dev: [the four curl words, the ng group shifts], read back together
+        if dewarp is not None and dewarp is not False:
+            seg = params if params is not None else _lib.SegmentParams()
+            cp = dewarp if isinstance(dewarp, _lib.CurlParams) else _lib.CurlParams(threshold=seg.threshold, light_text=seg.light_text)
+            words_dev, shifts_dev = estimate_curl_device(page, cp, stream)
+            page = dewarp_page_device(page, shifts_dev, cp.group, 0 if seg.light_text else 255, stream)
+            curl_dev, curl_group, n_curl = [words_dev, shifts_dev], int(cp.group), 4 + shifts_dev.numel()
         lay = None
         if layout is not None and layout is not False:
             seg = params if params is not None else _lib.SegmentParams()
@@ -457,12 +465,16 @@ class Model:
             max_blocks = 256
             blocks_dev, lcounts_dev, info_dev = layout_page_device(page, lay, seg.threshold, seg.light_text, max_blocks, stream)
             head = torch.cat([lcounts_dev, info_dev, skew_dev if skew_dev is not None else lcounts_dev[:0],
-                              clean_dev if clean_dev is not None else lcounts_dev[:0], blocks_dev.reshape(-1)]).cpu().numpy()
+                              clean_dev if clean_dev is not None else lcounts_dev[:0]] + (curl_dev if curl_dev is not None else [])
+                             + [blocks_dev.reshape(-1)]).cpu().numpy()
             lcounts, info = head[:4], head[4:8]                   # the first sync
             if skew_dev is not None:
                 skew = head[8:12]
             if clean_dev is not None:
                 cleaned = head[12:20] if skew_dev is not None else head[8:16]
+            if curl_dev is not None:
+                at = 8 + (4 if skew_dev is not None else 0) + (8 if clean_dev is not None else 0)
+                curl = head[at:at + n_curl]
             nb = int(lcounts[0])
             blocks = head[-6 * max_blocks:].reshape(max_blocks, 6)[:nb]
             block_seg = _lib.SegmentParams(*[getattr(seg, f) for f, _ in seg._fields_][:9])
@@ -491,24 +503,28 @@ class Model:
             truncated = bool((bcounts[:, 0] > max_boxes).any())
         else:
             boxes_dev, counts_dev = segment_page_device(page, params, max_boxes, stream)
-            if skew_dev is None and clean_dev is None:
+            if skew_dev is None and clean_dev is None and curl_dev is None:
                 counts = counts_dev.cpu().numpy()
             else:
                 both = torch.cat([counts_dev, skew_dev if skew_dev is not None else counts_dev[:0],
-                                  clean_dev if clean_dev is not None else counts_dev[:0]]).cpu().numpy()
+                                  clean_dev if clean_dev is not None else counts_dev[:0]]
+                                 + (curl_dev if curl_dev is not None else [])).cpu().numpy()
                 counts = both[:4]
                 if skew_dev is not None:
                     skew = both[4:8]
+                if curl_dev is not None:
+                    curl, both = both[-n_curl:], both[:-n_curl]
                 if clean_dev is not None:
                     cleaned = both[-8:]
             n = int(min(counts[0], max_boxes))
             rows = boxes_dev[:n].cpu().numpy()
             truncated = bool(counts[0] > max_boxes)
         return SimpleNamespace(page=page, skew_dev=skew_dev, skew=skew, cleaned=cleaned, lay=lay, blocks=blocks, block_id=block_id, nb=nb,
-                               lcounts=lcounts, boxes_dev=boxes_dev, rows=rows, counts=counts, n=n, truncated=truncated)
+                               lcounts=lcounts, boxes_dev=boxes_dev, rows=rows, counts=counts, n=n, truncated=truncated, curl=curl,
+                               curl_group=curl_group)
 
     def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None, flatten=None,
-                       layout=None, clean=None, orient=None, rectify=None, scale=None):
+                       layout=None, clean=None, orient=None, rectify=None, scale=None, dewarp=None):
         """Read a scanned page: segment it into word boxes (aocr_segment_page), crop them (aocr_crop_lines) and recognise the crops.
         page: a uint8 (H,W) numpy array or tensor (gray; a 3-D array raises ValueError: colour pages are out of scope).  params: an
         `aocr.SegmentParams` (default: Otsu threshold, dark text).  The counts and boxes are read back once (the one sync), then the boxes are
@@ -580,10 +596,23 @@ class Model:
         (how many components qualified, None likewise), scale_shape ((Wo, Ho), None unless scaled) and unscaled_corners (n,4,2) float64: the
         corner pixels of every box -- source_corners with deskew, those of source_boxes with orient, else those of boxes -- on the page as it
         was before resizing, xs = (x + 0.5) * W / Wo - 0.5 (aocr.page.unscale_points); with rectify, photo_corners goes through this map
-        first.  Limits (a median of boxes, not an x-height; below about 4 pixels the estimate is noise): DESIGN.md section 19."""
-        from .page import (bucket_width, clean_page_device, crop_lines_device, estimate_glyph_size_device, estimate_orientation_device,
-                           find_page_quad_device, flatten_page_device, rectify_plan, resize_page_device, rotate_page_device, scale_plan,
-                           source_corners, unrotate_boxes, unrotate_points, unscale_points, warp_page_device, warp_points)
+        first.  Limits (a median of boxes, not an x-height; below about 4 pixels the estimate is noise): DESIGN.md section 19.
+        dewarp: None or False (the default) reads the page as it is.  True or an `aocr.CurlParams` takes out page curl -- the curved text
+        lines of a page bending into a book's gutter, which a shear cannot straighten -- after the deskew and before layout and segmentation
+        (so an orient=True half-turn restart redoes it): the row shift of every group of columns against the middle group is estimated
+        (aocr_estimate_curl; True: groups of 128 columns, shifts up to 8 rows, the threshold and light_text of `params`) and every column is
+        moved back by its interpolated shift (aocr_dewarp_page, filled with paper: 0 with light_text, else 255); the shifts go from one to
+        the other on the device, and the curl words and shifts come back with the existing readback (no additional sync).  The namespace
+        then also carries curl_shifts (ng) int32, curl_group, curl_max (the largest |shift|), curl_pairs (the pairs of neighbouring groups
+        with a non-zero shift) and uncurled_corners (n,4,2) float64: every box's corner pixels on the page that the dewarp read
+        (aocr.page.uncurl_points: x stays, y moves by the column's shift); boxes are in dewarped-page coordinates.  source_corners,
+        photo_corners and unscaled_corners then start from uncurled_corners with y rounded half up (floor(y + 0.5)); source_boxes stays an
+        axis-aligned box and ignores the curl.  Limits (max_shift against the line pitch, errors adding up along the chain, empty margins,
+        no foreshortening): DESIGN.md section 20."""
+        from .page import (box_corners, bucket_width, clean_page_device, crop_lines_device, estimate_glyph_size_device,
+                           estimate_orientation_device, find_page_quad_device, flatten_page_device, rectify_plan, resize_page_device,
+                           rotate_page_device, scale_plan, source_corners, source_points, uncurl_points, unrotate_boxes, unrotate_points,
+                           unscale_points, warp_page_device, warp_points)
         if isinstance(page, np.ndarray):
             if page.ndim != 2 or page.dtype != np.uint8:
                 raise ValueError(f"page must be a uint8 (H, W) array, got {page.dtype} {page.shape}: colour pages are out of scope")
@@ -653,7 +682,7 @@ class Model:
                 if not 0 <= quarter <= 3:
                     raise ValueError(f"orient={orient!r}: None, False, True or 0..3 clockwise quarter turns")
             page = rotate_page_device(page0, quarter, None, stream)
-        st = self._page_boxes(page, params, max_boxes, deskew, layout, clean_dev, stream)
+        st = self._page_boxes(page, params, max_boxes, deskew, layout, clean_dev, stream, dewarp)
         if orient is True:
             m = min(st.n, self.batch_size)                          # which way up: the recogniser reads the first boxes both ways
             orient_scores = (0.0, 0.0)
@@ -667,7 +696,7 @@ class Model:
             if orient_scores[1] > orient_scores[0]:
                 quarter = (quarter + 2) & 3
                 page = rotate_page_device(page0, quarter, None, stream)
-                st = self._page_boxes(page, params, max_boxes, deskew, layout, clean_dev, stream)
+                st = self._page_boxes(page, params, max_boxes, deskew, layout, clean_dev, stream, dewarp)
         page, skew_dev, skew, cleaned, lay = st.page, st.skew_dev, st.skew, st.cleaned, st.lay
         blocks, block_id, nb, lcounts = st.blocks, st.block_id, st.nb, st.lcounts
         boxes_dev, rows, counts, n, truncated = st.boxes_dev, st.rows, st.counts, st.n, st.truncated
@@ -712,10 +741,20 @@ class Model:
         if clean_dev is not None:
             res.clean_components, res.clean_specks, res.clean_rules, res.clean_ink_removed = (int(cleaned[0]), int(cleaned[1]), int(cleaned[2]),
                                                                                               int(cleaned[5]))
+        curled = None                                               # (x, y) int64 of the boxes' corner pixels on the page that dewarp read
+        if st.curl is not None:
+            res.curl_shifts, res.curl_group = st.curl[4:].astype(np.int32), st.curl_group
+            res.curl_max, res.curl_pairs = int(st.curl[1]), int(st.curl[3])
+            ux, uy = uncurl_points(*box_corners(res.boxes), res.curl_shifts, res.curl_group)
+            res.uncurled_corners = np.stack([ux, uy], axis=2)
+            curled = ux.astype(np.int64), np.floor(uy + 0.5).astype(np.int64)
         if skew_dev is not None:
             res.skew_steps, res.skew_slope_q16 = int(skew[0]), int(skew[1])
             res.skew_deg = math.degrees(math.atan(res.skew_slope_q16 / 65536.0))
-            res.source_corners = source_corners(res.boxes, res.skew_slope_q16, page.shape[0], page.shape[1])
+            if curled is None:
+                res.source_corners = source_corners(res.boxes, res.skew_slope_q16, page.shape[0], page.shape[1])
+            else:
+                res.source_corners = np.stack(source_points(*curled, res.skew_slope_q16, page.shape[0], page.shape[1]), axis=2)
         if quarter is not None:
             H0, W0 = int(page0.shape[0]), int(page0.shape[1])
             res.orientation, res.orient_runs, res.orient_scores = quarter, orient_runs, orient_scores
@@ -726,6 +765,8 @@ class Model:
         if rect is not None or scl is not None:
             if skew_dev is not None:
                 pc = res.source_corners
+            elif curled is not None:
+                pc = np.stack(curled if quarter is None else unrotate_points(*curled, quarter, H0, W0), axis=2)
             else:
                 b = (res.source_boxes if quarter is not None else res.boxes).astype(np.int64).reshape(-1, 4)
                 pc = np.stack([np.stack([b[:, 0], b[:, 2] - 1, b[:, 2] - 1, b[:, 0]], axis=1),

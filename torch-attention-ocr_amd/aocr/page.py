@@ -12,7 +12,10 @@ of the largest paper component), `rectify_plan` (`aocr_rectify_plan`, host only)
 resample) before all of them; `warp_points` takes points of the rectified page back to the photograph.  Every one of them counts in
 pixels of text at 300 dpi: a page scanned at another resolution goes through `estimate_glyph_size_device` (`aocr_estimate_glyph_size`: the
 median of min(w, h) over the component boxes), `scale_plan` (host only) and `resize_page_device` (`aocr_resize_page`: exact area
-resampling) after the flattening; `unscale_points` takes points back to the page before resizing."""
+resampling) after the flattening; `unscale_points` takes points back to the page before resizing.  A shear takes out one slope: the
+curved lines of a page bending into a book's gutter go through `estimate_curl_device` (`aocr_estimate_curl`: the row shift between
+neighbouring column groups by correlation) and `dewarp_page_device` (`aocr_dewarp_page`: every column moved by its shift) after the
+deskew; `uncurl_points` takes points back to the page before it."""
 from __future__ import annotations
 
 import ctypes as C
@@ -21,7 +24,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import Box, CleanParams, FlattenParams, GlyphParams, LayoutParams, RectifyParams, ScaleParams, SegmentParams, SkewParams, check, lib, ptr
+from ._lib import Box, CleanParams, CurlParams, FlattenParams, GlyphParams, LayoutParams, RectifyParams, ScaleParams, SegmentParams, SkewParams, check, lib, ptr
 
 IMG_H = 32
 MIN_ASPECT = 0.5
@@ -307,15 +310,95 @@ def source_corners(boxes, slope_q16, H, W):
     """(n, 4, 2) int64: for every box (x0 y0 x1 y1, half-open, deskewed-page coordinates) the source-page (x, y) of its corner pixels
     (x0, y0), (x1-1, y0), (x1-1, y1-1), (x0, y1-1) under `aocr_deskew_page`'s mapping with slope_q16 (clamped like the device clamps it).
     Host numpy; the corners of a box near the rim may lie outside the source page."""
+    x, y = box_corners(boxes)
+    sx, sy = source_points(x, y, slope_q16, H, W)
+    return np.stack([sx, sy], axis=2)
+
+
+def box_corners(boxes):
+    """(x, y), each (n, 4) int64: the corner pixels (x0, y0), (x1-1, y0), (x1-1, y1-1), (x0, y1-1) of half-open boxes x0 y0 x1 y1."""
     b = np.asarray(boxes, np.int64)
     b = b.reshape(-1, b.shape[-1] if b.ndim > 1 else 4)[:, :4]
-    s = min(max(int(slope_q16), -16384), 16384)
-    cx, cy = int(W) >> 1, int(H) >> 1
     x = np.stack([b[:, 0], b[:, 2] - 1, b[:, 2] - 1, b[:, 0]], axis=1)
     y = np.stack([b[:, 1], b[:, 1], b[:, 3] - 1, b[:, 3] - 1], axis=1)
+    return x, y
+
+
+def source_points(x, y, slope_q16, H, W):
+    """(sx, sy) int64: the source-page pixel of pixel (x, y) of the deskewed page under `aocr_deskew_page`'s mapping with slope_q16 (clamped
+    like the device clamps it): `source_corners` point by point.  Integer arrays; host numpy."""
+    x, y = np.asarray(x, np.int64), np.asarray(y, np.int64)
+    s = min(max(int(slope_q16), -16384), 16384)
+    cx, cy = int(W) >> 1, int(H) >> 1
     sy = y + (((x - cx) * s + 32768) >> 16)
     sx = x - (((y - cy) * s + 32768) >> 16)
-    return np.stack([sx, sy], axis=2)
+    return sx, sy
+
+
+def estimate_curl_device(page_dev, params=None, stream=None, scores=False):
+    """(curl (4) int32: ng, max |shift|, the threshold used, pairs with a non-zero shift; shifts (ng) int32: the rows by which the text of
+    every group of 32 * group columns sits below that of the middle group) as device tensors (`aocr_estimate_curl`); with scores=True also
+    scores (ng - 1, 2 * max_shift + 1) int64: every pair's correlation at every candidate shift, -max_shift first.  params: a `CurlParams`
+    (default: Otsu, groups of 128 columns, shifts up to 8 rows).  Enqueues only.  stream: as for `segment_page_device`, the current torch
+    stream; the scratch is freed when this returns."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    params = params if params is not None else CurlParams()
+    dev = page_dev.device
+    need = int(lib.aocr_curl_scratch_bytes(H, W, params.group, params.max_shift))
+    if need == 0:
+        check(1, "aocr_curl_scratch_bytes")
+    ng = -(-((W + 31) // 32) // params.group)
+    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    curl = torch.zeros(4, dtype=torch.int32, device=dev)
+    shifts = torch.zeros(ng, dtype=torch.int32, device=dev)
+    sc = torch.zeros((ng - 1, 2 * params.max_shift + 1), dtype=torch.int64, device=dev) if scores else None
+    check(lib.aocr_estimate_curl(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), ptr(curl), ptr(shifts),
+                                 ptr(sc) if scores and sc.numel() else None), "aocr_estimate_curl")
+    return (curl, shifts, sc) if scores else (curl, shifts)
+
+
+def dewarp_page_device(page_dev, shifts, group, fill=255, stream=None):
+    """a new (H, W) uint8 device tensor: every column of the page moved along y by its shift (`aocr_dewarp_page`: the shifts interpolated
+    between the group centres in Q8, two source rows blended; `fill` where a source row is outside the page).  shifts: the (ng) int32 device
+    tensor of `estimate_curl_device` (read on the device: no host sync) for the same `group`.  Enqueues only.  stream: as for
+    `segment_page_device`."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    dev = page_dev.device
+    group = int(group)
+    if not 1 <= group <= 16:
+        raise ValueError(f"group={group}: 1..16")
+    ng = -(-((W + 31) // 32) // group)
+    assert isinstance(shifts, torch.Tensor) and shifts.dtype == torch.int32 and shifts.device == dev and shifts.numel() == ng, \
+        f"shifts must be {ng} int32 words on the page's device"
+    shifts = shifts.contiguous()
+    out = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    check(lib.aocr_dewarp_page(_stream(stream, dev), ptr(page_dev), pitch, H, W, group, ptr(shifts), int(fill), ptr(out), W), "aocr_dewarp_page")
+    return out
+
+
+def curl_shift_q8(x, shifts, group):
+    """q(x) int64: the row shift of column x in Q8 as `aocr_dewarp_page` takes it from the group shifts (clamped to +-16384 like the device
+    clamps them): flat up to the first group centre and from the last one on, between two centres interpolated with a floor division.
+    x: an int array or int; host numpy."""
+    s = np.clip(np.asarray(shifts, np.int64).reshape(-1), -16384, 16384)
+    x = np.asarray(x, np.int64)
+    group, ng = int(group), len(s)
+    w, h = 32 * group, 16 * group
+    j = np.clip((x - h) // w, 0, max(ng - 2, 0))
+    j1 = np.minimum(j + 1, ng - 1)
+    t = x - (j * w + h)
+    q = 256 * s[j] + ((s[j1] - s[j]) * t * 256 + h) // w        # numpy's // floors
+    q = np.where(x <= h, 256 * s[0], q)
+    return np.where(x >= (ng - 1) * w + h, 256 * s[ng - 1], q)
+
+
+def uncurl_points(x, y, shifts, group):
+    """(x, y + q(x) / 256) float64: where `aocr_dewarp_page` with these shifts samples the page for the pixel (x, y) of the dewarped page.
+    x: integer columns.  Host numpy."""
+    x = np.asarray(x, np.int64)
+    return x.astype(np.float64), np.asarray(y, np.float64) + curl_shift_q8(x, shifts, group) / 256.0
 
 
 def find_page_quad_device(page_dev, threshold=-1, dark_paper=0, stream=None):
@@ -463,6 +546,6 @@ def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
     return min(img_w, int(max_img_w))
 
 
-__all__ = ["GlyphParams", "ScaleParams", "estimate_glyph_size_device", "resize_page_device", "scale_plan", "unscale_points", "RectifyParams", "find_page_quad_device", "rectify_plan", "warp_page_device", "warp_points", "SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "CleanParams", "Box", "label_components_device", "clean_page_device", "segment_page_device", "crop_lines_device",
+__all__ = ["CurlParams", "estimate_curl_device", "dewarp_page_device", "curl_shift_q8", "uncurl_points", "source_points", "box_corners", "GlyphParams", "ScaleParams", "estimate_glyph_size_device", "resize_page_device", "scale_plan", "unscale_points", "RectifyParams", "find_page_quad_device", "rectify_plan", "warp_page_device", "warp_points", "SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "CleanParams", "Box", "label_components_device", "clean_page_device", "segment_page_device", "crop_lines_device",
            "estimate_skew_device", "deskew_page_device", "flatten_page_device", "ink_integral_device", "layout_page_device", "source_corners",
            "rotate_page_device", "estimate_orientation_device", "unrotate_boxes", "unrotate_points", "bucket_width"]

@@ -1111,4 +1111,53 @@ int aocr_resize_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32
   return check_launch("aocr_resize_page");
 }
 
+static bool curl_sizes_ok(int32_t group, int32_t max_shift) { return group >= 1 && group <= 16 && max_shift >= 0 && max_shift <= 64; }
+
+size_t aocr_curl_scratch_bytes(int32_t H, int32_t W, int32_t group, int32_t max_shift) {
+  if (!(page_size_ok(H, W) && curl_sizes_ok(group, max_shift))) {
+    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26) group=%d (1..16) max_shift=%d (0..64)", H, W, group, max_shift);
+    return 0;
+  }
+  return curl_scratch_bytes(H, W, group, max_shift);
+}
+
+int aocr_estimate_curl(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_curl_params* params,
+                       void* scratch_dev, int32_t curl_dev[4], int32_t* shifts_dev, uint64_t* scores_dev) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(params, "params is NULL");
+  if (check_threshold(params->threshold)) return 1;
+  REQUIRE(params->group >= 1 && params->group <= 16, "group=%d: 1..16", params->group);
+  REQUIRE(params->max_shift >= 0 && params->max_shift <= 64, "max_shift=%d: 0..64", params->max_shift);
+  REQUIRE(params->min_ink >= 0 && params->min_ink <= (1 << 20), "min_ink=%d: 0..2^20", params->min_ink);
+  REQUIRE(params->reserved[0] == 0 && params->reserved[1] == 0 && params->reserved[2] == 0, "reserved words must be 0");
+  if (check_scratch(scratch_dev, curl_dev && shifts_dev)) return 1;
+  REQUIRE(((uintptr_t)curl_dev & 3) == 0 && ((uintptr_t)shifts_dev & 3) == 0, "curl_dev and shifts_dev must be 4-byte aligned");
+  REQUIRE(((uintptr_t)scores_dev & 7) == 0, "scores_dev must be 8-byte aligned");
+  const int ng = curl_groups(W, params->group);
+  const size_t scratch_bytes = curl_scratch_bytes(H, W, params->group, params->max_shift);
+  if (check_words(page_dev, pitch, H, W, scratch_dev, scratch_bytes, curl_dev, 4, "curl_dev")) return 1;
+  if (check_words(page_dev, pitch, H, W, scratch_dev, scratch_bytes, shifts_dev, ng, "shifts_dev")) return 1;
+  if (scores_dev) {
+    const Span scores = span_bytes(scores_dev, (size_t)(ng - 1) * (2 * params->max_shift + 1) * sizeof(uint64_t));
+    REQUIRE(disjoint(scores, span_rows(page_dev, pitch, H, W)), "scores_dev overlaps the page");
+    REQUIRE(disjoint(scores, span_bytes(scratch_dev, scratch_bytes)), "scores_dev overlaps the scratch");
+  }
+  estimate_curl((hipStream_t)stream, page_dev, pitch, H, W, *params, scratch_dev, curl_dev, shifts_dev, scores_dev);
+  return check_launch("aocr_estimate_curl");
+}
+
+int aocr_dewarp_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t group, const int32_t* shifts_dev,
+                     int32_t fill, uint8_t* out_dev, int64_t out_pitch) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(group >= 1 && group <= 16, "group=%d: 1..16", group);
+  REQUIRE(shifts_dev, "shifts_dev is NULL");
+  REQUIRE(((uintptr_t)shifts_dev & 3) == 0, "shifts_dev must be 4-byte aligned");
+  REQUIRE(out_dev, "out_dev is NULL");
+  if (check_out(page_dev, pitch, H, W, out_dev, out_pitch, H, W, "W=", [&] { REQUIRE(fill >= 0 && fill <= 255, "fill=%d: 0..255", fill); return 0; }))
+    return 1;
+  REQUIRE(disjoint(span_rows(out_dev, out_pitch, H, W), span_bytes(shifts_dev, curl_groups(W, group) * sizeof(int32_t))), "out_dev overlaps shifts_dev");
+  dewarp_page((hipStream_t)stream, page_dev, pitch, H, W, group, shifts_dev, fill, out_dev, out_pitch);
+  return check_launch("aocr_dewarp_page");
+}
+
 }  // extern "C"

@@ -374,6 +374,19 @@ void estimate_skew(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int
                    uint64_t* scores);
 void deskew_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const int32_t* skew, int slope_q16, int fill, uint8_t* out,
                  int64_t out_pitch);
+// the strip profiles of aocr_estimate_skew (skew.hip's strips_kernel, one launch): R[b * strip_rows(H) + y] = ink pixels of row y inside the
+// 32-column strip b, uint8, for b < ceil(W / 32) and y < H; the other bytes of a strip's strip_rows(H) are not all written.  fixed >= 0 is
+// the threshold, else hdr[0] is read on the device (otsu_threshold's; -1: nothing is ink)
+int strip_rows(int H);
+void strip_profiles(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, int light, int fixed, const int32_t* hdr, uint8_t* R);
+// page dewarp (curl.hip; include/aocr.h: aocr_estimate_curl, aocr_dewarp_page): the row shift of every column group against the middle one
+// from correlations of neighbouring groups' profiles, and the column-wise resample that takes the shifts out
+int curl_groups(int W, int group);             // ng
+size_t curl_scratch_bytes(int H, int W, int group, int max_shift);
+void estimate_curl(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_curl_params& p, void* scratch, int32_t* curl,
+                   int32_t* shifts, uint64_t* scores);
+void dewarp_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, int group, const int32_t* shifts, int fill, uint8_t* out,
+                 int64_t out_pitch);
 // page background flattening (flatten.hip; include/aocr.h: aocr_flatten_page): windowed max, windowed mean, division, on a pitched gray page
 size_t flatten_scratch_bytes(int H, int W);
 void flatten_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_flatten_params& p, void* scratch, uint8_t* out,

@@ -7,7 +7,7 @@
 //   strips_kernel    the one page read.  A workgroup owns STRIP_ROWS consecutive rows, one wave per row at a time (wave_row16 of
 //                    page_common.h): a 16-bit ink mask per 16-byte load split at the strip boundary (a load starts anywhere in its
 //                    32-column strip: the row's base address is arbitrary) and added to the per-strip counters in LDS with integer
-//                    atomics.  R is written as uint8 [strip][row], 8 rows per store.
+//                    atomics.  R is written as uint8 [strip][row], 8 rows per store.  curl.hip launches it too, through strip_profiles.
 //   sweep_kernel     grid (row chunk, candidate): one thread per profile row r walks the strips (consecutive threads read consecutive
 //                    bytes of R), squares its sum and the workgroup adds the squares in uint64: one partial per (candidate, chunk).
 //   pick_kernel      one workgroup: the partials of a candidate are added in chunk order, the scores written, the winner taken by the
@@ -44,7 +44,7 @@ SkewLayout skew_layout(int H, int W, int n_steps) {
   SkewLayout l;
   ScratchCursor c;
   l.nb = (W + 31) / 32;
-  l.hs = (H + 15) & ~15;                       // rows of one strip of R, padded so that every 8-row store is aligned and inside
+  l.hs = strip_rows(H);
   const int dmax = std::max(max_off(l.nb, W >> 1, SLOPE_MAX), max_off(l.nb, W >> 1, -SLOPE_MAX));
   l.max_chunks = cdiv(H + 2 * dmax, SWEEP_THREADS);
   l.hist = c.take(256 * sizeof(uint32_t));
@@ -153,6 +153,14 @@ __global__ __launch_bounds__(256) void deskew_kernel(const uint8_t* __restrict__
 
 }  // namespace
 
+// rows of one strip of R, padded so that every 8-row store is aligned and inside
+int strip_rows(int H) { return (H + 15) & ~15; }
+
+// shared with curl.hip
+void strip_profiles(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, int light, int fixed, const int32_t* hdr, uint8_t* R) {
+  hipLaunchKernelGGL(strips_kernel, dim3(cdiv(H, STRIP_ROWS)), dim3(256), 0, s, page, pitch, H, W, light, fixed, hdr, (W + 31) / 32, strip_rows(H), R);
+}
+
 size_t skew_scratch_bytes(int H, int W, int n_steps) { return skew_layout(H, W, n_steps).total; }
 
 void estimate_skew(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_skew_params& p, void* scratch, int32_t* skew,
@@ -166,7 +174,7 @@ void estimate_skew(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int
   const int dmax = std::max(max_off(l.nb, W >> 1, K * p.step_q16), max_off(l.nb, W >> 1, -K * p.step_q16));
   const int nchunks = cdiv(H + 2 * dmax, SWEEP_THREADS);                  // <= l.max_chunks: K * step_q16 <= SLOPE_MAX
   page_threshold(s, page, pitch, H, W, fixed, hist, hdr);
-  hipLaunchKernelGGL(strips_kernel, dim3(cdiv(H, STRIP_ROWS)), dim3(256), 0, s, page, pitch, H, W, light, fixed, hdr, l.nb, l.hs, R);
+  strip_profiles(s, page, pitch, H, W, light, fixed, hdr, R);
   hipLaunchKernelGGL(sweep_kernel, dim3(nchunks, 2 * K + 1), dim3(SWEEP_THREADS), 0, s, R, H, W, l.nb, l.hs, K, p.step_q16, partials);
   hipLaunchKernelGGL(pick_kernel, dim3(1), dim3(256), 0, s, partials, nchunks, K, p.step_q16, fixed, hdr, skew, scores);
 }
