@@ -6,10 +6,13 @@ the greedy decoder cluster kernel (AOCR_NO_DEC_CHAINS=1) and the per-step launch
 2. the attention rows are the fp64 oracle's, teacher-forced with [GO, labels[:, :-1]] (a hypothesis' state depends on its tokens only, so
    this replays the winning beam too); rows sum to 1 up to the first EOS and are 0 after it;
 3. char_logp is the oracle's log-probability of each emitted token (0 on the PAD-at-no-cost steps) and sums to the score;
-4. Model.recognize reads a list of uint8 images without labels and returns what step(forward_only=True) reads.
+4. Model.recognize reads a list of uint8 images without labels and returns what step(forward_only=True) reads;
+5. Model.recognize_page with every optional stage on at once, as one column and with layout=True, reads what the public stage functions
+   called one after the other read, publishes the corner fields of tests/backmap_ref.py and makes no read of its own per stage.
 Weights are sharpened (oracle_torch.sharpen_params) and the BatchNorm statistics calibrated, so that the attention is peaked and a mis-indexed
 row shows."""
 import random
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -188,3 +191,142 @@ def test_recognize_rejects_bad_arguments(cuda):
     rc = aocr.lib.aocr_recognize(m._h, aocr.ptr(images), 4, 36, 1, None, None, aocr.ptr(scores), None, None)
     assert rc != 0 and "NULL" in aocr.last_error()
     m.shutdown()
+
+
+# ---- Model.recognize_page with every stage at once -------------------------------------------------------------------------------------------
+# The planted 600 x 800 page of curl_cases, curled (20 rows of sag) and then skewed (17 steps of 64 / 65536), doubled, turned upside down and
+# photographed on a desk with rectify_cases.text_photo's keystone: rectify (four corners given), flatten, scale=0.5, clean, orient=2, deskew
+# and dewarp each have something to do, and every estimate that would cost a sync is given by value.  What is expected is computed here from
+# the public stage functions in the documented order, once for both tests; the corner fields by tests/backmap_ref.py.
+PAGE_B = 32
+
+
+@pytest.fixture(scope="module")
+def staged(cuda):
+    import math
+    import aocr
+    import rectify_ref as RR
+    import skew_ref as SK
+    from curl_cases import SEGMENT, curled_page
+    m, O, ocfg, P0, st, _ = make(SMALL, B=PAGE_B, W=100, maxlen=8, compute="f32", max_decoder_l=12, max_beam=5)
+    m.set_parameters(O.sharpen_params(P0), st)
+    given = np.ascontiguousarray(np.kron(SK.deskew(curled_page(20), -17 * 64), np.ones((2, 2), np.uint8))[::-1, ::-1])
+    Hp, Wp = given.shape
+    H, W = Hp + 60, Wp + 80
+    quad = [31, 22, W - 44, 14, W - 25, H - 16, 12, H - 25]
+    photo = RR.make_photo(given, quad, H, W, 50)
+    corners = [tuple(quad[2 * i:2 * i + 2]) for i in range(4)]
+    params = aocr.SegmentParams(**SEGMENT)
+    skew_p, group = aocr.SkewParams(threshold=128, n_steps=32), 4
+    s = SimpleNamespace(m=m, photo=photo, params=params, group=group)
+    s.options = dict(rectify=corners, flatten=True, scale=0.5, clean=True, orient=2, deskew=skew_p, dewarp=True)
+    s.size, s.coef = aocr.rectify_plan(np.array(corners))
+    page = aocr.warp_page_device(torch.from_numpy(photo).to(cuda), s.coef, s.size, 255)
+    page = aocr.flatten_page_device(page, aocr.FlattenParams(light_text=0))
+    H1, W1 = page.shape
+    s.shape = (max(int(math.floor(W1 * 0.5 + 0.5)), 1), max(int(math.floor(H1 * 0.5 + 0.5)), 1))
+    s.resize = (H1, W1, s.shape[1], s.shape[0])
+    page = aocr.resize_page_device(page, s.shape)
+    page, cleaned = aocr.clean_page_device(page, aocr.CleanParams(threshold=128, light_text=0))
+    s.turn = (2, page.shape[0], page.shape[1])
+    page = aocr.rotate_page_device(page, 2)
+    skew = aocr.estimate_skew_device(page, skew_p)
+    page = aocr.deskew_page_device(page, skew, 255)
+    curl, shifts = aocr.estimate_curl_device(page, aocr.CurlParams(threshold=128, light_text=0))
+    s.final = aocr.dewarp_page_device(page, shifts, group, 255)
+    s.cleaned, s.skew, s.curl, s.shifts = cleaned.cpu().numpy(), skew.cpu().numpy(), curl.cpu().numpy(), shifts.cpu().numpy()
+    print(f"[recognize_page every stage] photo {photo.shape} -> {s.size} -> {s.shape}; skew {s.skew.tolist()}, curl {s.curl.tolist()} {s.shifts.tolist()}, "
+          f"cleaned {s.cleaned.tolist()}")
+    assert s.skew[1] != 0 and s.curl[1] > 0                                    # the shear and the curl are there to be taken out
+    yield s
+    m.check_health()
+    m.shutdown()
+
+
+def _read_page(s, monkeypatch, **kw):
+    """(the namespace, the elements of every Tensor.cpu() of the call before its first recognize_device, those after it)."""
+    reads = []
+    real_cpu, real_rec = torch.Tensor.cpu, s.m.recognize_device
+    with monkeypatch.context() as mp:
+        mp.setattr(torch.Tensor, "cpu", lambda t, *a, **k: (reads.append(t.numel()), real_cpu(t, *a, **k))[1])
+        mp.setattr(s.m, "recognize_device", lambda *a, **k: (reads.append("loop"), real_rec(*a, **k))[1])
+        res = s.m.recognize_page(s.photo, s.params, width=100, **s.options, **kw)
+    at = reads.index("loop")
+    return res, reads[:at], [r for r in reads[at:] if r != "loop"]
+
+
+def _check_staged(s, res, rows, cuda):
+    """everything but the layout fields: `rows` (n, 6) are the boxes expected on s.final."""
+    import math
+    import aocr
+    from backmap_ref import corner_fields
+    n = len(rows)
+    assert n > PAGE_B and res.n_found == n and not res.truncated and res.threshold == 128
+    np.testing.assert_array_equal(res.boxes, rows[:, :4])
+    np.testing.assert_array_equal(res.line, rows[:, 4])
+    np.testing.assert_array_equal(res.ink, rows[:, 5])
+    boxes_dev = torch.from_numpy(np.ascontiguousarray(rows)).to(cuda)
+    for c0 in range(0, n, PAGE_B):
+        ref = s.m.recognize(aocr.crop_lines_device(s.final, boxes_dev[c0:c0 + PAGE_B], None, 100))
+        np.testing.assert_array_equal(res.labels[c0:c0 + PAGE_B], ref.labels)
+        np.testing.assert_array_equal(res.scores[c0:c0 + PAGE_B], ref.scores)
+        assert res.text[c0:c0 + PAGE_B] == ref.text
+    assert (res.widths == 100).all() and res.flatten_radius == 16
+    assert (res.clean_components, res.clean_specks, res.clean_rules, res.clean_ink_removed) == tuple(int(s.cleaned[i]) for i in (0, 1, 2, 5))
+    assert (res.orientation, res.orient_runs, res.orient_scores) == (2, None, None)
+    assert (res.skew_steps, res.skew_slope_q16) == (int(s.skew[0]), int(s.skew[1])) and res.skew_deg == math.degrees(math.atan(int(s.skew[1]) / 65536.0))
+    np.testing.assert_array_equal(res.curl_shifts, s.shifts)
+    assert res.curl_shifts.dtype == np.int32 and (res.curl_group, res.curl_max, res.curl_pairs) == (s.group, int(s.curl[1]), int(s.curl[3]))
+    assert (res.scaled, res.scale_size, res.scale_quartiles, res.scale_glyphs, res.scale_shape) == (True, None, None, None, s.shape)
+    assert (res.rectified, res.rectify_size, res.rectify_area) == (True, s.size, None)
+    np.testing.assert_array_equal(res.rectify_quad, np.array(s.options["rectify"]))
+    want = corner_fields(rows[:, :4], (s.shifts, s.group), (int(s.skew[1]), s.final.shape[0], s.final.shape[1]), s.turn, s.resize, s.coef)
+    assert sorted(want) == ["photo_corners", "source_boxes", "source_corners", "uncurled_corners", "unscaled_corners"]
+    for k, v in want.items():
+        got = getattr(res, k)
+        assert got.dtype == v.dtype and got.shape == v.shape and np.array_equal(got, v), k
+    layout = {"block", "blocks", "block_depth", "n_blocks", "layout_overflow"}
+    assert set(vars(res)) - layout == {
+        "boxes", "line", "ink", "text", "labels", "scores", "widths", "threshold", "n_found", "n_lines", "truncated", "flatten_radius",
+        "clean_components", "clean_specks", "clean_rules", "clean_ink_removed", "curl_shifts", "curl_group", "curl_max", "curl_pairs",
+        "skew_steps", "skew_slope_q16", "skew_deg", "orientation", "orient_runs", "orient_scores", "scaled", "scale_size", "scale_quartiles",
+        "scale_glyphs", "scale_shape", "rectified", "rectify_quad", "rectify_size", "rectify_area"} | set(want)
+
+
+def test_recognize_page_every_stage_single_column(cuda, staged, monkeypatch):
+    import aocr
+    s = staged
+    res, before, after = _read_page(s, monkeypatch)
+    boxes_dev, counts_dev = aocr.segment_page_device(s.final, s.params)
+    counts = counts_dev.cpu().numpy()
+    rows = boxes_dev[:int(counts[0])].cpu().numpy()
+    assert (res.n_found, res.n_lines, res.threshold) == tuple(int(v) for v in counts[:3])
+    _check_staged(s, res, rows, cuda)
+    assert not hasattr(res, "blocks") and not hasattr(res, "block")
+    # one read brings every word back -- counts 4, skew 4, clean 8, curl 4 + ng: no stage adds a sync of its own -- and the boxes follow it
+    n = len(rows)
+    assert before == [4 + 4 + 8 + 4 + len(s.shifts), 6 * n], before
+    assert len(after) == 2 * -(-n // PAGE_B)                                 # labels and scores of every chunk
+    print(f"[recognize_page every stage] {n} boxes in {res.n_lines} lines; reads {before} then {len(after)} in the loop")
+
+
+def test_recognize_page_every_stage_layout(cuda, staged, monkeypatch):
+    import layout_ref as L
+    import segment_ref as R
+    from curl_cases import SEGMENT
+    s = staged
+    res, before, after = _read_page(s, monkeypatch, layout=True)
+    final = s.final.cpu().numpy()
+    want_blocks, want_counts, info = L.layout_page(final, 128, 0)
+    rows, ids, lines, found, truncated = L.segment_blocks(final, want_blocks, **dict(R.DEFAULTS, **SEGMENT))
+    nb = len(want_blocks)
+    assert nb >= 1 and res.n_blocks == nb == want_counts[0] and res.layout_overflow == bool(want_counts[3]) and info[0] == 128
+    np.testing.assert_array_equal(res.blocks, want_blocks[:, :4])
+    np.testing.assert_array_equal(res.block_depth, want_blocks[:, 4])
+    np.testing.assert_array_equal(res.block, ids)
+    assert res.block.dtype == np.int32 and (res.n_found, res.n_lines, res.truncated) == (found, lines, truncated)
+    _check_staged(s, res, rows, cuda)
+    # two reads: the layout's counts 4, info 4 and 256 blocks with skew 4, clean 8, curl 4 + ng; then every block's counts and boxes
+    assert before == [4 + 4 + 4 + 8 + 4 + len(s.shifts) + 6 * 256, nb * (4 + 6 * 1024)], before
+    assert len(after) == 2 * -(-len(rows) // PAGE_B)
+    print(f"[recognize_page every stage, layout] {len(rows)} boxes in {lines} lines of {nb} blocks; reads {before}")

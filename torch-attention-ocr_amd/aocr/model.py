@@ -20,6 +20,8 @@ import torch
 from . import _lib, dist
 from ._lib import Config, check, lib, ptr
 from .dictionary import edit_distance_device
+from .page import backmap_corners, bucket_width, crop_lines_device, rotate_page_device
+from .page_pipeline import clean_stage, flatten_stage, orient_stage, page_boxes, rectify_stage, scale_stage
 
 PAD, GO, EOS = 1, 2, 3
 GROUPS = ["cnn", "enc_fw", "enc_bw", "dec", "proj"]
@@ -50,19 +52,22 @@ def encoder_columns(W: int) -> np.ndarray:
     return 4.0 * np.arange(max(T, 0), dtype=np.float64) + 4.0
 
 
+def _cut(row):
+    """the ids of a label row up to its first EOS."""
+    out = []
+    for v in row:
+        if v == EOS:
+            break
+        out.append(int(v))
+    return out
+
+
 def eval_word_err_rate(labels: np.ndarray, target_labels: np.ndarray, visualize: bool = False):
     """evalWordErrRate, src/utils/utils.lua:136-175: sequences are cut at the first EOS (3) and compared exactly."""
     B = labels.shape[0]
     werr, pred, gold = 0.0, [], []
     for b in range(B):
-        def cut(row):
-            out = []
-            for v in row:
-                if v == EOS:
-                    break
-                out.append(int(v))
-            return out
-        p, g = cut(labels[b]), cut(target_labels[b])
+        p, g = _cut(labels[b]), _cut(target_labels[b])
         if visualize:
             pred.append(numlist2str(p)); gold.append(numlist2str(g))
         if p != g:
@@ -423,14 +428,7 @@ class Model:
                 lexicon.to(self.device)
             snapped = lexicon.nearest(labels, lexicon_rows, self._stream())
         labels_h = labels.cpu().numpy()
-        text = []
-        for row in labels_h:
-            ids = []
-            for v in row:
-                if v == EOS:
-                    break
-                ids.append(int(v))
-            text.append(numlist2str(ids))
+        text = [numlist2str(_cut(row)) for row in labels_h]
         self.check_health()
         res = SimpleNamespace(labels=labels_h, scores=scores.cpu().numpy(), text=text, char_logp=clp.cpu().numpy(),
                               attention=attn.cpu().numpy() if attn is not None else None, columns=encoder_columns(images.shape[3]))
@@ -439,89 +437,9 @@ class Model:
             res.word = [lexicon.words[i] if i >= 0 else None for i in res.word_index.tolist()]
         return res
 
-    def _page_boxes(self, page, params, max_boxes, deskew, layout, clean_dev, stream, dewarp=None):
-        """the middle of recognize_page, from the deskew to the boxes on the host: everything that reads the page in its final orientation and
-        has to be redone when recognize_page(orient=True) turns the page by another half turn.  Returns its locals as a namespace."""
-        from .page import (deskew_page_device, dewarp_page_device, estimate_curl_device, estimate_skew_device, layout_page_device,
-                           segment_page_device)
-        skew = cleaned = blocks = block_id = nb = lcounts = None
-        skew_dev = None
-        if deskew is not None and deskew is not False:
-            seg = params if params is not None else _lib.SegmentParams()
-            sp = deskew if isinstance(deskew, _lib.SkewParams) else _lib.SkewParams(threshold=seg.threshold, light_text=seg.light_text)
-            skew_dev = estimate_skew_device(page, sp, stream)
-            page = deskew_page_device(page, skew_dev, 0 if seg.light_text else 255, stream)
-        curl = curl_dev = curl_group = None                       # curl_dev: [the four curl words, the ng group shifts], read back together
-        if dewarp is not None and dewarp is not False:
-            seg = params if params is not None else _lib.SegmentParams()
-            cp = dewarp if isinstance(dewarp, _lib.CurlParams) else _lib.CurlParams(threshold=seg.threshold, light_text=seg.light_text)
-            words_dev, shifts_dev = estimate_curl_device(page, cp, stream)
-            page = dewarp_page_device(page, shifts_dev, cp.group, 0 if seg.light_text else 255, stream)
-            curl_dev, curl_group, n_curl = [words_dev, shifts_dev], int(cp.group), 4 + shifts_dev.numel()
-        lay = None
-        if layout is not None and layout is not False:
-            seg = params if params is not None else _lib.SegmentParams()
-            lay = layout if isinstance(layout, _lib.LayoutParams) else _lib.LayoutParams()
-            max_blocks = 256
-            blocks_dev, lcounts_dev, info_dev = layout_page_device(page, lay, seg.threshold, seg.light_text, max_blocks, stream)
-            head = torch.cat([lcounts_dev, info_dev, skew_dev if skew_dev is not None else lcounts_dev[:0],
-                              clean_dev if clean_dev is not None else lcounts_dev[:0]] + (curl_dev if curl_dev is not None else [])
-                             + [blocks_dev.reshape(-1)]).cpu().numpy()
-            lcounts, info = head[:4], head[4:8]                   # the first sync
-            if skew_dev is not None:
-                skew = head[8:12]
-            if clean_dev is not None:
-                cleaned = head[12:20] if skew_dev is not None else head[8:16]
-            if curl_dev is not None:
-                at = 8 + (4 if skew_dev is not None else 0) + (8 if clean_dev is not None else 0)
-                curl = head[at:at + n_curl]
-            nb = int(lcounts[0])
-            blocks = head[-6 * max_blocks:].reshape(max_blocks, 6)[:nb]
-            block_seg = _lib.SegmentParams(*[getattr(seg, f) for f, _ in seg._fields_][:9])
-            block_seg.threshold = int(info[0])                    # the page's threshold: every block thresholds like the whole page
-            per = [segment_page_device(page[b[1]:b[3], b[0]:b[2]], block_seg, max_boxes, stream) for b in blocks.tolist()]
-            if nb:
-                all_boxes = torch.stack([bx for bx, _ in per])                          # (nb, max_boxes, 6)
-                all_counts = torch.stack([c for _, c in per])                           # (nb, 4)
-                all_boxes[:, :, :4] += blocks_dev[:nb][:, [0, 1, 0, 1]][:, None, :]
-                lines_dev = all_counts[:, 1]
-                all_boxes[:, :, 4] += (torch.cumsum(lines_dev, 0) - lines_dev).to(torch.int32)[:, None]
-                all_boxes = all_boxes.reshape(-1, 6)
-                back = torch.cat([all_counts.reshape(-1), all_boxes.reshape(-1)]).cpu().numpy()     # the second sync
-                bcounts = back[:4 * nb].reshape(nb, 4)
-                taken = np.minimum(bcounts[:, 0], max_boxes)
-                keep = np.concatenate([b * max_boxes + np.arange(t) for b, t in enumerate(taken.tolist())]).astype(np.int64)
-                rows = back[4 * nb:].reshape(-1, 6)[keep]
-                boxes_dev = all_boxes[torch.from_numpy(keep).to(self.device)]
-                block_id = np.repeat(np.arange(nb, dtype=np.int32), taken)
-            else:
-                bcounts = np.zeros((0, 4), np.int32)
-                rows, block_id = np.zeros((0, 6), np.int32), np.zeros(0, np.int32)
-                boxes_dev = torch.zeros((0, 6), dtype=torch.int32, device=self.device)
-            n = len(rows)
-            counts = np.array([bcounts[:, 0].sum(), bcounts[:, 1].sum(), info[0], 0], np.int64)
-            truncated = bool((bcounts[:, 0] > max_boxes).any())
-        else:
-            boxes_dev, counts_dev = segment_page_device(page, params, max_boxes, stream)
-            if skew_dev is None and clean_dev is None and curl_dev is None:
-                counts = counts_dev.cpu().numpy()
-            else:
-                both = torch.cat([counts_dev, skew_dev if skew_dev is not None else counts_dev[:0],
-                                  clean_dev if clean_dev is not None else counts_dev[:0]]
-                                 + (curl_dev if curl_dev is not None else [])).cpu().numpy()
-                counts = both[:4]
-                if skew_dev is not None:
-                    skew = both[4:8]
-                if curl_dev is not None:
-                    curl, both = both[-n_curl:], both[:-n_curl]
-                if clean_dev is not None:
-                    cleaned = both[-8:]
-            n = int(min(counts[0], max_boxes))
-            rows = boxes_dev[:n].cpu().numpy()
-            truncated = bool(counts[0] > max_boxes)
-        return SimpleNamespace(page=page, skew_dev=skew_dev, skew=skew, cleaned=cleaned, lay=lay, blocks=blocks, block_id=block_id, nb=nb,
-                               lcounts=lcounts, boxes_dev=boxes_dev, rows=rows, counts=counts, n=n, truncated=truncated, curl=curl,
-                               curl_group=curl_group)
+    def _page_boxes(self, page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev):
+        """the middle of recognize_page (aocr.page_pipeline.page_boxes), reached through the model so that a caller can wrap it."""
+        return page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev)
 
     def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None, flatten=None,
                        layout=None, clean=None, orient=None, rectify=None, scale=None, dewarp=None):
@@ -609,10 +527,6 @@ class Model:
         photo_corners and unscaled_corners then start from uncurled_corners with y rounded half up (floor(y + 0.5)); source_boxes stays an
         axis-aligned box and ignores the curl.  Limits (max_shift against the line pitch, errors adding up along the chain, empty margins,
         no foreshortening): DESIGN.md section 20."""
-        from .page import (box_corners, bucket_width, clean_page_device, crop_lines_device, estimate_glyph_size_device,
-                           estimate_orientation_device, find_page_quad_device, flatten_page_device, rectify_plan, resize_page_device,
-                           rotate_page_device, scale_plan, source_corners, source_points, uncurl_points, unrotate_boxes, unrotate_points,
-                           unscale_points, warp_page_device, warp_points)
         if isinstance(page, np.ndarray):
             if page.ndim != 2 or page.dtype != np.uint8:
                 raise ValueError(f"page must be a uint8 (H, W) array, got {page.dtype} {page.shape}: colour pages are out of scope")
@@ -623,66 +537,15 @@ class Model:
         page = page.to(self.device)
         beam_size = min(beam_size or 1, self.target_vocab_size)
         stream = self._stream()
-        rect = None
-        if rectify is not None and rectify is not False:
-            seg = params if params is not None else _lib.SegmentParams()
-            rect = SimpleNamespace(used=False, quad=None, size=None, area=None, coef=None)
-            if rectify is True or isinstance(rectify, _lib.RectifyParams):
-                rp = rectify if isinstance(rectify, _lib.RectifyParams) else _lib.RectifyParams(dark_paper=seg.light_text)
-                words = find_page_quad_device(page, rp.threshold, rp.dark_paper, stream).cpu().numpy()         # the additional sync
-                rect.area = int(words[9])
-                if rect.area > 0:
-                    rect.quad = words[:8].reshape(4, 2).astype(np.int64)
-                rect.used = bool(words[11]) and rect.area * 100 >= rp.min_area_percent * int(page.shape[0]) * int(page.shape[1])
-            else:
-                rp = _lib.RectifyParams(dark_paper=seg.light_text)
-                q = np.asarray(rectify)
-                if q.shape != (4, 2) or not np.all(q == np.round(q)):
-                    raise ValueError(f"rectify={rectify!r}: None, False, True, an aocr.RectifyParams or four integer (x, y) corners TL, TR, BR, BL")
-                rect.quad, rect.used = q.astype(np.int64), True
-            if rect.used:
-                rect.size, rect.coef = rectify_plan(rect.quad, rp.width, rp.height)
-                fill = rp.fill if rp.fill is not None else (0 if seg.light_text else 255)
-                page = warp_page_device(page, rect.coef, rect.size, fill, stream)
-        flat = None
-        if flatten is not None and flatten is not False:
-            seg = params if params is not None else _lib.SegmentParams()
-            flat = flatten if isinstance(flatten, _lib.FlattenParams) else _lib.FlattenParams(light_text=seg.light_text)
-            page = flatten_page_device(page, flat, stream)
-        scl = None
-        if scale is not None and scale is not False:
-            seg = params if params is not None else _lib.SegmentParams()
-            H1, W1 = int(page.shape[0]), int(page.shape[1])
-            scl = SimpleNamespace(shape=None, size=None, quartiles=None, glyphs=None, H=H1, W=W1)
-            if scale is True or isinstance(scale, _lib.ScaleParams):
-                sp = scale if isinstance(scale, _lib.ScaleParams) else _lib.ScaleParams(_lib.GlyphParams(threshold=seg.threshold, light_text=seg.light_text))
-                words = estimate_glyph_size_device(page, sp.glyph, stream).cpu().numpy()                      # the additional sync
-                scl.size, scl.quartiles, scl.glyphs = int(words[0]), (int(words[1]), int(words[2])), int(words[3])
-                scl.shape = scale_plan(scl.size, scl.glyphs, H1, W1, sp)
-            else:
-                ok = isinstance(scale, (int, float, np.integer, np.floating)) and not isinstance(scale, bool)
-                if not (ok and math.isfinite(float(scale)) and float(scale) > 0):
-                    raise ValueError(f"scale={scale!r}: None, False, True, an aocr.ScaleParams or a positive ratio")
-                scl.shape = (max(int(math.floor(W1 * float(scale) + 0.5)), 1), max(int(math.floor(H1 * float(scale) + 0.5)), 1))
-            if scl.shape is not None:
-                page = resize_page_device(page, scl.shape, stream)
-        clean_dev = None
-        if clean is not None and clean is not False:
-            seg = params if params is not None else _lib.SegmentParams()
-            cp = clean if isinstance(clean, _lib.CleanParams) else _lib.CleanParams(threshold=seg.threshold, light_text=seg.light_text)
-            page, clean_dev = clean_page_device(page, cp, stream)
-        quarter, page0, orient_runs, orient_scores = None, page, None, None
-        if orient is not None and orient is not False:
-            if orient is True:
-                seg = params if params is not None else _lib.SegmentParams()
-                words = estimate_orientation_device(page, seg.threshold, seg.light_text, stream).cpu().numpy()    # the additional sync
-                quarter, orient_runs = int(words[0]), (int(words[1]), int(words[2]))
-            else:
-                quarter = int(orient)
-                if not 0 <= quarter <= 3:
-                    raise ValueError(f"orient={orient!r}: None, False, True or 0..3 clockwise quarter turns")
-            page = rotate_page_device(page0, quarter, None, stream)
-        st = self._page_boxes(page, params, max_boxes, deskew, layout, clean_dev, stream, dewarp)
+        seg = params if params is not None else _lib.SegmentParams()
+        page, rect = rectify_stage(page, stream, seg, rectify)
+        page, flat = flatten_stage(page, stream, seg, flatten)
+        page, scl = scale_stage(page, stream, seg, scale)
+        page0, clean_dev = clean_stage(page, stream, seg, clean)
+        page, quarter, orient_runs = orient_stage(page0, stream, seg, orient)
+        middle = (stream, seg, max_boxes, deskew, dewarp, layout, clean_dev)
+        st = self._page_boxes(page, *middle)
+        orient_scores = None
         if orient is True:
             m = min(st.n, self.batch_size)                          # which way up: the recogniser reads the first boxes both ways
             orient_scores = (0.0, 0.0)
@@ -695,11 +558,8 @@ class Model:
                 orient_scores = tuple(float(v) for v in torch.stack([up, down]).cpu().numpy())
             if orient_scores[1] > orient_scores[0]:
                 quarter = (quarter + 2) & 3
-                page = rotate_page_device(page0, quarter, None, stream)
-                st = self._page_boxes(page, params, max_boxes, deskew, layout, clean_dev, stream, dewarp)
-        page, skew_dev, skew, cleaned, lay = st.page, st.skew_dev, st.skew, st.cleaned, st.lay
-        blocks, block_id, nb, lcounts = st.blocks, st.block_id, st.nb, st.lcounts
-        boxes_dev, rows, counts, n, truncated = st.boxes_dev, st.rows, st.counts, st.n, st.truncated
+                st = self._page_boxes(rotate_page_device(page0, quarter, None, stream), *middle)
+        page, rows, counts, n = st.page, st.rows, st.counts, st.n
         if width is not None:
             widths = np.full(n, int(width), np.int64)
         else:
@@ -713,7 +573,7 @@ class Model:
             members = np.nonzero(widths == w)[0]
             for c0 in range(0, len(members), self.batch_size):
                 idx = members[c0:c0 + self.batch_size]
-                sel = boxes_dev[torch.from_numpy(idx).to(self.device)]
+                sel = st.boxes_dev[torch.from_numpy(idx).to(self.device)]
                 crops = crop_lines_device(page, sel, None, int(w), self.img_h, stream)
                 lab, sc, _, _ = self.recognize_device(crops, beam_size, trie)
                 if lexicon is not None:
@@ -722,69 +582,36 @@ class Model:
                 labels[idx], scores[idx] = lab.cpu().numpy(), sc.cpu().numpy()
         if n:
             self.check_health()
-        text = []
-        for row in labels:
-            ids = []
-            for v in row:
-                if v == EOS:
-                    break
-                ids.append(int(v))
-            text.append(numlist2str(ids))
+        text = [numlist2str(_cut(row)) for row in labels]
         res = SimpleNamespace(boxes=rows[:, :4].copy(), line=rows[:, 4].copy(), ink=rows[:, 5].copy(), text=text, labels=labels, scores=scores,
                               widths=widths, threshold=int(counts[2]), n_found=int(counts[0]), n_lines=int(counts[1]),
-                              truncated=truncated)
-        if lay is not None:
-            res.block, res.blocks, res.block_depth = block_id, blocks[:, :4].copy(), blocks[:, 4].copy()
-            res.n_blocks, res.layout_overflow = nb, bool(lcounts[3])
+                              truncated=st.truncated)
+        if st.lay is not None:
+            res.block, res.blocks, res.block_depth = st.block_id, st.blocks[:, :4].copy(), st.blocks[:, 4].copy()
+            res.n_blocks, res.layout_overflow = st.nb, bool(st.lcounts[3])
         if flat is not None:
             res.flatten_radius = int(flat.radius)
-        if clean_dev is not None:
-            res.clean_components, res.clean_specks, res.clean_rules, res.clean_ink_removed = (int(cleaned[0]), int(cleaned[1]), int(cleaned[2]),
-                                                                                              int(cleaned[5]))
-        curled = None                                               # (x, y) int64 of the boxes' corner pixels on the page that dewarp read
+        if st.cleaned is not None:
+            res.clean_components, res.clean_specks, res.clean_rules, res.clean_ink_removed = (int(st.cleaned[0]), int(st.cleaned[1]),
+                                                                                              int(st.cleaned[2]), int(st.cleaned[5]))
+        curl = skew = turn = None                                   # what each stage left behind for aocr.page.backmap_corners
         if st.curl is not None:
             res.curl_shifts, res.curl_group = st.curl[4:].astype(np.int32), st.curl_group
             res.curl_max, res.curl_pairs = int(st.curl[1]), int(st.curl[3])
-            ux, uy = uncurl_points(*box_corners(res.boxes), res.curl_shifts, res.curl_group)
-            res.uncurled_corners = np.stack([ux, uy], axis=2)
-            curled = ux.astype(np.int64), np.floor(uy + 0.5).astype(np.int64)
-        if skew_dev is not None:
-            res.skew_steps, res.skew_slope_q16 = int(skew[0]), int(skew[1])
+            curl = res.curl_shifts, res.curl_group
+        if st.skew is not None:
+            res.skew_steps, res.skew_slope_q16 = int(st.skew[0]), int(st.skew[1])
             res.skew_deg = math.degrees(math.atan(res.skew_slope_q16 / 65536.0))
-            if curled is None:
-                res.source_corners = source_corners(res.boxes, res.skew_slope_q16, page.shape[0], page.shape[1])
-            else:
-                res.source_corners = np.stack(source_points(*curled, res.skew_slope_q16, page.shape[0], page.shape[1]), axis=2)
+            skew = res.skew_slope_q16, page.shape[0], page.shape[1]
         if quarter is not None:
-            H0, W0 = int(page0.shape[0]), int(page0.shape[1])
             res.orientation, res.orient_runs, res.orient_scores = quarter, orient_runs, orient_scores
-            res.source_boxes = unrotate_boxes(res.boxes, quarter, H0, W0)
-            if skew_dev is not None:
-                sx, sy = unrotate_points(res.source_corners[:, :, 0], res.source_corners[:, :, 1], quarter, H0, W0)
-                res.source_corners = np.stack([sx, sy], axis=2)
-        if rect is not None or scl is not None:
-            if skew_dev is not None:
-                pc = res.source_corners
-            elif curled is not None:
-                pc = np.stack(curled if quarter is None else unrotate_points(*curled, quarter, H0, W0), axis=2)
-            else:
-                b = (res.source_boxes if quarter is not None else res.boxes).astype(np.int64).reshape(-1, 4)
-                pc = np.stack([np.stack([b[:, 0], b[:, 2] - 1, b[:, 2] - 1, b[:, 0]], axis=1),
-                               np.stack([b[:, 1], b[:, 1], b[:, 3] - 1, b[:, 3] - 1], axis=1)], axis=2)
-            pc = pc.astype(np.float64)
+            turn = quarter, int(page0.shape[0]), int(page0.shape[1])
         if scl is not None:
             res.scaled, res.scale_size, res.scale_quartiles, res.scale_glyphs, res.scale_shape = (scl.shape is not None, scl.size, scl.quartiles,
                                                                                                   scl.glyphs, scl.shape)
-            if scl.shape is not None:
-                ux, uy = unscale_points(pc[:, :, 0], pc[:, :, 1], scl.H, scl.W, scl.shape[1], scl.shape[0])
-                pc = np.stack([ux, uy], axis=2)
-            res.unscaled_corners = pc
         if rect is not None:
             res.rectified, res.rectify_quad, res.rectify_size, res.rectify_area = rect.used, rect.quad, rect.size, rect.area
-            if rect.used:
-                px, py = warp_points(rect.coef, pc[:, :, 0], pc[:, :, 1])
-                pc = np.stack([px, py], axis=2)
-            res.photo_corners = pc
+        vars(res).update(backmap_corners(res.boxes, curl, skew, turn, None if scl is None else scl.resize, None if rect is None else rect.warp))
         if lexicon is not None:
             res.word_index, res.word_distance = word_index, word_distance
             res.word = [lexicon.words[i] if i >= 0 else None for i in word_index.tolist()]

@@ -53,6 +53,15 @@ def _page_view(page_dev):
     return page_dev, int(pitch)
 
 
+def _scratch(query, dev, *args):
+    """the int64 scratch tensor of a call on `dev`: lib.<query>(*args) bytes, rounded up to whole words.  A size of 0 is the library turning
+    the arguments down: raised through `check` under the query's name."""
+    need = int(getattr(lib, query)(*args))
+    if need == 0:
+        check(1, query)
+    return torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+
+
 def segment_page_device(page_dev, params=None, max_boxes=1024, stream=None):
     """(boxes (max_boxes, 6) int32 rows x0 y0 x1 y1 line ink, counts (4) int32: boxes found, lines, threshold, 0) as device tensors.
     Rows of boxes beyond min(counts[0], max_boxes) are not written (they hold zeros).  Enqueues only.
@@ -62,10 +71,7 @@ def segment_page_device(page_dev, params=None, max_boxes=1024, stream=None):
     H, W = page_dev.shape
     params = params if params is not None else SegmentParams()
     dev = page_dev.device
-    need = int(lib.aocr_segment_scratch_bytes(H, W, max_boxes))
-    if need == 0:
-        check(1, "aocr_segment_scratch_bytes")
-    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    scratch = _scratch("aocr_segment_scratch_bytes", dev, H, W, max_boxes)
     boxes = torch.zeros((max_boxes, 6), dtype=torch.int32, device=dev)
     counts = torch.zeros(4, dtype=torch.int32, device=dev)
     check(lib.aocr_segment_page(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), max_boxes, ptr(boxes),
@@ -102,10 +108,7 @@ def estimate_skew_device(page_dev, params=None, stream=None, scores=False):
     H, W = page_dev.shape
     params = params if params is not None else SkewParams()
     dev = page_dev.device
-    need = int(lib.aocr_skew_scratch_bytes(H, W, params.n_steps))
-    if need == 0:
-        check(1, "aocr_skew_scratch_bytes")
-    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    scratch = _scratch("aocr_skew_scratch_bytes", dev, H, W, params.n_steps)
     skew = torch.zeros(4, dtype=torch.int32, device=dev)
     sc = torch.zeros(2 * params.n_steps + 1, dtype=torch.int64, device=dev) if scores else None
     check(lib.aocr_estimate_skew(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), ptr(skew), ptr(sc)),
@@ -139,10 +142,7 @@ def flatten_page_device(page_dev, params=None, stream=None):
     H, W = page_dev.shape
     params = params if params is not None else FlattenParams()
     dev = page_dev.device
-    need = int(lib.aocr_flatten_scratch_bytes(H, W, params.radius))
-    if need == 0:
-        check(1, "aocr_flatten_scratch_bytes")
-    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    scratch = _scratch("aocr_flatten_scratch_bytes", dev, H, W, params.radius)
     out = torch.empty((H, W), dtype=torch.uint8, device=dev)
     check(lib.aocr_flatten_page(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), ptr(out), W), "aocr_flatten_page")
     return out
@@ -151,10 +151,7 @@ def flatten_page_device(page_dev, params=None, stream=None):
 def _ink_integral(page_dev, pitch, threshold, light_text, stream):
     H, W = page_dev.shape
     dev = page_dev.device
-    need = int(lib.aocr_integral_scratch_bytes(H, W))
-    if need == 0:
-        check(1, "aocr_integral_scratch_bytes")
-    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    scratch = _scratch("aocr_integral_scratch_bytes", dev, H, W)
     sat_pitch = (W + 1 + 3) & ~3                             # rows of whole 16-byte words
     sat = torch.empty((H + 1, sat_pitch), dtype=torch.int32, device=dev)
     info = torch.zeros(4, dtype=torch.int32, device=dev)
@@ -183,11 +180,8 @@ def layout_page_device(page_dev, params=None, threshold=-1, light_text=0, max_bl
     H, W = page_dev.shape
     params = params if params is not None else LayoutParams()
     dev = page_dev.device
-    need = int(lib.aocr_layout_scratch_bytes(H, W, max_blocks))
-    if need == 0:
-        check(1, "aocr_layout_scratch_bytes")
+    scratch = _scratch("aocr_layout_scratch_bytes", dev, H, W, max_blocks)        # checked before the ink table is built
     sat, info = _ink_integral(page_dev, pitch, threshold, light_text, stream)
-    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
     blocks = torch.zeros((max_blocks, 6), dtype=torch.int32, device=dev)
     counts = torch.zeros(4, dtype=torch.int32, device=dev)
     check(lib.aocr_layout_blocks(_stream(stream, dev), ptr(sat), sat.stride(0), H, W, C.byref(params), ptr(scratch), max_blocks, ptr(blocks),
@@ -204,10 +198,7 @@ def label_components_device(page_dev, threshold=-1, light_text=0, connectivity=8
     page_dev, pitch = _page_view(page_dev)
     H, W = page_dev.shape
     dev = page_dev.device
-    need = int(lib.aocr_components_scratch_bytes(H, W))
-    if need == 0:
-        check(1, "aocr_components_scratch_bytes")
-    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    scratch = _scratch("aocr_components_scratch_bytes", dev, H, W)
     labels = torch.empty((H, W), dtype=torch.int32, device=dev)
     comps = torch.zeros((max(int(max_components), 1), 6), dtype=torch.int32, device=dev)
     info = torch.zeros(4, dtype=torch.int32, device=dev)
@@ -225,10 +216,7 @@ def clean_page_device(page_dev, params=None, stream=None):
     H, W = page_dev.shape
     params = params if params is not None else CleanParams()
     dev = page_dev.device
-    need = int(lib.aocr_clean_scratch_bytes(H, W))
-    if need == 0:
-        check(1, "aocr_clean_scratch_bytes")
-    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    scratch = _scratch("aocr_clean_scratch_bytes", dev, H, W)
     out = torch.empty((H, W), dtype=torch.uint8, device=dev)
     counts = torch.zeros(8, dtype=torch.int32, device=dev)
     check(lib.aocr_clean_page(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), ptr(out), W, ptr(counts)),
@@ -264,10 +252,7 @@ def estimate_orientation_device(page_dev, threshold=-1, light_text=0, stream=Non
     page_dev, pitch = _page_view(page_dev)
     H, W = page_dev.shape
     dev = page_dev.device
-    need = int(lib.aocr_orient_scratch_bytes(H, W))
-    if need == 0:
-        check(1, "aocr_orient_scratch_bytes")
-    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    scratch = _scratch("aocr_orient_scratch_bytes", dev, H, W)
     orient = torch.zeros(8, dtype=torch.int32, device=dev)
     check(lib.aocr_estimate_orientation(_stream(stream, dev), ptr(page_dev), pitch, H, W, int(threshold), int(light_text), ptr(scratch),
                                         ptr(orient)), "aocr_estimate_orientation")
@@ -345,11 +330,8 @@ def estimate_curl_device(page_dev, params=None, stream=None, scores=False):
     H, W = page_dev.shape
     params = params if params is not None else CurlParams()
     dev = page_dev.device
-    need = int(lib.aocr_curl_scratch_bytes(H, W, params.group, params.max_shift))
-    if need == 0:
-        check(1, "aocr_curl_scratch_bytes")
+    scratch = _scratch("aocr_curl_scratch_bytes", dev, H, W, params.group, params.max_shift)
     ng = -(-((W + 31) // 32) // params.group)
-    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
     curl = torch.zeros(4, dtype=torch.int32, device=dev)
     shifts = torch.zeros(ng, dtype=torch.int32, device=dev)
     sc = torch.zeros((ng - 1, 2 * params.max_shift + 1), dtype=torch.int64, device=dev) if scores else None
@@ -409,10 +391,7 @@ def find_page_quad_device(page_dev, threshold=-1, dark_paper=0, stream=None):
     page_dev, pitch = _page_view(page_dev)
     H, W = page_dev.shape
     dev = page_dev.device
-    need = int(lib.aocr_quad_scratch_bytes(H, W))
-    if need == 0:
-        check(1, "aocr_quad_scratch_bytes")
-    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    scratch = _scratch("aocr_quad_scratch_bytes", dev, H, W)
     quad = torch.zeros(16, dtype=torch.int32, device=dev)
     check(lib.aocr_find_page_quad(_stream(stream, dev), ptr(page_dev), pitch, H, W, int(threshold), int(dark_paper), ptr(scratch), ptr(quad)),
           "aocr_find_page_quad")
@@ -474,10 +453,7 @@ def estimate_glyph_size_device(page_dev, params=None, stream=None):
     H, W = page_dev.shape
     params = params if params is not None else GlyphParams()
     dev = page_dev.device
-    need = int(lib.aocr_glyph_scratch_bytes(H, W))
-    if need == 0:
-        check(1, "aocr_glyph_scratch_bytes")
-    scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    scratch = _scratch("aocr_glyph_scratch_bytes", dev, H, W)
     glyph = torch.zeros(8, dtype=torch.int32, device=dev)
     check(lib.aocr_estimate_glyph_size(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), ptr(glyph)),
           "aocr_estimate_glyph_size")
@@ -536,6 +512,50 @@ def unscale_points(x, y, H, W, Ho, Wo):
     return (x + 0.5) * W / Wo - 0.5, (y + 0.5) * H / Ho - 0.5
 
 
+def backmap_corners(boxes, curl=None, skew=None, turn=None, resize=None, warp=None):
+    """The corner fields of `Model.recognize_page`: the corner pixels of the final page's boxes carried back through every stage that ran,
+    in the one order the stages have: curl, shear, quarter turn, resize, perspective warp.  Host numpy; a dict of (n, 4, 2) arrays
+    ((n, 4) for source_boxes) holding only the fields of the stages given.  boxes: (n, >= 4) x0 y0 x1 y1, half-open.  Each stage is None when
+    it was not asked for, else what it left behind:
+    curl = (shifts, group): uncurled_corners, float64 `uncurl_points` of `box_corners(boxes)`; the later stages go on from them as int64
+    with y rounded half up, floor(y + 0.5).
+    skew = (slope_q16, H, W), H x W the final page: source_corners, int64 `source_points` of those corners, with a turn carried through
+    `unrotate_points` afterwards.
+    turn = (quarter, H0, W0), H0 x W0 the page before the turn: source_boxes, `unrotate_boxes(boxes, ...)`, which ignores shear and curl.
+    resize = (H, W, Ho, Wo), the page before and after `aocr_resize_page`, or () when the plan left the page alone: unscaled_corners,
+    float64 `unscale_points` of the incoming corners (() : the incoming corners).
+    warp = the nine coefficients of `rectify_plan`, or () when no sheet was used: photo_corners, float64 `warp_points` of the corners
+    that the resize put out (() : those corners).
+    The corners entering resize and warp are source_corners with skew; otherwise, with curl, the rounded uncurled corners carried through
+    `unrotate_points`; otherwise the corner pixels of source_boxes (of boxes without a turn).  The last case takes the corners of the
+    un-rotated BOX, the one before un-rotates the corner POINTS: for an odd quarter turn the two list the same four pixels in a different
+    order.  That is how recognize_page has always published them, and it is kept."""
+    out = {}
+    x, y = box_corners(boxes)
+    if curl is not None:
+        ux, uy = uncurl_points(x, y, *curl)
+        out["uncurled_corners"] = np.stack([ux, uy], axis=2)
+        x, y = ux.astype(np.int64), np.floor(uy + 0.5).astype(np.int64)
+    if skew is not None:
+        x, y = source_points(x, y, *skew)
+    if turn is not None:
+        out["source_boxes"] = unrotate_boxes(boxes, *turn)
+        x, y = unrotate_points(x, y, *turn) if curl is not None or skew is not None else box_corners(out["source_boxes"])
+    if skew is not None:
+        out["source_corners"] = np.stack([x, y], axis=2)
+    if resize is not None or warp is not None:
+        x, y = x.astype(np.float64), y.astype(np.float64)
+    if resize is not None:
+        if len(resize):
+            x, y = unscale_points(x, y, *resize)
+        out["unscaled_corners"] = np.stack([x, y], axis=2)
+    if warp is not None:
+        if len(warp):
+            x, y = warp_points(warp, x, y)
+        out["photo_corners"] = np.stack([x, y], axis=2)
+    return out
+
+
 def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
     """DataGen's width rule for a w x h box, ceil(clamp(w/h, 0.5, max_aspect) * 32), rounded up to a multiple of width_step and capped at
     max_img_w.  max_aspect None: max_img_w / 32."""
@@ -546,6 +566,6 @@ def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
     return min(img_w, int(max_img_w))
 
 
-__all__ = ["CurlParams", "estimate_curl_device", "dewarp_page_device", "curl_shift_q8", "uncurl_points", "source_points", "box_corners", "GlyphParams", "ScaleParams", "estimate_glyph_size_device", "resize_page_device", "scale_plan", "unscale_points", "RectifyParams", "find_page_quad_device", "rectify_plan", "warp_page_device", "warp_points", "SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "CleanParams", "Box", "label_components_device", "clean_page_device", "segment_page_device", "crop_lines_device",
+__all__ = ["backmap_corners", "CurlParams", "estimate_curl_device", "dewarp_page_device", "curl_shift_q8", "uncurl_points", "source_points", "box_corners", "GlyphParams", "ScaleParams", "estimate_glyph_size_device", "resize_page_device", "scale_plan", "unscale_points", "RectifyParams", "find_page_quad_device", "rectify_plan", "warp_page_device", "warp_points", "SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "CleanParams", "Box", "label_components_device", "clean_page_device", "segment_page_device", "crop_lines_device",
            "estimate_skew_device", "deskew_page_device", "flatten_page_device", "ink_integral_device", "layout_page_device", "source_corners",
            "rotate_page_device", "estimate_orientation_device", "unrotate_boxes", "unrotate_points", "bucket_width"]

@@ -1,0 +1,183 @@
+"""The stage chain of `Model.recognize_page` in front of the recogniser, as plain functions of the page: rectify, flatten, scale, clean and
+the quarter turn (one function each, in that order), then `page_boxes`: deskew, dewarp, layout and segmentation down to the boxes on the
+host.  Every function takes the page on the device, the raw handle of the current torch stream and the page's resolved `SegmentParams`,
+enqueues on that stream, and returns the page with a small record of what it did (None when the stage was not asked for).  What needs a
+model -- the which-way-up probe, the crop-and-recognise loop, the lexicon -- stays in `Model`; the way back from box corners to the page as
+given is `aocr.page.backmap_corners`."""
+from __future__ import annotations
+
+import math
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from . import _lib
+from .page import (clean_page_device, deskew_page_device, dewarp_page_device, estimate_curl_device, estimate_glyph_size_device,
+                   estimate_orientation_device, estimate_skew_device, find_page_quad_device, flatten_page_device, layout_page_device,
+                   rectify_plan, resize_page_device, rotate_page_device, scale_plan, segment_page_device, warp_page_device)
+
+MAX_BLOCKS = 256
+
+
+def asked(option):
+    """whether a stage option of recognize_page asks for its stage: anything but None and False."""
+    return option is not None and option is not False
+
+
+def paper(seg):
+    """the gray level of paper, what a resampling stage fills with outside the page."""
+    return 0 if seg.light_text else 255
+
+
+def read_named(pieces):
+    """One readback of many small results: `pieces` maps names to int32 device tensors, lists of them, or None.  The pieces that are not
+    None are flattened and joined in the mapping's order by ONE torch.cat(...).cpu() -- one sync -- and come back as a dict from name to
+    numpy view (a list's tensors as one view, end to end); names given as None are absent."""
+    parts = {k: [t.reshape(-1) for t in (v if isinstance(v, (list, tuple)) else [v])] for k, v in pieces.items() if v is not None}
+    host = torch.cat([t for ts in parts.values() for t in ts]).cpu().numpy()
+    out, at = {}, 0
+    for k, ts in parts.items():
+        n = sum(t.numel() for t in ts)
+        out[k], at = host[at:at + n], at + n
+    return out
+
+
+def rectify_stage(page, stream, seg, rectify):
+    """(page, rect): rect.used, quad, size, area as recognize_page publishes them; rect.warp the nine coefficients, () when no sheet was used."""
+    if not asked(rectify):
+        return page, None
+    rect = SimpleNamespace(used=False, quad=None, size=None, area=None, warp=())
+    if rectify is True or isinstance(rectify, _lib.RectifyParams):
+        rp = rectify if isinstance(rectify, _lib.RectifyParams) else _lib.RectifyParams(dark_paper=seg.light_text)
+        words = find_page_quad_device(page, rp.threshold, rp.dark_paper, stream).cpu().numpy()         # the additional sync
+        rect.area = int(words[9])
+        if rect.area > 0:
+            rect.quad = words[:8].reshape(4, 2).astype(np.int64)
+        rect.used = bool(words[11]) and rect.area * 100 >= rp.min_area_percent * int(page.shape[0]) * int(page.shape[1])
+    else:
+        rp = _lib.RectifyParams(dark_paper=seg.light_text)
+        q = np.asarray(rectify)
+        if q.shape != (4, 2) or not np.all(q == np.round(q)):
+            raise ValueError(f"rectify={rectify!r}: None, False, True, an aocr.RectifyParams or four integer (x, y) corners TL, TR, BR, BL")
+        rect.quad, rect.used = q.astype(np.int64), True
+    if rect.used:
+        rect.size, rect.warp = rectify_plan(rect.quad, rp.width, rp.height)
+        page = warp_page_device(page, rect.warp, rect.size, rp.fill if rp.fill is not None else paper(seg), stream)
+    return page, rect
+
+
+def flatten_stage(page, stream, seg, flatten):
+    """(page, the FlattenParams used)."""
+    if not asked(flatten):
+        return page, None
+    flat = flatten if isinstance(flatten, _lib.FlattenParams) else _lib.FlattenParams(light_text=seg.light_text)
+    return flatten_page_device(page, flat, stream), flat
+
+
+def scale_stage(page, stream, seg, scale):
+    """(page, scl): scl.shape, size, quartiles, glyphs as recognize_page publishes them; scl.resize (H, W, Ho, Wo), the page before and
+    after, () when the page was left alone."""
+    if not asked(scale):
+        return page, None
+    H, W = int(page.shape[0]), int(page.shape[1])
+    scl = SimpleNamespace(shape=None, size=None, quartiles=None, glyphs=None, resize=())
+    if scale is True or isinstance(scale, _lib.ScaleParams):
+        sp = scale if isinstance(scale, _lib.ScaleParams) else _lib.ScaleParams(_lib.GlyphParams(threshold=seg.threshold, light_text=seg.light_text))
+        words = estimate_glyph_size_device(page, sp.glyph, stream).cpu().numpy()                      # the additional sync
+        scl.size, scl.quartiles, scl.glyphs = int(words[0]), (int(words[1]), int(words[2])), int(words[3])
+        scl.shape = scale_plan(scl.size, scl.glyphs, H, W, sp)
+    else:
+        ok = isinstance(scale, (int, float, np.integer, np.floating)) and not isinstance(scale, bool)
+        if not (ok and math.isfinite(float(scale)) and float(scale) > 0):
+            raise ValueError(f"scale={scale!r}: None, False, True, an aocr.ScaleParams or a positive ratio")
+        scl.shape = (max(int(math.floor(W * float(scale) + 0.5)), 1), max(int(math.floor(H * float(scale) + 0.5)), 1))
+    if scl.shape is not None:
+        page, scl.resize = resize_page_device(page, scl.shape, stream), (H, W, scl.shape[1], scl.shape[0])
+    return page, scl
+
+
+def clean_stage(page, stream, seg, clean):
+    """(page, the eight clean counts on the device: they come back with the boxes' readback)."""
+    if not asked(clean):
+        return page, None
+    cp = clean if isinstance(clean, _lib.CleanParams) else _lib.CleanParams(threshold=seg.threshold, light_text=seg.light_text)
+    return clean_page_device(page, cp, stream)
+
+
+def orient_stage(page, stream, seg, orient):
+    """(page, quarter, runs): the clockwise quarter turns applied, and (N_h, N_v) when they were estimated (orient=True)."""
+    if not asked(orient):
+        return page, None, None
+    runs = None
+    if orient is True:
+        words = estimate_orientation_device(page, seg.threshold, seg.light_text, stream).cpu().numpy()    # the additional sync
+        quarter, runs = int(words[0]), (int(words[1]), int(words[2]))
+    else:
+        quarter = int(orient)
+        if not 0 <= quarter <= 3:
+            raise ValueError(f"orient={orient!r}: None, False, True or 0..3 clockwise quarter turns")
+    return rotate_page_device(page, quarter, None, stream), quarter, runs
+
+
+def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev):
+    """the middle of recognize_page, from the deskew to the boxes on the host: everything that reads the page in its final orientation and
+    has to be redone when recognize_page(orient=True) turns the page by another half turn.  Returns a namespace: page, boxes_dev, rows, counts,
+    n, truncated; skew, cleaned, curl (the words read back, None without the stage), curl_group; lay, blocks, block_id, nb, lcounts
+    (None without layout)."""
+    st = SimpleNamespace(curl_group=None, lay=None, blocks=None, block_id=None, nb=None, lcounts=None)
+    skew_dev = curl_dev = None
+    if asked(deskew):
+        sp = deskew if isinstance(deskew, _lib.SkewParams) else _lib.SkewParams(threshold=seg.threshold, light_text=seg.light_text)
+        skew_dev = estimate_skew_device(page, sp, stream)
+        page = deskew_page_device(page, skew_dev, paper(seg), stream)
+    if asked(dewarp):
+        cp = dewarp if isinstance(dewarp, _lib.CurlParams) else _lib.CurlParams(threshold=seg.threshold, light_text=seg.light_text)
+        words_dev, shifts_dev = estimate_curl_device(page, cp, stream)
+        page = dewarp_page_device(page, shifts_dev, cp.group, paper(seg), stream)
+        curl_dev, st.curl_group = [words_dev, shifts_dev], int(cp.group)      # the four curl words, then the ng group shifts
+    st.page = page
+    riders = dict(skew=skew_dev, cleaned=clean_dev, curl=curl_dev)            # what comes back with the first readback, whichever it is
+    if asked(layout):
+        st.lay = layout if isinstance(layout, _lib.LayoutParams) else _lib.LayoutParams()
+        blocks_dev, lcounts_dev, info_dev = layout_page_device(page, st.lay, seg.threshold, seg.light_text, MAX_BLOCKS, stream)
+        got = read_named(dict(lcounts=lcounts_dev, info=info_dev, **riders, blocks=blocks_dev))             # the first sync
+        st.lcounts, info = got["lcounts"], got["info"]
+        st.nb = nb = int(st.lcounts[0])
+        st.blocks = got["blocks"].reshape(MAX_BLOCKS, 6)[:nb]
+        block_seg = _lib.SegmentParams(*[getattr(seg, f) for f, _ in seg._fields_][:9])
+        block_seg.threshold = int(info[0])                        # the page's threshold: every block thresholds like the whole page
+        per = [segment_page_device(page[b[1]:b[3], b[0]:b[2]], block_seg, max_boxes, stream) for b in st.blocks.tolist()]
+        if nb:
+            all_boxes = torch.stack([bx for bx, _ in per])                          # (nb, max_boxes, 6)
+            all_counts = torch.stack([c for _, c in per])                           # (nb, 4)
+            all_boxes[:, :, :4] += blocks_dev[:nb][:, [0, 1, 0, 1]][:, None, :]
+            lines_dev = all_counts[:, 1]
+            all_boxes[:, :, 4] += (torch.cumsum(lines_dev, 0) - lines_dev).to(torch.int32)[:, None]
+            all_boxes = all_boxes.reshape(-1, 6)
+            back = torch.cat([all_counts.reshape(-1), all_boxes.reshape(-1)]).cpu().numpy()     # the second sync
+            bcounts = back[:4 * nb].reshape(nb, 4)
+            taken = np.minimum(bcounts[:, 0], max_boxes)
+            keep = np.concatenate([b * max_boxes + np.arange(t) for b, t in enumerate(taken.tolist())]).astype(np.int64)
+            st.rows = back[4 * nb:].reshape(-1, 6)[keep]
+            st.boxes_dev = all_boxes[torch.from_numpy(keep).to(page.device)]
+            st.block_id = np.repeat(np.arange(nb, dtype=np.int32), taken)
+        else:
+            bcounts = np.zeros((0, 4), np.int32)
+            st.rows, st.block_id = np.zeros((0, 6), np.int32), np.zeros(0, np.int32)
+            st.boxes_dev = torch.zeros((0, 6), dtype=torch.int32, device=page.device)
+        st.n = len(st.rows)
+        st.counts = np.array([bcounts[:, 0].sum(), bcounts[:, 1].sum(), info[0], 0], np.int64)
+        st.truncated = bool((bcounts[:, 0] > max_boxes).any())
+    else:
+        st.boxes_dev, counts_dev = segment_page_device(page, seg, max_boxes, stream)
+        if all(v is None for v in riders.values()):
+            got = dict(counts=counts_dev.cpu().numpy())           # nothing rides along: the counts as they are, no torch.cat
+        else:
+            got = read_named(dict(counts=counts_dev, **riders))
+        st.counts = got["counts"]
+        st.n = int(min(st.counts[0], max_boxes))
+        st.rows = st.boxes_dev[:st.n].cpu().numpy()
+        st.truncated = bool(st.counts[0] > max_boxes)
+    st.skew, st.cleaned, st.curl = got.get("skew"), got.get("cleaned"), got.get("curl")
+    return st
