@@ -458,7 +458,7 @@ int aocr_get_tensor(aocr_model* m, const char* name, const void** ptr_dev, int32
   else if (n == "dc_bstamps") { REQUIRE(m->dc_xtab, "no decoder cluster kernel in this configuration"); *ptr_dev = m->dc_xtab + (size_t)((d.B + 31) / 32) * 32 + 16; *ndim = 1; shape[0] = 32; }
   else if (n == "dc_times") { REQUIRE(m->cl_err, "no cluster kernels in this configuration"); *ptr_dev = m->cl_err + 16 + 2048; *ndim = 1; shape[0] = 32 * 4 * 16 * 2; }   // 32 members x 4 gathers x 16 x u64 (10 ns ticks)
   else if (n == "g0") {                                   // debugging aid (AOCR_DBG_STOP=1|2): the gradient map the CNN backward pass stopped at
-    const char* e = getenv("AOCR_DBG_STOP"); const int stop = e ? atoi(e) : 0;
+    const int stop = knob::AOCR_DBG_STOP();
     const int64_t cnt = stop == 1 ? (int64_t)d.B * d.T * 512 : (int64_t)d.B * d.H4 * d.W2 * 512;
     if (m->bf16) bf16_to_f32(m->s, m->G0b, m->G0, cnt);
     *ptr_dev = m->G0; *ndim = 4; shape[0] = d.B; shape[1] = stop == 1 ? d.Ho7 : d.H4; shape[2] = stop == 1 ? d.Wo7 : d.W2; shape[3] = 512;
@@ -483,8 +483,8 @@ int aocr_profile_kernel(aocr_model* m, int32_t which, int32_t iters, float* ms_p
   constexpr size_t SLAB = (size_t)4 << 20;
   double bytes = 0.0;
   // bf16 data-gradient maps (conv_backward_data's dx16, round 4): what the step's BatchNorm backward / un-pool passes read when the switch is on
-  const char* const nd = getenv("AOCR_DX16");
-  const bool dx16 = (nd && nd[0] == '1') && !getenv("AOCR_BN_PARTIAL_OLD") && !getenv("AOCR_UNPOOL4") && !getenv("AOCR_HALO8") && B * d.H4 * d.W2 % 256 == 0;
+  // G1 as those two replays find it: conv6's data gradient in front of conv5's BatchNorm backward, conv7's in front of conv6's un-pool (cnn_backward's calls)
+  const bool dx16 = which == AOCR_PK_BN_BWD ? conv_dgrad_bf16_out(B, d.H4, d.W2, 512, 512, 3, 1) : which == AOCR_PK_UNPOOL ? conv_dgrad_bf16_out(B, d.H6, d.W2, 512, 512, 2, 0) : false;
   const bf16_t* const g1h = dx16 ? reinterpret_cast<const bf16_t*>(m->G1) : nullptr;
   const double dab = dx16 ? 2.0 : 4.0;                    // bytes per element of d A / d(pooled)
   // ids >= 2: the bandwidth-bound kernels, each replayed on the buffers the last TRAINING step left, with the arguments cnn_forward /
@@ -493,7 +493,7 @@ int aocr_profile_kernel(aocr_model* m, int32_t which, int32_t iters, float* ms_p
   auto run = [&]() {
     switch (which) {
     case 0:
-      if (const char* const pl = getenv("AOCR_PROBE_LAYER")) {   // debugging aid (tools/debug/conv_probe.py): the tagged launch of conv3 / conv4 / conv5 forward instead, as cnn_forward makes it
+      if (const char* const pl = knob::AOCR_PROBE_LAYER()) {   // debugging aid (tools/debug/conv_probe.py): the tagged launch of conv3 / conv4 / conv5 forward instead, as cnn_forward makes it
         int bnc = 0, y16 = 0; const int l = atoi(pl);
         if (l == 3) { conv_forward(m->s, m->bf16, m->A2, m->conv[3].w, m->conv[3].b, m->Y3, nullptr, d.B, d.H2, d.W2, 128, 256, 3, 1, 0, 0, m->A2b, m->wb[3], nullptr, 1, nullptr, nullptr, nullptr, (double*)m->bn_scratch, &bnc, &y16); break; }
         if (l == 4) { conv_forward(m->s, m->bf16, m->A3, m->conv[4].w, m->conv[4].b, nullptr, m->idx4, d.B, d.H2, d.W2, 256, 256, 3, 1, 1, 2, m->A3b, m->wb[4], m->A4b, 1); break; }
@@ -548,9 +548,9 @@ int aocr_profile_kernel(aocr_model* m, int32_t which, int32_t iters, float* ms_p
   float ms = 0.f; hipEventElapsedTime(&ms, e0, e1);
   hipEventDestroy(e0); hipEventDestroy(e1);
   *ms_per_launch = ms / iters;
-  if (which == 0 && getenv("AOCR_PROBE")) {
+  if (which == 0 && knob::AOCR_PROBE()) {
     unsigned long long pr[8] = {0}; kprobe_read(pr);
-    if (getenv("AOCR_PROBE_LAYER")) for (int k = 1; k >= 0; --k) if (pr[4 * k + 1]) fprintf(stderr, "[aocr] probe: workgroup %d of the tagged launch: start -> K loop %.1f us, K loop %.1f us (%llu cycles = %.2f GHz), whole workgroup (last store acknowledged) %.1f us\n", k ? 17 : 300, pr[4 * k + 2] / 100.0, pr[4 * k + 1] / 100.0, pr[4 * k], pr[4 * k] / (pr[4 * k + 1] * 10.0) , pr[4 * k + 3] / 100.0);
+    if (knob::AOCR_PROBE_LAYER()) for (int k = 1; k >= 0; --k) if (pr[4 * k + 1]) fprintf(stderr, "[aocr] probe: workgroup %d of the tagged launch: start -> K loop %.1f us, K loop %.1f us (%llu cycles = %.2f GHz), whole workgroup (last store acknowledged) %.1f us\n", k ? 17 : 300, pr[4 * k + 2] / 100.0, pr[4 * k + 1] / 100.0, pr[4 * k], pr[4 * k] / (pr[4 * k + 1] * 10.0) , pr[4 * k + 3] / 100.0);
     for (int k = 0; k < 2; ++k) if (pr[4 * k + 1]) fprintf(stderr, "[aocr] probe (%s halo kernel, conv6 forward): K loop of one workgroup %llu shader cycles in %.1f us = %.2f GHz\n", k ? "4-wave" : "8-wave", pr[4 * k], pr[4 * k + 1] / 100.0, pr[4 * k] / (pr[4 * k + 1] * 10.0)), fprintf(stderr, "[aocr]   prologue %.1f us, whole workgroup %.1f us (stores acknowledged)\n", pr[4 * k + 2] / 100.0, pr[4 * k + 3] / 100.0);
   }
   *flops_per_launch = which < 2 ? 2.0 * (double)d.B * d.H4 * d.W2 * 512.0 * (9.0 * 512.0) : bytes;

@@ -78,7 +78,7 @@ const char* comm_init_rccl(aocr_model* m, const char id[128], int nranks, int ra
   // communicator and the others on the first -- mismatched collectives, a hang at the first SyncBN sum.  So a failed split is an error on
   // the rank that sees it (the host aborts the job), never a silent fall-back; only a librccl WITHOUT the entry point (the same on every
   // rank of a node: one library) or AOCR_ONE_COMM=1 (set for the whole job) share one communicator.
-  if (sync_bn && g_rccl.split && !getenv("AOCR_ONE_COMM")) {
+  if (sync_bn && g_rccl.split && !knob::AOCR_ONE_COMM()) {
     void* c2 = nullptr;
     const int rs = g_rccl.split(c, 0, rank, &c2, nullptr);
     if (rs != 0 || !c2) {

@@ -1314,7 +1314,7 @@ __global__ __launch_bounds__(256, 1) void dec_ch_bwd_kernel(DecClBwdArgs p) {
 }
 
 // ---------------------------------------------------------------------------------------------
-bool dec_chain_enabled() { const char* e = getenv("AOCR_NO_DEC_CHAINS"); return !(e && e[0] == '1'); }
+bool dec_chain_enabled() { return !knob::AOCR_NO_DEC_CHAINS(); }
 
 void dec_chain_forward(hipStream_t s, const DecClFwdArgs& a0, bool greedy_decode) {
   static const int cus = [] { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
@@ -1328,13 +1328,13 @@ void dec_chain_forward(hipStream_t s, const DecClFwdArgs& a0, bool greedy_decode
     (void)hipFuncSetAttribute((const void*)dec_ch_fwd_kernel<true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CH_DEC_LDS);
     (void)hipFuncSetAttribute((const void*)dec_ch_fwd_kernel<true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CH_DEC_LDS);
   }
-  const bool res = a0.T <= 64 && !getenv("AOCR_CH_NO_RES");
+  const bool res = a0.T <= 64 && !knob::AOCR_CH_NO_RES();
   for (int g0 = 0; g0 < groups; g0 += per_pass) {
-    DecClFwdArgs a = a0; a.group0 = g0; a.ngroups = std::min(per_pass, groups - g0); a.force_remote = getenv("AOCR_CL_REMOTE") != nullptr;
-    { const char* e = getenv("AOCR_DC_STAMPS"); a.stamps = (e && e[0] != 'b') ? a.xtab + (size_t)groups * NM : nullptr; }      // ("beam": only the beam-search launches)
+    DecClFwdArgs a = a0; a.group0 = g0; a.ngroups = std::min(per_pass, groups - g0); a.force_remote = knob::AOCR_CL_REMOTE();
+    { const char* e = knob::AOCR_DC_STAMPS(); a.stamps = (e && e[0] != 'b') ? a.xtab + (size_t)groups * NM : nullptr; }      // ("beam": only the beam-search launches)
     const dim3 grid(8 * NM * ((a.ngroups + 7) / 8));
     if (greedy_decode) {
-      a.pgroups = groups; a.tokx = reinterpret_cast<unsigned*>(a.pbuf + (size_t)2 * groups * 32 * 32 * 40); a.no_early = getenv("AOCR_NO_DEC_EARLY") != nullptr;
+      a.pgroups = groups; a.tokx = reinterpret_cast<unsigned*>(a.pbuf + (size_t)2 * groups * 32 * 32 * 40); a.no_early = knob::AOCR_NO_DEC_EARLY();
       if (hist && res) hipLaunchKernelGGL((dec_ch_fwd_kernel<true, true, false, true>), grid, dim3(256), (size_t)CH_DEC_LDS, s, a);
       else if (hist) hipLaunchKernelGGL((dec_ch_fwd_kernel<true, false, false, true>), grid, dim3(256), (size_t)CH_DEC_LDS, s, a);
       else if (res) hipLaunchKernelGGL((dec_ch_fwd_kernel<true, true>), grid, dim3(256), (size_t)CH_DEC_LDS, s, a);
@@ -1357,7 +1357,7 @@ static int beam_pass_groups(int B, int L, int k) { return (int)std::min<long>(st
 int dec_chain_beam_passes(int B, int L, int k) { const int g = beam_pass_groups(B, L, k); return g < 1 ? 0 : (beam_groups(B, k) + g - 1) / g; }
 int dec_chain_beam_group_cap() { return chain_per_pass(); }
 bool dec_chain_beam_supported(int B, int L, int k, int V) {
-  if (k < 2 || k > 8 || V > 40 || B < 1 || getenv("AOCR_NO_DEC_CHAINS_BEAM") || !dec_chain_enabled()) return false;
+  if (k < 2 || k > 8 || V > 40 || B < 1 || knob::AOCR_NO_DEC_CHAINS_BEAM() || !dec_chain_enabled()) return false;
   return beam_pass_groups(B, L, k) >= 1;
 }
 void dec_chain_beam_forward(hipStream_t s, const DecClFwdArgs& a0) {
@@ -1369,11 +1369,11 @@ void dec_chain_beam_forward(hipStream_t s, const DecClFwdArgs& a0) {
     (void)hipFuncSetAttribute((const void*)dec_ch_fwd_kernel<true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(CH_DEC_LDS + CH_BEAM_EXTRA));
     (void)hipFuncSetAttribute((const void*)dec_ch_fwd_kernel<true, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(CH_DEC_LDS + CH_BEAM_EXTRA));
   }
-  const bool res = a0.T <= 64 && !getenv("AOCR_CH_NO_RES");
+  const bool res = a0.T <= 64 && !knob::AOCR_CH_NO_RES();
   unsigned epoch = a0.epoch;
   for (int g0 = 0; g0 < groups; g0 += per_pass, ++epoch) {
-    DecClFwdArgs a = a0; a.group0 = g0; a.ngroups = std::min(per_pass, groups - g0); a.force_remote = getenv("AOCR_CL_REMOTE") != nullptr;
-    a.epoch = epoch; a.stamps = getenv("AOCR_DC_STAMPS") ? a.xtab + (size_t)cap * NM : nullptr; a.no_early = 1;
+    DecClFwdArgs a = a0; a.group0 = g0; a.ngroups = std::min(per_pass, groups - g0); a.force_remote = knob::AOCR_CL_REMOTE();
+    a.epoch = epoch; a.stamps = knob::AOCR_DC_STAMPS() ? a.xtab + (size_t)cap * NM : nullptr; a.no_early = 1;
     a.rows_slot = 32 * per_pass;
     a.pgroups = cap; a.tokx = reinterpret_cast<unsigned*>(a.pbuf + (size_t)2 * cap * 32 * 32 * 40);
     const dim3 grid(8 * NM * ((a.ngroups + 7) / 8));
@@ -1389,8 +1389,8 @@ void dec_chain_backward(hipStream_t s, const DecClBwdArgs& a0) {
   const int groups = (a0.B + R - 1) / R, per_pass = std::max(8, cus / (8 * NM) * 8);
   (void)hipFuncSetAttribute((const void*)dec_ch_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CH_BWD_LDS);
   for (int g0 = 0; g0 < groups; g0 += per_pass) {
-    DecClBwdArgs a = a0; a.group0 = g0; a.ngroups = std::min(per_pass, groups - g0); a.force_remote = getenv("AOCR_CL_REMOTE") != nullptr;
-    a.stamps = getenv("AOCR_DC_STAMPS") ? a.xtab + (size_t)groups * NM + 16 : nullptr;
+    DecClBwdArgs a = a0; a.group0 = g0; a.ngroups = std::min(per_pass, groups - g0); a.force_remote = knob::AOCR_CL_REMOTE();
+    a.stamps = knob::AOCR_DC_STAMPS() ? a.xtab + (size_t)groups * NM + 16 : nullptr;
     hipLaunchKernelGGL(dec_ch_bwd_kernel, dim3(8 * NM * ((a.ngroups + 7) / 8)), dim3(256), (size_t)CH_BWD_LDS, s, a);
   }
 }

@@ -982,21 +982,21 @@ bool dec_cluster_supported(int Hd, int Ld, int input_feed, int T, int L, int cus
 size_t dec_cluster_bwd_xbuf_bytes(int B) { return (size_t)((B + R - 1) / R) * 5 * NM * 128 * sizeof(unsigned) + 256; }
 bool dec_cluster_bwd_supported(int Hd, int Ld, int input_feed, int T, int L, int cus) { return dec_cluster_supported(Hd, Ld, input_feed, T, L, cus) && L + 2 < 512; }
 void dec_cluster_backward(hipStream_t s, const DecClBwdArgs& a0) {
-  if (a0.drop_h.thr == 0 && a0.drop_out.thr == 0 && dec_chain_enabled() && !getenv("AOCR_NO_DEC_CHAINS_BWD")) { dec_chain_backward(s, a0); return; }      // round 5: two chains per group, tag-free exchange
+  if (a0.drop_h.thr == 0 && a0.drop_out.thr == 0 && dec_chain_enabled() && !knob::AOCR_NO_DEC_CHAINS_BWD()) { dec_chain_backward(s, a0); return; }      // round 5: two chains per group, tag-free exchange
   static const int cus = [] { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
   const int groups = (a0.B + R - 1) / R, per_pass = std::max(8, cus / (8 * NM) * 8);
   (void)hipFuncSetAttribute((const void*)dec_cl_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BWD_LDS_BYTES);
   (void)hipFuncSetAttribute((const void*)dec_cl_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BWD_LDS_BYTES);
   for (int g0 = 0; g0 < groups; g0 += per_pass) {
-    DecClBwdArgs a = a0; a.group0 = g0; a.ngroups = std::min(per_pass, groups - g0); a.force_remote = getenv("AOCR_CL_REMOTE") != nullptr;
-    a.stamps = getenv("AOCR_DC_STAMPS") ? a.xtab + (size_t)groups * NM + 16 : nullptr;   // debugging aid (-DDC_DEBUG_STAMPS): cycles per phase of workgroup 0
+    DecClBwdArgs a = a0; a.group0 = g0; a.ngroups = std::min(per_pass, groups - g0); a.force_remote = knob::AOCR_CL_REMOTE();
+    a.stamps = knob::AOCR_DC_STAMPS() ? a.xtab + (size_t)groups * NM + 16 : nullptr;   // debugging aid (-DDC_DEBUG_STAMPS): cycles per phase of workgroup 0
     if (a.drop_h.thr != 0 || a.drop_out.thr != 0) hipLaunchKernelGGL(dec_cl_bwd_kernel<true>, dim3(8 * NM * ((a.ngroups + 7) / 8)), dim3(256), (size_t)BWD_LDS_BYTES, s, a);
     else hipLaunchKernelGGL(dec_cl_bwd_kernel<false>, dim3(8 * NM * ((a.ngroups + 7) / 8)), dim3(256), (size_t)BWD_LDS_BYTES, s, a);
   }
 }
 
 void dec_cluster_forward(hipStream_t s, const DecClFwdArgs& a0, bool greedy_decode) {
-  if (a0.drop_h.thr == 0 && a0.drop_out.thr == 0 && dec_chain_enabled() && !(greedy_decode && getenv("AOCR_NO_DEC_CHAINS_GREEDY"))) { dec_chain_forward(s, a0, greedy_decode); return; }      // round 5: two chains per group, tag-free exchange
+  if (a0.drop_h.thr == 0 && a0.drop_out.thr == 0 && dec_chain_enabled() && !(greedy_decode && knob::AOCR_NO_DEC_CHAINS_GREEDY())) { dec_chain_forward(s, a0, greedy_decode); return; }      // round 5: two chains per group, tag-free exchange
   static const int cus = [] { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
   const int groups = (a0.B + R - 1) / R, per_pass = std::max(8, cus / (8 * NM) * 8);
   const size_t lds = LDS_BYTES;
@@ -1006,8 +1006,8 @@ void dec_cluster_forward(hipStream_t s, const DecClFwdArgs& a0, bool greedy_deco
   const bool hist = greedy_decode && a0.sc_hist;                   // aocr_recognize: the variant that keeps the score history
   if (hist) (void)hipFuncSetAttribute((const void*)dec_cl_fwd_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   for (int g0 = 0; g0 < groups; g0 += per_pass) {
-    DecClFwdArgs a = a0; a.group0 = g0; a.ngroups = std::min(per_pass, groups - g0); a.force_remote = getenv("AOCR_CL_REMOTE") != nullptr; a.no_early = getenv("AOCR_NO_DEC_EARLY") != nullptr;
-    a.stamps = getenv("AOCR_DC_STAMPS") ? a.xtab + (size_t)groups * NM : nullptr;   // debugging aid: cycles per phase of workgroup 0
+    DecClFwdArgs a = a0; a.group0 = g0; a.ngroups = std::min(per_pass, groups - g0); a.force_remote = knob::AOCR_CL_REMOTE(); a.no_early = knob::AOCR_NO_DEC_EARLY();
+    a.stamps = knob::AOCR_DC_STAMPS() ? a.xtab + (size_t)groups * NM : nullptr;   // debugging aid: cycles per phase of workgroup 0
     if (greedy_decode) {
       a.tokx = reinterpret_cast<unsigned*>(a.pbuf + (size_t)groups * 32 * 32 * 40);
       if (hist) hipLaunchKernelGGL((dec_cl_fwd_kernel<true, false, true>), dim3(8 * NM * ((a.ngroups + 7) / 8)), dim3(256), lds, s, a);

@@ -144,15 +144,8 @@ inline bool sync_bn_on(const aocr_model* m) { return m->comm.provider != 0 && m-
 // held behind the encoder BPTT, so no collective kernel is ever co-resident with a cluster kernel.  AOCR_COMM_EARLY_BUCKET0=1 releases it
 // as soon as the decoder's gradients are complete; the encoder cluster launches then keep comm_reserved_cus() compute units free for the
 // collective's workgroups (AOCR_COMM_RESERVE_CUS, default 32 = RCCL's channel count on an 8-GPU xGMI node).
-inline bool env_on(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }      // round-4 switches test the VALUE ("0" = off)
-inline bool comm_early_bucket0() { return env_on("AOCR_COMM_EARLY_BUCKET0"); }      // read per call, like every dispatch switch
-inline bool comm_holds_bucket0(const aocr_model* m) { return m->comm.provider != 0 && !comm_early_bucket0(); }
-inline int comm_reserved_cus(const aocr_model* m) {
-  if (m->comm.provider == 0 || !comm_early_bucket0()) return 0;
-  const char* e = getenv("AOCR_COMM_RESERVE_CUS");
-  const int n = e ? atoi(e) : 32;
-  return n < 0 ? 0 : (n > 128 ? 128 : n);
-}
+inline bool comm_holds_bucket0(const aocr_model* m) { return m->comm.provider != 0 && !knob::AOCR_COMM_EARLY_BUCKET0(); }
+inline int comm_reserved_cus(const aocr_model* m) { return (m->comm.provider == 0 || !knob::AOCR_COMM_EARLY_BUCKET0()) ? 0 : knob::AOCR_COMM_RESERVE_CUS(); }
 void prof_mark_slow(aocr_model* m, int tag);
 inline void prof_mark(aocr_model* m, int tag) { if (m->prof_on) prof_mark_slow(m, tag); }
 void step_prologue(aocr_model* m, size_t grad_bytes);              // start of a training step (capi.hip): gradient zeroing, weight shadows, token table

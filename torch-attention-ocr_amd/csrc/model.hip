@@ -349,7 +349,7 @@ void cnn_forward(aocr_model* m, const float* images, const Dims& d, int training
   if (m->shadow_pending) { hipStreamWaitEvent(s, m->shadow_done, 0); m->shadow_pending = false; }       // the rest of the table (conv3 .. conv7, the recurrent matrices): refreshed under conv2
   // evaluation mode, bf16: BatchNorm + ReLU of conv3 / conv5 are a per-channel affine map -> folded into the conv epilogue, which then writes only
   // the bf16 shadow (no fp32 map, no apply pass); conv7's BatchNorm also transposes to (T, B) and stays a pass of its own
-  const bool fold = bf && !training && !getenv("AOCR_NO_BN_FOLD");
+  const bool fold = bf && !training && !knob::AOCR_NO_BN_FOLD();
   if (fold) {
     prof_mark(m, AOCR_PROF_BN); bn_eval_prepare(s, m->bn[3].rm, m->bn[3].rv, m->bn[3].save, 256);
     prof_mark(m, AOCR_PROF_CONV_FWD); conv_forward(s, bf, m->A2, m->conv[3].w, m->conv[3].b, nullptr, nullptr, B, d.H2, d.W2, 128, 256, 3, 1, 0, 0, m->A2b, m->wb[3], m->A3b, 0,
@@ -383,7 +383,7 @@ void cnn_forward(aocr_model* m, const float* images, const Dims& d, int training
 // join in front of the CNN backward pass -- the filter gradients queue behind them on the same stream)
 static bool cnn_wgrad_on_side(aocr_model* m) {
   auto evok = [](hipEvent_t& e) { return e || hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess; };
-  return m->bf16 && m->G2b && !getenv("AOCR_DBG_STOP") && !m->prof_on && m->side && m->side_done && !getenv("AOCR_NO_SIDE_WGRAD") && !env_on("AOCR_NO_CNN_WGRAD_SIDE") &&
+  return m->bf16 && m->G2b && !knob::AOCR_DBG_STOP_SET() && !m->prof_on && m->side && m->side_done && !knob::AOCR_NO_SIDE_WGRAD() && !knob::AOCR_NO_CNN_WGRAD_SIDE() &&
          evok(m->cw_map[0]) && evok(m->cw_map[1]) && evok(m->cw_done[0]) && evok(m->cw_done[1]) && evok(m->cw_main);
 }
 
@@ -397,11 +397,10 @@ static void cnn_backward(aocr_model* m, const float* images, const Dims& d) {
   // gradient k and E_(k-1).  d Y alternates between two bf16 buffers so that E_(k-1) can write the next map while the filter gradient k still reads
   // its own; an event per buffer keeps E_(k-2) from overwriting it before that filter gradient is done.  AOCR_NO_CNN_WGRAD_SIDE=1: one stream.
   bf16_t* Gb[2] = {m->G0b, m->G2b}; int gp = 0;
-  const char* dbg_stop = getenv("AOCR_DBG_STOP");          // debugging aid: leave the gradient map of a stage in place (tap "g0")
-  const int stop = dbg_stop ? atoi(dbg_stop) : 0;
+  const int stop = knob::AOCR_DBG_STOP();                  // debugging aid: leave the gradient map of a stage in place (tap "g0")
   const bool ws = !stop && cnn_wgrad_on_side(m);
   hipStream_t sw = ws ? m->side : s;
-  const bool wg_after = ws && env_on("AOCR_CNN_WGRAD_AFTER_DGRAD");      // A/B: start the filter gradient of a stage behind its data gradient (beside the next elementwise pass only)
+  const bool wg_after = ws && knob::AOCR_CNN_WGRAD_AFTER_DGRAD();      // A/B: start the filter gradient of a stage behind its data gradient (beside the next elementwise pass only)
   if (!ws) Gb[1] = Gb[0];
   auto map_ready = [&]() { if (ws) { hipEventRecord(m->cw_map[gp], s); hipStreamWaitEvent(sw, m->cw_map[gp], 0); } };        // d Y_k (Gb[gp]) is complete: the side stream may read it
   auto wgrad_done = [&]() { if (ws) hipEventRecord(m->cw_done[gp], sw); };
@@ -413,7 +412,7 @@ static void cnn_backward(aocr_model* m, const float* images, const Dims& d) {
   // instead of eight dependent ~10 us dispatches
   constexpr size_t SLAB = (size_t)4 << 20;                      // floats per slab: >= 2048 x 1024 (BatchNorm), 4096 x 640 (conv1)
   ColsumJobs cj; cj.n = 0; cj.total = 0;
-  ColsumJobs* defer = (bf && m->gmax >= 8 * SLAB && !getenv("AOCR_NO_COLSUM_DEFER")) ? &cj : nullptr;
+  ColsumJobs* defer = (bf && m->gmax >= 8 * SLAB && !knob::AOCR_NO_COLSUM_DEFER()) ? &cj : nullptr;
   auto slab = [&](int k) { return defer ? G0 + (size_t)k * SLAB : G0; };
   // bn7 + relu (dX is time-major, Y7 batch-major)
   // bf16 mode: the BatchNorm backward writes only the bf16 shadow of its gradient, takes the ReLU mask from the bf16 output
@@ -453,7 +452,7 @@ static void cnn_backward(aocr_model* m, const float* images, const Dims& d) {
     if (wg_after) { D(); map_ready(); W(); wgrad_done(); } else { map_ready(); W(); wgrad_done(); D(); } }
   prof_mark(m, AOCR_PROF_POOL_CONV1); conv1_backward(s, images, m->conv[1].w, m->conv[1].b, G1, m->conv[1].dw, m->conv[1].db, B, d.H, d.W,
                  (size_t)B * d.H1 * d.W1 * 128 >= (size_t)4096 * 640 ? slab(6) : nullptr, defer,      // G0 is free here: use it as the partial slab
-                 m->route1_valid && !getenv("AOCR_CONV1_RECOMPUTE") ? m->route1 : nullptr);
+                 m->route1_valid && !knob::AOCR_CONV1_RECOMPUTE() ? m->route1 : nullptr);
   if (defer) colsum_flush(s, cj);                               // conv4.b, conv3.b, conv2.b, conv1.w, conv1.b
   if (ws) { hipEventRecord(m->side_done, sw); hipStreamWaitEvent(s, m->side_done, 0); }
 }
@@ -466,8 +465,7 @@ static void cnn_backward(aocr_model* m, const float* images, const Dims& d) {
 // workgroup; AOCR_NO_SEQ=1 forces the per-step kernels (parity tests compare the two).
 static bool seq_kernels_ok(const aocr_model* m, int B) {
   if (!m->bf16 || !m->ehs_b[0][0] || !m->enc[0][0].swh.wb) return false;
-  const char* e = getenv("AOCR_NO_SEQ");
-  if (e && e[0] == '1') return false;
+  if (knob::AOCR_NO_SEQ()) return false;
   static const int cus = [] { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
   return enc_seq_supported(B, m->He, cus);
 }
@@ -476,10 +474,7 @@ static bool seq_kernels_ok(const aocr_model* m, int B) {
 // the one-workgroup-per-16-rows kernels / the per-step kernels (parity tests compare the paths).
 static bool cluster_ok(const aocr_model* m, int B, int T, int& G, int& RT, int& groups) {
   if (!m->bf16 || !m->cl_xbuf || !m->ehs_b[0][0] || !m->enc[0][0].swh.wb || !m->edz_b[0][0]) return false;
-  const char* e = getenv("AOCR_NO_CLUSTER");
-  if (e && e[0] == '1') return false;
-  e = getenv("AOCR_NO_SEQ");                              // "no whole-sequence kernels at all": the per-step launch chain
-  if (e && e[0] == '1') return false;
+  if (knob::AOCR_NO_CLUSTER() || knob::AOCR_NO_SEQ()) return false;      // (NO_SEQ: "no whole-sequence kernels at all": the per-step launch chain)
   static const int cus = [] { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
   return enc_cluster_plan(B, m->He, T, cus - comm_reserved_cus(m), G, RT, groups);
 }
@@ -510,11 +505,11 @@ static DropSpec drop_site(const aocr_model* m, int site, long long off) {
 // Off under the family profile (prof_on: one stream), AOCR_NO_LAYER_PIPE=1, or when the layers' groups do not fit the chip at once.
 // AOCR_LAYER_PIPE_CHUNKS=n forces the chunk count (tests: short sequences).
 static int layer_pipe_chunks(const aocr_model* m, int T, int G, int groups) {
-  if (m->Le < 2 || m->prof_on || getenv("AOCR_NO_LAYER_PIPE")) return 0;
+  if (m->Le < 2 || m->prof_on || knob::AOCR_NO_LAYER_PIPE()) return 0;
   static const int cus = [] { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
   if (2 * groups * G * m->Le > cus) return 0;
   int C = std::min(8, T / 48);
-  if (const char* e = getenv("AOCR_LAYER_PIPE_CHUNKS")) C = std::min(atoi(e), T);
+  if (const char* e = knob::AOCR_LAYER_PIPE_CHUNKS()) C = std::min(atoi(e), T);
   return C >= 2 ? C : 0;
 }
 static bool layer_pipe_streams(aocr_model* m, int n_events) {
@@ -594,7 +589,7 @@ void encoder_forward(aocr_model* m, const Dims& d) {
   const bool cluster = cluster_ok(m, B, T, clG, clRT, clGroups);
   const int pipeC = cluster ? layer_pipe_chunks(m, T, clG, clGroups) : 0;
   if (pipeC && layer_pipe_streams(m, (m->Le + 1) * pipeC + m->Le + 1)) {
-    if (getenv("AOCR_TRACE")) fprintf(stderr, "[aocr] encoder forward: cluster kernels, layer wavefront of %d chunks\n", pipeC);
+    if (knob::AOCR_TRACE()) fprintf(stderr, "[aocr] encoder forward: cluster kernels, layer wavefront of %d chunks\n", pipeC);
     encoder_forward_pipe(m, d, pipeC, clG, clRT, clGroups);
     if (m->context_b) copy2d_bf16(s, m->context, Hd, m->context_b, Hd, B * T, Hd);
     return;
@@ -628,7 +623,7 @@ void encoder_forward(aocr_model* m, const Dims& d) {
     zero_many(s, zl);
     prof_mark(m, AOCR_PROF_ENC_SEQ);
     const bool top = l == m->Le - 1;
-    if (getenv("AOCR_TRACE")) fprintf(stderr, "[aocr] encoder layer %d forward: %s kernels\n", l, cluster ? "cluster" : seq_kernels_ok(m, B) ? "whole-sequence" : "per-step");
+    if (knob::AOCR_TRACE()) fprintf(stderr, "[aocr] encoder layer %d forward: %s kernels\n", l, cluster ? "cluster" : seq_kernels_ok(m, B) ? "whole-sequence" : "per-step");
     if (cluster) {                                        // groups of He/64 CUs, recurrent weights resident in registers
       EncClFwdArgs a; a.B = B; a.T = T; a.He = He; a.Hd = Hd; a.groups = clGroups; a.epoch = next_epoch(m); a.xbuf = m->cl_xbuf; a.err = m->cl_err; a.xtab = m->cl_xtab;
       for (int dir = 0; dir < 2; ++dir) {
@@ -757,7 +752,7 @@ static void encoder_backward(aocr_model* m, const Dims& d) {
     for (int l = 0; l < m->Le && cluster; ++l) cluster = m->edz_b[0][l] && m->enc[0][l].swh.wtb && m->enc[0][l].swi.wtb;
     const int pipeC = cluster ? layer_pipe_chunks(m, T, clG, clGroups) : 0;
     if (pipeC && layer_pipe_streams(m, (m->Le + 1) * pipeC + m->Le + 1)) {
-      if (getenv("AOCR_TRACE")) fprintf(stderr, "[aocr] encoder backward: cluster kernels, layer wavefront of %d chunks\n", pipeC);
+      if (knob::AOCR_TRACE()) fprintf(stderr, "[aocr] encoder backward: cluster kernels, layer wavefront of %d chunks\n", pipeC);
       encoder_backward_pipe(m, d, pipeC, clG, clRT, clGroups);
       return;
     }
@@ -767,11 +762,11 @@ static void encoder_backward(aocr_model* m, const Dims& d) {
     prof_mark(m, AOCR_PROF_ENC_SEQ);
     int clG = 0, clRT = 0, clGroups = 0;
     const bool cluster = cluster_ok(m, B, T, clG, clRT, clGroups) && m->edz_b[0][l] && m->enc[0][l].swh.wtb;
-    const bool dc_direct = top && cluster && !env_on("AOCR_ENC_DC_COPY");      // the cluster kernel reads the halves of the decoder's initial-state gradient in place (one 9 us launch off the main stream's critical chain)
+    const bool dc_direct = top && cluster && !knob::AOCR_ENC_DC_COPY();      // the cluster kernel reads the halves of the decoder's initial-state gradient in place (one 9 us launch off the main stream's critical chain)
     if (top && !dc_direct) copy2d_pair(s, m->dc_st[0], m->dc_st[0] + He, Hd, m->edc[0][l], m->edc[1][l], He, B, He);        // model.lua:666,680 (both directions in one launch)
     else if (!top) for (int dir = 0; dir < 2; ++dir) hipMemsetAsync(m->edc[dir][l], 0, slot * sizeof(float), s);
     const bool seq = cluster || (seq_kernels_ok(m, B) && m->edz_b[0][l] && m->enc[0][l].swh.wtb);
-    if (getenv("AOCR_TRACE")) fprintf(stderr, "[aocr] encoder layer %d backward: %s kernels\n", l, cluster ? "cluster" : seq ? "whole-sequence" : "per-step");
+    if (knob::AOCR_TRACE()) fprintf(stderr, "[aocr] encoder layer %d backward: %s kernels\n", l, cluster ? "cluster" : seq ? "whole-sequence" : "per-step");
     if (cluster) {
       EncClBwdArgs a; a.B = B; a.T = T; a.He = He; a.groups = clGroups; a.epoch = next_epoch(m); a.pbuf = m->cl_pbuf; a.err = m->cl_err; a.xtab = m->cl_xtab;
       for (int dir = 0; dir < 2; ++dir) {
@@ -826,7 +821,7 @@ static void encoder_backward(aocr_model* m, const Dims& d) {
     // round 4: the layer's weight gradients join the decoder's on the side stream (nothing reads them before the optimizer), behind an event that
     // marks the end of this layer's BPTT: 0.11 ms off the main stream at C3, where they ran between d X and the CNN backward pass
     bool wg_side = false;
-    if (m->side_busy && m->side && !env_on("AOCR_NO_ENC_WGRAD_SIDE")) {
+    if (m->side_busy && m->side && !knob::AOCR_NO_ENC_WGRAD_SIDE()) {
       if (!m->enc_ev && hipEventCreateWithFlags(&m->enc_ev, hipEventDisableTiming) != hipSuccess) m->enc_ev = nullptr;
       if (m->enc_ev) { hipEventRecord(m->enc_ev, s); wg_side = true; }
     }
@@ -947,16 +942,14 @@ static void dec_init_state(aocr_model* m, const Dims& d, float* const* c0, float
 // He = 256); AOCR_NO_DEC_CLUSTER=1 keeps the per-step launch chain (parity tests compare the two).
 static bool dec_cluster_ok(const aocr_model* m, int T, int L) {
   if (!m->bf16 || !m->dc_xbuf || !m->ctxa_b || !m->dec[0].swi.wb || !m->swa.wtb || !m->swc.wb) return false;
-  const char* e = getenv("AOCR_NO_DEC_CLUSTER");
-  if (e && e[0] == '1') return false;
+  if (knob::AOCR_NO_DEC_CLUSTER()) return false;
   static const int cus = [] { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
   return dec_cluster_supported(m->Hd, m->Ld, m->cfg.input_feed, T, L, cus);
 }
 
 static bool dec_cluster_bwd_ok(const aocr_model* m, int T, int L) {
   if (!m->dc_bxbuf || !m->dpre_b || !m->dq_b || !m->ddz_b[0] || !m->dec[0].swi.wtb || !m->swc.wtb) return false;
-  const char* e = getenv("AOCR_NO_DEC_CLUSTER_BWD");
-  if (e && e[0] == '1') return false;
+  if (knob::AOCR_NO_DEC_CLUSTER_BWD()) return false;
   static const int cus = [] { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
   return dec_cluster_bwd_supported(m->Hd, m->Ld, m->cfg.input_feed, T, L, cus);
 }
@@ -972,7 +965,7 @@ void decoder_tf_forward(aocr_model* m, const Dims& d, const int32_t* tgt, int64_
   const LstmP& p1 = m->dec[0];
   const bool sh = m->bf16 && m->out_b != nullptr;
   const bool drop = keep_gates && m->drop_on;                       // training only
-  const bool drop_cl = drop && m->dhm_b[0] && !getenv("AOCR_NO_DEC_CLUSTER_DROP");     // round 3: the cluster kernels evaluate the masks themselves
+  const bool drop_cl = drop && m->dhm_b[0] && !knob::AOCR_NO_DEC_CLUSTER_DROP();     // round 3: the cluster kernels evaluate the masks themselves
   const bool use_cl = sh && (!drop || drop_cl) && dec_cluster_ok(m, T, L);
   // Round 4: the embedding part of the first layer's gate input depends on the token only (nn.LookupTable -> W_i2h[:, :E], LSTM.lua:55-56,79-80).
   // The whole-sequence kernel reads it from the per-token table [V][4 Hd] (what the decode path already does) instead of a (L B, 4 Hd) tensor
@@ -980,7 +973,7 @@ void decoder_tf_forward(aocr_model* m, const Dims& d, const int32_t* tgt, int64_
   // and 50 MB less written and read per step.  The backward pass follows (decoder_backward: sums of d z by token).  AOCR_NO_EMB_TABLE=1: the tensor.
   // Round 6: the launch chain of bf16 mode takes the table too (its gate epilogue gathers the token's row, as the decode path always did): at the reference-default
   // shape the (L B, 4 Hd) tensor was a 157 MB product in front of the loop and a K = 4 Hd -> E product + scatter behind it (87 + 99 us of a 8.3 ms step).
-  m->emb_table = (use_cl || (sh && !env_on("AOCR_NO_EMB_TABLE_CHAIN"))) && segsum_supported(4 * Hd, m->V, E) && !env_on("AOCR_NO_EMB_TABLE");
+  m->emb_table = (use_cl || (sh && !knob::AOCR_NO_EMB_TABLE_CHAIN())) && segsum_supported(4 * Hd, m->V, E) && !knob::AOCR_NO_EMB_TABLE();
   if (m->tab_ready) { hipStreamWaitEvent(s, m->tab_done, 0); m->tab_ready = false; m->tab_valid = true; }       // step_prologue of this call (joined even when unused: the decode path writes the same buffer)
   if (m->emb_table) { if (!m->tab_valid) { gemm(s, bf, m->lookup, E, true, p1.wi, p1.in, true, m->bzx_tab, 4 * Hd, m->V, 4 * Hd, E, p1.bi, p1.bh, 0); m->tab_valid = true; } }      // (tab_valid: this API call already has the table -- the beam pass in front of a gold pass)
   else {
@@ -1010,7 +1003,7 @@ void decoder_tf_forward(aocr_model* m, const Dims& d, const int32_t* tgt, int64_
       // round 5: on the side stream, beside the projector / loss / d logits launches that follow (small grids: 85 us of mostly idle chip between the two
       // whole-sequence kernels at C3), joined in front of attention_dctx -- 21 us off the main stream
       auto ev = [](hipEvent_t& e) { return e || hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess; };
-      if (!m->prof_on && !getenv("AOCR_NO_SIDE_WGRAD") && !env_on("AOCR_NO_Q_SIDE") && side_create(m) && ev(m->q_go) && ev(m->q_done)) {
+      if (!m->prof_on && !knob::AOCR_NO_SIDE_WGRAD() && !knob::AOCR_NO_Q_SIDE() && side_create(m) && ev(m->q_go) && ev(m->q_done)) {
         hipEventRecord(m->q_go, s); hipStreamWaitEvent(m->side, m->q_go, 0);
         gemm_hh(m->side, m->dhs_b[1] + slot, Hd, m->swa.wb, Hd, m->q_all, Hd, L * B, Hd, Hd, nullptr, nullptr, 0);
         hipEventRecord(m->q_done, m->side); m->q_pending = true;
@@ -1079,7 +1072,7 @@ void loss_and_dlogits(aocr_model* m, const Dims& d, const int32_t* tge, int64_t 
 static bool side_create(aocr_model* m);
 // the side stream of the backward pass (created on first use, lowest priority) -- AOCR_NO_SIDE_WGRAD=1 keeps everything on one stream
 static bool side_stream_on(aocr_model* m, int B, int T) {
-  if (m->prof_on || !m->bf16 || getenv("AOCR_NO_SIDE_WGRAD")) return false;
+  if (m->prof_on || !m->bf16 || knob::AOCR_NO_SIDE_WGRAD()) return false;
   // The encoder BPTT cluster kernel needs every workgroup of a group resident at once; beside it the side stream's GEMM workgroups
   // must find free compute units, or they delay the group members that are placed last (bounded spins, aocr_cluster_status).
   // C3: 16 groups x 2 directions x 4 members = 128 of 256 units -> on.  He = 512 at batch 400: 256 workgroups per pass -> off.
@@ -1099,7 +1092,7 @@ static bool side_stream_on(aocr_model* m, int B, int T) {
 static bool side_create(aocr_model* m) {
   if (!m->side) {
     int lo = 0, hi = 0; hipDeviceGetStreamPriorityRange(&lo, &hi);            // lo = numerically greatest = lowest priority
-    const hipError_t e = getenv("AOCR_SIDE_PLAIN") ? hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking) : hipStreamCreateWithPriority(&m->side, hipStreamNonBlocking, lo);
+    const hipError_t e = knob::AOCR_SIDE_PLAIN() ? hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking) : hipStreamCreateWithPriority(&m->side, hipStreamNonBlocking, lo);
     if (e != hipSuccess) { m->side = nullptr; return false; }
     if (hipEventCreateWithFlags(&m->side_go, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&m->side_done, hipEventDisableTiming) != hipSuccess) return false;
     if (hipStreamCreateWithPriority(&m->side2, hipStreamNonBlocking, lo) != hipSuccess) m->side2 = nullptr;      // optional (decoder_backward)
@@ -1118,7 +1111,7 @@ void step_prologue(aocr_model* m, size_t grad_bytes) {             // grad_bytes
   // (bf16 mode only: in exact-fp32 mode the same move -- gradient zeroing and the 16 per-step weight transposes beside the forward pass -- measured SLOWER, C2 7.52 -> 7.74 ms:
   //  the forward pass there is a chain of ~150 small dependent launches, and the side stream's launches get in their way)
   const int bn_n = 2 * (256 + 512 + 512);
-  const bool side = m->bf16 && !m->prof_on && !getenv("AOCR_NO_SIDE_WGRAD") && !env_on("AOCR_NO_SIDE_PROLOGUE") && side_create(m) && ev(m->zero_done) && ev(m->shadow_done) && ev(m->tab_done);
+  const bool side = m->bf16 && !m->prof_on && !knob::AOCR_NO_SIDE_WGRAD() && !knob::AOCR_NO_SIDE_PROLOGUE() && side_create(m) && ev(m->zero_done) && ev(m->shadow_done) && ev(m->tab_done);
   if (!side) {
     if (grad_bytes) { hipMemsetAsync(m->grads, 0, grad_bytes, m->s); if (m->bn_snap) step_snapshot(m->s, m->bn_state, m->bn_snap, bn_n, m->cl_err); }
     return;
@@ -1128,7 +1121,7 @@ void step_prologue(aocr_model* m, size_t grad_bytes) {             // grad_bytes
   if (!m->shadow_host.empty()) {
     // conv2's taps first, with an event of their own: conv2 starts as soon as conv1 is done (the rest of the table -- 100 MB of traffic -- runs under conv2
     // and is joined in front of conv3): 25 us off the head of the step at C3, where conv2 waited for the whole table and the cross-stream hand-over
-    const bool split = m->shadow_tiles_conv2 > 0 && ev(m->shadow2_done) && !env_on("AOCR_NO_SHADOW_SPLIT");
+    const bool split = m->shadow_tiles_conv2 > 0 && ev(m->shadow2_done) && !knob::AOCR_NO_SHADOW_SPLIT();
     if (split) {
       shadow_jobs(m->side, m->shadow_dev, (int)m->shadow_host.size(), m->shadow_tiles_conv2, 0);
       hipEventRecord(m->shadow2_done, m->side);
@@ -1139,7 +1132,7 @@ void step_prologue(aocr_model* m, size_t grad_bytes) {             // grad_bytes
     hipEventRecord(m->shadow_done, m->side); m->shadow_pending = true; m->shadow2_pending = split;
   }
   if (grad_bytes) { hipMemsetAsync(m->grads, 0, grad_bytes, m->side); hipEventRecord(m->zero_done, m->side); m->zero_pending = true; }
-  if (m->bzx_tab && !env_on("AOCR_NO_EMB_TABLE") && segsum_supported(4 * m->Hd, m->V, m->E)) {
+  if (m->bzx_tab && !knob::AOCR_NO_EMB_TABLE() && segsum_supported(4 * m->Hd, m->V, m->E)) {
     const LstmP& p1 = m->dec[0];
     gemm(m->side, true, m->lookup, m->E, true, p1.wi, p1.in, true, m->bzx_tab, 4 * m->Hd, m->V, 4 * m->Hd, m->E, p1.bi, p1.bh, 0);
     hipEventRecord(m->tab_done, m->side);
@@ -1261,7 +1254,7 @@ static void decoder_backward(aocr_model* m, const Dims& d, const int32_t* tgt) {
   // during which the chip is mostly idle), not behind them -- the side streams were the critical path of this section (the main stream idled ~70 us at
   // the join in front of the CNN backward pass).  The first side-stream kernels are small (token sums, the projector's 96-workgroup product): the encoder
   // BPTT kernel still finds its compute units when it starts.  AOCR_SIDE_GO_LATE=1: the old place.
-  const bool side_on = side_stream_on(m, B, T), side_early = side_on && !env_on("AOCR_SIDE_GO_LATE");
+  const bool side_on = side_stream_on(m, B, T), side_early = side_on && !knob::AOCR_SIDE_GO_LATE();
   if (side_early) hipEventRecord(m->side_go, s);
   if (m->loss_pending && !side_early) { sum_to_scalar(s, m->nll_rows, (int64_t)L * B, m->loss_pending); m->loss_pending = nullptr; }      // the step's loss (loss_and_dlogits): behind the BPTT, in front of every event the exchange waits for (side streams released early: on the side stream below, off the chain the encoder BPTT waits for)
   if (m->q_pending) { hipStreamWaitEvent(s, m->q_done, 0); m->q_pending = false; }          // q of all steps (decoder_tf_forward put the product on the side stream)
@@ -1281,7 +1274,7 @@ static void decoder_backward(aocr_model* m, const Dims& d, const int32_t* tgt) {
   // gradients on the side stream too, that stream had become the critical path (the main stream idled ~120 us at the join).  It rejoins the first side
   // stream at the end of this function, so "the side stream is done" still means "every hoisted gradient is done".
   hipStream_t s2 = s;
-  if (m->side_busy && m->side2 && m->side2_done && !env_on("AOCR_NO_SIDE2")) { s2 = m->side2; hipStreamWaitEvent(s2, m->side_go, 0); }
+  if (m->side_busy && m->side2 && m->side2_done && !knob::AOCR_NO_SIDE2()) { s2 = m->side2; hipStreamWaitEvent(s2, m->side_go, 0); }
   gemm(s2, bf, m->dlogits, LOGIT_LD, false, m->out_all + slot, Hd, false, m->dwo, Hd, V, Hd, rows, nullptr, nullptr, EP_ATOMIC);
   const float* h_top_all = m->dhs[Ld - 1] + slot;
   WGradProblem wg[16]; int nwg = 0;
@@ -1339,7 +1332,7 @@ void backward_all(aocr_model* m, const float* images, const int32_t* tgt, const 
   // product + its slab sums at C3) start only when the BPTT kernel ends, so the main stream -- 50 us of d X -- idled ~90 us at the join; now BatchNorm 7's
   // backward pass and conv7's data gradient run beside them, the side stream's first filter gradient queues behind them (it shares their slab scratch: same
   // stream, in order), and cnn_backward's own join at its end covers both.  AOCR_JOIN_BEFORE_CNN_BWD=1: the join.
-  const bool through = m->side_busy && cnn_wgrad_on_side(m) && !env_on("AOCR_JOIN_BEFORE_CNN_BWD");
+  const bool through = m->side_busy && cnn_wgrad_on_side(m) && !knob::AOCR_JOIN_BEFORE_CNN_BWD();
   if (through) {                                                // the bucket events: behind both streams, recorded on the side stream
     hipEventRecord(m->cw_main, m->s); hipStreamWaitEvent(m->side, m->cw_main, 0);
     if (hold0) hipEventRecord(m->grad_ev[0], m->side);
@@ -1369,7 +1362,7 @@ void decode_beam(aocr_model* m, const Dims& d, const int32_t* tgt, int beam, int
   // (lookup W_i2h[:, :E]^T + both biases, LSTM.lua:55-56,79-80), gathered per step instead of a K = 20 GEMM per step.
   if (m->tab_ready) { hipStreamWaitEvent(s, m->tab_done, 0); m->tab_ready = false; m->tab_valid = true; }       // step_prologue of this decode call computed it on the side stream
   if (!m->tab_valid) { gemm(s, bf, m->lookup, E, true, p1.wi, p1.in, true, m->bzx_tab, 4 * Hd, V, 4 * Hd, E, p1.bi, p1.bh, 0); m->tab_valid = true; }
-  if (k == 1 && V <= 40 && m->out_b && m->dc_pbuf && !getenv("AOCR_NO_DEC_GREEDY") && dec_cluster_ok(m, T, Lt)) {
+  if (k == 1 && V <= 40 && m->out_b && m->dc_pbuf && !knob::AOCR_NO_DEC_GREEDY() && dec_cluster_ok(m, T, Lt)) {
     // greedy decode: the whole loop (cell, attention, projector, LogSoftMax, selection) as one launch of the decoder cluster kernel
     float* tc0[MAXL]; float* th0[MAXL];
     for (int l = 0; l < Ld; ++l) { tc0[l] = m->dcs[l]; th0[l] = m->dhs[l]; }
@@ -1415,7 +1408,7 @@ void decode_beam(aocr_model* m, const Dims& d, const int32_t* tgt, int beam, int
   // Round 6: in bf16 mode the chain keeps bf16 shadows of its beam state (the gate / attention epilogues write them, the gather by parent converts), so its step
   // products read both operands from shadows -- the kernels of the training chain (from ~130 rows stepl.h; at Hd = 1024 and T <= 64 scores against ctx W_a) instead
   // of the fp32-activation forms.  The products round the same fp32 values to bf16 either way.  AOCR_NO_DECODE_SHADOWS=1: off
-  const bool dsh = m->bf16 && m->bcat_b && !env_on("AOCR_NO_DECODE_SHADOWS");
+  const bool dsh = m->bf16 && m->bcat_b && !knob::AOCR_NO_DECODE_SHADOWS();
   const bool dctxa = dsh && m->ctxa_b && m->swa.wtb && attention_dual_ok(T, Hd, m->context_b, m->ctxa_b);
   if (dctxa) { if (!m->ctxa_fresh) gemm_hh_shadow(s, m->context_b, Hd, m->swa.wtb, Hd, m->dctx, Hd, m->ctxa_b, Hd, B * T, Hd, Hd); m->ctxa_fresh = true; }      // (the gold pass of this call scores against the same context)
   dec_init_state(m, d, c0, h0, m->bfeed[0], B, false, dsh ? m->bh_b[0] : nullptr, dsh ? m->bfeed_b[0] : nullptr);      // the launch chain's beam buffers (the greedy cluster kernel above has its own: not initialised for nothing)

@@ -5,6 +5,7 @@
 #include "aocr.h"
 #include "epilogues.h"
 #include "mfma_gemm.h"
+#include "knobs.h"
 
 namespace aocr {
 
@@ -122,6 +123,8 @@ void conv_backward_data(hipStream_t s, bool bf16, const float* dy, const float* 
                         int Cout, int ks, int pad, const bf16_t* dyb = nullptr, const bf16_t* wtb = nullptr, const float* wtf = nullptr,
                         int* dx16 = nullptr /* the caller accepts dx written as bf16 into the first half of the same buffer; *dx16 = 1 when that happened */,
                         const struct BnBwdFuse* bnb = nullptr, int* bnb_chunks = nullptr /* the BatchNorm backward behind this data gradient: its partial sums from the conv epilogue; *bnb_chunks = row tiles written (pass to bn_relu_backward as sums_chunks), 0 = not taken */);
+// what conv_backward_data puts in *dx16 for this shape in bf16 mode (shadows supplied, dx16 accepted) under the switches as they are now: aocr_profile_kernel asks the launcher's own predicate
+bool conv_dgrad_bf16_out(int B, int H, int W, int Cin, int Cout, int ks, int pad);
 void conv_backward_filter(hipStream_t s, bool bf16, const float* x, const float* dy, float* dw, float* dbias, int B, int H,
                           int W, int Cin, int Cout, int ks, int pad, const bf16_t* xb = nullptr, const bf16_t* dyb = nullptr,
                           float* part = nullptr, size_t part_floats = 0, int profile_tag = 0);   // part: scratch for the split-K slabs (else fp32 atomics)

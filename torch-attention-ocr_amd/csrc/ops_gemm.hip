@@ -17,12 +17,12 @@ static void split_k(int K, int chunk, int& ksplit, int& kper) {
 static thread_local const char* t_trace_fn = nullptr;
 struct TraceScope { explicit TraceScope(const char* fn) { t_trace_fn = fn; } ~TraceScope() { t_trace_fn = nullptr; } };
 static void trace_launch(const char* kernel, const char* inst, long long M, long long N, long long K) {
-  if (t_trace_fn && getenv("AOCR_TRACE")) fprintf(stderr, "[aocr] %s: %s[%s] %lld %lld %lld\n", t_trace_fn, kernel, inst, M, N, K);
+  if (t_trace_fn && knob::AOCR_TRACE()) fprintf(stderr, "[aocr] %s: %s[%s] %lld %lld %lld\n", t_trace_fn, kernel, inst, M, N, K);
 }
 // the recurrent-step launchers' line: the instantiation names the template arguments that differ between their branches -- NT, the GATES kind (0 plain, 1 gate
 // tiles, 2 half gate tiles), waves and, for two row tiles per workgroup, "mt2": gemm_step_kernel[2,2,w8], gemm_step_kernel[4,1,w4,mt2]
 static void trace_step(int nt, int gates, int waves, int mt, long long M, long long N, long long K) {
-  if (!t_trace_fn || !getenv("AOCR_TRACE")) return;
+  if (!t_trace_fn || !knob::AOCR_TRACE()) return;
   char inst[32]; snprintf(inst, sizeof inst, "%d,%d,w%d%s", nt, gates, waves, mt == 2 ? ",mt2" : "");
   trace_launch("gemm_step_kernel", inst, M, N, K);
 }
@@ -42,27 +42,21 @@ static const bf16_t* zero_page() {
   static const bf16_t* z = [] { void* p = nullptr; (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_zero_page)); return (const bf16_t*)p; }();
   return z;
 }
-static bool env_is_0(const char* name) { const char* e = getenv(name); return e && e[0] == '0'; }
-static bool env_is_1(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }      // switches are read per call; "0" means off
-static int wgrad_halo_min_n() { const char* e = getenv("AOCR_WGRAD_HALO_MINN"); return e ? atoi(e) : 576; }       // smallest N = 9 Cin that takes conv_wgrad_halo_kernel: conv2 (64 -> 128) upwards; A/B at C3: 2304 -> 1152 (conv3 too) = 5.505 -> 5.455 ms per step, 1152 -> 576 (conv2 too, 128-channel tiles): see DESIGN.md (AOCR_WGRAD_HALO_MINN)
-static bool dma_forced() { const char* e = getenv("AOCR_FORCE_DMA"); return e && e[0] == '1'; }     // read per call: tests toggle it
-static bool dma_disabled() { const char* e = getenv("AOCR_NO_DMA"); return e && e[0] == '1'; }       // tests: compare against the 128 x 128 kernels
 static bool dma_eligible(int M, int N, int K, int C) {
-  if (N % 256 || K % 32 || C % 32 || M < 256 || dma_disabled()) return false;
-  if (dma_forced()) return true;
+  if (N % 256 || K % 32 || C % 32 || M < 256 || knob::AOCR_NO_DMA()) return false;
+  if (knob::AOCR_FORCE_DMA()) return true;
   const int blocks = cdiv(M, 256) * (N / 256), rounds = cdiv(blocks, 256);
   return blocks >= 200 && blocks * 10 >= rounds * 256 * 8;          // >= 80 % of the CU-rounds it occupies
 }
 // narrow variant: N = 128 or 64 (two workgroups per CU)
 static bool dma_narrow_eligible(int M, int N, int K, int C) {
-  if ((N != 128 && N != 64) || K % 32 || C % 32 || M < 256 || dma_disabled()) return false;
-  return dma_forced() || cdiv(M, 256) >= 400;
+  if ((N != 128 && N != 64) || K % 32 || C % 32 || M < 256 || knob::AOCR_NO_DMA()) return false;
+  return knob::AOCR_FORCE_DMA() || cdiv(M, 256) >= 400;
 }
 template <class AL, class BL, class EP>
 static void launch_dma_narrow(hipStream_t s, const AL& a, const BL& b, const EP& ep, int M, int N, int K) {
   const int gy = cdiv(M, 256);
-  const char* const ns = getenv("AOCR_NO_NARROW_STAGED");  // A/B and parity: the quad epilogue (read per call)
-  const int staged = !(ns && ns[0] == '1');
+  const int staged = !knob::AOCR_NO_NARROW_STAGED();       // A/B and parity: the quad epilogue
   trace_launch("gemm_dma_narrow_kernel", N % 128 == 0 ? "2" : "1", M, N, K);
   if (N % 128 == 0) { const int gx = N / 128; hipLaunchKernelGGL((gemm_dma_narrow_kernel<AL, BL, EP, 2>), dim3(gx * gy), dim3(512), 0, s, a, b, ep, K, gx, gy, zero_page(), staged); }   // (N > 128: column blocks of 128)
   else          hipLaunchKernelGGL((gemm_dma_narrow_kernel<AL, BL, EP, 1>), dim3(gy), dim3(512), 0, s, a, b, ep, K, 1, gy, zero_page(), staged);
@@ -70,40 +64,39 @@ static void launch_dma_narrow(hipStream_t s, const AL& a, const BL& b, const EP&
 // 128 x 128 tiles on the LDS-DMA ring (gemm_dma128_kernel): every bf16 K-contiguous pair the larger LDS-DMA kernels do not take (small / ragged M).
 // AOCR_NO_DMA128=1: the register-staged 128 x 128 kernel (the parity reference: same k order, bit-identical)
 static bool dma128_eligible(int M, int N, int K, int C) {
-  if (N % 128 || K % 32 || C % 32 || M < 1 || dma_disabled()) return false;
-  const char* e = getenv("AOCR_NO_DMA128");
-  return !(e && e[0] == '1');
+  return !(N % 128 || K % 32 || C % 32 || M < 1 || knob::AOCR_NO_DMA()) && !knob::AOCR_NO_DMA128();
 }
 template <class AL, class BL, class EP>
 static void launch_dma128(hipStream_t s, const AL& a, const BL& b, const EP& ep, int M, int N, int K) {
   const int gx = N / 128, gy = cdiv(M, 128);
   // <= one workgroup per compute unit: a deep ring (7 tiles in flight) is all the latency hiding that workgroup has; otherwise two workgroups of 3 tiles in flight
   static const int cus = [] { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
-  const char* const w4 = getenv("AOCR_DMA128_W4");         // A/B: the 4-wave form at every grid size
-  trace_launch("gemm_dma128_kernel", gx * gy > cus ? "4,4" : (w4 && w4[0] == '1') ? "8,4" : "8,8", M, N, K);
-  if (gx * gy <= cus && !(w4 && w4[0] == '1')) hipLaunchKernelGGL((gemm_dma128_kernel<AL, BL, EP, 8, 8>), dim3(gx * gy), dim3(512), 0, s, a, b, ep, K, gx, gy, zero_page());
+  const bool w4 = knob::AOCR_DMA128_W4();                  // A/B: the 4-wave form at every grid size
+  trace_launch("gemm_dma128_kernel", gx * gy > cus ? "4,4" : w4 ? "8,4" : "8,8", M, N, K);
+  if (gx * gy <= cus && !w4) hipLaunchKernelGGL((gemm_dma128_kernel<AL, BL, EP, 8, 8>), dim3(gx * gy), dim3(512), 0, s, a, b, ep, K, gx, gy, zero_page());
   else if (gx * gy <= cus) hipLaunchKernelGGL((gemm_dma128_kernel<AL, BL, EP, 8, 4>), dim3(gx * gy), dim3(256), 0, s, a, b, ep, K, gx, gy, zero_page());
   else hipLaunchKernelGGL((gemm_dma128_kernel<AL, BL, EP, 4, 4>), dim3(gx * gy), dim3(256), 0, s, a, b, ep, K, gx, gy, zero_page());
 }
 // 256 x 128 tiles of the narrow kernel for a WIDE product whose 256 x 256 grid would leave half the chip idle (conv7 forward: 63 x 2 tiles)
 static bool dma_mid_eligible(int M, int N, int K, int C) {
-  if (N % 128 || K % 32 || C % 32 || M < 256 || dma_disabled() || getenv("AOCR_NO_NARROW_WIDE")) return false;       // conv forward 0.846 -> 0.825 ms per C3 step (conv7: 74.6 us on 128 x 128 tiles)
+  if (N % 128 || K % 32 || C % 32 || M < 256 || knob::AOCR_NO_DMA() || knob::AOCR_NO_NARROW_WIDE()) return false;      // conv forward 0.846 -> 0.825 ms per C3 step (conv7: 74.6 us on 128 x 128 tiles)
   const int blocks = cdiv(M, 256) * (N / 128);
   return blocks >= 200 && blocks <= 512;
 }
+// "this launch has the staged 256 x 256 tile": the bit of AOCR_HALO4_STAGED for its kind of output is on (1 fp32 tile of the data gradient, 2 of conv3 / conv5
+// forward, 4 pooled tile) and the launch is not the 8-wave halo kernel's, which has no staged epilogue.  halo: the shape takes a halo-resident kernel
+static bool staged256(int bit, bool halo) { return (knob::AOCR_HALO4_STAGED() & bit) != 0 && !(halo && knob::AOCR_HALO8()); }
 template <class AL, class BL, class EP>
 static void launch_dma(hipStream_t s, const AL& a, const BL& b, const EP& ep, int M, int N, int K, int tag = 0) {
   const int gx = N / 256, gy = cdiv(M, 256);
-  const char* const so = getenv("AOCR_HALO4_STAGED");        // the same switch as the halo kernel's: output tiles through LDS (read per call: tests toggle it)
-  const int opt = so ? atoi(so) : 7;
+  const int opt = knob::AOCR_HALO4_STAGED();                 // the same switch as the halo kernel's: output tiles through LDS
   trace_launch("gemm_dma_bf16_kernel", tag ? "tag" : "", M, N, K);
   if (tag) hipLaunchKernelGGL((gemm_dma_bf16_kernel<AL, BL, EP, 0, false, false, 1>), dim3(gx * gy), dim3(512), 0, s, a, b, ep, K, gx, gy, zero_page(), opt);
   else hipLaunchKernelGGL((gemm_dma_bf16_kernel<AL, BL, EP>), dim3(gx * gy), dim3(512), 0, s, a, b, ep, K, gx, gy, zero_page(), opt);
 }
 // halo-resident 3 x 3 kernel (gemm_halo_bf16_kernel): the tile must be MT / W whole rows of one image
 static bool halo_eligible(const LoadConvK& g, int N, int MT, int NT) {
-  const char* e = getenv("AOCR_NO_HALO");                      // read per call (A/B runs, parity tests against the im2col kernels)
-  if (e && e[0] == '1') return false;
+  if (knob::AOCR_NO_HALO()) return false;                      // A/B runs, parity tests against the im2col kernels
   const int W = g.Wr;
   if (g.KW != 3 || g.W != g.Wr || g.H != g.Hr || (W != 32 && W != 64 && W != 128)) return false;
   const int R = MT / W;
@@ -115,10 +108,8 @@ template <int SGN, int MT, int NT, class EP>
 static void launch_halo(hipStream_t s, const LoadConvKh& a, const LoadKh& b, const EP& ep, int M, int N, int tag = 0) {
   const int gx = N / NT, gy = M / MT;
   if constexpr (MT == 256 && NT == 256) {                 // four waves of 128 x 128 with hand-placed reads / DMA (AOCR_HALO8=1: the 8-wave kernel; bit-identical)
-    const bool eight = getenv("AOCR_HALO8") != nullptr;          // read per call: tests toggle it
-    if (!eight) {
-      const char* const so = getenv("AOCR_HALO4_STAGED");
-      const int opt = so ? atoi(so) : 7;   // 1: fp32 tile of the data gradient, 2: of conv3 / conv5 forward, 4: pooled tile -- through LDS
+    if (!knob::AOCR_HALO8()) {
+      const int opt = knob::AOCR_HALO4_STAGED();   // staged256's bits
       trace_launch("gemm_halo4_bf16_kernel", SGN > 0 ? "fwd" : "dgrad", M, N, 9LL * a.g.C);
       if (tag) hipLaunchKernelGGL((gemm_halo4_bf16_kernel<EP, SGN, 1>), dim3(gx * gy), dim3(256), 0, s, a, b, ep, gx, gy, zero_page(), opt);
       else hipLaunchKernelGGL((gemm_halo4_bf16_kernel<EP, SGN>), dim3(gx * gy), dim3(256), 0, s, a, b, ep, gx, gy, zero_page(), opt);
@@ -156,13 +147,12 @@ static void launch_big(hipStream_t s, bool bf16, const AL& a, const BL& b, const
   // nn.Linear forward) wherever a 128 x 128 tile is mostly full: C2 conv forward 1.86 -> 1.35 ms, data gradient 2.46 -> 1.98 ms per step.
   // The M/N-contiguous pairs (filter / weight gradients: transposing stagers, split-K) measured SLOWER on it (1.67 -> 1.85 ms) and keep
   // the fragment-from-global kernel.  AOCR_NO_LDS_F32=1 restores that kernel everywhere (bit-identical results).
-  const bool no_lds32 = getenv("AOCR_NO_LDS_F32") != nullptr;          // read per call: tests toggle it
+  const bool no_lds32 = knob::AOCR_NO_LDS_F32();
   if constexpr (HasPtr8<AL>::v && HasPtr8<BL>::v) {
     // round 4: branch-free staging + tile shape by grid size (gemm_f32t_kernel); AOCR_NO_F32T=1 restores gemm_lds_f32_kernel (bit-identical)
-    if (!no_lds32 && !env_is_1("AOCR_NO_F32T") && M >= 96 && N >= 16 && K >= 32 && f32t_ok(a) && f32t_ok(b)) {      // (N < 64: the projector, 39 columns: rows past N stage zeros)
+    if (!no_lds32 && !knob::AOCR_NO_F32T() && M >= 96 && N >= 16 && K >= 32 && f32t_ok(a) && f32t_ok(b)) {      // (N < 64: the projector, 39 columns: rows past N stage zeros)
       int kp; split_k(K, 32, ksplit, kp);
-      const char* ft = getenv("AOCR_F32T_TILE");                       // A/B: 1 = 128 x 128, 2 = 64 x 128, 3 = 64 x 64
-      const int force = ft ? atoi(ft) : 0;
+      const int force = knob::AOCR_F32T_TILE();                        // A/B: 1 = 128 x 128, 2 = 64 x 128, 3 = 64 x 64
       auto wgs = [&](int bm, int bn) { return (long long)cdiv(M, bm) * cdiv(N, bn) * ksplit; };
       const int pick = force ? force : (N > 64 && wgs(128, 128) >= 512) ? 1 : (N > 64 && wgs(64, 128) >= 512) ? 2 : 3;
       if (pick == 1) {
@@ -187,12 +177,11 @@ static void launch_big(hipStream_t s, bool bf16, const AL& a, const BL& b, const
   if constexpr (HasStagerW<AL>::v && HasStagerW<BL>::v) {
     // round 4: M/N-contiguous pairs (filter gradients, recurrent weight gradients) through a [k][m] LDS image (gemm_f32w_kernel);
     // AOCR_NO_F32W=1 restores the fragment-from-global kernel
-    if (!env_is_1("AOCR_NO_F32W") && M >= 64 && N >= 64 && K >= 64 && f32w_ok(a) && f32w_ok(b)) {
+    if (!knob::AOCR_NO_F32W() && M >= 64 && N >= 64 && K >= 64 && f32w_ok(a) && f32w_ok(b)) {
       // at least AOCR_F32W_MINK (default 192) of K per k range: the callers' split (pick_ksplit: 768 workgroups) gave the recurrent weight gradients at batch 64
       // (K = L B = 1536) 12-24 ranges of 64-128 rows -- 2-4 tiles of MFMA work under a 128 x 128 tile of memory-side atomics each (88 us, MFMA-busy 0.17).
       // Measured at C2 (ms per step, same box): 32 (the callers' split) 7.70, 128 7.62, 160 7.56, 192 7.51-7.57, 256 7.59, 384 7.66, 768 8.08.
-      const char* mk = getenv("AOCR_F32W_MINK"); const int mink = mk ? std::max(32, atoi(mk)) : 192;
-      ksplit = std::min(ksplit, std::max(1, K / mink));
+      ksplit = std::min(ksplit, std::max(1, K / knob::AOCR_F32W_MINK()));
       int kp; split_k(K, 32, ksplit, kp);
       const int gx = cdiv(N, 128), gy = cdiv(M, 128);
       hipLaunchKernelGGL((gemm_f32w_kernel<AL, BL, EP>), dim3(gx * gy, 1, ksplit), dim3(256), 0, s, a, b, ep, K, kp, gx, gy);
@@ -222,12 +211,7 @@ void launch_conv_wgrad(hipStream_t s, bool bf16, const LoadMN& a, const LoadConv
   launch_big(s, bf16, a, b, ep, M, N, K, ksplit);
 }
 
-static bool quarter_gate_tiles(int H, int M, int nz) {
-  static const bool off = getenv("AOCR_NO_QUARTER_TILES") != nullptr;
-  return !off && H % 8 == 0 && (H / 32) * cdiv(M, 32) * nz < 128;
-}
-static bool step_waves16() { return getenv("AOCR_STEP_WAVES16") != nullptr; }      // (read per call, like every dispatch switch: tests reach all three wave counts in one process)
-static bool step_waves8() { return getenv("AOCR_STEP_WAVES4") == nullptr; }
+static bool quarter_gate_tiles(int H, int M, int nz) { return !knob::AOCR_NO_QUARTER_TILES() && H % 8 == 0 && (H / 32) * cdiv(M, 32) * nz < 128; }
 template <int NT, bool GATES, class ARGS>
 static void launch_small(hipStream_t s, bool bf16, int nz, const ARGS* z, int M, int ncols, int gate_stride) {
   if (M <= 0 || ncols <= 0) return;
@@ -242,7 +226,7 @@ static void launch_small(hipStream_t s, bool bf16, int nz, const ARGS* z, int M,
                 ((GATES && NT == 4) || (!GATES && NT == 1))) {
     // round 4: wave-private LDS staging with whole-line loads for the exact-fp32 steps too (gemm_step_f32_kernel); AOCR_NO_STEP_F32=1: the
     // fragment-from-global kernels below
-    bool ok = !env_is_1("AOCR_NO_STEP_F32") && (GATES ? ncols % 8 == 0 : ncols % 32 == 0);
+    bool ok = !knob::AOCR_NO_STEP_F32() && (GATES ? ncols % 8 == 0 : ncols % 32 == 0);
     for (int i = 0; i < nz && ok; ++i)
       ok = z[i].K > 0 && z[i].K % 32 == 0 && z[i].a.vec && z[i].b.vec && z[i].a.K == z[i].K && z[i].b.K == z[i].K &&
            (z[i].a.p1 ? z[i].a.K0 % 32 == 0 : z[i].a.K0 >= z[i].K) && (z[i].b.p1 ? z[i].b.K0 % 32 == 0 : z[i].b.K0 >= z[i].K);
@@ -252,7 +236,7 @@ static void launch_small(hipStream_t s, bool bf16, int nz, const ARGS* z, int M,
       // of the decoder's d h products at batch 64: 32-96 workgroups x 8 chunks per wave).  Measured SLOWER (those launches 15.5-16.6 -> 17.5-18.2 us,
       // C2 7.67 -> 7.81 ms per step: the 1024-thread workgroup's launch and 16-way reduction cost more than the shorter K loop saves): opt-in.
       const int wgs = (GATES ? ncols / 8 : ncols / 32) * cdiv(M, 32) * nz;
-      const bool deep = env_is_1("AOCR_STEP_F32_W16") && z[0].K >= 2048 && wgs <= 128;
+      const bool deep = knob::AOCR_STEP_F32_W16() && z[0].K >= 2048 && wgs <= 128;
       if constexpr (GATES) hipLaunchKernelGGL((gemm_step_f32_kernel<true, EPT>), dim3(ncols / 8, cdiv(M, 32), nz), dim3(512), 0, s, zz, gate_stride);
       else if (deep) hipLaunchKernelGGL((gemm_step_f32_kernel<false, EPT, 16>), dim3(ncols / 32, cdiv(M, 32), nz), dim3(1024), 0, s, zz, gate_stride);
       else hipLaunchKernelGGL((gemm_step_f32_kernel<false, EPT>), dim3(ncols / 32, cdiv(M, 32), nz), dim3(512), 0, s, zz, gate_stride);
@@ -268,7 +252,7 @@ static void launch_small(hipStream_t s, bool bf16, int nz, const ARGS* z, int M,
       return;
     }
   }
-  if (step_waves8())
+  if (!knob::AOCR_STEP_WAVES4())
     hipLaunchKernelGGL((gemm_small_kernel<false, NT, GATES, decltype(z[0].a), decltype(z[0].b), decltype(z[0].ep), 8>), grid, dim3(512), 0, s,
                        zz, gate_stride);
   else
@@ -291,16 +275,42 @@ void launch_small_gates_bwd(hipStream_t s, bool bf16, int nz, const GatesBwdArgs
 
 // half gate tiles (16 hidden units x 4 gates per workgroup) when the 32-unit grid would leave CUs idle; AOCR_NO_HALF_TILES=1 disables
 static bool half_gate_tiles(int H, int M, int nz) {
-  const char* e = getenv("AOCR_NO_HALF_TILES");
-  if (e && e[0] == '1') return false;
-  const char* g = getenv("AOCR_HALF_TILES_MAXGRID");       // A/B: the 32-unit grid size below which the half tiles are taken
-  return H % 16 == 0 && (H / 32) * cdiv(M, 32) * nz < (g ? atoi(g) : 200);
+  return !knob::AOCR_NO_HALF_TILES() && H % 16 == 0 && (H / 32) * cdiv(M, 32) * nz < knob::AOCR_HALF_TILES_MAXGRID();
+}
+// half gate tiles of the staged step kernel (callers: GATES && NT == 4, half_gate_tiles() holds)
+template <class AL, class BL, class EP>
+static void launch_step_half_gates(hipStream_t s, const SmallArgs2<AL, BL, EP>& zz, bool w8, int nz, int M, int ncols, int K, int gate_stride) {
+  trace_step(2, 2, w8 ? 8 : 4, 1, M, ncols, K);
+  if (w8)
+    hipLaunchKernelGGL((gemm_step_kernel<2, 2, AL, EP, 8>), dim3(ncols / 16, cdiv(M, 32), nz), dim3(512), 0, s, zz, gate_stride);
+  else
+    hipLaunchKernelGGL((gemm_step_kernel<2, 2, AL, EP>), dim3(ncols / 16, cdiv(M, 32), nz), dim3(256), 0, s, zz, gate_stride);
+}
+// one 32-row tile per workgroup of the staged step kernel on the widest wave count allowed: 16 (NT = 1, K >= 1024), 8 (NT <= 2), else 4
+template <int NT, bool GATES, class AL, class BL, class EP>
+static void launch_step_by_waves(hipStream_t s, const SmallArgs2<AL, BL, EP>& zz, bool w8, bool w16, dim3 grid, int M, int ncols, int K, int gate_stride) {
+  if constexpr (NT == 1) {
+    if (w16 && K >= 1024) {                      // 147 KB of LDS; 64 k per wave at K = 1024
+      trace_step(NT, GATES ? 1 : 0, 16, 1, M, ncols, K);
+      hipLaunchKernelGGL((gemm_step_kernel<NT, GATES ? 1 : 0, AL, EP, 16>), grid, dim3(1024), 0, s, zz, gate_stride);
+      return;
+    }
+  }
+  if constexpr (NT <= 2) {
+    if (w8) {
+      trace_step(NT, GATES ? 1 : 0, 8, 1, M, ncols, K);
+      hipLaunchKernelGGL((gemm_step_kernel<NT, GATES ? 1 : 0, AL, EP, 8>), grid, dim3(512), 0, s, zz, gate_stride);
+      return;
+    }
+  }
+  trace_step(NT, GATES ? 1 : 0, 4, 1, M, ncols, K);
+  hipLaunchKernelGGL((gemm_step_kernel<NT, GATES ? 1 : 0, AL, EP>), grid, dim3(256), 0, s, zz, gate_stride);
 }
 template <int NT, bool GATES, class ARGS>
 static void launch_small_bf16(hipStream_t s, int nz, const ARGS* z, int M, int ncols, int gate_stride) {
   if (M <= 0 || ncols <= 0) return;
   const TraceScope ts("launch_small_bf16");
-  const bool w8 = step_waves8(), w16 = w8 && step_waves16();
+  const bool w8 = !knob::AOCR_STEP_WAVES4(), w16 = w8 && knob::AOCR_STEP_WAVES16();
   dim3 grid(GATES ? cdiv(ncols, 32) : cdiv(ncols, 32 * NT), cdiv(M, 32), nz);
   SmallArgs2<decltype(z[0].a), decltype(z[0].b), decltype(z[0].ep)> zz; zz.z[0] = z[0]; zz.z[1] = z[nz > 1 ? 1 : 0]; zz.z[2] = z[nz > 2 ? 2 : 0];
   bool staged = ncols % 32 == 0;                              // wave-private-LDS kernel: full-line loads, needs 64-aligned K
@@ -309,31 +319,9 @@ static void launch_small_bf16(hipStream_t s, int nz, const ARGS* z, int M, int n
              (!z[i].b.p1 || z[i].b.ld1 % 8 == 0);
   if (staged) {
     if constexpr (GATES && NT == 4) {
-      if (half_gate_tiles(ncols, M, nz)) {
-        trace_step(2, 2, w8 ? 8 : 4, 1, M, ncols, z[0].K);
-        if (w8)
-          hipLaunchKernelGGL((gemm_step_kernel<2, 2, decltype(z[0].a), decltype(z[0].ep), 8>), dim3(ncols / 16, cdiv(M, 32), nz), dim3(512), 0, s, zz, gate_stride);
-        else
-          hipLaunchKernelGGL((gemm_step_kernel<2, 2, decltype(z[0].a), decltype(z[0].ep)>), dim3(ncols / 16, cdiv(M, 32), nz), dim3(256), 0, s, zz, gate_stride);
-        return;
-      }
+      if (half_gate_tiles(ncols, M, nz)) { launch_step_half_gates(s, zz, w8, nz, M, ncols, z[0].K, gate_stride); return; }
     }
-    if constexpr (NT == 1) {
-      if (w16 && z[0].K >= 1024) {                    // 147 KB of LDS; 64 k per wave at K = 1024
-        trace_step(NT, GATES ? 1 : 0, 16, 1, M, ncols, z[0].K);
-        hipLaunchKernelGGL((gemm_step_kernel<NT, GATES ? 1 : 0, decltype(z[0].a), decltype(z[0].ep), 16>), grid, dim3(1024), 0, s, zz, gate_stride);
-        return;
-      }
-    }
-    if constexpr (NT <= 2) {
-      if (w8) {
-        trace_step(NT, GATES ? 1 : 0, 8, 1, M, ncols, z[0].K);
-        hipLaunchKernelGGL((gemm_step_kernel<NT, GATES ? 1 : 0, decltype(z[0].a), decltype(z[0].ep), 8>), grid, dim3(512), 0, s, zz, gate_stride);
-        return;
-      }
-    }
-    trace_step(NT, GATES ? 1 : 0, 4, 1, M, ncols, z[0].K);
-    hipLaunchKernelGGL((gemm_step_kernel<NT, GATES ? 1 : 0, decltype(z[0].a), decltype(z[0].ep)>), grid, dim3(256), 0, s, zz, gate_stride);
+    launch_step_by_waves<NT, GATES>(s, zz, w8, w16, grid, M, ncols, z[0].K, gate_stride);
     return;
   }
   trace_launch("gemm_small_kernel", NT == 4 ? (GATES ? "bf16,4,gates" : "bf16,4,plain") : (GATES ? "bf16,1,gates" : "bf16,1,plain"), M, ncols, z[0].K);
@@ -347,10 +335,9 @@ static void launch_small_bf16(hipStream_t s, int nz, const ARGS* z, int M, int n
 //   three plain products per launch: from 160 workgroups of 64 x 128 (400 rows x N = 1024: 38.8 / 30.8 us; at 256 rows the small tiles win);
 //   one plain product: only at K >= 4096 and >= 160 workgroups (1280 rows: 37.3 / 28.4 us) -- below that its 416+ small workgroups beat every tile shape here.
 // AOCR_NO_STEPL=1: off (A/B runs, parity tests); AOCR_STEPL_MIN_WGS=n: taken from n of its own workgroups, whatever the kind (tests force it at small batch).
-static int stepl_min_wgs() { const char* const e = getenv("AOCR_STEPL_MIN_WGS"); return e ? atoi(e) : -1; }
 template <class ARGS>
 static bool stepl_eligible(const ARGS* z, int nz, int M) {
-  if (env_is_1("AOCR_NO_STEPL")) return false;
+  if (knob::AOCR_NO_STEPL()) return false;
   for (int i = 0; i < nz; ++i) {
     const auto& a = z[i].a; const auto& b = z[i].b;
     if (z[i].K <= 0 || z[i].K % 128 || a.K0 % 64 || b.K0 != a.K0 || (a.p1 != nullptr) != (b.p1 != nullptr)) return false;
@@ -364,38 +351,32 @@ template <int NT, bool GATES, class ARGS>
 static void launch_small_bf16_hh(hipStream_t s, int nz, const ARGS* z, int M, int ncols, int gate_stride) {
   if (M <= 0 || ncols <= 0) return;
   const TraceScope ts("launch_small_bf16_hh");
-  const bool w8 = step_waves8(), w16 = w8 && step_waves16();
+  const bool w8 = !knob::AOCR_STEP_WAVES4(), w16 = w8 && knob::AOCR_STEP_WAVES16();
   dim3 grid(GATES ? cdiv(ncols, 32) : cdiv(ncols, 32 * NT), cdiv(M, 32), nz);
   SmallArgs2<decltype(z[0].a), decltype(z[0].b), decltype(z[0].ep)> zz; zz.z[0] = z[0]; zz.z[1] = z[nz > 1 ? 1 : 0]; zz.z[2] = z[nz > 2 ? 2 : 0];
   if constexpr (GATES && NT == 4) {
     // large batch (round 6; the reference-default decoder: 400 rows x Hd = 1024): 64 x 128 gate tiles on the LDS-DMA ring, eight waves, four-unit epilogue (stepl.h)
-    if (stepl_eligible(z, nz, M) && (stepl_min_wgs() >= 0 ? (ncols / 32) * cdiv(M, 64) * nz >= stepl_min_wgs() : (ncols / 16) * cdiv(M, 32) * nz > 256)) {
+    const int min_wgs = knob::AOCR_STEPL_MIN_WGS();
+    if (stepl_eligible(z, nz, M) && (min_wgs >= 0 ? (ncols / 32) * cdiv(M, 64) * nz >= min_wgs : (ncols / 16) * cdiv(M, 32) * nz > 256)) {
       const int gx = ncols / 32, gy = cdiv(M, 64);
       trace_launch("gemm_stepl_kernel", "gates", M, ncols, z[0].K);
       hipLaunchKernelGGL((gemm_stepl_kernel<2, 4, 1, decltype(z[0].ep), 6, 2, 8, true>), dim3(gx * gy * nz), dim3(512), 0, s, zz, gate_stride, gx, gy);
       return;
     }
-    if (half_gate_tiles(ncols, M, nz)) {
-      trace_step(2, 2, w8 ? 8 : 4, 1, M, ncols, z[0].K);
-      if (w8)
-        hipLaunchKernelGGL((gemm_step_kernel<2, 2, decltype(z[0].a), decltype(z[0].ep), 8>), dim3(ncols / 16, cdiv(M, 32), nz), dim3(512), 0, s, zz, gate_stride);
-      else
-        hipLaunchKernelGGL((gemm_step_kernel<2, 2, decltype(z[0].a), decltype(z[0].ep)>), dim3(ncols / 16, cdiv(M, 32), nz), dim3(256), 0, s, zz, gate_stride);
-      return;
-    }
+    if (half_gate_tiles(ncols, M, nz)) { launch_step_half_gates(s, zz, w8, nz, M, ncols, z[0].K, gate_stride); return; }
     // two row tiles per workgroup where the single-tile grid is more than a round of the chip anyway (reference default He = 512: M = 400, 32 x 13 workgroups):
     // the weight tile is streamed by half as many row blocks and every weight fragment feeds two MFMAs.  AOCR_NO_STEP_MT2=1: off
-    { const char* e = getenv("AOCR_NO_STEP_MT2");
-      if (!(e && e[0] == '1') && cdiv(ncols, 32) * cdiv(M, 64) * nz >= 200) {
-        trace_step(NT, 1, 4, 2, M, ncols, z[0].K);
-        hipLaunchKernelGGL((gemm_step_kernel<NT, 1, decltype(z[0].a), decltype(z[0].ep), 4, 2>), dim3(cdiv(ncols, 32), cdiv(M, 64), nz), dim3(256), 0, s, zz, gate_stride);
-        return;
-      } }
+    if (!knob::AOCR_NO_STEP_MT2() && cdiv(ncols, 32) * cdiv(M, 64) * nz >= 200) {
+      trace_step(NT, 1, 4, 2, M, ncols, z[0].K);
+      hipLaunchKernelGGL((gemm_step_kernel<NT, 1, decltype(z[0].a), decltype(z[0].ep), 4, 2>), dim3(cdiv(ncols, 32), cdiv(M, 64), nz), dim3(256), 0, s, zz, gate_stride);
+      return;
+    }
   }
   if constexpr (!GATES && NT == 1) {
     // plain products at large batch (the backward step's d z W_h2h / input-feed group of three; single deep products from ~1280 rows): stepl.h, see stepl_eligible
     const int lw = ncols % 128 == 0 ? (ncols / 128) * cdiv(M, 64) * nz : 0;          // its workgroups
-    if (lw > 0 && stepl_eligible(z, nz, M) && (stepl_min_wgs() >= 0 ? lw >= stepl_min_wgs() : lw >= 160 && (nz == 3 || (nz == 1 && z[0].K >= 4096)))) {
+    const int min_wgs = knob::AOCR_STEPL_MIN_WGS();
+    if (lw > 0 && stepl_eligible(z, nz, M) && (min_wgs >= 0 ? lw >= min_wgs : lw >= 160 && (nz == 3 || (nz == 1 && z[0].K >= 4096)))) {
       const int gx = ncols / 128, gy = cdiv(M, 64);
       trace_launch("gemm_stepl_kernel", "plain", M, ncols, z[0].K);
       hipLaunchKernelGGL((gemm_stepl_kernel<2, 4, 0, decltype(z[0].ep), 6, 2, 8, true>), dim3(gx * gy * nz), dim3(512), 0, s, zz, gate_stride, gx, gy);
@@ -406,32 +387,16 @@ static void launch_small_bf16_hh(hipStream_t s, int nz, const ARGS* z, int M, in
     // ONE deep plain product at large batch (K >= 2048 at >= 320 rows: the backward step's d z_2 W_i2h in front of the lower cell, the out product): two row tiles per workgroup, 64 x 32
     // tiles on 224 workgroups of 8 waves -- 16.6 -> 14.8 us (tools/ubench/step400.hip; at K = 1024 and for three products per launch the 32 x 32 tiles win).  Same K
     // split and summation order as the one-tile form: bit-identical.  AOCR_NO_STEP_MT2=1: off
-    { const char* e = getenv("AOCR_NO_STEP_MT2");
-      const char* const mk = getenv("AOCR_STEP_MT2_MINK");        // the K from which the two-tile form is taken (A/B on the reference-default step: decoder 3.31 ms at 4096, 3.26 at 2048, 3.31 at 1024)
-      if (!(e && e[0] == '1') && nz == 1 && z[0].K >= (mk ? atoi(mk) : 2048) && M >= 320 && cdiv(ncols, 32) * cdiv(M, 64) >= 200 && w8) {
-        trace_step(1, 0, 8, 2, M, ncols, z[0].K);
-        hipLaunchKernelGGL((gemm_step_kernel<1, 0, decltype(z[0].a), decltype(z[0].ep), 8, 2>), dim3(cdiv(ncols, 32), cdiv(M, 64), nz), dim3(512), 0, s, zz, gate_stride);
-        return;
-      } }
+    // AOCR_STEP_MT2_MINK: the K from which the two-tile form is taken (A/B on the reference-default step: decoder 3.31 ms at 4096, 3.26 at 2048, 3.31 at 1024)
+    if (!knob::AOCR_NO_STEP_MT2() && nz == 1 && z[0].K >= knob::AOCR_STEP_MT2_MINK() && M >= 320 && cdiv(ncols, 32) * cdiv(M, 64) >= 200 && w8) {
+      trace_step(1, 0, 8, 2, M, ncols, z[0].K);
+      hipLaunchKernelGGL((gemm_step_kernel<1, 0, decltype(z[0].a), decltype(z[0].ep), 8, 2>), dim3(cdiv(ncols, 32), cdiv(M, 64), nz), dim3(512), 0, s, zz, gate_stride);
+      return;
+    }
   }
   // (measured and dropped: 64 x 64 tiles -- NT = 2, MT = 2, eight waves -- for the plain step products of the backward pass at M = 400: 336 workgroups instead of
   //  1248, 350 MB instead of 640 MB per launch, decoder backward 2.27 -> 2.34 ms: there the many small workgroups are what hides the latency)
-  if constexpr (NT == 1) {
-    if (w16 && z[0].K >= 1024) {
-      trace_step(NT, GATES ? 1 : 0, 16, 1, M, ncols, z[0].K);
-      hipLaunchKernelGGL((gemm_step_kernel<NT, GATES ? 1 : 0, decltype(z[0].a), decltype(z[0].ep), 16>), grid, dim3(1024), 0, s, zz, gate_stride);
-      return;
-    }
-  }
-  if constexpr (NT <= 2) {
-    if (w8) {
-      trace_step(NT, GATES ? 1 : 0, 8, 1, M, ncols, z[0].K);
-      hipLaunchKernelGGL((gemm_step_kernel<NT, GATES ? 1 : 0, decltype(z[0].a), decltype(z[0].ep), 8>), grid, dim3(512), 0, s, zz, gate_stride);
-      return;
-    }
-  }
-  trace_step(NT, GATES ? 1 : 0, 4, 1, M, ncols, z[0].K);
-  hipLaunchKernelGGL((gemm_step_kernel<NT, GATES ? 1 : 0, decltype(z[0].a), decltype(z[0].ep)>), grid, dim3(256), 0, s, zz, gate_stride);
+  launch_step_by_waves<NT, GATES>(s, zz, w8, w16, grid, M, ncols, z[0].K, gate_stride);
 }
 // ---- recurrent-step products at LARGE batch (round 5; the reference's default shape: 400 rows, Hd = 1024).  The step kernels above are built for latency at 32-256
 // rows: 32-row tiles, every workgroup streams its own weight slice -- at 400 rows a gate launch re-reads its 16 MB of weights 13 times (41.5 us for 6.7 GFLOP =
@@ -444,11 +409,11 @@ static LoadKhCat cat_of(const LoadKh2& a) {
   return c;
 }
 bool big_step_eligible(int M, int N, int K) {
-  const char* const e = getenv("AOCR_BIG_STEP_MIN_ROWS"); const int min_rows = e ? atoi(e) : 320;       // (read per call, like every dispatch switch) C3 / C4 launch-chain fallbacks (<= 256 rows) stay on the step kernels
+  // AOCR_BIG_STEP_MIN_ROWS (320): C3 / C4 launch-chain fallbacks (<= 256 rows) stay on the step kernels
   // MEASURED SLOWER, so opt-in (AOCR_BIG_STEP=1; tests/test_configs_gpu.py keeps its oracle test): at 400 rows x Hd = 1024 the 128 x 128 grid is 128 workgroups of 64 K steps, and
   // a workgroup's L2 -> LDS stream sustains ~32 GB/s (1 MB of operands in 32 us): gate product 32 us + 7 us for the cell pass against 41.5 us fused in the step kernel, the
   // N = 1024 products 19-25 us against 17 -- decoder 5.06 -> 5.82 ms per step of the reference-default workload.  Both forms are bound by what one compute unit pulls from L2.
-  return env_is_1("AOCR_BIG_STEP") && M >= min_rows && N >= 1024 && dma128_eligible(M, N, K, 32);
+  return knob::AOCR_BIG_STEP() && M >= knob::AOCR_BIG_STEP_MIN_ROWS() && N >= 1024 && dma128_eligible(M, N, K, 32);
 }
 static bool big_step_store_(hipStream_t s, const LoadKh2& a, const LoadKh2& b, const EpStore& ep, int M, int N) {       // (the caller holds the TraceScope)
   if (!big_step_eligible(M, N, a.K) || (a.p1 && a.K0 % 32) || (b.p1 && b.K0 % 32) || (a.p1 != nullptr) != (b.p1 != nullptr) || (a.p1 && a.K0 != b.K0)) return false;
@@ -516,7 +481,7 @@ int gemm(hipStream_t s, bool bf16, const float* A, int64_t lda, bool a_k, const 
   // skinny products (a 20- or 39-wide side: embedding part of the first decoder layer, projector and their backward): 128 x 128 tiles
   // give 48 workgroups for 6144 rows and pad N or K 3-6x; the 32 x 32 step kernel (K quartered over its waves) fills the chip
   // (only where K is a multiple of the step kernel's 16-deep chunk: its fragment loads have no K tail)
-  const bool skinny = bf16 && M >= 1024 && N <= 64 && K % 16 == 0 && !getenv("AOCR_NO_SKINNY");     // (an EP_ATOMIC epilogue stays atomic: one add per element, no split-K)
+  const bool skinny = bf16 && M >= 1024 && N <= 64 && K % 16 == 0 && !knob::AOCR_NO_SKINNY();  // (an EP_ATOMIC epilogue stays atomic: one add per element, no split-K)
   if (skinny && a_k && b_k) { SmallKKArgs z; z.a = make_loadk(A, lda, M, K); z.b = make_loadk(B, ldb, N, K); z.ep = ep; z.K = K; launch_small_kk(s, true, 1, &z, M, N); }
   else if (skinny && a_k && !b_k) { SmallKMNArgs z; z.a = make_loadk(A, lda, M, K); z.b = make_loadmn(B, ldb, N, K); z.ep = ep; z.K = K; launch_small_kmn(s, true, 1, &z, M, N); }
   else if (a_k && b_k) launch_big_kk(s, bf16, make_loadk(A, lda, M, K), make_loadk(B, ldb, N, K), ep, M, N, K, ks);
@@ -627,7 +592,7 @@ __global__ __launch_bounds__(256) void project_loss_kernel(ProjLossArgs g) {
   }
 }
 bool project_loss_ok(int rows, int V, int Hd) {
-  return rows >= 1024 && V >= 2 && V <= 40 && Hd % 64 == 0 && !getenv("AOCR_NO_SKINNY") && !env_is_1("AOCR_NO_PROJ_FUSE");      // rows >= 1024: where gemm() takes the skinny kernel for the logits
+  return rows >= 1024 && V >= 2 && V <= 40 && Hd % 64 == 0 && !knob::AOCR_NO_SKINNY() && !knob::AOCR_NO_PROJ_FUSE();      // rows >= 1024: where gemm() takes the skinny kernel for the logits
 }
 void project_loss(hipStream_t s, const float* out, int64_t ldo, const float* wo, const float* bo, float* logits, float* dlogits, int64_t ld, float* nll, float* dout,
                   const int32_t* tgt, int64_t st, int64_t sb, int Bt, int rows, int V, int Hd, float scale) {
@@ -636,6 +601,11 @@ void project_loss(hipStream_t s, const float* out, int64_t ldo, const float* wo,
   hipLaunchKernelGGL(project_loss_kernel, dim3(1, cdiv(rows, 32)), dim3(256), 0, s, g);
 }
 
+// hoisted bf16 GEMMs with 256 x 128 tiles that fill the chip take the narrow LDS-DMA kernel (two workgroups per CU: one's epilogue under the other's 16-step K loop):
+// hoisted GEMMs 0.739 -> 0.713 ms per C3 step (AOCR_NO_HH_NARROW: the 128 x 128 kernels).  A ragged last row tile is taken too unless AOCR_HH_NARROW_FULL_ONLY=1
+static bool hh_narrow_ok(int M, int N, int K) {
+  return !knob::AOCR_NO_HH_NARROW() && !knob::AOCR_NO_DMA() && (M % 256 == 0 || (M >= 256 && !knob::AOCR_HH_NARROW_FULL_ONLY())) && N % 128 == 0 && K % 32 == 0 && cdiv(M, 256) * (N / 128) >= 200;
+}
 void gemm_hh(hipStream_t s, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, float* C, int64_t ldc, int M, int N, int K,
              const float* bias, const float* bias2, int flags) {
   const TraceScope ts("gemm_hh");
@@ -645,9 +615,7 @@ void gemm_hh(hipStream_t s, const bf16_t* A, int64_t lda, const bf16_t* B, int64
   // 63 x 4 workgroups: 56 / 47 us against 47 / 43 us; round 3: the BK = 64 form of the 128 x 128 kernel -- half the barriers and
   // staging round trips over the 16 tiles -- measured slower too: hoisted GEMMs 0.726 -> 0.745 ms per step)
   // (round 3, again with that kernel's output tile staged through LDS: hoisted GEMMs 0.750 -> 0.760 ms per step: still no faster)
-  // hoisted bf16 GEMMs with full 256 x 128 tiles that fill the chip: the narrow LDS-DMA kernel (two workgroups per CU: one's epilogue under the other's 16-step K loop):
-  // hoisted GEMMs 0.739 -> 0.713 ms per C3 step (AOCR_NO_HH_NARROW=1: the 128 x 128 kernel)
-  if (!getenv("AOCR_NO_HH_NARROW") && !dma_disabled() && (M % 256 == 0 || (M >= 256 && !env_is_1("AOCR_HH_NARROW_FULL_ONLY"))) && N % 128 == 0 && K % 32 == 0 && cdiv(M, 256) * (N / 128) >= 200) { launch_dma_narrow(s, a, b, make_store(C, ldc, M, N, bias, bias2, flags), M, N, K); return; }
+  if (hh_narrow_ok(M, N, K)) { launch_dma_narrow(s, a, b, make_store(C, ldc, M, N, bias, bias2, flags), M, N, K); return; }
   if (dma128_eligible(M, N, K, 32)) { launch_dma128(s, a, b, make_store(C, ldc, M, N, bias, bias2, flags), M, N, K); return; }       // small / ragged M (32-64 lines per GPU)
   launch_lds(s, a, b, make_store(C, ldc, M, N, bias, bias2, flags), M, N, K, 1);
 }
@@ -655,7 +623,7 @@ void gemm_hh(hipStream_t s, const bf16_t* A, int64_t lda, const bf16_t* B, int64
 // C = [A0 | A1] . [B0 | B1]^T  (K = K0 + K1 over two buffer pairs; bf16, K-contiguous), one launch of the narrow LDS-DMA kernel.  Returns false when the
 // shape does not take that kernel (the caller then runs two products).
 bool gemm_hh_cat(hipStream_t s, const bf16_t* A0, const bf16_t* A1, int64_t lda, const bf16_t* B0, const bf16_t* B1, int64_t ldb, float* C, int64_t ldc, int M, int N, int K0, int K1) {
-  if (getenv("AOCR_NO_HH_NARROW") || env_is_1("AOCR_NO_HH_CAT") || dma_disabled() || (M % 256 && (M < 256 || env_is_1("AOCR_HH_NARROW_FULL_ONLY"))) || N % 128 || K0 % 32 || K1 % 32 || cdiv(M, 256) * (N / 128) < 200) return false;
+  if (K0 % 32 || K1 % 32 || !hh_narrow_ok(M, N, K0 + K1) || knob::AOCR_NO_HH_CAT()) return false;
   const TraceScope ts("gemm_hh_cat");
   LoadKhCat a; a.p0 = A0; a.p1 = A1; a.ld0 = a.ld1 = lda; a.rows = M; a.K0 = K0; a.K = K0 + K1;
   LoadKhCat b; b.p0 = B0; b.p1 = B1; b.ld0 = b.ld1 = ldb; b.rows = N; b.K0 = K0; b.K = K0 + K1;
@@ -669,8 +637,8 @@ void gemm_hh_shadow(hipStream_t s, const bf16_t* A, int64_t lda, const bf16_t* B
   LoadKh a; a.p = A; a.ld = lda; a.rows = M; a.K = K;
   LoadKh b; b.p = B; b.ld = ldb; b.rows = N; b.K = K;
   EpStore e = make_store(C, ldc, M, N, nullptr, nullptr, 0); e.Cb = Cb; e.ldcb = ldcb;
-  if (!getenv("AOCR_NO_HH_NARROW") && !dma_disabled() && (M % 256 == 0 || (M >= 256 && !env_is_1("AOCR_HH_NARROW_FULL_ONLY"))) && N % 128 == 0 && K % 32 == 0 && cdiv(M, 256) * (N / 128) >= 200) {
-    if (!env_is_1("AOCR_NO_NARROW_STAGED")) e.C = nullptr;      // every reader takes the bf16 copy (ctx W_a of the decoder kernels): the staged tile skips the fp32 store (33 MB per C3 step)
+  if (hh_narrow_ok(M, N, K)) {
+    if (!knob::AOCR_NO_NARROW_STAGED()) e.C = nullptr;     // every reader takes the bf16 copy (ctx W_a of the decoder kernels): the staged tile skips the fp32 store (33 MB per C3 step)
     launch_dma_narrow(s, a, b, e, M, N, K); return;
   }
   if (dma128_eligible(M, N, K, 32)) { launch_dma128(s, a, b, e, M, N, K); return; }
@@ -707,8 +675,7 @@ static int grouped_launch_dma(hipStream_t s, const WGradProblem* const* q, int c
   if (cnt > 8) cnt = 8;
   long long tiles = 0; int kmin = 1 << 30;
   for (int i = 0; i < cnt; ++i) { tiles += (long long)(q[i]->M / 256) * (q[i]->N / 256); kmin = std::min(kmin, q[i]->K); }
-  const char* tg = getenv("AOCR_WGRAD_DMA_WGS");                           // A/B: workgroups aimed at per launch
-  int ks = (int)((tg ? atoi(tg) : 256) / tiles); if (ks < 1) ks = 1;           // never more than one round of the 256 CUs (312 workgroups = a second round of 56: 120 instead of 75 us for the encoder's four problems)
+  int ks = (int)(knob::AOCR_WGRAD_DMA_WGS() / tiles); if (ks < 1) ks = 1;           // never more than one round of the 256 CUs (312 workgroups = a second round of 56: 120 instead of 75 us for the encoder's four problems)
   ks = std::min(ks, std::max(1, kmin / 768));                                 // at least 24 K steps per workgroup
   while (ks > 1 && (size_t)tiles * 65536 * ks > part_floats) --ks;
   if ((size_t)tiles * 65536 * ks > part_floats) return 0;
@@ -736,8 +703,8 @@ void grouped_wgrad(hipStream_t s, bool bf16, const WGradProblem* p, int n, float
   }
   // problems whose operands both have bf16 shadows (16-byte pieces: M, N, lda, ldb multiples of 8) take the transposed-read kernel
   const WGradProblem* hs[16]; const WGradProblem* fs[16]; const WGradProblem* ds[16]; int nh = 0, nf = 0, nd = 0;
-  const bool dma_ok = part && !dma_disabled() && !env_is_1("AOCR_NO_WGRAD_DMA_GROUPED");
-  const char* dmk = getenv("AOCR_WGRAD_DMA_MINK"); const int dma_mink = dmk ? atoi(dmk) : 2048;      // smallest K (rows L B / T B) that takes the LDS-DMA kernel
+  const bool dma_ok = part && !knob::AOCR_NO_DMA() && !knob::AOCR_NO_WGRAD_DMA_GROUPED();
+  const int dma_mink = knob::AOCR_WGRAD_DMA_MINK();      // smallest K (rows L B / T B) that takes the LDS-DMA kernel
   for (int i = 0; i < n && i < 16; ++i) {
     const bool ok = p[i].Ab && p[i].Bb && p[i].M % 8 == 0 && p[i].N % 8 == 0 && p[i].lda % 8 == 0 && p[i].ldb % 8 == 0;
     const bool deep = ok && dma_ok && p[i].M % 256 == 0 && p[i].N % 256 == 0 && p[i].K % 32 == 0 && p[i].K >= dma_mink &&
@@ -779,16 +746,13 @@ void conv_forward(hipStream_t s, bool bf16, const float* x, const float* w, cons
     LoadKh bh; bh.p = wb; bh.ld = a.K; bh.rows = Cout; bh.K = a.K;
     // BatchNorm statistics in the epilogue: only where EVERY tile of the launch takes tile256_store_f32 (full 256 x 256 tiles of a 256-wide LDS-DMA kernel with the
     // staged fp32 tile switched on; the 8-wave halo kernel has no staged epilogue), and the row tiles fit bn_relu_forward's chunk table (512)
-    if (bn_part && bn_chunks && y && !yb && !bn_save && pool == 0 && dma_eligible(a.rows, Cout, a.K, Cin) && a.rows % 256 == 0 && a.rows / 256 <= 512 && !getenv("AOCR_NO_BN_STATS_FUSE")) {
-      const char* const so = getenv("AOCR_HALO4_STAGED");
-      const bool staged = ((so ? atoi(so) : 7) & 2) != 0;
-      const bool halo = pad == 1 && halo_eligible(a, Cout, 256, 256);
-      if (staged && !(halo && getenv("AOCR_HALO8"))) {
+    if (bn_part && bn_chunks && y && !yb && !bn_save && pool == 0 && dma_eligible(a.rows, Cout, a.K, Cin) && a.rows % 256 == 0 && a.rows / 256 <= 512 && !knob::AOCR_NO_BN_STATS_FUSE()) {
+      if (staged256(2, pad == 1 && halo_eligible(a, Cout, 256, 256))) {
         ep.bn_part = bn_part; *bn_chunks = a.rows / 256;
         // The statistics come from the accumulators, so y itself could be stored as bf16 (AOCR_BN_Y16=1): -0.065 ms per C3 step (BatchNorm 0.49 -> 0.46 ms, conv forward
         // 0.83 -> 0.755) -- NOT the default: it is one more rounding than "bf16 contraction operands" (the model tests/test_configs_gpu.py holds the product to), and the
         // ReLU / arg-max decisions it flips take the conv-stack gradients from cosine 0.997 to 0.986 against the bf16-operand oracle (limit 0.995).
-        if (y_bf16 && getenv("AOCR_BN_Y16") && Cout % 4 == 0 && !getenv("AOCR_BN_PARTIAL_OLD")) {   // only bn_partial4_kernel / bn_apply_relu_kernel read a bf16 x (xh): never with the 4-byte-access fallback
+        if (y_bf16 && knob::AOCR_BN_Y16() && Cout % 4 == 0 && !knob::AOCR_BN_PARTIAL_OLD()) {   // only bn_partial4_kernel / bn_apply_relu_kernel read a bf16 x (xh): never with the 4-byte-access fallback
           ep.y16 = reinterpret_cast<bf16_t*>(y); ep.y = nullptr; *y_bf16 = 1; }
       }
     }
@@ -802,6 +766,16 @@ void conv_forward(hipStream_t s, bool bf16, const float* x, const float* w, cons
   } else {
     launch_conv_fwd(s, bf16, a, make_loadk(w, a.K, Cout, a.K), ep, a.rows, Cout, a.K);
   }
+}
+
+// the bf16 data gradient `a` leaves its map as bf16 (dx16: see conv_backward_data): opt-in, and only where every tile is a staged 256 x 256 one
+static bool dgrad_bf16_out(const LoadConvK& a, int Cin, int Cout, int pad) {
+  return dma_eligible(a.rows, Cin, a.K, Cout) && a.rows % 256 == 0 && Cin % 256 == 0 && knob::AOCR_DX16() && !knob::AOCR_BN_PARTIAL_OLD() && !knob::AOCR_UNPOOL4() &&   // (the generic forms of the two reader kernels take fp32 only)
+         staged256(1, pad == 1 && halo_eligible(a, Cin, 256, 256));
+}
+bool conv_dgrad_bf16_out(int B, int H, int W, int Cin, int Cout, int ks, int pad) {
+  const int Ho = H + 2 * pad - ks + 1, Wo = W + 2 * pad - ks + 1;
+  return dgrad_bf16_out(make_convk(nullptr, B, Ho, Wo, Cout, ks, -1, pad, H, W, 0), Cin, Cout, pad);
 }
 
 void conv_backward_data(hipStream_t s, bool bf16, const float* dy, const float* w, float* dx, int B, int H, int W, int Cin,
@@ -821,11 +795,7 @@ void conv_backward_data(hipStream_t s, bool bf16, const float* dy, const float* 
     // OPT-IN (AOCR_DX16=1), not the default -- measured at C3: 5.463 -> 5.407 ms per step (BatchNorm 0.50 -> 0.48, data gradients 0.79 -> 0.77), but it is one more
     // rounding than "bf16 contraction operands", the model the parity tests hold the product to: with the GPU's decisions imposed on the bf16-operand oracle the
     // lowest gradient cosine falls from 0.99998 to 0.99983 (conv2.b; tests/test_configs_gpu.py requires 0.9999).  Parity first -- as for AOCR_BN_Y16.
-    if (dx16 && dma_eligible(a.rows, Cin, a.K, Cout) && a.rows % 256 == 0 && Cin % 256 == 0 && env_is_1("AOCR_DX16") && !getenv("AOCR_BN_PARTIAL_OLD") && !getenv("AOCR_UNPOOL4")) {   // (the generic forms of the two reader kernels take fp32 only)
-      const char* const so = getenv("AOCR_HALO4_STAGED");
-      const bool halo = pad == 1 && halo_eligible(a, Cin, 256, 256);
-      if (((so ? atoi(so) : 7) & 1) && !(halo && getenv("AOCR_HALO8"))) { ep.C = nullptr; ep.Cb = reinterpret_cast<bf16_t*>(dx); ep.ldcb = Cin; *dx16 = 1; }
-    }
+    if (dx16 && dgrad_bf16_out(a, Cin, Cout, pad)) { ep.C = nullptr; ep.Cb = reinterpret_cast<bf16_t*>(dx); ep.ldcb = Cin; *dx16 = 1; }
     // Round 4: the sums pass of the BatchNorm backward that follows -- (sum d, sum d xhat) per channel, a re-read of this output (4 B), x (4 B) and the mask
     // (2 B) per element -- from the staged fp32 tile of the 256 x 256 kernels: the output values pass through a thread that keeps four fixed columns anyway
     // (as for the forward statistics, EpConv::bn_part), so only x and the mask are read, by the workgroup that has the tile's output in LDS.
@@ -833,12 +803,9 @@ void conv_backward_data(hipStream_t s, bool bf16, const float* dy, const float* 
     // MEASURED, NOT THE DEFAULT (AOCR_BNB_FUSE=1 turns it on): at C3 the BatchNorm family drops 0.50 -> 0.365 ms per step, but the data gradients rise 0.767 -> 0.931 ms
     // -- the 201 MB of x / mask reads per layer land in an epilogue that nothing overlaps (one workgroup per CU, all of a round finishing together) -- net
     // 5.262 -> 5.280 ms per step, same box, two runs each.  The separate sums pass runs at 5.1 TB/s; it stays.
-    if (bnb && bnb_chunks && ep.C && dma_eligible(a.rows, Cin, a.K, Cout) && a.rows % 256 == 0 && Cin % 256 == 0 && a.rows / 256 <= 512 && env_is_1("AOCR_BNB_FUSE")) {
-      const char* const so = getenv("AOCR_HALO4_STAGED");
-      const bool halo = pad == 1 && halo_eligible(a, Cin, 256, 256);
-      if (((so ? atoi(so) : 7) & 1) && !(halo && getenv("AOCR_HALO8"))) {
-        ep.bnb_x = bnb->x; ep.bnb_yb = bnb->yb; ep.bnb_save = bnb->save; ep.bnb_part = bnb->part; *bnb_chunks = a.rows / 256;
-      }
+    if (bnb && bnb_chunks && ep.C && dma_eligible(a.rows, Cin, a.K, Cout) && a.rows % 256 == 0 && Cin % 256 == 0 && a.rows / 256 <= 512 && knob::AOCR_BNB_FUSE() &&
+        staged256(1, pad == 1 && halo_eligible(a, Cin, 256, 256))) {
+      ep.bnb_x = bnb->x; ep.bnb_yb = bnb->yb; ep.bnb_save = bnb->save; ep.bnb_part = bnb->part; *bnb_chunks = a.rows / 256;
     }
     if (dma_eligible(a.rows, Cin, a.K, Cout) && pad == 1 && halo_eligible(a, Cin, 256, 256)) launch_halo<-1, 256, 256>(s, ah, bh, ep, a.rows, Cin);
     else if (dma_eligible(a.rows, Cin, a.K, Cout)) launch_dma(s, ah, bh, ep, a.rows, Cin, a.K);
@@ -875,19 +842,20 @@ void conv_backward_filter(hipStream_t s, bool bf16, const float* x, const float*
     // (round 6: ragged rows too -- W % 32 != 0 pads every row to whole 32-pixel segments with zero slots; taken while at least 3/4 of the slots are pixels:
     //  the reference-default shape's 25- / 50-wide maps (0.78).  AOCR_WGRAD_HALO_RAGGED=0: whole segments only, as before)
     const int spr = (W + 31) / 32;
-    const bool ragged_ok = W % 32 == 0 || (!env_is_0("AOCR_WGRAD_HALO_RAGGED") && W * 4 >= spr * 32 * 3);
-    if (ks == 3 && pad == 1 && ragged_ok && Cout % hmt == 0 && Cin % 32 == 0 && part && !dma_disabled() && !env_is_1("AOCR_NO_WGRAD_HALO") && !getenv("AOCR_WGRAD_ATOMIC") &&
-        (dma_forced() || (P >= 8192 && N >= wgrad_halo_min_n()))) {
+    const bool ragged_ok = W % 32 == 0 || (knob::AOCR_WGRAD_HALO_RAGGED() && W * 4 >= spr * 32 * 3);
+    // AOCR_WGRAD_HALO_MINN (576): conv2 (64 -> 128) upwards; A/B at C3: 2304 -> 1152 (conv3 too) = 5.505 -> 5.455 ms per step, 1152 -> 576 (conv2 too, 128-channel tiles): see DESIGN.md
+    if (ks == 3 && pad == 1 && ragged_ok && Cout % hmt == 0 && Cin % 32 == 0 && part && !knob::AOCR_NO_DMA() && !knob::AOCR_NO_WGRAD_HALO() && !knob::AOCR_WGRAD_ATOMIC() &&
+        (knob::AOCR_FORCE_DMA() || (P >= 8192 && N >= knob::AOCR_WGRAD_HALO_MINN()))) {
       const int htiles = (Cin / 32) * (Cout / hmt), S = B * H * spr;
       int ksh = htiles >= 256 ? 1 : 256 / htiles; if (ksh > S) ksh = S;                   // one round of the 256 CUs
-      { const char* ms = getenv("AOCR_WGRAD_HALO_MINSTEPS"); const int minsteps = ms ? atoi(ms) : 0;       // A/B: at small P fewer, longer k ranges (less slab traffic) instead of a full round
+      { const int minsteps = knob::AOCR_WGRAD_HALO_MINSTEPS();       // A/B: at small P fewer, longer k ranges (less slab traffic) instead of a full round
         if (minsteps > 0 && S / ksh < minsteps) ksh = std::max(1, S / minsteps); }
       const int per = cdiv(S, ksh); ksh = cdiv(S, per);
       const size_t mn = (size_t)Cout * N;
       if (mn * ksh <= part_floats) {
         // (IM = !AOCR_NO_WGRAD_ISSUE_MID: MFMAs start behind their own k-half's reads, DMA issue between the halves -- mfma_gemm.h)
 #define AOCR_WGH(TAGV, MGV, RGV, IMV, THREADS, MTV) hipLaunchKernelGGL((conv_wgrad_halo_kernel<TAGV, MGV, RGV, IMV>), dim3(htiles * ksh), dim3(THREADS), 0, s, dyb, xb, part, (long long)mn, B, H, W, Cin, Cout, Cin / 32, Cout / MTV, ksh, per, zero_page())
-        const bool im = !env_is_1("AOCR_NO_WGRAD_ISSUE_MID");
+        const bool im = !knob::AOCR_NO_WGRAD_ISSUE_MID();
         { char inst[48]; snprintf(inst, sizeof inst, "%d,%s,%s", hmt, W % 32 ? "ragged" : "whole", im ? "issue_mid" : "no_issue_mid");
           trace_launch("conv_wgrad_halo_kernel", inst, Cout, N, P); }
         if (W % 32) {                                            // ragged rows: the form with the row-end pointer steps and the d y validity compare
@@ -903,10 +871,10 @@ void conv_backward_filter(hipStream_t s, bool bf16, const float* x, const float*
         return;
       }
     }
-    if (Cout % 256 == 0 && Cin % 8 == 0 && !dma_disabled() && (dma_forced() || (P >= 8192 && tiles <= 256 && N % 256 == 0 && N >= 2304))) {
+    if (Cout % 256 == 0 && Cin % 8 == 0 && !knob::AOCR_NO_DMA() && (knob::AOCR_FORCE_DMA() || (P >= 8192 && tiles <= 256 && N % 256 == 0 && N >= 2304))) {
       int ks2 = tiles >= 128 ? (tiles >= 200 ? 1 : 2) : 256 / tiles, kper2; split_k(P, 32, ks2, kper2);      // one round of the 256 CUs
       const size_t mn = (size_t)Cout * N;
-      float* const slab = (part && ks2 > 1 && mn * ks2 <= part_floats && !getenv("AOCR_WGRAD_ATOMIC")) ? part : nullptr;
+      float* const slab = (part && ks2 > 1 && mn * ks2 <= part_floats && !knob::AOCR_WGRAD_ATOMIC()) ? part : nullptr;
       trace_launch("conv_wgrad_dma_kernel", slab ? "slab" : "atomic", Cout, N, P);
       if (profile_tag)        // the same kernel under its own symbol (ABL bit 256 selects nothing): aocr_profile_kernel, per-kernel rocprofv3 / PMC rows
         hipLaunchKernelGGL((conv_wgrad_dma_kernel<EpStore, 256>), dim3(tiles * ks2), dim3(512), 0, s, ah, bh, ep, P, kper2, cdiv(N, 256), Cout / 256, zero_page(), ks2, slab, (long long)mn);
@@ -919,7 +887,7 @@ void conv_backward_filter(hipStream_t s, bool bf16, const float* x, const float*
     int ks = ksplit, kper; split_k(P, 32, ks, kper);
     const int gx = cdiv(N, 128), gy = cdiv(Cout, 128);
     const size_t mn = (size_t)Cout * N;
-    float* const slab = (part && ks > 1 && mn * ks <= part_floats && !getenv("AOCR_WGRAD_ATOMIC")) ? part : nullptr;
+    float* const slab = (part && ks > 1 && mn * ks <= part_floats && !knob::AOCR_WGRAD_ATOMIC()) ? part : nullptr;
     trace_launch("conv_wgrad_tr_kernel", slab ? "slab" : "atomic", Cout, N, P);
     hipLaunchKernelGGL((conv_wgrad_tr_kernel<EpStore>), dim3(gx * gy * ks), dim3(256), 0, s, ah, bh, ep, P, kper, gx, gy, ks, slab, (long long)mn);
     if (slab) splitk_reduce(s, slab, ks, mn, dw);

@@ -25,7 +25,7 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 // launch decision, so the kernel tests can prove which instantiation a shape reached.  a b c: the launch's shape (attention: B T Hd; BatchNorm: rows C tb_rows;
 // un-pool: B*Ho Wo C; conv1: B H W)
 static void launch_trace(const char* fn, const char* kernel, const char* inst, int a, int b, int c) {
-  if (getenv("AOCR_TRACE")) fprintf(stderr, "[aocr] %s: %s[%s] %d %d %d\n", fn, kernel, inst, a, b, c);
+  if (knob::AOCR_TRACE()) fprintf(stderr, "[aocr] %s: %s[%s] %d %d %d\n", fn, kernel, inst, a, b, c);
 }
 static void chunks_trace(const char* fn, int n, int64_t rows, int C, int tb_rows) {     // the partial sums came from the producing conv: "chunks[n]"
   char inst[16]; snprintf(inst, sizeof inst, "%d", n);
@@ -304,7 +304,7 @@ void conv1_backward(hipStream_t s, const float* x, const float* w, const float* 
   // with a scratch slab (blocks * 640 floats, at most 2048*640) every workgroup writes its partial sums and two column sums finish
   // the job: no contended global atomics, more workgroups
   int blocks = (int)std::min<int64_t>((strips + 3) / 4, scratch ? 2048 : 1024);
-  if (getenv("AOCR_CONV1_SCALAR")) {
+  if (knob::AOCR_CONV1_SCALAR()) {
     launch_trace("conv1_backward", "conv1_bwd_kernel", "", B, H, W);
     hipLaunchKernelGGL(conv1_bwd_kernel, dim3(blocks), dim3(256), 0, s, x, w, bias, dyp, dw, db, B, H, W, Hp, Wp, scratch);
   } else if (route) {
@@ -543,7 +543,7 @@ void unpool_relu_backward(hipStream_t s, const float* dpooled, const float* pool
   const int C4 = C / 4;
   if (dbias && partial && dyb && (256 % C4 == 0)) {     // fused bias gradient: per-workgroup partial rows, then one small column sum
     int blocks = (int)std::min<int64_t>((total + 255) / 256, 2048);             // grid stride 2048*256 is a multiple of every C4 | 256
-    if (!dy && pooledb && C % 8 == 0 && 256 % (C / 8) == 0 && !getenv("AOCR_UNPOOL4")) {
+    if (!dy && pooledb && C % 8 == 0 && 256 % (C / 8) == 0 && !knob::AOCR_UNPOOL4()) {
       const int64_t total8 = total / 2; const int blocks8 = (int)std::min<int64_t>((total8 + 255) / 256, 2048);
       launch_trace("unpool_relu_backward", "unpool8_kernel", "", B * Ho, Wo, C);
       hipLaunchKernelGGL(unpool8_kernel, dim3(blocks8), dim3(256), 0, s, dpooled, idx, dyb, partial, B, Ho, Wo, C, pool, Hp, Wp, pooledb, dpooled16);
@@ -681,7 +681,7 @@ __global__ __launch_bounds__(1024) void bn_partial4_kernel(const float* __restri
     __syncthreads();
   }
 }
-static bool bn_partial4_ok(int C) { const int C4 = C >> 2; return C % 4 == 0 && C4 >= 1 && C4 <= 256 && (C4 & (C4 - 1)) == 0 && !getenv("AOCR_BN_PARTIAL_OLD"); }
+static bool bn_partial4_ok(int C) { const int C4 = C >> 2; return C % 4 == 0 && C4 >= 1 && C4 <= 256 && (C4 & (C4 - 1)) == 0 && !knob::AOCR_BN_PARTIAL_OLD(); }
 
 // sums the per-chunk partials of 16 channels with 256 threads (16 k-slices per channel, LDS tree): returns the totals to the
 // 16 threads with kslice == 0
@@ -1481,7 +1481,7 @@ constexpr int ATTN_NW = 16;
 template <bool BWD>
 static void attn_launch(hipStream_t s, const float* ctx, const float* u, int64_t ldu, const float* a_in, float* p_out, float* o,
                         int64_t ldo, int B, int T, int Hd, int ctx_div, bf16_t* ob, int64_t ldob, const bf16_t* ctxb, const float* cfwd = nullptr, int64_t ldcf = 0) {
-  if (getenv("AOCR_ATTN_BWD_TWO_PASS")) cfwd = nullptr;          // A/B: the streamed backward kernel's two-pass form
+  if (knob::AOCR_ATTN_BWD_TWO_PASS()) cfwd = nullptr;          // A/B: the streamed backward kernel's two-pass form
   const char* const fn = BWD ? "attention_backward" : "attention_forward";
 #define AOCR_ATTN_BF16(NC, RW, STREAM) do {                                                                                   \
     launch_trace(fn, "attn_bf16_kernel", !(STREAM) ? #NC "," #RW ",reg,w16" : (!BWD || cfwd) ? #NC "," #RW ",stream,w16,onepass" : #NC "," #RW ",stream,w16,twopass", B, T, Hd); \
@@ -1491,10 +1491,10 @@ static void attn_launch(hipStream_t s, const float* ctx, const float* u, int64_t
                        ldo, T, ctx_div, ob, ldob, (const bf16_t*)nullptr, (float*)nullptr, (int64_t)0, cfwd, ldcf); } while (0)
   // AOCR_NO_ATTN_BF16=1 (A/B): the fp32-context kernels instead of attn_bf16_kernel / attn_bf16_beam_kernel.  It does NOT cover attn_reg_h512_kernel below, which
   // a bf16 shadow at (Hd = 512, T <= 64) always reaches (tests/test_attention_kernels_gpu.py records it: no_attn_bf16_h512).
-  const bool bf_ok = ctxb && ldu % 4 == 0 && !getenv("AOCR_NO_ATTN_BF16");
+  const bool bf_ok = ctxb && ldu % 4 == 0 && !knob::AOCR_NO_ATTN_BF16();
   if constexpr (!BWD) {
     // beam decode over a long context: one workgroup per IMAGE (its k hypotheses share every context row that is loaded); k <= 5, rows = images x k
-    if (bf_ok && ctx_div > 1 && ctx_div <= 5 && B % ctx_div == 0 && T > 64 && (Hd == 1024 || Hd == 512) && (size_t)ctx_div * T * 4 <= 96 * 1024 && !getenv("AOCR_NO_ATTN_BEAM_GROUP")) {
+    if (bf_ok && ctx_div > 1 && ctx_div <= 5 && B % ctx_div == 0 && T > 64 && (Hd == 1024 || Hd == 512) && (size_t)ctx_div * T * 4 <= 96 * 1024 && !knob::AOCR_NO_ATTN_BEAM_GROUP()) {
       const size_t dyn = (size_t)ctx_div * T * sizeof(float);
       if (Hd == 1024) {
         launch_trace(fn, "attn_bf16_beam_kernel", "2,4,5", B, T, Hd);
@@ -1515,7 +1515,7 @@ static void attn_launch(hipStream_t s, const float* ctx, const float* u, int64_t
   else if (bf_ok && Hd == 512 && T <= 128) AOCR_ATTN_BF16(1, 8, false);
   else if (bf_ok && Hd == 512 && T <= 256) AOCR_ATTN_BF16(1, 16, false);
   else if (bf_ok && Hd == 512) AOCR_ATTN_BF16(1, 4, true);
-  else if (bf_ok && Hd == 1024 && T <= 32 && !getenv("AOCR_ATTN_NW16")) {
+  else if (bf_ok && Hd == 1024 && T <= 32 && !knob::AOCR_ATTN_NW16()) {
     launch_trace(fn, "attn_bf16_kernel", "2,4,reg,w8", B, T, Hd);
     hipLaunchKernelGGL((attn_bf16_kernel<BWD, 2, 4, false, 8>), dim3(B), dim3(512), (size_t)T * sizeof(float), s, ctxb, u, ldu, a_in, p_out, o, ldo, T, ctx_div, ob, ldob);
   }
@@ -1545,7 +1545,7 @@ void attention_backward(hipStream_t s, const float* ctx, const float* q, const f
 }
 
 // Two-context forms (attn_bf16_kernel<..., DUAL>): Hd = 1024, T <= 64, bf16 context and its pre-multiplied copy ctxa = bf16(ctx W_a).  false: shape not taken.
-bool attention_dual_ok(int T, int Hd, const bf16_t* ctxb, const bf16_t* ctxab) { return Hd == 1024 && T <= 64 && ctxb && ctxab && !getenv("AOCR_NO_CHAIN_CTXA"); }
+bool attention_dual_ok(int T, int Hd, const bf16_t* ctxb, const bf16_t* ctxab) { return Hd == 1024 && T <= 64 && ctxb && ctxab && !knob::AOCR_NO_CHAIN_CTXA(); }
 void attention_forward_dual(hipStream_t s, const float* h_top, int64_t ldh, float* a, float* c, int64_t ldc, int B, int T, int ctx_div, bf16_t* cb, int64_t ldcb,
                             const bf16_t* ctxb, const bf16_t* ctxab) {
   launch_trace("attention_forward_dual", "attn_bf16_kernel", T <= 32 ? "2,4,reg,w8,dual" : "2,4,reg,w16,dual", B, T, 1024);

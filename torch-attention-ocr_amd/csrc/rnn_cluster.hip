@@ -675,7 +675,7 @@ bool enc_cluster_plan(int B, int He, int T, int cus, int& G, int& RT, int& group
   G = He / 64;
   RT = 1; groups = (B + 15) / 16;
   if (2 * groups * G > cus && G <= 4) { RT = 2; groups = (B + 31) / 32; }
-  { const char* e = getenv("AOCR_ENC_RT2"); if (e && e[0] == '1' && G <= 4 && B > 16) { RT = 2; groups = (B + 31) / 32; } }      // A/B: two row tiles per group although one fits the chip (read per call, like every A/B switch of this file)
+  if (knob::AOCR_ENC_RT2() && G <= 4 && B > 16) { RT = 2; groups = (B + 31) / 32; }      // A/B: two row tiles per group although one fits the chip
   return true;
 }
 size_t enc_cluster_xbuf_bytes(int B, int He) {                   // forward exchange buffer for the largest plan (RT = 1 granularity covers RT = 2; 8-row groups: twice the slots)
@@ -704,17 +704,16 @@ static int cluster_cus() {
 // dispatch trace (AOCR_TRACE set, read per call; the format of ops_gemm.hip's lines): one stderr line per call with the configuration the call resolved to --
 // the kernel instantiation [G,RT(,ctx)], B T He, the rows per tile, the groups per direction, the launches the gids were split into and whether the exchange is forced remote
 static void cl_trace(const char* fn, const char* kernel, const char* ctx, int B, int T, int He, int G, int RT, int rh, int groups, int passes, int remote) {
-  if (getenv("AOCR_TRACE")) fprintf(stderr, "[aocr] %s: %s[%d,%d%s] %d %d %d G=%d RT=%d rh=%d groups=%d passes=%d remote=%d\n", fn, kernel, G, RT, ctx, B, T, He, G, RT, rh, groups, passes, remote);
+  if (knob::AOCR_TRACE()) fprintf(stderr, "[aocr] %s: %s[%d,%d%s] %d %d %d G=%d RT=%d rh=%d groups=%d passes=%d remote=%d\n", fn, kernel, G, RT, ctx, B, T, He, G, RT, rh, groups, passes, remote);
 }
 void enc_cluster_forward(hipStream_t s, const EncClFwdArgs& a00, int G, int RT, int reserve_cus, int concurrent) {
-  EncClFwdArgs a0 = a00; a0.force_remote = getenv("AOCR_CL_REMOTE") != nullptr;    // testing aid: write-through granules even inside one XCD
+  EncClFwdArgs a0 = a00; a0.force_remote = knob::AOCR_CL_REMOTE();    // testing aid: write-through granules even inside one XCD
   // Half tiles (8 batch rows per group) whenever twice the groups still fit the chip in one launch: the step is bound by the output stores of a CU
   // (store_outputs), and half the rows are half the bytes.  C3: 32 + 32 groups of 4 = all 256 CUs instead of 128; AOCR_ENC_RH16=1: 16-row groups.
   a0.rh = 16;
-  { const char* e = getenv("AOCR_ENC_RH16");
-    const int g8 = (a0.B + 7) / 8;
+  { const int g8 = (a0.B + 7) / 8;
     // (layer wavefront, round 6: `concurrent` launches of this size share the chip -- C5 at 128 strips: two layers x 128 CUs on 16-row groups overlap, two x 256 on 8-row groups would queue)
-    if (!(e && e[0] == '1') && RT == 1 && a0.B > 8 && concurrent * 2 * g8 * G <= cluster_cus() - reserve_cus) { a0.rh = 8; a0.groups = g8; a0.gslot = a00.gslot * 2; } }
+    if (!knob::AOCR_ENC_RH16() && RT == 1 && a0.B > 8 && concurrent * 2 * g8 * G <= cluster_cus() - reserve_cus) { a0.rh = 8; a0.groups = g8; a0.gslot = a00.gslot * 2; } }
   const int per_pass = std::max(8, (cluster_cus() - reserve_cus) / (8 * G) * 8);          // groups (gids) one launch can keep resident; reserve_cus: compute units left to a co-resident collective (model.h: comm_reserved_cus)
   cl_trace("enc_cluster_forward", "enc_cl_fwd_kernel", a0.d[0].ctx ? ",ctx" : "", a0.B, a0.T, a0.He, G, RT, a0.rh, a0.groups, (2 * a0.groups + per_pass - 1) / per_pass, a0.force_remote);
   for (int g0 = 0; g0 < 2 * a0.groups; g0 += per_pass) {
@@ -726,11 +725,11 @@ void enc_cluster_forward(hipStream_t s, const EncClFwdArgs& a00, int G, int RT, 
   }
 }
 void enc_cluster_backward(hipStream_t s, const EncClBwdArgs& a00, int G, int RT, int reserve_cus, int concurrent) {
-  EncClBwdArgs a0 = a00; a0.force_remote = getenv("AOCR_CL_REMOTE") != nullptr;
+  EncClBwdArgs a0 = a00; a0.force_remote = knob::AOCR_CL_REMOTE();
   // Half tiles as in the forward launch, but only while they leave half the chip free: the hoisted weight-gradient GEMMs run beside this kernel on the
   // side streams (C3: 128 + 128 CUs; 8-row groups there would take all 256).  AOCR_ENC_BWD_RH=8 / 16 forces one.
   a0.rh = 16;
-  { const char* e = getenv("AOCR_ENC_BWD_RH");
+  { const char* e = knob::AOCR_ENC_BWD_RH();
     const int g8 = (a0.B + 7) / 8, cus = cluster_cus() - reserve_cus;
     const bool fits = RT == 1 && a0.B > 8 && concurrent * 2 * g8 * G <= cus;
     if (fits && ((e && e[0] == '8') || (!(e && e[0] == '1') && 2 * g8 * G <= cus / 2))) { a0.rh = 8; a0.groups = g8; a0.gslot = a00.gslot * 2; } }

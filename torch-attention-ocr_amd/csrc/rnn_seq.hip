@@ -280,16 +280,16 @@ bool enc_seq_supported(int B, int He, int blocks_limit) {
 
 void enc_seq_forward(hipStream_t s, const EncSeqFwdArgs& a0) {
   EncSeqFwdArgs a = a0;
-  const char* e = getenv("AOCR_SEQ_ABL"); a.abl = e ? atoi(e) : 0;
+  a.abl = knob::AOCR_SEQ_ABL();
   static unsigned long long* dbg = nullptr;
-  const bool stamp = getenv("AOCR_SEQ_STAMP") != nullptr;
+  const bool stamp = knob::AOCR_SEQ_STAMP();
   if (stamp && !dbg) { (void)hipMalloc(&dbg, 16 * sizeof(unsigned long long)); }
   a.dbg = stamp ? dbg : nullptr;
   const int He = a.He;
   const size_t lds = 8 * SEQ_RING + 8 * SEQ_ZXB + 2 * 16 * (He * 2 + 32);
   dim3 grid(a.B / 16, 2), block(512);
   const bool ctx = a.d[0].ctx != nullptr;
-  if (getenv("AOCR_TRACE")) fprintf(stderr, "[aocr] enc_seq_forward: enc_seq_fwd_kernel[%d%s] %d %d %d\n", He / 32, ctx ? ",ctx" : "", a.B, a.T, He);   // dispatch trace (the format of ops_gemm.hip's lines): [NKS(,ctx)] B T He
+  if (knob::AOCR_TRACE()) fprintf(stderr, "[aocr] enc_seq_forward: enc_seq_fwd_kernel[%d%s] %d %d %d\n", He / 32, ctx ? ",ctx" : "", a.B, a.T, He);   // dispatch trace (the format of ops_gemm.hip's lines): [NKS(,ctx)] B T He
 #define AOCR_SEQ_FWD(NKS)                                                                                          \
   do {                                                                                                             \
     if (ctx) {                                                                                                     \
@@ -497,7 +497,7 @@ void enc_seq_backward(hipStream_t s, const EncSeqBwdArgs& a) {
   const int He = a.He;
   const size_t lds = 8 * SEQ_RING + 2 * 16 * (4 * He * 2 + 32);
   dim3 grid(a.B / 16, 2), block(512);
-  if (getenv("AOCR_TRACE")) fprintf(stderr, "[aocr] enc_seq_backward: enc_seq_bwd_kernel[%d] %d %d %d\n", He / 32, a.B, a.T, He);
+  if (knob::AOCR_TRACE()) fprintf(stderr, "[aocr] enc_seq_backward: enc_seq_bwd_kernel[%d] %d %d %d\n", He / 32, a.B, a.T, He);
 #define AOCR_SEQ_BWD(NKS)                                                                                          \
   do {                                                                                                             \
     (void)hipFuncSetAttribute((const void*)enc_seq_bwd_kernel<NKS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
