@@ -449,6 +449,42 @@ typedef struct aocr_warp {
 int aocr_augment_lines(void* stream, const float* in_dev, const aocr_warp* warp_dev, int32_t n_images, int32_t H, int32_t W,
                        uint64_t seed, uint64_t counter, float* out_dev);
 
+/* ---- scan degradation: elastic displacement, stroke weight, optical blur ---------------------------------------------------
+ * What an affine map cannot do to a rendered glyph: wobble it locally, thicken or starve its strokes, soften its edges.  It runs before
+ * aocr_augment_lines (ink, paper and optics come before the camera's map and the sensor's noise; a blur after the noise would remove it).
+ * in_dev, out_dev: (n_images, 1, H, W) fp32 in 0..255, the layout of aocr_augment_lines; they must not alias.  rec_dev[i]: the record of
+ * image i, composed by the host: the device computes no exp.  Three stages per output pixel (x, y) of image i, every float operation one
+ * rounded single-precision op, in this order:
+ *  1 elastic  nodes every `pitch` pixels, GX = (W-1)/pitch + 2 by GY = (H-1)/pitch + 2 of them (integer divisions); node (gx, gy) draws
+ *             r = splitmix64(base_e + ((i*GY + gy)*GX + gx)), base_e = splitmix64(seed ^ counter*0xD1342543DE82EF95 ^ AOCR_DEGRADE_STREAM)
+ *             (the constant keeps this stream apart from aocr_augment_lines' noise under the same seed and counter);
+ *             u1 = (r >> 40) * 2^-24, u2 = ((r >> 16) & 0xFFFFFF) * 2^-24, dx = amp_x*((u1 + u1) - 1), dy = amp_y*((u2 + u2) - 1);
+ *             gx = x / pitch, f = (float)(x - gx*pitch) * inv_pitch, ax = (f*f)*(3 - (f + f)) (smoothstep: no crease at a cell border); gy, ay
+ *             from y alike; with p q r s = the dx of nodes (gx,gy) (gx+1,gy) (gx,gy+1) (gx+1,gy+1):
+ *             top = (1-ax)*p + ax*q, bot = (1-ax)*r + ax*s, ex = (1-ay)*top + ay*bot; ey from the four dy alike;
+ *             sx = x + ex, sy = y + ey, clamped to [-1, W] and [-1, H] (NaN becomes -1), then the four-tap bilinear rule of
+ *             aocr_augment_lines on in_dev, taps outside the image reading `fill`: E(x, y);
+ *  2 stroke   lo, hi = min, max of E over the 3x3 neighbourhood, coordinates clamped to the image;
+ *             thick >= 0: t = thick, M = (1-t)*E + t*lo (ink is dark: the minimum spreads it);  else t = -thick, M = (1-t)*E + t*hi;
+ *  3 blur     Bh(x,y) = w0*M(x,y), then for k = 1..4 in turn Bh = Bh + wk*(M(x-k,y) + M(x+k,y)), coordinates clamped to the image;
+ *             Bv from Bh alike along y;  out = min(max(Bv, 0), 255).
+ * The record (0, 0, pitch, 1/pitch, 0, {1,0,0,0,0}, fill) returns in_dev bit for bit; amp_x = amp_y = 0 switches stage 1 off at any pitch.
+ * 1 <= H, W <= 16384; n_images <= 65535; n_images == 0 is a no-op.  Bad sizes, NULL or aliased pointers return an error before anything is
+ * enqueued.  The records are device memory, which the call does not read: a record with pitch < 2 is rejected by the hosts that compose
+ * records (aocr/degrade.py, lua/augment.lua) before they upload it, and the kernel leaves the image of such a record unwritten.
+ * One launch; no intermediate image goes through HBM.  The call only enqueues; the result does not depend on launch geometry. */
+#define AOCR_DEGRADE_STREAM 0x4445475241444531ull
+typedef struct aocr_degrade {
+  float amp_x, amp_y;    /* elastic amplitude in pixels, >= 0: a node moves its neighbourhood by up to this much */
+  int32_t pitch;         /* spacing of the displacement nodes in pixels, >= 2 */
+  float inv_pitch;       /* 1/pitch, computed on the host and cast to fp32 */
+  float thick;           /* in [-1, 1]: > 0 darkens (thickens) strokes, < 0 lightens (thins) them */
+  float taps[5];         /* w0..w4 of the symmetric 9-tap blur, normalised on the host in float64 (w0 + 2 (w1+..+w4) = 1) and cast to fp32 */
+  float fill;            /* value of the source outside the image, 0..255 */
+} aocr_degrade;
+int aocr_degrade_lines(void* stream, const float* in_dev, const aocr_degrade* rec_dev, int32_t n_images, int32_t H, int32_t W,
+                       uint64_t seed, uint64_t counter, float* out_dev);
+
 /* ---- synthetic word lines: lexicon words rendered from a glyph atlas into a batch of line crops and its targets ---------
  * The reference's training set (train.lua:21) is rendered dictionary words stretched to 32 x 100; this renders such crops where the
  * train step reads them.  out_dev: (n_images, 1, H, W) fp32 in 0..255, the layout aocr_preprocess_lines writes and aocr_augment_lines

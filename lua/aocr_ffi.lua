@@ -89,6 +89,8 @@ typedef struct aocr_image_desc { int64_t offset; int32_t height, width, channels
 int aocr_preprocess_lines(void* stream, const uint8_t* src_dev, const aocr_image_desc* desc_dev, int32_t n_images, int32_t out_h, int32_t out_w, float* out_dev);
 typedef struct aocr_warp { float m00, m01, m02; float m10, m11, m12; float gain, offset; float fill; float noise; } aocr_warp;
 int aocr_augment_lines(void* stream, const float* in_dev, const aocr_warp* warp_dev, int32_t n_images, int32_t H, int32_t W, uint64_t seed, uint64_t counter, float* out_dev);
+typedef struct aocr_degrade { float amp_x, amp_y; int32_t pitch; float inv_pitch; float thick; float taps[5]; float fill; } aocr_degrade;
+int aocr_degrade_lines(void* stream, const float* in_dev, const aocr_degrade* rec_dev, int32_t n_images, int32_t H, int32_t W, uint64_t seed, uint64_t counter, float* out_dev);
 typedef struct aocr_glyph_atlas { const uint8_t* pixels_dev; const uint8_t* advance_dev; int32_t n_faces, n_glyphs, gh, gw; } aocr_glyph_atlas;
 typedef struct aocr_synth_style { int32_t word, face; float spacing; float sx, sy; float x0, y0; float fg, bg; } aocr_synth_style;
 int aocr_synth_lines(void* stream, const aocr_lexicon* lex, const aocr_glyph_atlas* atlas, const aocr_synth_style* style_dev, int32_t n_images, int32_t H, int32_t W, int32_t L, float* out_dev, int32_t* targets_dev, int32_t* targets_eval_dev);

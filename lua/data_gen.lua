@@ -61,6 +61,15 @@ local function preprocess(items, imgW, augment, counter)
     local src_dev, desc_dev, out_dev = A.device_bytes(total), A.device_bytes(n * ffi.sizeof('aocr_image_desc')), A.device_bytes(n * 32 * imgW * 4)
     A.upload(src_dev, src, total); A.upload(desc_dev, desc, n * ffi.sizeof('aocr_image_desc'))
     A.check(A.lib.aocr_preprocess_lines(nil, src_dev:as('uint8_t*'), desc_dev:as('aocr_image_desc*'), n, 32, imgW, out_dev:as('float*')), 'aocr_preprocess_lines')
+    if augment and augment.degrade then                                    -- ink, paper and optics first: elastic, stroke weight, blur
+        local dg = augment.degrade
+        local rec, rec_bytes = dg:params(n, 32, imgW, counter), n * ffi.sizeof('aocr_degrade')
+        local rec_dev, deg_dev = A.device_bytes(rec_bytes), A.device_bytes(n * 32 * imgW * 4)
+        A.upload(rec_dev, rec, rec_bytes)
+        A.check(A.lib.aocr_degrade_lines(nil, out_dev:as('float*'), rec_dev:as('aocr_degrade*'), n, 32, imgW, dg.seed, counter, deg_dev:as('float*')), 'aocr_degrade_lines')
+        out_dev, deg_dev = deg_dev, out_dev
+        rec_dev:free(); deg_dev:free()
+    end
     if augment then                                                        -- warp / contrast / noise where the batch already is
         local warp, warp_bytes = augment:params(n, 32, imgW, counter), n * ffi.sizeof('aocr_warp')
         local warp_dev, aug_dev = A.device_bytes(warp_bytes), A.device_bytes(n * 32 * imgW * 4)

@@ -10,6 +10,8 @@ from .model import Model, eval_word_err_rate, numlist2str, encoder_columns, GROU
 from . import synth
 from . import data
 from .data import DataGen
+from . import degrade
+from .degrade import Degrader
 from . import augment
 from .augment import Augmenter
 from . import synth_lines
@@ -20,5 +22,5 @@ from . import dictionary
 from . import t7, checkpoint
 from .dictionary import Trie, load_dictionary, build_trie, levenshtein, Lexicon, load_lexicon
 
-__all__ = ["Model", "DataGen", "Augmenter", "augment", "GlyphAtlas", "SynthGen", "synth_lines", "page", "SegmentParams", "segment_page_device", "crop_lines_device", "SkewParams", "estimate_skew_device", "deskew_page_device", "FlattenParams", "flatten_page_device", "LayoutParams", "ink_integral_device", "layout_page_device", "CleanParams", "label_components_device", "clean_page_device", "source_corners", "rotate_page_device", "estimate_orientation_device", "unrotate_boxes", "RectifyParams", "find_page_quad_device", "rectify_plan", "warp_page_device", "warp_points", "GlyphParams", "ScaleParams", "estimate_glyph_size_device", "resize_page_device", "scale_plan", "unscale_points", "CurlParams", "estimate_curl_device", "dewarp_page_device", "curl_shift_q8", "uncurl_points", "source_points", "data", "dictionary", "t7", "checkpoint", "Trie", "load_dictionary", "build_trie", "levenshtein", "Lexicon", "load_lexicon", "AocrError", "Config", "COMPUTE_F32", "COMPUTE_BF16", "lib", "last_error", "check", "ptr",
+__all__ = ["Model", "DataGen", "Augmenter", "augment", "Degrader", "degrade", "GlyphAtlas", "SynthGen", "synth_lines", "page", "SegmentParams", "segment_page_device", "crop_lines_device", "SkewParams", "estimate_skew_device", "deskew_page_device", "FlattenParams", "flatten_page_device", "LayoutParams", "ink_integral_device", "layout_page_device", "CleanParams", "label_components_device", "clean_page_device", "source_corners", "rotate_page_device", "estimate_orientation_device", "unrotate_boxes", "RectifyParams", "find_page_quad_device", "rectify_plan", "warp_page_device", "warp_points", "GlyphParams", "ScaleParams", "estimate_glyph_size_device", "resize_page_device", "scale_plan", "unscale_points", "CurlParams", "estimate_curl_device", "dewarp_page_device", "curl_shift_q8", "uncurl_points", "source_points", "data", "dictionary", "t7", "checkpoint", "Trie", "load_dictionary", "build_trie", "levenshtein", "Lexicon", "load_lexicon", "AocrError", "Config", "COMPUTE_F32", "COMPUTE_BF16", "lib", "last_error", "check", "ptr",
            "param_table", "eval_word_err_rate", "numlist2str", "encoder_columns", "GROUPS", "synth"]

@@ -219,6 +219,7 @@ SIGNATURES = {
     "aocr_lexicon_nearest": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "aocr_preprocess_lines": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "aocr_augment_lines": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_uint64, C.c_uint64, _vp]),
+    "aocr_degrade_lines": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_uint64, C.c_uint64, _vp]),
     "aocr_synth_lines": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "aocr_segment_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
     "aocr_segment_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),

@@ -13,6 +13,7 @@ import torch
 
 from . import synth
 from ._lib import check, lib, ptr
+from .degrade import Degrader
 
 PARAM_STREAM = 0x41554700          # stream of the per-image uniforms: counter_uniform(seed, PARAM_STREAM + counter, 8 n)
 
@@ -50,10 +51,17 @@ class Augmenter:
         gain = g    offset = 128 (1 - g) + b            fill, noise: the constructor's
 
     (det A = 1 / (sx sy)).  The ten values are composed in float64 and cast once to fp32; negative zeros are normalised to +0.
+
+    ``degrade``: a ``Degrader`` (aocr/degrade.py) whose elastic displacement, stroke weight and blur ``apply`` runs first, under the same
+    counter and on the same stream: ink, paper and optics come before the camera's map and the sensor's noise (a blur after the noise would
+    remove it).  None: this stage alone.
     """
 
     def __init__(self, rotate_deg=0.0, shear=0.0, scale=1.0, translate=(0.0, 0.0), contrast=1.0, brightness=0.0, noise=0.0,
-                 fill=255.0, seed=910820):
+                 fill=255.0, seed=910820, degrade=None):
+        if degrade is not None and not isinstance(degrade, Degrader):
+            raise TypeError("degrade is an aocr.Degrader or None")
+        self.degrade = degrade
         if scale <= 0 or contrast <= 0:
             raise ValueError("scale and contrast are ratios > 0 (1 = no change)")
         self.rotate_deg, self.shear, self.scale = float(rotate_deg), float(shear), float(scale)
@@ -88,6 +96,8 @@ class Augmenter:
         """a new ``(n,1,H,W)`` fp32 device tensor: ``images_dev`` under the records and the noise field of batch ``counter``."""
         if not (images_dev.is_cuda and images_dev.dtype == torch.float32 and images_dev.dim() == 4 and images_dev.shape[1] == 1):
             raise ValueError("apply() takes a (n,1,H,W) fp32 device tensor (there is no CPU fallback)")
+        if self.degrade is not None:
+            images_dev = self.degrade.apply(images_dev, counter, stream)
         images_dev = images_dev.contiguous()
         n, _, H, W = images_dev.shape
         if n == 0:

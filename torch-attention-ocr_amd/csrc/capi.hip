@@ -762,6 +762,17 @@ int aocr_augment_lines(void* stream, const float* in_dev, const aocr_warp* warp_
   return check_launch("aocr_augment_lines");
 }
 
+int aocr_degrade_lines(void* stream, const float* in_dev, const aocr_degrade* rec_dev, int32_t n_images, int32_t H, int32_t W, uint64_t seed,
+                       uint64_t counter, float* out_dev) {
+  REQUIRE(in_dev && rec_dev && out_dev, "NULL argument");
+  REQUIRE(in_dev != out_dev, "in_dev and out_dev must not alias");
+  REQUIRE(n_images >= 0 && H >= 1 && W >= 1 && H <= 16384 && W <= 16384, "bad sizes: n_images=%d H=%d W=%d (H, W in 1..16384)", n_images, H, W);
+  REQUIRE(n_images <= 65535, "n_images=%d: at most 65535 images per call", n_images);
+  if (n_images == 0) return 0;
+  degrade_lines((hipStream_t)stream, in_dev, rec_dev, n_images, H, W, seed, counter, out_dev);
+  return check_launch("aocr_degrade_lines");
+}
+
 int aocr_synth_lines(void* stream, const aocr_lexicon* lex, const aocr_glyph_atlas* atlas, const aocr_synth_style* style_dev, int32_t n_images,
                      int32_t H, int32_t W, int32_t L, float* out_dev, int32_t* targets_dev, int32_t* targets_eval_dev) {
   REQUIRE(lex, "lexicon is NULL");

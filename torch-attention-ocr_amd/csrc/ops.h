@@ -361,6 +361,10 @@ void preprocess_lines(hipStream_t s, const uint8_t* src, const aocr_image_desc* 
 // training augmentation (data.hip): affine warp + gain / offset + counter-based noise of n (1,H,W) images, in != out
 void augment_lines(hipStream_t s, const float* in, const aocr_warp* warp, int n_images, int H, int W, uint64_t seed, uint64_t counter,
                    float* out);
+// scan degradation (degrade.hip; include/aocr.h: aocr_degrade_lines): elastic displacement, stroke weight and blur of n (1,H,W) images in one
+// launch, in != out
+void degrade_lines(hipStream_t s, const float* in, const aocr_degrade* rec, int n_images, int H, int W, uint64_t seed, uint64_t counter,
+                   float* out);
 // synthetic word lines (synth.hip; include/aocr.h: aocr_synth_lines): lexicon rows drawn from a glyph atlas into n (1,H,W) crops, and
 // their targets / targets_eval rows (n, L) unless both are nullptr
 void synth_lines(hipStream_t s, const aocr_lexicon& lex, const aocr_glyph_atlas& atlas, const aocr_synth_style* style, int n_images, int H,
