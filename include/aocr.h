@@ -978,6 +978,74 @@ int aocr_estimate_curl(void* stream, const uint8_t* page_dev, int64_t pitch, int
 int aocr_dewarp_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t group,
                      const int32_t* shifts_dev, int32_t fill, uint8_t* out_dev, int64_t out_pitch);
 
+/* ---- colour pages: the paper colour, and the gray page every other stage reads, in front of aocr_find_page_quad and aocr_flatten_page -----------
+ * A colour scanner or a phone delivers interleaved RGB.  aocr_gray_page replaces the reduction to gray that a caller otherwise does on the
+ * host (3 bytes per pixel read, 1 written, no host sync: the shape does not change), and keeps what that reduction throws away: a pixel's
+ * chroma tells a red form rule, a yellow highlighter stroke or a blue stamp from black ink, so such pixels can be turned into paper before
+ * any profile or threshold sees them.  aocr_estimate_page_colour replaces a host histogram of the page: it finds the colour of the paper, which
+ * aocr_gray_page divides out so that yellowed paper or warm light costs no contrast.  Both are integer arithmetic, specified exactly.
+ * The page: H rows of W pixels of 3 bytes, rows pitch >= 3*W bytes apart, any base address and any pitch (pitch % 3 != 0 included); byte
+ * 3*x + c of a row is channel c (0 R, 1 G, 2 B) of pixel x.  1 <= H, W <= 16384, H*W <= 2^26, the limits of aocr_warp_page.
+ *
+ * aocr_estimate_page_colour (device):
+ *   hist       hist_c[v] = the number of pixels whose channel c is v;
+ *   window     S_c(v) = hist_c[v-2] + ... + hist_c[v+2], bins outside 0..255 counting as 0;
+ *   paper      p_c = the v >= paper_min with the largest S_c(v), the larger v on a tie; 255 when no pixel has channel c >= paper_min;
+ *   output     colour_dev = [p_R, p_G, p_B, 1, 0 x 12].
+ * Only paper_min of params is used; the others must still be valid.  Limit: the mode is taken over the whole picture, so a desk that covers
+ * more of a photograph than the sheet wins it: give the paper in params, or rely on aocr_warp_page and aocr_flatten_page afterwards.
+ * scratch_dev: aocr_colour_scratch_bytes(H, W) bytes, 16-byte aligned, overwritten by the call (0 and an error containing "bad sizes" for
+ * bad sizes).  colour_dev (4-byte aligned) must not overlap the page or the scratch.
+ *
+ * aocr_gray_page (device), for every pixel (r, g, b):
+ *   paper      p = colour_in_dev[0..2] when colour_in_dev is not NULL, read on the device (the output of aocr_estimate_page_colour: no host
+ *              read in between) and clamped to 1..255; otherwise params->paper, or (255, 255, 255) when params->balance is 0.  paper[0] < 0
+ *              (estimate) with balance 1 and no colour_in_dev is an error;
+ *   balance    r' = min(255, (r*255 + p_R/2) / p_R) with integer division, and likewise g', b': p = (255, 255, 255) is the identity;
+ *   chroma     mx, mn = the largest and smallest of r', g', b';  c = mx - mn;  the pixel is coloured when c >= chroma_min;
+ *   hue class  six classes centred on the primaries and secondaries (AOCR_HUE_*):
+ *              mx == r':        2*(g'-b') >= c: YELLOW;  else 2*(b'-g') >  c: MAGENTA;  else RED;
+ *              else mx == g':   2*(r'-b') >  c: YELLOW;  else 2*(b'-r') >= c: CYAN;     else GREEN;
+ *              else:            2*(g'-r') >  c: CYAN;    else 2*(r'-g') >= c: MAGENTA;  else BLUE;
+ *   output     a coloured pixel whose class bit (1 << class) is set in drop becomes fill; otherwise mode 0 gives
+ *              (w_R*r' + w_G*g' + w_B*b' + 128) >> 8 and mode 1 gives mn (any coloured ink on white paper comes out dark);
+ *   counts     colour_out_dev, when not NULL, is overwritten (not accumulated) with [p_R, p_G, p_B, estimated, n_RED, n_YELLOW, n_GREEN,
+ *              n_CYAN, n_BLUE, n_MAGENTA, n_dropped, 0 x 5]: the paper used; estimated = (colour_in_dev[3] != 0), 0 without
+ *              colour_in_dev; n_class = the coloured pixels of the class, dropped or not; n_dropped = the pixels replaced by fill.
+ *              colour_out_dev may be colour_in_dev itself; otherwise the two must not overlap.
+ * Limits: coloured text is dropped together with coloured marks of its class; below chroma_min the hue of a dark pixel is noise, which is
+ * why such a pixel is never dropped.  The luma weights (77, 150, 29) stay within 1 gray level of round(255 * rgb2y): DESIGN.md section 21.
+ * out_dev follows the rules of aocr_deskew_page: H rows of W bytes, out_pitch >= W apart, any alignment; bytes between W and out_pitch are
+ * untouched; it must not overlap the page or the colour words.  No scratch.
+ * All three calls enqueue only, never synchronise or allocate; the results do not depend on launch geometry, atomics order or run (integer
+ * sums only).  NULL pointers, pitch < 3*W, out_pitch < W, weights that are negative or do not sum to 256, mode or balance outside {0, 1},
+ * drop outside 0..63, chroma_min or paper_min outside 1..255, a given paper outside 1..255, fill outside 0..255 or an overlap return an
+ * error that names the argument before anything is enqueued and leave the outputs untouched. */
+#define AOCR_HUE_RED 0
+#define AOCR_HUE_YELLOW 1
+#define AOCR_HUE_GREEN 2
+#define AOCR_HUE_CYAN 3
+#define AOCR_HUE_BLUE 4
+#define AOCR_HUE_MAGENTA 5
+
+typedef struct aocr_colour_params {
+  int32_t weights[3];    /* w_R, w_G, w_B: each >= 0, 256 in sum; (77, 150, 29) is luma, (256, 0, 0) reads the red channel */
+  int32_t mode;          /* 0: the weighted sum; 1: the smallest balanced channel */
+  int32_t balance;       /* 1: divide the paper colour out; 0: the paper is (255, 255, 255) */
+  int32_t paper[3];      /* the paper colour, 1..255 each; paper[0] < 0: estimated (aocr_estimate_page_colour into colour_in_dev) */
+  int32_t paper_min;     /* 1..255: the darkest value the estimate takes for paper */
+  int32_t chroma_min;    /* 1..255: a pixel is coloured when max - min of its balanced channels reaches this */
+  int32_t drop;          /* 0..63: bit (1 << AOCR_HUE_*) set: coloured pixels of that class become fill */
+  int32_t fill;          /* 0..255 */
+} aocr_colour_params;
+
+size_t aocr_colour_scratch_bytes(int32_t H, int32_t W);
+int aocr_estimate_page_colour(void* stream, const uint8_t* rgb_dev, int64_t pitch, int32_t H, int32_t W,
+                              const aocr_colour_params* params, void* scratch_dev, int32_t colour_dev[16]);
+int aocr_gray_page(void* stream, const uint8_t* rgb_dev, int64_t pitch, int32_t H, int32_t W,
+                   const aocr_colour_params* params, const int32_t* colour_in_dev, int32_t* colour_out_dev,
+                   uint8_t* out_dev, int64_t out_pitch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,10 @@ typedef struct aocr_curl_params { int32_t threshold; int32_t light_text; int32_t
 size_t aocr_curl_scratch_bytes(int32_t H, int32_t W, int32_t group, int32_t max_shift);
 int aocr_estimate_curl(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_curl_params* params, void* scratch_dev, int32_t curl_dev[4], int32_t* shifts_dev, uint64_t* scores_dev);
 int aocr_dewarp_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t group, const int32_t* shifts_dev, int32_t fill, uint8_t* out_dev, int64_t out_pitch);
+typedef struct aocr_colour_params { int32_t weights[3]; int32_t mode; int32_t balance; int32_t paper[3]; int32_t paper_min; int32_t chroma_min; int32_t drop; int32_t fill; } aocr_colour_params;
+size_t aocr_colour_scratch_bytes(int32_t H, int32_t W);
+int aocr_estimate_page_colour(void* stream, const uint8_t* rgb_dev, int64_t pitch, int32_t H, int32_t W, const aocr_colour_params* params, void* scratch_dev, int32_t colour_dev[16]);
+int aocr_gray_page(void* stream, const uint8_t* rgb_dev, int64_t pitch, int32_t H, int32_t W, const aocr_colour_params* params, const int32_t* colour_in_dev, int32_t* colour_out_dev, uint8_t* out_dev, int64_t out_pitch);
 ]]
 
 local M = {}

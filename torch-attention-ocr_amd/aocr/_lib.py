@@ -127,6 +127,38 @@ class CurlParams(C.Structure):
         super().__init__(int(threshold), int(light_text), int(group), int(max_shift), int(min_ink), (C.c_int32 * 3)(0, 0, 0))
 
 
+HUE_RED, HUE_YELLOW, HUE_GREEN, HUE_CYAN, HUE_BLUE, HUE_MAGENTA = range(6)      # AOCR_HUE_* of include/aocr.h: the bits of ColourParams.drop
+
+
+class ColourParams(C.Structure):
+    """mirror of `aocr_colour_params` (include/aocr.h): how `aocr_gray_page` turns an RGB page into the gray page the other stages read.
+    weights: (w_R, w_G, w_B), each >= 0 and 256 in sum ((77, 150, 29): luma; (256, 0, 0): the red channel); mode 0: the weighted sum, 1: the
+    smallest balanced channel; balance 1: the paper colour is divided out; paper: (p_R, p_G, p_B) in 1..255, None: estimated on the device
+    (`aocr_estimate_page_colour`, which takes the most frequent value >= paper_min of every channel); a pixel is coloured when the spread
+    of its balanced channels reaches chroma_min; drop: a sum of 1 << HUE_*, the classes whose coloured pixels become `fill`.  The
+    constructor raises ValueError for what the library would turn down."""
+    _fields_ = [("weights", C.c_int32 * 3), ("mode", C.c_int32), ("balance", C.c_int32), ("paper", C.c_int32 * 3)] + \
+               [(n, C.c_int32) for n in ("paper_min", "chroma_min", "drop", "fill")]
+
+    def __init__(self, weights=(77, 150, 29), mode=0, balance=1, paper=None, paper_min=128, chroma_min=64, drop=0, fill=255):
+        w = [int(v) for v in weights]
+        if len(w) != 3 or min(w) < 0 or sum(w) != 256:
+            raise ValueError(f"weights={weights!r}: three integers >= 0 that sum to 256")
+        p = [-1, -1, -1] if paper is None else [int(v) for v in paper]
+        if len(p) != 3 or (paper is not None and not all(1 <= v <= 255 for v in p)):
+            raise ValueError(f"paper={paper!r}: None or three integers in 1..255")
+        mode, balance, paper_min, chroma_min, drop, fill = int(mode), int(balance), int(paper_min), int(chroma_min), int(drop), int(fill)
+        if mode not in (0, 1) or balance not in (0, 1):
+            raise ValueError(f"mode={mode} balance={balance}: 0 or 1 each")
+        if not (1 <= paper_min <= 255 and 1 <= chroma_min <= 255):
+            raise ValueError(f"paper_min={paper_min} chroma_min={chroma_min}: 1..255 each")
+        if not 0 <= drop <= 63:
+            raise ValueError(f"drop={drop}: 0..63, a sum of 1 << HUE_*")
+        if not 0 <= fill <= 255:
+            raise ValueError(f"fill={fill}: 0..255")
+        super().__init__((C.c_int32 * 3)(*w), mode, balance, (C.c_int32 * 3)(*p), paper_min, chroma_min, drop, fill)
+
+
 class ScaleParams:
     """how `Model.recognize_page(scale=...)` brings the text of a page to the size the other stages' defaults were written for
     (`aocr_estimate_glyph_size`, `aocr.scale_plan`, `aocr_resize_page`; plain Python: there is no C struct behind it).  glyph: the
@@ -250,6 +282,9 @@ SIGNATURES = {
     "aocr_curl_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32]),
     "aocr_estimate_curl": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "aocr_dewarp_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _i32, _vp, _i32, _vp, C.c_int64]),
+    "aocr_colour_scratch_bytes": (C.c_size_t, [_i32, _i32]),
+    "aocr_estimate_page_colour": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp]),
+    "aocr_gray_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, _vp, C.c_int64]),
     "aocr_beam_select": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32]),
 }
 

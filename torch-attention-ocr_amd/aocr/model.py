@@ -21,7 +21,7 @@ from . import _lib, dist
 from ._lib import Config, check, lib, ptr
 from .dictionary import edit_distance_device
 from .page import backmap_corners, bucket_width, crop_lines_device, rotate_page_device
-from .page_pipeline import clean_stage, flatten_stage, orient_stage, page_boxes, rectify_stage, scale_stage
+from .page_pipeline import asked, clean_stage, colour_stage, flatten_stage, orient_stage, page_boxes, rectify_stage, scale_stage
 
 PAD, GO, EOS = 1, 2, 3
 GROUPS = ["cnn", "enc_fw", "enc_bw", "dec", "proj"]
@@ -437,14 +437,14 @@ class Model:
             res.word = [lexicon.words[i] if i >= 0 else None for i in res.word_index.tolist()]
         return res
 
-    def _page_boxes(self, page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev):
+    def _page_boxes(self, page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None):
         """the middle of recognize_page (aocr.page_pipeline.page_boxes), reached through the model so that a caller can wrap it."""
-        return page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev)
+        return page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev)
 
     def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None, flatten=None,
-                       layout=None, clean=None, orient=None, rectify=None, scale=None, dewarp=None):
+                       layout=None, clean=None, orient=None, rectify=None, scale=None, dewarp=None, colour=None):
         """Read a scanned page: segment it into word boxes (aocr_segment_page), crop them (aocr_crop_lines) and recognise the crops.
-        page: a uint8 (H,W) numpy array or tensor (gray; a 3-D array raises ValueError: colour pages are out of scope).  params: an
+        page: a uint8 (H,W) numpy array or tensor (gray; a 3-D array raises ValueError unless `colour` is asked for: see below).  params: an
         `aocr.SegmentParams` (default: Otsu threshold, dark text).  The counts and boxes are read back once (the one sync), then the boxes are
         bucketed by crop width: `width` an int gives one bucket; otherwise each box gets DataGen's width rule (aocr.page.bucket_width with
         width_step, capped at max_img_w).  Every bucket is cropped and recognised in chunks of at most batch_size rows through
@@ -526,7 +526,33 @@ class Model:
         (aocr.page.uncurl_points: x stays, y moves by the column's shift); boxes are in dewarped-page coordinates.  source_corners,
         photo_corners and unscaled_corners then start from uncurled_corners with y rounded half up (floor(y + 0.5)); source_boxes stays an
         axis-aligned box and ignores the curl.  Limits (max_shift against the line pitch, errors adding up along the chain, empty margins,
-        no foreshortening): DESIGN.md section 20."""
+        no foreshortening): DESIGN.md section 20.
+        colour: None or False (the default) takes a gray page, and a 3-D page raises ValueError.  Anything else takes a colour page, a uint8
+        (H, W, 3) RGB array or tensor as aocr.data.load_image returns it for a colour file (anything else then raises ValueError), and
+        reduces it to gray on the device FIRST, before rectify (aocr_estimate_page_colour, aocr_gray_page): the colour of the paper is
+        estimated and divided out of every channel, so that yellowed paper or warm light costs no contrast, and the gray value is the luma
+        of the balanced pixel.  An `aocr.ColourParams` is used as given: with drop, the coloured pixels of the chosen hue classes (a red
+        form rule, a highlighter stroke, a blue stamp: 1 << aocr.HUE_RED ...) become fill before any threshold or profile sees them; mode 1
+        takes the darkest channel instead, so that coloured ink comes out dark.  True: the defaults, nothing dropped, fill = paper (0 with
+        light_text, else 255), and with light_text no balancing.  The shape does not change, so boxes and corner fields are unaffected; the
+        sixteen colour words come back with the existing readback (no additional sync).  The namespace then also carries colour_paper (the
+        three paper values divided out), colour_balanced (whether the page was balanced: the params' balance), colour_hues (6) int64: the coloured pixels
+        of the classes RED, YELLOW, GREEN, CYAN, BLUE, MAGENTA, and colour_dropped (the pixels replaced by fill).  Limits (a desk larger
+        than the sheet wins the paper estimate; coloured text goes with coloured marks of its class): DESIGN.md section 21."""
+        if asked(colour):
+            ok = isinstance(page, (np.ndarray, torch.Tensor)) and len(page.shape) == 3 and page.shape[2] == 3 and \
+                page.dtype == (np.uint8 if isinstance(page, np.ndarray) else torch.uint8)
+            if not ok:
+                raise ValueError(f"colour={colour!r}: page must be a uint8 (H, W, 3) RGB array or tensor, got {getattr(page, 'dtype', type(page))} "
+                                 f"{tuple(getattr(page, 'shape', ()))}")
+            if not (colour is True or isinstance(colour, _lib.ColourParams)):
+                raise ValueError(f"colour={colour!r}: None, False, True or an aocr.ColourParams")
+            if isinstance(page, np.ndarray):
+                page = torch.from_numpy(np.ascontiguousarray(page))
+            seg = params if params is not None else _lib.SegmentParams()
+            page, colour_dev, colour_used = colour_stage(page.to(self.device), self._stream(), seg, colour)
+        else:
+            colour_dev = None
         if isinstance(page, np.ndarray):
             if page.ndim != 2 or page.dtype != np.uint8:
                 raise ValueError(f"page must be a uint8 (H, W) array, got {page.dtype} {page.shape}: colour pages are out of scope")
@@ -543,7 +569,7 @@ class Model:
         page, scl = scale_stage(page, stream, seg, scale)
         page0, clean_dev = clean_stage(page, stream, seg, clean)
         page, quarter, orient_runs = orient_stage(page0, stream, seg, orient)
-        middle = (stream, seg, max_boxes, deskew, dewarp, layout, clean_dev)
+        middle = (stream, seg, max_boxes, deskew, dewarp, layout, clean_dev) + (() if colour_dev is None else (colour_dev,))
         st = self._page_boxes(page, *middle)
         orient_scores = None
         if orient is True:
@@ -594,6 +620,9 @@ class Model:
         if st.cleaned is not None:
             res.clean_components, res.clean_specks, res.clean_rules, res.clean_ink_removed = (int(st.cleaned[0]), int(st.cleaned[1]),
                                                                                               int(st.cleaned[2]), int(st.cleaned[5]))
+        if st.colour is not None:
+            res.colour_paper, res.colour_balanced = tuple(int(v) for v in st.colour[:3]), bool(colour_used.balance)
+            res.colour_hues, res.colour_dropped = st.colour[4:10].astype(np.int64), int(st.colour[10])
         curl = skew = turn = None                                   # what each stage left behind for aocr.page.backmap_corners
         if st.curl is not None:
             res.curl_shifts, res.curl_group = st.curl[4:].astype(np.int32), st.curl_group

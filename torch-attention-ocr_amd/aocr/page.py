@@ -15,7 +15,10 @@ median of min(w, h) over the component boxes), `scale_plan` (host only) and `res
 resampling) after the flattening; `unscale_points` takes points back to the page before resizing.  A shear takes out one slope: the
 curved lines of a page bending into a book's gutter go through `estimate_curl_device` (`aocr_estimate_curl`: the row shift between
 neighbouring column groups by correlation) and `dewarp_page_device` (`aocr_dewarp_page`: every column moved by its shift) after the
-deskew; `uncurl_points` takes points back to the page before it."""
+deskew; `uncurl_points` takes points back to the page before it.  All of them read a gray page: a colour page, (H, W, 3) RGB, goes through
+`estimate_page_colour_device` (`aocr_estimate_page_colour`: the paper colour, the mode of every channel) and `gray_page_device`
+(`aocr_gray_page`: the paper divided out, a weighted sum or the darkest channel, and the coloured pixels of chosen hue classes -- a red
+form rule, a highlighter stroke, a stamp -- turned into paper) before any of them; the shape does not change, so no box needs a way back."""
 from __future__ import annotations
 
 import ctypes as C
@@ -24,7 +27,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import Box, CleanParams, CurlParams, FlattenParams, GlyphParams, LayoutParams, RectifyParams, ScaleParams, SegmentParams, SkewParams, check, lib, ptr
+from ._lib import Box, CleanParams, ColourParams, CurlParams, FlattenParams, GlyphParams, LayoutParams, RectifyParams, ScaleParams, SegmentParams, SkewParams, check, lib, ptr
 
 IMG_H = 32
 MIN_ASPECT = 0.5
@@ -51,6 +54,25 @@ def _page_view(page_dev):
         page_dev = page_dev.contiguous()
         pitch = W
     return page_dev, int(pitch)
+
+
+def _rgb_view(rgb_dev):
+    """`_page_view` for a colour page: an (H, W, 3) uint8 device tensor whose pixels are contiguous (3 bytes, channel stride 1, pixel stride
+    3); a view of a wider image is taken as it is: its row stride is the pitch."""
+    if not (isinstance(rgb_dev, torch.Tensor) and rgb_dev.dim() == 3 and rgb_dev.shape[2] == 3 and rgb_dev.dtype == torch.uint8):
+        raise ValueError("page must be a 3-D uint8 tensor (H, W, 3)")
+    if not rgb_dev.is_cuda:
+        raise ValueError("page must be on the device")
+    H, W, _ = rgb_dev.shape
+    if H < 1 or W < 1:
+        raise ValueError(f"empty page {tuple(rgb_dev.shape)}")
+    if rgb_dev.stride(2) != 1 or (W > 1 and rgb_dev.stride(1) != 3):
+        rgb_dev = rgb_dev.contiguous()
+    pitch = rgb_dev.stride(0) if H > 1 else 3 * W
+    if pitch < 3 * W:                                        # an expanded (stride 0) view
+        rgb_dev = rgb_dev.contiguous()
+        pitch = 3 * W
+    return rgb_dev, int(pitch)
 
 
 def _scratch(query, dev, *args):
@@ -383,6 +405,46 @@ def uncurl_points(x, y, shifts, group):
     return x.astype(np.float64), np.asarray(y, np.float64) + curl_shift_q8(x, shifts, group) / 256.0
 
 
+def estimate_page_colour_device(rgb_dev, params=None, stream=None):
+    """colour (16) int32 device tensor: the paper colour p_R, p_G, p_B of an (H, W, 3) uint8 RGB page, 1, then zeros
+    (`aocr_estimate_page_colour`): for every channel the value >= params.paper_min whose five-bin window of the channel's histogram holds
+    the most pixels.  params: a `ColourParams` (default: paper_min 128).  Enqueues only.  stream: as for `segment_page_device`, the current
+    torch stream; the scratch is freed when this returns."""
+    rgb_dev, pitch = _rgb_view(rgb_dev)
+    H, W, _ = rgb_dev.shape
+    params = params if params is not None else ColourParams()
+    dev = rgb_dev.device
+    scratch = _scratch("aocr_colour_scratch_bytes", dev, H, W)
+    colour = torch.zeros(16, dtype=torch.int32, device=dev)
+    check(lib.aocr_estimate_page_colour(_stream(stream, dev), ptr(rgb_dev), pitch, H, W, C.byref(params), ptr(scratch), ptr(colour)),
+          "aocr_estimate_page_colour")
+    return colour
+
+
+def gray_page_device(rgb_dev, params=None, colour=None, stream=None, counts=False):
+    """a new (H, W) uint8 device tensor: the (H, W, 3) uint8 RGB page reduced to gray by `aocr_gray_page` (the paper divided out, the
+    weighted sum or the darkest channel, the coloured pixels of the classes in params.drop replaced by params.fill); with counts=True
+    (gray, words (16) int32: the paper used, whether it was estimated, the coloured pixels of the six hue classes, the pixels dropped, zeros).
+    params: a `ColourParams` (default: luma weights, balanced, nothing dropped).  colour: the device tensor of `estimate_page_colour_device`
+    (its paper is read on the device: no host sync); None: the paper of params, or, when params asks for an estimate, the estimate is
+    enqueued here first.  Enqueues only.  stream: as for `segment_page_device`."""
+    rgb_dev, pitch = _rgb_view(rgb_dev)
+    H, W, _ = rgb_dev.shape
+    params = params if params is not None else ColourParams()
+    dev = rgb_dev.device
+    if colour is None and params.balance and params.paper[0] < 0:
+        colour = estimate_page_colour_device(rgb_dev, params, stream)
+    if colour is not None:
+        assert isinstance(colour, torch.Tensor) and colour.dtype == torch.int32 and colour.device == dev and colour.numel() >= 16, \
+            "colour must be 16 int32 words on the page's device"
+        colour = colour.contiguous()
+    words = torch.empty(16, dtype=torch.int32, device=dev) if counts else None
+    out = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    check(lib.aocr_gray_page(_stream(stream, dev), ptr(rgb_dev), pitch, H, W, C.byref(params), ptr(colour), ptr(words), ptr(out), W),
+          "aocr_gray_page")
+    return (out, words) if counts else out
+
+
 def find_page_quad_device(page_dev, threshold=-1, dark_paper=0, stream=None):
     """quad (16) int32 device tensor: x y of the corners TL, TR, BR, BL of the paper, the threshold used, the sheet's area, components found,
     valid, 0, 0, 0, 0 (`aocr_find_page_quad`): the extremes along the diagonals of the largest 8-connected component of (v > threshold), or
@@ -566,6 +628,6 @@ def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
     return min(img_w, int(max_img_w))
 
 
-__all__ = ["backmap_corners", "CurlParams", "estimate_curl_device", "dewarp_page_device", "curl_shift_q8", "uncurl_points", "source_points", "box_corners", "GlyphParams", "ScaleParams", "estimate_glyph_size_device", "resize_page_device", "scale_plan", "unscale_points", "RectifyParams", "find_page_quad_device", "rectify_plan", "warp_page_device", "warp_points", "SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "CleanParams", "Box", "label_components_device", "clean_page_device", "segment_page_device", "crop_lines_device",
+__all__ = ["backmap_corners", "ColourParams", "estimate_page_colour_device", "gray_page_device", "CurlParams", "estimate_curl_device", "dewarp_page_device", "curl_shift_q8", "uncurl_points", "source_points", "box_corners", "GlyphParams", "ScaleParams", "estimate_glyph_size_device", "resize_page_device", "scale_plan", "unscale_points", "RectifyParams", "find_page_quad_device", "rectify_plan", "warp_page_device", "warp_points", "SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "CleanParams", "Box", "label_components_device", "clean_page_device", "segment_page_device", "crop_lines_device",
            "estimate_skew_device", "deskew_page_device", "flatten_page_device", "ink_integral_device", "layout_page_device", "source_corners",
            "rotate_page_device", "estimate_orientation_device", "unrotate_boxes", "unrotate_points", "bucket_width"]

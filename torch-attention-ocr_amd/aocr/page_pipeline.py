@@ -1,5 +1,5 @@
-"""The stage chain of `Model.recognize_page` in front of the recogniser, as plain functions of the page: rectify, flatten, scale, clean and
-the quarter turn (one function each, in that order), then `page_boxes`: deskew, dewarp, layout and segmentation down to the boxes on the
+"""The stage chain of `Model.recognize_page` in front of the recogniser, as plain functions of the page: colour, rectify, flatten, scale, clean
+and the quarter turn (one function each, in that order), then `page_boxes`: deskew, dewarp, layout and segmentation down to the boxes on the
 host.  Every function takes the page on the device, the raw handle of the current torch stream and the page's resolved `SegmentParams`,
 enqueues on that stream, and returns the page with a small record of what it did (None when the stage was not asked for).  What needs a
 model -- the which-way-up probe, the crop-and-recognise loop, the lexicon -- stays in `Model`; the way back from box corners to the page as
@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from .page import (clean_page_device, deskew_page_device, dewarp_page_device, estimate_curl_device, estimate_glyph_size_device,
-                   estimate_orientation_device, estimate_skew_device, find_page_quad_device, flatten_page_device, layout_page_device,
+                   estimate_orientation_device, gray_page_device, estimate_skew_device, find_page_quad_device, flatten_page_device, layout_page_device,
                    rectify_plan, resize_page_device, rotate_page_device, scale_plan, segment_page_device, warp_page_device)
 
 MAX_BLOCKS = 256
@@ -41,6 +41,16 @@ def read_named(pieces):
         n = sum(t.numel() for t in ts)
         out[k], at = host[at:at + n], at + n
     return out
+
+
+def colour_stage(page, stream, seg, colour):
+    """(gray page, the sixteen colour words on the device: they come back with the boxes' readback, the ColourParams used) of an (H, W, 3) RGB
+    page.  colour True:
+    the defaults, filled with paper; with light text the page is not balanced (its most frequent colour is no paper to divide by)."""
+    if not asked(colour):
+        return page, None, None
+    cp = colour if isinstance(colour, _lib.ColourParams) else _lib.ColourParams(fill=paper(seg), balance=0 if seg.light_text else 1)
+    return gray_page_device(page, cp, None, stream, counts=True) + (cp,)
 
 
 def rectify_stage(page, stream, seg, rectify):
@@ -120,10 +130,10 @@ def orient_stage(page, stream, seg, orient):
     return rotate_page_device(page, quarter, None, stream), quarter, runs
 
 
-def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev):
+def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None):
     """the middle of recognize_page, from the deskew to the boxes on the host: everything that reads the page in its final orientation and
     has to be redone when recognize_page(orient=True) turns the page by another half turn.  Returns a namespace: page, boxes_dev, rows, counts,
-    n, truncated; skew, cleaned, curl (the words read back, None without the stage), curl_group; lay, blocks, block_id, nb, lcounts
+    n, truncated; skew, cleaned, curl, colour (the words read back, None without the stage), curl_group; lay, blocks, block_id, nb, lcounts
     (None without layout)."""
     st = SimpleNamespace(curl_group=None, lay=None, blocks=None, block_id=None, nb=None, lcounts=None)
     skew_dev = curl_dev = None
@@ -137,7 +147,7 @@ def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev):
         page = dewarp_page_device(page, shifts_dev, cp.group, paper(seg), stream)
         curl_dev, st.curl_group = [words_dev, shifts_dev], int(cp.group)      # the four curl words, then the ng group shifts
     st.page = page
-    riders = dict(skew=skew_dev, cleaned=clean_dev, curl=curl_dev)            # what comes back with the first readback, whichever it is
+    riders = dict(skew=skew_dev, cleaned=clean_dev, curl=curl_dev, colour=colour_dev)            # what comes back with the first readback, whichever it is
     if asked(layout):
         st.lay = layout if isinstance(layout, _lib.LayoutParams) else _lib.LayoutParams()
         blocks_dev, lcounts_dev, info_dev = layout_page_device(page, st.lay, seg.threshold, seg.light_text, MAX_BLOCKS, stream)
@@ -179,5 +189,5 @@ def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev):
         st.n = int(min(st.counts[0], max_boxes))
         st.rows = st.boxes_dev[:st.n].cpu().numpy()
         st.truncated = bool(st.counts[0] > max_boxes)
-    st.skew, st.cleaned, st.curl = got.get("skew"), got.get("cleaned"), got.get("curl")
+    st.skew, st.cleaned, st.curl, st.colour = got.get("skew"), got.get("cleaned"), got.get("curl"), got.get("colour")
     return st

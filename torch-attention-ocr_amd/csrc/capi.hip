@@ -1171,4 +1171,65 @@ int aocr_dewarp_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32
   return check_launch("aocr_dewarp_page");
 }
 
+size_t aocr_colour_scratch_bytes(int32_t H, int32_t W) { return scratch_size_ok(H, W) ? colour_scratch_bytes() : 0; }
+
+static int check_rgb(const uint8_t* rgb_dev, int64_t pitch, int32_t H, int32_t W) {
+  REQUIRE(rgb_dev, "rgb_dev is NULL");
+  REQUIRE(page_size_ok(H, W), "bad page size H=%d W=%d: 1..16384 each, H*W <= 2^26", H, W);
+  REQUIRE(pitch >= 3 * (int64_t)W, "pitch=%lld is smaller than 3 * W=%d", (long long)pitch, W);
+  return 0;
+}
+
+static int check_colour_params(const aocr_colour_params* p) {
+  REQUIRE(p, "params is NULL");
+  REQUIRE(p->weights[0] >= 0 && p->weights[1] >= 0 && p->weights[2] >= 0 && p->weights[0] + p->weights[1] + p->weights[2] == 256,
+          "weights=%d %d %d: each >= 0 and 256 in sum", p->weights[0], p->weights[1], p->weights[2]);
+  REQUIRE(p->mode == 0 || p->mode == 1, "mode=%d: 0 or 1", p->mode);
+  REQUIRE(p->balance == 0 || p->balance == 1, "balance=%d: 0 or 1", p->balance);
+  if (p->paper[0] >= 0)
+    REQUIRE(p->paper[0] >= 1 && p->paper[0] <= 255 && p->paper[1] >= 1 && p->paper[1] <= 255 && p->paper[2] >= 1 && p->paper[2] <= 255,
+            "paper=%d %d %d: 1..255 each, or paper[0] < 0 for an estimate", p->paper[0], p->paper[1], p->paper[2]);
+  REQUIRE(p->paper_min >= 1 && p->paper_min <= 255, "paper_min=%d: 1..255", p->paper_min);
+  REQUIRE(p->chroma_min >= 1 && p->chroma_min <= 255, "chroma_min=%d: 1..255", p->chroma_min);
+  REQUIRE(p->drop >= 0 && p->drop <= 63, "drop=%d: 0..63", p->drop);
+  REQUIRE(p->fill >= 0 && p->fill <= 255, "fill=%d: 0..255", p->fill);
+  return 0;
+}
+
+int aocr_estimate_page_colour(void* stream, const uint8_t* rgb_dev, int64_t pitch, int32_t H, int32_t W, const aocr_colour_params* params,
+                              void* scratch_dev, int32_t colour_dev[16]) {
+  if (check_rgb(rgb_dev, pitch, H, W)) return 1;
+  if (check_colour_params(params)) return 1;
+  REQUIRE(scratch_dev, "scratch_dev is NULL");
+  REQUIRE(colour_dev, "colour_dev is NULL");
+  if (check_scratch(scratch_dev, true)) return 1;
+  REQUIRE(((uintptr_t)colour_dev & 3) == 0, "colour_dev must be 4-byte aligned");
+  if (check_words(rgb_dev, pitch, H, 3 * W, scratch_dev, colour_scratch_bytes(), colour_dev, 16, "colour_dev")) return 1;
+  estimate_page_colour((hipStream_t)stream, rgb_dev, pitch, H, W, *params, scratch_dev, colour_dev);
+  return check_launch("aocr_estimate_page_colour");
+}
+
+int aocr_gray_page(void* stream, const uint8_t* rgb_dev, int64_t pitch, int32_t H, int32_t W, const aocr_colour_params* params,
+                   const int32_t* colour_in_dev, int32_t* colour_out_dev, uint8_t* out_dev, int64_t out_pitch) {
+  if (check_rgb(rgb_dev, pitch, H, W)) return 1;
+  if (check_colour_params(params)) return 1;
+  REQUIRE(colour_in_dev || !params->balance || params->paper[0] >= 0, "colour_in_dev is NULL and params->paper asks for an estimate");
+  REQUIRE(((uintptr_t)colour_in_dev & 3) == 0 && ((uintptr_t)colour_out_dev & 3) == 0, "colour_in_dev and colour_out_dev must be 4-byte aligned");
+  REQUIRE(out_dev, "out_dev is NULL");
+  REQUIRE(out_pitch >= W, "out_pitch=%lld is smaller than W=%d", (long long)out_pitch, W);
+  const Span rgb = span_rows(rgb_dev, pitch, H, 3 * (int64_t)W), out = span_rows(out_dev, out_pitch, H, W);
+  REQUIRE(disjoint(out, rgb), "out_dev overlaps the page");
+  for (const int32_t* words : {colour_in_dev, (const int32_t*)colour_out_dev}) {
+    if (!words) continue;
+    const char* name = words == colour_in_dev ? "colour_in_dev" : "colour_out_dev";
+    REQUIRE(disjoint(span_bytes(words, 16 * sizeof(int32_t)), rgb), "%s overlaps the page", name);
+    REQUIRE(disjoint(span_bytes(words, 16 * sizeof(int32_t)), out), "out_dev overlaps %s", name);
+  }
+  REQUIRE(!colour_in_dev || !colour_out_dev || colour_in_dev == colour_out_dev ||
+              disjoint(span_bytes(colour_in_dev, 16 * sizeof(int32_t)), span_bytes(colour_out_dev, 16 * sizeof(int32_t))),
+          "colour_out_dev overlaps colour_in_dev without being equal to it");
+  gray_page((hipStream_t)stream, rgb_dev, pitch, H, W, *params, colour_in_dev, colour_out_dev, out_dev, out_pitch);
+  return check_launch("aocr_gray_page");
+}
+
 }  // extern "C"

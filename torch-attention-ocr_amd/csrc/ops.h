@@ -394,6 +394,13 @@ void estimate_curl(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int
                    int32_t* shifts, uint64_t* scores);
 void dewarp_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, int group, const int32_t* shifts, int fill, uint8_t* out,
                  int64_t out_pitch);
+// colour pages (colour.hip; include/aocr.h: aocr_estimate_page_colour, aocr_gray_page): the paper colour from three channel histograms, and the
+// balanced gray page with the coloured pixels of chosen hue classes replaced by paper
+size_t colour_scratch_bytes();
+void estimate_page_colour(hipStream_t s, const uint8_t* rgb, int64_t pitch, int H, int W, const aocr_colour_params& p, void* scratch,
+                          int32_t* colour);
+void gray_page(hipStream_t s, const uint8_t* rgb, int64_t pitch, int H, int W, const aocr_colour_params& p, const int32_t* colour_in,
+               int32_t* colour_out, uint8_t* out, int64_t out_pitch);
 // page background flattening (flatten.hip; include/aocr.h: aocr_flatten_page): windowed max, windowed mean, division, on a pitched gray page
 size_t flatten_scratch_bytes(int H, int W);
 void flatten_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_flatten_params& p, void* scratch, uint8_t* out,
