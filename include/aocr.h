@@ -1046,6 +1046,66 @@ int aocr_gray_page(void* stream, const uint8_t* rgb_dev, int64_t pitch, int32_t 
                    const aocr_colour_params* params, const int32_t* colour_in_dev, int32_t* colour_out_dev,
                    uint8_t* out_dev, int64_t out_pitch);
 
+/* ---- word slant: the lean of the writing inside every box, and crops with the lean taken out, between aocr_segment_page and the recogniser ----
+ * Italic print and handwriting lean by 10 to 40 degrees: a horizontal shear of every word, which neither aocr_deskew_page (rows against
+ * columns, up to slope 0.25) nor aocr_dewarp_page touches.  aocr_estimate_slant finds one slant per box by a sweep of sheared column
+ * profiles; aocr_crop_lines_slanted is aocr_crop_lines with every row of a box moved back along x.  Integer arithmetic, specified exactly;
+ * every >> is an arithmetic (floor) shift of a signed value.  The page follows the rules of aocr_segment_page: any base address,
+ * pitch >= W, 1 <= H, W <= 16384, H*W <= 2^26.
+ *
+ * aocr_estimate_slant (device), for every box i < n, n = min(n_boxes, count_dev[0]) read on the device (count_dev == NULL: n = n_boxes):
+ *   box        x0, y0, x1, y1 clamped to the page before any read;  h = y1 - y0, w = x1 - x0, cy = (y0 + y1) >> 1;
+ *   ink        thr = params.threshold when >= 0, else threshold_dev[0], read on the device (the word aocr_segment_page wrote to counts_dev[2]:
+ *              no host read in between);  I[y][x] = (v <= thr), or (v > thr) with light_text, for the pixels inside the clamped box and 0
+ *              everywhere else: the ink of neighbouring words does not count.  thr == -1 (Otsu found one gray value): nothing is ink;
+ *   candidates k = -K..K (K = n_steps), s_k = k * step_q16 columns per row in Q16;  off_k(y) = ((cy - y) * s_k + 32768) >> 16;
+ *              D_k = max over y in [y0, y1) of |off_k(y)|.  Positive s: the strokes lean to the right, the top of a stroke is to the right
+ *              of its foot;
+ *   profile    P_k[c] = sum over y in [y0, y1) of I[y][c + off_k(y)] for c in [x0 - D_k, x1 + D_k): every ink pixel lands in exactly one c;
+ *   score      score_k = sum over c of P_k[c]^2, an exact unsigned 64-bit integer;
+ *   winner     candidates in the order 0, -1, +1, -2, +2, ...: the first with the strictly largest score.  K = 0 gives k = 0;
+ *   outputs    slant_dev[4*i ..] = [k, k * step_q16, flag, the ink pixels of the box];  scores_dev[i*(2K+1) + k + K] = score_k when not NULL;
+ *              flag 0: estimated;  flag 1: h > AOCR_SLANT_MAX_H, not estimated: k = 0, the ink word is still filled, the scores are 0;
+ *              flag 2: the box is empty after clamping: [0, 0, 2, 0], the scores are 0.
+ * Rows >= n of slant_dev and scores_dev are untouched.  n_boxes <= 65535; n_boxes == 0 is a no-op.
+ * Limits: the sum of squares rewards any vertical alignment, not only strokes; a box of one round glyph has no slant to find; boxes taller
+ * than AOCR_SLANT_MAX_H rows are skipped; the slant is one per box, not per character.
+ * scratch_dev: aocr_slant_scratch_bytes(n_boxes, n_steps) bytes, 16-byte aligned, overwritten by the call (0 and an error containing "bad
+ * sizes" for n_boxes outside 0..65535 or n_steps outside 0..64).  slant_dev (4-byte aligned) and scores_dev (8-byte aligned) must not
+ * overlap the page or the scratch.
+ *
+ * aocr_crop_lines_slanted (device): row i < n of out_dev (n_boxes, 1, out_h, out_w) fp32, n as for aocr_crop_lines:
+ *   slant      s = slant_dev[4*i + 1], read on the device (slant_dev = the output of aocr_estimate_slant: no host read in between) and clamped
+ *              to [-65536, 65536];  slant_dev == NULL: s = 0;
+ *   extent     off(y) = ((cy - y) * s + 32768) >> 16 with the clamped box's cy;  D = max(|off(y0)|, |off(y1 - 1)|);
+ *   V          h rows, w + 2D columns:  V[r][c] = page[y0 + r][sx] with sx = x0 - D + c + off(y0 + r) when x0 <= sx < x1, else fill (0..255):
+ *              the widening by D on each side loses no ink of the box, and reading inside the box only lets no neighbour's ink in;
+ *   output     V scaled to out_h x out_w with the arithmetic of aocr_preprocess_lines, operation for operation: bit-identical to
+ *              aocr_preprocess_lines on a contiguous copy of V.
+ * With slant_dev == NULL, or every s == 0, the output equals that of aocr_crop_lines bit for bit.  A box that is empty after clamping gives
+ * 255.0; rows >= n are untouched; n_boxes <= 65535; n_boxes == 0 is a no-op.  No scratch.
+ * Both calls enqueue only, never synchronise or allocate; the results do not depend on launch geometry, atomics order or run (integer sums
+ * only).  Invalid params, sizes, non-zero reserved words, NULL pointers, a -1 threshold with threshold_dev == NULL, fill outside 0..255 or
+ * an overlap return an error that names the argument before anything is enqueued and leave the outputs untouched. */
+#define AOCR_SLANT_MAX_H 256
+
+typedef struct aocr_slant_params {
+  int32_t threshold;     /* 0..254 fixed; -1: read threshold_dev[0] on the device (the word aocr_segment_page wrote to counts_dev[2]) */
+  int32_t light_text;    /* 1: ink = (v > threshold) instead */
+  int32_t step_q16;      /* 1..8192: difference between neighbouring candidates, columns per row, Q16 */
+  int32_t n_steps;       /* K in 0..64, K * step_q16 <= 65536 (45 degrees) */
+  int32_t reserved[4];   /* must be 0 */
+} aocr_slant_params;
+
+size_t aocr_slant_scratch_bytes(int32_t n_boxes, int32_t n_steps);
+int aocr_estimate_slant(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                        const aocr_box* boxes_dev, const int32_t* count_dev, int32_t n_boxes,
+                        const aocr_slant_params* params, const int32_t* threshold_dev, void* scratch_dev,
+                        int32_t* slant_dev, uint64_t* scores_dev);
+int aocr_crop_lines_slanted(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                            const aocr_box* boxes_dev, const int32_t* count_dev, int32_t n_boxes,
+                            const int32_t* slant_dev, int32_t fill, int32_t out_h, int32_t out_w, float* out_dev);
+
 #ifdef __cplusplus
 }
 #endif

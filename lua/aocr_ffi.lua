@@ -135,6 +135,10 @@ typedef struct aocr_colour_params { int32_t weights[3]; int32_t mode; int32_t ba
 size_t aocr_colour_scratch_bytes(int32_t H, int32_t W);
 int aocr_estimate_page_colour(void* stream, const uint8_t* rgb_dev, int64_t pitch, int32_t H, int32_t W, const aocr_colour_params* params, void* scratch_dev, int32_t colour_dev[16]);
 int aocr_gray_page(void* stream, const uint8_t* rgb_dev, int64_t pitch, int32_t H, int32_t W, const aocr_colour_params* params, const int32_t* colour_in_dev, int32_t* colour_out_dev, uint8_t* out_dev, int64_t out_pitch);
+typedef struct aocr_slant_params { int32_t threshold; int32_t light_text; int32_t step_q16; int32_t n_steps; int32_t reserved[4]; } aocr_slant_params;
+size_t aocr_slant_scratch_bytes(int32_t n_boxes, int32_t n_steps);
+int aocr_estimate_slant(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_box* boxes_dev, const int32_t* count_dev, int32_t n_boxes, const aocr_slant_params* params, const int32_t* threshold_dev, void* scratch_dev, int32_t* slant_dev, uint64_t* scores_dev);
+int aocr_crop_lines_slanted(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_box* boxes_dev, const int32_t* count_dev, int32_t n_boxes, const int32_t* slant_dev, int32_t fill, int32_t out_h, int32_t out_w, float* out_dev);
 ]]
 
 local M = {}

@@ -127,6 +127,19 @@ class CurlParams(C.Structure):
         super().__init__(int(threshold), int(light_text), int(group), int(max_shift), int(min_ink), (C.c_int32 * 3)(0, 0, 0))
 
 
+SLANT_MAX_H = 256                                                               # AOCR_SLANT_MAX_H of include/aocr.h
+
+
+class SlantParams(C.Structure):
+    """mirror of `aocr_slant_params` (include/aocr.h): the candidates of `aocr_estimate_slant`, k = -n_steps..n_steps at k * step_q16 / 65536
+    columns per row (n_steps * step_q16 <= 65536, 45 degrees).  threshold -1: the device word given with the call (the threshold that
+    `aocr_segment_page` wrote to its counts).  The defaults sweep +-36.9 degrees in steps of 1/16 column per row."""
+    _fields_ = [(n, C.c_int32) for n in ("threshold", "light_text", "step_q16", "n_steps")] + [("reserved", C.c_int32 * 4)]
+
+    def __init__(self, threshold=-1, light_text=0, step_q16=4096, n_steps=12):
+        super().__init__(int(threshold), int(light_text), int(step_q16), int(n_steps), (C.c_int32 * 4)(0, 0, 0, 0))
+
+
 HUE_RED, HUE_YELLOW, HUE_GREEN, HUE_CYAN, HUE_BLUE, HUE_MAGENTA = range(6)      # AOCR_HUE_* of include/aocr.h: the bits of ColourParams.drop
 
 
@@ -285,6 +298,9 @@ SIGNATURES = {
     "aocr_colour_scratch_bytes": (C.c_size_t, [_i32, _i32]),
     "aocr_estimate_page_colour": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp]),
     "aocr_gray_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, _vp, C.c_int64]),
+    "aocr_slant_scratch_bytes": (C.c_size_t, [_i32, _i32]),
+    "aocr_estimate_slant": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "aocr_crop_lines_slanted": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
     "aocr_beam_select": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32]),
 }
 

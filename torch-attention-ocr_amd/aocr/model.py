@@ -20,8 +20,8 @@ import torch
 from . import _lib, dist
 from ._lib import Config, check, lib, ptr
 from .dictionary import edit_distance_device
-from .page import backmap_corners, bucket_width, crop_lines_device, rotate_page_device
-from .page_pipeline import asked, clean_stage, colour_stage, flatten_stage, orient_stage, page_boxes, rectify_stage, scale_stage
+from .page import backmap_corners, bucket_width, crop_lines_device, crop_lines_slanted_device, rotate_page_device, slant_extent
+from .page_pipeline import asked, clean_stage, colour_stage, flatten_stage, orient_stage, page_boxes, paper, rectify_stage, scale_stage
 
 PAD, GO, EOS = 1, 2, 3
 GROUPS = ["cnn", "enc_fw", "enc_bw", "dec", "proj"]
@@ -437,12 +437,12 @@ class Model:
             res.word = [lexicon.words[i] if i >= 0 else None for i in res.word_index.tolist()]
         return res
 
-    def _page_boxes(self, page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None):
+    def _page_boxes(self, page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None, deslant=None):
         """the middle of recognize_page (aocr.page_pipeline.page_boxes), reached through the model so that a caller can wrap it."""
-        return page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev)
+        return page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev, deslant)
 
     def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None, flatten=None,
-                       layout=None, clean=None, orient=None, rectify=None, scale=None, dewarp=None, colour=None):
+                       layout=None, clean=None, orient=None, rectify=None, scale=None, dewarp=None, colour=None, deslant=None):
         """Read a scanned page: segment it into word boxes (aocr_segment_page), crop them (aocr_crop_lines) and recognise the crops.
         page: a uint8 (H,W) numpy array or tensor (gray; a 3-D array raises ValueError unless `colour` is asked for: see below).  params: an
         `aocr.SegmentParams` (default: Otsu threshold, dark text).  The counts and boxes are read back once (the one sync), then the boxes are
@@ -538,7 +538,17 @@ class Model:
         sixteen colour words come back with the existing readback (no additional sync).  The namespace then also carries colour_paper (the
         three paper values divided out), colour_balanced (whether the page was balanced: the params' balance), colour_hues (6) int64: the coloured pixels
         of the classes RED, YELLOW, GREEN, CYAN, BLUE, MAGENTA, and colour_dropped (the pixels replaced by fill).  Limits (a desk larger
-        than the sheet wins the paper estimate; coloured text goes with coloured marks of its class): DESIGN.md section 21."""
+        than the sheet wins the paper estimate; coloured text goes with coloured marks of its class): DESIGN.md section 21.
+        deslant: None or False (the default) crops the boxes as they are.  True or an `aocr.SlantParams` takes the lean of italic print and
+        handwriting out of every crop: right after the segmentation, on the page that was segmented, one slant per box is estimated on the
+        device (aocr_estimate_slant: a sweep of sheared column profiles; True: +-12 steps of 1/16 column per row with the light_text of
+        `params`; the threshold is the word the segmentation left on the device, with layout the page threshold already read back, the
+        estimate then running per block), and the slant words come back inside the readback of the boxes (no additional sync).  Every box
+        is bucketed by (w + 2D, h), D = aocr.page.slant_extent, and cropped with its rows moved back along x (aocr_crop_lines_slanted, filled
+        with paper: 0 with light_text, else 255); the which-way-up probe of orient=True keeps the plain crops.  The namespace then also
+        carries slant_q16 (n) int32, slant_deg (n) float64 (atan(s / 65536) in degrees), slant_flags (n) int32 (0 estimated, 1 taller than
+        256 rows and left alone, 2 empty) and slant_extent (n) int32; boxes and every *_corners field stay what they are: the boxes do not
+        move.  Limits (any vertical alignment scores, one round glyph has no slant, one slant per box): DESIGN.md section 22."""
         if asked(colour):
             ok = isinstance(page, (np.ndarray, torch.Tensor)) and len(page.shape) == 3 and page.shape[2] == 3 and \
                 page.dtype == (np.uint8 if isinstance(page, np.ndarray) else torch.uint8)
@@ -570,7 +580,8 @@ class Model:
         page0, clean_dev = clean_stage(page, stream, seg, clean)
         page, quarter, orient_runs = orient_stage(page0, stream, seg, orient)
         middle = (stream, seg, max_boxes, deskew, dewarp, layout, clean_dev) + (() if colour_dev is None else (colour_dev,))
-        st = self._page_boxes(page, *middle)
+        extra = dict(deslant=deslant) if asked(deslant) else {}
+        st = self._page_boxes(page, *middle, **extra)
         orient_scores = None
         if orient is True:
             m = min(st.n, self.batch_size)                          # which way up: the recogniser reads the first boxes both ways
@@ -584,12 +595,14 @@ class Model:
                 orient_scores = tuple(float(v) for v in torch.stack([up, down]).cpu().numpy())
             if orient_scores[1] > orient_scores[0]:
                 quarter = (quarter + 2) & 3
-                st = self._page_boxes(rotate_page_device(page0, quarter, None, stream), *middle)
+                st = self._page_boxes(rotate_page_device(page0, quarter, None, stream), *middle, **extra)
         page, rows, counts, n = st.page, st.rows, st.counts, st.n
+        extent = slant_extent(rows, st.slant[:, 1]) if st.slant is not None else np.zeros(n, np.int32)
         if width is not None:
             widths = np.full(n, int(width), np.int64)
         else:
-            widths = np.array([bucket_width(int(r[2] - r[0]), int(r[3] - r[1]), self.max_img_w, width_step) for r in rows], np.int64).reshape(n)
+            widths = np.array([bucket_width(int(r[2] - r[0]) + 2 * int(d), int(r[3] - r[1]), self.max_img_w, width_step)
+                               for r, d in zip(rows, extent)], np.int64).reshape(n)
         labels = np.full((n, self.max_decoder_l), PAD, np.int32)
         scores = np.zeros(n, np.float32)
         word_index, word_distance = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
@@ -599,8 +612,12 @@ class Model:
             members = np.nonzero(widths == w)[0]
             for c0 in range(0, len(members), self.batch_size):
                 idx = members[c0:c0 + self.batch_size]
-                sel = st.boxes_dev[torch.from_numpy(idx).to(self.device)]
-                crops = crop_lines_device(page, sel, None, int(w), self.img_h, stream)
+                idx_dev = torch.from_numpy(idx).to(self.device)
+                sel = st.boxes_dev[idx_dev]
+                if st.slant_dev is None:
+                    crops = crop_lines_device(page, sel, None, int(w), self.img_h, stream)
+                else:
+                    crops = crop_lines_slanted_device(page, sel, None, st.slant_dev[idx_dev], int(w), self.img_h, paper(seg), stream)
                 lab, sc, _, _ = self.recognize_device(crops, beam_size, trie)
                 if lexicon is not None:
                     wi, wd = lexicon.nearest(lab, None, stream)
@@ -623,6 +640,9 @@ class Model:
         if st.colour is not None:
             res.colour_paper, res.colour_balanced = tuple(int(v) for v in st.colour[:3]), bool(colour_used.balance)
             res.colour_hues, res.colour_dropped = st.colour[4:10].astype(np.int64), int(st.colour[10])
+        if st.slant is not None:
+            res.slant_q16, res.slant_flags, res.slant_extent = st.slant[:, 1].astype(np.int32), st.slant[:, 2].astype(np.int32), extent
+            res.slant_deg = np.degrees(np.arctan(res.slant_q16 / 65536.0))
         curl = skew = turn = None                                   # what each stage left behind for aocr.page.backmap_corners
         if st.curl is not None:
             res.curl_shifts, res.curl_group = st.curl[4:].astype(np.int32), st.curl_group

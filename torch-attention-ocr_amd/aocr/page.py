@@ -18,7 +18,11 @@ neighbouring column groups by correlation) and `dewarp_page_device` (`aocr_dewar
 deskew; `uncurl_points` takes points back to the page before it.  All of them read a gray page: a colour page, (H, W, 3) RGB, goes through
 `estimate_page_colour_device` (`aocr_estimate_page_colour`: the paper colour, the mode of every channel) and `gray_page_device`
 (`aocr_gray_page`: the paper divided out, a weighted sum or the darkest channel, and the coloured pixels of chosen hue classes -- a red
-form rule, a highlighter stroke, a stamp -- turned into paper) before any of them; the shape does not change, so no box needs a way back."""
+form rule, a highlighter stroke, a stamp -- turned into paper) before any of them; the shape does not change, so no box needs a way back.
+None of them straightens the writing inside a box: italic print and handwriting go through `estimate_slant_device` (`aocr_estimate_slant`:
+one slant per box from a sweep of sheared column profiles) after the segmentation, and `crop_lines_slanted_device`
+(`aocr_crop_lines_slanted`: the crops with every row moved back along x) takes the place of `crop_lines_device`; `slant_extent` is how far
+such a crop reaches beyond its box on either side.  The boxes do not move."""
 from __future__ import annotations
 
 import ctypes as C
@@ -27,7 +31,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import Box, CleanParams, ColourParams, CurlParams, FlattenParams, GlyphParams, LayoutParams, RectifyParams, ScaleParams, SegmentParams, SkewParams, check, lib, ptr
+from ._lib import Box, CleanParams, ColourParams, CurlParams, FlattenParams, GlyphParams, LayoutParams, RectifyParams, ScaleParams, SegmentParams, SkewParams, SlantParams, check, lib, ptr
 
 IMG_H = 32
 MIN_ASPECT = 0.5
@@ -618,6 +622,78 @@ def backmap_corners(boxes, curl=None, skew=None, turn=None, resize=None, warp=No
     return out
 
 
+def estimate_slant_device(page_dev, boxes, counts, params=None, threshold_dev=None, stream=None, scores=False):
+    """slant (n_boxes, 4) int32 device tensor: for every box the winning candidate k, its slant k * step_q16 (columns per row, Q16; positive:
+    the strokes lean to the right), a flag (0 estimated, 1 taller than 256 rows and left alone, 2 empty) and the ink pixels of the box
+    (`aocr_estimate_slant`); with scores=True (slant, scores (n_boxes, 2 * n_steps + 1) int64: every candidate's score, k = -n_steps
+    first).  Rows >= min(n_boxes, counts[0]) are not written (they hold zeros).  boxes (n_boxes, 6) int32 and counts (>= 1) int32 device
+    tensors as `segment_page_device` returns them; counts None: every row of boxes.  params: a `SlantParams` (default: +-12 steps of 1/16
+    column per row); with threshold -1 the threshold is read on the device from threshold_dev[0], and threshold_dev None then takes
+    counts[2:3], the word `aocr_segment_page` left there.  Enqueues only.  stream: as for `segment_page_device`, the current torch stream;
+    the scratch is freed when this returns."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    dev = page_dev.device
+    params = params if params is not None else SlantParams()
+    assert boxes.dim() == 2 and boxes.shape[1] == 6 and boxes.dtype == torch.int32 and boxes.device == dev
+    boxes = boxes.contiguous()
+    n = int(boxes.shape[0])
+    if counts is not None:
+        assert counts.dtype == torch.int32 and counts.device == dev and counts.numel() >= 1
+        counts = counts.contiguous()
+    if threshold_dev is None and params.threshold < 0:
+        if counts is None or counts.numel() < 3:
+            raise ValueError("threshold -1 needs threshold_dev, or the counts of segment_page_device")
+        threshold_dev = counts[2:3]
+    if threshold_dev is not None:
+        assert threshold_dev.dtype == torch.int32 and threshold_dev.device == dev and threshold_dev.numel() >= 1
+        threshold_dev = threshold_dev.contiguous()
+    nc = 2 * params.n_steps + 1
+    slant = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+    sc = torch.zeros((n, nc), dtype=torch.int64, device=dev) if scores else None
+    scratch = _scratch("aocr_slant_scratch_bytes", dev, n, params.n_steps)
+    check(lib.aocr_estimate_slant(_stream(stream, dev), ptr(page_dev), pitch, H, W, ptr(boxes), ptr(counts), n, C.byref(params), ptr(threshold_dev),
+                                  ptr(scratch), ptr(slant), ptr(sc) if scores and n else None), "aocr_estimate_slant")
+    return (slant, sc) if scores else slant
+
+
+def crop_lines_slanted_device(page_dev, boxes, counts, slant, out_w, out_h=IMG_H, fill=255, stream=None):
+    """`crop_lines_device` with the slant taken out (`aocr_crop_lines_slanted`): row i is box i of the page, every row of the box moved along x
+    by its offset, widened by `slant_extent` on either side and filled with `fill` where the source column is outside the box, scaled as
+    `aocr_preprocess_lines` scales it.  slant: the (n_boxes, 4) int32 device tensor of `estimate_slant_device` (word 1 of every row is read
+    on the device: no host sync), or None: the plain crops, bit for bit.  Enqueues only.  stream: as for `segment_page_device`."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    dev = page_dev.device
+    assert boxes.dim() == 2 and boxes.shape[1] == 6 and boxes.dtype == torch.int32 and boxes.device == dev
+    boxes = boxes.contiguous()
+    n = int(boxes.shape[0])
+    if counts is not None:
+        assert counts.dtype == torch.int32 and counts.device == dev and counts.numel() >= 1
+        counts = counts.contiguous()
+    if slant is not None:
+        assert slant.dtype == torch.int32 and slant.device == dev and tuple(slant.shape) == (n, 4), f"slant must be ({n}, 4) int32 on the page's device"
+        slant = slant.contiguous()
+    out = torch.full((n, 1, int(out_h), int(out_w)), 255.0, dtype=torch.float32, device=dev)
+    if n:
+        check(lib.aocr_crop_lines_slanted(_stream(stream, dev), ptr(page_dev), pitch, H, W, ptr(boxes), ptr(counts), n, ptr(slant), int(fill),
+                                          int(out_h), int(out_w), ptr(out)), "aocr_crop_lines_slanted")
+    return out
+
+
+def slant_extent(boxes, slant_q16):
+    """D (n) int32: how many columns `aocr_crop_lines_slanted` adds on either side of every box, max(|off(y0)|, |off(y1 - 1)|) with
+    off(y) = ((cy - y) * s + 32768) >> 16, cy = (y0 + y1) >> 1 and s the slant clamped to +-65536; 0 for an empty box.  boxes (n, >= 4)
+    x0 y0 x1 y1 inside the page (what `aocr_segment_page` writes); host numpy."""
+    b = np.asarray(boxes, np.int64)
+    b = b.reshape(-1, b.shape[-1] if b.ndim > 1 else 4)
+    s = np.clip(np.asarray(slant_q16, np.int64).reshape(-1), -65536, 65536)
+    y0, y1 = b[:, 1], b[:, 3]
+    cy = (y0 + y1) >> 1
+    d = np.maximum(np.abs(((cy - y0) * s + 32768) >> 16), np.abs(((cy - (y1 - 1)) * s + 32768) >> 16))
+    return np.where((y1 > y0) & (b[:, 2] > b[:, 0]), d, 0).astype(np.int32)
+
+
 def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
     """DataGen's width rule for a w x h box, ceil(clamp(w/h, 0.5, max_aspect) * 32), rounded up to a multiple of width_step and capped at
     max_img_w.  max_aspect None: max_img_w / 32."""
@@ -628,6 +704,6 @@ def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
     return min(img_w, int(max_img_w))
 
 
-__all__ = ["backmap_corners", "ColourParams", "estimate_page_colour_device", "gray_page_device", "CurlParams", "estimate_curl_device", "dewarp_page_device", "curl_shift_q8", "uncurl_points", "source_points", "box_corners", "GlyphParams", "ScaleParams", "estimate_glyph_size_device", "resize_page_device", "scale_plan", "unscale_points", "RectifyParams", "find_page_quad_device", "rectify_plan", "warp_page_device", "warp_points", "SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "CleanParams", "Box", "label_components_device", "clean_page_device", "segment_page_device", "crop_lines_device",
+__all__ = ["backmap_corners", "SlantParams", "estimate_slant_device", "crop_lines_slanted_device", "slant_extent", "ColourParams", "estimate_page_colour_device", "gray_page_device", "CurlParams", "estimate_curl_device", "dewarp_page_device", "curl_shift_q8", "uncurl_points", "source_points", "box_corners", "GlyphParams", "ScaleParams", "estimate_glyph_size_device", "resize_page_device", "scale_plan", "unscale_points", "RectifyParams", "find_page_quad_device", "rectify_plan", "warp_page_device", "warp_points", "SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "CleanParams", "Box", "label_components_device", "clean_page_device", "segment_page_device", "crop_lines_device",
            "estimate_skew_device", "deskew_page_device", "flatten_page_device", "ink_integral_device", "layout_page_device", "source_corners",
            "rotate_page_device", "estimate_orientation_device", "unrotate_boxes", "unrotate_points", "bucket_width"]

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .page import (clean_page_device, deskew_page_device, dewarp_page_device, estimate_curl_device, estimate_glyph_size_device,
+from .page import (clean_page_device, deskew_page_device, estimate_slant_device, dewarp_page_device, estimate_curl_device, estimate_glyph_size_device,
                    estimate_orientation_device, gray_page_device, estimate_skew_device, find_page_quad_device, flatten_page_device, layout_page_device,
                    rectify_plan, resize_page_device, rotate_page_device, scale_plan, segment_page_device, warp_page_device)
 
@@ -130,12 +130,28 @@ def orient_stage(page, stream, seg, orient):
     return rotate_page_device(page, quarter, None, stream), quarter, runs
 
 
-def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None):
+def slant_params(seg, deslant, threshold=-1):
+    """the SlantParams of recognize_page(deslant=...): True takes the defaults with the light_text of the segment params; `threshold` replaces
+    a params' -1 where the page threshold is already on the host (the layout path)."""
+    if isinstance(deslant, _lib.SlantParams):
+        sp = _lib.SlantParams(deslant.threshold, deslant.light_text, deslant.step_q16, deslant.n_steps)
+    elif deslant is True:
+        sp = _lib.SlantParams(light_text=seg.light_text)
+    else:
+        raise ValueError(f"deslant={deslant!r}: None, False, True or an aocr.SlantParams")
+    if sp.threshold < 0:
+        sp.threshold = int(threshold)
+    return sp
+
+
+def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None, deslant=None):
     """the middle of recognize_page, from the deskew to the boxes on the host: everything that reads the page in its final orientation and
     has to be redone when recognize_page(orient=True) turns the page by another half turn.  Returns a namespace: page, boxes_dev, rows, counts,
     n, truncated; skew, cleaned, curl, colour (the words read back, None without the stage), curl_group; lay, blocks, block_id, nb, lcounts
-    (None without layout)."""
-    st = SimpleNamespace(curl_group=None, lay=None, blocks=None, block_id=None, nb=None, lcounts=None)
+    (None without layout); slant (n, 4) and slant_dev, the words of aocr_estimate_slant for the boxes kept (None without deslant).  The
+    slant estimate is enqueued right after the segmentation, on the page that was segmented, and its words come back with the boxes: no
+    readback of its own."""
+    st = SimpleNamespace(curl_group=None, lay=None, blocks=None, block_id=None, nb=None, lcounts=None, slant=None, slant_dev=None)
     skew_dev = curl_dev = None
     if asked(deskew):
         sp = deskew if isinstance(deskew, _lib.SkewParams) else _lib.SkewParams(threshold=seg.threshold, light_text=seg.light_text)
@@ -164,30 +180,48 @@ def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, 
             all_boxes[:, :, :4] += blocks_dev[:nb][:, [0, 1, 0, 1]][:, None, :]
             lines_dev = all_counts[:, 1]
             all_boxes[:, :, 4] += (torch.cumsum(lines_dev, 0) - lines_dev).to(torch.int32)[:, None]
+            slants = []
+            if asked(deslant):                                  # per block, its boxes in page coordinates against the whole page
+                sp = slant_params(seg, deslant, int(info[0]))
+                slants = [estimate_slant_device(page, all_boxes[b], all_counts[b], sp, None, stream).reshape(-1) for b in range(nb)]
             all_boxes = all_boxes.reshape(-1, 6)
-            back = torch.cat([all_counts.reshape(-1), all_boxes.reshape(-1)]).cpu().numpy()     # the second sync
+            back = torch.cat([all_counts.reshape(-1), all_boxes.reshape(-1)] + slants).cpu().numpy()     # the second sync
             bcounts = back[:4 * nb].reshape(nb, 4)
             taken = np.minimum(bcounts[:, 0], max_boxes)
             keep = np.concatenate([b * max_boxes + np.arange(t) for b, t in enumerate(taken.tolist())]).astype(np.int64)
-            st.rows = back[4 * nb:].reshape(-1, 6)[keep]
-            st.boxes_dev = all_boxes[torch.from_numpy(keep).to(page.device)]
+            st.rows = back[4 * nb:4 * nb + 6 * nb * max_boxes].reshape(-1, 6)[keep]
+            keep_dev = torch.from_numpy(keep).to(page.device)
+            st.boxes_dev = all_boxes[keep_dev]
+            if slants:
+                st.slant = back[4 * nb + 6 * nb * max_boxes:].reshape(-1, 4)[keep]
+                st.slant_dev = torch.cat(slants).reshape(-1, 4)[keep_dev]
             st.block_id = np.repeat(np.arange(nb, dtype=np.int32), taken)
         else:
             bcounts = np.zeros((0, 4), np.int32)
             st.rows, st.block_id = np.zeros((0, 6), np.int32), np.zeros(0, np.int32)
             st.boxes_dev = torch.zeros((0, 6), dtype=torch.int32, device=page.device)
+            if asked(deslant):
+                slant_params(seg, deslant)
+                st.slant, st.slant_dev = np.zeros((0, 4), np.int32), torch.zeros((0, 4), dtype=torch.int32, device=page.device)
         st.n = len(st.rows)
         st.counts = np.array([bcounts[:, 0].sum(), bcounts[:, 1].sum(), info[0], 0], np.int64)
         st.truncated = bool((bcounts[:, 0] > max_boxes).any())
     else:
         st.boxes_dev, counts_dev = segment_page_device(page, seg, max_boxes, stream)
+        if asked(deslant):                                      # the threshold is the device word counts_dev[2] unless the params fix one
+            st.slant_dev = estimate_slant_device(page, st.boxes_dev, counts_dev, slant_params(seg, deslant), counts_dev[2:3], stream)
         if all(v is None for v in riders.values()):
             got = dict(counts=counts_dev.cpu().numpy())           # nothing rides along: the counts as they are, no torch.cat
         else:
             got = read_named(dict(counts=counts_dev, **riders))
         st.counts = got["counts"]
         st.n = int(min(st.counts[0], max_boxes))
-        st.rows = st.boxes_dev[:st.n].cpu().numpy()
+        if st.slant_dev is None:
+            st.rows = st.boxes_dev[:st.n].cpu().numpy()
+        else:                                                   # the slant words ride with the boxes
+            st.slant_dev = st.slant_dev[:st.n]
+            back = torch.cat([st.boxes_dev[:st.n].reshape(-1), st.slant_dev.reshape(-1)]).cpu().numpy()
+            st.rows, st.slant = back[:6 * st.n].reshape(-1, 6), back[6 * st.n:].reshape(-1, 4)
         st.truncated = bool(st.counts[0] > max_boxes)
     st.skew, st.cleaned, st.curl, st.colour = got.get("skew"), got.get("cleaned"), got.get("curl"), got.get("colour")
     return st

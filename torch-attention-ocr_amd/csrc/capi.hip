@@ -1232,4 +1232,60 @@ int aocr_gray_page(void* stream, const uint8_t* rgb_dev, int64_t pitch, int32_t 
   return check_launch("aocr_gray_page");
 }
 
+static bool slant_sizes_ok(int32_t n_boxes, int32_t n_steps) { return n_boxes >= 0 && n_boxes <= 65535 && n_steps >= 0 && n_steps <= 64; }
+
+size_t aocr_slant_scratch_bytes(int32_t n_boxes, int32_t n_steps) {
+  if (!slant_sizes_ok(n_boxes, n_steps)) {
+    fail("bad sizes n_boxes=%d (0..65535) n_steps=%d (0..64)", n_boxes, n_steps);
+    return 0;
+  }
+  return slant_scratch_bytes(n_boxes, n_steps);
+}
+
+int aocr_estimate_slant(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_box* boxes_dev,
+                        const int32_t* count_dev, int32_t n_boxes, const aocr_slant_params* params, const int32_t* threshold_dev,
+                        void* scratch_dev, int32_t* slant_dev, uint64_t* scores_dev) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(n_boxes >= 0 && n_boxes <= 65535, "bad sizes: n_boxes=%d (0..65535)", n_boxes);
+  REQUIRE(params, "params is NULL");
+  if (check_threshold(params->threshold)) return 1;
+  REQUIRE(params->step_q16 >= 1 && params->step_q16 <= 8192, "step_q16=%d: 1..8192", params->step_q16);
+  REQUIRE(params->n_steps >= 0 && params->n_steps <= 64, "n_steps=%d: 0..64", params->n_steps);
+  REQUIRE(params->n_steps * params->step_q16 <= 65536, "n_steps=%d * step_q16=%d exceeds 65536 (45 degrees)", params->n_steps, params->step_q16);
+  REQUIRE(params->reserved[0] == 0 && params->reserved[1] == 0 && params->reserved[2] == 0 && params->reserved[3] == 0,
+          "reserved words must be 0");
+  REQUIRE(params->threshold >= 0 || threshold_dev, "threshold_dev is NULL and params->threshold asks for the device word");
+  REQUIRE(((uintptr_t)threshold_dev & 3) == 0 && ((uintptr_t)count_dev & 3) == 0, "threshold_dev and count_dev must be 4-byte aligned");
+  if (n_boxes == 0) return 0;
+  REQUIRE(boxes_dev, "boxes_dev is NULL");
+  REQUIRE(slant_dev, "slant_dev is NULL");
+  if (check_scratch(scratch_dev, true)) return 1;
+  REQUIRE(((uintptr_t)boxes_dev & 3) == 0 && ((uintptr_t)slant_dev & 3) == 0, "boxes_dev and slant_dev must be 4-byte aligned");
+  REQUIRE(((uintptr_t)scores_dev & 7) == 0, "scores_dev must be 8-byte aligned");
+  const size_t scratch_bytes = slant_scratch_bytes(n_boxes, params->n_steps);
+  if (check_words(page_dev, pitch, H, W, scratch_dev, scratch_bytes, slant_dev, 4 * n_boxes, "slant_dev")) return 1;
+  if (scores_dev) {
+    const Span scores = span_bytes(scores_dev, (size_t)n_boxes * (2 * params->n_steps + 1) * sizeof(uint64_t));
+    REQUIRE(disjoint(scores, span_rows(page_dev, pitch, H, W)), "scores_dev overlaps the page");
+    REQUIRE(disjoint(scores, span_bytes(scratch_dev, scratch_bytes)), "scores_dev overlaps the scratch");
+  }
+  estimate_slant((hipStream_t)stream, page_dev, pitch, H, W, boxes_dev, count_dev, n_boxes, *params, threshold_dev, scratch_dev, slant_dev,
+                 scores_dev);
+  return check_launch("aocr_estimate_slant");
+}
+
+int aocr_crop_lines_slanted(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_box* boxes_dev,
+                            const int32_t* count_dev, int32_t n_boxes, const int32_t* slant_dev, int32_t fill, int32_t out_h, int32_t out_w,
+                            float* out_dev) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(n_boxes >= 0 && n_boxes <= 65535 && out_h >= 1 && out_w >= 1 && (int64_t)out_h * out_w <= INT32_MAX,
+          "bad sizes: n_boxes=%d (0..65535) out_h=%d out_w=%d", n_boxes, out_h, out_w);
+  REQUIRE(fill >= 0 && fill <= 255, "fill=%d: 0..255", fill);
+  REQUIRE(((uintptr_t)slant_dev & 3) == 0, "slant_dev must be 4-byte aligned");
+  if (n_boxes == 0) return 0;
+  REQUIRE(boxes_dev && out_dev, "NULL argument: boxes_dev or out_dev");
+  crop_lines_slanted((hipStream_t)stream, page_dev, pitch, H, W, boxes_dev, count_dev, n_boxes, slant_dev, fill, out_h, out_w, out_dev);
+  return check_launch("aocr_crop_lines_slanted");
+}
+
 }  // extern "C"

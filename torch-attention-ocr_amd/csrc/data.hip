@@ -5,6 +5,7 @@
 // One thread per output pixel; every float operation is an explicitly rounded (non-contracted) single-precision op in the
 // order of the restatement, so the result is bit-identical to it.  HBM-bound and tiny: the images of a batch are a few MB.
 #include "ops.h"
+#include "resample.h"
 
 // HIP's __fmul_rn / __fadd_rn are plain operators and hipcc contracts a*b+c into an FMA by default (-ffp-contract=fast, which
 // also ignores `#pragma clang fp contract`): this file is compiled with -ffp-contract=off (Makefile: FLAGS_data) so that every
@@ -26,28 +27,7 @@ struct Gray {                                            // 255 * rgb2y of sourc
   }
 };
 
-// element di of scaleLinear_rowcol(src[0..n), dst_len); F(i) yields src[i]
-template <class F> __device__ __forceinline__ float scale_elem(const F& src, int n, int dst_len, int di) {
-  if (dst_len == n) return src(di);
-  if (dst_len > n) {
-    if (n == 1) return src(0);
-    if (di == dst_len - 1) return src(n - 1);
-    const float scale = __fdiv_rn((float)(n - 1), (float)(dst_len - 1));
-    const float sf = __fmul_rn((float)di, scale);
-    const int si = (int)sf;
-    const float fr = __fsub_rn(sf, (float)si);
-    return __fadd_rn(__fmul_rn(__fsub_rn(1.0f, fr), src(si)), __fmul_rn(fr, src(si + 1)));
-  }
-  const float scale = __fdiv_rn((float)n, (float)dst_len);
-  const float s0 = __fmul_rn((float)di, scale), s1 = __fmul_rn((float)(di + 1), scale);
-  const int si0_i = (int)s0, si1_i = (int)s1;
-  const float si0_f = __fsub_rn(s0, (float)si0_i), si1_f = __fsub_rn(s1, (float)si1_i);
-  float acc = __fmul_rn(__fsub_rn(1.0f, si0_f), src(si0_i));
-  float cnt = __fsub_rn(1.0f, si0_f);
-  for (int si = si0_i + 1; si < si1_i; ++si) { acc = __fadd_rn(acc, src(si)); cnt = __fadd_rn(cnt, 1.0f); }
-  if (si1_i < n) { acc = __fadd_rn(acc, __fmul_rn(si1_f, src(si1_i))); cnt = __fadd_rn(cnt, si1_f); }
-  return __fdiv_rn(acc, cnt);
-}
+// scale_elem, element di of scaleLinear_rowcol: resample.h (shared with slant.hip's slanted crops)
 
 __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restrict__ src, const aocr_image_desc* __restrict__ desc,
                                                          int out_h, int out_w, float* __restrict__ out) {

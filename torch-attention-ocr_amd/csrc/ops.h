@@ -450,4 +450,11 @@ void resize_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W
 // crops (data.hip; aocr_crop_lines): preprocess_lines' scaling of n box rectangles of a pitched page, n = min(n_boxes, count[0]) on the device
 void crop_lines(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_box* boxes, const int32_t* count, int n_boxes,
                 int out_h, int out_w, float* out);
+// word slant (slant.hip; include/aocr.h: aocr_estimate_slant, aocr_crop_lines_slanted): one slant per box from a sweep of sheared column
+// profiles, and crop_lines with every row of a box moved back along x (the scaling itself is resample.h's, shared with data.hip)
+size_t slant_scratch_bytes(int n_boxes, int n_steps);
+void estimate_slant(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_box* boxes, const int32_t* count, int n_boxes,
+                    const aocr_slant_params& p, const int32_t* threshold, void* scratch, int32_t* slant, uint64_t* scores);
+void crop_lines_slanted(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_box* boxes, const int32_t* count,
+                        int n_boxes, const int32_t* slant, int fill, int out_h, int out_w, float* out);
 }  // namespace aocr
