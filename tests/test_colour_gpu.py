@@ -12,22 +12,15 @@ import colour_ref as K
 import segment_ref as R
 from colour_cases import (HEIGHTS, MARKED_BOXES, MARKED_DROP, MARKED_SEG, MERGE_SHAPE, OFFSETS, OUTS, PITCH_EXTRA, WIDTHS, all_paper, marked_page,
                           paper_rgb, random_rgb)
+from page_harness import expect_placed, garbage_scratch, guarded_words, place, poisoned
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -7
 GUARD = 4                # words behind the sixteen that every raw call gets: they must keep their sentinel
 POISON = 0xAB
-
-
-def _place(cuda, rgb, pitch=None, offset=0, fill=99):
-    """the page inside a larger device buffer: rows `pitch` bytes apart, starting `offset` bytes in; every other byte is `fill`."""
-    H, W, _ = rgb.shape
-    pitch = pitch or 3 * W
-    buf = np.full(offset + H * pitch + 16, fill, np.uint8)
-    np.lib.stride_tricks.as_strided(buf[offset:], (H, 3 * W), (pitch, 1))[:] = rgb.reshape(H, 3 * W)
-    dev = torch.from_numpy(buf).to(cuda)
-    return dev, dev.data_ptr() + offset, pitch
+TAIL = 32                # bytes of the gray page's buffer behind the last row's pitch
+AROUND = 99              # the bytes around a placed RGB page, where a test does not say otherwise: neither paper nor ink
 
 
 def _params(**kw):
@@ -39,13 +32,13 @@ def _gray(cuda, rgb, params, words_in=None, alias=False, counts=True, pitch=None
     """raw aocr_gray_page into a poisoned buffer: (the whole buffer, the 16 words and GUARD sentinels or None, status)."""
     import aocr
     H, W, _ = rgb.shape
-    dev, addr, pitch = _place(cuda, rgb, pitch, offset)
+    dev, addr, pitch = place(cuda, rgb, pitch, offset, fill=AROUND, elem=3)
     out_pitch = W + out_extra
-    buf = torch.full((out_offset + H * out_pitch + 32,), POISON, dtype=torch.uint8, device=cuda)
+    buf = poisoned(cuda, out_offset + H * out_pitch + TAIL, POISON)
     win = None
     if words_in is not None:
         win = torch.tensor([int(v) for v in words_in] + [SENTINEL] * GUARD, dtype=torch.int32, device=cuda)
-    wout = win if alias else (torch.full((16 + GUARD,), SENTINEL, dtype=torch.int32, device=cuda) if counts else None)
+    wout = win if alias else (guarded_words(cuda, 16, GUARD, SENTINEL, torch.int32) if counts else None)
     st = aocr.lib.aocr_gray_page(None, C.c_void_p(addr), pitch, H, W, C.byref(params), aocr.ptr(win), aocr.ptr(wout),
                                  C.c_void_p(buf.data_ptr() + out_offset), out_pitch)
     torch.cuda.synchronize()
@@ -53,10 +46,7 @@ def _gray(cuda, rgb, params, words_in=None, alias=False, counts=True, pitch=None
 
 
 def _expect(gray, out_extra, out_offset):
-    H, W = gray.shape
-    buf = np.full(out_offset + H * (W + out_extra) + 32, POISON, np.uint8)
-    np.lib.stride_tricks.as_strided(buf[out_offset:], (H, W), (W + out_extra, 1))[:] = gray
-    return buf
+    return expect_placed(gray, gray.shape[1] + out_extra, out_offset, poison=POISON, tail=TAIL)
 
 
 _pages = {}
@@ -116,11 +106,11 @@ def _estimate(cuda, rgb, paper_min=128, pitch=None, offset=0, scratch=None):
     """raw aocr_estimate_page_colour: (the 16 words and GUARD sentinels, status, the scratch tensor); the scratch holds poison."""
     import aocr
     H, W, _ = rgb.shape
-    dev, addr, pitch = _place(cuda, rgb, pitch, offset, fill=255)
+    dev, addr, pitch = place(cuda, rgb, pitch, offset, fill=255, elem=3)
     need = aocr.lib.aocr_colour_scratch_bytes(H, W)
     if scratch is None:
-        scratch = torch.full(((need + 7) // 8,), -1, dtype=torch.int64, device=cuda)
-    out = torch.full((16 + GUARD,), SENTINEL, dtype=torch.int32, device=cuda)
+        scratch = garbage_scratch(cuda, need, 0)                                      # no floor: exactly the queried size
+    out = guarded_words(cuda, 16, GUARD, SENTINEL, torch.int32)
     st = aocr.lib.aocr_estimate_page_colour(None, C.c_void_p(addr), pitch, H, W, C.byref(_params(paper_min=paper_min)), aocr.ptr(scratch),
                                             aocr.ptr(out))
     torch.cuda.synchronize()
@@ -162,7 +152,7 @@ def test_invalid_arguments_leave_everything_untouched(cuda):
     import aocr
     rgb = _random(70, 43)
     H, W, _ = rgb.shape
-    dev, addr, pitch = _place(cuda, rgb)
+    dev, addr, pitch = place(cuda, rgb, fill=AROUND, elem=3)
     good = dict(paper=(250, 240, 200))
 
     def raw(**fields):
@@ -180,7 +170,7 @@ def test_invalid_arguments_leave_everything_untouched(cuda):
                   (raw(drop=64), "drop"), (raw(drop=-1), "drop"), (raw(chroma_min=0), "chroma_min"), (raw(chroma_min=256), "chroma_min"),
                   (raw(paper_min=0), "paper_min"), (raw(paper_min=256), "paper_min"), (raw(paper=(0, 240, 200)), "paper"),
                   (raw(paper=(250, 240, 256)), "paper"), (raw(fill=-1), "fill"), (raw(fill=256), "fill")]
-    out = torch.full((H * W + 64,), POISON, dtype=torch.uint8, device=cuda)
+    out = poisoned(cuda, H * W + 64, POISON)
     words = torch.full((16,), SENTINEL, dtype=torch.int32, device=cuda)
     scratch = torch.full((aocr.lib.aocr_colour_scratch_bytes(H, W) // 8,), -1, dtype=torch.int64, device=cuda)
     src, ok = C.c_void_p(addr), _params(**good)

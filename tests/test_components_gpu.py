@@ -5,8 +5,6 @@ output page with the padding between W and out_pitch, over garbage-filled scratc
 from the tile of csrc/components.hip, read from its source: they are the smallest at which each seam of the kernels is crossed."""
 import ctypes as C
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
@@ -16,6 +14,7 @@ import components_ref as CR
 import segment_ref as R
 from components_cases import (CLEAN_CASES, LABEL_CASES, MOTIVE_BOXES, MOTIVE_CLEAN, MOTIVE_SEG, border_crossers, checkerboard, corner_diagonals,
                               framed_text, motive_page, serpentine, u_shape)
+from page_harness import csrc_constants, expect_placed, garbage_scratch, guarded_words, place, poisoned
 from segment_cases import SEEDED_SHAPES, seeded_page
 
 pytestmark = pytest.mark.gpu
@@ -23,28 +22,18 @@ pytestmark = pytest.mark.gpu
 POISON = 0xABABABAB
 SENTINEL = -7
 GUARD_ROWS = 4
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT_FILL = 0x5A          # the poison of aocr_clean_page's output buffer
+OUT_TAIL = 16            # bytes of that buffer behind the last row's pitch
 
 
 def _tile():
-    src = open(os.path.join(ROOT, "torch-attention-ocr_amd", "csrc", "components.hip")).read()
-    t = {n: int(v) for n, v in re.findall(r"constexpr int (CC_TILE_H|CC_TILE_W) = (\d+);", src)}
+    t = csrc_constants("components.hip", ("CC_TILE_H", "CC_TILE_W"))
     assert len(t) == 2
     return t["CC_TILE_H"], t["CC_TILE_W"]
 
 
-def _place(cuda, page, pitch=None, offset=0, fill=0):
-    """the page inside a larger device buffer: rows `pitch` bytes apart, starting `offset` bytes in; every other byte is `fill` (ink, were it read)."""
-    H, W = page.shape
-    pitch = pitch or W
-    buf = np.full(offset + H * pitch + 16, fill, np.uint8)
-    np.lib.stride_tricks.as_strided(buf[offset:], (H, W), (pitch, 1))[:] = page
-    dev = torch.from_numpy(buf).to(cuda)
-    return dev, dev.data_ptr() + offset, pitch
-
-
 def _scratch(cuda, need):
-    return torch.full(((max(need, 1 << 12) + 7) // 8,), -1, dtype=torch.int64, device=cuda)
+    return garbage_scratch(cuda, need, 1 << 12)
 
 
 def _label(cuda, page, thr=128, light=0, conn=8, pitch=None, offset=0, lp=None, mc=4096, comps=True, shape=None, scratch=None, labels=True,
@@ -52,11 +41,11 @@ def _label(cuda, page, thr=128, light=0, conn=8, pitch=None, offset=0, lp=None, 
     """raw aocr_label_components: (the whole label buffer (H, lp) plus 8 guard words as the device left it, comps (mc + GUARD_ROWS, 6), info, status)."""
     import aocr
     H, W = shape or page.shape
-    dev, addr, pitch = _place(cuda, page, pitch, offset, fill=255 if light else 0)
+    dev, addr, pitch = place(cuda, page, pitch, offset, fill=255 if light else 0)
     lp = lp or page.shape[1]
     lab = torch.from_numpy(np.full(page.shape[0] * lp + 8, POISON, np.uint32).view(np.int32)).to(cuda)
-    cm = torch.full((max(mc, 1) + GUARD_ROWS, 6), SENTINEL, dtype=torch.int32, device=cuda)
-    inf = torch.full((4,), SENTINEL, dtype=torch.int32, device=cuda)
+    cm = guarded_words(cuda, max(mc, 1), GUARD_ROWS, SENTINEL, torch.int32, width=6)
+    inf = guarded_words(cuda, 4, 0, SENTINEL, torch.int32)
     if scratch is None:
         scratch = _scratch(cuda, aocr.lib.aocr_components_scratch_bytes(*page.shape))
     st = aocr.lib.aocr_label_components(None, C.c_void_p(addr), pitch, H, W, thr, light, conn, None if no_scratch else aocr.ptr(scratch),
@@ -92,14 +81,14 @@ def _seeded_ref(shape, thr, light, conn):
     return page, CR.label_components(page, thr, light, conn, max_components=page.size)
 
 
-def _clean(cuda, page, params, pitch=None, offset=0, op=None, shape=None, out=True, counts=True, no_scratch=False, reserved=0, out_fill=0x5A):
+def _clean(cuda, page, params, pitch=None, offset=0, op=None, shape=None, out=True, counts=True, no_scratch=False, reserved=0, out_fill=OUT_FILL):
     """raw aocr_clean_page: (the whole output buffer (H, op) plus 16 guard bytes, counts, status)."""
     import aocr
     H, W = shape or page.shape
-    dev, addr, pitch = _place(cuda, page, pitch, offset, fill=255 if params.get("light_text") else 0)
+    dev, addr, pitch = place(cuda, page, pitch, offset, fill=255 if params.get("light_text") else 0)
     op = op or page.shape[1]
-    o = torch.full((page.shape[0] * op + 16,), out_fill, dtype=torch.uint8, device=cuda)
-    cnt = torch.full((8,), SENTINEL, dtype=torch.int32, device=cuda)
+    o = poisoned(cuda, page.shape[0] * op + OUT_TAIL, out_fill)
+    cnt = guarded_words(cuda, 8, 0, SENTINEL, torch.int32)
     p = aocr.CleanParams(**params)
     p.reserved[0] = reserved
     sc = _scratch(cuda, aocr.lib.aocr_clean_scratch_bytes(*page.shape))
@@ -109,12 +98,8 @@ def _clean(cuda, page, params, pitch=None, offset=0, op=None, shape=None, out=Tr
     return o.cpu().numpy(), cnt.cpu().numpy(), st
 
 
-def _expect_out(page, op=None, out_fill=0x5A):
-    H, W = page.shape
-    op = op or W
-    buf = np.full(H * op + 16, out_fill, np.uint8)
-    np.lib.stride_tricks.as_strided(buf, (H, W), (op, 1))[:] = page
-    return buf
+def _expect_out(page, op=None, out_fill=OUT_FILL):
+    return expect_placed(page, op, 0, poison=out_fill, tail=OUT_TAIL)
 
 
 # ---- aocr_label_components ---------------------------------------------------------------------------------------------------------------------

@@ -11,40 +11,31 @@ import torch
 import curl_ref as K
 import segment_ref as R
 from curl_cases import GATED, PLANTED, SEGMENT, TIE, curled_page, gated_page, noise_page, planted_page, text_page, tie_page
+from page_harness import expect_placed, garbage_scratch, guarded_words, place, poisoned
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -7
 GUARD = 4                # entries beyond shifts_dev's ng and scores_dev's (ng-1)(2D+1) that every raw call gets: they must keep their sentinel
 POISON = 0xAB
-
-
-def _place(cuda, page, pitch=None, offset=0, fill=0):
-    """the page inside a larger device buffer: rows `pitch` bytes apart, starting `offset` bytes in; every other byte is `fill`."""
-    H, W = page.shape
-    pitch = pitch or W
-    buf = np.full(offset + H * pitch + 16, fill, np.uint8)
-    view = np.lib.stride_tricks.as_strided(buf[offset:], (H, W), (pitch, 1))
-    view[:] = page
-    dev = torch.from_numpy(buf).to(cuda)
-    return dev, dev.data_ptr() + offset, pitch
+TAIL = 32                # bytes of the dewarped page's buffer behind the last row's pitch
 
 
 def _estimate(cuda, page, params, pitch=None, offset=0, scores=True, shape=None):
     """raw aocr_estimate_curl: (curl (4), shifts (ng) then GUARD sentinels, scores then GUARD sentinels, status); the scratch holds garbage."""
     import aocr
     H, W = shape or page.shape
-    dev, addr, pitch = _place(cuda, page, pitch, offset)
+    dev, addr, pitch = place(cuda, page, pitch, offset)
     p = aocr.CurlParams(**{k: v for k, v in params.items() if k != "reserved"})
     if "reserved" in params:
         p.reserved[1] = params["reserved"]
     g, D = min(max(p.group, 1), 16), min(max(p.max_shift, 0), 64)
     ng = K.n_groups(max(W, 1), g)
     need = aocr.lib.aocr_curl_scratch_bytes(H, W, p.group, p.max_shift)
-    scratch = torch.full(((max(need, 1 << 16) + 7) // 8,), -1, dtype=torch.int64, device=cuda)
-    curl = torch.full((4,), SENTINEL, dtype=torch.int32, device=cuda)
-    sh = torch.full((ng + GUARD,), SENTINEL, dtype=torch.int32, device=cuda)
-    sc = torch.full(((ng - 1) * (2 * D + 1) + GUARD,), SENTINEL, dtype=torch.int64, device=cuda)
+    scratch = garbage_scratch(cuda, need, 1 << 16)
+    curl = guarded_words(cuda, 4, 0, SENTINEL, torch.int32)
+    sh = guarded_words(cuda, ng, GUARD, SENTINEL, torch.int32)
+    sc = guarded_words(cuda, (ng - 1) * (2 * D + 1), GUARD, SENTINEL, torch.int64)
     st = aocr.lib.aocr_estimate_curl(None, C.c_void_p(addr), pitch, H, W, C.byref(p), aocr.ptr(scratch), aocr.ptr(curl), aocr.ptr(sh),
                                      aocr.ptr(sc) if scores else None)
     torch.cuda.synchronize()
@@ -67,8 +58,8 @@ def _dewarp(cuda, page, shifts, group, fill, out_pitch, out_offset, pitch=None, 
     """raw aocr_dewarp_page into a poisoned buffer: (the whole buffer as the device left it, status)."""
     import aocr
     H, W = page.shape
-    dev, addr, pitch = _place(cuda, page, pitch, offset, fill=99)
-    buf = torch.full((out_offset + H * out_pitch + 32,), POISON, dtype=torch.uint8, device=cuda)
+    dev, addr, pitch = place(cuda, page, pitch, offset, fill=99)
+    buf = poisoned(cuda, out_offset + H * out_pitch + TAIL, POISON)
     sh = torch.tensor([int(v) for v in shifts], dtype=torch.int32, device=cuda)
     st = aocr.lib.aocr_dewarp_page(None, C.c_void_p(addr), pitch, H, W, group, aocr.ptr(sh), fill, C.c_void_p(buf.data_ptr() + out_offset), out_pitch)
     torch.cuda.synchronize()
@@ -76,10 +67,7 @@ def _dewarp(cuda, page, shifts, group, fill, out_pitch, out_offset, pitch=None, 
 
 
 def _expect(page, shifts, group, fill, out_pitch, out_offset):
-    H, W = page.shape
-    buf = np.full(out_offset + H * out_pitch + 32, POISON, np.uint8)
-    np.lib.stride_tricks.as_strided(buf[out_offset:], (H, W), (out_pitch, 1))[:] = K.dewarp(page, shifts, group, fill)
-    return buf
+    return expect_placed(K.dewarp(page, shifts, group, fill), out_pitch, out_offset, poison=POISON, tail=TAIL)
 
 
 # H, W, kind; every shape runs at pitch = W, offset 0 and at pitch = W + 5, offset 3.  (64, 129): a one-column last group with group = 1
@@ -205,7 +193,7 @@ def test_invalid_arguments_leave_the_outputs_untouched(cuda):
         assert aocr.lib.aocr_curl_scratch_bytes(*args) == 0 and "bad sizes" in aocr.last_error(), args
     need = aocr.lib.aocr_curl_scratch_bytes(40, 100, 2, 8)
     assert need > 0 and need % 256 == 0
-    dev, addr, pitch = _place(cuda, page)
+    dev, addr, pitch = place(cuda, page)
     p = aocr.CurlParams(**good)
     scratch = torch.empty(1 << 16, dtype=torch.int64, device=cuda)
     curl = torch.full((4,), SENTINEL, dtype=torch.int32, device=cuda)
@@ -217,7 +205,7 @@ def test_invalid_arguments_leave_the_outputs_untouched(cuda):
     assert call(None, C.c_void_p(addr), pitch, 40, 100, None, aocr.ptr(scratch), aocr.ptr(curl), aocr.ptr(sh), None) != 0
     assert call(None, C.c_void_p(addr), pitch, 40, 100, C.byref(p), aocr.ptr(scratch), aocr.ptr(curl), C.c_void_p(addr + 48), None) != 0
     assert "overlap" in aocr.last_error()
-    out = torch.full((40 * 100,), POISON, dtype=torch.uint8, device=cuda)
+    out = poisoned(cuda, 40 * 100, POISON)
     for args, word in (((0, aocr.ptr(sh), 255, aocr.ptr(out), 100), "group"), ((17, aocr.ptr(sh), 255, aocr.ptr(out), 100), "group"),
                        ((2, None, 255, aocr.ptr(out), 100), "shifts_dev"), ((2, aocr.ptr(sh), 256, aocr.ptr(out), 100), "fill"),
                        ((2, aocr.ptr(sh), -1, aocr.ptr(out), 100), "fill"), ((2, aocr.ptr(sh), 255, aocr.ptr(out), 99), "out_pitch"),

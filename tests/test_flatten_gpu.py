@@ -2,8 +2,6 @@
 exact byte equality, of the whole output buffer: the flattened page, and the guard pattern everywhere else.  tests/test_flatten_cpu.py shows
 on the restatement alone that the lit pages used here cannot be segmented before flattening and can after it."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
@@ -13,35 +11,27 @@ import flatten_ref as F
 import segment_ref as R
 import skew_ref as S
 from flatten_cases import CASES, clean_page, light, lit_page
+from page_harness import csrc_constants, expect_placed, garbage_scratch, place, poisoned
 from segment_cases import SEEDED_SHAPES, seeded_page
 
 pytestmark = pytest.mark.gpu
 
 POISON = 0xAB
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _place(cuda, page, pitch=None, offset=0, fill=99):
-    """the page inside a larger device buffer: rows `pitch` bytes apart, starting `offset` bytes in; every other byte is `fill`."""
-    H, W = page.shape
-    pitch = pitch or W
-    buf = np.full(offset + H * pitch + 16, fill, np.uint8)
-    np.lib.stride_tricks.as_strided(buf[offset:], (H, W), (pitch, 1))[:] = page
-    dev = torch.from_numpy(buf).to(cuda)
-    return dev, dev.data_ptr() + offset, pitch
+AROUND = 99              # the bytes around every placed page: neither paper nor ink
+TAIL = 32                # bytes of the output buffer behind the last row's pitch
 
 
 def _flatten(cuda, page, radius, light_text=0, pitch=None, offset=0, out_pitch=None, out_offset=0, shape=None, reserved=(0, 0), scratch=True):
     """raw aocr_flatten_page into a poisoned buffer over garbage scratch: (the whole output buffer as the device left it, status)."""
     import aocr
     H, W = shape or page.shape
-    dev, addr, pitch = _place(cuda, page, pitch, offset)
+    dev, addr, pitch = place(cuda, page, pitch, offset, fill=AROUND)
     out_pitch = out_pitch or page.shape[1]
-    buf = torch.full((out_offset + page.shape[0] * out_pitch + 32,), POISON, dtype=torch.uint8, device=cuda)
+    buf = poisoned(cuda, out_offset + page.shape[0] * out_pitch + TAIL, POISON)
     p = aocr.FlattenParams(radius, light_text)
     p.reserved[0], p.reserved[1] = reserved
     need = aocr.lib.aocr_flatten_scratch_bytes(H, W, radius)
-    sc = torch.full(((max(need, 1 << 12) + 7) // 8,), -1, dtype=torch.int64, device=cuda)
+    sc = garbage_scratch(cuda, need, 1 << 12)
     st = aocr.lib.aocr_flatten_page(None, C.c_void_p(addr), pitch, H, W, C.byref(p), aocr.ptr(sc) if scratch else None,
                                     C.c_void_p(buf.data_ptr() + out_offset), out_pitch)
     torch.cuda.synchronize()
@@ -49,17 +39,12 @@ def _flatten(cuda, page, radius, light_text=0, pitch=None, offset=0, out_pitch=N
 
 
 def _expect(want, out_pitch=None, out_offset=0):
-    H, W = want.shape
-    out_pitch = out_pitch or W
-    buf = np.full(out_offset + H * out_pitch + 32, POISON, np.uint8)
-    np.lib.stride_tricks.as_strided(buf[out_offset:], (H, W), (out_pitch, 1))[:] = want
-    return buf
+    return expect_placed(want, out_pitch, out_offset, poison=POISON, tail=TAIL)
 
 
 def _tiling():
     """the tile sizes of csrc/flatten.hip."""
-    src = open(os.path.join(ROOT, "torch-attention-ocr_amd", "csrc", "flatten.hip")).read()
-    return {n: int(v) for n, v in re.findall(r"constexpr int (HSEG|HROWS|VT_COLS|VT_ROWS|VS_WORDS|VS_ROWS) = (\d+);", src)}
+    return csrc_constants("flatten.hip", ("HSEG", "HROWS", "VT_COLS", "VT_ROWS", "VS_WORDS", "VS_ROWS"))
 
 
 @pytest.mark.parametrize("light_text", [0, 1], ids=["dark", "light"])
@@ -122,7 +107,7 @@ def test_invalid_arguments_leave_the_output_untouched(cuda):
         got, st = _flatten(cuda, page, **kw)
         assert st != 0 and word in aocr.last_error(), (kw, aocr.last_error())
         assert (got == POISON).all(), kw
-    dev, addr, pitch = _place(cuda, page)
+    dev, addr, pitch = place(cuda, page, fill=AROUND)
     p = aocr.FlattenParams()
     sc = torch.empty(1 << 14, dtype=torch.int64, device=cuda)
     for out in (addr + 50, addr - 50, addr):                                    # an output that overlaps the page

@@ -3,8 +3,6 @@ Model.recognize_page(layout=...) against the restatement's block-by-block segmen
 buffers over poison: the table with the padding between W+1 and sat_pitch, the rows of blocks_dev beyond the count, over garbage-filled
 scratch.  tests/test_layout_cpu.py shows on the restatement alone what the two-column page used here is cut into."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
@@ -13,6 +11,7 @@ import torch
 import layout_ref as L
 import segment_ref as R
 from layout_cases import CASES, TWO_COL, two_column_page
+from page_harness import csrc_constants, garbage_scratch, guarded_words, place
 from segment_cases import SEEDED_SHAPES, seeded_page
 
 pytestmark = pytest.mark.gpu
@@ -20,17 +19,6 @@ pytestmark = pytest.mark.gpu
 POISON = 0xABABABAB
 SENTINEL = -7
 GUARD_ROWS = 4
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _place(cuda, page, pitch=None, offset=0, fill=0):
-    """the page inside a larger device buffer: rows `pitch` bytes apart, starting `offset` bytes in; every other byte is `fill` (ink, were it read)."""
-    H, W = page.shape
-    pitch = pitch or W
-    buf = np.full(offset + H * pitch + 16, fill, np.uint8)
-    np.lib.stride_tricks.as_strided(buf[offset:], (H, W), (pitch, 1))[:] = page
-    dev = torch.from_numpy(buf).to(cuda)
-    return dev, dev.data_ptr() + offset, pitch
 
 
 def _integral(cuda, page, threshold=-1, light_text=0, pitch=None, offset=0, sat_pitch=None, shape=None, scratch=True, sat=True, info=True):
@@ -38,12 +26,12 @@ def _integral(cuda, page, threshold=-1, light_text=0, pitch=None, offset=0, sat_
     device left it, info, status, the device tensor)."""
     import aocr
     H, W = shape or page.shape
-    dev, addr, pitch = _place(cuda, page, pitch, offset)
+    dev, addr, pitch = place(cuda, page, pitch, offset, fill=0)           # the bytes around the page are ink, were they read
     sat_pitch = sat_pitch or page.shape[1] + 1
     buf = torch.from_numpy(np.full((page.shape[0] + 1) * sat_pitch + 8, POISON, np.uint32).view(np.int32)).to(cuda)
-    inf = torch.full((4,), SENTINEL, dtype=torch.int32, device=cuda)
+    inf = guarded_words(cuda, 4, 0, SENTINEL, torch.int32)
     need = aocr.lib.aocr_integral_scratch_bytes(H, W)
-    sc = torch.full(((max(need, 1 << 12) + 7) // 8,), -1, dtype=torch.int64, device=cuda)
+    sc = garbage_scratch(cuda, need, 1 << 12)
     st = aocr.lib.aocr_ink_integral(None, C.c_void_p(addr), pitch, H, W, threshold, light_text, aocr.ptr(sc) if scratch else None,
                                     aocr.ptr(buf) if sat else None, sat_pitch, aocr.ptr(inf) if info else None)
     torch.cuda.synchronize()
@@ -66,9 +54,9 @@ def _blocks(cuda, sat_dev, sat_pitch, H, W, params, max_blocks, scratch=None, sa
     p.reserved = reserved
     need = aocr.lib.aocr_layout_scratch_bytes(H, W, max_blocks)
     if scratch is None:
-        scratch = torch.full(((max(need, 1 << 12) + 7) // 8,), -1, dtype=torch.int64, device=cuda)
-    blocks = torch.full((max(max_blocks, 1) + GUARD_ROWS, 6), SENTINEL, dtype=torch.int32, device=cuda)
-    cnt = torch.full((4,), SENTINEL, dtype=torch.int32, device=cuda)
+        scratch = garbage_scratch(cuda, need, 1 << 12)
+    blocks = guarded_words(cuda, max(max_blocks, 1), GUARD_ROWS, SENTINEL, torch.int32, width=6)
+    cnt = guarded_words(cuda, 4, 0, SENTINEL, torch.int32)
     st = aocr.lib.aocr_layout_blocks(None, aocr.ptr(sat_dev) if sat else None, sat_pitch, H, W, C.byref(p), aocr.ptr(scratch), max_blocks,
                                      aocr.ptr(blocks) if out else None, aocr.ptr(cnt) if counts else None)
     torch.cuda.synchronize()
@@ -84,8 +72,7 @@ def _check_blocks(got, got_counts, want, want_counts, what):
 
 def _tiling():
     """the tile sizes of csrc/layout.hip."""
-    src = open(os.path.join(ROOT, "torch-attention-ocr_amd", "csrc", "layout.hip")).read()
-    return {n: int(v) for n, v in re.findall(r"constexpr int (SAT_ROWS|SAT_COLS|SCAN_GROUPS) = (\d+);", src)}
+    return csrc_constants("layout.hip", ("SAT_ROWS", "SAT_COLS", "SCAN_GROUPS"))
 
 
 @pytest.mark.parametrize("thr,light", [(128, 0), (-1, 0), (128, 1), (-1, 1)], ids=["fixed", "otsu", "fixed_light", "otsu_light"])
@@ -151,7 +138,7 @@ def test_two_column_page_matches_restatement(cuda):
     np.testing.assert_array_equal(got, _expect_table(S, sat_pitch))
     import aocr
     need = aocr.lib.aocr_layout_scratch_bytes(H, W, 1024)
-    scratch = torch.full(((need + 7) // 8,), -1, dtype=torch.int64, device=cuda)
+    scratch = garbage_scratch(cuda, need, 0)                                          # exactly the queried size
     seen = set()
     for min_ink, max_blocks in ((2, 256), (1, 256), (2, 1), (2, 1024), (1, 5), (2, 256)):
         params = dict(L.DEFAULTS, min_ink=min_ink, **TWO_COL)

@@ -9,32 +9,23 @@ import torch
 
 import orient_ref as R
 from orient_cases import PAINTED, SHAPES, text_page
+from page_harness import expect_placed, garbage_scratch, guarded_words, place, poisoned
 from segment_cases import paint, seeded_page
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -7
 POISON = 0xAB
-
-
-def _place(cuda, page, pitch=None, offset=0, fill=0):
-    """the page inside a larger device buffer: rows `pitch` bytes apart, starting `offset` bytes in; every other byte is `fill`."""
-    H, W = page.shape
-    pitch = pitch or W
-    buf = np.full(offset + H * pitch + 16, fill, np.uint8)
-    view = np.lib.stride_tricks.as_strided(buf[offset:], (H, W), (pitch, 1))
-    view[:] = page
-    dev = torch.from_numpy(buf).to(cuda)
-    return dev, dev.data_ptr() + offset, pitch
+TAIL = 32                # bytes of the turned page's buffer behind the last row's pitch
 
 
 def _rotate(cuda, page, quarter, out_pitch, out_offset, orient_words=None, pitch=None, offset=0, shape=None):
     """raw aocr_rotate_page into a poisoned buffer sized for the output of `quarter`: (the whole buffer as the device left it, status)."""
     import aocr
     H, W = shape or page.shape
-    dev, addr, pitch = _place(cuda, page, pitch, offset, fill=99)
+    dev, addr, pitch = place(cuda, page, pitch, offset, fill=99)
     Ho = page.shape[1] if quarter & 1 else page.shape[0]
-    buf = torch.full((out_offset + Ho * max(out_pitch, 1) + 32,), POISON, dtype=torch.uint8, device=cuda)
+    buf = poisoned(cuda, out_offset + Ho * max(out_pitch, 1) + TAIL, POISON)
     od = torch.tensor(orient_words, dtype=torch.int32, device=cuda) if orient_words is not None else None
     st = aocr.lib.aocr_rotate_page(None, C.c_void_p(addr), pitch, H, W, aocr.ptr(od), quarter, C.c_void_p(buf.data_ptr() + out_offset), out_pitch)
     torch.cuda.synchronize()
@@ -45,9 +36,7 @@ def _expect(page, q, quarter, out_pitch, out_offset):
     turned = np.rot90(page, -q)
     Ho, Wo = turned.shape
     assert (Ho, Wo) == (page.shape[::-1] if quarter & 1 else page.shape)
-    buf = np.full(out_offset + Ho * out_pitch + 32, POISON, np.uint8)
-    np.lib.stride_tricks.as_strided(buf[out_offset:], (Ho, Wo), (out_pitch, 1))[:] = turned
-    return buf
+    return expect_placed(turned, out_pitch, out_offset, poison=POISON, tail=TAIL)
 
 
 _pages = {}
@@ -97,13 +86,13 @@ def test_rotate_invalid_arguments_leave_the_output_untouched(cuda):
         shape = kw.pop("shape", None)
         pitch = kw.pop("pitch", None)
         H, W = shape or page.shape
-        dev, addr, p = _place(cuda, page)
-        buf = torch.full((257 * 257 + 32,), POISON, dtype=torch.uint8, device=cuda)
+        dev, addr, p = place(cuda, page)
+        buf = poisoned(cuda, 257 * 257 + 32, POISON)
         st = aocr.lib.aocr_rotate_page(None, C.c_void_p(addr), pitch or p, H, W, None, kw["quarter"], aocr.ptr(buf), kw["out_pitch"])
         torch.cuda.synchronize()
         assert st != 0 and word in aocr.last_error(), (kw, aocr.last_error())
         assert (buf == POISON).all(), kw
-    dev, addr, p = _place(cuda, page)
+    dev, addr, p = place(cuda, page)
     assert aocr.lib.aocr_rotate_page(None, C.c_void_p(addr), p, 70, 257, None, 1, None, 70) != 0 and "out_dev" in aocr.last_error()
     assert aocr.lib.aocr_rotate_page(None, C.c_void_p(addr), p, 70, 257, None, 1, C.c_void_p(addr + 100), 70) != 0 and "overlap" in aocr.last_error()
     assert aocr.lib.aocr_rotate_page(None, None, p, 70, 257, None, 1, C.c_void_p(addr), 70) != 0
@@ -116,10 +105,10 @@ def _estimate(cuda, page, threshold, light, pitch=None, offset=0, shape=None):
     """raw aocr_estimate_orientation: (orient (8) then 4 sentinels, status); the scratch holds garbage."""
     import aocr
     H, W = shape or page.shape
-    dev, addr, pitch = _place(cuda, page, pitch, offset, fill=255 if light else 0)
+    dev, addr, pitch = place(cuda, page, pitch, offset, fill=255 if light else 0)
     need = aocr.lib.aocr_orient_scratch_bytes(max(H, 1), max(W, 1))
-    scratch = torch.full(((max(need, 1 << 12) + 7) // 8,), -1, dtype=torch.int64, device=cuda)
-    out = torch.full((12,), SENTINEL, dtype=torch.int32, device=cuda)
+    scratch = garbage_scratch(cuda, need, 1 << 12)
+    out = guarded_words(cuda, 8, 4, SENTINEL, torch.int32)
     st = aocr.lib.aocr_estimate_orientation(None, C.c_void_p(addr), pitch, H, W, threshold, light, aocr.ptr(scratch), aocr.ptr(out))
     torch.cuda.synchronize()
     return out.cpu().numpy(), st
@@ -184,7 +173,7 @@ def test_estimate_invalid_arguments_leave_the_output_untouched(cuda):
         assert (got == SENTINEL).all()
     assert aocr.lib.aocr_orient_scratch_bytes(0, 5) == 0 and aocr.lib.aocr_orient_scratch_bytes(16384, 4097) == 0
     assert aocr.lib.aocr_orient_scratch_bytes(16384, 4096) % 16 == 0 and aocr.lib.aocr_orient_scratch_bytes(1, 1) > 0
-    dev, addr, p = _place(cuda, page)
+    dev, addr, p = place(cuda, page)
     out = torch.full((8,), SENTINEL, dtype=torch.int32, device=cuda)
     scratch = torch.empty(1 << 10, dtype=torch.int64, device=cuda)
     assert aocr.lib.aocr_estimate_orientation(None, C.c_void_p(addr), p, 70, 257, 128, 0, None, aocr.ptr(out)) != 0

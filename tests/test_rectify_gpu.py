@@ -9,22 +9,13 @@ import torch
 
 import rectify_cases as RC
 import rectify_ref as R
+from page_harness import corner_pixels, expect_placed, garbage_scratch, guarded_words, place, poisoned, same_reading
 from segment_cases import seeded_page
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -7
 POISON = 0xAB
-
-
-def _place(cuda, page, pitch=None, offset=0, fill=0):
-    """the page inside a larger device buffer: rows `pitch` bytes apart, starting `offset` bytes in; every other byte is `fill`."""
-    H, W = page.shape
-    pitch = pitch or W
-    buf = np.full(offset + H * pitch + 16, fill, np.uint8)
-    np.lib.stride_tricks.as_strided(buf[offset:], (H, W), (pitch, 1))[:] = page
-    dev = torch.from_numpy(buf).to(cuda)
-    return dev, dev.data_ptr() + offset, pitch
 
 
 def _coef(c):
@@ -48,14 +39,13 @@ def test_warp_matches_restatement(cuda, shape):
     import aocr
     H, W, pitch, offset = shape
     page = _seeded(H, W)
-    dev, addr, pitch = _place(cuda, page, pitch, offset, fill=99)
+    dev, addr, pitch = place(cuda, page, pitch, offset, fill=99)
     n_fill = n_page = 0
     for name, coef, Ho, Wo in RC.warp_cases(H, W):
         for fill, (out_pitch, out_offset) in ((255, (Wo, 0)), (7, (Wo + 5, 3))):
             want_img = R.warp_page(page, coef, fill, Ho, Wo)
-            want = np.full(out_offset + Ho * out_pitch + 32, POISON, np.uint8)
-            np.lib.stride_tricks.as_strided(want[out_offset:], (Ho, Wo), (out_pitch, 1))[:] = want_img
-            buf = torch.full((len(want),), POISON, dtype=torch.uint8, device=cuda)
+            want = expect_placed(want_img, out_pitch, out_offset, poison=POISON, tail=32)
+            buf = poisoned(cuda, len(want), POISON)
             st = aocr.lib.aocr_warp_page(None, C.c_void_p(addr), pitch, H, W, _coef(coef), fill, C.c_void_p(buf.data_ptr() + out_offset), out_pitch,
                                          Ho, Wo)
             assert st == 0, (name, aocr.last_error())
@@ -94,17 +84,17 @@ def test_warp_invalid_arguments_leave_the_output_untouched(cuda):
     for kw, word in ((dict(fill=256), "fill"), (dict(fill=-1), "fill"), (dict(shape=(0, 129)), "page size"), (dict(shape=(63, 16385), pitch=16385), "page size"),
                      (dict(pitch=128), "pitch"), (dict(out=(0, 129)), "output size"), (dict(out=(63, 0)), "output size"),
                      (dict(out=(16385, 4)), "output size"), (dict(out=(16384, 4097)), "output size"), (dict(out_pitch=128), "out_pitch")):
-        dev, addr, p = _place(cuda, page)
+        dev, addr, p = place(cuda, page)
         H, W = kw.get("shape", page.shape)
         Ho, Wo = kw.get("out", page.shape)
-        buf = torch.full((63 * 129 + 32,), POISON, dtype=torch.uint8, device=cuda)
+        buf = poisoned(cuda, 63 * 129 + 32, POISON)
         st = aocr.lib.aocr_warp_page(None, C.c_void_p(addr), kw.get("pitch", p), H, W, _coef(ident), kw.get("fill", 255), aocr.ptr(buf),
                                      kw.get("out_pitch", max(Wo, 1)), Ho, Wo)
         torch.cuda.synchronize()
         assert st != 0 and word in aocr.last_error(), (kw, aocr.last_error())
         assert (buf == POISON).all(), kw
-    dev, addr, p = _place(cuda, page)
-    buf = torch.full((63 * 129 + 32,), POISON, dtype=torch.uint8, device=cuda)
+    dev, addr, p = place(cuda, page)
+    buf = poisoned(cuda, 63 * 129 + 32, POISON)
     assert aocr.lib.aocr_warp_page(None, C.c_void_p(addr), p, 63, 129, None, 255, aocr.ptr(buf), 129, 63, 129) != 0 and "coef" in aocr.last_error()
     assert aocr.lib.aocr_warp_page(None, C.c_void_p(addr), p, 63, 129, _coef(ident), 255, None, 129, 63, 129) != 0 and "out_dev" in aocr.last_error()
     assert aocr.lib.aocr_warp_page(None, None, p, 63, 129, _coef(ident), 255, aocr.ptr(buf), 129, 63, 129) != 0
@@ -120,10 +110,10 @@ def _quad(cuda, page, threshold, dark, pitch=None, offset=0, shape=None, around=
     """raw aocr_find_page_quad: (quad (16) then 4 sentinels, status); the scratch holds garbage."""
     import aocr
     H, W = shape or page.shape
-    dev, addr, pitch = _place(cuda, page, pitch, offset, fill=around)
+    dev, addr, pitch = place(cuda, page, pitch, offset, fill=around)
     need = aocr.lib.aocr_quad_scratch_bytes(max(min(H, 16384), 1), max(min(W, 4096), 1))
-    scratch = torch.full(((max(need, 1 << 12) + 7) // 8,), -1, dtype=torch.int64, device=cuda)
-    out = torch.full((20,), SENTINEL, dtype=torch.int32, device=cuda)
+    scratch = garbage_scratch(cuda, need, 1 << 12)
+    out = guarded_words(cuda, 16, 4, SENTINEL, torch.int32)
     st = aocr.lib.aocr_find_page_quad(None, C.c_void_p(addr), pitch, H, W, threshold, dark, aocr.ptr(scratch), aocr.ptr(out))
     torch.cuda.synchronize()
     return out.cpu().numpy(), st
@@ -181,7 +171,7 @@ def test_quad_invalid_arguments_leave_the_output_untouched(cuda):
         assert (got == SENTINEL).all()
     assert aocr.lib.aocr_quad_scratch_bytes(0, 5) == 0 and aocr.lib.aocr_quad_scratch_bytes(16384, 4097) == 0
     assert aocr.lib.aocr_quad_scratch_bytes(16384, 4096) % 16 == 0 and aocr.lib.aocr_quad_scratch_bytes(1, 1) > 0
-    dev, addr, p = _place(cuda, page)
+    dev, addr, p = place(cuda, page)
     out = torch.full((16,), SENTINEL, dtype=torch.int32, device=cuda)
     need = aocr.lib.aocr_quad_scratch_bytes(70, 257)
     scratch = torch.empty((need + 7) // 8 + 8, dtype=torch.int64, device=cuda)
@@ -202,19 +192,6 @@ def test_quad_invalid_arguments_leave_the_output_untouched(cuda):
 NEW_FIELDS = ("rectified", "rectify_quad", "rectify_size", "rectify_area", "photo_corners")
 
 
-def _same_reading(a, b):
-    np.testing.assert_array_equal(a.boxes, b.boxes)
-    np.testing.assert_array_equal(a.line, b.line)
-    np.testing.assert_array_equal(a.labels, b.labels)
-    assert a.text == b.text and a.n_lines == b.n_lines
-
-
-def _corner_pixels(boxes):
-    b = np.asarray(boxes, np.int64).reshape(-1, 4)
-    return (np.stack([b[:, 0], b[:, 2] - 1, b[:, 2] - 1, b[:, 0]], 1).astype(np.float64),
-            np.stack([b[:, 1], b[:, 1], b[:, 3] - 1, b[:, 3] - 1], 1).astype(np.float64))
-
-
 def test_recognize_page_rectify(cuda):
     import aocr
     from test_step_gpu import make
@@ -232,17 +209,17 @@ def test_recognize_page_rectify(cuda):
     for none in (None, False):                                                               # rectify=None is the call as it was
         same = m.recognize_page(upright, params, width=100, rectify=none)
         assert sorted(vars(same)) == sorted(vars(base))
-        _same_reading(same, base)
+        same_reading(same, base)
 
     area = int(R.find_page_quad(photo)[9])
     for how in (True, aocr.RectifyParams(), [tuple(quad[2 * i:2 * i + 2]) for i in range(4)], np.array(quad).reshape(4, 2)):
         res = m.recognize_page(photo, params, width=100, rectify=how)
-        _same_reading(res, base)
+        same_reading(res, base)
         np.testing.assert_array_equal(res.scores, base.scores)
         assert res.rectified is True and res.rectify_size == (Wo, Ho)
         np.testing.assert_array_equal(res.rectify_quad, np.array(quad).reshape(4, 2))
         assert res.rectify_area == (area if how is True or isinstance(how, aocr.RectifyParams) else None)
-        cx, cy = _corner_pixels(res.boxes)
+        cx, cy = corner_pixels(res.boxes)
         X, Y, _ = R.warp_points(coef, cx, cy)
         assert res.photo_corners.shape == (len(res.boxes), 4, 2) and res.photo_corners.dtype == np.float64
         np.testing.assert_array_equal(res.photo_corners, np.stack([X, Y], 2))
@@ -259,9 +236,9 @@ def test_recognize_page_rectify(cuda):
     # a sheet too small to be the page: the photograph is read as it is
     small = m.recognize_page(photo, params, width=100, rectify=aocr.RectifyParams(min_area_percent=99))
     plain = m.recognize_page(photo, params, width=100)
-    _same_reading(small, plain)
+    same_reading(small, plain)
     assert small.rectified is False and small.rectify_size is None and small.rectify_area == area
-    cx, cy = _corner_pixels(small.boxes)
+    cx, cy = corner_pixels(small.boxes)
     np.testing.assert_array_equal(small.photo_corners, np.stack([cx, cy], 2))
 
     # a page without a desk: one component fills the frame, the quad is the image corners, rectification is a copy
@@ -270,16 +247,16 @@ def test_recognize_page_rectify(cuda):
     nodesk = m.recognize_page(filled, params, width=100, rectify=True)
     np.testing.assert_array_equal(nodesk.rectify_quad, [[0, 0], [W - 1, 0], [W - 1, H - 1], [0, H - 1]])
     assert nodesk.rectified and nodesk.rectify_size == (W, H)
-    _same_reading(nodesk, m.recognize_page(filled, params, width=100))
+    same_reading(nodesk, m.recognize_page(filled, params, width=100))
 
     # with deskew and orient the corners start from source_corners: slope 0 and no turn here, so they are the corner pixels again
     both = m.recognize_page(photo, params, width=100, rectify=True, orient=0, deskew=aocr.SkewParams(n_steps=0))
-    _same_reading(both, base)
-    cx, cy = _corner_pixels(both.boxes)
+    same_reading(both, base)
+    cx, cy = corner_pixels(both.boxes)
     X, Y, _ = R.warp_points(coef, cx, cy)
     np.testing.assert_array_equal(both.photo_corners, np.stack([X, Y], 2))
     turned = m.recognize_page(photo, params, width=100, rectify=True, orient=2)
-    cx, cy = _corner_pixels(turned.source_boxes)
+    cx, cy = corner_pixels(turned.source_boxes)
     X, Y, _ = R.warp_points(coef, cx, cy)
     np.testing.assert_array_equal(turned.photo_corners, np.stack([X, Y], 2))
     print(f"[recognize_page rectify] quad {quad} -> {Wo} x {Ho}, sheet {area} pixels, {len(base.text)} boxes in {base.n_lines} lines")

@@ -10,22 +10,13 @@ import torch
 import components_cases as CC
 import scale_cases as SC
 import scale_ref as S
+from page_harness import corner_pixels, expect_placed, garbage_scratch, guarded_words, place, poisoned, same_reading
 from rectify_cases import TEXT_SEGMENT
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -7
 POISON = 0xAB
-
-
-def _place(cuda, page, pitch=None, offset=0, fill=0):
-    """the page inside a larger device buffer: rows `pitch` bytes apart, starting `offset` bytes in; every other byte is `fill`."""
-    H, W = page.shape
-    pitch = pitch or W
-    buf = np.full(offset + H * pitch + 16, fill, np.uint8)
-    np.lib.stride_tricks.as_strided(buf[offset:], (H, W), (pitch, 1))[:] = page
-    dev = torch.from_numpy(buf).to(cuda)
-    return dev, dev.data_ptr() + offset, pitch
 
 
 # ---- aocr_resize_page ------------------------------------------------------------------------------------------------------------------------
@@ -37,11 +28,10 @@ def test_resize_matches_restatement(cuda, shape):
     (H, W, pitch, offset), (Ho, Wo), (out_pitch, out_offset) = shape
     page = SC.resize_source(H, W)
     out_pitch = out_pitch or Wo
-    dev, addr, pitch = _place(cuda, page, pitch, offset, fill=99)
+    dev, addr, pitch = place(cuda, page, pitch, offset, fill=99)
     want_img = S.resize_page(page, Ho, Wo)
-    want = np.full(out_offset + Ho * out_pitch + 32, POISON, np.uint8)
-    np.lib.stride_tricks.as_strided(want[out_offset:], (Ho, Wo), (out_pitch, 1))[:] = want_img
-    buf = torch.full((len(want),), POISON, dtype=torch.uint8, device=cuda)
+    want = expect_placed(want_img, out_pitch, out_offset, poison=POISON, tail=32)
+    buf = poisoned(cuda, len(want), POISON)
     st = aocr.lib.aocr_resize_page(None, C.c_void_p(addr), pitch, H, W, C.c_void_p(buf.data_ptr() + out_offset), out_pitch, Ho, Wo)
     assert st == 0, aocr.last_error()
     got = buf.cpu().numpy()
@@ -82,16 +72,16 @@ def test_resize_invalid_arguments_leave_the_output_untouched(cuda):
                      (dict(shape=(63, 16385), pitch=16385), "page size"), (dict(pitch=128), "pitch"), (dict(out=(0, 129)), "output size"),
                      (dict(out=(63, 0)), "output size"), (dict(out=(16385, 129)), "output size"),
                      (dict(shape=(4096, 4096), pitch=4096, out=(16384, 4097)), "output size"), (dict(out_pitch=128), "out_pitch")):
-        dev, addr, p = _place(cuda, page)
+        dev, addr, p = place(cuda, page)
         H, W = kw.get("shape", page.shape)
         Ho, Wo = kw.get("out", page.shape)
-        buf = torch.full((63 * 129 + 32,), POISON, dtype=torch.uint8, device=cuda)
+        buf = poisoned(cuda, 63 * 129 + 32, POISON)
         st = f(None, C.c_void_p(addr), kw.get("pitch", p), H, W, aocr.ptr(buf), kw.get("out_pitch", max(Wo, 1)), Ho, Wo)
         torch.cuda.synchronize()
         assert st != 0 and word in aocr.last_error(), (kw, aocr.last_error())
         assert (buf == POISON).all(), kw
-    dev, addr, p = _place(cuda, page)
-    buf = torch.full((63 * 129 + 32,), POISON, dtype=torch.uint8, device=cuda)
+    dev, addr, p = place(cuda, page)
+    buf = poisoned(cuda, 63 * 129 + 32, POISON)
     assert f(None, C.c_void_p(addr), p, 63, 129, None, 129, 63, 129) != 0 and "out_dev" in aocr.last_error()
     assert f(None, None, p, 63, 129, aocr.ptr(buf), 129, 63, 129) != 0 and "page_dev" in aocr.last_error()
     assert f(None, C.c_void_p(addr), p, 63, 129, C.c_void_p(addr + 100), 129, 20, 129) != 0 and "overlap" in aocr.last_error()
@@ -105,11 +95,11 @@ def _glyph(cuda, page, params=None, pitch=None, offset=0, shape=None, around=255
     """raw aocr_estimate_glyph_size: (glyph (8) then 4 sentinels, status); the scratch holds garbage."""
     import aocr
     H, W = shape or page.shape
-    dev, addr, pitch = _place(cuda, page, pitch, offset, fill=around)
+    dev, addr, pitch = place(cuda, page, pitch, offset, fill=around)
     p = params if params is not None else aocr.GlyphParams(**kw)
     need = aocr.lib.aocr_glyph_scratch_bytes(max(min(H, 16384), 1), max(min(W, 4096), 1))
-    scratch = torch.full(((max(need, 1 << 12) + 7) // 8,), -1, dtype=torch.int64, device=cuda)
-    out = torch.full((12,), SENTINEL, dtype=torch.int32, device=cuda)
+    scratch = garbage_scratch(cuda, need, 1 << 12)
+    out = guarded_words(cuda, 8, 4, SENTINEL, torch.int32)
     st = aocr.lib.aocr_estimate_glyph_size(None, C.c_void_p(addr), pitch, H, W, C.byref(p), aocr.ptr(scratch), aocr.ptr(out))
     torch.cuda.synchronize()
     return out.cpu().numpy(), st
@@ -192,7 +182,7 @@ def test_glyph_invalid_arguments_leave_the_output_untouched(cuda):
         assert st != 0 and word in aocr.last_error() and (got == SENTINEL).all()
     assert aocr.lib.aocr_glyph_scratch_bytes(0, 5) == 0 and aocr.lib.aocr_glyph_scratch_bytes(16384, 4097) == 0
     assert aocr.lib.aocr_glyph_scratch_bytes(16384, 4096) % 16 == 0 and aocr.lib.aocr_glyph_scratch_bytes(1, 1) > 0
-    dev, addr, pt = _place(cuda, page)
+    dev, addr, pt = place(cuda, page)
     out = torch.full((8,), SENTINEL, dtype=torch.int32, device=cuda)
     need = aocr.lib.aocr_glyph_scratch_bytes(H, W)
     scratch = torch.empty((need + 7) // 8 + 8, dtype=torch.int64, device=cuda)
@@ -214,19 +204,6 @@ def test_glyph_invalid_arguments_leave_the_output_untouched(cuda):
 NEW_FIELDS = ("scaled", "scale_size", "scale_quartiles", "scale_glyphs", "scale_shape", "unscaled_corners")
 
 
-def _same_reading(a, b):
-    np.testing.assert_array_equal(a.boxes, b.boxes)
-    np.testing.assert_array_equal(a.line, b.line)
-    np.testing.assert_array_equal(a.labels, b.labels)
-    assert a.text == b.text and a.n_lines == b.n_lines
-
-
-def _corner_pixels(boxes):
-    b = np.asarray(boxes, np.int64).reshape(-1, 4)
-    return (np.stack([b[:, 0], b[:, 2] - 1, b[:, 2] - 1, b[:, 0]], 1).astype(np.float64),
-            np.stack([b[:, 1], b[:, 1], b[:, 3] - 1, b[:, 3] - 1], 1).astype(np.float64))
-
-
 def test_recognize_page_scale(cuda):
     import aocr
     from test_step_gpu import make
@@ -244,14 +221,14 @@ def test_recognize_page_scale(cuda):
     for none in (None, False):                                                               # scale=None is the call as it was
         same = m.recognize_page(p, params, width=100, scale=none)
         assert sorted(vars(same)) == sorted(vars(base))
-        _same_reading(same, base)
+        same_reading(same, base)
 
     # a ratio given: the 2x page halved is p exactly, so the reading is that of p, and the corners map back onto the 2x page
     half = m.recognize_page(twice, params, width=100, scale=0.5)
-    _same_reading(half, base)
+    same_reading(half, base)
     np.testing.assert_array_equal(half.scores, base.scores)
     assert half.scaled is True and half.scale_shape == (W, H) and half.scale_size is None and half.scale_quartiles is None and half.scale_glyphs is None
-    cx, cy = _corner_pixels(base.boxes)
+    cx, cy = corner_pixels(base.boxes)
     ux, uy = S.unscale(cx, cy, 2 * H, 2 * W, H, W)
     assert half.unscaled_corners.shape == (len(base.boxes), 4, 2) and half.unscaled_corners.dtype == np.float64
     np.testing.assert_array_equal(half.unscaled_corners, np.stack([ux, uy], 2))
@@ -261,7 +238,7 @@ def test_recognize_page_scale(cuda):
     want = S.estimate_glyph_size(p, threshold=params.threshold)
     for how in (True, aocr.ScaleParams(aocr.GlyphParams(threshold=params.threshold))):
         auto = m.recognize_page(p, params, width=100, scale=how)
-        _same_reading(auto, base)
+        same_reading(auto, base)
         assert auto.scaled is False and auto.scale_shape is None and auto.scale_size == want[0] == 15
         assert auto.scale_quartiles == (int(want[1]), int(want[2])) and auto.scale_glyphs == want[3]
         np.testing.assert_array_equal(auto.unscaled_corners, np.stack([cx, cy], 2))
@@ -273,14 +250,14 @@ def test_recognize_page_scale(cuda):
     assert big.scaled is True and big.scale_size == want2[0] == 30 and big.scale_glyphs == want2[3]
     assert big.scale_shape == plan == S.scale_plan(30, int(want2[3]), 2 * H, 2 * W)
     assert big.n_lines == 12
-    bx, by = _corner_pixels(big.boxes)
+    bx, by = corner_pixels(big.boxes)
     ux, uy = S.unscale(bx, by, 2 * H, 2 * W, plan[1], plan[0])
     np.testing.assert_array_equal(big.unscaled_corners, np.stack([ux, uy], 2))
 
     # with rectify, photo_corners goes through the scale map first: the image corners as the quad make the warp a copy
     quad = [(0, 0), (2 * W - 1, 0), (2 * W - 1, 2 * H - 1), (0, 2 * H - 1)]
     both = m.recognize_page(twice, params, width=100, rectify=quad, scale=0.5)
-    _same_reading(both, base)
+    same_reading(both, base)
     np.testing.assert_array_equal(both.photo_corners, half.unscaled_corners)
     np.testing.assert_array_equal(both.unscaled_corners, half.unscaled_corners)
 

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import segment_ref as R
+from page_harness import garbage_scratch, guarded_words, place
 from segment_cases import CASES, SEEDED, SEEDED_SHAPES, seeded_page
 
 pytestmark = pytest.mark.gpu
@@ -18,29 +19,18 @@ GUARD_ROWS = 4           # rows of boxes_dev beyond max_boxes that every raw cal
 CHARS = "0123456789abcdefghijklmnopqrstuvwxyz"
 
 
-def _place(cuda, page, pitch=None, offset=0, fill=0):
-    """the page inside a larger device buffer: rows `pitch` bytes apart, starting `offset` bytes in; every other byte is `fill` (ink, were it read)."""
-    H, W = page.shape
-    pitch = pitch or W
-    buf = np.full(offset + H * pitch + 16, fill, np.uint8)
-    view = np.lib.stride_tricks.as_strided(buf[offset:], (H, W), (pitch, 1))
-    view[:] = page
-    dev = torch.from_numpy(buf).to(cuda)
-    return dev, dev.data_ptr() + offset, pitch
-
-
 def _segment(cuda, page, params, max_boxes=64, pitch=None, offset=0):
     """raw aocr_segment_page: (boxes (max_boxes + GUARD_ROWS, 6) with SENTINEL in the rows that were not written, counts, status).  The
     tensor is longer than max_boxes, so that a write past the cut lands in rows the caller checks, not in the allocator's slack."""
     import aocr
     H, W = page.shape
-    dev, addr, pitch = _place(cuda, page, pitch, offset)
+    dev, addr, pitch = place(cuda, page, pitch, offset, fill=0)           # the bytes around the page are ink, were they read
     p = aocr.SegmentParams(**params)
     need = aocr.lib.aocr_segment_scratch_bytes(H, W, max_boxes)
     assert need > 0
-    scratch = torch.full(((need + 7) // 8,), -1, dtype=torch.int64, device=cuda)      # garbage: the call must not rely on zeroed scratch
-    boxes = torch.full((max_boxes + GUARD_ROWS, 6), SENTINEL, dtype=torch.int32, device=cuda)
-    counts = torch.full((4,), SENTINEL, dtype=torch.int32, device=cuda)
+    scratch = garbage_scratch(cuda, need, 0)                              # exactly the queried size: the call must not rely on zeroed scratch
+    boxes = guarded_words(cuda, max_boxes, GUARD_ROWS, SENTINEL, torch.int32, width=6)
+    counts = guarded_words(cuda, 4, 0, SENTINEL, torch.int32)
     st = aocr.lib.aocr_segment_page(None, C.c_void_p(addr), pitch, H, W, C.byref(p), aocr.ptr(scratch), max_boxes, aocr.ptr(boxes), aocr.ptr(counts))
     torch.cuda.synchronize()
     return boxes.cpu().numpy(), counts.cpu().numpy(), st
@@ -240,7 +230,7 @@ def test_invalid_arguments_leave_the_outputs_untouched(cuda):
         boxes, counts, st = _segment(cuda, page, dict(good, **{field: v}), 16)
         assert st != 0 and field in aocr.last_error(), (field, aocr.last_error())
         assert (boxes == SENTINEL).all() and (counts == SENTINEL).all(), field
-    dev, addr, pitch = _place(cuda, page)
+    dev, addr, pitch = place(cuda, page)
     p = aocr.SegmentParams(**good)
     boxes = torch.full((16, 6), SENTINEL, dtype=torch.int32, device=cuda)
     counts = torch.full((4,), SENTINEL, dtype=torch.int32, device=cuda)
@@ -299,7 +289,7 @@ def test_crop_lines_equals_preprocess_lines(cuda, out_w):
     bx[:, :4] = np.array(CROP_BOXES, np.int64).astype(np.int32)
     boxes = torch.from_numpy(bx).to(cuda)
     for pitch, offset in ((128, 0), (141, 3)):
-        dev, addr, pitch = _place(cuda, page, pitch, offset, fill=99)
+        dev, addr, pitch = place(cuda, page, pitch, offset, fill=99)
 
         def crop(count, n_boxes):
             out = torch.full((n, 1, 32, out_w), float(SENTINEL), dtype=torch.float32, device=cuda)

@@ -10,6 +10,7 @@ import torch
 
 import segment_ref as R
 import skew_ref as S
+from page_harness import expect_placed, garbage_scratch, guarded_words, place, poisoned
 from skew_cases import PLANTED, PLANTED_K0, SEGMENT, noise_page, planted_page, text_page, tie_page
 
 pytestmark = pytest.mark.gpu
@@ -17,29 +18,19 @@ pytestmark = pytest.mark.gpu
 SENTINEL = -7
 GUARD = 4                # entries of scores_dev beyond 2K+1 that every raw call gets: they must keep their sentinel
 POISON = 0xAB
-
-
-def _place(cuda, page, pitch=None, offset=0, fill=0):
-    """the page inside a larger device buffer: rows `pitch` bytes apart, starting `offset` bytes in; every other byte is `fill`."""
-    H, W = page.shape
-    pitch = pitch or W
-    buf = np.full(offset + H * pitch + 16, fill, np.uint8)
-    view = np.lib.stride_tricks.as_strided(buf[offset:], (H, W), (pitch, 1))
-    view[:] = page
-    dev = torch.from_numpy(buf).to(cuda)
-    return dev, dev.data_ptr() + offset, pitch
+TAIL = 32                # bytes of the deskewed page's buffer behind the last row's pitch
 
 
 def _estimate(cuda, page, params, pitch=None, offset=0, scores=True, shape=None):
     """raw aocr_estimate_skew: (skew (4), scores (2K+1) uint64 then GUARD sentinels, status); the scratch holds garbage."""
     import aocr
     H, W = shape or page.shape
-    dev, addr, pitch = _place(cuda, page, pitch, offset)
+    dev, addr, pitch = place(cuda, page, pitch, offset)
     p = aocr.SkewParams(**params)
     need = aocr.lib.aocr_skew_scratch_bytes(H, W, p.n_steps)
-    scratch = torch.full(((max(need, 1 << 16) + 7) // 8,), -1, dtype=torch.int64, device=cuda)
-    skew = torch.full((4,), SENTINEL, dtype=torch.int32, device=cuda)
-    sc = torch.full((2 * max(p.n_steps, 0) + 1 + GUARD,), SENTINEL, dtype=torch.int64, device=cuda)
+    scratch = garbage_scratch(cuda, need, 1 << 16)
+    skew = guarded_words(cuda, 4, 0, SENTINEL, torch.int32)
+    sc = guarded_words(cuda, 2 * max(p.n_steps, 0) + 1, GUARD, SENTINEL, torch.int64)
     st = aocr.lib.aocr_estimate_skew(None, C.c_void_p(addr), pitch, H, W, C.byref(p), aocr.ptr(scratch), aocr.ptr(skew), aocr.ptr(sc) if scores else None)
     torch.cuda.synchronize()
     return skew.cpu().numpy(), sc.cpu().numpy(), st
@@ -152,14 +143,14 @@ def test_invalid_arguments_leave_the_outputs_untouched(cuda):
         skew, sc, st = _estimate(cuda, page, good, pit, 0, shape=(H, W))
         assert st != 0 and word in aocr.last_error(), (H, W, pit, aocr.last_error())
         assert (skew == SENTINEL).all() and (sc == SENTINEL).all()
-    dev, addr, pitch = _place(cuda, page)
+    dev, addr, pitch = place(cuda, page)
     p = aocr.SkewParams(**good)
     scratch = torch.empty(1 << 16, dtype=torch.int64, device=cuda)
     skew = torch.full((4,), SENTINEL, dtype=torch.int32, device=cuda)
     assert aocr.lib.aocr_estimate_skew(None, C.c_void_p(addr), pitch, 40, 100, C.byref(p), None, aocr.ptr(skew), None) != 0
     assert aocr.lib.aocr_estimate_skew(None, C.c_void_p(addr), pitch, 40, 100, C.byref(p), aocr.ptr(scratch), None, None) != 0
     assert aocr.lib.aocr_estimate_skew(None, C.c_void_p(addr), pitch, 40, 100, None, aocr.ptr(scratch), aocr.ptr(skew), None) != 0
-    out = torch.full((40 * 100,), POISON, dtype=torch.uint8, device=cuda)
+    out = poisoned(cuda, 40 * 100, POISON)
     for args, word in (((None, 0, 256, aocr.ptr(out), 100), "fill"), ((None, 0, -1, aocr.ptr(out), 100), "fill"), ((None, 0, 255, aocr.ptr(out), 99), "out_pitch"),
                        ((None, 0, 255, None, 100), "out_dev"), ((None, 0, 255, C.c_void_p(addr + 50), 100), "overlap")):
         st = aocr.lib.aocr_deskew_page(None, C.c_void_p(addr), pitch, 40, 100, *args)
@@ -173,8 +164,8 @@ def _deskew(cuda, page, slope, fill, out_pitch, out_offset, skew_words=None, pit
     """raw aocr_deskew_page into a poisoned buffer: (the whole buffer as the device left it, status)."""
     import aocr
     H, W = page.shape
-    dev, addr, pitch = _place(cuda, page, pitch, offset, fill=99)
-    buf = torch.full((out_offset + H * out_pitch + 32,), POISON, dtype=torch.uint8, device=cuda)
+    dev, addr, pitch = place(cuda, page, pitch, offset, fill=99)
+    buf = poisoned(cuda, out_offset + H * out_pitch + TAIL, POISON)
     sk = torch.tensor(skew_words, dtype=torch.int32, device=cuda) if skew_words is not None else None
     st = aocr.lib.aocr_deskew_page(None, C.c_void_p(addr), pitch, H, W, aocr.ptr(sk), slope, fill, C.c_void_p(buf.data_ptr() + out_offset), out_pitch)
     torch.cuda.synchronize()
@@ -182,10 +173,7 @@ def _deskew(cuda, page, slope, fill, out_pitch, out_offset, skew_words=None, pit
 
 
 def _expect(page, slope, fill, out_pitch, out_offset):
-    H, W = page.shape
-    buf = np.full(out_offset + H * out_pitch + 32, POISON, np.uint8)
-    np.lib.stride_tricks.as_strided(buf[out_offset:], (H, W), (out_pitch, 1))[:] = S.deskew(page, slope, fill)
-    return buf
+    return expect_placed(S.deskew(page, slope, fill), out_pitch, out_offset, poison=POISON, tail=TAIL)
 
 
 @pytest.mark.parametrize("W", [1, 15, 16, 17, 333])

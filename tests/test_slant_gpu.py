@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import slant_ref as R
+from page_harness import garbage_scratch, guarded_words, place
 from slant_cases import DEFAULTS, PLANTED_K, STROKE, bar_page, bar_word, seeded_page, stroke_5x7
 
 pytestmark = pytest.mark.gpu
@@ -19,22 +20,12 @@ SENTINEL = -7
 GUARD = 3                # rows beyond n_boxes that every raw call's outputs get: they must keep their sentinel
 
 
-def _place(cuda, page, pitch=None, offset=0, fill=0):
-    """the page inside a larger device buffer: rows `pitch` bytes apart, starting `offset` bytes in; every other byte is `fill`."""
-    H, W = page.shape
-    pitch = pitch or W
-    buf = np.full(offset + H * pitch + 16, fill, np.uint8)
-    np.lib.stride_tricks.as_strided(buf[offset:], (H, W), (pitch, 1))[:] = page
-    dev = torch.from_numpy(buf).to(cuda)
-    return dev, dev.data_ptr() + offset, pitch
-
-
 def _estimate(cuda, page, boxes, params, count=None, word=None, pitch=None, offset=0, scores=True, shape=None, n_boxes=None):
     """raw aocr_estimate_slant over poison: (slant (n + GUARD, 4), scores (n + GUARD, 2K + 1), status).  count: the device word count_dev[0]
     (None: count_dev = NULL); word: the device word threshold_dev[0] (None: threshold_dev = NULL); the scratch holds garbage."""
     import aocr
     H, W = shape or page.shape
-    dev, addr, placed = _place(cuda, page, max(pitch or 0, page.shape[1]), offset, fill=131)      # `pitch` below the page's width is only passed on
+    dev, addr, placed = place(cuda, page, max(pitch or 0, page.shape[1]), offset, fill=131)      # `pitch` below the page's width is only passed on
     pitch = pitch or placed
     p = aocr.SlantParams(**{k: v for k, v in params.items() if k != "reserved"})
     if "reserved" in params:
@@ -43,10 +34,9 @@ def _estimate(cuda, page, boxes, params, count=None, word=None, pitch=None, offs
     n = len(bx) if n_boxes is None else n_boxes
     K = min(max(p.n_steps, 0), 64)
     need = aocr.lib.aocr_slant_scratch_bytes(min(max(n, 0), 65535), K)
-    scratch = torch.full(((max(need, 1 << 12) + 7) // 8,), -1, dtype=torch.int64, device=cuda)
-    rows = max(n, 0) + GUARD
-    sl = torch.full((rows, 4), SENTINEL, dtype=torch.int32, device=cuda)
-    sc = torch.full((rows, 2 * K + 1), SENTINEL, dtype=torch.int64, device=cuda)
+    scratch = garbage_scratch(cuda, need, 1 << 12)
+    sl = guarded_words(cuda, max(n, 0), GUARD, SENTINEL, torch.int32, width=4)
+    sc = guarded_words(cuda, max(n, 0), GUARD, SENTINEL, torch.int64, width=2 * K + 1)
     cnt = torch.tensor([count, 9, 9, 9], dtype=torch.int32, device=cuda) if count is not None else None
     thr = torch.tensor([word], dtype=torch.int32, device=cuda) if word is not None else None
     st = aocr.lib.aocr_estimate_slant(None, C.c_void_p(addr), pitch, H, W, aocr.ptr(bx), aocr.ptr(cnt), n, C.byref(p), aocr.ptr(thr),
@@ -166,7 +156,7 @@ def _crop_reference(cuda, page, slants, fill, out_w):
 def _crop(cuda, page, bx, slants, fill, out_w, pitch=None, offset=0, count=None, n_boxes=None, plain=False):
     import aocr
     n = len(bx)
-    dev, addr, pitch = _place(cuda, page, pitch, offset, fill=99)
+    dev, addr, pitch = place(cuda, page, pitch, offset, fill=99)
     boxes = torch.from_numpy(bx).to(cuda)
     out = torch.full((n, 1, 32, out_w), float(SENTINEL), dtype=torch.float32, device=cuda)
     cnt = torch.tensor([count, 0, 0, 0], dtype=torch.int32, device=cuda) if count is not None else None
@@ -239,7 +229,7 @@ def test_invalid_arguments_leave_the_outputs_untouched(cuda):
     for nb in (-1, 65536):
         sl, sc, st = _estimate(cuda, page, boxes, DEFAULTS, n_boxes=nb)
         assert st != 0 and "n_boxes" in aocr.last_error() and (sl == SENTINEL).all() and (sc == SENTINEL).all()
-    dev, addr, pitch = _place(cuda, page)
+    dev, addr, pitch = place(cuda, page)
     p = aocr.SlantParams(**DEFAULTS)
     bx = torch.from_numpy(np.ascontiguousarray(boxes)).to(cuda)
     scratch = torch.empty(1 << 12, dtype=torch.int64, device=cuda)

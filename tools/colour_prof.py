@@ -7,9 +7,7 @@ one JSON line and writes it to profiles/colour_prof.json.
 `colour_prof.py --trace N` instead runs N estimates and N gray passes and nothing else, for
 `rocprofv3 --kernel-trace --stats -- python tools/colour_prof.py --trace 300`."""
 import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -17,7 +15,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from segment_prof import H, W, HBM_BYTES_PER_S, WINDOWS, windows             # noqa: E402  (also puts the package on sys.path)
+from segment_prof import H, W, HBM_BYTES_PER_S, WINDOWS, emit, time_rows     # noqa: E402  (also puts the package on sys.path)
 from layout_prof import GUTTER, HEADLINE_ROWS, two_column_a4                  # noqa: E402
 import aocr                                                                   # noqa: E402
 
@@ -69,18 +67,13 @@ def main():
     w = words.cpu().tolist()
     row["paper"], row["hues"], row["dropped"] = w[:3], w[4:10], w[10]
     row["paper_pixels_are_white"] = bool(int((out == 255).sum()) > H * W // 2)
-    for name, fn, iters in (("estimate", estimate, 50), ("gray", gray, 50), ("torch_luma", torch_luma, 20)):
-        t = windows(fn, iters)
-        row[name + "_ms"], row[name + "_ms_min"], row[name + "_ms_max"] = statistics.median(t), min(t), max(t)
+    time_rows(row, [("estimate", estimate, 50), ("gray", gray, 50), ("torch_luma", torch_luma, 20)])
     row["estimate_floor_ms"] = 3 * H * W / HBM_BYTES_PER_S * 1e3                # one read of the page
     row["gray_floor_ms"] = 4 * H * W / HBM_BYTES_PER_S * 1e3                    # one read of the page and one write of the gray page
     row["estimate_over_floor"] = row["estimate_ms"] / row["estimate_floor_ms"]
     row["gray_over_floor"] = row["gray_ms"] / row["gray_floor_ms"]
     row["torch_luma_over_gray"] = row["torch_luma_ms"] / row["gray_ms"]
-    line = json.dumps({k: (round(v, 5) if isinstance(v, float) else v) for k, v in row.items()})
-    print(line, flush=True)
-    with open(os.path.join(HERE, "..", "profiles", "colour_prof.json"), "w") as f:
-        f.write(line + "\n")
+    emit(row, "colour")
 
 
 if __name__ == "__main__":

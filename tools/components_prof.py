@@ -9,7 +9,6 @@ text page.  Prints one JSON line and writes it to profiles/components_prof.json.
 `components_prof.py --trace N CONTENT` instead runs N labelling calls and N cleaning calls on one content (checker: 4-connectivity) and
 nothing else, for `rocprofv3 --kernel-trace --stats -- python tools/components_prof.py --trace 100 text`."""
 import ctypes as C
-import json
 import os
 import statistics
 import sys
@@ -20,7 +19,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "..", "tests"))
-from segment_prof import H, W, HBM_BYTES_PER_S, WINDOWS, windows              # noqa: E402  (also puts the package on sys.path)
+from segment_prof import H, W, HBM_BYTES_PER_S, WINDOWS, emit, time_rows, windows     # noqa: E402  (also puts the package on sys.path)
 from layout_cases import two_column_page                                      # noqa: E402
 import aocr                                                                   # noqa: E402
 
@@ -85,9 +84,8 @@ def main():
         row[name + "_info"], row[name + "_counts"] = info.cpu().tolist(), counts.cpu().tolist()
         iters = 20 if name.startswith("checker") else 50
         for call, fn in (("label", label), ("clean", clean)):
-            t = windows(lambda: fn(page, conn), iters)
             k = f"{name}_{call}"
-            row[k + "_ms"], row[k + "_ms_min"], row[k + "_ms_max"] = statistics.median(t), min(t), max(t)
+            time_rows(row, [(k, lambda: fn(page, conn), iters)])
             row[k + "_over_floor"] = row[k + "_ms"] / row[call + "_floor_ms"]
     page = torch.from_numpy(content["text"][0]).to(dev)
     sat_pitch = (W + 1 + 3) & ~3
@@ -110,10 +108,7 @@ def main():
     row["segment_otsu_ms"] = statistics.median(windows(seg, 50))
     row["checker_label_over_text_label"] = row["checker_label_ms"] / row["text_label_ms"]
     row["text_label_over_segment"] = row["text_label_ms"] / row["segment_otsu_ms"]
-    line = json.dumps({k: (round(v, 5) if isinstance(v, float) else v) for k, v in row.items()})
-    print(line, flush=True)
-    with open(os.path.join(HERE, "..", "profiles", "components_prof.json"), "w") as f:
-        f.write(line + "\n")
+    emit(row, "components")
 
 
 if __name__ == "__main__":

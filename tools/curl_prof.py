@@ -6,9 +6,7 @@ profiles/curl_prof.json.
 `curl_prof.py --trace N` instead runs N estimate calls, N dewarp calls and N deskew calls and nothing else, for
 `rocprofv3 --kernel-trace --stats -- python tools/curl_prof.py --trace 300` (profiles/curl_kernel_stats.csv)."""
 import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -16,7 +14,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from segment_prof import HBM_BYTES_PER_S, WINDOWS, a4_page, windows           # noqa: E402  (also puts the package on sys.path)
+from segment_prof import HBM_BYTES_PER_S, WINDOWS, a4_page, emit, time_rows   # noqa: E402  (also puts the package on sys.path)
 import aocr                                                                   # noqa: E402
 
 H, W = 3300, 2550
@@ -72,15 +70,10 @@ def main():
     row["lines_flat"] = int(aocr.segment_page_device(torch.from_numpy(flat_h).to(dev), seg, 4096)[1][1])
     row["lines_curled"] = int(aocr.segment_page_device(page, seg, 4096)[1][1])
     row["lines_dewarped"] = int(aocr.segment_page_device(out, seg, 4096)[1][1])
-    for name, fn in (("estimate_otsu", est), ("dewarp", dewarp), ("deskew", deskew)):
-        t = windows(fn, 50)
-        row[name + "_ms"], row[name + "_ms_min"], row[name + "_ms_max"] = statistics.median(t), min(t), max(t)
+    time_rows(row, [("estimate_otsu", est, 50), ("dewarp", dewarp, 50), ("deskew", deskew, 50)])
     row["copy_floor_ms"] = 2 * H * W / HBM_BYTES_PER_S * 1e3                  # one read and one write of the page
     row["dewarp_over_deskew"] = row["dewarp_ms"] / row["deskew_ms"]
-    line = json.dumps({k: (round(v, 5) if isinstance(v, float) else v) for k, v in row.items()})
-    print(line, flush=True)
-    with open(os.path.join(HERE, "..", "profiles", "curl_prof.json"), "w") as f:
-        f.write(line + "\n")
+    emit(row, "curl")
 
 
 if __name__ == "__main__":

@@ -6,9 +6,7 @@ writes it to profiles/flatten_prof.json.
 `flatten_prof.py --trace N [radius]` instead runs N flatten calls and nothing else, for
 `rocprofv3 --kernel-trace --stats -- python tools/flatten_prof.py --trace 300`."""
 import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -16,7 +14,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from segment_prof import H, W, HBM_BYTES_PER_S, WINDOWS, a4_page, windows     # noqa: E402  (also puts the package on sys.path)
+from segment_prof import H, W, HBM_BYTES_PER_S, WINDOWS, a4_page, emit, time_rows     # noqa: E402  (also puts the package on sys.path)
 import aocr                                                                   # noqa: E402
 
 FLOOR = 110
@@ -77,18 +75,13 @@ def main():
     flat(16, clean)
     row["clean_page_unchanged"] = bool(torch.equal(out, clean))
     flat(16)
-    for name, fn in (("flatten_r16", lambda: flat(16)), ("flatten_r48", lambda: flat(48)), ("flatten_r127", lambda: flat(127)),
-                     ("segment_otsu", lambda: seg(out)), ("estimate_otsu", lambda: est(out))):
-        t = windows(fn, 50)
-        row[name + "_ms"], row[name + "_ms_min"], row[name + "_ms_max"] = statistics.median(t), min(t), max(t)
+    time_rows(row, [("flatten_r16", lambda: flat(16), 50), ("flatten_r48", lambda: flat(48), 50), ("flatten_r127", lambda: flat(127), 50),
+                    ("segment_otsu", lambda: seg(out), 50), ("estimate_otsu", lambda: est(out), 50)])
     row["floor_ms"] = 2 * H * W / HBM_BYTES_PER_S * 1e3                       # one read and one write of the page
     row["r48_over_r16"] = row["flatten_r48_ms"] / row["flatten_r16_ms"]
     row["flatten_r16_over_floor"] = row["flatten_r16_ms"] / row["floor_ms"]
     row["flatten_r16_over_segment"] = row["flatten_r16_ms"] / row["segment_otsu_ms"]
-    line = json.dumps({k: (round(v, 5) if isinstance(v, float) else v) for k, v in row.items()})
-    print(line, flush=True)
-    with open(os.path.join(HERE, "..", "profiles", "flatten_prof.json"), "w") as f:
-        f.write(line + "\n")
+    emit(row, "flatten")
 
 
 if __name__ == "__main__":

@@ -6,16 +6,14 @@ table write (5 bytes per pixel) at the HBM rate.  Prints one JSON line and write
 `layout_prof.py --trace N` instead runs N table calls (Otsu) and N cuts and nothing else, for
 `rocprofv3 --kernel-trace --stats -- python tools/layout_prof.py --trace 300`."""
 import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from segment_prof import H, W, HBM_BYTES_PER_S, WINDOWS, a4_page, windows     # noqa: E402  (also puts the package on sys.path)
+from segment_prof import H, W, HBM_BYTES_PER_S, WINDOWS, a4_page, emit, time_rows     # noqa: E402  (also puts the package on sys.path)
 import aocr                                                                   # noqa: E402
 
 HEADLINE_ROWS, BODY_ROW, GUTTER = 330, 400, (1200, 1280)
@@ -76,19 +74,14 @@ def main():
     row["table_total_matches_mask"] = bool(int(info[1]) == int((page <= int(info[0])).sum()))
     row["layout_counts"] = counts.cpu().tolist()
     row["blocks"] = blocks[:int(counts[0])].cpu().tolist()
-    for name, fn, iters in (("integral_otsu", lambda: table(-1), 50), ("integral_fixed", lambda: table(128), 50), ("layout_blocks", cut, 20),
-                            ("segment_otsu", seg, 50)):
-        t = windows(fn, iters)
-        row[name + "_ms"], row[name + "_ms_min"], row[name + "_ms_max"] = statistics.median(t), min(t), max(t)
+    time_rows(row, [("integral_otsu", lambda: table(-1), 50), ("integral_fixed", lambda: table(128), 50), ("layout_blocks", cut, 20),
+                    ("segment_otsu", seg, 50)])
     row["floor_ms"] = 5 * H * W / HBM_BYTES_PER_S * 1e3                       # one read of the page and one write of the table
     row["integral_fixed_over_floor"] = row["integral_fixed_ms"] / row["floor_ms"]
     row["integral_otsu_over_floor"] = row["integral_otsu_ms"] / row["floor_ms"]
     row["integral_otsu_over_segment"] = row["integral_otsu_ms"] / row["segment_otsu_ms"]
     row["layout_blocks_over_segment"] = row["layout_blocks_ms"] / row["segment_otsu_ms"]
-    line = json.dumps({k: (round(v, 5) if isinstance(v, float) else v) for k, v in row.items()})
-    print(line, flush=True)
-    with open(os.path.join(HERE, "..", "profiles", "layout_prof.json"), "w") as f:
-        f.write(line + "\n")
+    emit(row, "layout")
 
 
 if __name__ == "__main__":

@@ -6,9 +6,7 @@ times its calls; next to the byte floor at the HBM rate: 2 bytes per pixel for t
 `orient_prof.py --trace N` instead runs N quarter turns (q = 1) and nothing else, for
 `rocprofv3 --kernel-trace --stats -- python tools/orient_prof.py --trace 300`."""
 import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -16,7 +14,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from segment_prof import H, W, HBM_BYTES_PER_S, WINDOWS, a4_page, windows     # noqa: E402  (also puts the package on sys.path)
+from segment_prof import H, W, HBM_BYTES_PER_S, WINDOWS, a4_page, emit, time_rows     # noqa: E402  (also puts the package on sys.path)
 import aocr                                                                   # noqa: E402
 
 
@@ -50,10 +48,8 @@ def main():
         row[f"rotate_q{q}_matches_rot90"] = bool(np.array_equal(out.cpu().numpy().reshape(shape), np.rot90(page_h, -q)))
     estimate(-1)
     row["orient_words"] = words.cpu().tolist()
-    for name, fn, iters in (("rotate_q1", lambda: rotate(1), 50), ("rotate_q2", lambda: rotate(2), 50), ("rotate_q3", lambda: rotate(3), 50),
-                            ("estimate_fixed", lambda: estimate(128), 50), ("estimate_otsu", lambda: estimate(-1), 50), ("deskew", deskew, 50)):
-        t = windows(fn, iters)
-        row[name + "_ms"], row[name + "_ms_min"], row[name + "_ms_max"] = statistics.median(t), min(t), max(t)
+    time_rows(row, [("rotate_q1", lambda: rotate(1), 50), ("rotate_q2", lambda: rotate(2), 50), ("rotate_q3", lambda: rotate(3), 50),
+                    ("estimate_fixed", lambda: estimate(128), 50), ("estimate_otsu", lambda: estimate(-1), 50), ("deskew", deskew, 50)])
     row["rotate_floor_ms"] = 2 * H * W / HBM_BYTES_PER_S * 1e3                # one read and one write of the page
     row["estimate_floor_ms"] = H * W / HBM_BYTES_PER_S * 1e3                  # one read
     for q in (1, 2, 3):
@@ -62,10 +58,7 @@ def main():
     row["estimate_fixed_over_floor"] = row["estimate_fixed_ms"] / row["estimate_floor_ms"]
     row["estimate_otsu_over_floor"] = row["estimate_otsu_ms"] / row["estimate_floor_ms"]
     row["estimate_otsu_over_deskew"] = row["estimate_otsu_ms"] / row["deskew_ms"]
-    line = json.dumps({k: (round(v, 5) if isinstance(v, float) else v) for k, v in row.items()})
-    print(line, flush=True)
-    with open(os.path.join(HERE, "..", "profiles", "orient_prof.json"), "w") as f:
-        f.write(line + "\n")
+    emit(row, "orient")
 
 
 if __name__ == "__main__":

@@ -5,9 +5,7 @@ warm-up calls, then medians over windows, as tools/segment_prof.py times its cal
 image for the warp, the deskew and the rotation, and one read of the page for the quad (its scratch traffic is several times that).  No
 pass/fail gate.  Prints one JSON line and writes it to profiles/rectify_prof.json."""
 import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -15,7 +13,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from segment_prof import H, W, WINDOWS, a4_page, windows                      # noqa: E402  (also puts the package on sys.path)
+from segment_prof import H, W, WINDOWS, a4_page, emit, time_rows             # noqa: E402  (also puts the package on sys.path)
 import aocr                                                                   # noqa: E402
 
 QUAD = [150, 100, W - 200, 60, W - 80, H - 90, 60, H - 150]                   # TL, TR, BR, BL
@@ -61,10 +59,8 @@ def main():
     def rotate():
         aocr.check(aocr.lib.aocr_rotate_page(st, aocr.ptr(page), W, H, W, None, 1, aocr.ptr(out), H), "rotate")
 
-    for name, fn, iters in (("find_quad_otsu", lambda: find(-1), 20), ("find_quad_fixed", lambda: find(128), 20), ("warp", warp, 50),
-                            ("deskew", deskew, 50), ("rotate_q1", rotate, 50)):
-        t = windows(fn, iters)
-        row[name + "_ms"], row[name + "_ms_min"], row[name + "_ms_max"] = statistics.median(t), min(t), max(t)
+    time_rows(row, [("find_quad_otsu", lambda: find(-1), 20), ("find_quad_fixed", lambda: find(128), 20), ("warp", warp, 50),
+                    ("deskew", deskew, 50), ("rotate_q1", rotate, 50)])
     row["warp_gb_s"] = (H * W + Ho * Wo) / row["warp_ms"] * 1e-6
     row["deskew_gb_s"] = 2 * H * W / row["deskew_ms"] * 1e-6
     row["rotate_q1_gb_s"] = 2 * H * W / row["rotate_q1_ms"] * 1e-6
@@ -73,10 +69,7 @@ def main():
     row["warp_over_deskew"] = row["warp_ms"] / row["deskew_ms"]
     row["warp_ns_per_pixel"] = row["warp_ms"] * 1e6 / (Ho * Wo)
     row["find_quad_otsu_over_deskew"] = row["find_quad_otsu_ms"] / row["deskew_ms"]
-    line = json.dumps({k: (round(v, 5) if isinstance(v, float) else v) for k, v in row.items()})
-    print(line, flush=True)
-    with open(os.path.join(HERE, "..", "profiles", "rectify_prof.json"), "w") as f:
-        f.write(line + "\n")
+    emit(row, "rectify")
 
 
 if __name__ == "__main__":

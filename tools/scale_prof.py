@@ -5,16 +5,14 @@ over windows, as tools/segment_prof.py times its calls; GB/s counts the bytes ea
 the deskew, one read of the page for the estimate and the labelling (their scratch traffic is several times that).  No pass/fail gate.
 Prints one JSON line and writes it to profiles/scale_prof.json."""
 import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from segment_prof import H, W, WINDOWS, a4_page, windows                      # noqa: E402  (also puts the package on sys.path)
+from segment_prof import H, W, WINDOWS, a4_page, emit, time_rows             # noqa: E402  (also puts the package on sys.path)
 import aocr                                                                   # noqa: E402
 
 
@@ -50,10 +48,8 @@ def main():
     glyph()
     row["glyph_words"] = words.cpu().tolist()
     row["plan_native"] = aocr.scale_plan(row["glyph_words"][0], row["glyph_words"][3], H, W)
-    for name, fn, iters in (("resize_half", lambda: resize("half"), 50), ("resize_twice", lambda: resize("twice"), 50), ("glyph_otsu", glyph, 20),
-                            ("label_otsu", label, 20), ("deskew", deskew, 50)):
-        t = windows(fn, iters)
-        row[name + "_ms"], row[name + "_ms_min"], row[name + "_ms_max"] = statistics.median(t), min(t), max(t)
+    time_rows(row, [("resize_half", lambda: resize("half"), 50), ("resize_twice", lambda: resize("twice"), 50), ("glyph_otsu", glyph, 20),
+                    ("label_otsu", label, 20), ("deskew", deskew, 50)])
     for name in sizes:
         Wo, Ho = sizes[name]
         row[f"resize_{name}_gb_s"] = (H * W + Ho * Wo) / row[f"resize_{name}_ms"] * 1e-6
@@ -65,10 +61,7 @@ def main():
         row[f"resize_{name}_over_deskew"] = row[f"resize_{name}_ms"] / row["deskew_ms"]
         row[f"resize_{name}_per_byte_over_deskew"] = row["deskew_gb_s"] / row[f"resize_{name}_gb_s"]
     row["glyph_over_label"] = row["glyph_otsu_ms"] / row["label_otsu_ms"]
-    line = json.dumps({k: (round(v, 5) if isinstance(v, float) else v) for k, v in row.items()})
-    print(line, flush=True)
-    with open(os.path.join(HERE, "..", "profiles", "scale_prof.json"), "w") as f:
-        f.write(line + "\n")
+    emit(row, "scale")
 
 
 if __name__ == "__main__":

@@ -39,6 +39,21 @@ def windows(fn, iters):
     return out
 
 
+def time_rows(row, named_fns):
+    """row[name + "_ms"], "_ms_min" and "_ms_max": the median, least and greatest window of fn, for every (name, fn, iters), in that order."""
+    for name, fn, iters in named_fns:
+        t = windows(fn, iters)
+        row[name + "_ms"], row[name + "_ms_min"], row[name + "_ms_max"] = statistics.median(t), min(t), max(t)
+
+
+def emit(row, stage):
+    """the row as one JSON line, floats rounded to 5 places: printed, and written to profiles/<stage>_prof.json."""
+    line = json.dumps({k: (round(v, 5) if isinstance(v, float) else v) for k, v in row.items()})
+    print(line, flush=True)
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", stage + "_prof.json"), "w") as f:
+        f.write(line + "\n")
+
+
 def a4_page(seed=300):
     """lines of atlas words at 40..56 px pitch with 18..30 px between words, 150 px margins; glyphs at their atlas size (32 px high)."""
     atlas = aocr.GlyphAtlas.default()
@@ -94,9 +109,7 @@ def main():
             crop()
         torch.cuda.synchronize()
         return
-    for name, p in (("segment_otsu", otsu), ("segment_fixed", fixed)):
-        t = windows(lambda: seg(p), 50)
-        row[name + "_ms"], row[name + "_ms_min"], row[name + "_ms_max"] = statistics.median(t), min(t), max(t)
+    time_rows(row, [("segment_otsu", lambda: seg(otsu), 50), ("segment_fixed", lambda: seg(fixed), 50)])
     blank = torch.full((H, W), 255, dtype=torch.uint8, device=dev)
     t = windows(lambda: seg(fixed, blank), 50)                  # no ink: the row profile reads the page, every later kernel finds nothing to do
     row["segment_fixed_blank_page_ms"] = statistics.median(t)

@@ -6,16 +6,14 @@ profiles/skew_prof.json.
 `skew_prof.py --trace N` instead runs N estimate calls and N deskew calls and nothing else, for
 `rocprofv3 --kernel-trace --stats -- python tools/skew_prof.py --trace 300`."""
 import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from segment_prof import H, W, HBM_BYTES_PER_S, WINDOWS, a4_page, windows     # noqa: E402  (also puts the package on sys.path)
+from segment_prof import H, W, HBM_BYTES_PER_S, WINDOWS, a4_page, emit, time_rows     # noqa: E402  (also puts the package on sys.path)
 import aocr                                                                   # noqa: E402
 
 SLOPE = 1144                                   # atan(1144 / 65536) = 1.0 degree: 18 steps of the default sweep
@@ -64,17 +62,13 @@ def main():
     row["lines_deskewed"], row["boxes_deskewed"] = int(counts[1]), int(counts[0])
     seg(straight)
     row["lines_straight"], row["boxes_straight"] = int(counts[1]), int(counts[0])
-    for name, fn in (("estimate_otsu", lambda: est(otsu)), ("estimate_fixed", lambda: est(fixed)), ("deskew", desk), ("segment_otsu", lambda: seg(out))):
-        t = windows(fn, 50)
-        row[name + "_ms"], row[name + "_ms_min"], row[name + "_ms_max"] = statistics.median(t), min(t), max(t)
+    time_rows(row, [("estimate_otsu", lambda: est(otsu), 50), ("estimate_fixed", lambda: est(fixed), 50), ("deskew", desk, 50),
+                    ("segment_otsu", lambda: seg(out), 50)])
     row["read_floor_ms"] = H * W / HBM_BYTES_PER_S * 1e3                      # the estimate's floor: one read of the page
     row["deskew_floor_ms"] = 2 * H * W / HBM_BYTES_PER_S * 1e3                # one read and one write
     row["sweep_byte_adds"] = row["candidates"] * row["strips"] * H
     row["estimate_over_segment"] = row["estimate_otsu_ms"] / row["segment_otsu_ms"]
-    line = json.dumps({k: (round(v, 5) if isinstance(v, float) else v) for k, v in row.items()})
-    print(line, flush=True)
-    with open(os.path.join(HERE, "..", "profiles", "skew_prof.json"), "w") as f:
-        f.write(line + "\n")
+    emit(row, "skew")
 
 
 if __name__ == "__main__":

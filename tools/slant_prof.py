@@ -4,9 +4,7 @@ aocr_crop_lines, on the seeded A4 page of tools/segment_prof.py (3508 x 2480, ab
 segmentation's own, on the device.  HIP events, warm-up calls, then medians over windows, as tools/segment_prof.py times its calls.
 Prints one JSON line and writes it to profiles/slant_prof.json."""
 import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -14,7 +12,7 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from segment_prof import WINDOWS, a4_page, windows                            # noqa: E402  (also puts the package on sys.path)
+from segment_prof import WINDOWS, a4_page, emit, time_rows                    # noqa: E402  (also puts the package on sys.path)
 import aocr                                                                   # noqa: E402
 
 MAX_BOXES, OUT_H, OUT_W = 4096, 32, 100
@@ -61,15 +59,10 @@ def main():
     words = slant.cpu().numpy()
     row["slant_histogram"] = {int(k): int(v) for k, v in zip(*np.unique(words[:, 0], return_counts=True))}
     row["flags"] = [int((words[:, 2] == f).sum()) for f in range(3)]
-    for name, fn in (("segment_otsu", segment), ("estimate", estimate), ("crop", crop), ("crop_slanted", crop_slanted)):
-        t = windows(fn, 50)
-        row[name + "_ms"], row[name + "_ms_min"], row[name + "_ms_max"] = statistics.median(t), min(t), max(t)
+    time_rows(row, [("segment_otsu", segment, 50), ("estimate", estimate, 50), ("crop", crop, 50), ("crop_slanted", crop_slanted, 50)])
     row["estimate_over_segment"] = row["estimate_ms"] / row["segment_otsu_ms"]
     row["crop_slanted_over_crop"] = row["crop_slanted_ms"] / row["crop_ms"]
-    line = json.dumps({k: (round(v, 5) if isinstance(v, float) else v) for k, v in row.items()})
-    print(line, flush=True)
-    with open(os.path.join(HERE, "..", "profiles", "slant_prof.json"), "w") as f:
-        f.write(line + "\n")
+    emit(row, "slant")
 
 
 if __name__ == "__main__":
