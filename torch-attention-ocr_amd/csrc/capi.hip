@@ -6,7 +6,7 @@
 #include <functional>
 #include <new>
 #include <string>
-#include "model.h"
+#include "cnn.h"
 
 using namespace aocr;
 
@@ -55,22 +55,20 @@ int aocr_param_entry(const aocr_config* cfg, int32_t index, char name[64], int32
   for (int i = 0; i < 4; ++i) shape[i] = e.shape[i];
   return 0;
 }
-int64_t aocr_bn_state_count(void) { return 2 * (256 + 512 + 512); }
+int64_t aocr_bn_state_count(void) { return cnn_bn_state_floats(); }
 
 static void bind_params(aocr_model* m) {
   auto find = [&](const std::string& n) -> int64_t {
     for (auto& e : m->layout.e) if (e.name == n) return e.offset;
     return -1;
   };
-  static const int convs[7][4] = {{1, 64, 3, 1}, {64, 128, 3, 1}, {128, 256, 3, 1}, {256, 256, 3, 1},
-                                  {256, 512, 3, 1}, {512, 512, 3, 1}, {512, 512, 2, 0}};
   float* bnst = m->bn_state; int bi = 0;
-  for (int i = 1; i <= 7; ++i) {
+  for (int i = 1; i <= CNN_LAYERS; ++i) {
     char nm[64];
-    ConvP& c = m->conv[i]; c.cin = convs[i - 1][0]; c.cout = convs[i - 1][1]; c.ks = convs[i - 1][2]; c.pad = convs[i - 1][3];
+    ConvP& c = m->conv[i]; c.cin = CNN[i].cin; c.cout = CNN[i].cout; c.ks = CNN[i].ks; c.pad = CNN[i].pad;
     snprintf(nm, 64, "cnn.conv%d.w", i); int64_t o = find(nm); c.w = m->params + o; c.dw = m->grads + o;
     snprintf(nm, 64, "cnn.conv%d.b", i); o = find(nm); c.b = m->params + o; c.db = m->grads + o;
-    if (i == 3 || i == 5 || i == 7) {
+    if (CNN[i].bn) {
       BnP& b = m->bn[i]; b.C = c.cout;
       snprintf(nm, 64, "cnn.bn%d.w", i); o = find(nm); b.w = m->params + o; b.dw = m->grads + o;
       snprintf(nm, 64, "cnn.bn%d.b", i); o = find(nm); b.b = m->params + o; b.db = m->grads + o;
@@ -283,15 +281,11 @@ int aocr_train_forward_backward(aocr_model* m, const float* images_dev, const in
   return check_launch("aocr_train_forward_backward");
 }
 
-static int64_t conv5_offset(const Layout& l) {
-  for (const ParamEntry& e : l.e) if (e.name == "cnn.conv5.w") return e.offset;
-  return 0;
-}
 int aocr_grad_buckets(const aocr_config* cfg, int64_t begin[AOCR_GRAD_BUCKETS], int64_t end[AOCR_GRAD_BUCKETS]) {
   if (check_cfg(cfg)) return 1;
   REQUIRE(begin && end, "NULL argument");
   const Layout l = build_layout(*cfg);
-  const int64_t c5 = conv5_offset(l);
+  const int64_t c5 = cnn_conv5_offset();
   begin[0] = l.group_off[3]; end[0] = l.group_off[AOCR_NUM_GROUPS];       // decoder + projector
   begin[1] = l.group_off[1]; end[1] = l.group_off[3];                     // both encoder directions
   begin[2] = c5;             end[2] = l.group_off[1];                     // CNN from conv5 upwards
@@ -421,6 +415,10 @@ int aocr_get_tensor(aocr_model* m, const char* name, const void** ptr_dev, int32
   REQUIRE(m->last_valid, "no step has run yet");
   const Dims& d = m->last; std::string n = name;
   for (int i = 0; i < 4; ++i) shape[i] = 1;
+  CnnStage S[CNN_LAYERS + 1]; cnn_stages(m, d, S);
+  const int li = n.empty() ? 0 : n.back() - '0';          // "conv<li>" / "idx<li>"
+  const bool tap_conv = n.size() == 5 && n.compare(0, 4, "conv") == 0 && li >= 1 && li < CNN_LAYERS;
+  const bool tap_idx = n.size() == 4 && n.compare(0, 3, "idx") == 0 && li >= 2 && li < CNN_LAYERS && CNN[li].pool;
   if (n == "feats") { *ptr_dev = m->X; *ndim = 3; shape[0] = d.T; shape[1] = d.B; shape[2] = 512; }
   else if (n == "dfeats") { *ptr_dev = m->dX; *ndim = 3; shape[0] = d.T; shape[1] = d.B; shape[2] = 512; }
   else if (n == "context") { *ptr_dev = m->context; *ndim = 3; shape[0] = d.B; shape[1] = d.T; shape[2] = m->Hd; }
@@ -429,16 +427,13 @@ int aocr_get_tensor(aocr_model* m, const char* name, const void** ptr_dev, int32
   else if (n == "dlogits") { *ptr_dev = m->dlogits; *ndim = 3; shape[0] = d.L; shape[1] = d.B; shape[2] = LOGIT_LD; }      // (after a training step)
   else if (n == "dout_proj") { *ptr_dev = m->dout_proj; *ndim = 3; shape[0] = d.L; shape[1] = d.B; shape[2] = m->Hd; }
   else if (n == "outs") { *ptr_dev = m->out_all + (size_t)d.B * m->Hd; *ndim = 3; shape[0] = d.L; shape[1] = d.B; shape[2] = m->Hd; }
-  else if (n == "conv1") { if (m->bf16) bf16_to_f32(m->s, m->A1b, m->A1, (int64_t)d.B * d.H1 * d.W1 * 64); *ptr_dev = m->A1; *ndim = 4; shape[0] = d.B; shape[1] = d.H1; shape[2] = d.W1; shape[3] = 64; }
-  else if (n == "conv2") { if (m->bf16) bf16_to_f32(m->s, m->A2b, m->A2, (int64_t)d.B * d.H2 * d.W2 * 128); *ptr_dev = m->A2; *ndim = 4; shape[0] = d.B; shape[1] = d.H2; shape[2] = d.W2; shape[3] = 128; }
-  else if (n == "conv6") { if (m->bf16) bf16_to_f32(m->s, m->A6b, m->A6, (int64_t)d.B * d.H6 * d.W2 * 512); *ptr_dev = m->A6; *ndim = 4; shape[0] = d.B; shape[1] = d.H6; shape[2] = d.W2; shape[3] = 512; }
-  // parity aids: the ReLU / max-pool DECISIONS of the forward pass (tests impose them on the fp64 oracle: tests/test_step_gpu.py)
-  else if (n == "conv3") { if (m->bf16) bf16_to_f32(m->s, m->A3b, m->A3, (int64_t)d.B * d.H2 * d.W2 * 256); *ptr_dev = m->A3; *ndim = 4; shape[0] = d.B; shape[1] = d.H2; shape[2] = d.W2; shape[3] = 256; }
-  else if (n == "conv4") { if (m->bf16) bf16_to_f32(m->s, m->A4b, m->A4, (int64_t)d.B * d.H4 * d.W2 * 256); *ptr_dev = m->A4; *ndim = 4; shape[0] = d.B; shape[1] = d.H4; shape[2] = d.W2; shape[3] = 256; }
-  else if (n == "conv5") { if (m->bf16) bf16_to_f32(m->s, m->A5b, m->A5, (int64_t)d.B * d.H4 * d.W2 * 512); *ptr_dev = m->A5; *ndim = 4; shape[0] = d.B; shape[1] = d.H4; shape[2] = d.W2; shape[3] = 512; }
-  else if (n == "idx2") { u8_to_f32(m->s, m->idx2, m->G0, (int64_t)d.B * d.H2 * d.W2 * 128); *ptr_dev = m->G0; *ndim = 4; shape[0] = d.B; shape[1] = d.H2; shape[2] = d.W2; shape[3] = 128; }
-  else if (n == "idx4") { u8_to_f32(m->s, m->idx4, m->G0, (int64_t)d.B * d.H4 * d.W2 * 256); *ptr_dev = m->G0; *ndim = 4; shape[0] = d.B; shape[1] = d.H4; shape[2] = d.W2; shape[3] = 256; }
-  else if (n == "idx6") { u8_to_f32(m->s, m->idx6, m->G0, (int64_t)d.B * d.H6 * d.W2 * 512); *ptr_dev = m->G0; *ndim = 4; shape[0] = d.B; shape[1] = d.H6; shape[2] = d.W2; shape[3] = 512; }
+  else if (tap_conv) {                                    // conv1 .. conv6: the map layer li hands to layer li + 1 (bf16 mode: materialised from its shadow)
+    const CnnStage& up = S[li + 1];
+    if (m->bf16) bf16_to_f32(m->s, up.xb, up.x, (int64_t)cnn_map_elems(d, li));
+    *ptr_dev = up.x; *ndim = 4; shape[0] = d.B; shape[1] = up.H; shape[2] = up.W; shape[3] = CNN[li].cout;
+  }
+  // parity aids: the max-pool DECISIONS of the forward pass (tests impose them on the fp64 oracle: tests/test_step_gpu.py)
+  else if (tap_idx) { const CnnStage& st = S[li]; u8_to_f32(m->s, st.idx, m->G0, (int64_t)cnn_map_elems(d, li)); *ptr_dev = m->G0; *ndim = 4; shape[0] = d.B; shape[1] = st.Ho; shape[2] = st.Wo; shape[3] = CNN[li].cout; }
   else if (n == "enc_dz0" || n == "enc_dz1") {           // debugging aid: bf16 d z of the top encoder layer, direction 0 / 1
     const int dir = n == "enc_dz1"; const int64_t cnt = (int64_t)d.T * d.B * 4 * m->He;
     REQUIRE(m->edz_b[dir][m->Le - 1], "no bf16 d z in this mode");
@@ -480,12 +475,15 @@ int aocr_profile_kernel(aocr_model* m, int32_t which, int32_t iters, float* ms_p
   REQUIRE((which != AOCR_PK_BN_FWD && which != AOCR_PK_BN_BWD && which != AOCR_PK_UNPOOL) || (n5 % 256 == 0 && n5 / 256 <= 512), "kernel id %d replays conv5's BatchNorm with the epilogue's 256-pixel statistics chunks: %lld pixels are not a multiple of 256 / more than 512 chunks", which, (long long)n5);
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   hipStream_t s = m->s; const int B = d.B;
-  constexpr size_t SLAB = (size_t)4 << 20;
+  CnnStage S[CNN_LAYERS + 1]; cnn_stages(m, d, S);         // the step's own view and launch functions (cnn.h): a replay is the launch the step makes, partial-sum slabs (cnn_slab) included
   double bytes = 0.0;
   // bf16 data-gradient maps (conv_backward_data's dx16, round 4): what the step's BatchNorm backward / un-pool passes read when the switch is on
   // G1 as those two replays find it: conv6's data gradient in front of conv5's BatchNorm backward, conv7's in front of conv6's un-pool (cnn_backward's calls)
   const bool dx16 = which == AOCR_PK_BN_BWD ? conv_dgrad_bf16_out(B, d.H4, d.W2, 512, 512, 3, 1) : which == AOCR_PK_UNPOOL ? conv_dgrad_bf16_out(B, d.H6, d.W2, 512, 512, 2, 0) : false;
-  const bf16_t* const g1h = dx16 ? reinterpret_cast<const bf16_t*>(m->G1) : nullptr;
+  S[5].dA16 = S[6].dA16 = dx16;
+  // bn_scratch is shared by every BatchNorm of the step, forward and backward: conv5's statistics are put back by the step's own hand-over (untimed)
+  if (which == AOCR_PK_BN_FWD) cnn_conv_fwd(m, S[5], 1, false);
+  int y16 = 0; if (which == 0) S[3].y16 = S[5].y16 = &y16;   // the replay of a training conv forward leaves its flag here: m->y16[] stays as the step left it
   const double dab = dx16 ? 2.0 : 4.0;                    // bytes per element of d A / d(pooled)
   // ids >= 2: the bandwidth-bound kernels, each replayed on the buffers the last TRAINING step left, with the arguments cnn_forward /
   // cnn_backward / decoder_backward pass (bf16 mode).  Outputs land where the step puts them (activations, gradient maps, gradient
@@ -493,38 +491,33 @@ int aocr_profile_kernel(aocr_model* m, int32_t which, int32_t iters, float* ms_p
   auto run = [&]() {
     switch (which) {
     case 0:
-      if (const char* const pl = knob::AOCR_PROBE_LAYER()) {   // debugging aid (tools/debug/conv_probe.py): the tagged launch of conv3 / conv4 / conv5 forward instead, as cnn_forward makes it
-        int bnc = 0, y16 = 0; const int l = atoi(pl);
-        if (l == 3) { conv_forward(m->s, m->bf16, m->A2, m->conv[3].w, m->conv[3].b, m->Y3, nullptr, d.B, d.H2, d.W2, 128, 256, 3, 1, 0, 0, m->A2b, m->wb[3], nullptr, 1, nullptr, nullptr, nullptr, (double*)m->bn_scratch, &bnc, &y16); break; }
-        if (l == 4) { conv_forward(m->s, m->bf16, m->A3, m->conv[4].w, m->conv[4].b, nullptr, m->idx4, d.B, d.H2, d.W2, 256, 256, 3, 1, 1, 2, m->A3b, m->wb[4], m->A4b, 1); break; }
-        if (l == 5) { conv_forward(m->s, m->bf16, m->A4, m->conv[5].w, m->conv[5].b, m->Y5, nullptr, d.B, d.H4, d.W2, 256, 512, 3, 1, 0, 0, m->A4b, m->wb[5], nullptr, 1, nullptr, nullptr, nullptr, (double*)m->bn_scratch, &bnc, &y16); break; }
+      {
+        const char* const pl = knob::AOCR_PROBE_LAYER();  // debugging aid (tools/debug/conv_probe.py): the tagged launch of conv3 / conv4 / conv5 forward instead, as cnn_forward makes it in training
+        const int l = pl ? atoi(pl) : 0;
+        cnn_conv_fwd(m, S[l >= 3 && l <= 5 ? l : 6], 1, false, 1);      // distinct symbol: TAG = 1
       }
-      conv_forward(m->s, m->bf16, m->A5, m->conv[6].w, m->conv[6].b, m->bf16 ? nullptr : m->A6, m->idx6, d.B, d.H4, d.W2, 512, 512, 3, 1, 1, 2, m->A5b, m->wb[6],
-                   m->A6b, 1);                              // exactly the launch cnn_forward makes for conv6 (distinct symbol: TAG = 1)
       break;
     case 1:                                                 // conv6 filter gradient as backward_all launches it (split-K slabs + their sum), summed into scratch
-      conv_backward_filter(m->s, m->bf16, m->A5, m->G0, m->G1, nullptr, d.B, d.H4, d.W2, 512, 512, 3, 1, m->A5b, m->G0b, m->wg_part, m->wg_part_floats, 1);
+      cnn_wgrad(m, S[6], s, m->G0b, 1, m->G1);
       break;
     case AOCR_PK_CONV1_FWD:                                 // R1 + R2: reads the image (fp32), writes the pooled 64-channel map as bf16
-      conv1_forward(s, m->last_images, m->conv[1].w, m->conv[1].b, nullptr, B, d.H, d.W, m->A1b, m->route1_valid ? m->route1 : nullptr);
+      cnn_conv1_fwd(m, m->last_images, d, m->route1_valid);
       bytes = (double)B * d.H * d.W * 4 + (double)B * d.H1 * d.W1 * 64 * 2 + (m->route1_valid ? (double)conv1_route_elems(B, d.H, d.W) * 2 : 0.0);
       break;
     case AOCR_PK_CONV1_BWD:                                 // reads the image and d(pooled map) (fp32, conv2's data gradient); writes 640 numbers
-      conv1_backward(s, m->last_images, m->conv[1].w, m->conv[1].b, m->G1, m->conv[1].dw, m->conv[1].db, B, d.H, d.W,
-                     (size_t)B * d.H1 * d.W1 * 128 >= (size_t)4096 * 640 ? m->G0 + 6 * SLAB : nullptr, nullptr, m->route1_valid ? m->route1 : nullptr);
+      cnn_conv1_bwd(m, m->last_images, d, nullptr);
       bytes = (double)B * d.H * d.W * 4 + (double)B * d.H1 * d.W1 * 64 * 4 + (m->route1_valid ? (double)conv1_route_elems(B, d.H, d.W) * 2 : 0.0);
       break;
     case AOCR_PK_BN_FWD:                                    // conv5's BatchNorm + ReLU as the step runs it: statistics from the conv epilogue -> finalize + ONE pass: fp32 y in, bf16 out
-      bn_relu_forward(s, m->Y5, nullptr, m->bn[5].w, m->bn[5].b, m->bn[5].rm, m->bn[5].rv, m->bn[5].save, m->bn_scratch, n5, 512, 1, 0, 0, m->A5b, nullptr, (int)(n5 / 256));
+      cnn_bn_fwd(m, S[5], 1, 0, nullptr);
       bytes = (double)n5 * 512 * (4 + 2);
       break;
     case AOCR_PK_BN_BWD:                                    // conv5's BatchNorm backward: sums pass (x fp32, d A fp32, mask bf16) + apply pass (the same + bf16 d x out)
-      bn_relu_backward(s, m->Y5, m->A5, m->G1, m->bn[5].w, m->bn[5].save, nullptr, m->bn[5].dw, m->bn[5].db, m->bn_scratch, n5, 512, 0, m->G0b, m->A5b,
-                       m->conv[5].db, m->G0 + 2 * SLAB, nullptr, nullptr, nullptr, g1h);
+      cnn_elem_bwd(m, S[5], m->G0b, nullptr, nullptr);
       bytes = (double)n5 * 512 * ((4 + dab + 2) + (4 + dab + 2 + 2));
       break;
     case AOCR_PK_UNPOOL:                                    // (2,1) un-pool + ReLU backward of conv6: d(pooled) fp32 + arg-max (1 B) + pooled mask (bf16) in, bf16 gradient of the un-pooled map out
-      unpool_relu_backward(s, m->G1, m->A6, m->idx6, nullptr, B, d.H4, d.W2, 512, 2, m->G0b, m->conv[6].db, m->G0 + 1 * SLAB, m->A6b, nullptr, g1h);
+      cnn_elem_bwd(m, S[6], m->G0b, nullptr, nullptr);
       bytes = (double)B * d.H6 * d.W2 * 512 * (dab + 1 + 2) + (double)n5 * 512 * 2;
       break;
     case AOCR_PK_ATTN_DCTX:                                 // d(context) of all L steps in one pass (model.lua:652-653): a, d s (L,B,T), d c, q (L,B,Hd) in; (B,T,Hd) fp32 out

@@ -1,4 +1,4 @@
-// model.h -- the aocr_model handle: parameter views, workspace carve-up and the fused step drivers.
+// model.h -- the aocr_model handle: parameter views, workspace carve-up and the fused step drivers (the CNN's: cnn.h).
 #pragma once
 #include <string>
 #include <vector>
@@ -61,20 +61,21 @@ struct aocr_model {
 
   // ---- workspace
   size_t ws_bytes;
-  // CNN
-  float *A1, *A2, *Y3, *A3, *A4, *Y5, *A5, *A6, *Y7, *X;
-  uint8_t *idx2, *idx4, *idx6;
+  // CNN, by layer number (cnn.h: the layer table): A = output map after ReLU / pooling / BatchNorm (1..6; layer 7's is X, time-major), Y = the conv's
+  // own output in front of a BatchNorm (3, 5, 7), idx = arg-max of the pool (2, 4, 6)
+  float *A[8], *Y[8], *X;
+  uint8_t* idx[8];
   uint16_t* route1 = nullptr; bool route1_valid = false;       // conv1's pooling/ReLU decisions of the last training forward (conv1_forward's route)
   float *G0, *G1, *dX; size_t gmax = 0;   // gmax: floats in G0 / G1
   // bf16 shadows of the contraction operands (bf16 compute mode only; nullptr otherwise)
-  aocr::bf16_t *A1b, *A2b, *A3b, *A4b, *A5b, *A6b, *G0b, *G2b = nullptr;
+  aocr::bf16_t *Ab[8], *G0b, *G2b = nullptr;
   hipEvent_t cw_map[2] = {nullptr, nullptr}, cw_done[2] = {nullptr, nullptr}, cw_main = nullptr;   // cnn_backward: gradient map ready / filter gradient done per map buffer
   aocr::bf16_t *wb[8], *wtb[8];
   float* wtf[8];                  // fp32 mode: conv taps re-laid as [Cin][tap][Cout] (K-contiguous B operand of the data gradient)
   // bf16 shadows of the recurrent activations / gradients (written by the producing epilogues)
   aocr::bf16_t *Xb, *ehs_b[2][aocr::MAXL], *edz_b[2][aocr::MAXL], *dhs_b[aocr::MAXL], *ddz_b[aocr::MAXL], *out_b, *cat_b, *dpre_b, *dq_b;
   void* bn_scratch; float* bn_save;
-  int y16[2] = {0, 0};            // the last forward pass left Y3 / Y5 (pre-BatchNorm maps) as bf16 in the first half of their buffers (conv_forward: y_bf16)
+  int y16[8] = {};                // [3], [5]: the last forward pass left Y3 / Y5 (pre-BatchNorm maps) as bf16 in the first half of their buffers (conv_forward: y_bf16)
   // encoder [dir][layer]
   float *ezx[2][aocr::MAXL], *ehs[2][aocr::MAXL], *ecs[2][aocr::MAXL], *egates[2][aocr::MAXL], *edz[2][aocr::MAXL], *edc[2][aocr::MAXL];
   float *edxl[2];
@@ -114,7 +115,6 @@ struct aocr_model {
   hipStream_t lay_s[aocr::MAXL] = {}; std::vector<hipEvent_t> lay_ev;
   hipStream_t side2 = nullptr; hipEvent_t side2_done = nullptr;   // second side stream (bias sums, projector gradWeight), joined into `side`
   hipStream_t side = nullptr; hipEvent_t side_go = nullptr, side_done = nullptr; bool side_busy = false;   // side stream of the backward pass (model.hip: decoder_backward)
-  int64_t conv5_off;              // offset of cnn.conv5.w in the flat vectors: the CNN group is split there
   aocr::Dims last;                // dims of the last step (for the parity taps)
   int last_valid;
   const float* last_images = nullptr; bool last_train = false;   // the caller's image buffer of the last aocr_train_forward_backward (aocr_profile_kernel replays conv1 on it)
@@ -151,7 +151,7 @@ inline void prof_mark(aocr_model* m, int tag) { if (m->prof_on) prof_mark_slow(m
 void step_prologue(aocr_model* m, size_t grad_bytes);              // start of a training step (capi.hip): gradient zeroing, weight shadows, token table
 void build_shadow_jobs(aocr_model* m);                              // after bind_params + model_carve
 int model_carve(aocr_model* m, void* base, size_t bytes);          // returns 0 / -1 (too small); base==nullptr: size only
-void cnn_forward(aocr_model* m, const float* images, const Dims& d, int training, int update_running);
+void refresh_rnn_shadows(aocr_model* m, hipStream_t st = nullptr);   // the recurrent matrices' shadows, one launch each (cnn_forward, when there is no job table)
 void encoder_forward(aocr_model* m, const Dims& d);
 void decoder_tf_forward(aocr_model* m, const Dims& d, const int32_t* tgt, int64_t st, int64_t sb, bool keep_gates);
 void loss_and_dlogits(aocr_model* m, const Dims& d, const int32_t* tge, int64_t st, int64_t sb, float grad_scale, bool want_grad,

@@ -2,7 +2,7 @@
 // as straight-line kernel launches on one HIP stream with a native time loop in place of the reference's
 // cloned cells (model_utils.lua:3-50).  Weight gradients of every recurrent Linear are hoisted out of the
 // time loops into one large-K contraction each; the loops keep only what is truly sequential.
-#include "model.h"
+#include "cnn.h"
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -22,16 +22,14 @@ static void add_entry(Layout& L, int64_t& off, const std::string& name, int grou
 Layout build_layout(const aocr_config& c) {
   Layout L; int64_t off = 0;
   const int He = c.enc_hidden, Hd = 2 * He;
-  static const int convs[7][4] = {{1, 64, 3, 1}, {64, 128, 3, 1}, {128, 256, 3, 1}, {256, 256, 3, 1},
-                                  {256, 512, 3, 1}, {512, 512, 3, 1}, {512, 512, 2, 0}};
   L.group_off[0] = 0;
-  for (int i = 0; i < 7; ++i) {                                            // cnn.lua:12-42
-    char nm[64];
-    snprintf(nm, 64, "cnn.conv%d.w", i + 1); add_entry(L, off, nm, 0, {convs[i][1], convs[i][2], convs[i][2], convs[i][0]});
-    snprintf(nm, 64, "cnn.conv%d.b", i + 1); add_entry(L, off, nm, 0, {convs[i][1]});
-    if (i == 2 || i == 4 || i == 6) {
-      snprintf(nm, 64, "cnn.bn%d.w", i + 1); add_entry(L, off, nm, 0, {convs[i][1]});
-      snprintf(nm, 64, "cnn.bn%d.b", i + 1); add_entry(L, off, nm, 0, {convs[i][1]});
+  for (int i = 1; i <= CNN_LAYERS; ++i) {                                  // cnn.lua:12-42
+    char nm[64]; const CnnLayer& c = CNN[i];
+    snprintf(nm, 64, "cnn.conv%d.w", i); add_entry(L, off, nm, 0, {c.cout, c.ks, c.ks, c.cin});
+    snprintf(nm, 64, "cnn.conv%d.b", i); add_entry(L, off, nm, 0, {c.cout});
+    if (c.bn) {
+      snprintf(nm, 64, "cnn.bn%d.w", i); add_entry(L, off, nm, 0, {c.cout});
+      snprintf(nm, 64, "cnn.bn%d.b", i); add_entry(L, off, nm, 0, {c.cout});
     }
   }
   L.group_off[1] = off;
@@ -85,29 +83,22 @@ int model_carve(aocr_model* m, void* base, size_t bytes) {
   Arena a; a.base = (char*)base; a.off = 0;
   const size_t B = d.B, T = d.T, L = d.L, He = m->He, Hd = m->Hd, E = m->E;
   const size_t R = B * (size_t)(c.max_beam > 1 ? c.max_beam : 1);
-  m->A1 = a.get<float>(B * d.H1 * d.W1 * 64);
-  m->A2 = a.get<float>(B * d.H2 * d.W2 * 128); m->idx2 = a.get<uint8_t>(B * d.H2 * d.W2 * 128);
-  m->Y3 = a.get<float>(B * d.H2 * d.W2 * 256); m->A3 = a.get<float>(B * d.H2 * d.W2 * 256);
-  m->A4 = a.get<float>(B * d.H4 * d.W2 * 256); m->idx4 = a.get<uint8_t>(B * d.H4 * d.W2 * 256);
-  m->Y5 = a.get<float>(B * d.H4 * d.W2 * 512); m->A5 = a.get<float>(B * d.H4 * d.W2 * 512);
-  m->A6 = a.get<float>(B * d.H6 * d.W2 * 512); m->idx6 = a.get<uint8_t>(B * d.H6 * d.W2 * 512);
-  m->Y7 = a.get<float>(B * T * 512); m->X = a.get<float>(T * B * 512); m->dX = a.get<float>(T * B * 512);
-  size_t gmax = B * d.H1 * d.W1 * 128;                                      // d(conv2 pre-pool output): the largest gradient map
-  m->G0 = a.get<float>(gmax); m->G1 = a.get<float>(gmax); m->gmax = gmax;
-  m->A1b = m->A2b = m->A3b = m->A4b = m->A5b = m->A6b = m->G0b = m->G2b = nullptr;
-  m->route1 = a.get<uint16_t>(conv1_route_elems((int)B, d.H, d.W)); m->route1_valid = false;
-  for (int i = 0; i < 8; ++i) { m->wb[i] = nullptr; m->wtb[i] = nullptr; m->wtf[i] = nullptr; }
-  if (!m->bf16) {
-    static const int wsz32[8] = {0, 0, 128 * 9 * 64, 256 * 9 * 128, 256 * 9 * 256, 512 * 9 * 256, 512 * 9 * 512, 512 * 4 * 512};
-    for (int i = 2; i <= 7; ++i) m->wtf[i] = a.get<float>(wsz32[i]);
+  for (int i = 0; i < 8; ++i) { m->A[i] = m->Y[i] = nullptr; m->idx[i] = nullptr; m->Ab[i] = nullptr; m->wb[i] = nullptr; m->wtb[i] = nullptr; m->wtf[i] = nullptr; }
+  for (int i = 1; i <= CNN_LAYERS; ++i) {                                   // A1; A2, idx2; Y3, A3; A4, idx4; Y5, A5; A6, idx6; Y7
+    if (CNN[i].bn) m->Y[i] = a.get<float>(cnn_map_elems(d, i));
+    if (i < CNN_LAYERS) m->A[i] = a.get<float>(cnn_map_elems(d, i));
+    if (CNN[i].pool && i > 1) m->idx[i] = a.get<uint8_t>(cnn_map_elems(d, i));
   }
+  m->X = a.get<float>(T * B * 512); m->dX = a.get<float>(T * B * 512);
+  const size_t gmax = cnn_gmax(d);
+  m->G0 = a.get<float>(gmax); m->G1 = a.get<float>(gmax); m->gmax = gmax;
+  m->G0b = m->G2b = nullptr;
+  m->route1 = a.get<uint16_t>(conv1_route_elems((int)B, d.H, d.W)); m->route1_valid = false;
+  if (!m->bf16) for (int i = 2; i <= CNN_LAYERS; ++i) m->wtf[i] = a.get<float>(cnn_weight_floats(i));
   if (m->bf16) {
-    m->A1b = a.get<bf16_t>(B * d.H1 * d.W1 * 64); m->A2b = a.get<bf16_t>(B * d.H2 * d.W2 * 128);
-    m->A3b = a.get<bf16_t>(B * d.H2 * d.W2 * 256); m->A4b = a.get<bf16_t>(B * d.H4 * d.W2 * 256);
-    m->A5b = a.get<bf16_t>(B * d.H4 * d.W2 * 512); m->A6b = a.get<bf16_t>(B * d.H6 * d.W2 * 512);
+    for (int i = 1; i < CNN_LAYERS; ++i) m->Ab[i] = a.get<bf16_t>(cnn_map_elems(d, i));
     m->G0b = a.get<bf16_t>(gmax); m->G2b = a.get<bf16_t>(gmax);      // G2b: second gradient-map shadow (cnn_backward: filter gradients on the side stream)
-    static const int wsz[8] = {0, 0, 128 * 9 * 64, 256 * 9 * 128, 256 * 9 * 256, 512 * 9 * 256, 512 * 9 * 512, 512 * 4 * 512};
-    for (int i = 2; i <= 7; ++i) { m->wb[i] = a.get<bf16_t>(wsz[i]); m->wtb[i] = a.get<bf16_t>(wsz[i]); }
+    for (int i = 2; i <= CNN_LAYERS; ++i) { m->wb[i] = a.get<bf16_t>(cnn_weight_floats(i)); m->wtb[i] = a.get<bf16_t>(cnn_weight_floats(i)); }
   }
   {                                                            // bf16 shadows of the recurrent weights (bf16 mode)
     auto sh = [&](ShW& w, size_t R_, size_t C_) {
@@ -176,7 +167,7 @@ int model_carve(aocr_model* m, void* base, size_t bytes) {
     m->cl_tbytes = ((size_t)m->Le * 4 * ((B + 15) / 16) * 8 + 64) * 8;    // a layer's 8-row launches start at slot l * 4 * ceil(B / 16) (enc_cluster_forward: gslot * 2) and use 2 * ceil(B / 8) <= 4 * ceil(B / 16) of them
     m->cl_xtab = a.get<unsigned long long>(m->cl_tbytes / 8);      // XCC ids of the members of every group
     m->cl_err = a.get<int>(16 + 256 * 8 + 4096);                 // error flag + the trash slots rows >= B store to + a debugging timeline
-    m->bn_snap = a.get<float>(2 * (256 + 512 + 512));            // aocr_bn_state_count() floats
+    m->bn_snap = a.get<float>(cnn_bn_state_floats());             // aocr_bn_state_count() floats
     if (Hd == 1024) m->ctxa_b = a.get<bf16_t>(B * T * Hd);        // the launch chain scores attention against ctx W_a too (round 6: attn_bf16_kernel<..., DUAL>, taken at T <= 64)
     if (Hd == 512 && m->Ld == 2 && m->cfg.input_feed) {          // the decoder loop as one launch (dec_cluster.hip)
       m->dc_xbytes = dec_cluster_xbuf_bytes((int)B); m->dc_tbytes = dec_cluster_xtab_bytes((int)std::max<size_t>(B, 32 * (size_t)dec_chain_beam_group_cap()));      // (beam search on the chain kernel indexes by the group within a launch: up to one group per XCD)
@@ -222,7 +213,7 @@ void build_shadow_jobs(aocr_model* m) {
   for (int i = 3; i <= 7; ++i) conv_jobs(i);
   if (m->shadow_host.size() > 128) { m->shadow_host.clear(); m->shadow_tiles = 0; m->shadow_tiles_conv2 = 0; }      // table too small: per-matrix launches
 }
-static void refresh_rnn_shadows(aocr_model* m, hipStream_t st = nullptr) {
+void refresh_rnn_shadows(aocr_model* m, hipStream_t st) {
   if (!st) st = m->s;
   auto up = [&](const ShW& w) {
     if (w.wb) weight_shadows(st, w.w, w.ld, w.R, w.C, w.wb, w.wtb);
@@ -319,142 +310,6 @@ static void run_gates_bwd(aocr_model* m, int nz, const LoadK* a, const ShW* cons
     for (int i = 0; i < nz; ++i) { z[i].a = a[i]; z[i].b = make_loadmn(w[i]->w, w[i]->ld, w[i]->C, a[i].K); z[i].ep = ep[i]; z[i].K = a[i].K; }
     launch_small_gates_bwd(m->s, false, nz, z, M, H);
   }
-}
-
-// ------------------------------------------------------------------------------------------------
-// CNN forward, cnn.lua:9-45.  Output X is time-major (T,B,512) (= cnn_output:transpose(1,2), model.lua:288).
-// ------------------------------------------------------------------------------------------------
-static int bn_sync_allreduce(void* ctx, void* buf, int64_t count, int dtype, hipStream_t s) { return comm_allreduce((aocr_model*)ctx, buf, count, dtype, s, 1); }
-
-void cnn_forward(aocr_model* m, const float* images, const Dims& d, int training, int update_running) {
-  hipStream_t s = m->s; const bool bf = m->bf16; const int B = d.B;
-  m->y16[0] = m->y16[1] = 0;                                     // only a training conv_forward below sets them again: the evaluation / folded branch leaves Y3 / Y5 untouched, never "bf16 from an older step"
-  const BnSync bsync_v{bn_sync_allreduce, m}; const BnSync* bsync = (training && sync_bn_on(m)) ? &bsync_v : nullptr;
-  if (bf && !m->shadow_host.empty()) {                          // every bf16 shadow of the step in one launch
-    if (!m->shadow_pending) shadow_jobs(s, m->shadow_dev, (int)m->shadow_host.size(), m->shadow_tiles);      // (pending: step_prologue put it on the side stream)
-  } else {
-    refresh_rnn_shadows(m);
-    for (int i = 2; i <= 7; ++i) {                              // refresh the re-laid weight copies (weights change every step)
-      if (bf) conv_weight_shadows(s, m->conv[i].w, m->wb[i], m->wtb[i], m->conv[i].cout, m->conv[i].ks * m->conv[i].ks, m->conv[i].cin);
-      else conv_weight_transpose_f32(s, m->conv[i].w, m->wtf[i], m->conv[i].cout, m->conv[i].ks * m->conv[i].ks, m->conv[i].cin);
-    }
-  }
-  // bf16 mode: the pooled conv outputs exist only as bf16 shadows (every consumer -- next conv, filter gradient, ReLU mask of the
-  // un-pool -- reads the shadow; aocr_get_tensor materialises fp32 on demand)
-  prof_mark(m, AOCR_PROF_POOL_CONV1); conv1_forward(s, images, m->conv[1].w, m->conv[1].b, bf ? nullptr : m->A1, B, d.H, d.W, m->A1b, training ? m->route1 : nullptr);
-  m->route1_valid = training;                                   // conv1_backward takes the pooling/ReLU decisions from here instead of re-evaluating the layer
-  if (m->shadow_pending && m->shadow2_pending) { hipStreamWaitEvent(s, m->shadow2_done, 0); m->shadow2_pending = false; }       // conv1 reads no shadow; conv2 reads its own taps (the first part of the table)
-  else if (m->shadow_pending) { hipStreamWaitEvent(s, m->shadow_done, 0); m->shadow_pending = false; }
-  prof_mark(m, AOCR_PROF_CONV_FWD); conv_forward(s, bf, m->A1, m->conv[2].w, m->conv[2].b, bf ? nullptr : m->A2, m->idx2, B, d.H1, d.W1, 64, 128, 3, 1, 1, 1, m->A1b, m->wb[2], m->A2b);
-  if (m->shadow_pending) { hipStreamWaitEvent(s, m->shadow_done, 0); m->shadow_pending = false; }       // the rest of the table (conv3 .. conv7, the recurrent matrices): refreshed under conv2
-  // evaluation mode, bf16: BatchNorm + ReLU of conv3 / conv5 are a per-channel affine map -> folded into the conv epilogue, which then writes only
-  // the bf16 shadow (no fp32 map, no apply pass); conv7's BatchNorm also transposes to (T, B) and stays a pass of its own
-  const bool fold = bf && !training && !knob::AOCR_NO_BN_FOLD();
-  if (fold) {
-    prof_mark(m, AOCR_PROF_BN); bn_eval_prepare(s, m->bn[3].rm, m->bn[3].rv, m->bn[3].save, 256);
-    prof_mark(m, AOCR_PROF_CONV_FWD); conv_forward(s, bf, m->A2, m->conv[3].w, m->conv[3].b, nullptr, nullptr, B, d.H2, d.W2, 128, 256, 3, 1, 0, 0, m->A2b, m->wb[3], m->A3b, 0,
-                                                   m->bn[3].save, m->bn[3].w, m->bn[3].b);
-  } else {
-  int bnc = 0;                                              // > 0: the conv's staged epilogue left the BatchNorm's partial sums in bn_scratch (training only)
-  prof_mark(m, AOCR_PROF_CONV_FWD); conv_forward(s, bf, m->A2, m->conv[3].w, m->conv[3].b, m->Y3, nullptr, B, d.H2, d.W2, 128, 256, 3, 1, 0, 0, m->A2b, m->wb[3], nullptr, 0,
-                                                 nullptr, nullptr, nullptr, training ? (double*)m->bn_scratch : nullptr, &bnc, &m->y16[0]);
-  prof_mark(m, AOCR_PROF_BN); bn_relu_forward(s, m->Y3, bf ? nullptr : m->A3, m->bn[3].w, m->bn[3].b, m->bn[3].rm, m->bn[3].rv, m->bn[3].save, m->bn_scratch,
-                  (int64_t)B * d.H2 * d.W2, 256, training, update_running, 0, m->A3b, bsync, bnc, m->y16[0] ? reinterpret_cast<const bf16_t*>(m->Y3) : nullptr);
-  }
-  prof_mark(m, AOCR_PROF_CONV_FWD); conv_forward(s, bf, m->A3, m->conv[4].w, m->conv[4].b, bf ? nullptr : m->A4, m->idx4, B, d.H2, d.W2, 256, 256, 3, 1, 1, 2, m->A3b, m->wb[4], m->A4b);
-  if (fold) {
-    prof_mark(m, AOCR_PROF_BN); bn_eval_prepare(s, m->bn[5].rm, m->bn[5].rv, m->bn[5].save, 512);
-    prof_mark(m, AOCR_PROF_CONV_FWD); conv_forward(s, bf, m->A4, m->conv[5].w, m->conv[5].b, nullptr, nullptr, B, d.H4, d.W2, 256, 512, 3, 1, 0, 0, m->A4b, m->wb[5], m->A5b, 0,
-                                                   m->bn[5].save, m->bn[5].w, m->bn[5].b);
-  } else {
-  int bnc = 0;
-  prof_mark(m, AOCR_PROF_CONV_FWD); conv_forward(s, bf, m->A4, m->conv[5].w, m->conv[5].b, m->Y5, nullptr, B, d.H4, d.W2, 256, 512, 3, 1, 0, 0, m->A4b, m->wb[5], nullptr, 0,
-                                                 nullptr, nullptr, nullptr, training ? (double*)m->bn_scratch : nullptr, &bnc, &m->y16[1]);
-  prof_mark(m, AOCR_PROF_BN); bn_relu_forward(s, m->Y5, bf ? nullptr : m->A5, m->bn[5].w, m->bn[5].b, m->bn[5].rm, m->bn[5].rv, m->bn[5].save, m->bn_scratch,
-                  (int64_t)B * d.H4 * d.W2, 512, training, update_running, 0, m->A5b, bsync, bnc, m->y16[1] ? reinterpret_cast<const bf16_t*>(m->Y5) : nullptr);
-  }
-  prof_mark(m, AOCR_PROF_CONV_FWD); conv_forward(s, bf, m->A5, m->conv[6].w, m->conv[6].b, bf ? nullptr : m->A6, m->idx6, B, d.H4, d.W2, 512, 512, 3, 1, 1, 2, m->A5b, m->wb[6], m->A6b);
-  prof_mark(m, AOCR_PROF_CONV_FWD); conv_forward(s, bf, m->A6, m->conv[7].w, m->conv[7].b, m->Y7, nullptr, B, d.H6, d.W2, 512, 512, 2, 0, 0, 0, m->A6b, m->wb[7], nullptr);
-  prof_mark(m, AOCR_PROF_BN); bn_relu_forward(s, m->Y7, m->X, m->bn[7].w, m->bn[7].b, m->bn[7].rm, m->bn[7].rv, m->bn[7].save, m->bn_scratch,
-                  (int64_t)B * d.T, 512, training, update_running, B, m->Xb, bsync);
-}
-
-// the filter gradients of the CNN backward pass run on the side stream (cnn_backward; backward_all asks too: the hoisted recurrent weight gradients then need no
-// join in front of the CNN backward pass -- the filter gradients queue behind them on the same stream)
-static bool cnn_wgrad_on_side(aocr_model* m) {
-  auto evok = [](hipEvent_t& e) { return e || hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess; };
-  return m->bf16 && m->G2b && !knob::AOCR_DBG_STOP_SET() && !m->prof_on && m->side && m->side_done && !knob::AOCR_NO_SIDE_WGRAD() && !knob::AOCR_NO_CNN_WGRAD_SIDE() &&
-         evok(m->cw_map[0]) && evok(m->cw_map[1]) && evok(m->cw_done[0]) && evok(m->cw_done[1]) && evok(m->cw_main);
-}
-
-static void cnn_backward(aocr_model* m, const float* images, const Dims& d) {
-  hipStream_t s = m->s; const bool bf = m->bf16; const int B = d.B;
-  const BnSync bsync_v{bn_sync_allreduce, m}; const BnSync* bsync = sync_bn_on(m) ? &bsync_v : nullptr;
-  float *G0 = m->G0, *G1 = m->G1;
-  // Round 4: the filter gradients on the side stream.  A stage is E_k (BatchNorm backward / un-pool: HBM-bound, writes the gradient map d Y_k) ->
-  // { filter gradient k, data gradient k } (both MFMA-bound, both read d Y_k) -> E_(k-1).  On one stream the elementwise passes (0.5 ms of the
-  // backward pass at C3) run with the MFMA pipes idle; with the filter gradient of stage k on the (low-priority) side stream it runs beside the data
-  // gradient k and E_(k-1).  d Y alternates between two bf16 buffers so that E_(k-1) can write the next map while the filter gradient k still reads
-  // its own; an event per buffer keeps E_(k-2) from overwriting it before that filter gradient is done.  AOCR_NO_CNN_WGRAD_SIDE=1: one stream.
-  bf16_t* Gb[2] = {m->G0b, m->G2b}; int gp = 0;
-  const int stop = knob::AOCR_DBG_STOP();                  // debugging aid: leave the gradient map of a stage in place (tap "g0")
-  const bool ws = !stop && cnn_wgrad_on_side(m);
-  hipStream_t sw = ws ? m->side : s;
-  const bool wg_after = ws && knob::AOCR_CNN_WGRAD_AFTER_DGRAD();      // A/B: start the filter gradient of a stage behind its data gradient (beside the next elementwise pass only)
-  if (!ws) Gb[1] = Gb[0];
-  auto map_ready = [&]() { if (ws) { hipEventRecord(m->cw_map[gp], s); hipStreamWaitEvent(sw, m->cw_map[gp], 0); } };        // d Y_k (Gb[gp]) is complete: the side stream may read it
-  auto wgrad_done = [&]() { if (ws) hipEventRecord(m->cw_done[gp], sw); };
-  auto next_map = [&]() { if (ws) { gp ^= 1; hipStreamWaitEvent(s, m->cw_done[gp], 0); } };                                    // the next E writes Gb[gp]: the filter gradient that read it two stages ago is done
-  int bnbc = 0;                                                  // > 0: the data gradient's epilogue left the BatchNorm backward's partial sums in bn_scratch (conv_backward_data: bnb_chunks)
-  int g16 = 0; const bf16_t* const G1h = reinterpret_cast<const bf16_t*>(G1);      // conv_backward_data left G1 as bf16 (its dx16): the BatchNorm backward / un-pool pass that follows reads it so
-  // bf16 mode: fp32 G0 is free for the whole pass (every gradient map lives in its bf16 shadow), so the eight partial slabs of the fused bias /
-  // conv1 gradients get regions of their own and their column sums are finished by TWO launches (before the bucket event, at the end)
-  // instead of eight dependent ~10 us dispatches
-  constexpr size_t SLAB = (size_t)4 << 20;                      // floats per slab: >= 2048 x 1024 (BatchNorm), 4096 x 640 (conv1)
-  ColsumJobs cj; cj.n = 0; cj.total = 0;
-  ColsumJobs* defer = (bf && m->gmax >= 8 * SLAB && !knob::AOCR_NO_COLSUM_DEFER()) ? &cj : nullptr;
-  auto slab = [&](int k) { return defer ? G0 + (size_t)k * SLAB : G0; };
-  // bn7 + relu (dX is time-major, Y7 batch-major)
-  // bf16 mode: the BatchNorm backward writes only the bf16 shadow of its gradient, takes the ReLU mask from the bf16 output
-  // shadow and accumulates the preceding conv's bias gradient (fp32 G0 is free there: partial slab)
-  prof_mark(m, AOCR_PROF_BN); bn_relu_backward(s, m->Y7, m->X, m->dX, m->bn[7].w, m->bn[7].save, bf ? nullptr : G0, m->bn[7].dw, m->bn[7].db, m->bn_scratch,
-                   (int64_t)B * d.T, 512, B, Gb[gp], bf ? m->Xb : nullptr, bf ? m->conv[7].db : nullptr, bf ? slab(0) : nullptr, bsync, defer);
-  if (stop == 1) { if (defer) colsum_flush(s, cj); return; }
-  { auto W = [&]() { prof_mark(m, AOCR_PROF_CONV_WGRAD); conv_backward_filter(sw, bf, m->A6, G0, m->conv[7].dw, bf ? nullptr : m->conv[7].db, B, d.H6, d.W2, 512, 512, 2, 0, m->A6b, Gb[gp], m->wg_part, m->wg_part_floats); };
-    auto D = [&]() { prof_mark(m, AOCR_PROF_CONV_DGRAD); conv_backward_data(s, bf, G0, m->conv[7].w, G1, B, d.H6, d.W2, 512, 512, 2, 0, Gb[gp], m->wtb[7], m->wtf[7], bf ? &g16 : nullptr); };
-    if (wg_after) { D(); map_ready(); W(); wgrad_done(); } else { map_ready(); W(); wgrad_done(); D(); } }
-  next_map(); prof_mark(m, AOCR_PROF_POOL_CONV1); unpool_relu_backward(s, G1, m->A6, m->idx6, bf ? nullptr : G0, B, d.H4, d.W2, 512, 2, Gb[gp], bf ? m->conv[6].db : nullptr, bf ? slab(1) : nullptr, bf ? m->A6b : nullptr, defer, g16 ? G1h : nullptr);   // bf16: shadow only + fused bias gradient (fp32 G0 is free: partial slab)
-  if (stop == 2) { if (defer) colsum_flush(s, cj); return; }
-  { auto W = [&]() { prof_mark(m, AOCR_PROF_CONV_WGRAD); conv_backward_filter(sw, bf, m->A5, G0, m->conv[6].dw, bf ? nullptr : m->conv[6].db, B, d.H4, d.W2, 512, 512, 3, 1, m->A5b, Gb[gp], m->wg_part, m->wg_part_floats); };
-    auto D = [&]() { prof_mark(m, AOCR_PROF_CONV_DGRAD); { const BnBwdFuse bf5{m->Y5, m->A5b, m->bn[5].save, (double*)m->bn_scratch}; conv_backward_data(s, bf, G0, m->conv[6].w, G1, B, d.H4, d.W2, 512, 512, 3, 1, Gb[gp], m->wtb[6], m->wtf[6], bf ? &g16 : nullptr, (bf && !m->y16[1]) ? &bf5 : nullptr, &bnbc); } };
-    if (wg_after) { D(); map_ready(); W(); wgrad_done(); } else { map_ready(); W(); wgrad_done(); D(); } }
-  next_map(); prof_mark(m, AOCR_PROF_BN); bn_relu_backward(s, m->Y5, m->A5, G1, m->bn[5].w, m->bn[5].save, bf ? nullptr : G0, m->bn[5].dw, m->bn[5].db, m->bn_scratch,
-                   (int64_t)B * d.H4 * d.W2, 512, 0, Gb[gp], bf ? m->A5b : nullptr, bf ? m->conv[5].db : nullptr, bf ? slab(2) : nullptr, bsync, defer, m->y16[1] ? reinterpret_cast<const bf16_t*>(m->Y5) : nullptr, g16 ? G1h : nullptr, bnbc); bnbc = 0;
-  { auto W = [&]() { prof_mark(m, AOCR_PROF_CONV_WGRAD); conv_backward_filter(sw, bf, m->A4, G0, m->conv[5].dw, bf ? nullptr : m->conv[5].db, B, d.H4, d.W2, 256, 512, 3, 1, m->A4b, Gb[gp], m->wg_part, m->wg_part_floats); };
-    auto D = [&]() { prof_mark(m, AOCR_PROF_CONV_DGRAD); conv_backward_data(s, bf, G0, m->conv[5].w, G1, B, d.H4, d.W2, 256, 512, 3, 1, Gb[gp], m->wtb[5], m->wtf[5], bf ? &g16 : nullptr); };
-    if (wg_after) { D(); map_ready(); W(); wgrad_done(); } else { map_ready(); W(); wgrad_done(); }
-  if (defer) colsum_flush(s, cj);                               // conv7.b, conv6.b, conv5.b
-  if (ws) { hipEventRecord(m->cw_main, s); hipStreamWaitEvent(sw, m->cw_main, 0); hipEventRecord(m->grad_ev[2], sw); }      // (behind the filter gradient of conv5 on the side stream AND the bias sums on this one)
-  else hipEventRecord(m->grad_ev[2], s);                        // every CNN gradient from conv5.w upwards is complete
-    if (!wg_after) D(); }
-  next_map(); prof_mark(m, AOCR_PROF_POOL_CONV1); unpool_relu_backward(s, G1, m->A4, m->idx4, bf ? nullptr : G0, B, d.H2, d.W2, 256, 2, Gb[gp], bf ? m->conv[4].db : nullptr, bf ? slab(3) : nullptr, bf ? m->A4b : nullptr, defer, g16 ? G1h : nullptr);   // bf16: shadow only + fused bias gradient (fp32 G0 is free: partial slab)
-  { auto W = [&]() { prof_mark(m, AOCR_PROF_CONV_WGRAD); conv_backward_filter(sw, bf, m->A3, G0, m->conv[4].dw, bf ? nullptr : m->conv[4].db, B, d.H2, d.W2, 256, 256, 3, 1, m->A3b, Gb[gp], m->wg_part, m->wg_part_floats); };
-    auto D = [&]() { prof_mark(m, AOCR_PROF_CONV_DGRAD); { const BnBwdFuse bf3{m->Y3, m->A3b, m->bn[3].save, (double*)m->bn_scratch}; conv_backward_data(s, bf, G0, m->conv[4].w, G1, B, d.H2, d.W2, 256, 256, 3, 1, Gb[gp], m->wtb[4], m->wtf[4], bf ? &g16 : nullptr, (bf && !m->y16[0]) ? &bf3 : nullptr, &bnbc); } };
-    if (wg_after) { D(); map_ready(); W(); wgrad_done(); } else { map_ready(); W(); wgrad_done(); D(); } }
-  next_map(); prof_mark(m, AOCR_PROF_BN); bn_relu_backward(s, m->Y3, m->A3, G1, m->bn[3].w, m->bn[3].save, bf ? nullptr : G0, m->bn[3].dw, m->bn[3].db, m->bn_scratch,
-                   (int64_t)B * d.H2 * d.W2, 256, 0, Gb[gp], bf ? m->A3b : nullptr, bf ? m->conv[3].db : nullptr, bf ? slab(4) : nullptr, bsync, defer, m->y16[0] ? reinterpret_cast<const bf16_t*>(m->Y3) : nullptr, g16 ? G1h : nullptr, bnbc); bnbc = 0;
-  { auto W = [&]() { prof_mark(m, AOCR_PROF_CONV_WGRAD); conv_backward_filter(sw, bf, m->A2, G0, m->conv[3].dw, bf ? nullptr : m->conv[3].db, B, d.H2, d.W2, 128, 256, 3, 1, m->A2b, Gb[gp], m->wg_part, m->wg_part_floats); };
-    auto D = [&]() { prof_mark(m, AOCR_PROF_CONV_DGRAD); conv_backward_data(s, bf, G0, m->conv[3].w, G1, B, d.H2, d.W2, 128, 256, 3, 1, Gb[gp], m->wtb[3], m->wtf[3]); };
-    if (wg_after) { D(); map_ready(); W(); wgrad_done(); } else { map_ready(); W(); wgrad_done(); D(); } }
-  next_map(); prof_mark(m, AOCR_PROF_POOL_CONV1); unpool_relu_backward(s, G1, m->A2, m->idx2, bf ? nullptr : G0, B, d.H1, d.W1, 128, 1, Gb[gp], bf ? m->conv[2].db : nullptr, bf ? slab(5) : nullptr, bf ? m->A2b : nullptr, defer);   // bf16: shadow only + fused bias gradient (fp32 G0 is free: partial slab)
-  { auto W = [&]() { prof_mark(m, AOCR_PROF_CONV_WGRAD); conv_backward_filter(sw, bf, m->A1, G0, m->conv[2].dw, bf ? nullptr : m->conv[2].db, B, d.H1, d.W1, 64, 128, 3, 1, m->A1b, Gb[gp], m->wg_part, m->wg_part_floats); };
-    auto D = [&]() { prof_mark(m, AOCR_PROF_CONV_DGRAD); conv_backward_data(s, bf, G0, m->conv[2].w, G1, B, d.H1, d.W1, 64, 128, 3, 1, Gb[gp], m->wtb[2], m->wtf[2]); };
-    if (wg_after) { D(); map_ready(); W(); wgrad_done(); } else { map_ready(); W(); wgrad_done(); D(); } }
-  prof_mark(m, AOCR_PROF_POOL_CONV1); conv1_backward(s, images, m->conv[1].w, m->conv[1].b, G1, m->conv[1].dw, m->conv[1].db, B, d.H, d.W,
-                 (size_t)B * d.H1 * d.W1 * 128 >= (size_t)4096 * 640 ? slab(6) : nullptr, defer,      // G0 is free here: use it as the partial slab
-                 m->route1_valid && !knob::AOCR_CONV1_RECOMPUTE() ? m->route1 : nullptr);
-  if (defer) colsum_flush(s, cj);                               // conv4.b, conv3.b, conv2.b, conv1.w, conv1.b
-  if (ws) { hipEventRecord(m->side_done, sw); hipStreamWaitEvent(s, m->side_done, 0); }
 }
 
 // ------------------------------------------------------------------------------------------------
