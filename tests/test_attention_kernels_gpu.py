@@ -1,6 +1,6 @@
 """GPU: every attention kernel instantiation (csrc/ops_misc.hip: attn_launch behind attention_forward / attention_backward, the two
-attention_*_dual launchers, attention_dctx) against a float64 reference, called directly through tests/libkprobe.so.  Method and helpers
-of tests/test_kernels_bf16_gpu.py and tests/test_step_kernels_bf16_gpu.py: every output is a window of a wider buffer or has a sentinel
+attention_*_dual launchers, attention_dctx) against a float64 reference, called directly through tests/libkprobe.so.  Method
+of tests/test_kernels_bf16_gpu.py and tests/test_step_kernels_bf16_gpu.py, helpers of tests/kernel_harness.py: every output is a window of a wider buffer or has a sentinel
 tail, nothing outside the window may change, and every case asserts the kernel it reached from the AOCR_TRACE dispatch line
 ("[aocr] <function>: <kernel>[<instantiation>] B T Hd").
 
@@ -103,15 +103,13 @@ measured (largest error / tolerance per test, MI355X):
   test_attention_dctx_exact[33-65-96]: 0 of 18720 elements differ from float64
   test_attention_dctx_exact[70-130-512]: 0 of 199680 elements differ from float64
 """
-import ctypes as C
 import math
 
 import pytest
 import torch
 
-from test_kernels_bf16_gpu import Buf, _switches, bf, bound, expect, ints, kp, rnd, setenv, trace_of  # noqa: F401
-from test_kernels_bf16_gpu import call, SENT
-from test_step_kernels_bf16_gpu import Mat, out
+from kernel_harness import _switches  # noqa: F401  this import IS how the autouse fixture reaches the module (tests/test_kernel_harness_cpu.py checks it)
+from kernel_harness import SENT, Buf, Mat, bf, bound, call, expect, ints, kp, out, ratio, rnd, setenv, vp
 
 pytestmark = pytest.mark.gpu
 
@@ -119,7 +117,6 @@ TOL_A, TOL_C = 2e-5, 5e-5           # test_ops_gpu.py::test_attention (c: times 
 TOL_DS, TOL_DQ = 5e-5, 1e-4         # times max(1, max |d a|) (d q: and max |ctx|)
 P_EDGE = 0.05                       # least reference probability of a planted edge row in its batch row
 QC, QU = 2.0 ** -2, 2.0 ** -3       # quanta of the context and of u
-vp = C.c_void_p
 
 
 def edges(T, chunk):
@@ -176,10 +173,6 @@ class Problem:
 
 def plain_ctx(nimg, T, Hd, seed):
     return ints(nimg, T, Hd, seed=seed, lo=-2, hi=2).double() * QC
-
-
-def ratio(got, ref, tol):
-    return ((got.double() - ref).abs() / tol).max().item()
 
 
 def b16(t):

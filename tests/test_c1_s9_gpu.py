@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_step_gpu import make, relerr
+from model_harness import make, relerr
 from tol import check_logits
 
 pytestmark = pytest.mark.gpu
@@ -127,7 +127,7 @@ def test_decode_parity_calibrated_statistics(cuda, case, beam, B):
     """Decode parity on BatchNorm statistics calibrated to the batch (O.calibrated_bn_state): unlike the initial 0 / 1 statistics
     the evaluation-mode CNN is normalised, the LSTM gates do not saturate and the decoded strings differ from image to image --
     labels, beam scores, gold scores, loss and the exact-match count against O.decode_beam (model.lua:321-627)."""
-    from test_step_gpu import CASES
+    from model_harness import CASES
     m, O, ocfg, P, st, batch = make(CASES[case], B=B, W=36, maxlen=5, max_decoder_l=10)
     img, tgt, tge = (torch.from_numpy(np.asarray(x)) for x in batch[:3])
     st = O.calibrated_bn_state(P, img)

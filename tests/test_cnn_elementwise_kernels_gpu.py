@@ -1,6 +1,6 @@
 """GPU: every BatchNorm, un-pool, conv1 and column-sum kernel variant (csrc/ops_misc.hip) against a float64 / exact-integer reference
 (tests/cnn_elementwise_ref.py), called directly through tests/libkprobe.so with the optional arguments the bf16 train step passes.
-Helpers and fixture of tests/test_kernels_bf16_gpu.py: every device buffer has a sentinel tail that must survive, partial slabs and
+Helpers and fixture of tests/kernel_harness.py: every device buffer has a sentinel tail that must survive, partial slabs and
 scratch are allocated at exactly the size csrc/ops.h documents, accumulating outputs start from non-zero integers, and every case
 asserts the AOCR_TRACE line(s) of the launch decision it reached.
 
@@ -32,10 +32,10 @@ import pytest
 import torch
 
 import cnn_elementwise_ref as R
-from test_kernels_bf16_gpu import SENT, Buf, _switches, bf, bits, call, expect, ints, kp, rnd, setenv, trace_of  # noqa: F401
+from kernel_harness import _switches  # noqa: F401  this import IS how the autouse fixture reaches the module (tests/test_kernel_harness_cpu.py checks it)
+from kernel_harness import SENT, Buf, bf, bits, call, expect, i32, i64, ints, kp, rnd, setenv, trace_of, vp
 
 pytestmark = pytest.mark.gpu
-vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
 U = R.U
 
 # ---- bounds: c = fp32 roundings + 1, from the kernels' expressions
@@ -51,27 +51,6 @@ C_DW = 5
 # conv1 forward: bias + nine FMAs                                                                        -> 9 roundings
 C_CONV = 10
 BF = 2.0 ** -8                      # RNE to bf16 (8 significant bits): half an ulp is at most 2^-8 of the value
-
-
-def lib():
-    k = kp()
-    if not getattr(k, "_cnn_elementwise", False):
-        sig = {
-            "kp_bn_relu_forward2": [vp] * 9 + [i64, i32, i32, i32, i32, vp, i32, i32, vp],
-            "kp_bn_relu_backward": [vp] * 10 + [i64, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, i32],
-            "kp_unpool_relu_backward": [vp] * 5 + [i32] * 5 + [vp, vp, vp, vp, i32, vp],
-            "kp_conv1_forward": [vp] * 5 + [i32] * 3 + [vp, vp],
-            "kp_conv1_backward": [vp] * 7 + [i32] * 3 + [vp, i32, vp],
-            "kp_colsum_accum": [vp, vp, i64, i64, i32, vp, vp],
-            "kp_colsum_jobs": [vp, i32] + [vp] * 7,
-        }
-        for n, a in sig.items():
-            getattr(k, n).argtypes = a
-            getattr(k, n).restype = i32
-        k.kp_conv1_route_elems.argtypes = [i32, i32, i32]
-        k.kp_conv1_route_elems.restype = sz
-        k._cnn_elementwise = True
-    return k
 
 
 def P(b):
@@ -129,7 +108,6 @@ def encode_route(r, B, H, W):
 
 
 def conv1_fwd(xd, wd, bd, B, H, W, out, with_route, capfd, what):
-    lib()
     Hp, Wp = H // 2, W // 2
     dst = out.split("+")
     y = Buf((B, Hp, Wp, 64), fill=SENT) if "y" in dst else None
@@ -144,7 +122,6 @@ def conv1_fwd(xd, wd, bd, B, H, W, out, with_route, capfd, what):
 
 
 def conv1_bwd(xd, wd, bd, gd, dw0, db0, B, H, W, kernel, finish, route, monkeypatch, capfd, what):
-    lib()
     if kernel == "scalar":
         monkeypatch.setenv("AOCR_CONV1_SCALAR", "1")
     else:
@@ -277,7 +254,6 @@ UNPOOL_CASES = [("c8_p22", 2, 4, 6, 8, 1), ("c64_p22_odd", 1, 5, 7, 64, 1), ("c9
 
 @pytest.mark.parametrize("case", UNPOOL_CASES, ids=[c[0] for c in UNPOOL_CASES])
 def test_unpool_exact(case, monkeypatch, capfd):
-    lib()
     name, B, Ho, Wo, Cc, pool = case
     Hp, Wp = Ho // 2, (Wo // 2 if pool == 1 else Wo)
     g = ints(B, Hp, Wp, Cc, seed=21)
@@ -330,7 +306,6 @@ UNPOOL_RANDOM = [("c64_p22_odd", 2, 5, 7, 64, 1), ("c128_p21", 2, 6, 5, 128, 2),
 
 @pytest.mark.parametrize("case", UNPOOL_RANDOM, ids=[c[0] for c in UNPOOL_RANDOM])
 def test_unpool_random(case, monkeypatch, capfd):
-    lib()
     name, B, Ho, Wo, Cc, pool = case
     worst = {}
     Hp, Wp = Ho // 2, (Wo // 2 if pool == 1 else Wo)
@@ -391,7 +366,6 @@ def partial4_ok(Cc, old):
 
 def bn_scratch(Cc, chunks=None):
     """bn_relu_*'s scratch (bn_scratch_bytes(C) bytes of doubles), optionally holding `chunks` (n, C, 2) partial sums; the rest is junk the launcher must not read"""
-    lib()
     nd = kp().kp_bn_scratch_bytes(Cc) // 8
     s = Buf((nd,), torch.float64, fill=1e30)
     if chunks is not None:
@@ -598,7 +572,6 @@ COLSUM_ROWS = (1, 15, 16, 17, 129, 5000)
 
 @pytest.mark.parametrize("N", COLSUM_N)
 def test_colsum_accum(N, monkeypatch, capfd):
-    lib()
     for rows in COLSUM_ROWS:
         # ld a multiple of 4 on an aligned base (16-byte loads); ld % 4 != 0; a base one float off 16 bytes (both: the scalar branch)
         for ld, offset in (((N + 3) // 4 * 4 + 4, 0), ((N + 3) // 4 * 4 + 1, 0), ((N + 3) // 4 * 4, 1)):
@@ -623,7 +596,6 @@ JOBS8 = [(5000, 576, 640, 0, 0), (129, 64, 640, 0, 0), (17, 39, 41, 0, 1), (1, 3
 
 @pytest.mark.parametrize("njobs", (1, 8, 9))
 def test_colsum_jobs(njobs, monkeypatch, capfd):
-    lib()
     jobs = (JOBS8 + [(33, 64, 64, 0, 1)])[:njobs]
     ops, outs, out2s, refs = [], [], [], []
     for i, (rows, N, ld, offset, with_out2) in enumerate(jobs):
@@ -660,7 +632,6 @@ def colsum_random_operand(rows, N, ld, offset, seed):
 
 
 def test_colsum_random(monkeypatch, capfd):
-    lib()
     worst = {}
     ops = [colsum_random_operand(*c, seed=75 + i) for i, c in enumerate(COLSUM_RANDOM)]
     o0 = [ints(c[1], seed=76, lo=1, hi=4) for c in COLSUM_RANDOM]

@@ -241,7 +241,7 @@ def test_host_wrappers_take_a_view_and_chain_on_the_device(cuda, monkeypatch):
 # ---- Model.recognize_page(colour=...) --------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model(cuda):
-    from test_step_gpu import make
+    from model_harness import make
     m, O, ocfg, P0, st, _ = make(dict(enc_hidden=32, enc_layers=1, dec_layers=2, input_feed=True), B=32, W=100, maxlen=8, compute="f32",
                                  max_decoder_l=12, max_beam=5)
     m.set_parameters(O.sharpen_params(P0), st)

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_step_gpu import make, relerr, _gpu_cnn_decisions
+from model_harness import gpu_cnn_decisions, make, relerr
 from tol import check_logits
 
 pytestmark = pytest.mark.gpu
@@ -323,7 +323,7 @@ def test_c3_bf16_all_gradients_vs_oracle(cuda):
     check_bf16_gradients("C3 bf16", grads, G, Gq)
     # The conv stack's cosine of 0.97-0.999 is ReLU / arg-max DECISION flips between two bf16 forward passes (check_bf16_gradients):
     # tested here by imposing the GPU's own decisions on the bf16-operand oracle -- then every tensor agrees to bf16 arithmetic noise.
-    dec = _gpu_cnn_decisions(m, B)
+    dec = gpu_cnn_decisions(m, B)
     with O.operand_rounding("bf16"):
         loss_d, Gd, _, _ = O.train_step_autograd(P, st, ocfg, img, tgt, tge, cnn_decisions=dec)
     worst = ("", 1.0)

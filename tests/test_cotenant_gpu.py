@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_step_gpu import make
+from model_harness import make
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))

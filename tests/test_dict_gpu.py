@@ -125,7 +125,7 @@ def test_edit_distance_kernel(cuda, B, L):
 def test_decode_with_dictionary_small(cuda, case, beam, digit_prefix):
     import aocr
     import dict_oracle as DO
-    from test_step_gpu import CASES, make
+    from model_harness import CASES, make
     m, O, ocfg, P, st, batch = make(CASES[case], B=4, W=36, maxlen=5, max_decoder_l=10)
     st = {k: (v + 0.05 if k.endswith("rm") else v * 1.3) for k, v in st.items()}
     P = dict(P); P["proj.b"] = P["proj.b"].clone(); P["proj.b"][:3] -= 4.0     # random weights: make PAD/GO/EOS unlikely, so words get spelled
@@ -159,7 +159,7 @@ def test_dictionary_decode_full_size_property(cuda):
     """C3 geometry (batch 256, 32x256, bf16), beam 3, a 20 k-word lexicon: whatever the random weights prefer, every decoded row
     must spell a path of the trie (PAD keeps the node, model.lua:469,502-503) -- a size-independent property of the constraint."""
     import aocr
-    from test_step_gpu import make
+    from model_harness import make
     m, O, ocfg, P, st, batch = make(dict(enc_hidden=256, enc_layers=1, dec_layers=2, input_feed=True), B=256, W=256, maxlen=23,
                                     compute="bf16", max_decoder_l=30, max_beam=3)
     P = dict(P); P["proj.b"] = P["proj.b"].clone(); P["proj.b"][:3] -= 4.0
@@ -189,7 +189,7 @@ def test_greedy_dictionary_decode_cluster_kernel(cuda, monkeypatch):
     """Greedy (beam 1) dictionary decode through the decoder cluster kernel's DEC variant (trie test + node update inside the kernel's
     selection) against the launch chain with project_select_kernel: same labels, every row on a trie path."""
     import aocr
-    from test_step_gpu import make
+    from model_harness import make
     rng = random.Random(7)
     words = _words(rng, 5000, "abcdefghijklmnopqrstuvwxyz", 3, 9)
     out = {}
@@ -221,7 +221,7 @@ def test_beam_dictionary_decode_chain_kernel(cuda, monkeypatch, beam):
     the repeat-the-best rule when fewer candidates than beams are admissible: model.lua:405-445,460-513) against the launch chain with
     project_select_kernel: same labels, every row on a trie path."""
     import aocr
-    from test_step_gpu import make
+    from model_harness import make
     rng = random.Random(11)
     words = _words(rng, 5000, "abcdefghijklmnopqrstuvwxyz", 3, 9)
     out = {}

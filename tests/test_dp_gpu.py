@@ -20,7 +20,7 @@ CFG = dict(enc_hidden=32, enc_layers=1, dec_layers=2, input_feed=True)
 
 def _build(B, W, compute="f32"):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from test_step_gpu import make
+    from model_harness import make
     return make(CFG, B=B, W=W, maxlen=6, compute=compute, max_decoder_l=8, max_beam=1)
 
 
@@ -98,7 +98,7 @@ ENV_BF16 = dict(AOCR_FORCE_DMA="1", AOCR_LAYER_PIPE_CHUNKS="3")          # small
 
 def _build_bf16(B, W):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from test_step_gpu import make
+    from model_harness import make
     return make(CFG_BF16, B=B, W=W, maxlen=6, compute="bf16", max_decoder_l=8, max_beam=1)
 
 

@@ -11,7 +11,7 @@ import enc_seq_ref as R
 import oracle_torch as O
 
 F64 = torch.float64
-TOL_CELL = 2e-5                      # tests/test_step_kernels_bf16_gpu.py
+TOL_CELL = 2e-5                      # tests/kernel_harness.py
 
 
 @pytest.mark.parametrize("B,T,He", [(3, 1, 8), (4, 5, 16), (2, 2, 8)])

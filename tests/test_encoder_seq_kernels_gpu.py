@@ -1,7 +1,7 @@
 """GPU: the whole-sequence encoder kernels of the default configuration -- enc_seq_fwd_kernel / enc_seq_bwd_kernel (csrc/rnn_seq.hip) and
 enc_cl_fwd_kernel / enc_cl_bwd_kernel (csrc/rnn_cluster.hip) -- called directly through tests/libkprobe.so and held, step by step, to the float64
-restatement of tests/enc_seq_ref.py (itself checked on the CPU in tests/test_enc_seq_ref_cpu.py).  Method and helpers of
-tests/test_kernels_bf16_gpu.py / tests/test_step_kernels_bf16_gpu.py: sentinel-filled outputs with sentinel tails, JUNK around every strided window,
+restatement of tests/enc_seq_ref.py (itself checked on the CPU in tests/test_enc_seq_ref_cpu.py).  Method of
+tests/test_kernels_bf16_gpu.py / tests/test_step_kernels_bf16_gpu.py, helpers of tests/kernel_harness.py: sentinel-filled outputs with sentinel tails, JUNK around every strided window,
 the configuration each call reached asserted from its AOCR_TRACE line, err[0] == 0 after every cluster call.
 
 DEVICE-FED comparison.  Step t of the reference is computed from the device's OWN saved hsb(t') and cs(t') (backward: from the device's own dzb of the
@@ -38,12 +38,11 @@ import pytest
 import torch
 
 import enc_seq_ref as R
-from test_kernels_bf16_gpu import SENT, Buf, _switches, bound, kp, setenv, trace_of  # noqa: F401  (_switches: the autouse fixture)
-from test_step_kernels_bf16_gpu import JUNK, TOL_BWD, TOL_CELL
+from kernel_harness import _switches  # noqa: F401  this import IS how the autouse fixture reaches the module (tests/test_kernel_harness_cpu.py checks it)
+from kernel_harness import JUNK, SENT, TOL_BWD, TOL_CELL, Buf, bound, i32, i64, kp, launch, ratio, setenv, sz, trace_of, vp
 
 pytestmark = pytest.mark.gpu
 
-vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
 SENT_B = -3.0                       # sentinel of the bf16 outputs (exact in bf16)
 ERR_INTS = 16 + 256 * 8 + 4096      # model.hip: cl_err
 KNOBS = ("AOCR_ENC_RT2", "AOCR_ENC_RH16", "AOCR_ENC_BWD_RH", "AOCR_CL_REMOTE", "AOCR_SEQ_ABL", "AOCR_SEQ_STAMP")
@@ -81,27 +80,6 @@ class EncClBwd(C.Structure):
     _fields_ = [("d", EncBwdDir * 2), ("c", EncCl)]
 
 
-_SIGS = False
-
-
-def lib():
-    global _SIGS
-    k = kp()
-    if not _SIGS:
-        for n in ("kp_enc_seq_forward", "kp_enc_seq_backward", "kp_enc_cluster_forward", "kp_enc_cluster_backward"):
-            getattr(k, n).argtypes, getattr(k, n).restype = [vp, vp], i32
-        k.kp_enc_seq_supported.argtypes, k.kp_enc_seq_supported.restype = [i32, i32], i32
-        k.kp_enc_cluster_plan.argtypes, k.kp_enc_cluster_plan.restype = [i32, i32, i32, i32, vp, vp, vp], i32
-        for n in ("kp_enc_cluster_xbuf_bytes", "kp_enc_cluster_pbuf_bytes"):
-            getattr(k, n).argtypes, getattr(k, n).restype = [i32, i32], sz
-        _SIGS = True
-    return k
-
-
-def launch(name, args):
-    return getattr(lib(), name)(C.c_void_p(torch.cuda.current_stream().cuda_stream), C.byref(args))
-
-
 @pytest.fixture(autouse=True)
 def _knobs(monkeypatch, _switches):
     for k in KNOBS:
@@ -127,10 +105,6 @@ def same_bits(a, b):
 
 def is_sentinel(t):
     return bool((t == (SENT_B if t.dtype == torch.bfloat16 else SENT)).all())
-
-
-def ratio(got, ref, tol):
-    return ((got.double() - ref).abs() / tol).max().item()
 
 
 def in_rne_range(got_b, ref, tol):
@@ -351,9 +325,9 @@ class Exchange:
 
     def __init__(self, B, T, He, kind, layers=1, reserve=0):
         G, RT, groups = C.c_int(0), C.c_int(0), C.c_int(0)
-        assert lib().kp_enc_cluster_plan(B, He, T, reserve, C.byref(G), C.byref(RT), C.byref(groups)) == 1, "the cluster kernels do not take this shape here"
+        assert kp().kp_enc_cluster_plan(B, He, T, reserve, C.byref(G), C.byref(RT), C.byref(groups)) == 1, "the cluster kernels do not take this shape here"
         self.G, self.RT, self.groups, self.layers, self.reserve = G.value, RT.value, groups.value, layers, reserve
-        per = lib().kp_enc_cluster_xbuf_bytes(B, He) if kind == "x" else lib().kp_enc_cluster_pbuf_bytes(B, He)
+        per = kp().kp_enc_cluster_xbuf_bytes(B, He) if kind == "x" else kp().kp_enc_cluster_pbuf_bytes(B, He)
         self.buf = Buf((layers * per // 8,), torch.int64, fill=0)
         self.xtab = Buf((layers * 4 * ((B + 15) // 16) * 8 + 64,), torch.int64, fill=0)
         self.err = Buf((ERR_INTS,), torch.int32, fill=0)
@@ -402,7 +376,7 @@ assert {c[:3] for c in SEQ_CASES} <= set(R.SEQ_SHAPES)
 
 @pytest.mark.parametrize("B,T,He,ctx", SEQ_CASES)
 def test_seq_forward(B, T, He, ctx, capfd):
-    assert lib().kp_enc_seq_supported(B, He) == 1
+    assert kp().kp_enc_seq_supported(B, He) == 1
     p = Fwd(B, T, He, "seq", ctx, seed=B + T)
     a = EncSeqFwd()
     a.d, a.B, a.T, a.He, a.Hd = p.dirs(), B, T, He, 2 * He
@@ -431,7 +405,7 @@ def test_seq_backward(B, T, He, dh2, capfd):
 
 
 def test_seq_wrappers_refuse_what_the_model_would_not_launch():
-    assert lib().kp_enc_seq_supported(21, 256) == 0 and lib().kp_enc_seq_supported(16, 512) == 0
+    assert kp().kp_enc_seq_supported(21, 256) == 0 and kp().kp_enc_seq_supported(16, 512) == 0
     p = Fwd(16, 1, 64, "seq", False)
     a = EncSeqFwd()
     a.d, a.B, a.T, a.He, a.Hd = p.dirs(), 21, 1, 64, 128

@@ -144,7 +144,7 @@ def test_python_surface_on_a_view(cuda):
 
 def test_recognize_page_flatten(cuda):
     import aocr
-    from test_step_gpu import make
+    from model_harness import make
     B = 32
     m, O, ocfg, P0, st, _ = make(dict(enc_hidden=32, enc_layers=1, dec_layers=2, input_feed=True), B=B, W=100, maxlen=8, compute="f32",
                                  max_decoder_l=12, max_beam=5)

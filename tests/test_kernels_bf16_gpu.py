@@ -13,147 +13,19 @@ output, and the error against float64 on the bf16-rounded operands stays within 
 (fp32 accumulation of K exact bf16 x bf16 products; tests/tol.py holds the model-level bounds).
 
 Each case asserts the kernel it reached from the AOCR_TRACE dispatch line ("[aocr] <function>: <kernel>[<instantiation>] M N K"),
-so a moved threshold cannot silently send a case to another kernel.  Every device buffer has a sentinel-filled tail that must survive."""
+so a moved threshold cannot silently send a case to another kernel.  Every device buffer has a sentinel-filled tail that must survive.
+The helpers the other kernel-level files share with this one (Buf, the operand generators, the trace assertions, the shim's handle) are in
+tests/kernel_harness.py."""
 import ctypes as C
-import os
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+from kernel_harness import _switches  # noqa: F401  this import IS how the autouse fixture reaches the module (tests/test_kernel_harness_cpu.py checks it)
+from kernel_harness import EP_ACCUM, EP_RELU, EP_TANH, SENT, Buf, bf, bits, bound, call, expect, ints, kp, nhwc, rnd, setenv, trace_of
+
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BOUND_C = 4.0                       # per-element bound of the random cases: BOUND_C * sqrt(K) * 2^-24 * (|A| |B|)
-SLACK = 4096                        # sentinel elements behind every device buffer
-SENT = -12345.0
-SWITCHES = ("AOCR_FORCE_DMA", "AOCR_HALO8", "AOCR_HALO4_STAGED", "AOCR_NO_HALO", "AOCR_NO_DMA128", "AOCR_DMA128_W4", "AOCR_NO_NARROW_STAGED",
-            "AOCR_NO_WGRAD_HALO", "AOCR_WGRAD_HALO_RAGGED", "AOCR_NO_WGRAD_ISSUE_MID", "AOCR_WGRAD_ATOMIC", "AOCR_WGRAD_HALO_MINSTEPS",
-            "AOCR_HH_NARROW_FULL_ONLY", "AOCR_NO_HH_CAT", "AOCR_NO_WGRAD_DMA_GROUPED", "AOCR_WGRAD_DMA_MINK", "AOCR_DX16", "AOCR_NO_DMA",
-            "AOCR_NO_HH_NARROW", "AOCR_NO_NARROW_WIDE", "AOCR_WGRAD_HALO_MINN", "AOCR_BN_Y16", "AOCR_NO_BN_STATS_FUSE", "AOCR_BNB_FUSE",
-            "AOCR_WGRAD_DMA_WGS", "AOCR_BN_PARTIAL_OLD", "AOCR_UNPOOL4", "AOCR_CONV1_SCALAR",
-            # the recurrent-step launchers (tests/test_step_kernels_bf16_gpu.py shares this fixture)
-            "AOCR_NO_HALF_TILES", "AOCR_HALF_TILES_MAXGRID", "AOCR_NO_STEP_MT2", "AOCR_STEP_MT2_MINK", "AOCR_NO_STEPL", "AOCR_STEPL_MIN_WGS",
-            "AOCR_STEP_WAVES4", "AOCR_STEP_WAVES16", "AOCR_BIG_STEP", "AOCR_BIG_STEP_MIN_ROWS",
-            # the attention launchers (tests/test_attention_kernels_gpu.py shares this fixture)
-            "AOCR_NO_ATTN_BF16", "AOCR_ATTN_NW16", "AOCR_NO_ATTN_BEAM_GROUP", "AOCR_ATTN_BWD_TWO_PASS", "AOCR_NO_CHAIN_CTXA")
-
-_KP = None
-vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
-
-
-def kp():
-    global _KP
-    if _KP is None:
-        import aocr  # noqa: F401  (libaocr.so first; the shim resolves against it)
-        lib = C.CDLL(os.path.join(ROOT, "tests", "libkprobe.so"))
-        sig = {
-            "kp_conv_forward": [vp, i32, vp, vp, vp, vp, vp] + [i32] * 9 + [vp] * 8,
-            "kp_conv_backward_data": [vp, i32, vp, vp, vp] + [i32] * 7 + [vp, vp, vp],
-            "kp_conv_backward_filter": [vp, i32, vp, vp, vp, vp] + [i32] * 7 + [vp, vp, vp, sz],
-            "kp_conv_weight_shadows": [vp, vp, vp, vp, i32, i32, i32],
-            "kp_splitk_reduce": [vp, vp, i32, sz, vp],
-            "kp_gemm_hh": [vp, vp, i64, vp, i64, vp, i64, i32, i32, i32, vp, vp, i32],
-            "kp_gemm_hh_shadow": [vp, vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32],
-            "kp_gemm_hh_cat": [vp, vp, vp, i64, vp, vp, i64, vp, i64, i32, i32, i32, i32, vp],
-            "kp_grouped_wgrad": [vp, i32, i32] + [vp] * 11 + [vp, sz],
-            "kp_bn_relu_forward": [vp] * 9 + [i64, i32, i32, i32, i32],
-            "kp_bn_eval_prepare": [vp, vp, vp, vp, i32],
-            "kp_attention_forward": [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, i64, vp],
-            "kp_attention_backward": [vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, vp, vp, vp, i64],
-            "kp_attention_forward_dual": [vp, vp, i64, vp, vp, i64, i32, i32, i32, vp, i64, vp, vp],
-            "kp_attention_backward_dual": [vp, vp, vp, i64, vp, vp, vp, vp, i32, i32, vp, vp],
-            "kp_attention_dual_ok": [i32, i32, vp, vp],
-            "kp_attention_dctx": [vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, i32],
-        }
-        for n, a in sig.items():
-            getattr(lib, n).argtypes = a
-            getattr(lib, n).restype = i32
-        lib.kp_bn_scratch_bytes.argtypes = [i32]
-        lib.kp_bn_scratch_bytes.restype = sz
-        _KP = lib
-    return _KP
-
-
-def call(name, *args):
-    rc = getattr(kp(), name)(C.c_void_p(torch.cuda.current_stream().cuda_stream), *args)
-    assert rc == 0, f"{name}: hipGetLastError() = {rc}"
-
-
-@pytest.fixture(autouse=True)
-def _switches(monkeypatch, cuda):
-    for k in SWITCHES:
-        monkeypatch.delenv(k, raising=False)
-    monkeypatch.setenv("AOCR_TRACE", "1")
-
-
-def ints(*shape, seed, lo=-4, hi=4):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(lo, hi + 1, shape, generator=g).float()
-
-
-def rnd(*shape, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.rand(*shape, generator=g, dtype=torch.float64) * 2 - 1
-
-
-class Buf:
-    """A device buffer (from a CPU tensor, or of `shape` filled with `fill`) with SLACK sentinel elements behind it."""
-
-    def __init__(self, t, dtype=torch.float32, fill=None):
-        if fill is not None:
-            shape = tuple(t)
-            n = 1
-            for s in shape:
-                n *= s
-            self.full = torch.full((n + SLACK,), fill, dtype=dtype, device="cuda")
-        else:
-            shape = tuple(t.shape)
-            n = t.numel()
-            self.full = torch.empty(n + SLACK, dtype=dtype, device="cuda")
-            self.full[:n] = t.reshape(-1).to(dtype).cuda()
-        self.tail_val = SENT if dtype.is_floating_point else 0x5A
-        self.full[n:] = self.tail_val
-        self.n, self.shape, self.dtype = n, shape, dtype
-        self.t = self.full[:n].view(shape)
-
-    def ptr(self):
-        return C.c_void_p(self.full.data_ptr())
-
-    def cpu(self):
-        return self.t.cpu()
-
-    def check_tail(self, what):
-        tail = self.full[self.n:].cpu()
-        assert torch.equal(tail, torch.full_like(tail, self.tail_val)), f"{what}: write past the end of the buffer"
-
-
-def bf(t):
-    """torch's RNE bf16 image of t, as a bit-comparable int16 tensor."""
-    return t.float().to(torch.bfloat16).view(torch.int16)
-
-
-def bits(buf):
-    return buf.cpu().view(torch.int16)
-
-
-def trace_of(capfd, fn):
-    err = capfd.readouterr().err
-    return [ln for ln in err.splitlines() if ln.startswith(f"[aocr] {fn}: ")]
-
-
-def expect(capfd, fn, kernel):
-    lines = trace_of(capfd, fn)
-    assert lines, f"{fn}: no dispatch trace line (AOCR_TRACE)"
-    assert all(f": {kernel}" in ln for ln in lines), (kernel, lines)
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous()
-
-
-def bound(mag, K):
-    return BOUND_C * (K ** 0.5) * 2.0 ** -24 * mag
 
 
 def pool_ref(z, pool):
@@ -192,11 +64,6 @@ FWD_CASES = [
     ("h1_b1", 1, 1, 300, 32, 256, 3, 1, {}, "gemm_dma128_kernel[8,8]"),
     ("h2_b1", 1, 2, 150, 32, 256, 3, 1, {}, "gemm_dma128_kernel[8,8]"),
 ]
-
-
-def setenv(monkeypatch, env):
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
 
 
 def conv_operands(B, H, W, Cin, Cout, ks, seed):
@@ -508,7 +375,6 @@ HH_CASES = [
     ("lds_n100", 300, 100, 64, {}, "gemm_lds_bf16_kernel[32]"),
     ("lds_k48", 200, 128, 48, {}, "gemm_lds_bf16_kernel[32]"),
 ]
-EP_RELU, EP_TANH, EP_ACCUM = 1, 2, 4
 
 
 @pytest.mark.parametrize("case", HH_CASES, ids=[c[0] for c in HH_CASES])

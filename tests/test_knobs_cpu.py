@@ -80,7 +80,7 @@ def test_design_table_lists_every_switch_once():
 
 
 def test_kernel_test_switches_are_declared():
-    tree = ast.parse(_read(os.path.join(ROOT, "tests", "test_kernels_bf16_gpu.py")))
+    tree = ast.parse(_read(os.path.join(ROOT, "tests", "kernel_harness.py")))
     value = next(n.value for n in tree.body if isinstance(n, ast.Assign) and any(getattr(t, "id", None) == "SWITCHES" for t in n.targets))
     switches = ast.literal_eval(value)
     assert len(switches) > 40

@@ -7,6 +7,8 @@ import subprocess
 
 import pytest
 
+from kernel_harness import SIGS
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "torch-attention-ocr_amd", "csrc")
 LIB = os.path.join(ROOT, "torch-attention-ocr_amd", "aocr", "libaocr.so")
@@ -68,3 +70,5 @@ def test_kprobe_symbols_resolve_in_libaocr(tmp_path):
                  "kp_enc_seq_supported", "kp_enc_seq_forward", "kp_enc_seq_backward", "kp_enc_cluster_plan", "kp_enc_cluster_xbuf_bytes",
                  "kp_enc_cluster_pbuf_bytes", "kp_enc_cluster_forward", "kp_enc_cluster_backward"):
         assert name in exported
+    unexported = sorted(set(SIGS) - exported)
+    assert not unexported, f"in kernel_harness.SIGS, not exported by the compiled shim: {unexported}"

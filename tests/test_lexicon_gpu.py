@@ -268,7 +268,7 @@ def test_through_the_model(cuda):
     """Model.recognize(images, lexicon=...) on the small fp32 configuration of test_recognize_gpu.py: the snapped words are the reference's
     for the labels the call returns, and labels / scores / text are those of the same call without a lexicon."""
     import aocr
-    from test_step_gpu import make
+    from model_harness import make
     B, W = 32, 100
     m, O, ocfg, P0, st, batch = make(dict(enc_hidden=32, enc_layers=1, dec_layers=2, input_feed=True), B=B, W=W, maxlen=8, compute="f32",
                                      max_decoder_l=12, max_beam=5)

@@ -189,7 +189,7 @@ RECTS = [(4, 14, 6, 40), (4, 14, 50, 70), (4, 14, 90, 139), (24, 33, 3, 20), (24
 
 def test_recognize_page_orient(cuda):
     import aocr
-    from test_step_gpu import make
+    from model_harness import make
     B, W = 32, 100
     m, O, ocfg, P0, st, _ = make(dict(enc_hidden=32, enc_layers=1, dec_layers=2, input_feed=True), B=B, W=W, maxlen=8, compute="f32",
                                  max_decoder_l=12, max_beam=5)

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from cdecl import defines
-from test_step_gpu import make
+from model_harness import make
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

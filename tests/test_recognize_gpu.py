@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_step_gpu import make
+from model_harness import make
 
 pytestmark = pytest.mark.gpu
 

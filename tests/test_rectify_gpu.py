@@ -194,7 +194,7 @@ NEW_FIELDS = ("rectified", "rectify_quad", "rectify_size", "rectify_area", "phot
 
 def test_recognize_page_rectify(cuda):
     import aocr
-    from test_step_gpu import make
+    from model_harness import make
     m, O, ocfg, P0, st, _ = make(dict(enc_hidden=32, enc_layers=1, dec_layers=2, input_feed=True), B=32, W=100, maxlen=8, compute="f32",
                                  max_decoder_l=12, max_beam=5)
     m.set_parameters(O.sharpen_params(P0), st)

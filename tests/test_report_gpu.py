@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_step_gpu import CASES, make
+from model_harness import CASES, make
 
 pytestmark = pytest.mark.gpu
 

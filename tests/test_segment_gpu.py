@@ -327,7 +327,7 @@ def _first_eos_text(aocr, labels):
 
 def test_recognize_page(cuda):
     import aocr
-    from test_step_gpu import make
+    from model_harness import make
     B, W = 32, 100
     m, O, ocfg, P0, st, _ = make(dict(enc_hidden=32, enc_layers=1, dec_layers=2, input_feed=True), B=B, W=W, maxlen=8, compute="f32",
                                  max_decoder_l=12, max_beam=5)
@@ -388,7 +388,7 @@ def test_recognize_page_in_chunks(cuda):
     """a bucket with more boxes than batch_size: the 8 boxes of the atlas page at one width through a batch_size-3 model, three chunks
     (3, 3, 2), scattered back in reading order; and bucketed widths, where a bucket of 3 is one full chunk."""
     import aocr
-    from test_step_gpu import make
+    from model_harness import make
     B, W = 3, 100
     m, O, ocfg, P0, st, _ = make(dict(enc_hidden=32, enc_layers=1, dec_layers=2, input_feed=True), B=B, W=W, maxlen=8, compute="f32",
                                  max_decoder_l=12, max_beam=5)

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_step_gpu import make, relerr, cosine
+from model_harness import make, relerr, cosine
 from tol import check_logits
 
 pytestmark = pytest.mark.gpu

@@ -1,6 +1,6 @@
 """GPU: every branch of the bf16 fused recurrent-step launchers (csrc/ops_gemm.hip: launch_small_gates_fwd_hh/_h, launch_small_hh/_h,
 launch_small_gates_bwd_hh/_h, gates_elem_bwd, big_step_store, big_step_gates_fwd) against an exact reference, called directly through
-tests/libkprobe.so.  Method and helpers of tests/test_kernels_bf16_gpu.py: sentinel tails (and here the padding columns of every strided
+tests/libkprobe.so.  Method of tests/test_kernels_bf16_gpu.py, helpers of tests/kernel_harness.py: sentinel tails (and here the padding columns of every strided
 buffer) must survive every call, and every case asserts the kernel it reached from the AOCR_TRACE dispatch line.
 
 Operands.  A-side values are small integers, B-side values small integers times a power of two q: all exact in bf16, every product and
@@ -41,25 +41,18 @@ import numpy as np
 import pytest
 import torch
 
-from test_kernels_bf16_gpu import (EP_ACCUM, EP_RELU, EP_TANH, SENT, Buf, _switches, bf, bound, expect, ints, kp, rnd,  # noqa: F401
-                                   setenv, trace_of)
+from kernel_harness import _switches  # noqa: F401  this import IS how the autouse fixture reaches the module (tests/test_kernel_harness_cpu.py checks it)
+from kernel_harness import (EP_ACCUM, EP_RELU, EP_TANH, SENT, TOL_BWD, TOL_CELL, Buf, Drop, Mat, bf, bound, call, expect, i32, i64, ints, out,
+                            ratio, rb, rnd, setenv, trace_of, vp)
 
 pytestmark = pytest.mark.gpu
 
 Q = 2.0 ** -4                       # B-side quantum of the gate cases
-TOL_CELL = 2e-5                     # test_ops_gpu.py::test_lstm_cell, exact-fp32 cell
-TOL_BWD = 5e-5                      # its backward part (times max(1, max |dh|))
-JUNK = 3.0                          # what surrounds every operand window (exact in bf16: a wrong stride changes sums)
 HH, HF = "launch_small_bf16_hh", "launch_small_bf16"
-vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
 
 
 class Operand(C.Structure):
     _fields_ = [("p0", vp), ("ld0", i64), ("K0", i32), ("p1", vp), ("ld1", i64), ("K1", i32), ("rows", i32)]
-
-
-class Drop(C.Structure):
-    _fields_ = [("base", C.c_ulonglong), ("thr", C.c_ulonglong), ("scale", C.c_float), ("off", C.c_longlong)]
 
 
 class Store(C.Structure):
@@ -79,59 +72,6 @@ class GatesBwd(C.Structure):
                 ("dz", vp), ("lddz", i64), ("dc_out", vp), ("lddco", i64), ("dzb", vp), ("lddzb", i64), ("drop", Drop), ("gil", i32)]
 
 
-_SIGS = False
-
-
-def lib():
-    global _SIGS
-    k = kp()
-    if not _SIGS:
-        for n in ("kp_small_gates_fwd_hh", "kp_small_gates_fwd_h", "kp_small_hh", "kp_small_h", "kp_small_gates_bwd_hh", "kp_small_gates_bwd_h"):
-            getattr(k, n).argtypes = [vp, i32, vp, i32, i32]
-        k.kp_gates_elem_bwd.argtypes = [vp, vp, i32, i32]
-        k.kp_big_step_store.argtypes = [vp, vp, i32, i32, vp]
-        k.kp_big_step_gates_fwd.argtypes = [vp, vp, i32, i32, vp, C.c_size_t, vp]
-        for n in ("kp_small_gates_fwd_hh", "kp_small_gates_fwd_h", "kp_small_hh", "kp_small_h", "kp_small_gates_bwd_hh", "kp_small_gates_bwd_h",
-                  "kp_gates_elem_bwd", "kp_big_step_store", "kp_big_step_gates_fwd"):
-            getattr(k, n).restype = i32
-        _SIGS = True
-    return k
-
-
-def call(name, *args):
-    rc = getattr(lib(), name)(C.c_void_p(torch.cuda.current_stream().cuda_stream), *args)
-    assert rc == 0, f"{name}: hipGetLastError() = {rc}"
-
-
-class Mat:
-    """A [rows][cols] window at column `off` of a device buffer with row stride ld = off + cols + pad (Buf: sentinel tail behind it).
-    data: the window's content, the rest is JUNK (an operand); no data: everything is `fill` (an output)."""
-
-    def __init__(self, rows, cols, dtype=torch.float32, data=None, pad=8, off=0, fill=SENT):
-        self.rows, self.cols, self.off, self.ld = rows, cols, off, off + cols + pad
-        host = torch.full((rows, self.ld), JUNK if data is not None else fill, dtype=torch.float64)
-        if data is not None:
-            host[:, off:off + cols] = data.double()
-        self.buf = Buf(host, dtype)
-        self.init = self.buf.cpu().clone()
-        self.addr = self.buf.full.data_ptr() + off * self.buf.full.element_size()
-
-    def win(self):
-        return self.buf.cpu()[:, self.off:self.off + self.cols]
-
-    def check(self, what):
-        """nothing outside the window was written: the padding columns and the tail"""
-        self.buf.check_tail(what)
-        now = self.buf.cpu().clone()
-        now[:, self.off:self.off + self.cols] = self.init[:, self.off:self.off + self.cols]
-        assert torch.equal(now.view(torch.int16 if now.dtype == torch.bfloat16 else torch.int32),
-                           self.init.view(torch.int16 if now.dtype == torch.bfloat16 else torch.int32)), f"{what}: write outside its columns"
-
-
-def out(rows, cols, dtype=torch.float32, pad=8, off=0):
-    return Mat(rows, cols, dtype, None, pad, off, SENT if dtype == torch.float32 else -3.0)
-
-
 def operand(t, segs, dtype, vary=0):
     """t [rows][K] as one or two K segments with different row strides -> (Operand, the Mats that own the memory)."""
     o, K0 = Operand(), segs[0]
@@ -143,11 +83,6 @@ def operand(t, segs, dtype, vary=0):
         o.p1, o.ld1, o.K1 = m1.addr, m1.ld, segs[1]
         mats.append(m1)
     return o, mats
-
-
-def rb(t):
-    """round to bf16, as float32"""
-    return t.float().to(torch.bfloat16).float()
 
 
 def drop_spec(p, seed, step, site, off, n):
@@ -162,11 +97,6 @@ def drop_spec(p, seed, step, site, off, n):
 
 def no_drop():
     return Drop(0, 0, 1.0, 0)
-
-
-def ratio(got, ref, tol):
-    """largest |got - ref| / tol (tol a number or a tensor)"""
-    return ((got.double() - ref).abs() / tol).max().item()
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -41,7 +41,7 @@ def test_save_t7_round_trip(cuda, tmp_path, layout):
     """Model.save to Torch7 serialization in the reference's own layout (the five nets as nn / nngraph trees, model.lua:720-725) and in
     the flat layout; Model.load reads both back bit for bit."""
     import aocr
-    from test_step_gpu import CASES, make
+    from model_harness import CASES, make
     m, O, ocfg, P, st, batch = make(CASES[0], B=4, W=36, maxlen=5)
     m.train_forward_backward(batch); m.sgd_step()
     m.global_step = 17; m.optim_state = {"learningRate": 0.05}

@@ -1,6 +1,7 @@
 """GPU: the loss, token-sum, optimizer, weight-shadow, beam-search and small elementwise kernels (csrc/ops_misc.hip; project_loss_kernel of
 csrc/ops_gemm.hip) against the references of tests/tail_ref.py (checked on the CPU by tests/test_tail_ref_cpu.py), called directly through
-tests/libkprobe.so.  Method and helpers of tests/test_kernels_bf16_gpu.py and tests/test_step_kernels_bf16_gpu.py: every output and every
+tests/libkprobe.so.  Method of tests/test_kernels_bf16_gpu.py and tests/test_step_kernels_bf16_gpu.py, helpers of tests/kernel_harness.py
+(call_sync: every call is followed by a device synchronisation): every output and every
 += target has a sentinel tail, every strided buffer padding columns, and both must survive each call; accumulating outputs start from a
 non-zero buffer.
 
@@ -39,12 +40,11 @@ import pytest
 import torch
 
 import tail_ref as R
-from test_kernels_bf16_gpu import SENT, Buf, _switches, bf, bound, ints, kp, rnd  # noqa: F401
-from test_step_kernels_bf16_gpu import Drop, Mat
+from kernel_harness import _switches  # noqa: F401  this import IS how the autouse fixture reaches the module (tests/test_kernel_harness_cpu.py checks it)
+from kernel_harness import SENT, Buf, Drop, Mat, bf, bound, call_sync, i32, i64, ints, kp, rnd, sz, vp
 
 pytestmark = pytest.mark.gpu
 
-vp, i32, i64, sz, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_float
 TOL_LOGP, TOL_NLL, TOL_DLOGITS, LOSS_SCALE = 1e-5, 1e-5, 1e-6, 1.0 / 64      # test_ops_gpu.py::test_logsoftmax_nll
 TOL_SCORE = 1e-5                                                              # test_ops_gpu.py::test_beam_select
 ISENT = -7
@@ -57,58 +57,6 @@ class Trie(C.Structure):
 class DecInit(C.Structure):
     _fields_ = [("c0", vp * 4), ("h0", vp * 4), ("hb", vp * 4), ("feed0", vp), ("outb", vp), ("cfw", vp), ("cbw", vp), ("hfw", vp), ("hbw", vp),
                 ("B", i32), ("He", i32), ("Hd", i32), ("Ld", i32), ("copy_h", i32)]
-
-
-_SIG = {
-    "kp_logsoftmax_nll": [vp, vp, i64, vp, i64, i64, i32, vp, vp, vp, i64, i32, f32],
-    "kp_project_loss_ok": [i32, i32, i32],
-    "kp_project_loss": [vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, i64, i32, i32, i32, i32, f32],
-    "kp_gemm": [vp, i32, vp, i64, i32, vp, i64, i32, vp, i64, i32, i32, i32, vp, vp, i32, vp],
-    "kp_sum_to_scalar": [vp, vp, i64, vp],
-    "kp_gold_scores": [vp, vp, vp, i32, i32],
-    "kp_segsum_supported": [i32, i32, i32],
-    "kp_segsum_by_token": [vp, vp, i64, vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, i32, vp, vp],
-    "kp_embedding_gather": [vp, vp, vp, i64, i64, vp, i32, i32, i32],
-    "kp_embedding_scatter_accum": [vp, vp, vp, i64, i64, vp, i32, i32, i32, i32],
-    "kp_cl_err_latch": [], "kp_cl_err_sticky": [],
-    "kp_sgd_clip_update": [vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, i32],
-    "kp_adadelta_update": [vp, vp, vp, vp, vp, i64, f32, f32, f32, vp, vp, vp, i32],
-    "kp_step_snapshot": [vp, vp, vp, i32, vp],
-    "kp_shadow_jobs": [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp],
-    "kp_beam_select": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp, vp],
-    "kp_project_select": [vp, vp, i64, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp],
-    "kp_gather_beam_rows_many": [vp, i32, vp, vp, i64, vp, i32, i32, i32, i32, vp],
-    "kp_gather_beam_rows": [vp, vp, i64, vp, i64, vp, i32, i32, i32, i32],
-    "kp_token_rows": [vp, vp, vp, i64, vp, i32, i32],
-    "kp_beam_backtrace": [vp, vp, vp, vp, vp, vp, i32, i32, i32],
-    "kp_recognize_gather": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32],
-    "kp_dec_init": [vp, vp],
-    "kp_dpre_tanh": [vp, vp, vp, vp, vp, i64, vp, vp],
-    "kp_dropout_apply": [vp, vp, vp, vp, i64, vp],
-    "kp_dropout_apply_b": [vp, vp, vp, vp, i64, vp],
-    "kp_zero_many": [vp, i32, vp, vp],
-    "kp_copy2d_bf16": [vp, vp, i64, vp, i64, i32, i32],
-}
-_SIZES = {"kp_segsum_index_ints": [i32, i32], "kp_sgd_scratch_bytes": [], "kp_shadow_job_bytes": []}
-_READY = False
-
-
-def lib():
-    global _READY
-    k = kp()
-    if not _READY:
-        for n, a in _SIG.items():
-            getattr(k, n).argtypes, getattr(k, n).restype = a, i32
-        for n, a in _SIZES.items():
-            getattr(k, n).argtypes, getattr(k, n).restype = a, sz
-        _READY = True
-    return k
-
-
-def call(name, *args):
-    rc = getattr(lib(), name)(vp(torch.cuda.current_stream().cuda_stream), *args)
-    assert rc == 0, f"{name}: hipGetLastError() = {rc}"
-    torch.cuda.synchronize()
 
 
 _KEEP = []
@@ -180,7 +128,7 @@ def counted_tokens(rows, V, counts, seed):
 @pytest.mark.parametrize("with_db2", [True, False])
 def test_segsum_by_token(L, B, ncols, V, E, counts, model_strides, with_db2):
     rows = L * B
-    assert lib().kp_segsum_supported(ncols, V, E) == 1
+    assert kp().kp_segsum_supported(ncols, V, E) == 1
     tok = counted_tokens(rows, V, counts, seed=L)
     hist = torch.bincount(tok, minlength=V + 1)
     assert all(int(hist[t]) == c for t, c in counts.items())
@@ -192,14 +140,14 @@ def test_segsum_by_token(L, B, ncols, V, E, counts, model_strides, with_db2):
     S_ref = R.token_sums(dz, tok, V)
     db_ref, dlk_ref, dW_ref = R.token_sum_products(S_ref, W, lookup, E)
     dzm, Wm, lk = Mat(rows, ncols, data=dz), Mat(ncols, E, data=W, pad=8), Buf(lookup)
-    S, index = Buf((V, ncols), fill=SENT), iout(lib().kp_segsum_index_ints(rows, V))
+    S, index = Buf((V, ncols), fill=SENT), iout(kp().kp_segsum_index_ints(rows, V))
     db1, db2, dlk = Buf(init[0]), Buf(init[1]), Buf(init[2])
     dW = Mat(ncols, E, pad=8)
     dW.buf.t[:, :E] = init[3].cuda()
     dW.init = dW.buf.cpu().clone()
     assert dW.ld == Wm.ld > E
-    call("kp_segsum_by_token", P(dzm), dzm.ld, P(ibuf(stored)), st, sb, L, B, ncols, V, P(S), P(index), P(db1), P(db2) if with_db2 else None, P(Wm),
-         Wm.ld, P(lk), E, P(dlk), P(dW))
+    call_sync("kp_segsum_by_token", P(dzm), dzm.ld, P(ibuf(stored)), st, sb, L, B, ncols, V, P(S), P(index), P(db1), P(db2) if with_db2 else None, P(Wm),
+              Wm.ld, P(lk), E, P(dlk), P(dW))
     for b, nm in ((S, "S"), (index, "index"), (db1, "db1"), (db2, "db2"), (dlk, "dlookup")):
         b.check_tail(nm)
     dW.check("dW")
@@ -223,11 +171,11 @@ def test_embedding_scatter_and_gather(L, B, E):
     stored, st, sb = layout(tok, L, B, E != 256)
     demb, init, table = ints(rows, E, seed=1, lo=-2, hi=2), ints(V, E, seed=2), ints(V, E, seed=3)
     d, dt, tokd = Buf(demb), Buf(init), ibuf(stored)
-    call("kp_embedding_scatter_accum", P(d), P(tokd), st, sb, P(dt), L, B, E, V)
+    call_sync("kp_embedding_scatter_accum", P(d), P(tokd), st, sb, P(dt), L, B, E, V)
     dt.check_tail("dtable")
     same(dt.cpu(), init + R.embedding_scatter(demb, tok, V), "dtable")
     out = Buf((rows, E), fill=SENT)
-    call("kp_embedding_gather", P(Buf(table)), P(tokd), st, sb, P(out), L, B, E)
+    call_sync("kp_embedding_gather", P(Buf(table)), P(tokd), st, sb, P(out), L, B, E)
     out.check_tail("embedding_gather")
     same(out.cpu(), R.token_rows(table, tok), "embedding_gather")
 
@@ -247,7 +195,7 @@ def test_gather_beam_rows_many(n, kin_is_k, width):
     dsts = [Mat(B * k, width, pad=ld - width) for _ in range(n)]
     dstb = [Mat(B * k, width, torch.bfloat16, pad=ld - width, fill=-3.0) if i % 2 == 0 else None for i in range(n)]
     arr = lambda ms: (vp * n)(*[m.addr if m is not None else None for m in ms])
-    call("kp_gather_beam_rows_many", n, arr(srcs), arr(dsts), ld, P(ibuf(parents)), B, kin, k, width, arr(dstb))
+    call_sync("kp_gather_beam_rows_many", n, arr(srcs), arr(dsts), ld, P(ibuf(parents)), B, kin, k, width, arr(dstb))
     for i in range(n):
         ref = R.gather_rows(srcs[i].win(), parents, B, kin, k)
         dsts[i].check(f"dst {i}")
@@ -256,7 +204,7 @@ def test_gather_beam_rows_many(n, kin_is_k, width):
             dstb[i].check(f"dstb {i}")
             assert torch.equal(dstb[i].win().view(torch.int16), bf(ref)), f"bf16 copy {i}"
     one = Mat(B * k, width, pad=5)                                                          # the single-tensor form, another destination stride
-    call("kp_gather_beam_rows", P(srcs[0]), ld, P(one), one.ld, P(ibuf(parents)), B, kin, k, width)
+    call_sync("kp_gather_beam_rows", P(srcs[0]), ld, P(one), one.ld, P(ibuf(parents)), B, kin, k, width)
     one.check("gather_beam_rows")
     assert torch.equal(one.win(), R.gather_rows(srcs[0].win(), parents, B, kin, k))
 
@@ -268,7 +216,7 @@ def test_token_rows():
     spaced = torch.full((Rr, stride), 99, dtype=torch.int64)
     spaced[:, 0] = tok
     dst = Buf((Rr, width), fill=SENT)
-    call("kp_token_rows", P(Buf(table)), P(ibuf(spaced)), stride, P(dst), Rr, width)
+    call_sync("kp_token_rows", P(Buf(table)), P(ibuf(spaced)), stride, P(dst), Rr, width)
     dst.check_tail("token_rows")
     same(dst.cpu(), R.token_rows(table, tok), "token_rows")
 
@@ -305,7 +253,7 @@ def test_backtrace_and_recognize_gather(k):
         assert R.winner(final[1])[0] == 0 and R.winner(final[2])[0] == k - 1
     labels, scores = iout(B * Lt), Buf((B,), fill=SENT)
     ht, hp, fs = ibuf(hist_tok), ibuf(hist_par), Buf(final)
-    call("kp_beam_backtrace", P(ht), P(hp), P(fs), P(labels), P(scores), Lt, B, k)
+    call_sync("kp_beam_backtrace", P(ht), P(hp), P(fs), P(labels), P(scores), Lt, B, k)
     labels.check_tail("labels"); scores.check_tail("scores")
     assert torch.equal(labels.cpu().long().reshape(B, Lt), labels_ref)
     same(scores.cpu(), scores_ref, "scores")
@@ -316,12 +264,12 @@ def test_backtrace_and_recognize_gather(k):
         cl_ref, at_ref = R.recognize_gather(lab, par[1], final, sc_hist, attn_hist)
         assert float(cl_ref[3, 3:].abs().max()) == 0.0 and float(at_ref[3, 3:].abs().max()) == 0.0 and float(at_ref[3, 2].abs().max()) > 0
         cl, at = Buf((B, Lt), fill=SENT), Buf((B, Lt, T), fill=SENT)
-        call("kp_recognize_gather", P(ibuf(lab)), P(par[0]), P(fs), P(Buf(sc_hist)), P(Buf(attn_hist)), P(cl), P(at), Lt, B, k, T)
+        call_sync("kp_recognize_gather", P(ibuf(lab)), P(par[0]), P(fs), P(Buf(sc_hist)), P(Buf(attn_hist)), P(cl), P(at), Lt, B, k, T)
         cl.check_tail("char_logp"); at.check_tail("attn")
         same(at.cpu(), at_ref, "attn")
         close(cl.cpu(), cl_ref, 2e-6, "char_logp")                                        # one fp32 subtraction of scores below 8
         only = Buf((B, Lt, T), fill=SENT)
-        call("kp_recognize_gather", P(ibuf(lab)), P(par[0]), P(fs), P(Buf(sc_hist)), P(Buf(attn_hist)), None, P(only), Lt, B, k, T)
+        call_sync("kp_recognize_gather", P(ibuf(lab)), P(par[0]), P(fs), P(Buf(sc_hist)), P(Buf(attn_hist)), None, P(only), Lt, B, k, T)
         same(only.cpu(), at_ref, "attn alone")
 
 
@@ -343,17 +291,17 @@ def test_shadow_jobs(split):
         wts.append(Mat(Cc, Rr, torch.bfloat16, pad=4 if i != 2 else 1, fill=-3.0))
     assert ws[3][0] % 16 == 4
     n = len(pieces)
-    jobs = Buf((n * lib().kp_shadow_job_bytes(),), torch.uint8, fill=0)
+    jobs = Buf((n * kp().kp_shadow_job_bytes(),), torch.uint8, fill=0)
     A = lambda vals, t=vp: (t * n)(*vals)
     args = [n, A([w[0] for w in ws]), A([m.addr for m in wbs]), A([m.addr for m in wts]), A([w[1] for w in ws], i64), A([m.ld for m in wbs], i64),
             A([m.ld for m in wts], i64), A([p[0] for p in pieces], i32), A([p[1] for p in pieces], i32), P(jobs)]
     total = i32(-1)
     tiles = sum(math.ceil(p[0] / 32) * math.ceil(p[1] / 32) for p in pieces)
     if split:
-        call("kp_shadow_jobs", *args, 0, 5, C.byref(total))                               # 4 tiles of piece 0 + the first of piece 1
-        call("kp_shadow_jobs", *args, 5, -1, C.byref(total))
+        call_sync("kp_shadow_jobs", *args, 0, 5, C.byref(total))                               # 4 tiles of piece 0 + the first of piece 1
+        call_sync("kp_shadow_jobs", *args, 5, -1, C.byref(total))
     else:
-        call("kp_shadow_jobs", *args, 0, -1, C.byref(total))
+        call_sync("kp_shadow_jobs", *args, 0, -1, C.byref(total))
     assert total.value == tiles == 4 + 6 + 1 + 3
     jobs.check_tail("job table")
     for i in range(n):
@@ -381,7 +329,7 @@ def test_dec_init(Hd, copy_h, shadows):
     a.feed0, a.outb = feed.full.data_ptr(), outb.full.data_ptr() if shadows else None
     a.cfw, a.cbw, a.hfw, a.hbw = (s.full.data_ptr() for s in sb)
     a.B, a.He, a.Hd, a.Ld, a.copy_h = B, He, Hd, Ld, copy_h
-    call("kp_dec_init", C.byref(a))
+    call_sync("kp_dec_init", C.byref(a))
     c_ref, h_ref = R.dec_init(*[s.float() for s in src], Hd, Ld, copy_h)
     for l in range(Ld):
         for b, nm in ((c0[l], "c0"), (h0[l], "h0"), (hb[l], "hb")):
@@ -409,7 +357,7 @@ def test_zero_many():
     base = buf.full.data_ptr()
     assert base % 16 == 0
     n = len(sizes)
-    call("kp_zero_many", n, (vp * n)(*[base + s for s in starts]), (sz * n)(*sizes))
+    call_sync("kp_zero_many", n, (vp * n)(*[base + s for s in starts]), (sz * n)(*sizes))
     buf.check_tail("zero_many")
     ref = torch.full((pos,), 0xA5, dtype=torch.uint8)
     for s, b in zip(starts, sizes):
@@ -422,7 +370,7 @@ def test_copy2d_bf16(cols):
     rows = 37
     src = Mat(rows, cols, data=ints(rows, cols, seed=1, lo=-200, hi=200) * (1.0 + 2.0 ** -9), pad=4)
     dst = Mat(rows, cols, torch.bfloat16, pad=8 if cols == 64 else 3, fill=-3.0)
-    call("kp_copy2d_bf16", P(src), src.ld, P(dst), dst.ld, rows, cols)
+    call_sync("kp_copy2d_bf16", P(src), src.ld, P(dst), dst.ld, rows, cols)
     dst.check("copy2d_bf16")
     assert torch.equal(dst.win().view(torch.int16), bf(src.win()))
 
@@ -437,17 +385,17 @@ def test_dropout_kernels():
     x = vals[torch.randint(0, 5, (n,), generator=torch.Generator().manual_seed(1))]
     ref = x.double() * mk
     dst, dstb = Buf((n,), fill=SENT), Buf((n,), torch.bfloat16, fill=-3.0)
-    call("kp_dropout_apply", P(Buf(x)), P(dst), P(dstb), n, C.byref(d))
+    call_sync("kp_dropout_apply", P(Buf(x)), P(dst), P(dstb), n, C.byref(d))
     dst.check_tail("dropout dst"); dstb.check_tail("dropout dstb")
     same(dst.cpu(), ref, "dropout_apply")
     assert torch.equal(dstb.cpu().view(torch.int16), bf(ref))
     dst2, dstb2 = Buf((n,), fill=SENT), Buf((n,), torch.bfloat16, fill=-3.0)
-    call("kp_dropout_apply_b", P(Buf(x, torch.bfloat16)), P(dst2), P(dstb2), n, C.byref(d))
+    call_sync("kp_dropout_apply_b", P(Buf(x, torch.bfloat16)), P(dst2), P(dstb2), n, C.byref(d))
     dst2.check_tail("dropout_b dst"); dstb2.check_tail("dropout_b dstb")
     same(dst2.cpu(), ref, "dropout_apply_b")
     assert torch.equal(dstb2.cpu().view(torch.int16), bf(ref))
     only_b = Buf((n,), torch.bfloat16, fill=-3.0)
-    call("kp_dropout_apply", P(Buf(x)), None, P(only_b), n, C.byref(d))
+    call_sync("kp_dropout_apply", P(Buf(x)), None, P(only_b), n, C.byref(d))
     assert torch.equal(only_b.cpu().view(torch.int16), bf(ref))
     # d pre: `out` holds the masked value (0, +-1, +-2 -> unmasked 0, +-0.5, +-1); every result is exact
     g1, g2 = ints(n, seed=2, lo=-3, hi=3), ints(n, seed=3, lo=-3, hi=3)
@@ -456,12 +404,12 @@ def test_dropout_kernels():
     for second in (g2, None):
         ref_d = R.dpre(g1, second, out, mk)
         dp, dpb = Buf((n,), fill=SENT), Buf((n,), torch.bfloat16, fill=-3.0)
-        call("kp_dpre_tanh", P(Buf(g1)), P(Buf(second)) if second is not None else None, P(Buf(out)), P(dp), n, P(dpb), C.byref(d))
+        call_sync("kp_dpre_tanh", P(Buf(g1)), P(Buf(second)) if second is not None else None, P(Buf(out)), P(dp), n, P(dpb), C.byref(d))
         dp.check_tail("dpre"); dpb.check_tail("dpreb")
         same(dp.cpu(), ref_d, "dpre_tanh with a mask")
         assert torch.equal(dpb.cpu().view(torch.int16), bf(ref_d))
     plain = Buf((n,), fill=SENT)
-    call("kp_dpre_tanh", P(Buf(g1)), P(Buf(g2)), P(Buf(half)), P(plain), n, None, None)
+    call_sync("kp_dpre_tanh", P(Buf(g1)), P(Buf(g2)), P(Buf(half)), P(plain), n, None, None)
     same(plain.cpu(), R.dpre(g1, g2, half), "dpre_tanh")
 
 
@@ -490,8 +438,8 @@ def test_logsoftmax_nll(L, Bt, V, ld, model_strides):
     tok = ibuf(stored)
     for skip in (None, "logp", "dlogits", "nll"):
         lp, dl, nll = Buf((rows, V), fill=SENT), Buf((rows, ld), fill=SENT), Buf((rows,), fill=SENT)
-        call("kp_logsoftmax_nll", P(xm), ld, P(tok), st, sb, Bt, P(lp) if skip != "logp" else None, P(dl) if skip != "dlogits" else None,
-             P(nll) if skip != "nll" else None, rows, V, LOSS_SCALE)
+        call_sync("kp_logsoftmax_nll", P(xm), ld, P(tok), st, sb, Bt, P(lp) if skip != "logp" else None, P(dl) if skip != "dlogits" else None,
+                  P(nll) if skip != "nll" else None, rows, V, LOSS_SCALE)
         for b, nm in ((lp, "logp"), (dl, "dlogits"), (nll, "nll")):
             b.check_tail(nm)
             if skip == nm:
@@ -510,8 +458,8 @@ def test_logsoftmax_nll(L, Bt, V, ld, model_strides):
             assert float(d[y == R.PAD].abs().max()) == 0.0
     nl = Buf(nll_ref.reshape(L, Bt))
     total, gold = Buf((1,), fill=SENT), Buf((Bt,), fill=SENT)
-    call("kp_sum_to_scalar", P(nl), rows, P(total))
-    call("kp_gold_scores", P(nl), P(gold), L, Bt)
+    call_sync("kp_sum_to_scalar", P(nl), rows, P(total))
+    call_sync("kp_gold_scores", P(nl), P(gold), L, Bt)
     total.check_tail("sum"); gold.check_tail("gold")
     f = nl.cpu().double()
     close(total.cpu(), f.sum().reshape(1), 1e-6 * max(1.0, float(f.sum())), "sum_to_scalar")          # fp64 sum, one rounding to fp32
@@ -521,7 +469,7 @@ def test_logsoftmax_nll(L, Bt, V, ld, model_strides):
 @pytest.mark.parametrize("V", [2, 39, 40])
 @pytest.mark.parametrize("Hd", [64, 128])
 def test_project_loss(V, Hd):
-    k = lib()
+    k = kp()
     assert k.kp_project_loss_ok(1045, V, Hd) == 1
     assert k.kp_project_loss_ok(1045, 41, Hd) == 0 and k.kp_project_loss_ok(1045, V, 96) == 0 and k.kp_project_loss_ok(1023, V, Hd) == 0
     Bt, L, ld, rows_alloc = 11, 95, 40, 1056
@@ -538,7 +486,7 @@ def test_project_loss(V, Hd):
     def outputs():
         return Mat(rows_alloc, V, pad=ld - V), Mat(rows_alloc, ld, pad=0), Buf((rows_alloc,), fill=SENT), Buf((rows_alloc, Hd), fill=SENT)
     logits, dlog, nll, dout = outputs()
-    call("kp_project_loss", P(om), om.ld, P(wod), P(bod), P(logits), P(dlog), ld, P(nll), P(dout), P(tok), st, sb, Bt, rows, V, Hd, LOSS_SCALE)
+    call_sync("kp_project_loss", P(om), om.ld, P(wod), P(bod), P(logits), P(dlog), ld, P(nll), P(dout), P(tok), st, sb, Bt, rows, V, Hd, LOSS_SCALE)
     logits.check("logits"); dlog.check("dlogits"); nll.check_tail("nll"); dout.check_tail("dout")
     for t, nm in ((logits.win(), "logits"), (dlog.win(), "dlogits"), (dout.cpu(), "dout"), (nll.cpu(), "nll")):
         assert float((t[rows:] - SENT).abs().max()) == 0.0, f"{nm}: rows past the end written"
@@ -557,10 +505,10 @@ def test_project_loss(V, Hd):
     # the contract of ops.h: bit-identical to gemm + logsoftmax_nll + gemm on the same operands
     l2, d2, n2, o2 = outputs()
     rc = i32(-1)
-    call("kp_gemm", 1, P(om), om.ld, 1, P(wod), Hd, 1, P(l2), ld, rows, V, Hd, P(bod), None, 0, C.byref(rc))
+    call_sync("kp_gemm", 1, P(om), om.ld, 1, P(wod), Hd, 1, P(l2), ld, rows, V, Hd, P(bod), None, 0, C.byref(rc))
     assert rc.value == 0
-    call("kp_logsoftmax_nll", P(l2), ld, P(tok), st, sb, Bt, None, P(d2), P(n2), rows, V, LOSS_SCALE)
-    call("kp_gemm", 1, P(d2), ld, 1, P(wod), Hd, 0, P(o2), Hd, rows, Hd, V, None, None, 0, C.byref(rc))
+    call_sync("kp_logsoftmax_nll", P(l2), ld, P(tok), st, sb, Bt, None, P(d2), P(n2), rows, V, LOSS_SCALE)
+    call_sync("kp_gemm", 1, P(d2), ld, 1, P(wod), Hd, 0, P(o2), Hd, rows, Hd, V, None, None, 0, C.byref(rc))
     assert rc.value == 0
     bits = lambda t: t.contiguous().view(torch.int32)
     assert torch.equal(bits(logits.win()[:rows]), bits(l2.win()[:rows])), "logits differ from gemm"
@@ -577,8 +525,8 @@ N_PARAMS = 5010
 
 
 def sgd_call(p, g, lr, clip, err=None, bn=None, snap=None, bn_n=0, norms=None):
-    scratch = Buf((lib().kp_sgd_scratch_bytes(),), torch.uint8, fill=0)
-    call("kp_sgd_clip_update", P(p), P(g), (i64 * 6)(*OFF), lr, clip, P(norms), P(scratch), P(err), P(bn), P(snap), bn_n)
+    scratch = Buf((kp().kp_sgd_scratch_bytes(),), torch.uint8, fill=0)
+    call_sync("kp_sgd_clip_update", P(p), P(g), (i64 * 6)(*OFF), lr, clip, P(norms), P(scratch), P(err), P(bn), P(snap), bn_n)
     scratch.check_tail("sgd scratch")
 
 
@@ -617,7 +565,7 @@ def test_sgd_clip_update_random():
 
 @pytest.mark.parametrize("opt", ["sgd", "adadelta"])
 def test_optimizer_skip_path(opt):
-    latch, sticky, bn_n = lib().kp_cl_err_latch(), lib().kp_cl_err_sticky(), 300
+    latch, sticky, bn_n = kp().kp_cl_err_latch(), kp().kp_cl_err_sticky(), 300
     p0, g0 = rnd(N_PARAMS, seed=5).float(), (rnd(N_PARAMS, seed=6) * 0.3).float()
     var0, acc0 = rnd(N_PARAMS, seed=7).abs().float(), rnd(N_PARAMS, seed=8).abs().float()
     bn0, snap0 = rnd(bn_n, seed=9).float(), rnd(bn_n, seed=10).float()
@@ -630,7 +578,7 @@ def test_optimizer_skip_path(opt):
         if opt == "sgd":
             sgd_call(p, g, 0.1, 5.0, err, bn, snap, bn_n)
         else:
-            call("kp_adadelta_update", P(p), P(g), P(var), P(acc), N_PARAMS, 0.9, 1e-6, 0.0, P(err), P(bn), P(snap), bn_n)
+            call_sync("kp_adadelta_update", P(p), P(g), P(var), P(acc), N_PARAMS, 0.9, 1e-6, 0.0, P(err), P(bn), P(snap), bn_n)
         for b, nm in ((p, "params"), (g, "grads"), (var, "var"), (acc, "acc"), (bn, "bn_state"), (snap, "bn_snap"), (err, "err")):
             b.check_tail(nm)
 
@@ -657,21 +605,21 @@ def test_optimizer_skip_path(opt):
 
 
 def test_step_snapshot():
-    sticky, bn_n = lib().kp_cl_err_sticky(), 300
+    sticky, bn_n = kp().kp_cl_err_sticky(), 300
     bn0 = rnd(bn_n, seed=11).float()
     for code in (0, 5):
         bn, snap = Buf(bn0), Buf((bn_n,), fill=SENT)
         words = torch.zeros(64, dtype=torch.int32)
         words[0], words[sticky] = code, 9
         err = ibuf(words)
-        call("kp_step_snapshot", P(bn), P(snap), bn_n, P(err))
+        call_sync("kp_step_snapshot", P(bn), P(snap), bn_n, P(err))
         snap.check_tail("bn_snap"); err.check_tail("err")
         assert torch.equal(snap.cpu(), bn0) and torch.equal(bn.cpu(), bn0)
         e0, s = R.snapshot_rule(code, 9)
         w = err.cpu()
         assert (int(w[0]), int(w[sticky])) == (e0, s) and int(w.abs().sum()) == s
     snap = Buf((bn_n,), fill=SENT)
-    call("kp_step_snapshot", P(Buf(bn0)), P(snap), bn_n, None)                              # without the word block
+    call_sync("kp_step_snapshot", P(Buf(bn0)), P(snap), bn_n, None)                              # without the word block
     assert torch.equal(snap.cpu(), bn0)
 
 
@@ -748,15 +696,15 @@ def run_selection(form, case, B, V, kin, kout, Hd):
     tvp = C.byref(tv) if tv is not None else None
     if form == "logp":
         lp = Buf(case["logp"] if "logp" in case else torch.log_softmax(case["logits"], 1))
-        call("kp_beam_select", P(lp), P(keep[0]), P(scores), P(toks), P(pars), B, kin, kout, V, None, 0, tvp, P(sc_out))
+        call_sync("kp_beam_select", P(lp), P(keep[0]), P(scores), P(toks), P(pars), B, kin, kout, V, None, 0, tvp, P(sc_out))
     elif form == "logits":
         lg = Mat(B * kin, V, data=case["logits"], pad=3)
-        call("kp_beam_select", None, P(keep[0]), P(scores), P(toks), P(pars), B, kin, kout, V, P(lg), lg.ld, tvp, P(sc_out))
+        call_sync("kp_beam_select", None, P(keep[0]), P(scores), P(toks), P(pars), B, kin, kout, V, P(lg), lg.ld, tvp, P(sc_out))
     else:
         hm = Mat(B * kin, Hd, data=case["h"], pad=4)
         assert hm.ld == Hd + 4
-        call("kp_project_select", P(hm), hm.ld, P(Buf(case["wo"])), P(Buf(case["bo"])), Hd, P(keep[0]), P(scores), P(toks), P(pars), B, kin, kout, V, tvp,
-             P(sc_out))
+        call_sync("kp_project_select", P(hm), hm.ld, P(Buf(case["wo"])), P(Buf(case["bo"])), Hd, P(keep[0]), P(scores), P(toks), P(pars), B, kin, kout, V, tvp,
+                  P(sc_out))
     for b, nm in ((scores, "beam_scores"), (toks, "tokens"), (pars, "parents"), (sc_out, "sc_out"), (loc_out, "loc_out")):
         b.check_tail(nm)
     return toks.cpu().long().reshape(B, kout), pars.cpu().long().reshape(B, kout), scores.cpu()[:B * kout].reshape(B, kout), sc_out.cpu(), \

@@ -6,7 +6,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 for d in ("tests", "oracle", "torch-attention-ocr_amd"):
     sys.path.insert(0, os.path.join(ROOT, d))
 import torch
-from test_step_gpu import make
+from model_harness import make
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 W, L = 256, 24
 m, O, ocfg, P, st, batch = make(dict(enc_hidden=256, enc_layers=1, dec_layers=2, input_feed=True), B=B, W=W, maxlen=L - 1, compute="bf16", max_decoder_l=L, max_beam=1)

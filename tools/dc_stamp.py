@@ -7,7 +7,7 @@ os.environ["AOCR_DC_STAMPS"] = "1"
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tests")); sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "oracle"))
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "torch-attention-ocr_amd"))
 import torch
-from test_step_gpu import make
+from model_harness import make
 B, W, L = 256, 256, 24
 m, O, ocfg, P, st, batch = make(dict(enc_hidden=256, enc_layers=1, dec_layers=2, input_feed=True), B=B, W=W, maxlen=L - 1, compute="bf16", max_decoder_l=L, max_beam=1)
 for _ in range(3):

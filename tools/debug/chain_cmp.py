@@ -3,7 +3,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
 for d in ("tests", "oracle", "torch-attention-ocr_amd"):
     sys.path.insert(0, os.path.join(ROOT, d))
 import torch
-from test_step_gpu import make, relerr
+from model_harness import make, relerr
 B, W, maxlen = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])
 cfg = dict(enc_hidden=256, enc_layers=1, dec_layers=2, input_feed=True)
 out = {}

@@ -4,7 +4,7 @@ import os, sys
 for d in ("tests", "oracle", "torch-attention-ocr_amd"):
     sys.path.insert(0, d)
 import torch
-from test_step_gpu import make
+from model_harness import make
 cfg = dict(enc_hidden=256, enc_layers=1, dec_layers=2, input_feed=True)
 m, O, ocfg, P, st, batch = make(cfg, B=256, W=256, maxlen=11, compute="bf16", max_decoder_l=12, max_beam=1)
 for _ in range(2):

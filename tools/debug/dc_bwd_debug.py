@@ -3,7 +3,7 @@ import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tests")); sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "oracle"))
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "torch-attention-ocr_amd"))
 import torch
-from test_step_gpu import make, relerr
+from model_harness import make, relerr
 B, W, maxlen = 32, 72, 6
 out = {}
 for knob in ("0", "1"):

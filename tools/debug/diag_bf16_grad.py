@@ -6,7 +6,7 @@ sys.path.insert(0, os.path.join(ROOT, "torch-attention-ocr_amd")); sys.path.inse
 import numpy as np, torch
 import torch.nn.functional as F
 import oracle_torch as O
-from test_step_gpu import make
+from model_harness import make
 
 saved = {}
 orig = F.conv2d

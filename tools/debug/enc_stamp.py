@@ -3,7 +3,7 @@ import os, sys
 for d in ("tests", "oracle", "torch-attention-ocr_amd"):
     sys.path.insert(0, d)
 import torch
-from test_step_gpu import make
+from model_harness import make
 w = sys.argv[1] if len(sys.argv) > 1 else "c3"
 if w == "c3": cfg, B, W, H = dict(enc_hidden=256, enc_layers=1, dec_layers=2, input_feed=True), 256, 256, 32
 else: cfg, B, W, H = dict(enc_hidden=512, enc_layers=1, dec_layers=2, input_feed=True), 16, 1024, 32

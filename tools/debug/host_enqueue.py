@@ -3,7 +3,7 @@ import sys, time
 for d in ("tests", "oracle", "torch-attention-ocr_amd"):
     sys.path.insert(0, d)
 import torch
-from test_step_gpu import make
+from model_harness import make
 w = sys.argv[1] if len(sys.argv) > 1 else "c3"
 cfgs = {"c3": (dict(enc_hidden=256, enc_layers=1, dec_layers=2, input_feed=True), 256, 256, "bf16", 24),
         "ref": (dict(enc_hidden=512, enc_layers=1, dec_layers=2, input_feed=True), 400, 100, "bf16", 24),

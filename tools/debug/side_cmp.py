@@ -3,7 +3,7 @@ import os, sys
 for d in ("tests", "oracle", "torch-attention-ocr_amd"):
     sys.path.insert(0, d)
 import torch
-from test_step_gpu import make
+from model_harness import make
 cfg = dict(enc_hidden=256, enc_layers=1, dec_layers=2, input_feed=True)
 def run(env):
     for k, v in env.items(): os.environ[k] = v

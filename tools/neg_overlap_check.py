@@ -1,7 +1,7 @@
 import sys, os
 sys.path.insert(0, "tests"); sys.path.insert(0, "torch-attention-ocr_amd"); sys.path.insert(0, "oracle")
 import torch
-from test_step_gpu import make
+from model_harness import make
 from aocr import check, lib, ptr
 from aocr import dist as adist
 m, O, ocfg, P, st, batch = make(dict(enc_hidden=256, enc_layers=1, dec_layers=2, input_feed=True), B=32, W=100, maxlen=10, max_decoder_l=12, max_beam=1, compute="bf16")

@@ -4,7 +4,7 @@ import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tests")); sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "oracle"))
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "torch-attention-ocr_amd"))
 import torch
-from test_step_gpu import make
+from model_harness import make
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 3000
 drop = float(sys.argv[2]) if len(sys.argv) > 2 else 0.0            # round 3: the dropout instances of the decoder cluster kernels
 beam = int(sys.argv[3]) if len(sys.argv) > 3 else 1                # round 5: > 1 adds a beam-search decode (chain kernel, several launches) every 50th step
