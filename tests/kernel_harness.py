@@ -25,10 +25,15 @@ SWITCHES = ("AOCR_FORCE_DMA", "AOCR_HALO8", "AOCR_HALO4_STAGED", "AOCR_NO_HALO",
             "AOCR_NO_HALF_TILES", "AOCR_HALF_TILES_MAXGRID", "AOCR_NO_STEP_MT2", "AOCR_STEP_MT2_MINK", "AOCR_NO_STEPL", "AOCR_STEPL_MIN_WGS",
             "AOCR_STEP_WAVES4", "AOCR_STEP_WAVES16", "AOCR_BIG_STEP", "AOCR_BIG_STEP_MIN_ROWS",
             # the attention launchers
-            "AOCR_NO_ATTN_BF16", "AOCR_ATTN_NW16", "AOCR_NO_ATTN_BEAM_GROUP", "AOCR_ATTN_BWD_TWO_PASS", "AOCR_NO_CHAIN_CTXA")
+            "AOCR_NO_ATTN_BF16", "AOCR_ATTN_NW16", "AOCR_NO_ATTN_BEAM_GROUP", "AOCR_ATTN_BWD_TWO_PASS", "AOCR_NO_CHAIN_CTXA",
+            # the whole-sequence decoder launchers
+            "AOCR_NO_DEC_CHAINS", "AOCR_NO_DEC_CHAINS_BWD", "AOCR_NO_DEC_CHAINS_GREEDY", "AOCR_CH_NO_RES", "AOCR_NO_DEC_EARLY", "AOCR_CL_REMOTE",
+            "AOCR_DC_STAMPS")
 EP_RELU, EP_TANH, EP_ACCUM = 1, 2, 4
 TOL_CELL = 2e-5                     # test_ops_gpu.py::test_lstm_cell, exact-fp32 cell
 TOL_BWD = 5e-5                      # its backward part (times max(1, max |dh|))
+TOL_A, TOL_C = 2e-5, 5e-5           # test_ops_gpu.py::test_attention (c: times max |ctx|)
+TOL_DS, TOL_DQ = 5e-5, 1e-4         # times max(1, max |d a|) (d q: and max |ctx|)
 JUNK = 3.0                          # what surrounds every operand window (exact in bf16: a wrong stride changes sums)
 
 _KP = None
@@ -103,12 +108,16 @@ _INT = {                                                              # return i
     "kp_enc_seq_supported": [i32, i32],
     "kp_enc_seq_forward": [vp, vp], "kp_enc_seq_backward": [vp, vp], "kp_enc_cluster_forward": [vp, vp], "kp_enc_cluster_backward": [vp, vp],
     "kp_enc_cluster_plan": [i32, i32, i32, i32, vp, vp, vp],
+    # the whole-sequence decoder kernels (tests/test_decoder_seq_kernels_gpu.py)
+    "kp_dec_cluster_supported": [i32] * 5, "kp_dec_cluster_bwd_supported": [i32] * 5,
+    "kp_dec_cluster_forward": [vp, vp], "kp_dec_cluster_backward": [vp, vp],
 }
 _SIZE = {                                                             # return size_t
     "kp_bn_scratch_bytes": [i32],
     "kp_conv1_route_elems": [i32, i32, i32],
     "kp_segsum_index_ints": [i32, i32], "kp_sgd_scratch_bytes": [], "kp_shadow_job_bytes": [],
     "kp_enc_cluster_xbuf_bytes": [i32, i32], "kp_enc_cluster_pbuf_bytes": [i32, i32],
+    "kp_dec_cluster_xbuf_bytes": [i32], "kp_dec_cluster_bwd_xbuf_bytes": [i32], "kp_dec_cluster_pbuf_bytes": [i32], "kp_dec_cluster_xtab_bytes": [i32],
 }
 SIGS = {**{n: (i32, a) for n, a in _INT.items()}, **{n: (sz, a) for n, a in _SIZE.items()}}       # name -> (restype, argtypes)
 

@@ -544,4 +544,77 @@ int kp_enc_cluster_backward(hipStream_t s, const KpEncClBwd* p) {
   return (int)hipGetLastError();
 }
 
+// ---- the whole-sequence decoder kernels (csrc/dec_cluster.hip, csrc/dec_chain.hip), for tests/test_decoder_seq_kernels_gpu.py.  One flat struct per problem
+// (mirrored there as ctypes.Structure): the fields of DecClFwdArgs / DecClBwdArgs the model sets, plus what the caller allocated.  The wrappers call the PUBLIC
+// launchers, so AOCR_NO_DEC_CHAINS* choose between the cluster and the chain kernels exactly as in the model.  Like the KP_ENC_* wrappers they REFUSE -- one of
+// the KP_DEC_* codes, nothing launched -- what the model would not launch: the kernels of a launch wait for each other and index the buffers by group.
+//   xbuf / pbuf / xtab  dec_cluster_xbuf_bytes / dec_cluster_bwd_xbuf_bytes, dec_cluster_pbuf_bytes (greedy only), dec_cluster_xtab_bytes of B
+//   err                 16 + 256 * 8 + 4096 ints (model.hip: cl_err): the error record, the trash slots of the lanes of rows >= B, the stamps builds' timeline
+struct KpDecFwd {
+  int B, T, L, Hd; unsigned epoch; int greedy;
+  const void *w1i, *w1h, *w2i, *w2h, *wc; const float *b2i, *b2h, *zx1; const void *ctxb, *ctxa;
+  float* cs[2]; void* hsb[2]; float* gates[2]; float *a_all, *out; void *cat_b, *out_b;
+  unsigned long long* xbuf; size_t xbuf_bytes; unsigned long long* xtab; size_t xtab_bytes; int* err; size_t err_ints;
+  const int32_t* tok0; int tok0_stride; const float *wo, *bo; int V; float* pbuf; size_t pbuf_bytes; int32_t* labels; float* scores;
+  const unsigned long long* trie_mask; const int32_t* trie_base; const int32_t* trie_child;
+  KpDrop drop_h, drop_out; void* hm_b;
+  const int32_t* zx_tok; int64_t zx_st, zx_sb; float* sc_hist;
+};
+struct KpDecBwd {
+  int B, T, L, Hd; unsigned epoch;
+  const void *w2i_t, *w2h_t, *w1h_t, *w1f_t, *wc_t, *wa_t; const float *dout_proj, *out, *a_all; const void* ctxb;
+  const float* cs[2]; const float* gates[2];
+  float* dpre; void* dpre_b; float* dcat; float* ds_all; float* dq; void* dq_b; float* dz[2]; void* dzb[2]; float* dc_st[2]; float* dh_rec[2]; float* dfeed;
+  unsigned long long* xbuf; size_t xbuf_bytes; unsigned long long* xtab; size_t xtab_bytes; int* err; size_t err_ints;
+  KpDrop drop_h, drop_out;
+};
+enum { KP_DEC_UNSUPPORTED = 2101, KP_DEC_XBUF_SMALL = 2102, KP_DEC_PBUF_SMALL = 2103, KP_DEC_XTAB_SMALL = 2104, KP_DEC_ERR_SMALL = 2105, KP_DEC_BAD_ARGS = 2106 };
+
+int kp_dec_cluster_supported(int Hd, int Ld, int input_feed, int T, int L) { return aocr::dec_cluster_supported(Hd, Ld, input_feed, T, L, kp_cus()) ? 1 : 0; }
+int kp_dec_cluster_bwd_supported(int Hd, int Ld, int input_feed, int T, int L) { return aocr::dec_cluster_bwd_supported(Hd, Ld, input_feed, T, L, kp_cus()) ? 1 : 0; }
+size_t kp_dec_cluster_xbuf_bytes(int B) { return aocr::dec_cluster_xbuf_bytes(B); }
+size_t kp_dec_cluster_bwd_xbuf_bytes(int B) { return aocr::dec_cluster_bwd_xbuf_bytes(B); }
+size_t kp_dec_cluster_pbuf_bytes(int B) { return aocr::dec_cluster_pbuf_bytes(B); }
+size_t kp_dec_cluster_xtab_bytes(int B) { return aocr::dec_cluster_xtab_bytes(B); }
+
+int kp_dec_cluster_forward(hipStream_t s, const KpDecFwd* p) {
+  if (p->B < 1 || p->L < 1 || p->epoch == 0 || p->epoch >= (1u << 20)) return KP_DEC_BAD_ARGS;
+  if ((p->greedy || p->zx_tok) && (p->V < 1 || p->V > 40)) return KP_DEC_BAD_ARGS;
+  if (p->greedy && (!p->tok0 || p->tok0_stride < p->L || !p->wo || !p->bo || !p->labels || !p->scores)) return KP_DEC_BAD_ARGS;
+  if (!aocr::dec_cluster_supported(p->Hd, 2, 1, p->T, p->L, kp_cus())) return KP_DEC_UNSUPPORTED;
+  if (!p->xbuf || p->xbuf_bytes < aocr::dec_cluster_xbuf_bytes(p->B)) return KP_DEC_XBUF_SMALL;
+  if (p->greedy && (!p->pbuf || p->pbuf_bytes < aocr::dec_cluster_pbuf_bytes(p->B))) return KP_DEC_PBUF_SMALL;
+  if (!p->xtab || p->xtab_bytes < aocr::dec_cluster_xtab_bytes(p->B)) return KP_DEC_XTAB_SMALL;
+  if (!p->err || p->err_ints < 16 + 256 * 8 + 4096) return KP_DEC_ERR_SMALL;
+  aocr::DecClFwdArgs a; a.B = p->B; a.T = p->T; a.L = p->L; a.epoch = p->epoch;
+  a.w1i = H16(p->w1i); a.w1h = H16(p->w1h); a.w2i = H16(p->w2i); a.w2h = H16(p->w2h); a.wc = H16(p->wc);
+  a.b2i = p->b2i; a.b2h = p->b2h; a.zx1 = p->zx1; a.ctxb = H16(p->ctxb); a.ctxa = H16(p->ctxa);
+  for (int l = 0; l < 2; ++l) { a.cs[l] = p->cs[l]; a.hsb[l] = W16(p->hsb[l]); a.gates[l] = p->gates[l]; }
+  a.a_all = p->a_all; a.out = p->out; a.cat_b = W16(p->cat_b); a.out_b = W16(p->out_b);
+  a.xbuf = p->xbuf; a.xtab = p->xtab; a.err = p->err;
+  a.tok0 = p->tok0; a.tok0_stride = p->tok0_stride; a.wo = p->wo; a.bo = p->bo; a.V = p->V; a.pbuf = p->pbuf; a.labels = p->labels; a.scores = p->scores;
+  a.trie_mask = p->trie_mask; a.trie_base = p->trie_base; a.trie_child = p->trie_child;
+  a.drop_h = drop_of(p->drop_h); a.drop_out = drop_of(p->drop_out); a.hm_b = W16(p->hm_b);
+  a.zx_tok = p->zx_tok; a.zx_st = p->zx_st; a.zx_sb = p->zx_sb; a.sc_hist = p->sc_hist;
+  aocr::dec_cluster_forward(s, a, p->greedy != 0);
+  return (int)hipGetLastError();
+}
+int kp_dec_cluster_backward(hipStream_t s, const KpDecBwd* p) {
+  if (p->B < 1 || p->L < 1 || p->epoch == 0 || p->epoch >= (1u << 20)) return KP_DEC_BAD_ARGS;
+  if (!aocr::dec_cluster_bwd_supported(p->Hd, 2, 1, p->T, p->L, kp_cus())) return KP_DEC_UNSUPPORTED;
+  if (!p->xbuf || p->xbuf_bytes < aocr::dec_cluster_bwd_xbuf_bytes(p->B)) return KP_DEC_XBUF_SMALL;
+  if (!p->xtab || p->xtab_bytes < aocr::dec_cluster_xtab_bytes(p->B)) return KP_DEC_XTAB_SMALL;
+  if (!p->err || p->err_ints < 16 + 256 * 8 + 4096) return KP_DEC_ERR_SMALL;
+  aocr::DecClBwdArgs a; a.B = p->B; a.T = p->T; a.L = p->L; a.epoch = p->epoch;
+  a.w2i_t = H16(p->w2i_t); a.w2h_t = H16(p->w2h_t); a.w1h_t = H16(p->w1h_t); a.w1f_t = H16(p->w1f_t); a.wc_t = H16(p->wc_t); a.wa_t = H16(p->wa_t);
+  a.dout_proj = p->dout_proj; a.out = p->out; a.a_all = p->a_all; a.ctxb = H16(p->ctxb);
+  for (int l = 0; l < 2; ++l) {
+    a.cs[l] = p->cs[l]; a.gates[l] = p->gates[l]; a.dz[l] = p->dz[l]; a.dzb[l] = W16(p->dzb[l]); a.dc_st[l] = p->dc_st[l]; a.dh_rec[l] = p->dh_rec[l];
+  }
+  a.dpre = p->dpre; a.dpre_b = W16(p->dpre_b); a.dcat = p->dcat; a.ds_all = p->ds_all; a.dq = p->dq; a.dq_b = W16(p->dq_b); a.dfeed = p->dfeed;
+  a.xbuf = p->xbuf; a.xtab = p->xtab; a.err = p->err; a.drop_h = drop_of(p->drop_h); a.drop_out = drop_of(p->drop_out);
+  aocr::dec_cluster_backward(s, a);
+  return (int)hipGetLastError();
+}
+
 }  // extern "C"

@@ -109,12 +109,10 @@ import pytest
 import torch
 
 from kernel_harness import _switches  # noqa: F401  this import IS how the autouse fixture reaches the module (tests/test_kernel_harness_cpu.py checks it)
-from kernel_harness import SENT, Buf, Mat, bf, bound, call, expect, ints, kp, out, ratio, rnd, setenv, vp
+from kernel_harness import SENT, TOL_A, TOL_C, TOL_DQ, TOL_DS, Buf, Mat, bf, bound, call, expect, ints, kp, out, ratio, rnd, setenv, vp
 
 pytestmark = pytest.mark.gpu
 
-TOL_A, TOL_C = 2e-5, 5e-5           # test_ops_gpu.py::test_attention (c: times max |ctx|)
-TOL_DS, TOL_DQ = 5e-5, 1e-4         # times max(1, max |d a|) (d q: and max |ctx|)
 P_EDGE = 0.05                       # least reference probability of a planted edge row in its batch row
 QC, QU = 2.0 ** -2, 2.0 ** -3       # quanta of the context and of u
 

@@ -50,7 +50,9 @@ def test_kprobe_symbols_resolve_in_libaocr(tmp_path):
                  "project_select", "gather_beam_rows_many", "gather_beam_rows", "token_rows", "beam_backtrace", "recognize_gather", "dec_init",
                  "dpre_tanh", "dropout_apply", "dropout_apply_b", "zero_many", "copy2d_bf16", "sum_to_scalar", "gold_scores", "edit_distance",
                  "enc_seq_supported", "enc_seq_forward", "enc_seq_backward", "enc_cluster_plan", "enc_cluster_xbuf_bytes", "enc_cluster_pbuf_bytes",
-                 "enc_cluster_forward", "enc_cluster_backward"):
+                 "enc_cluster_forward", "enc_cluster_backward",
+                 "dec_cluster_supported", "dec_cluster_bwd_supported", "dec_cluster_xbuf_bytes", "dec_cluster_bwd_xbuf_bytes", "dec_cluster_pbuf_bytes",
+                 "dec_cluster_xtab_bytes", "dec_cluster_forward", "dec_cluster_backward"):
         assert any(f"{len(name)}{name}E" in s for s in wanted), f"the shim does not call aocr::{name}"
     defined = _symbols(LIB, "--defined-only")
     missing = sorted(wanted - defined)
@@ -68,7 +70,9 @@ def test_kprobe_symbols_resolve_in_libaocr(tmp_path):
                  "kp_gather_beam_rows", "kp_token_rows", "kp_beam_backtrace", "kp_recognize_gather", "kp_dec_init", "kp_dpre_tanh",
                  "kp_dropout_apply", "kp_dropout_apply_b", "kp_zero_many", "kp_copy2d_bf16", "kp_sum_to_scalar", "kp_gold_scores",
                  "kp_enc_seq_supported", "kp_enc_seq_forward", "kp_enc_seq_backward", "kp_enc_cluster_plan", "kp_enc_cluster_xbuf_bytes",
-                 "kp_enc_cluster_pbuf_bytes", "kp_enc_cluster_forward", "kp_enc_cluster_backward"):
+                 "kp_enc_cluster_pbuf_bytes", "kp_enc_cluster_forward", "kp_enc_cluster_backward",
+                 "kp_dec_cluster_supported", "kp_dec_cluster_bwd_supported", "kp_dec_cluster_xbuf_bytes", "kp_dec_cluster_bwd_xbuf_bytes",
+                 "kp_dec_cluster_pbuf_bytes", "kp_dec_cluster_xtab_bytes", "kp_dec_cluster_forward", "kp_dec_cluster_backward"):
         assert name in exported
     unexported = sorted(set(SIGS) - exported)
     assert not unexported, f"in kernel_harness.SIGS, not exported by the compiled shim: {unexported}"

@@ -353,6 +353,7 @@ __global__ __launch_bounds__(256, 1) void dec_ch_fwd_kernel(DecClFwdArgs p) {
   };
   // LSTM cell on this lane's (unit, row): returns the packed h of the four units of (row, wave) in lanes q == 0
   auto cell = [&](const f32x4& z, float& c, f32x4& g, u32x2& hp) {
+#pragma clang fp contract(off)      // f c + i g rounds each product in every instantiation, here and in dec_cluster.hip: the same bits (tests/test_decoder_seq_kernels_gpu.py)
     const float ig = sigmoidf_(z[0]), fg = sigmoidf_(z[1]), og = sigmoidf_(z[2]), gg = tanhf_(z[3]);
     const float cn = fg * c + ig * gg, hn = og * tanhf_(cn);
     c = cn; g = f32x4{ig, fg, og, gg};
@@ -993,6 +994,7 @@ __global__ __launch_bounds__(256, 1) void dec_ch_bwd_kernel(DecClBwdArgs p) {
   };
   // cell backward of one layer on this lane's 4 units (EpGatesBwd), inputs from the staging buffer
   auto cell_bwd = [&](int buf, const f32x4& dh, f32x4& dcs_, f32x4 (&dz)[4]) {
+#pragma clang fp contract(off)      // every inlined copy, here and in dec_cluster.hip, rounds each product and sum on its own: the same bits (tests/test_decoder_seq_kernels_gpu.py); covers this body only, not tanhf_ / sigmoidf_
     const unsigned char* b = cellb + buf * 6144 + lane * 16;
     const f32x4 cn = *reinterpret_cast<const f32x4*>(b), cp = *reinterpret_cast<const f32x4*>(b + 1024);
 #pragma unroll
@@ -1329,6 +1331,8 @@ void dec_chain_forward(hipStream_t s, const DecClFwdArgs& a0, bool greedy_decode
     (void)hipFuncSetAttribute((const void*)dec_ch_fwd_kernel<true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CH_DEC_LDS);
   }
   const bool res = a0.T <= 64 && !knob::AOCR_CH_NO_RES();
+  dec_trace("dec_chain_forward", "dec_ch_fwd_kernel", greedy_decode ? (hist ? (res ? "dec,res,hist" : "dec,hist") : (res ? "dec,res" : "dec")) : (res ? "tf,res" : "tf"), a0.B, a0.T, a0.L, groups,
+            (groups + per_pass - 1) / per_pass, knob::AOCR_CL_REMOTE());
   for (int g0 = 0; g0 < groups; g0 += per_pass) {
     DecClFwdArgs a = a0; a.group0 = g0; a.ngroups = std::min(per_pass, groups - g0); a.force_remote = knob::AOCR_CL_REMOTE();
     { const char* e = knob::AOCR_DC_STAMPS(); a.stamps = (e && e[0] != 'b') ? a.xtab + (size_t)groups * NM : nullptr; }      // ("beam": only the beam-search launches)
@@ -1371,6 +1375,8 @@ void dec_chain_beam_forward(hipStream_t s, const DecClFwdArgs& a0) {
   }
   const bool res = a0.T <= 64 && !knob::AOCR_CH_NO_RES();
   unsigned epoch = a0.epoch;
+  dec_trace("dec_chain_beam_forward", "dec_ch_fwd_kernel", hist ? (res ? "dec,res,beam,hist" : "dec,beam,hist") : (res ? "dec,res,beam" : "dec,beam"), a0.B, a0.T, a0.L, groups,
+            per_pass > 0 ? (groups + per_pass - 1) / per_pass : 0, knob::AOCR_CL_REMOTE());
   for (int g0 = 0; g0 < groups; g0 += per_pass, ++epoch) {
     DecClFwdArgs a = a0; a.group0 = g0; a.ngroups = std::min(per_pass, groups - g0); a.force_remote = knob::AOCR_CL_REMOTE();
     a.epoch = epoch; a.stamps = knob::AOCR_DC_STAMPS() ? a.xtab + (size_t)cap * NM : nullptr; a.no_early = 1;
@@ -1388,6 +1394,7 @@ void dec_chain_backward(hipStream_t s, const DecClBwdArgs& a0) {
   static const int cus = [] { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
   const int groups = (a0.B + R - 1) / R, per_pass = std::max(8, cus / (8 * NM) * 8);
   (void)hipFuncSetAttribute((const void*)dec_ch_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CH_BWD_LDS);
+  dec_trace("dec_chain_backward", "dec_ch_bwd_kernel", "bptt", a0.B, a0.T, a0.L, groups, (groups + per_pass - 1) / per_pass, knob::AOCR_CL_REMOTE());
   for (int g0 = 0; g0 < groups; g0 += per_pass) {
     DecClBwdArgs a = a0; a.group0 = g0; a.ngroups = std::min(per_pass, groups - g0); a.force_remote = knob::AOCR_CL_REMOTE();
     a.stamps = knob::AOCR_DC_STAMPS() ? a.xtab + (size_t)groups * NM + 16 : nullptr;

@@ -292,6 +292,7 @@ __global__ __launch_bounds__(256, 1) void dec_cl_fwd_kernel(DecClFwdArgs p) {
   // LSTM cell on this lane's (unit, row) pairs; returns the packed h of the four units of (row, wave) in lanes q == 0
   u32x2 hpm[2] = {u32x2{0u, 0u}, u32x2{0u, 0u}};                    // DROP: Dropout(h1) of this lane's cells, packed like hp
   auto cell = [&](const f32x4 (&z)[2], float (&c)[2], f32x4 (&g)[2], u32x2 (&hp)[2], long long moff = -1) {
+#pragma clang fp contract(off)      // f c + i g rounds each product in every instantiation, here and in dec_chain.hip: the same bits (tests/test_decoder_seq_kernels_gpu.py)
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt) {
       const float ig = sigmoidf_(z[rt][0]), fg = sigmoidf_(z[rt][1]), og = sigmoidf_(z[rt][2]), gg = tanhf_(z[rt][3]);
@@ -723,6 +724,7 @@ __global__ __launch_bounds__(256, 1) void dec_cl_bwd_kernel(DecClBwdArgs p) {
     }
   };
   auto cell_bwd = [&](const CellIn& ci, const f32x4& dh, f32x4& dcs, f32x4 (&dz)[4]) {
+#pragma clang fp contract(off)      // every inlined copy, here and in dec_chain.hip, rounds each product and sum on its own: the same bits (tests/test_decoder_seq_kernels_gpu.py); covers this body only, not tanhf_ / sigmoidf_
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const float ig = ci.g[i][0], fg = ci.g[i][1], og = ci.g[i][2], gg = ci.g[i][3];
@@ -985,6 +987,7 @@ void dec_cluster_backward(hipStream_t s, const DecClBwdArgs& a0) {
   if (a0.drop_h.thr == 0 && a0.drop_out.thr == 0 && dec_chain_enabled() && !knob::AOCR_NO_DEC_CHAINS_BWD()) { dec_chain_backward(s, a0); return; }      // round 5: two chains per group, tag-free exchange
   static const int cus = [] { int n = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
   const int groups = (a0.B + R - 1) / R, per_pass = std::max(8, cus / (8 * NM) * 8);
+  dec_trace("dec_cluster_backward", "dec_cl_bwd_kernel", (a0.drop_h.thr != 0 || a0.drop_out.thr != 0) ? "bptt,drop" : "bptt", a0.B, a0.T, a0.L, groups, (groups + per_pass - 1) / per_pass, knob::AOCR_CL_REMOTE());
   (void)hipFuncSetAttribute((const void*)dec_cl_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BWD_LDS_BYTES);
   (void)hipFuncSetAttribute((const void*)dec_cl_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BWD_LDS_BYTES);
   for (int g0 = 0; g0 < groups; g0 += per_pass) {
@@ -1005,6 +1008,8 @@ void dec_cluster_forward(hipStream_t s, const DecClFwdArgs& a0, bool greedy_deco
   (void)hipFuncSetAttribute((const void*)dec_cl_fwd_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const bool hist = greedy_decode && a0.sc_hist;                   // aocr_recognize: the variant that keeps the score history
   if (hist) (void)hipFuncSetAttribute((const void*)dec_cl_fwd_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  dec_trace("dec_cluster_forward", "dec_cl_fwd_kernel", greedy_decode ? (hist ? "dec,hist" : "dec") : (a0.drop_h.thr != 0 || a0.drop_out.thr != 0) ? "tf,drop" : "tf", a0.B, a0.T, a0.L, groups,
+            (groups + per_pass - 1) / per_pass, knob::AOCR_CL_REMOTE());
   for (int g0 = 0; g0 < groups; g0 += per_pass) {
     DecClFwdArgs a = a0; a.group0 = g0; a.ngroups = std::min(per_pass, groups - g0); a.force_remote = knob::AOCR_CL_REMOTE(); a.no_early = knob::AOCR_NO_DEC_EARLY();
     a.stamps = knob::AOCR_DC_STAMPS() ? a.xtab + (size_t)groups * NM : nullptr;   // debugging aid: cycles per phase of workgroup 0

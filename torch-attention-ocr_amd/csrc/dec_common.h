@@ -2,6 +2,8 @@
 // dec_chain.hip: two interleaved chains of 16 rows): L1-bypassing loads, exchange stores, counted vmcnt waits, DPP wave reductions.
 #pragma once
 #include "ops.h"
+#include "knobs.h"
+#include <cstdio>
 
 namespace aocr {
 
@@ -9,6 +11,13 @@ namespace aocr {
 bool dec_chain_enabled();
 void dec_chain_forward(hipStream_t s, const DecClFwdArgs& a, bool greedy_decode = false);
 void dec_chain_backward(hipStream_t s, const DecClBwdArgs& a);
+
+// dispatch trace (AOCR_TRACE set, read per call; the format of ops_gemm.hip's lines): one stderr line per call of a decoder launcher with the kernel and the
+// template arguments it launched -- tf | dec (teacher-forced | greedy decode), res, beam, hist, drop --, then B T L, the groups of 32 rows (beam: of images),
+// the launches they take and whether AOCR_CL_REMOTE asks for the write-through exchange
+inline void dec_trace(const char* fn, const char* kernel, const char* inst, int B, int T, int L, int groups, int passes, bool remote) {
+  if (knob::AOCR_TRACE()) fprintf(stderr, "[aocr] %s: %s[%s] %d %d %d groups=%d passes=%d remote=%d\n", fn, kernel, inst, B, T, L, groups, passes, remote ? 1 : 0);
+}
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
