@@ -569,6 +569,47 @@ int aocr_segment_page(void* stream, const uint8_t* page_dev, int64_t pitch, int3
                       const aocr_segment_params* params, void* scratch_dev, int32_t max_boxes,
                       aocr_box* boxes_dev, int32_t counts_dev[4]);
 
+/* aocr_segment_page with one word gap per line, estimated from the line itself.  params.word_gap is one number for the whole page, and word
+ * spacing is not: a headline above body text, a footnote or a caption under it, letter-spaced print and the blocks of a multi-column page set
+ * in different sizes are wrongly cut by any single value.  Steps 1-4, 6 and 7 are those of aocr_segment_page, bit for bit; step 5 takes
+ * gap_b in place of params.word_gap, for band b with rows [y0, y1), h = y1 - y0 (every division is a floor division of non-negative ints):
+ *   runs      maximal runs r_0 .. r_m of columns with col_ink >= 1: nothing merged, min_word_w not applied yet (no ink column: m = 0);
+ *   gaps      g_j = start(r_j) - end(r_(j-1)) for j = 1..m (ends are exclusive: the empty columns between two runs, >= 1); interior gaps only;
+ *   bounds    lo = max(1, h * lo_percent / 100), hi = max(lo, h * hi_percent / 100), clip = min(hi, 255);
+ *   histogram hist[min(g_j, clip)] += 1, 256 bins: a gutter or a tab cannot pull the classes apart (a gap of hi or more is a word gap whatever
+ *             its size);
+ *   split     t = the Otsu threshold of step 2 on hist, operation for operation (-1: no gap, or one distinct clipped length); with t >= 0,
+ *             a = the largest occupied bin <= t, c = the smallest occupied bin > t, and est = (a + c + 1) >> 1, so a < est <= c; with
+ *             t = -1, a = c = 0;
+ *   decision  est is used when m >= min_gaps, t >= 0 and c * 100 >= a * ratio_percent; else est = max(1, h * default_percent / 100);
+ *             gap_b = min(max(est, lo), hi);
+ *   flags     0 estimated, 1 too few gaps (m < min_gaps), 2 one gap length (t = -1), 3 classes not separated (the ratio), the first that
+ *             applies in this order; + 4 when the clamp changed the value (gap_b != est);
+ *   words     runs with fewer than gap_b empty columns between them are one word; min_word_w, the boxes and the counts follow as in
+ *             aocr_segment_page.
+ * When every band ends with gap_b = G the boxes and counts are those of aocr_segment_page with word_gap = G.  The band height stands in for
+ * the em.  Limits: h <= 16384 and the percents <= 400 keep h * percent below 2^23; a, c <= 255 and ratio_percent <= 100000 keep
+ * a * ratio_percent below 2^25; m < 8192.
+ * params: as for aocr_segment_page, but word_gap == 0 (one box per band) is an error; any other word_gap is not read.  boxes_dev and counts_dev
+ * mean what they mean there, so aocr_crop_lines and aocr_estimate_slant take them unchanged.  spacing_dev: NULL, or max_lines >= 0 rows of 8
+ * words, 4-byte aligned, disjoint from the page and the scratch: row b < min(lines, max_lines) = {gap_b, flags, m, a, c, h, 0, 0}; the other rows
+ * are untouched.  scratch_dev: aocr_segment_spaced_scratch_bytes(H, W, max_boxes) bytes, 16-byte aligned.  The page is not read again: the
+ * estimate works on the ink-column flags the words pass has staged.  Enqueues only, never synchronises or allocates; the result does not
+ * depend on launch geometry, atomics order or run.  Invalid arguments return an error before anything is enqueued and leave the outputs
+ * untouched. */
+typedef struct aocr_spacing_params {
+  int32_t min_gaps;        /* >= 1: a band with fewer interior gaps takes the default */
+  int32_t lo_percent, hi_percent, default_percent;   /* of the band height; 1 <= lo <= default <= hi <= 400 */
+  int32_t ratio_percent;   /* 100..100000: the word-gap class must start at ratio_percent / 100 times the end of the letter-gap class */
+  int32_t reserved[3];     /* must be 0 */
+} aocr_spacing_params;
+
+size_t aocr_segment_spaced_scratch_bytes(int32_t H, int32_t W, int32_t max_boxes);
+int aocr_segment_page_spaced(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                             const aocr_segment_params* params, const aocr_spacing_params* spacing,
+                             void* scratch_dev, int32_t max_boxes, aocr_box* boxes_dev, int32_t counts_dev[4],
+                             int32_t max_lines, int32_t* spacing_dev);
+
 /* The crops of a page: row i < n of out_dev (n_boxes, 1, out_h, out_w) fp32 is rectangle boxes_dev[i] of the page scaled to out_h x out_w with
  * the arithmetic of aocr_preprocess_lines on a one-channel image, operation for operation (rows to out_w first, then columns to out_h): the
  * result is bit-identical to aocr_preprocess_lines on a contiguous copy of the rectangle.  n = min(n_boxes, count_dev[0]) is read on the

@@ -98,6 +98,9 @@ typedef struct aocr_segment_params { int32_t threshold; int32_t light_text; int3
 typedef struct aocr_box { int32_t x0, y0, x1, y1, line, ink; } aocr_box;
 size_t aocr_segment_scratch_bytes(int32_t H, int32_t W, int32_t max_boxes);
 int aocr_segment_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_segment_params* params, void* scratch_dev, int32_t max_boxes, aocr_box* boxes_dev, int32_t counts_dev[4]);
+typedef struct aocr_spacing_params { int32_t min_gaps; int32_t lo_percent, hi_percent, default_percent; int32_t ratio_percent; int32_t reserved[3]; } aocr_spacing_params;
+size_t aocr_segment_spaced_scratch_bytes(int32_t H, int32_t W, int32_t max_boxes);
+int aocr_segment_page_spaced(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_segment_params* params, const aocr_spacing_params* spacing, void* scratch_dev, int32_t max_boxes, aocr_box* boxes_dev, int32_t counts_dev[4], int32_t max_lines, int32_t* spacing_dev);
 int aocr_crop_lines(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_box* boxes_dev, const int32_t* count_dev, int32_t n_boxes, int32_t out_h, int32_t out_w, float* out_dev);
 typedef struct aocr_skew_params { int32_t threshold; int32_t light_text; int32_t step_q16; int32_t n_steps; } aocr_skew_params;
 size_t aocr_skew_scratch_bytes(int32_t H, int32_t W, int32_t n_steps);

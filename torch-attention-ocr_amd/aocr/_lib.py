@@ -57,6 +57,16 @@ class SegmentParams(C.Structure):
                          int(pad_x), int(pad_y), 0)
 
 
+class SpacingParams(C.Structure):
+    """mirror of `aocr_spacing_params` (include/aocr.h): how `aocr_segment_page_spaced` estimates the word gap of every line from the line's
+    own gaps.  The percents are of the band height: the estimate is clamped to lo..hi, and a line with fewer than min_gaps gaps, one gap
+    length, or two classes closer than ratio_percent / 100 takes default_percent.  How the defaults were chosen: DESIGN.md section 23."""
+    _fields_ = [(n, C.c_int32) for n in ("min_gaps", "lo_percent", "hi_percent", "default_percent", "ratio_percent")] + [("reserved", C.c_int32 * 3)]
+
+    def __init__(self, min_gaps=4, lo_percent=25, hi_percent=80, default_percent=40, ratio_percent=150):
+        super().__init__(int(min_gaps), int(lo_percent), int(hi_percent), int(default_percent), int(ratio_percent), (C.c_int32 * 3)(0, 0, 0))
+
+
 class SkewParams(C.Structure):
     """mirror of `aocr_skew_params` (include/aocr.h): the candidates of `aocr_estimate_skew`, k = -n_steps..n_steps at k * step_q16 / 65536 rows
     per column.  threshold -1: Otsu.  The defaults sweep +-5.4 degrees in steps of 0.056."""
@@ -268,6 +278,8 @@ SIGNATURES = {
     "aocr_synth_lines": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "aocr_segment_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
     "aocr_segment_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _i32, _vp, _vp]),
+    "aocr_segment_spaced_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
+    "aocr_segment_page_spaced": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
     "aocr_crop_lines": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     "aocr_skew_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
     "aocr_estimate_skew": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -437,12 +437,12 @@ class Model:
             res.word = [lexicon.words[i] if i >= 0 else None for i in res.word_index.tolist()]
         return res
 
-    def _page_boxes(self, page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None, deslant=None):
+    def _page_boxes(self, page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None, deslant=None, spacing=None):
         """the middle of recognize_page (aocr.page_pipeline.page_boxes), reached through the model so that a caller can wrap it."""
-        return page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev, deslant)
+        return page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev, deslant, spacing)
 
     def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None, flatten=None,
-                       layout=None, clean=None, orient=None, rectify=None, scale=None, dewarp=None, colour=None, deslant=None):
+                       layout=None, clean=None, orient=None, rectify=None, scale=None, dewarp=None, colour=None, deslant=None, spacing=None):
         """Read a scanned page: segment it into word boxes (aocr_segment_page), crop them (aocr_crop_lines) and recognise the crops.
         page: a uint8 (H,W) numpy array or tensor (gray; a 3-D array raises ValueError unless `colour` is asked for: see below).  params: an
         `aocr.SegmentParams` (default: Otsu threshold, dark text).  The counts and boxes are read back once (the one sync), then the boxes are
@@ -548,7 +548,16 @@ class Model:
         with paper: 0 with light_text, else 255); the which-way-up probe of orient=True keeps the plain crops.  The namespace then also
         carries slant_q16 (n) int32, slant_deg (n) float64 (atan(s / 65536) in degrees), slant_flags (n) int32 (0 estimated, 1 taller than
         256 rows and left alone, 2 empty) and slant_extent (n) int32; boxes and every *_corners field stay what they are: the boxes do not
-        move.  Limits (any vertical alignment scores, one round glyph has no slant, one slant per box): DESIGN.md section 22."""
+        move.  Limits (any vertical alignment scores, one round glyph has no slant, one slant per box): DESIGN.md section 22.
+        spacing: None or False (the default) cuts every line into words with the one word_gap of `params`.  True or an `aocr.SpacingParams`
+        estimates the word gap of every line on the device from the line's own gaps between ink-column runs (aocr_segment_page_spaced in
+        place of aocr_segment_page, per block with layout: Otsu's split of the gap lengths, clamped to a share of the line height; word_gap
+        is then not read, but 0 is an error), so that a headline, body text and a footnote on one page are each cut by their own gap.
+        The spacing rows come back inside the readback of the boxes (no additional sync).  The namespace then also carries word_gaps
+        (n_lines) int32, the gap used per line, spacing_flags (n_lines) int32 (0 estimated, 1 too few gaps, 2 one gap length, 3 classes
+        not separated: the share of the line height was used; + 4 clamped) and spacing_gaps (n_lines) int32, the gaps counted; with
+        layout they run across the blocks like the line numbers.  Limits (justified text, lines of one or two words, digits with wide
+        tracking, the band height as the em): DESIGN.md section 23."""
         if asked(colour):
             ok = isinstance(page, (np.ndarray, torch.Tensor)) and len(page.shape) == 3 and page.shape[2] == 3 and \
                 page.dtype == (np.uint8 if isinstance(page, np.ndarray) else torch.uint8)
@@ -581,6 +590,8 @@ class Model:
         page, quarter, orient_runs = orient_stage(page0, stream, seg, orient)
         middle = (stream, seg, max_boxes, deskew, dewarp, layout, clean_dev) + (() if colour_dev is None else (colour_dev,))
         extra = dict(deslant=deslant) if asked(deslant) else {}
+        if asked(spacing):
+            extra["spacing"] = spacing
         st = self._page_boxes(page, *middle, **extra)
         orient_scores = None
         if orient is True:
@@ -643,6 +654,8 @@ class Model:
         if st.slant is not None:
             res.slant_q16, res.slant_flags, res.slant_extent = st.slant[:, 1].astype(np.int32), st.slant[:, 2].astype(np.int32), extent
             res.slant_deg = np.degrees(np.arctan(res.slant_q16 / 65536.0))
+        if st.spacing is not None:
+            res.word_gaps, res.spacing_flags, res.spacing_gaps = (st.spacing[:, k].astype(np.int32) for k in range(3))
         curl = skew = turn = None                                   # what each stage left behind for aocr.page.backmap_corners
         if st.curl is not None:
             res.curl_shifts, res.curl_group = st.curl[4:].astype(np.int32), st.curl_group

@@ -22,7 +22,9 @@ form rule, a highlighter stroke, a stamp -- turned into paper) before any of the
 None of them straightens the writing inside a box: italic print and handwriting go through `estimate_slant_device` (`aocr_estimate_slant`:
 one slant per box from a sweep of sheared column profiles) after the segmentation, and `crop_lines_slanted_device`
 (`aocr_crop_lines_slanted`: the crops with every row moved back along x) takes the place of `crop_lines_device`; `slant_extent` is how far
-such a crop reaches beyond its box on either side.  The boxes do not move."""
+such a crop reaches beyond its box on either side.  The boxes do not move.  One `word_gap` cuts every line of the page into words; a page
+whose lines are set in different sizes goes through `segment_page_spaced_device` (`aocr_segment_page_spaced`: the gap of every line
+estimated from the line's own gaps) in place of `segment_page_device`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -31,7 +33,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import Box, CleanParams, ColourParams, CurlParams, FlattenParams, GlyphParams, LayoutParams, RectifyParams, ScaleParams, SegmentParams, SkewParams, SlantParams, check, lib, ptr
+from ._lib import Box, CleanParams, ColourParams, CurlParams, FlattenParams, GlyphParams, LayoutParams, RectifyParams, ScaleParams, SegmentParams, SkewParams, SlantParams, SpacingParams, check, lib, ptr
 
 IMG_H = 32
 MIN_ASPECT = 0.5
@@ -103,6 +105,28 @@ def segment_page_device(page_dev, params=None, max_boxes=1024, stream=None):
     check(lib.aocr_segment_page(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), max_boxes, ptr(boxes),
                                 ptr(counts)), "aocr_segment_page")
     return boxes, counts
+
+
+def segment_page_spaced_device(page_dev, params=None, spacing=None, max_boxes=1024, stream=None, max_lines=None):
+    """`segment_page_device` with one word gap per line, estimated on the device from the line's own gaps (`aocr_segment_page_spaced`):
+    (boxes, counts, spacing_rows (max_lines, 8) int32: gap used, flags (0 estimated, 1 too few gaps, 2 one gap length, 3 classes not
+    separated; + 4 clamped), gaps counted, the two occupied gap lengths around the split, band height, 0, 0) as device tensors.  Rows of
+    spacing_rows beyond min(counts[1], max_lines) are not written (they hold zeros).  params.word_gap is not read, but 0 is an error.
+    spacing: a `SpacingParams` (default: its defaults).  max_lines None: (H + 1) // 2, every line a page of H rows can have.  Enqueues
+    only.  stream: as for `segment_page_device`."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    params = params if params is not None else SegmentParams()
+    spacing = spacing if spacing is not None else SpacingParams()
+    max_lines = (H + 1) // 2 if max_lines is None else int(max_lines)
+    dev = page_dev.device
+    scratch = _scratch("aocr_segment_spaced_scratch_bytes", dev, H, W, max_boxes)
+    boxes = torch.zeros((max_boxes, 6), dtype=torch.int32, device=dev)
+    counts = torch.zeros(4, dtype=torch.int32, device=dev)
+    rows = torch.zeros((max(max_lines, 0), 8), dtype=torch.int32, device=dev)
+    check(lib.aocr_segment_page_spaced(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), C.byref(spacing), ptr(scratch), max_boxes,
+                                       ptr(boxes), ptr(counts), max_lines, ptr(rows) if max_lines > 0 else None), "aocr_segment_page_spaced")
+    return boxes, counts, rows
 
 
 def crop_lines_device(page_dev, boxes, counts, out_w, out_h=IMG_H, stream=None):
@@ -704,6 +728,6 @@ def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
     return min(img_w, int(max_img_w))
 
 
-__all__ = ["backmap_corners", "SlantParams", "estimate_slant_device", "crop_lines_slanted_device", "slant_extent", "ColourParams", "estimate_page_colour_device", "gray_page_device", "CurlParams", "estimate_curl_device", "dewarp_page_device", "curl_shift_q8", "uncurl_points", "source_points", "box_corners", "GlyphParams", "ScaleParams", "estimate_glyph_size_device", "resize_page_device", "scale_plan", "unscale_points", "RectifyParams", "find_page_quad_device", "rectify_plan", "warp_page_device", "warp_points", "SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "CleanParams", "Box", "label_components_device", "clean_page_device", "segment_page_device", "crop_lines_device",
+__all__ = ["backmap_corners", "SpacingParams", "segment_page_spaced_device", "SlantParams", "estimate_slant_device", "crop_lines_slanted_device", "slant_extent", "ColourParams", "estimate_page_colour_device", "gray_page_device", "CurlParams", "estimate_curl_device", "dewarp_page_device", "curl_shift_q8", "uncurl_points", "source_points", "box_corners", "GlyphParams", "ScaleParams", "estimate_glyph_size_device", "resize_page_device", "scale_plan", "unscale_points", "RectifyParams", "find_page_quad_device", "rectify_plan", "warp_page_device", "warp_points", "SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "CleanParams", "Box", "label_components_device", "clean_page_device", "segment_page_device", "crop_lines_device",
            "estimate_skew_device", "deskew_page_device", "flatten_page_device", "ink_integral_device", "layout_page_device", "source_corners",
            "rotate_page_device", "estimate_orientation_device", "unrotate_boxes", "unrotate_points", "bucket_width"]

@@ -15,7 +15,7 @@ import torch
 from . import _lib
 from .page import (clean_page_device, deskew_page_device, estimate_slant_device, dewarp_page_device, estimate_curl_device, estimate_glyph_size_device,
                    estimate_orientation_device, gray_page_device, estimate_skew_device, find_page_quad_device, flatten_page_device, layout_page_device,
-                   rectify_plan, resize_page_device, rotate_page_device, scale_plan, segment_page_device, warp_page_device)
+                   rectify_plan, resize_page_device, rotate_page_device, scale_plan, segment_page_device, segment_page_spaced_device, warp_page_device)
 
 MAX_BLOCKS = 256
 
@@ -144,15 +144,32 @@ def slant_params(seg, deslant, threshold=-1):
     return sp
 
 
-def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None, deslant=None):
+def spacing_params(spacing):
+    """the SpacingParams of recognize_page(spacing=...): True takes the defaults."""
+    if isinstance(spacing, _lib.SpacingParams):
+        return spacing
+    if spacing is True:
+        return _lib.SpacingParams()
+    raise ValueError(f"spacing={spacing!r}: None, False, True or an aocr.SpacingParams")
+
+
+def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None, deslant=None, spacing=None):
     """the middle of recognize_page, from the deskew to the boxes on the host: everything that reads the page in its final orientation and
     has to be redone when recognize_page(orient=True) turns the page by another half turn.  Returns a namespace: page, boxes_dev, rows, counts,
     n, truncated; skew, cleaned, curl, colour (the words read back, None without the stage), curl_group; lay, blocks, block_id, nb, lcounts
     (None without layout); slant (n, 4) and slant_dev, the words of aocr_estimate_slant for the boxes kept (None without deslant).  The
     slant estimate is enqueued right after the segmentation, on the page that was segmented, and its words come back with the boxes: no
-    readback of its own."""
-    st = SimpleNamespace(curl_group=None, lay=None, blocks=None, block_id=None, nb=None, lcounts=None, slant=None, slant_dev=None)
+    readback of its own.  spacing (n_lines, 8): the rows of aocr_segment_page_spaced, which then takes the place of aocr_segment_page (None
+    without spacing); they too come back with the boxes."""
+    st = SimpleNamespace(curl_group=None, lay=None, blocks=None, block_id=None, nb=None, lcounts=None, slant=None, slant_dev=None, spacing=None)
     skew_dev = curl_dev = None
+    spaced = spacing_params(spacing) if asked(spacing) else None
+
+    def segment(view, params):
+        """(boxes, counts, spacing rows or None) of a page or a block"""
+        if spaced is None:
+            return segment_page_device(view, params, max_boxes, stream) + (None,)
+        return segment_page_spaced_device(view, params, spaced, max_boxes, stream)
     if asked(deskew):
         sp = deskew if isinstance(deskew, _lib.SkewParams) else _lib.SkewParams(threshold=seg.threshold, light_text=seg.light_text)
         skew_dev = estimate_skew_device(page, sp, stream)
@@ -173,10 +190,10 @@ def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, 
         st.blocks = got["blocks"].reshape(MAX_BLOCKS, 6)[:nb]
         block_seg = _lib.SegmentParams(*[getattr(seg, f) for f, _ in seg._fields_][:9])
         block_seg.threshold = int(info[0])                        # the page's threshold: every block thresholds like the whole page
-        per = [segment_page_device(page[b[1]:b[3], b[0]:b[2]], block_seg, max_boxes, stream) for b in st.blocks.tolist()]
+        per = [segment(page[b[1]:b[3], b[0]:b[2]], block_seg) for b in st.blocks.tolist()]
         if nb:
-            all_boxes = torch.stack([bx for bx, _ in per])                          # (nb, max_boxes, 6)
-            all_counts = torch.stack([c for _, c in per])                           # (nb, 4)
+            all_boxes = torch.stack([bx for bx, _, _ in per])                       # (nb, max_boxes, 6)
+            all_counts = torch.stack([c for _, c, _ in per])                        # (nb, 4)
             all_boxes[:, :, :4] += blocks_dev[:nb][:, [0, 1, 0, 1]][:, None, :]
             lines_dev = all_counts[:, 1]
             all_boxes[:, :, 4] += (torch.cumsum(lines_dev, 0) - lines_dev).to(torch.int32)[:, None]
@@ -185,7 +202,8 @@ def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, 
                 sp = slant_params(seg, deslant, int(info[0]))
                 slants = [estimate_slant_device(page, all_boxes[b], all_counts[b], sp, None, stream).reshape(-1) for b in range(nb)]
             all_boxes = all_boxes.reshape(-1, 6)
-            back = torch.cat([all_counts.reshape(-1), all_boxes.reshape(-1)] + slants).cpu().numpy()     # the second sync
+            gaps = [r.reshape(-1) for _, _, r in per] if spaced is not None else []     # per block (block height + 1) // 2 rows of 8
+            back = torch.cat([all_counts.reshape(-1), all_boxes.reshape(-1)] + slants + gaps).cpu().numpy()     # the second sync
             bcounts = back[:4 * nb].reshape(nb, 4)
             taken = np.minimum(bcounts[:, 0], max_boxes)
             keep = np.concatenate([b * max_boxes + np.arange(t) for b, t in enumerate(taken.tolist())]).astype(np.int64)
@@ -193,8 +211,12 @@ def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, 
             keep_dev = torch.from_numpy(keep).to(page.device)
             st.boxes_dev = all_boxes[keep_dev]
             if slants:
-                st.slant = back[4 * nb + 6 * nb * max_boxes:].reshape(-1, 4)[keep]
+                st.slant = back[4 * nb + 6 * nb * max_boxes:4 * nb + 10 * nb * max_boxes].reshape(-1, 4)[keep]
                 st.slant_dev = torch.cat(slants).reshape(-1, 4)[keep_dev]
+            if gaps:                                            # the lines of the blocks end to end, as the line numbers run
+                tail = back[len(back) - sum(g.numel() for g in gaps):].reshape(-1, 8)
+                starts = np.cumsum([0] + [g.numel() // 8 for g in gaps[:-1]])
+                st.spacing = np.concatenate([tail[s0:s0 + n] for s0, n in zip(starts.tolist(), bcounts[:, 1].tolist())])
             st.block_id = np.repeat(np.arange(nb, dtype=np.int32), taken)
         else:
             bcounts = np.zeros((0, 4), np.int32)
@@ -203,11 +225,13 @@ def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, 
             if asked(deslant):
                 slant_params(seg, deslant)
                 st.slant, st.slant_dev = np.zeros((0, 4), np.int32), torch.zeros((0, 4), dtype=torch.int32, device=page.device)
+            if spaced is not None:
+                st.spacing = np.zeros((0, 8), np.int32)
         st.n = len(st.rows)
         st.counts = np.array([bcounts[:, 0].sum(), bcounts[:, 1].sum(), info[0], 0], np.int64)
         st.truncated = bool((bcounts[:, 0] > max_boxes).any())
     else:
-        st.boxes_dev, counts_dev = segment_page_device(page, seg, max_boxes, stream)
+        st.boxes_dev, counts_dev, gaps_dev = segment(page, seg)
         if asked(deslant):                                      # the threshold is the device word counts_dev[2] unless the params fix one
             st.slant_dev = estimate_slant_device(page, st.boxes_dev, counts_dev, slant_params(seg, deslant), counts_dev[2:3], stream)
         if all(v is None for v in riders.values()):
@@ -216,12 +240,22 @@ def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, 
             got = read_named(dict(counts=counts_dev, **riders))
         st.counts = got["counts"]
         st.n = int(min(st.counts[0], max_boxes))
-        if st.slant_dev is None:
+        if st.slant_dev is None and gaps_dev is None:
             st.rows = st.boxes_dev[:st.n].cpu().numpy()
-        else:                                                   # the slant words ride with the boxes
-            st.slant_dev = st.slant_dev[:st.n]
-            back = torch.cat([st.boxes_dev[:st.n].reshape(-1), st.slant_dev.reshape(-1)]).cpu().numpy()
-            st.rows, st.slant = back[:6 * st.n].reshape(-1, 6), back[6 * st.n:].reshape(-1, 4)
+        else:                                                   # the slant words and the spacing rows ride with the boxes
+            lines = int(st.counts[1])
+            parts = [st.boxes_dev[:st.n].reshape(-1)]
+            if st.slant_dev is not None:
+                st.slant_dev = st.slant_dev[:st.n]
+                parts.append(st.slant_dev.reshape(-1))
+            if gaps_dev is not None:
+                parts.append(gaps_dev[:lines].reshape(-1))
+            back = torch.cat(parts).cpu().numpy()
+            st.rows, at = back[:6 * st.n].reshape(-1, 6), 6 * st.n
+            if st.slant_dev is not None:
+                st.slant, at = back[at:at + 4 * st.n].reshape(-1, 4), at + 4 * st.n
+            if gaps_dev is not None:
+                st.spacing = back[at:at + 8 * lines].reshape(-1, 8)
         st.truncated = bool(st.counts[0] > max_boxes)
     st.skew, st.cleaned, st.curl, st.colour = got.get("skew"), got.get("cleaned"), got.get("curl"), got.get("colour")
     return st

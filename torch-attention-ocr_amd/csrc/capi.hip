@@ -822,6 +822,17 @@ static Span span_rows(const void* p, int64_t pitch, int64_t H, int64_t W, size_t
 static Span span_bytes(const void* p, size_t n) { return Span{(uintptr_t)p, (uintptr_t)p + n}; }
 static bool disjoint(Span a, Span b) { return a.hi <= b.lo || b.hi <= a.lo; }
 
+// a stage that writes a few words: the scratch, the page and the words lie apart.  name_dev: the words' name in the messages
+static int check_words(const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const void* scratch_dev, size_t scratch_bytes,
+                       const int32_t* words_dev, int n_words, const char* name_dev) {
+  const Span page = span_rows(page_dev, pitch, H, W), scratch = span_bytes(scratch_dev, scratch_bytes);
+  const Span words = span_bytes(words_dev, n_words * sizeof(int32_t));
+  REQUIRE(disjoint(scratch, page), "scratch_dev overlaps the page");
+  REQUIRE(disjoint(words, page), "%s overlaps the page", name_dev);
+  REQUIRE(disjoint(words, scratch), "%s overlaps the scratch", name_dev);
+  return 0;
+}
+
 // the output page of a stage, Ho x Wo (width: how the message names Wo).  between: the checks that the call reports after the pitch and
 // before the overlap
 static int check_out(const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const uint8_t* out_dev, int64_t out_pitch, int32_t Ho, int32_t Wo,
@@ -840,8 +851,9 @@ size_t aocr_segment_scratch_bytes(int32_t H, int32_t W, int32_t max_boxes) {
   return segment_scratch_bytes(H, W, max_boxes);
 }
 
-int aocr_segment_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_segment_params* params,
-                      void* scratch_dev, int32_t max_boxes, aocr_box* boxes_dev, int32_t counts_dev[4]) {
+// what aocr_segment_page and aocr_segment_page_spaced check alike, in this order
+static int check_segment(const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_segment_params* params, const void* scratch_dev,
+                         int32_t max_boxes, const aocr_box* boxes_dev, const int32_t* counts_dev) {
   if (check_page(page_dev, pitch, H, W)) return 1;
   if (check_scratch(scratch_dev, params && boxes_dev && counts_dev)) return 1;
   REQUIRE(max_boxes >= 1 && max_boxes <= 4096, "max_boxes=%d: 1..4096", max_boxes);
@@ -850,8 +862,45 @@ int aocr_segment_page(void* stream, const uint8_t* page_dev, int64_t pitch, int3
           params->min_row_ink, params->min_line_h, params->min_word_w);
   REQUIRE(params->merge_gap >= 0 && params->word_gap >= 0, "merge_gap=%d word_gap=%d must be >= 0", params->merge_gap, params->word_gap);
   REQUIRE(params->pad_x >= 0 && params->pad_y >= 0, "pad_x=%d pad_y=%d must be >= 0", params->pad_x, params->pad_y);
+  return 0;
+}
+
+int aocr_segment_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_segment_params* params,
+                      void* scratch_dev, int32_t max_boxes, aocr_box* boxes_dev, int32_t counts_dev[4]) {
+  if (check_segment(page_dev, pitch, H, W, params, scratch_dev, max_boxes, boxes_dev, counts_dev)) return 1;
   segment_page((hipStream_t)stream, page_dev, pitch, H, W, *params, scratch_dev, max_boxes, boxes_dev, counts_dev);
   return check_launch("aocr_segment_page");
+}
+
+size_t aocr_segment_spaced_scratch_bytes(int32_t H, int32_t W, int32_t max_boxes) {
+  if (!(page_size_ok(H, W) && max_boxes >= 1 && max_boxes <= 4096)) {
+    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26) max_boxes=%d (1..4096)", H, W, max_boxes);
+    return 0;
+  }
+  return segment_scratch_bytes(H, W, max_boxes);               // the estimate lives in LDS: the scratch of aocr_segment_page
+}
+
+int aocr_segment_page_spaced(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_segment_params* params,
+                             const aocr_spacing_params* spacing, void* scratch_dev, int32_t max_boxes, aocr_box* boxes_dev,
+                             int32_t counts_dev[4], int32_t max_lines, int32_t* spacing_dev) {
+  REQUIRE(spacing, "spacing is NULL");
+  if (check_segment(page_dev, pitch, H, W, params, scratch_dev, max_boxes, boxes_dev, counts_dev)) return 1;
+  REQUIRE(params->word_gap != 0, "word_gap=0 (one box per band) leaves nothing to estimate: call aocr_segment_page");
+  REQUIRE(spacing->min_gaps >= 1, "min_gaps=%d must be >= 1", spacing->min_gaps);
+  REQUIRE(1 <= spacing->lo_percent && spacing->lo_percent <= spacing->default_percent && spacing->default_percent <= spacing->hi_percent &&
+              spacing->hi_percent <= 400,
+          "lo_percent=%d default_percent=%d hi_percent=%d: 1 <= lo <= default <= hi <= 400", spacing->lo_percent, spacing->default_percent,
+          spacing->hi_percent);
+  REQUIRE(spacing->ratio_percent >= 100 && spacing->ratio_percent <= 100000, "ratio_percent=%d: 100..100000", spacing->ratio_percent);
+  REQUIRE(spacing->reserved[0] == 0 && spacing->reserved[1] == 0 && spacing->reserved[2] == 0, "reserved words must be 0");
+  REQUIRE(max_lines >= 0, "max_lines=%d must be >= 0", max_lines);
+  REQUIRE(((uintptr_t)spacing_dev & 3) == 0, "spacing_dev must be 4-byte aligned");
+  if (max_lines == 0) spacing_dev = nullptr;
+  if (spacing_dev && check_words(page_dev, pitch, H, W, scratch_dev, segment_scratch_bytes(H, W, max_boxes), spacing_dev,
+                                 8 * std::min(max_lines, (H + 1) / 2), "spacing_dev")) return 1;
+  segment_page_spaced((hipStream_t)stream, page_dev, pitch, H, W, *params, *spacing, scratch_dev, max_boxes, boxes_dev, counts_dev, max_lines,
+                      spacing_dev);
+  return check_launch("aocr_segment_page_spaced");
 }
 
 int aocr_crop_lines(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_box* boxes_dev,
@@ -1034,17 +1083,6 @@ int aocr_estimate_orientation(void* stream, const uint8_t* page_dev, int64_t pit
 }
 
 size_t aocr_quad_scratch_bytes(int32_t H, int32_t W) { return scratch_size_ok(H, W) ? quad_scratch_bytes(H, W) : 0; }
-
-// a stage that writes a few words: the scratch, the page and the words lie apart.  name_dev: the words' name in the messages
-static int check_words(const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const void* scratch_dev, size_t scratch_bytes,
-                       const int32_t* words_dev, int n_words, const char* name_dev) {
-  const Span page = span_rows(page_dev, pitch, H, W), scratch = span_bytes(scratch_dev, scratch_bytes);
-  const Span words = span_bytes(words_dev, n_words * sizeof(int32_t));
-  REQUIRE(disjoint(scratch, page), "scratch_dev overlaps the page");
-  REQUIRE(disjoint(words, page), "%s overlaps the page", name_dev);
-  REQUIRE(disjoint(words, scratch), "%s overlaps the scratch", name_dev);
-  return 0;
-}
 
 int aocr_find_page_quad(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t threshold, int32_t dark_paper,
                         void* scratch_dev, int32_t quad_dev[16]) {

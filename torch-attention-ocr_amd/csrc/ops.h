@@ -373,6 +373,11 @@ void synth_lines(hipStream_t s, const aocr_lexicon& lex, const aocr_glyph_atlas&
 size_t segment_scratch_bytes(int H, int W, int max_boxes);
 void segment_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_segment_params& p, void* scratch, int max_boxes,
                   aocr_box* boxes, int32_t* counts);
+// the same with one word gap per band, estimated from the band's own gaps (include/aocr.h: aocr_segment_page_spaced); the scratch is
+// segment_scratch_bytes; spacing_rows: max_lines rows of 8 words, or nullptr
+void segment_page_spaced(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_segment_params& p,
+                         const aocr_spacing_params& spacing, void* scratch, int max_boxes, aocr_box* boxes, int32_t* counts, int max_lines,
+                         int32_t* spacing_rows);
 // steps 1-2 of aocr_segment_page with Otsu (segment.hip): memset + histogram + Otsu; hist: 256 words, hdr[0] receives the threshold (-1: none)
 void otsu_threshold(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, uint32_t* hist, int32_t* hdr);
 // page deskew (skew.hip; include/aocr.h: aocr_estimate_skew, aocr_deskew_page): the sheared-profile sweep and the shear that removes the skew

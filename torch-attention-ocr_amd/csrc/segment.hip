@@ -14,6 +14,8 @@
 //   bands_kernel    one workgroup: text-row flags in LDS -> bands (find_runs of runs.h).
 //   colprof_kernel  one thread per column per band: consecutive threads read consecutive bytes, row after row of the band.
 //   words_kernel    one workgroup per band: ink-column flags in LDS -> words (the same find_runs); the first `cap` words of each band are kept.
+//                   words_spaced_kernel (aocr_segment_page_spaced) is the same body with the gap estimated per band in front of it: a first
+//                   find_runs for the raw runs, a 256-bin LDS histogram of their gaps, otsu_kernel's wave function on it (band_gap).
 //   offsets_kernel  one workgroup: exclusive prefix sum of the bands' word counts; writes counts_dev.
 //   emit_kernel     one wave per written box: finds its band by bisection of the offsets, sums the box's ink from the column profile,
 //                   pads, clamps and stores the box.
@@ -70,11 +72,12 @@ __global__ __launch_bounds__(256) void hist_kernel(const uint8_t* __restrict__ p
   if (s) atomicAdd(&hist[threadIdx.x], s);
 }
 
-__global__ __launch_bounds__(64) void otsu_kernel(const uint32_t* __restrict__ hist, int32_t* __restrict__ hdr) {
-  const int lane = threadIdx.x;
-  long long h[4], ln = 0, ls = 0;
+// Otsu's split of a 256-bin histogram by one wave (step 2 of aocr_segment_page): lane l holds bins 4l..4l+3 in h.  The first t in 0..254 with
+// the strictly largest score, -1 when no t has two non-empty classes; every lane returns it.
+__device__ __forceinline__ int otsu_wave(const long long (&h)[4], int lane) {
+  long long ln = 0, ls = 0;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) { h[k] = hist[4 * lane + k]; ln += h[k]; ls += (long long)(4 * lane + k) * h[k]; }
+  for (int k = 0; k < 4; ++k) { ln += h[k]; ls += (long long)(4 * lane + k) * h[k]; }
   long long pn = ln, ps = ls;                                               // inclusive prefix sums over lanes
   for (int d = 1; d < 64; d <<= 1) {
     const long long a = __shfl_up(pn, d), b = __shfl_up(ps, d);
@@ -98,6 +101,15 @@ __global__ __launch_bounds__(64) void otsu_kernel(const uint32_t* __restrict__ h
     const double ob = __shfl_xor(best, d); const int ot = __shfl_xor(bt, d);
     if (ob > best || (ob == best && ot < bt)) { best = ob; bt = ot; }
   }
+  return bt;
+}
+
+__global__ __launch_bounds__(64) void otsu_kernel(const uint32_t* __restrict__ hist, int32_t* __restrict__ hdr) {
+  const int lane = threadIdx.x;
+  long long h[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) h[k] = hist[4 * lane + k];
+  const int bt = otsu_wave(h, lane);
   if (lane == 0) hdr[0] = bt;                                               // -1: one gray value only, no ink
 }
 
@@ -138,20 +150,80 @@ __global__ __launch_bounds__(256) void colprof_kernel(const uint8_t* __restrict_
   }
 }
 
-__global__ __launch_bounds__(SEG_THREADS) void words_kernel(const uint16_t* __restrict__ col, int W, int word_gap, int min_word_w, int max_bands,
-                                                            int cap, const int32_t* __restrict__ hdr, uint32_t* __restrict__ words,
-                                                            int32_t* __restrict__ wcount) {
+// The gap of one band for aocr_segment_page_spaced (include/aocr.h, step 5): sh.flag is staged.  The raw runs (find_runs with gapmin 1), the
+// histogram of their clipped gaps in LDS (integer atomics: exact), then wave 0 alone: Otsu's split, the two occupied bins around it, the
+// decision and the spacing row.  Every thread returns the gap; sh.flag is left as it was.
+__device__ __forceinline__ int band_gap(RunsShared& sh, int W, int h, const aocr_spacing_params& sp, int32_t* __restrict__ row) {
+  __shared__ uint32_t ghist[256];
+  __shared__ int gap_sh;
+  const int K = find_runs(sh, W, 1, 1, [](int, int, int) {});              // sh.s / sh.e: the raw runs
+  if (threadIdx.x < 256) ghist[threadIdx.x] = 0;
+  __syncthreads();
+  const int lo = max(1, h * sp.lo_percent / 100), hi = max(lo, h * sp.hi_percent / 100), clip = min(hi, 255);
+  for (int j = 1 + (int)threadIdx.x; j < K; j += SEG_THREADS) atomicAdd(&ghist[min((int)sh.s[j] - (int)sh.e[j - 1], clip)], 1u);
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    const int lane = threadIdx.x, m = max(K - 1, 0);
+    long long hh[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) hh[k] = ghist[4 * lane + k];
+    const int t = otsu_wave(hh, lane);
+    int a = -1, c = SEG_NONE;                                              // the largest occupied bin <= t, the smallest one > t
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int v = 4 * lane + k;
+      if (hh[k] > 0) { if (v <= t) a = max(a, v); else c = min(c, v); }
+    }
+    for (int d = 32; d >= 1; d >>= 1) { a = max(a, __shfl_xor(a, d)); c = min(c, __shfl_xor(c, d)); }
+    if (t < 0) a = c = 0;
+    if (lane == 0) {
+      const int flag = m < sp.min_gaps ? 1 : t < 0 ? 2 : c * 100 < a * sp.ratio_percent ? 3 : 0;
+      const int est = flag == 0 ? (a + c + 1) >> 1 : max(1, h * sp.default_percent / 100);
+      const int gap = min(max(est, lo), hi);
+      gap_sh = gap;
+      if (row) {
+        row[0] = gap; row[1] = flag + (gap != est ? 4 : 0); row[2] = m; row[3] = a; row[4] = c; row[5] = h; row[6] = 0; row[7] = 0;
+      }
+    }
+  }
+  __syncthreads();
+  return gap_sh;
+}
+
+// SPACED: the gap of every band is estimated from the band (band_gap) instead of being word_gap
+template <bool SPACED>
+__device__ __forceinline__ void words_body(const uint16_t* __restrict__ col, int W, int word_gap, int min_word_w, int max_bands, int cap,
+                                           const int32_t* __restrict__ hdr, uint32_t* __restrict__ words, int32_t* __restrict__ wcount,
+                                           const uint32_t* __restrict__ bands, const aocr_spacing_params& sp, int max_lines,
+                                           int32_t* __restrict__ spacing) {
   __shared__ RunsShared sh;
   const int nb = min(hdr[1], max_bands);
-  const int gapmin = word_gap == 0 ? SEG_NONE : word_gap;                  // 0: nothing splits a band
+  int gapmin = word_gap == 0 ? SEG_NONE : word_gap;                        // 0: nothing splits a band
   for (int b = blockIdx.x; b < nb; b += gridDim.x) {
     for (int x = threadIdx.x; x < W; x += SEG_THREADS) sh.flag[x] = col[(size_t)b * W + x] >= 1;
     __syncthreads();
+    if constexpr (SPACED) {
+      const uint32_t yy = bands[b];
+      gapmin = band_gap(sh, W, (int)(yy >> 16) - (int)(yy & 0xffffu), sp, spacing && b < max_lines ? spacing + (size_t)b * 8 : nullptr);
+    }
     uint32_t* out = words + (size_t)b * cap;
     const int n = find_runs(sh, W, gapmin, min_word_w, [&](int k, int x0, int x1) { if (k < cap) out[k] = (uint32_t)x0 | ((uint32_t)x1 << 16); });
     if (threadIdx.x == 0) wcount[b] = n;
     __syncthreads();
   }
+}
+
+__global__ __launch_bounds__(SEG_THREADS) void words_kernel(const uint16_t* __restrict__ col, int W, int word_gap, int min_word_w, int max_bands,
+                                                            int cap, const int32_t* __restrict__ hdr, uint32_t* __restrict__ words,
+                                                            int32_t* __restrict__ wcount) {
+  words_body<false>(col, W, word_gap, min_word_w, max_bands, cap, hdr, words, wcount, nullptr, aocr_spacing_params{}, 0, nullptr);
+}
+
+__global__ __launch_bounds__(SEG_THREADS) void words_spaced_kernel(const uint16_t* __restrict__ col, int W, aocr_spacing_params sp, int min_word_w,
+                                                                   int max_bands, int cap, const int32_t* __restrict__ hdr,
+                                                                   const uint32_t* __restrict__ bands, uint32_t* __restrict__ words,
+                                                                   int32_t* __restrict__ wcount, int max_lines, int32_t* __restrict__ spacing) {
+  words_body<true>(col, W, 1, min_word_w, max_bands, cap, hdr, words, wcount, bands, sp, max_lines, spacing);
 }
 
 __global__ __launch_bounds__(SEG_THREADS) void offsets_kernel(const int32_t* __restrict__ wcount, int max_bands, int fixed, int32_t* __restrict__ woffset,
@@ -207,8 +279,10 @@ void otsu_threshold(hipStream_t s, const uint8_t* page, int64_t pitch, int H, in
   hipLaunchKernelGGL(otsu_kernel, dim3(1), dim3(64), 0, s, hist, hdr);
 }
 
-void segment_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_segment_params& p, void* scratch, int max_boxes,
-                  aocr_box* boxes, int32_t* counts) {
+// spacing == nullptr: aocr_segment_page; else aocr_segment_page_spaced, whose words launch estimates a gap per band
+static void segment_launches(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_segment_params& p,
+                             const aocr_spacing_params* spacing, void* scratch, int max_boxes, aocr_box* boxes, int32_t* counts, int max_lines,
+                             int32_t* spacing_rows) {
   const SegLayout l = seg_layout(H, W, max_boxes);
   uint32_t* hist = scratch_at<uint32_t>(scratch, l.hist);
   int32_t* hdr = scratch_at<int32_t>(scratch, l.hdr);
@@ -226,11 +300,26 @@ void segment_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int 
                      std::min(p.merge_gap, SEG_MAX_DIM), p.min_line_h, bands, hdr);
   hipLaunchKernelGGL(colprof_kernel, dim3(cdiv(W, 256), std::min(l.max_bands, 128)), dim3(256), 0, s, page, pitch, W, light, fixed, l.max_bands,
                      hdr, bands, col);
-  hipLaunchKernelGGL(words_kernel, dim3(std::min(l.max_bands, 128)), dim3(SEG_THREADS), 0, s, col, W, p.word_gap, p.min_word_w, l.max_bands,
-                     l.cap, hdr, words, wcount);
+  if (spacing)
+    hipLaunchKernelGGL(words_spaced_kernel, dim3(std::min(l.max_bands, 128)), dim3(SEG_THREADS), 0, s, col, W, *spacing, p.min_word_w, l.max_bands,
+                       l.cap, hdr, bands, words, wcount, max_lines, spacing_rows);
+  else
+    hipLaunchKernelGGL(words_kernel, dim3(std::min(l.max_bands, 128)), dim3(SEG_THREADS), 0, s, col, W, p.word_gap, p.min_word_w, l.max_bands,
+                       l.cap, hdr, words, wcount);
   hipLaunchKernelGGL(offsets_kernel, dim3(1), dim3(SEG_THREADS), 0, s, wcount, l.max_bands, fixed, woffset, hdr, counts);
   hipLaunchKernelGGL(emit_kernel, dim3(cdiv(max_boxes, 4)), dim3(256), 0, s, hdr, bands, woffset, words, col, H, W, l.max_bands, l.cap, p.pad_x,
                      p.pad_y, max_boxes, boxes);
+}
+
+void segment_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_segment_params& p, void* scratch, int max_boxes,
+                  aocr_box* boxes, int32_t* counts) {
+  segment_launches(s, page, pitch, H, W, p, nullptr, scratch, max_boxes, boxes, counts, 0, nullptr);
+}
+
+void segment_page_spaced(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_segment_params& p,
+                         const aocr_spacing_params& spacing, void* scratch, int max_boxes, aocr_box* boxes, int32_t* counts, int max_lines,
+                         int32_t* spacing_rows) {
+  segment_launches(s, page, pitch, H, W, p, &spacing, scratch, max_boxes, boxes, counts, max_lines, spacing_rows);
 }
 
 }  // namespace aocr
