@@ -813,6 +813,56 @@ int aocr_clean_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_
                     const aocr_clean_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch,
                     int32_t counts_dev[8]);
 
+/* ---- rule removal that keeps the text: run-length rules per pixel, after aocr_deskew_page / aocr_dewarp_page, before layout and segmentation --
+ * aocr_clean_page removes a rule only as a whole connected component, and a character that touches it goes with it: a word on its form
+ * line, an underlined word with a g, p or y, every cell text that touches a table grid.  The rule and the glyph are one component, so the
+ * decision is made per pixel, from run lengths: a rule is long one way and thin the other, and a stroke that crosses it is not thin.
+ * Integer arithmetic only, specified exactly.
+ *
+ * The page and the output follow the rules of aocr_clean_page: any base address, any pitch >= W, 1 <= H, W <= 16384, H*W <= 2^26; out_dev
+ * is H rows of W bytes, out_pitch >= W apart, bytes between W and out_pitch are untouched; the output, the page and the scratch must not
+ * overlap; counts_dev may be NULL (else 8 int32, 4-byte aligned, apart from the three).
+ *   ink         as everywhere: threshold 0..254, or -1 for Otsu (steps 1-2 of aocr_segment_page, bit for bit); ink = (v <= threshold), or
+ *               (v > threshold) with light_text; an Otsu threshold of -1 (one gray value): nothing is ink and the page is copied;
+ *   runs        for an ink pixel p = (y, x): its row run is the maximal run of ink in row y through p, columns [c, d); its column run the
+ *               maximal run of ink in column x through p, rows [a, b).  Runs end at the page's edge;
+ *   candidates  with L = min_len, T = max_thick, e = edge:  Hc(p): axes & 1, p is ink and d - c >= L;  Vc(p): axes & 2, p is ink and
+ *               b - a >= L.  Hc is the opening of the ink by a 1 x L segment, Vc the opening by an L x 1 segment;
+ *   erased      out[y][x] = fill (255, or 0 with light_text) when one of the following holds; every other byte is copied bit for bit:
+ *                 cross  Hc(p) and Vc(p): where two rules cross, neither is thin;
+ *                 byH    b - a <= T and some y' in [max(a, y - e), min(b - 1, y + e)] has Hc(y', x): a thin column run that belongs to a
+ *                        long row run; with e > 0 that includes the ragged rows directly above and below the run;
+ *                 byV    d - c <= T and some x' in [max(c, x - e), min(d - 1, x + e)] has Vc(y, x').
+ *               Because L > T, Hc(p) excludes byV and Vc(p) excludes byH: the classes need no precedence beyond counting cross first, then
+ *               byH, then byV.  A descender that crosses an underline has a column run longer than T, so every pixel of it stays, the
+ *               ones inside the rule's rows included;
+ *   counts      counts_dev = [the threshold used, the total ink, pixels erased, of them cross, of them byH and not cross, of them byV only,
+ *               candidate pixels kept ((Hc or Vc) and not erased: the strokes that cross a rule), 0].
+ * Limits: a rule thicker than T stays (all of it: none of its column runs is thin); dashed or dotted leaders are runs shorter than L; on
+ * a page that was not deskewed a rule of thickness t at slope s has runs of only about t / s pixels; the bottoms of letters that sit on
+ * a rule lose the rows within e of it; a headline stroke longer than L and no thicker than T is a rule.
+ * scratch_dev: aocr_rules_scratch_bytes(H, W) bytes, 16-byte aligned, overwritten by the call (0 and an error for bad sizes): three bit
+ * planes (ink, Hc, Vc: one uint64 per 64 columns of a row), one word per column and 64 rows, a histogram and a header: 7 / 16 of a byte
+ * per pixel, 3.7 MiB for A4 at 300 dpi, 28 MiB at H*W = 2^26.
+ * The call enqueues only, never synchronises or allocates; the result is a function of the page and the params alone (integer sums: no
+ * dependence on launch geometry or atomics order).  Invalid params (L <= T, T outside 1..16, e outside 0..4, axes outside 1..3, non-zero
+ * reserved), bad sizes, NULLs or overlap return an error before anything is enqueued and leave the outputs untouched.  A page with
+ * nothing to erase comes back identical. */
+typedef struct aocr_rule_params {
+  int32_t threshold;    /* 0..254, or -1: Otsu, steps 1-2 of aocr_segment_page, bit for bit */
+  int32_t light_text;   /* 1: ink = (v > threshold); erased pixels become 0 instead of 255 */
+  int32_t axes;         /* 1 horizontal rules, 2 vertical rules, 3 both */
+  int32_t min_len;      /* L: a run of at least L ink pixels is a rule candidate; max_thick < L <= 16384 */
+  int32_t max_thick;    /* T in 1..16: a rule is at most T pixels thick */
+  int32_t edge;         /* e in 0..4: ragged-edge pixels within e pixels of a candidate go with it */
+  int32_t reserved[2];  /* must be 0 */
+} aocr_rule_params;
+
+size_t aocr_rules_scratch_bytes(int32_t H, int32_t W);
+int aocr_remove_rules(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                      const aocr_rule_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch,
+                      int32_t counts_dev[8]);
+
 /* ---- page orientation: quarter turns, and which way the text lines run, in front of aocr_estimate_skew ------------------------------------
  * Every stage above reads row profiles and assumes that the lines run along x; aocr_estimate_skew sweeps slopes up to 0.25 only.  A page
  * fed sideways or upside down is turned here, on the device.  Integer arithmetic only, specified exactly.

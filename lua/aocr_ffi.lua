@@ -119,6 +119,9 @@ int aocr_label_components(void* stream, const uint8_t* page_dev, int64_t pitch, 
 typedef struct aocr_clean_params { int32_t threshold; int32_t light_text; int32_t connectivity; int32_t min_area; int32_t max_w, max_h; int32_t reserved[2]; } aocr_clean_params;
 size_t aocr_clean_scratch_bytes(int32_t H, int32_t W);
 int aocr_clean_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_clean_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch, int32_t counts_dev[8]);
+typedef struct aocr_rule_params { int32_t threshold; int32_t light_text; int32_t axes; int32_t min_len; int32_t max_thick; int32_t edge; int32_t reserved[2]; } aocr_rule_params;
+size_t aocr_rules_scratch_bytes(int32_t H, int32_t W);
+int aocr_remove_rules(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_rule_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch, int32_t counts_dev[8]);
 int aocr_rotate_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const int32_t* orient_dev, int32_t quarter, uint8_t* out_dev, int64_t out_pitch);
 size_t aocr_orient_scratch_bytes(int32_t H, int32_t W);
 int aocr_estimate_orientation(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, int32_t threshold, int32_t light_text, void* scratch_dev, int32_t orient_dev[8]);

@@ -105,6 +105,30 @@ class CleanParams(C.Structure):
         super().__init__(int(threshold), int(light_text), int(connectivity), int(min_area), int(max_w), int(max_h), (C.c_int32 * 2)(0, 0))
 
 
+class RuleParams(C.Structure):
+    """mirror of `aocr_rule_params` (include/aocr.h): which pixels `aocr_remove_rules` paints over.  A run of at least min_len ink pixels along
+    a row (axes & 1) or a column (axes & 2) is a rule candidate; of it go the pixels whose run across the rule is at most max_thick long,
+    the ragged pixels within `edge` of it, and the crossings of two rules; a stroke that crosses a rule is thicker and stays whole.
+    threshold -1: Otsu.  The defaults are a judgement for text at 300 dpi -- a third of an inch is longer than any stroke of body text, half a
+    millimetre thicker than a form line -- and nobody has tuned them on real scans.  The constructor raises ValueError for what the library
+    would turn down."""
+    _fields_ = [(n, C.c_int32) for n in ("threshold", "light_text", "axes", "min_len", "max_thick", "edge")] + [("reserved", C.c_int32 * 2)]
+
+    def __init__(self, threshold=-1, light_text=0, axes=3, min_len=100, max_thick=6, edge=1):
+        threshold, light_text, axes, min_len, max_thick, edge = (int(v) for v in (threshold, light_text, axes, min_len, max_thick, edge))
+        if not -1 <= threshold <= 254:
+            raise ValueError(f"threshold={threshold}: 0..254, or -1 for Otsu")
+        if axes not in (1, 2, 3):
+            raise ValueError(f"axes={axes}: 1 horizontal rules, 2 vertical rules, 3 both")
+        if not 1 <= max_thick <= 16:
+            raise ValueError(f"max_thick={max_thick}: 1..16")
+        if not max_thick < min_len <= 16384:
+            raise ValueError(f"min_len={min_len}: max_thick={max_thick} < min_len <= 16384")
+        if not 0 <= edge <= 4:
+            raise ValueError(f"edge={edge}: 0..4")
+        super().__init__(threshold, light_text, axes, min_len, max_thick, edge, (C.c_int32 * 2)(0, 0))
+
+
 class RectifyParams:
     """how `Model.recognize_page(rectify=...)` finds and straightens a photographed page (`aocr_find_page_quad`, `aocr_rectify_plan`,
     `aocr_warp_page`; plain Python: there is no C struct behind it).  threshold -1: Otsu; dark_paper 1: the paper is the dark side of the threshold
@@ -294,7 +318,9 @@ SIGNATURES = {
     "aocr_label_components": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, C.c_int64, _i32, _vp, _vp]),
     "aocr_clean_scratch_bytes": (C.c_size_t, [_i32, _i32]),
     "aocr_clean_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, C.c_int64, _vp]),
-    "aocr_rotate_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _i32, _vp, C.c_int64]),
+    "aocr_rules_scratch_bytes": (C.c_size_t, [_i32, _i32]),
+    "aocr_remove_rules": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, C.c_int64, _vp]),
+    "aocr_rotate_page": (C.c_int,[_vp, _vp, C.c_int64, _i32, _i32, _vp, _i32, _vp, C.c_int64]),
     "aocr_orient_scratch_bytes": (C.c_size_t, [_i32, _i32]),
     "aocr_estimate_orientation": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _i32, _i32, _vp, _vp]),
     "aocr_quad_scratch_bytes": (C.c_size_t, [_i32, _i32]),

@@ -437,12 +437,12 @@ class Model:
             res.word = [lexicon.words[i] if i >= 0 else None for i in res.word_index.tolist()]
         return res
 
-    def _page_boxes(self, page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None, deslant=None, spacing=None):
+    def _page_boxes(self, page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None, deslant=None, spacing=None, rules=None):
         """the middle of recognize_page (aocr.page_pipeline.page_boxes), reached through the model so that a caller can wrap it."""
-        return page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev, deslant, spacing)
+        return page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev, deslant, spacing, rules)
 
     def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None, flatten=None,
-                       layout=None, clean=None, orient=None, rectify=None, scale=None, dewarp=None, colour=None, deslant=None, spacing=None):
+                       layout=None, clean=None, orient=None, rectify=None, scale=None, dewarp=None, colour=None, deslant=None, spacing=None, rules=None):
         """Read a scanned page: segment it into word boxes (aocr_segment_page), crop them (aocr_crop_lines) and recognise the crops.
         page: a uint8 (H,W) numpy array or tensor (gray; a 3-D array raises ValueError unless `colour` is asked for: see below).  params: an
         `aocr.SegmentParams` (default: Otsu threshold, dark text).  The counts and boxes are read back once (the one sync), then the boxes are
@@ -557,7 +557,18 @@ class Model:
         (n_lines) int32, the gap used per line, spacing_flags (n_lines) int32 (0 estimated, 1 too few gaps, 2 one gap length, 3 classes
         not separated: the share of the line height was used; + 4 clamped) and spacing_gaps (n_lines) int32, the gaps counted; with
         layout they run across the blocks like the line numbers.  Limits (justified text, lines of one or two words, digits with wide
-        tracking, the band height as the em): DESIGN.md section 23."""
+        tracking, the band height as the em): DESIGN.md section 23.
+        rules: None or False (the default) reads the page with its rules.  True or an `aocr.RuleParams` takes the rules of a form or a table
+        out and keeps the text that touches them (aocr_remove_rules: per pixel, from run lengths -- a rule is long one way and thin the
+        other, a stroke that crosses it is not thin; True: both axes, runs of 100 pixels at most 6 thick, edge 1, with the threshold and
+        light_text of `params`: a judgement for 300 dpi, untuned), after deskew and dewarp (a rule is a pure row run only on a straight
+        page; an orient=True half-turn restart redoes it) and before layout and segmentation; layout, segmentation and the crops read the
+        page with the rules taken out.  The boxes do not move, so every *_corners field stays what it is.  The eight counts come back with
+        the existing readback (no additional sync).  The namespace then also carries rules_counts (8) int64 (threshold, total ink, erased,
+        crossings, of horizontal rules, of vertical rules, candidates kept, 0), rules_erased and rules_kept.  With clean: clean runs earlier
+        and still deletes a grid higher than its max_h together with what touches it: for forms pass clean=aocr.CleanParams(max_h=0) (specks
+        only) together with rules=True.  Limits (rules thicker than max_thick, dashed leaders, pages not deskewed, letter bottoms within
+        `edge` of a rule they sit on, long thin headline strokes): DESIGN.md section 24."""
         if asked(colour):
             ok = isinstance(page, (np.ndarray, torch.Tensor)) and len(page.shape) == 3 and page.shape[2] == 3 and \
                 page.dtype == (np.uint8 if isinstance(page, np.ndarray) else torch.uint8)
@@ -592,6 +603,8 @@ class Model:
         extra = dict(deslant=deslant) if asked(deslant) else {}
         if asked(spacing):
             extra["spacing"] = spacing
+        if asked(rules):
+            extra["rules"] = rules
         st = self._page_boxes(page, *middle, **extra)
         orient_scores = None
         if orient is True:
@@ -656,6 +669,9 @@ class Model:
             res.slant_deg = np.degrees(np.arctan(res.slant_q16 / 65536.0))
         if st.spacing is not None:
             res.word_gaps, res.spacing_flags, res.spacing_gaps = (st.spacing[:, k].astype(np.int32) for k in range(3))
+        if st.rules is not None:
+            res.rules_counts = st.rules.astype(np.int64)
+            res.rules_erased, res.rules_kept = int(st.rules[2]), int(st.rules[6])
         curl = skew = turn = None                                   # what each stage left behind for aocr.page.backmap_corners
         if st.curl is not None:
             res.curl_shifts, res.curl_group = st.curl[4:].astype(np.int32), st.curl_group

@@ -24,7 +24,9 @@ one slant per box from a sweep of sheared column profiles) after the segmentatio
 (`aocr_crop_lines_slanted`: the crops with every row moved back along x) takes the place of `crop_lines_device`; `slant_extent` is how far
 such a crop reaches beyond its box on either side.  The boxes do not move.  One `word_gap` cuts every line of the page into words; a page
 whose lines are set in different sizes goes through `segment_page_spaced_device` (`aocr_segment_page_spaced`: the gap of every line
-estimated from the line's own gaps) in place of `segment_page_device`."""
+estimated from the line's own gaps) in place of `segment_page_device`.  A form or a table is text that touches rules, one component with
+them: `remove_rules_device` (`aocr_remove_rules`: run lengths per pixel) takes out what is long one way and thin the other and leaves the
+strokes that cross it, after the deskew and before layout and segmentation.  The boxes do not move."""
 from __future__ import annotations
 
 import ctypes as C
@@ -33,7 +35,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import Box, CleanParams, ColourParams, CurlParams, FlattenParams, GlyphParams, LayoutParams, RectifyParams, ScaleParams, SegmentParams, SkewParams, SlantParams, SpacingParams, check, lib, ptr
+from ._lib import Box, CleanParams, ColourParams, CurlParams, FlattenParams, GlyphParams, LayoutParams, RectifyParams, RuleParams, ScaleParams, SegmentParams, SkewParams, SlantParams, SpacingParams, check, lib, ptr
 
 IMG_H = 32
 MIN_ASPECT = 0.5
@@ -271,6 +273,24 @@ def clean_page_device(page_dev, params=None, stream=None):
     counts = torch.zeros(8, dtype=torch.int32, device=dev)
     check(lib.aocr_clean_page(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), ptr(out), W, ptr(counts)),
           "aocr_clean_page")
+    return out, counts
+
+
+def remove_rules_device(page_dev, params=None, stream=None):
+    """(out, counts): out a new (H, W) uint8 device tensor, the page with its rules painted over by `aocr_remove_rules` and the strokes that
+    cross them kept (every other byte copied), and counts (8) int32: threshold, total ink, pixels erased, of them at crossings of two rules,
+    of them of horizontal rules, of them of vertical rules, candidate pixels kept, 0.  params: a `RuleParams` (default: Otsu, both axes, runs
+    of 100 pixels, 6 thick, edge 1).  Enqueues only.  stream: as for `segment_page_device`, the current torch stream; the scratch (7 / 16 of
+    a byte per pixel) is freed when this returns."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    params = params if params is not None else RuleParams()
+    dev = page_dev.device
+    scratch = _scratch("aocr_rules_scratch_bytes", dev, H, W)
+    out = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    counts = torch.zeros(8, dtype=torch.int32, device=dev)
+    check(lib.aocr_remove_rules(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), ptr(out), W, ptr(counts)),
+          "aocr_remove_rules")
     return out, counts
 
 

@@ -1,6 +1,6 @@
 """The stage chain of `Model.recognize_page` in front of the recogniser, as plain functions of the page: colour, rectify, flatten, scale, clean
-and the quarter turn (one function each, in that order), then `page_boxes`: deskew, dewarp, layout and segmentation down to the boxes on the
-host.  Every function takes the page on the device, the raw handle of the current torch stream and the page's resolved `SegmentParams`,
+and the quarter turn (one function each, in that order), then `page_boxes`: deskew, dewarp, rule removal, layout and segmentation down to
+the boxes on the host.  Every function takes the page on the device, the raw handle of the current torch stream and the page's resolved `SegmentParams`,
 enqueues on that stream, and returns the page with a small record of what it did (None when the stage was not asked for).  What needs a
 model -- the which-way-up probe, the crop-and-recognise loop, the lexicon -- stays in `Model`; the way back from box corners to the page as
 given is `aocr.page.backmap_corners`."""
@@ -15,7 +15,7 @@ import torch
 from . import _lib
 from .page import (clean_page_device, deskew_page_device, estimate_slant_device, dewarp_page_device, estimate_curl_device, estimate_glyph_size_device,
                    estimate_orientation_device, gray_page_device, estimate_skew_device, find_page_quad_device, flatten_page_device, layout_page_device,
-                   rectify_plan, resize_page_device, rotate_page_device, scale_plan, segment_page_device, segment_page_spaced_device, warp_page_device)
+                   rectify_plan, remove_rules_device, resize_page_device, rotate_page_device, scale_plan, segment_page_device, segment_page_spaced_device, warp_page_device)
 
 MAX_BLOCKS = 256
 
@@ -153,16 +153,28 @@ def spacing_params(spacing):
     raise ValueError(f"spacing={spacing!r}: None, False, True or an aocr.SpacingParams")
 
 
-def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None, deslant=None, spacing=None):
+def rule_params(seg, rules):
+    """the RuleParams of recognize_page(rules=...): True takes the defaults with the threshold and light_text of the segment params."""
+    if isinstance(rules, _lib.RuleParams):
+        return rules
+    if rules is True:
+        return _lib.RuleParams(threshold=seg.threshold, light_text=seg.light_text)
+    raise ValueError(f"rules={rules!r}: None, False, True or an aocr.RuleParams")
+
+
+def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None, deslant=None, spacing=None, rules=None):
     """the middle of recognize_page, from the deskew to the boxes on the host: everything that reads the page in its final orientation and
     has to be redone when recognize_page(orient=True) turns the page by another half turn.  Returns a namespace: page, boxes_dev, rows, counts,
     n, truncated; skew, cleaned, curl, colour (the words read back, None without the stage), curl_group; lay, blocks, block_id, nb, lcounts
     (None without layout); slant (n, 4) and slant_dev, the words of aocr_estimate_slant for the boxes kept (None without deslant).  The
     slant estimate is enqueued right after the segmentation, on the page that was segmented, and its words come back with the boxes: no
     readback of its own.  spacing (n_lines, 8): the rows of aocr_segment_page_spaced, which then takes the place of aocr_segment_page (None
-    without spacing); they too come back with the boxes."""
+    without spacing); they too come back with the boxes.  rules: aocr_remove_rules after the deskew and the dewarp (a rule is a pure row run
+    only on a straight page) and before layout and segmentation (a column-separator rule sits in the gutter the XY cut looks for); st.page
+    is then the page with the rules taken out, st.rules its eight counts, which ride with the first readback (None without rules)."""
     st = SimpleNamespace(curl_group=None, lay=None, blocks=None, block_id=None, nb=None, lcounts=None, slant=None, slant_dev=None, spacing=None)
-    skew_dev = curl_dev = None
+    skew_dev = curl_dev = rules_dev = None
+    ruled = rule_params(seg, rules) if asked(rules) else None
     spaced = spacing_params(spacing) if asked(spacing) else None
 
     def segment(view, params):
@@ -179,8 +191,10 @@ def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, 
         words_dev, shifts_dev = estimate_curl_device(page, cp, stream)
         page = dewarp_page_device(page, shifts_dev, cp.group, paper(seg), stream)
         curl_dev, st.curl_group = [words_dev, shifts_dev], int(cp.group)      # the four curl words, then the ng group shifts
+    if ruled is not None:
+        page, rules_dev = remove_rules_device(page, ruled, stream)
     st.page = page
-    riders = dict(skew=skew_dev, cleaned=clean_dev, curl=curl_dev, colour=colour_dev)            # what comes back with the first readback, whichever it is
+    riders = dict(skew=skew_dev, cleaned=clean_dev, curl=curl_dev, colour=colour_dev, rules=rules_dev)            # what comes back with the first readback, whichever it is
     if asked(layout):
         st.lay = layout if isinstance(layout, _lib.LayoutParams) else _lib.LayoutParams()
         blocks_dev, lcounts_dev, info_dev = layout_page_device(page, st.lay, seg.threshold, seg.light_text, MAX_BLOCKS, stream)
@@ -257,5 +271,5 @@ def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, 
             if gaps_dev is not None:
                 st.spacing = back[at:at + 8 * lines].reshape(-1, 8)
         st.truncated = bool(st.counts[0] > max_boxes)
-    st.skew, st.cleaned, st.curl, st.colour = got.get("skew"), got.get("cleaned"), got.get("curl"), got.get("colour")
+    st.skew, st.cleaned, st.curl, st.colour, st.rules = got.get("skew"), got.get("cleaned"), got.get("curl"), got.get("colour"), got.get("rules")
     return st

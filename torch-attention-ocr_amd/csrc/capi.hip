@@ -1058,6 +1058,36 @@ int aocr_clean_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_
   return check_launch("aocr_clean_page");
 }
 
+size_t aocr_rules_scratch_bytes(int32_t H, int32_t W) { return scratch_size_ok(H, W) ? rules_scratch_bytes(H, W) : 0; }
+
+int aocr_remove_rules(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_rule_params* params,
+                      void* scratch_dev, uint8_t* out_dev, int64_t out_pitch, int32_t counts_dev[8]) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(params, "params is NULL");
+  if (check_threshold(params->threshold)) return 1;
+  REQUIRE(params->axes >= 1 && params->axes <= 3, "axes=%d: 1 horizontal, 2 vertical, 3 both", params->axes);
+  REQUIRE(params->max_thick >= 1 && params->max_thick <= 16, "max_thick=%d: 1..16", params->max_thick);
+  REQUIRE(params->min_len > params->max_thick && params->min_len <= 16384, "min_len=%d: max_thick=%d < min_len <= 16384", params->min_len,
+          params->max_thick);
+  REQUIRE(params->edge >= 0 && params->edge <= 4, "edge=%d: 0..4", params->edge);
+  REQUIRE(params->reserved[0] == 0 && params->reserved[1] == 0, "reserved words must be 0");
+  if (check_scratch(scratch_dev, out_dev)) return 1;
+  REQUIRE(((uintptr_t)counts_dev & 3) == 0, "counts_dev must be 4-byte aligned");
+  if (check_out(page_dev, pitch, H, W, out_dev, out_pitch, H, W)) return 1;
+  const Span page = span_rows(page_dev, pitch, H, W), out = span_rows(out_dev, out_pitch, H, W);
+  const Span scratch = span_bytes(scratch_dev, rules_scratch_bytes(H, W));
+  REQUIRE(disjoint(out, scratch), "out_dev overlaps the scratch");
+  REQUIRE(disjoint(scratch, page), "scratch_dev overlaps the page");
+  if (counts_dev) {
+    const Span counts = span_bytes(counts_dev, 8 * sizeof(int32_t));
+    REQUIRE(disjoint(counts, page), "counts_dev overlaps the page");
+    REQUIRE(disjoint(counts, out), "counts_dev overlaps out_dev");
+    REQUIRE(disjoint(counts, scratch), "counts_dev overlaps the scratch");
+  }
+  remove_rules((hipStream_t)stream, page_dev, pitch, H, W, *params, scratch_dev, out_dev, out_pitch, counts_dev);
+  return check_launch("aocr_remove_rules");
+}
+
 int aocr_rotate_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const int32_t* orient_dev, int32_t quarter,
                      uint8_t* out_dev, int64_t out_pitch) {
   if (check_page(page_dev, pitch, H, W)) return 1;

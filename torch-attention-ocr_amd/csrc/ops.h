@@ -425,6 +425,11 @@ void label_components(hipStream_t s, const uint8_t* page, int64_t pitch, int H, 
 size_t clean_scratch_bytes(int H, int W);
 void clean_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_clean_params& p, void* scratch, uint8_t* out,
                 int64_t out_pitch, int32_t* counts);
+// rule removal that keeps the text (rules.hip; include/aocr.h: aocr_remove_rules): run-length rules per pixel on bit planes of the ink; counts
+// may be nullptr
+size_t rules_scratch_bytes(int H, int W);
+void remove_rules(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_rule_params& p, void* scratch, uint8_t* out,
+                  int64_t out_pitch, int32_t* counts);
 // where the launches of label_components leave every component's area (components.hip): the record of the component whose first pixel in
 // raster order is (rx, ry) is the four words at rec + 4 * (ry * sw + (rx >> 1)): area, min x, max x, max y.  scratch: label_components' own
 struct ComponentAreas { const int32_t* rec; int sw; };
