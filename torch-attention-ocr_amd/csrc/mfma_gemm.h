@@ -19,12 +19,17 @@
 #include <stdint.h>
 #include <type_traits>
 #include <utility>
+#include "halo4_skip.h"
 
 namespace aocr {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a compile-time constant in the body
+template <int... I, class F> __device__ __forceinline__ void aocr_static_for_impl(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F> __device__ __forceinline__ void aocr_static_for(F&& f) { aocr_static_for_impl(std::make_integer_sequence<int, N>{}, f); }
 
 // one operand fragment of a 32-row tile for one k-chunk: 4 floats (f32 mode, chunk 8)
 // or 8 floats (bf16 mode, chunk 16) per lane.
@@ -1104,7 +1109,8 @@ struct EpConv; struct EpStore;
 // (2,1)-pooled bf16 + arg-max tile of conv4 / conv6 in one; anything else returns false (-> the quad epilogue).
 // the fp32 tile of a 256 x 256 workgroup: two passes of 128 rows (the waves with wm == pass hold them) through a [128][256] fp32 LDS image.
 // NI = 32-column accumulator tiles per wave (wave tile 128 x 32 NI), NTH = threads of the workgroup.
-template <int NI, int NTH>
+// ILV (all three tiles): acc[mi] of wave-row wm is the tile's 32-row block 2 mi + wm instead of 4 wm + mi (gemm_halo4_bf16_kernel's SKIP form, halo4_skip.h).
+template <int NI, int NTH, bool ILV = false>
 __device__ __forceinline__ void tile256_store_f32(float* dst, int64_t ldc, const float* bias, bool relu, const f32x16 (&acc)[4][NI], unsigned char* lds,
                                                   int m_blk, int n_blk, int wm, int wn, int r, int h, int tid, double* part = nullptr, int C = 0, const float* bias2 = nullptr,
                                                   const float* bnb_x = nullptr, const bf16_t* bnb_yb = nullptr, const float* bnb_save = nullptr) {
@@ -1122,9 +1128,11 @@ __device__ __forceinline__ void tile256_store_f32(float* dst, int64_t ldc, const
   float ps[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   __syncthreads();                                        // every wave is out of the K loop
   for (int p = 0; p < 2; ++p) {
-    if (wm == p) {
+    if (ILV || wm == p) {                                 // ILV: every wave holds two blocks of either pass (mi = 2 p, 2 p + 1 -> blocks wm, 2 + wm of the pass)
 #pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
+      for (int mi = 0; mi < 4; ++mi) {
+        if (ILV && (mi >> 1) != p) continue;
+        const int lrow = ILV ? (2 * (mi & 1) + wm) * 32 : mi * 32;
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
@@ -1133,8 +1141,9 @@ __device__ __forceinline__ void tile256_store_f32(float* dst, int64_t ldc, const
             for (int i = 0; i < 4; ++i) {
               float x = acc[mi][ni][4 * q + i] + bb[ni];
               if (relu) x = fmaxf(x, 0.f);
-              *reinterpret_cast<float*>(lds + (mi * 32 + 8 * q + 4 * h + i) * PITCH + (wn * 32 * NI + ni * 32 + r) * 4) = x;
+              *reinterpret_cast<float*>(lds + (lrow + 8 * q + 4 * h + i) * PITCH + (wn * 32 * NI + ni * 32 + r) * 4) = x;
             }
+      }
     }
     __syncthreads();
     float* const d0 = dst + (int64_t)(m_blk + p * 128) * ldc + n_blk;
@@ -1217,7 +1226,8 @@ __device__ __forceinline__ void tile256_store_pooled(bf16_t* yb, uint8_t* idxp, 
   }
 }
 // the bf16-only tile (evaluation mode: conv3 / conv5 with their BatchNorm + ReLU folded in, EpConv::bn_save): [256][256] bf16 = 128 KB, one pass
-template <int NI, int NTH>
+// (ILV: never with part -- a lane's fp32 column sums run over its own rows, so another ownership rounds them differently)
+template <int NI, int NTH, bool ILV = false>
 __device__ __forceinline__ void tile256_store_bf16(bf16_t* yb, int Cout, const float* bias, bool relu, const float* bn_save, const float* bn_w, const float* bn_b,
                                                    const f32x16 (&acc)[4][NI], unsigned char* lds, int m_blk, int n_blk, int wm, int wn, int r, int h, int tid, double* part = nullptr) {
   float bb[NI], mu[NI], iv[NI], ww[NI], b2[NI];
@@ -1243,7 +1253,7 @@ __device__ __forceinline__ void tile256_store_bf16(bf16_t* yb, int Cout, const f
           if (relu) x = fmaxf(x, 0.f);
           if (bn_save) x = fmaxf((x - mu[ni]) * iv[ni] * ww[ni] + b2[ni], 0.f);      // the same expression as EpConv::quad / bn_apply_relu_kernel
           ps[ni] += x; pss[ni] = fmaf(x, x, pss[ni]);                                 // (part: column sums of the UNROUNDED values, 64 per lane and column)
-          *reinterpret_cast<bf16_t*>(lds + (wm * 128 + mi * 32 + 8 * q + 4 * h + i) * 512 + (wn * 32 * NI + ni * 32 + r) * 2) = (bf16_t)x;
+          *reinterpret_cast<bf16_t*>(lds + ((ILV ? 2 * mi + wm : 4 * wm + mi) * 32 + 8 * q + 4 * h + i) * 512 + (wn * 32 * NI + ni * 32 + r) * 2) = (bf16_t)x;
         }
   __syncthreads();
 #pragma unroll 4
@@ -1271,23 +1281,23 @@ __device__ __forceinline__ void tile256_store_bf16(bf16_t* yb, int Cout, const f
   }
 }
 // full 256 x 256 tiles only (the callers' grids may end in a ragged tile: that one takes the quad epilogue)
-template <int NI, int NTH, class EP>
+template <int NI, int NTH, bool ILV = false, class EP>
 __device__ __forceinline__ bool tile256_store_staged(const EP& ep, const f32x16 (&acc)[4][NI], unsigned char* lds, int m_blk, int n_blk, int wm, int wn, int r, int h, int tid, int opt) {
   if constexpr (std::is_same<EP, EpConv>::value) {
     if (m_blk + 256 > ep.rows || n_blk + 256 > ep.Cout) return false;
     if (ep.pmode == 0 && ep.y16 && ep.bn_part && !ep.yb && !ep.bn_save && (opt & 2)) {     // pre-BatchNorm output as bf16 + its statistics (training)
-      tile256_store_bf16<NI, NTH>(ep.y16, ep.Cout, ep.bias, ep.relu != 0, nullptr, nullptr, nullptr, acc, lds, m_blk, n_blk, wm, wn, r, h, tid, ep.bn_part); return true; }
-    if (ep.pmode == 0 && ep.yb && !ep.y && (opt & 2)) { tile256_store_bf16<NI, NTH>(ep.yb, ep.Cout, ep.bias, ep.relu != 0, ep.bn_save, ep.bn_w, ep.bn_b, acc, lds, m_blk, n_blk, wm, wn, r, h, tid); return true; }
+      tile256_store_bf16<NI, NTH, ILV>(ep.y16, ep.Cout, ep.bias, ep.relu != 0, nullptr, nullptr, nullptr, acc, lds, m_blk, n_blk, wm, wn, r, h, tid, ep.bn_part); return true; }
+    if (ep.pmode == 0 && ep.yb && !ep.y && (opt & 2)) { tile256_store_bf16<NI, NTH, ILV>(ep.yb, ep.Cout, ep.bias, ep.relu != 0, ep.bn_save, ep.bn_w, ep.bn_b, acc, lds, m_blk, n_blk, wm, wn, r, h, tid); return true; }
     if (ep.bn_save) return false;
-    if (ep.pmode == 2 && ep.yb && ep.idx && !ep.y && (opt & 4)) { tile256_store_pooled<NI, NTH>(ep.yb, ep.idx, ep.Cout, ep.bias, ep.relu != 0, acc, lds, m_blk, n_blk, wm, wn, r, h, tid); return true; }
-    if (ep.pmode == 0 && ep.y && !ep.yb && (opt & 2)) { tile256_store_f32<NI, NTH>(ep.y, ep.Cout, ep.bias, ep.relu != 0, acc, lds, m_blk, n_blk, wm, wn, r, h, tid, ep.bn_part, ep.Cout); return true; }
+    if (!ILV && ep.pmode == 2 && ep.yb && ep.idx && !ep.y && (opt & 4)) { tile256_store_pooled<NI, NTH>(ep.yb, ep.idx, ep.Cout, ep.bias, ep.relu != 0, acc, lds, m_blk, n_blk, wm, wn, r, h, tid); return true; }
+    if (ep.pmode == 0 && ep.y && !ep.yb && (opt & 2)) { tile256_store_f32<NI, NTH, ILV>(ep.y, ep.Cout, ep.bias, ep.relu != 0, acc, lds, m_blk, n_blk, wm, wn, r, h, tid, ep.bn_part, ep.Cout); return true; }
     return false;
   } else if constexpr (std::is_same<EP, EpStore>::value) {
     if (!ep.C && ep.Cb && !ep.flags && !ep.bias && !ep.bias2 && !ep.C1 && !ep.dg) {       // bf16-only data gradient (conv_backward_data's dx16: full tiles guaranteed by the caller)
-      tile256_store_bf16<NI, NTH>(ep.Cb, (int)ep.ldcb, nullptr, false, nullptr, nullptr, nullptr, acc, lds, m_blk, n_blk, wm, wn, r, h, tid); return true; }
+      tile256_store_bf16<NI, NTH, ILV>(ep.Cb, (int)ep.ldcb, nullptr, false, nullptr, nullptr, nullptr, acc, lds, m_blk, n_blk, wm, wn, r, h, tid); return true; }
     if (ep.flags || ep.bias || ep.bias2 || ep.C1 || ep.Cb || ep.dg || !(opt & 1) || m_blk + 256 > ep.M || n_blk + 256 > ep.N) return false;
-    if (ep.bnb_part) tile256_store_f32<NI, NTH>(ep.C, ep.ldc, nullptr, false, acc, lds, m_blk, n_blk, wm, wn, r, h, tid, ep.bnb_part, ep.N, nullptr, ep.bnb_x, ep.bnb_yb, ep.bnb_save);
-    else tile256_store_f32<NI, NTH>(ep.C, ep.ldc, nullptr, false, acc, lds, m_blk, n_blk, wm, wn, r, h, tid);      // (taking the biases here too cost the data-gradient kernel 157 -> 190 us: register pressure in its K loop)
+    if (ep.bnb_part) tile256_store_f32<NI, NTH, ILV>(ep.C, ep.ldc, nullptr, false, acc, lds, m_blk, n_blk, wm, wn, r, h, tid, ep.bnb_part, ep.N, nullptr, ep.bnb_x, ep.bnb_yb, ep.bnb_save);
+    else tile256_store_f32<NI, NTH, ILV>(ep.C, ep.ldc, nullptr, false, acc, lds, m_blk, n_blk, wm, wn, r, h, tid);      // (taking the biases here too cost the data-gradient kernel 157 -> 190 us: register pressure in its K loop)
     return true;
   } else return false;
 }
@@ -1671,7 +1681,15 @@ void gemm_halo_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const 
 //   6 + H(t-2) + 2 H(t-1) + H(t), H = 1 while tap <= 4); the <= 36 halo groups of a chunk are all issued by tap 4, so they have
 //   landed long before the last step's barrier.  Same k order per output element as the 8-wave kernel: bit-identical results.
 // ---------------------------------------------------------------------------
-template <class EP, int SGN, int TAG = 0>
+//   SKIP (the default wherever the pixel order is plain, ops_gemm.hip's halo4_skip_eligible; AOCR_NO_HALO4_SKIP=1: the form above): with pad 1 the
+//   kernel row dy = -1 of the first map row and dy = +1 of the last multiply the zero rows of the halo -- at the C3 shapes 1/6 (4 x 64 maps: the tile is
+//   the image) or 1/12 (8 x 64) of all MFMAs.  A 32-pixel block lies in one map row (W % 32 == 0), so such a block's MFMAs and A reads can go; but with
+//   wave-row wm holding blocks 4 wm + mi the first row's blocks all belong to wave-row 0 and the last row's to wave-row 1, and a step costs what its
+//   slowest wave costs (the barrier in its middle).  So the wave-rows INTERLEAVE: acc[mi] of wave-row wm is block 2 mi + wm, every wave has half of every
+//   map row (W >= 64) and loses the same number of blocks in the same steps: the first n (dy = -1) or the last n (dy = +1) of its four, n <= 2
+//   (halo4_skip.h), a wave-uniform count taken once per tile.  A shortened half-step keeps every B read and every LDS-DMA piece in its order (the vmcnt
+//   counts stand) and spreads them evenly over the MFMAs that remain.  A skipped product adds +0 per term: bit-identical outputs for finite weights.
+template <class EP, int SGN, int TAG = 0, bool SKIP = false>
 __global__ __launch_bounds__(256, 1)
 void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const bf16_t* zero, int opt) {
   unsigned long long pe0 = 0; if constexpr (TAG == 1) pe0 = wall_clock64();
@@ -1695,7 +1713,7 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
   unsigned abase[4][3];                                  // as in the 8-wave kernel: (halo row ty, col tx + dxi), k-chunk h
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi) {
-    const int local = wm * 128 + mi * 32 + r;
+    const int local = halo4_block(SKIP, wm, mi) * 32 + r;
     int ty, tx;
     if (g.pmode == 1) { const int win = local >> 2, wx = win % g.Wp; ty = 2 * (win / g.Wp) + ((local >> 1) & 1); tx = 2 * wx + (local & 1); }
     else if (g.pmode == 2) { const int win = local >> 1; tx = win % W; ty = 2 * (win / W) + (local & 1); }
@@ -1705,6 +1723,12 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
       const int col = tx + dxi, sw = ((col >> 2) & 3) ^ ((ty & 1) << 1);
       abase[mi][dxi] = lbase + (unsigned)(ty * P + col) * 64u + (unsigned)((h ^ sw) << 4);
     }
+  }
+  // SKIP: this wave's dead blocks in the steps of halo row 0 (the first ntop of its four) and of halo row 2 (the last nbot); plain pixel order only
+  int ntop = 0, nbot = 0;
+  if constexpr (SKIP) {
+    ntop = __builtin_amdgcn_readfirstlane(halo4_ndead(wm, 0, W, H, y0));
+    nbot = __builtin_amdgcn_readfirstlane(halo4_ndead(wm, 2, W, H, y0));
   }
   const int swzb = (r >> 2) & 3;
   unsigned boff[2];
@@ -1793,6 +1817,11 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
     AOCR_DSR(b0[0], boff[0], 0); AOCR_DSR(b0[1], boff[0], 2048); AOCR_DSR(b0[2], boff[0], 4096); AOCR_DSR(b0[3], boff[0], 6144);
   }
   unsigned long long pc0 = 0, pw0 = 0; if constexpr (TAG == 1) { pc0 = __builtin_readcyclecounter(); pw0 = wall_clock64(); }
+  typedef std::integral_constant<int, 0> I0; typedef std::integral_constant<int, 1> I1; typedef std::integral_constant<int, 2> I2; typedef std::integral_constant<int, 4> I4;
+  // the K loop for a wave whose first NTOP blocks are dead at halo row 0 and whose last NBOT at halo row 2 (without SKIP: 0, 0).  The counts are compile-time
+  // and the wave branches ONCE, in front of the loop: a branch around MFMAs inside it made the compiler move the 256 accumulator registers at every join
+  auto kloop = [&](auto ntc, auto nbc) {
+  constexpr int NTOP = decltype(ntc)::value, NBOT = decltype(nbc)::value;
   for (int chunk = 0; chunk < NC; ++chunk) {
     const unsigned hb = (chunk & 1) * HMAX, hbn = ((chunk + 1) & 1) * HMAX;
     const int chn = chunk + 1 < NC ? chunk + 1 : chunk;   // the chunk whose halo streams in (last chunk: its own again, into the other buffer)
@@ -1807,7 +1836,36 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
       const unsigned bs1 = (unsigned)((step & 3) * BSLOT), bs0n = (unsigned)(((step + 1) & 3) * BSLOT);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // F0(s), read under the MFMAs of the previous half
       AOCR_SB();
+      // ---- SKIP: a half-step with the live accumulators LO .. HI-1 (halo4_skip.h places its ops).  RALL: A reads of all four blocks (half 2 in front
+      // of a new kernel row, whose dead blocks are others), otherwise of the live ones (a dead block's registers keep their old value, which no MFMA takes)
+      auto half_op = [&](auto halfc, auto codec) {
+        constexpr int HALF = decltype(halfc)::value, CODE = decltype(codec)::value, ARG = CODE & 3;
+        if constexpr (CODE < 4) { if constexpr (HALF == 0) AOCR_DSR(a1[ARG], a_addr(ARG, TAP, 1), 0); else AOCR_DSR(a0[ARG], a_addr(ARG, TN, 0), 0); }
+        else if constexpr (CODE < 8) { if constexpr (HALF == 0) AOCR_DSR(b1[ARG], boff[1] + bs1, ARG * 2048); else AOCR_DSR(b0[ARG], boff[0] + bs0n, ARG * 2048); }
+        else if constexpr (CODE < 12) issue_b1(step + 3, k3, 2 * HALF + ARG);
+        else issue_halo_i(2 * TAP + HALF, chn, hbn);
+      };
+      auto half_skip = [&](auto halfc, auto loc, auto hic, auto rallc) {
+        constexpr int HALF = decltype(halfc)::value, LO = decltype(loc)::value, HI = decltype(hic)::value;
+        constexpr int RLO = decltype(rallc)::value ? 0 : LO, RHI = decltype(rallc)::value ? 4 : HI;
+        constexpr int NM = 4 * (HI - LO), NO = halo4_nops(RLO, RHI, HT != 0);
+        aocr_static_for<NM>([&](auto jc) {
+          constexpr int J = decltype(jc)::value, MI = LO + J / 4, NI = J % 4;
+          if constexpr (HALF == 0) acc[MI][NI] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[MI], b0[NI], acc[MI][NI], 0, 0, 0);
+          else acc[MI][NI] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[MI], b1[NI], acc[MI][NI], 0, 0, 0);
+          AOCR_SB();
+          aocr_static_for<NO>([&](auto kc) {
+            constexpr int K = decltype(kc)::value;
+            if constexpr (halo4_op_at(K, NM, NO) == J) half_op(halfc, std::integral_constant<int, halo4_op(K, RLO, RHI, HT != 0)>{});
+          });
+          AOCR_SB();
+        });
+      };
+      constexpr int DY = halo4_tap_dyi(SGN, TAP);          // halo row of this step's taps: 0 / 2 have dead blocks in the first / last map row
+      constexpr bool RALL2 = TN % 3 == 0;
+      typedef std::integral_constant<int, NTOP> LO0; typedef std::integral_constant<int, 4 - NBOT> HI2;
       // ---- half 1
+      auto half1_full = [&] {
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi) {
 #pragma unroll
@@ -1821,11 +1879,16 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
           AOCR_SB();
         }
       }
+      };
+      if constexpr (DY == 0 && NTOP > 0) half_skip(I0{}, LO0{}, I4{}, std::false_type{});
+      else if constexpr (DY == 2 && NBOT > 0) half_skip(I0{}, I0{}, HI2{}, std::false_type{});
+      else half1_full();
       asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NVM) : "memory");   // own weight pieces of step s+1 landed; F1(s) back
       __builtin_amdgcn_s_barrier();                       // ... everyone's; everyone is done with weight slot s-1 and (last tap) with this chunk's first-half reads
       AOCR_SB();
       // ---- half 2 (its reads are the next step's first k-half: a new kernel row / chunk moves the A address table first)
       if (TN % 3 == 0) { set_ab(TN == 0 ? hbn : hb, TN / 3); AOCR_SB(); }
+      auto half2_full = [&] {
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi) {
 #pragma unroll
@@ -1839,11 +1902,28 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
           AOCR_SB();
         }
       }
+      };
+      typedef std::integral_constant<bool, RALL2> RA;
+      if constexpr (DY == 0 && NTOP > 0) half_skip(I1{}, LO0{}, I4{}, RA{});
+      else if constexpr (DY == 2 && NBOT > 0) half_skip(I1{}, I0{}, HI2{}, RA{});
+      else half2_full();
     };
     step_fn(std::integral_constant<int, 0>{}); step_fn(std::integral_constant<int, 1>{}); step_fn(std::integral_constant<int, 2>{});
     step_fn(std::integral_constant<int, 3>{}); step_fn(std::integral_constant<int, 4>{}); step_fn(std::integral_constant<int, 5>{});
     step_fn(std::integral_constant<int, 6>{}); step_fn(std::integral_constant<int, 7>{}); step_fn(std::integral_constant<int, 8>{});
   }
+  };
+  if constexpr (SKIP) {                                   // wave-uniform (scalar) counts; every form passes the same barriers
+    if (ntop == 0 && nbot == 0) kloop(I0{}, I0{});        // (a tile in the middle of a tall map)
+    else if (ntop == 1 && nbot == 1) kloop(I1{}, I1{});   // 4 x 64: the tile is the image
+    else if (ntop == 1 && nbot == 0) kloop(I1{}, I0{});   // 8 x 64, upper tile; W = 32, wave-row 0
+    else if (ntop == 0 && nbot == 1) kloop(I0{}, I1{});
+    else if (ntop == 2 && nbot == 2) kloop(I2{}, I2{});   // 2 x 128
+    else if (ntop == 2 && nbot == 0) kloop(I2{}, I0{});
+    else if (ntop == 0 && nbot == 2) kloop(I0{}, I2{});
+    else if (ntop == 1) kloop(I1{}, I0{});                // (no such shape: skip what one form covers; fewer skipped blocks are always correct)
+    else kloop(I0{}, I0{});
+  } else kloop(I0{}, I0{});
 #undef AOCR_DSR
 #undef AOCR_SB
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // the trailing (zero-page) pieces and reads must land before the LDS is released
@@ -1852,8 +1932,8 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
 #pragma unroll
   for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(a0[i]), "v"(b0[i]), "v"(a1[i]), "v"(b1[i]));
   if constexpr (TAG == 1) { if ((blockIdx.x == 17 || blockIdx.x == 300) && tid == 0) { const int o = blockIdx.x == 17 ? 4 : 0; g_kprobe[o] = __builtin_readcyclecounter() - pc0; g_kprobe[o + 1] = wall_clock64() - pw0; g_kprobe[o + 2] = pw0 - pe0; } }
-  const int m0 = m_blk + wm * 128, n0 = n_blk + wn * 128;
-  if (tile256_store_staged<4, 256>(ep, acc, lds, m_blk, n_blk, wm, wn, r, h, tid, opt)) {
+  const int m0 = m_blk + (SKIP ? wm * 32 : wm * 128), n0 = n_blk + wn * 128;          // SKIP: block 2 mi + wm
+  if (tile256_store_staged<4, 256, SKIP>(ep, acc, lds, m_blk, n_blk, wm, wn, r, h, tid, opt)) {
     if constexpr (TAG == 1) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); if ((blockIdx.x == 17 || blockIdx.x == 300) && tid == 0) g_kprobe[blockIdx.x == 17 ? 7 : 3] = wall_clock64() - pe0; }
     return;
   }
@@ -1866,7 +1946,7 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
       for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[ni][i] = acc[mi][ni][4 * q + i];
-      ep.template quad<4>(m0 + 32 * mi + 8 * q + 4 * h, n0 + r, 32, v);
+      ep.template quad<4>(m0 + (SKIP ? 64 : 32) * mi + 8 * q + 4 * h, n0 + r, 32, v);
     }
   };
   store_mi(std::integral_constant<int, 0>{}); store_mi(std::integral_constant<int, 1>{});
@@ -2477,8 +2557,6 @@ __global__ __launch_bounds__(256) void wgrad_slab_reduce_kernel(WgDmaArgs g) {
 // A K step never straddles an image row: rows of W % 32 != 0 pixels end with a ragged segment whose pixel slots past W are zero in both operands (round 6: the
 // reference-default shape's 25- / 50-wide maps, the width buckets of C4).  Cout % 256 == 0 (128: MG = 2), Cin % 32 == 0.
 // ---------------------------------------------------------------------------
-template <int... I, class F> __device__ __forceinline__ void aocr_static_for_impl(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F> __device__ __forceinline__ void aocr_static_for(F&& f) { aocr_static_for_impl(std::make_integer_sequence<int, N>{}, f); }
 template <int TAG = 0, int MG = 4, bool RG = false, bool IM = false>       // RG: ragged rows (W % 32 != 0); the whole-segment form keeps its constant pointer steps and has no validity compare on d y.  IM: the DMA issue between the two k-halves' MFMAs, which start as soon as their own fragments are back (AOCR_NO_WGRAD_ISSUE_MID=1: the one-wait form)
 __global__ __launch_bounds__(128 * MG, 1)
 void conv_wgrad_halo_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, float* __restrict__ part, long long pstride,

@@ -16,8 +16,9 @@ static void split_k(int K, int chunk, int& ksplit, int& kper) {
 // "[aocr] <function>: <kernel>[<instantiation>] M N K", so the kernel tests can prove which branch a shape reached
 static thread_local const char* t_trace_fn = nullptr;
 struct TraceScope { explicit TraceScope(const char* fn) { t_trace_fn = fn; } ~TraceScope() { t_trace_fn = nullptr; } };
-static void trace_launch(const char* kernel, const char* inst, long long M, long long N, long long K) {
-  if (t_trace_fn && knob::AOCR_TRACE()) fprintf(stderr, "[aocr] %s: %s[%s] %lld %lld %lld\n", t_trace_fn, kernel, inst, M, N, K);
+// (note: a word behind the line for a variant that keeps the kernel's name and instantiation -- gemm_halo4_bf16_kernel's "skip")
+static void trace_launch(const char* kernel, const char* inst, long long M, long long N, long long K, const char* note = nullptr) {
+  if (t_trace_fn && knob::AOCR_TRACE()) fprintf(stderr, "[aocr] %s: %s[%s] %lld %lld %lld%s%s\n", t_trace_fn, kernel, inst, M, N, K, note ? " " : "", note ? note : "");
 }
 // the recurrent-step launchers' line: the instantiation names the template arguments that differ between their branches -- NT, the GATES kind (0 plain, 1 gate
 // tiles, 2 half gate tiles), waves and, for two row tiles per workgroup, "mt2": gemm_step_kernel[2,2,w8], gemm_step_kernel[4,1,w4,mt2]
@@ -103,6 +104,16 @@ static bool halo_eligible(const LoadConvK& g, int N, int MT, int NT) {
   if (g.Hr % R || (g.pmode != 0 && (R & 1)) || g.C % 32 || N % NT || g.rows % MT || g.K != 9 * g.C) return false;
   return true;
 }
+// "this launch of the 4-wave halo kernel takes its SKIP form" (interleaved blocks per wave-row, the padding rows' dead blocks skipped): plain pixel order -- the
+// pooled orders put a pool window's rows side by side, so no 32-pixel block lies in one map row -- with blocks inside one map row (W % 32 == 0) and whole rows per
+// tile (256 % W == 0; halo_eligible's widths all are).  Not with AOCR_BN_Y16's epilogue, whose fp32 column sums depend on which rows a lane holds.
+// AOCR_NO_HALO4_SKIP=1: the first form everywhere (the parity reference and the A/B baseline)
+template <class EP>
+static bool halo4_skip_eligible(const LoadConvK& g, const EP& ep) {
+  if (knob::AOCR_NO_HALO4_SKIP() || g.pmode != 0 || g.Wr % 32 || 256 % g.Wr) return false;
+  if constexpr (std::is_same<EP, EpConv>::value) { if (ep.y16 && ep.bn_part) return false; }
+  return true;
+}
 void kprobe_read(unsigned long long out[8]) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_kprobe), 64); }
 template <int SGN, int MT, int NT, class EP>
 static void launch_halo(hipStream_t s, const LoadConvKh& a, const LoadKh& b, const EP& ep, int M, int N, int tag = 0) {
@@ -110,8 +121,11 @@ static void launch_halo(hipStream_t s, const LoadConvKh& a, const LoadKh& b, con
   if constexpr (MT == 256 && NT == 256) {                 // four waves of 128 x 128 with hand-placed reads / DMA (AOCR_HALO8=1: the 8-wave kernel; bit-identical)
     if (!knob::AOCR_HALO8()) {
       const int opt = knob::AOCR_HALO4_STAGED();   // staged256's bits
-      trace_launch("gemm_halo4_bf16_kernel", SGN > 0 ? "fwd" : "dgrad", M, N, 9LL * a.g.C);
-      if (tag) hipLaunchKernelGGL((gemm_halo4_bf16_kernel<EP, SGN, 1>), dim3(gx * gy), dim3(256), 0, s, a, b, ep, gx, gy, zero_page(), opt);
+      const bool skip = halo4_skip_eligible(a.g, ep);
+      trace_launch("gemm_halo4_bf16_kernel", SGN > 0 ? "fwd" : "dgrad", M, N, 9LL * a.g.C, skip ? "skip" : nullptr);
+      if (skip && tag) hipLaunchKernelGGL((gemm_halo4_bf16_kernel<EP, SGN, 1, true>), dim3(gx * gy), dim3(256), 0, s, a, b, ep, gx, gy, zero_page(), opt);
+      else if (skip) hipLaunchKernelGGL((gemm_halo4_bf16_kernel<EP, SGN, 0, true>), dim3(gx * gy), dim3(256), 0, s, a, b, ep, gx, gy, zero_page(), opt);
+      else if (tag) hipLaunchKernelGGL((gemm_halo4_bf16_kernel<EP, SGN, 1>), dim3(gx * gy), dim3(256), 0, s, a, b, ep, gx, gy, zero_page(), opt);
       else hipLaunchKernelGGL((gemm_halo4_bf16_kernel<EP, SGN>), dim3(gx * gy), dim3(256), 0, s, a, b, ep, gx, gy, zero_page(), opt);
       return;
     }
