@@ -173,6 +173,41 @@ int aocr_sgd_step(aocr_model* m, float lr, float clip, float* norms_dev);
  * (what optim_adadelta.lua:37 means; the line itself would raise).  No clipping (:31-57). */
 int aocr_adadelta_step(aocr_model* m, float rho, float eps, float weight_decay, float* state_dev);
 
+/* AdamW (Adam with decoupled weight decay) with a per-group gradient clip, on the device.  No reference counterpart: the reference ships
+ * sgd_list and adadelta_list only.  aocr_adam_update is a model-free leaf like aocr_gemm / aocr_pointwise (explicit pointers, any 4-byte-aligned
+ * params_dev / grads_dev); aocr_adam_step applies it to the model's parameters and gradients on the model's stream.
+ * Groups: group_off[0..5], 0 = group_off[0] <= ... <= group_off[5] = n (the offsets aocr_param_counts sums to; a group may be empty).
+ * Norms and clip, per group k: pn[k] = ||w_k||_2 and gn[k] = ||g_k||_2, squares summed in double (one partial per workgroup, then a
+ *   fixed-order sum: no float atomics, the same bits on every run), the root taken in double;
+ *   scale[k] = (clip > 0 && gn[k] > clip) ? (float)((double)clip / gn[k]) : 1.0f, compared in double.  An empty group: norms 0, scale 1.
+ *   norms_dev (NULL or 15 floats) receives pn[5], gn[5] (each rounded to float once), scale[5].
+ * State: state_dev holds 2n floats {m | v} and, at byte offset 8n, a 32-byte tail {double p1, double p2, int64 steps, int64 reserved};
+ *   aocr_adam_state_bytes(n) = 8n + 32 bytes, 8-byte aligned, zeroed by the caller before the first step and kept between steps.
+ *   All-zero state is a fresh optimizer: steps == 0 reads p1 = p2 = 1.0.  Per applied step, by one thread, ahead of the element update:
+ *   p1 *= (double)beta1; p2 *= (double)beta2; steps += 1; c1 = (float)(1.0 - p1); c2 = (float)(1.0 - p2) -- running products, not pow.
+ * Element i of group k, all fp32, every operation rounded on its own (no fused multiply-add; '/' and sqrtf correctly rounded), in this order:
+ *   g  = grad[i] * scale[k]
+ *   m' = beta1*m + (1.0f-beta1)*g
+ *   v' = beta2*v + (1.0f-beta2)*(g*g)
+ *   u  = (m'/c1) / (sqrtf(v'/c2) + eps)
+ *   w' = w - lr*(u + wd*w)                 (decoupled decay; wd = 0 adds 0*w)
+ *   w, m, v are written; grads_dev is NOT modified (aocr_sgd_step's clip rescales it in place), so the gradient taps stay readable.
+ * skip_dev: NULL or one device int32; non-zero = nothing is written, not w, m, v nor the tail; norms_dev is still written.
+ * scratch_dev: aocr_adam_scratch_bytes() bytes, 8-byte aligned, overwritten by the call; calls on one stream may share it.
+ * Errors, all before anything is enqueued (non-zero return, aocr_last_error set, every output untouched): a params member that is not finite,
+ *   beta1 or beta2 outside [0, 1), eps <= 0, lr < 0, weight_decay < 0, clip < 0, a non-zero reserved word, group_off[0] != 0 or decreasing
+ *   offsets, state_dev not 8-byte aligned, a NULL pointer other than skip_dev / norms_dev.
+ * aocr_adam_step: the skip word is the model's time-out latch (aocr_cluster_status), consumed as aocr_sgd_step consumes it; a skipped step also
+ *   restores the BatchNorm running statistics from the step's snapshot.  A data-parallel all-reduce of the gradients goes before this call.
+ *   The bf16 weight shadows are refreshed at the start of the next forward pass, as after the other optimizers.
+ * No host sync in either call. */
+typedef struct aocr_adam_params { float lr, beta1, beta2, eps, weight_decay, clip; int32_t reserved[2]; } aocr_adam_params;
+size_t aocr_adam_state_bytes(int64_t n);
+size_t aocr_adam_scratch_bytes(void);
+int aocr_adam_update(void* stream, float* params_dev, const float* grads_dev, void* state_dev, const int64_t group_off[6],
+                     const aocr_adam_params* p, const int32_t* skip_dev, void* scratch_dev, float* norms_dev);
+int aocr_adam_step(aocr_model* m, const aocr_adam_params* p, void* state_dev, float* norms_dev);
+
 /* Teacher-forced forward only (no gradients).  training!=0 uses batch statistics
  * in BatchNorm (without touching running stats); logits_dev (L,B,vocab) receives the
  * pre-LogSoftMax projector output (output_projector.lua:5), loss_dev[0] the NLL sum. */

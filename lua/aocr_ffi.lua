@@ -52,6 +52,12 @@ int aocr_comm_info(aocr_model* m, int32_t* nranks, int32_t* sync_bn, int32_t* pr
 int aocr_comm_exposed_ms(aocr_model* m, float* ms);
 int aocr_sgd_step(aocr_model* m, float lr, float clip, float* norms_dev);
 int aocr_adadelta_step(aocr_model* m, float rho, float eps, float weight_decay, float* state_dev);
+typedef struct aocr_adam_params { float lr, beta1, beta2, eps, weight_decay, clip; int32_t reserved[2]; } aocr_adam_params;
+size_t aocr_adam_state_bytes(int64_t n);
+size_t aocr_adam_scratch_bytes(void);
+int aocr_adam_update(void* stream, float* params_dev, const float* grads_dev, void* state_dev, const int64_t group_off[6],
+                     const aocr_adam_params* p, const int32_t* skip_dev, void* scratch_dev, float* norms_dev);
+int aocr_adam_step(aocr_model* m, const aocr_adam_params* p, void* state_dev, float* norms_dev);
 int aocr_forward_logits(aocr_model* m, const float* images_dev, const int32_t* targets_dev, const int32_t* targets_eval_dev, int32_t B, int32_t W, int32_t L, int32_t training, float* logits_dev, float* loss_dev);
 int aocr_decode(aocr_model* m, const float* images_dev, const int32_t* targets_dev, const int32_t* targets_eval_dev, int32_t B, int32_t W, int32_t L, int32_t beam, int32_t* labels_dev, float* scores_dev, float* gold_scores_dev, float* loss_dev);
 typedef struct aocr_trie { const uint64_t* child_mask_dev; const int32_t* child_base_dev; const int32_t* child_dev; int32_t n_nodes, n_edges; } aocr_trie;

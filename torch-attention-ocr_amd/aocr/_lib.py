@@ -47,6 +47,25 @@ class SynthStyle(C.Structure):
     _fields_ = [("word", C.c_int32), ("face", C.c_int32)] + [(n, C.c_float) for n in ("spacing", "sx", "sy", "x0", "y0", "fg", "bg")]
 
 
+class AdamParams(C.Structure):
+    """mirror of `aocr_adam_params` (include/aocr.h): AdamW's step size, the two decay rates of the moment estimates, the denominator's eps,
+    the decoupled weight decay and the per-group gradient-norm clip (0: no clip).  The constructor raises ValueError for what the library
+    would turn down."""
+    _fields_ = [(n, C.c_float) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "clip")] + [("reserved", C.c_int32 * 2)]
+
+    def __init__(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip=0.0):
+        b1, b2 = (float(b) for b in betas)
+        lr, eps, weight_decay, clip = float(lr), float(eps), float(weight_decay), float(clip)
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"betas={betas!r}: each in [0, 1)")
+        if not (0.0 < eps < float("inf")):
+            raise ValueError(f"eps={eps}: finite and > 0")
+        for name, v in (("lr", lr), ("weight_decay", weight_decay), ("clip", clip)):
+            if not (0.0 <= v < float("inf")):
+                raise ValueError(f"{name}={v}: finite and >= 0")
+        super().__init__(lr, b1, b2, eps, weight_decay, clip, (C.c_int32 * 2)(0, 0))
+
+
 class SegmentParams(C.Structure):
     """mirror of `aocr_segment_params` (include/aocr.h): how `aocr_segment_page` finds lines and words.  threshold -1: Otsu."""
     _fields_ = [(n, C.c_int32) for n in ("threshold", "light_text", "min_row_ink", "merge_gap", "min_line_h", "word_gap", "min_word_w",
@@ -266,6 +285,10 @@ SIGNATURES = {
     "aocr_comm_info": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
     "aocr_sgd_step": (C.c_int, [_vp, _f32, _f32, _vp]),
     "aocr_adadelta_step": (C.c_int, [_vp, _f32, _f32, _f32, _vp]),
+    "aocr_adam_state_bytes": (_sz, [_i64]),
+    "aocr_adam_scratch_bytes": (_sz, []),
+    "aocr_adam_update": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(AdamParams), _vp, _vp, _vp]),
+    "aocr_adam_step": (C.c_int, [_vp, C.POINTER(AdamParams), _vp, _vp]),
     "aocr_forward_logits": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "aocr_decode": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "aocr_decode_dict": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),

@@ -83,6 +83,8 @@ class Model:
         self.global_step = 0
         self.optim_state = {}
         self.last_norms = None
+        self.last_norms_adam = None
+        self.optimizer, self.adam_opts, self.adam_state = "sgd", {}, None
         self._comm_stream = None
         self._buckets = None
         self._drop_last_gs, self._drop_repeat = None, 0
@@ -115,8 +117,23 @@ class Model:
         comp = g("compute")
         self.compute = _lib.COMPUTE_BF16 if comp in ("bf16", 1) else _lib.COMPUTE_F32
 
+    def _set_optimizer(self, config):
+        """which update `train_step_device` / `step` apply: optimizer="sgd" (the default: optim.sgd_list at optim_state.learningRate, clip 5) or
+        "adam" (AdamW, `adam_step`) with adam=dict(lr=, betas=, eps=, weight_decay=, clip=)."""
+        get = config.get if isinstance(config, dict) else (lambda k, d=None: getattr(config, k, d))
+        opt = get("optimizer", None) or "sgd"
+        if opt not in ("sgd", "adam"):
+            raise ValueError(f"optimizer={opt!r}: 'sgd' or 'adam'")
+        opts = dict(get("adam", None) or {})
+        unknown = sorted(set(opts) - {"lr", "betas", "eps", "weight_decay", "clip"})
+        if unknown:
+            raise ValueError(f"adam={opts!r}: unknown keys {unknown}")
+        _lib.AdamParams(**opts)                               # raises ValueError for what the library would turn down
+        self.optimizer, self.adam_opts = opt, opts
+
     def create(self, config):
         """model:create, model.lua:83-112: fresh parameters (Torch7 default init distributions [upstream])."""
+        self._set_optimizer(config)
         self._set_structure(config)
         self._set_runtime(config)
         self.global_step = 0
@@ -134,6 +151,7 @@ class Model:
         if magic[:2] != b"PK":                       # not a torch.save zip: a Torch7 file (the reference's checkpoint or our flat export)
             return self._load_t7(model_path, config)
         ck = torch.load(model_path, map_location="cpu", weights_only=True)        # tensors + plain containers only: no pickle execution
+        self._set_optimizer(config)
         self._set_structure(ck["config"])
         merged = dict(ck["config"])
         for k in ("max_encoder_l", "max_decoder_l", "batch_size", "prealloc", "img_h", "max_img_w", "max_beam", "compute"):
@@ -147,12 +165,20 @@ class Model:
         self._build()
         self.params.copy_(ck["params"].to(self.params.device))
         self.bn_state.copy_(ck["bn_state"].to(self.params.device))
+        self.adam_state = None
+        if "adam_state" in ck:                                # AdamW's moments and step bookkeeping (save writes the key only when the state exists)
+            st = ck["adam_state"]
+            if st.dtype != torch.uint8 or st.numel() != lib.aocr_adam_state_bytes(self.num_params):
+                raise ValueError(f"{model_path}: adam_state of {st.numel()} {st.dtype} elements, expected {lib.aocr_adam_state_bytes(self.num_params)} bytes")
+            self._adam_alloc().copy_(st.to(self.params.device))
         return self
 
     def _load_t7(self, model_path, config):
         """model:load on a Torch7-serialized checkpoint (model.lua:51-59): aocr.checkpoint pulls the tensors out of the nets."""
         from .checkpoint import read_t7_checkpoint
         ck = read_t7_checkpoint(model_path)
+        self._set_optimizer(config)
+        self.adam_state = None                                # the .t7 layouts carry no optimizer state
         merged = dict(_DEFAULTS); merged.update({k: v for k, v in ck["config"].items() if v is not None})
         self._set_structure(merged)
         for k in ("max_encoder_l", "max_decoder_l", "batch_size", "prealloc", "img_h", "max_img_w", "max_beam", "compute"):
@@ -345,6 +371,9 @@ class Model:
             dist.exchange_overlapped(self.grad_params, loss_dev, self._buckets, self._wait_bucket, self._comm_stream)
         if dist.world_size() > 1 and getattr(self, "_comm_cb", None) is None and not getattr(self, "_comm_rccl", False):
             self._exchange_timeout_flag()
+        if self.optimizer == "adam":
+            self.adam_step(**self.adam_opts)
+            return loss_dev
         norms = self._scal[2:12]
         check(lib.aocr_sgd_step(self._h, float(self.optim_state["learningRate"]), 5.0, ptr(norms)), "aocr_sgd_step")
         self.last_norms = norms
@@ -834,6 +863,31 @@ class Model:
             self.adadelta_state = torch.zeros(2 * self.num_params, dtype=torch.float32, device=self.device)
         check(lib.aocr_adadelta_step(self._h, rho, eps, weight_decay, ptr(self.adadelta_state)), "aocr_adadelta_step")
 
+    def _adam_alloc(self):
+        """`self.adam_state`: aocr_adam_state_bytes zeroed bytes on the device ({m | v | 32-byte tail}, include/aocr.h), 8-byte aligned."""
+        nbytes = lib.aocr_adam_state_bytes(self.num_params)
+        self._adam_words = torch.zeros(nbytes // 8, dtype=torch.int64, device=self.device)
+        self.adam_state = self._adam_words.view(torch.uint8)
+        return self.adam_state
+
+    def adam_step(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip=0.0):
+        """AdamW (include/aocr.h: aocr_adam_step) on the gradients of the last train_forward_backward, which it leaves as they are.  The state
+        lives in `self.adam_state` (allocated zeroed on first use: a fresh optimizer); the 15 norms {param norm[5], grad norm[5], clip scale[5]}
+        stay on the device in `self.last_norms_adam`.  Enqueues only: no host sync."""
+        if self.adam_state is None:
+            self._adam_alloc()
+        if getattr(self, "_adam_norms", None) is None:
+            self._adam_norms = torch.zeros(15, dtype=torch.float32, device=self.device)
+        p = _lib.AdamParams(lr, betas, eps, weight_decay, clip)
+        check(lib.aocr_adam_step(self._h, C.byref(p), ptr(self.adam_state), ptr(self._adam_norms)), "aocr_adam_step")
+        self.last_norms_adam = self._adam_norms
+
+    def adam_steps(self) -> int:
+        """updates AdamW has applied (the `steps` word of the state's tail; skipped steps do not count).  Synchronises."""
+        if self.adam_state is None:
+            return 0
+        return int(self._adam_words[self.num_params + 2].item())
+
     # ------------------------------------------------------------------ misc API of the reference class
     def vis(self, output_dir):
         """model:vis, model.lua:708-718."""
@@ -864,12 +918,20 @@ class Model:
                 import warnings
                 warnings.warn(f"Model.save({str(model_path)!r}): writing the flat 'aocr-flat-1' table; the reference's model:load "
                               "(src/model/model.lua:52-60) reads layout='reference' (or the Lua glue of INTEGRATION.md)", stacklevel=2)
+            if self.adam_state is not None and not getattr(self, "_t7_adam_warned", False):
+                import warnings
+                self._t7_adam_warned = True
+                warnings.warn(f"Model.save({str(model_path)!r}): the Torch7 layouts do not carry the AdamW state (adam_state); a run resumed from "
+                              "this file restarts its optimizer -- save without .t7 to keep it", stacklevel=2)
             writer = write_reference_checkpoint if layout == "reference" else write_flat_checkpoint
             writer(model_path, {k: v.numpy() for k, v in self.get_parameters().items()},
                    {k: v.numpy() for k, v in self.get_bn_state().items()}, self.config, self.global_step, self.optim_state)
             return
-        torch.save({"params": self.params.detach().cpu(), "bn_state": self.bn_state.detach().cpu(), "config": self.config,
-                    "global_step": self.global_step, "optim_state": dict(self.optim_state)}, model_path)
+        ck = {"params": self.params.detach().cpu(), "bn_state": self.bn_state.detach().cpu(), "config": self.config,
+              "global_step": self.global_step, "optim_state": dict(self.optim_state)}
+        if self.adam_state is not None:
+            ck["adam_state"] = self.adam_state.detach().cpu()
+        torch.save(ck, model_path)
 
     def sync_bn_state(self):
         """COLLECTIVE (every rank calls it): averages the BatchNorm running statistics over the ranks.  Needed only when the step ran

@@ -316,6 +316,48 @@ int aocr_adadelta_step(aocr_model* m, float rho, float eps, float weight_decay, 
   return check_launch("aocr_adadelta_step");
 }
 
+size_t aocr_adam_state_bytes(int64_t n) { return n < 0 ? 0 : (size_t)n * 8 + 32; }
+size_t aocr_adam_scratch_bytes(void) { return adam_scratch_bytes(); }
+static int check_adam_params(const aocr_adam_params* p) {
+  REQUIRE(p, "NULL params");
+  REQUIRE(std::isfinite(p->lr) && std::isfinite(p->beta1) && std::isfinite(p->beta2) && std::isfinite(p->eps) && std::isfinite(p->weight_decay) && std::isfinite(p->clip),
+          "lr=%g beta1=%g beta2=%g eps=%g weight_decay=%g clip=%g: not finite", p->lr, p->beta1, p->beta2, p->eps, p->weight_decay, p->clip);
+  REQUIRE(p->beta1 >= 0.f && p->beta1 < 1.f && p->beta2 >= 0.f && p->beta2 < 1.f, "beta1=%g beta2=%g outside [0, 1)", p->beta1, p->beta2);
+  REQUIRE(p->eps > 0.f, "eps=%g must be > 0", p->eps);
+  REQUIRE(p->lr >= 0.f && p->weight_decay >= 0.f && p->clip >= 0.f, "lr=%g weight_decay=%g clip=%g must be >= 0", p->lr, p->weight_decay, p->clip);
+  REQUIRE(p->reserved[0] == 0 && p->reserved[1] == 0, "reserved words must be 0");
+  return 0;
+}
+static int check_adam_state(const void* state_dev) {
+  REQUIRE(state_dev, "NULL state");
+  REQUIRE(((uintptr_t)state_dev & 7) == 0, "state_dev must be 8-byte aligned");
+  return 0;
+}
+int aocr_adam_update(void* stream, float* params_dev, const float* grads_dev, void* state_dev, const int64_t group_off[6],
+                     const aocr_adam_params* p, const int32_t* skip_dev, void* scratch_dev, float* norms_dev) {
+  if (check_adam_params(p) || check_adam_state(state_dev)) return 1;
+  REQUIRE(params_dev && grads_dev && group_off && scratch_dev, "NULL argument");
+  REQUIRE(((uintptr_t)params_dev & 3) == 0 && ((uintptr_t)grads_dev & 3) == 0 && ((uintptr_t)scratch_dev & 7) == 0, "params / grads must be 4-byte aligned, scratch 8-byte aligned");
+  REQUIRE(group_off[0] == 0, "group_off[0]=%lld must be 0", (long long)group_off[0]);
+  for (int k = 0; k < AOCR_NUM_GROUPS; ++k) REQUIRE(group_off[k + 1] >= group_off[k], "group_off decreases at %d", k + 1);
+  const AdamHyper h = {p->lr, p->beta1, p->beta2, p->eps, p->weight_decay, p->clip};
+  adam_update((hipStream_t)stream, params_dev, grads_dev, state_dev, group_off, h, skip_dev, scratch_dev, norms_dev);
+  return check_launch("aocr_adam_update");
+}
+int aocr_adam_step(aocr_model* m, const aocr_adam_params* p, void* state_dev, float* norms_dev) {
+  REQUIRE(m, "NULL model");
+  if (check_adam_params(p) || check_adam_state(state_dev)) return 1;
+  // scratch: the BatchNorm layers' partial-sum block -- every kernel of the step that used it is in front of this call on the model's stream, and the
+  // workspace keeps its size
+  REQUIRE(bn_scratch_bytes(512) >= adam_scratch_bytes(), "the BatchNorm scratch block is smaller than aocr_adam_scratch_bytes()");
+  prof_mark(m, AOCR_PROF_SGD);
+  optim_latch_restore(m->s, m->cl_err, m->bn_snap ? m->bn_state : nullptr, m->bn_snap, (int)aocr_bn_state_count());
+  const AdamHyper h = {p->lr, p->beta1, p->beta2, p->eps, p->weight_decay, p->clip};
+  adam_update(m->s, m->params, m->grads, state_dev, m->layout.group_off, h, m->cl_err ? m->cl_err + CL_ERR_LATCH : nullptr, m->bn_scratch, norms_dev);
+  prof_mark(m, -1);
+  return check_launch("aocr_adam_step");
+}
+
 int aocr_forward_logits(aocr_model* m, const float* images_dev, const int32_t* targets_dev, const int32_t* targets_eval_dev,
                         int32_t B, int32_t W, int32_t L, int32_t training, float* logits_dev, float* loss_dev) {
   Dims d; if (step_dims(m, B, W, L, d)) return 1;

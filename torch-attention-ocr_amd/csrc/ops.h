@@ -225,6 +225,15 @@ void step_snapshot(hipStream_t s, const float* bn_state, float* bn_snap, int n, 
 size_t sgd_scratch_bytes();
 void adadelta_update(hipStream_t s, float* params, float* grads, float* var, float* acc, int64_t n, float rho, float eps, float wd, int* err = nullptr,
                      float* bn_state = nullptr, const float* bn_snap = nullptr, int bn_n = 0);
+// AdamW on the flat vector (optim.hip; the arithmetic: include/aocr.h, aocr_adam_update).  state: {m | v | 32-byte tail}; skip: nullptr or one device word,
+// non-zero = write nothing but norms_out (nullptr or 15 floats); scratch: adam_scratch_bytes().  grads is read only.
+struct AdamHyper { float lr, beta1, beta2, eps, wd, clip; };
+size_t adam_scratch_bytes();
+void adam_update(hipStream_t s, float* params, const float* grads, void* state, const int64_t* group_off /*6 host values*/, const AdamHyper& h,
+                 const int* skip, void* scratch, float* norms_out);
+// the time-out half of an optimizer call whose update lives outside ops_misc.hip: the latch of the code (cl_err_latch) and, on a latched code, the restore of
+// the BatchNorm running statistics -- the code sgd_update_kernel / adadelta_kernel run, not a copy of it (ops_misc.hip).  The update then reads err[CL_ERR_LATCH].
+void optim_latch_restore(hipStream_t s, int* err, float* bn_state, const float* bn_snap, int bn_n);
 // one 2-D piece of the per-step bf16 weight shadow refresh (shadow_jobs_kernel); tile0 = first 32x32 tile of the piece, tx = tiles per row
 struct ShadowJob { const float* w; bf16_t* wb; bf16_t* wtb; int64_t ld, ldb, ldt; int R, C, tile0, tx; };
 void shadow_jobs(hipStream_t s, const ShadowJob* jobs_dev, int njobs, int total_tiles, int tile_off = 0);      // tiles [tile_off, tile_off + total_tiles) of the table

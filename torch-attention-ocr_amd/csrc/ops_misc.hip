@@ -2234,6 +2234,16 @@ void adadelta_update(hipStream_t s, float* params, float* grads, float* var, flo
   if (err) hipLaunchKernelGGL(cl_err_latch_kernel, dim3(1), dim3(1), 0, s, err);
   hipLaunchKernelGGL(adadelta_kernel, dim3(2048), dim3(256), 0, s, params, grads, var, acc, n, rho, eps, wd, skip, bn_state, bn_snap, bn_n);
 }
+// An optimizer whose update kernel lives in another file (optim.hip's AdamW) shares the skipped-step path instead of copying it: the latch, then
+// adadelta_kernel over ZERO parameters -- on a latched code its skip branch restores the running statistics, otherwise its update loop runs no
+// iteration, and its parameter / state pointers are never read.
+void optim_latch_restore(hipStream_t s, int* err, float* bn_state, const float* bn_snap, int bn_n) {
+  if (!err) return;
+  hipLaunchKernelGGL(cl_err_latch_kernel, dim3(1), dim3(1), 0, s, err);
+  if (bn_state)
+    hipLaunchKernelGGL(adadelta_kernel, dim3(cdiv(bn_n, 256)), dim3(256), 0, s, nullptr, nullptr, nullptr, nullptr, (int64_t)0, 0.f, 0.f, 0.f, err + CL_ERR_LATCH,
+                       bn_state, bn_snap, bn_n);
+}
 
 // =============================================================================================
 // beam search bookkeeping, model.lua:399-404, 446-458, 516-535, 573-585.
