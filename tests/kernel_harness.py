@@ -21,6 +21,9 @@ SWITCHES = ("AOCR_FORCE_DMA", "AOCR_HALO8", "AOCR_HALO4_STAGED", "AOCR_NO_HALO",
             "AOCR_HH_NARROW_FULL_ONLY", "AOCR_NO_HH_CAT", "AOCR_NO_WGRAD_DMA_GROUPED", "AOCR_WGRAD_DMA_MINK", "AOCR_DX16", "AOCR_NO_DMA",
             "AOCR_NO_HH_NARROW", "AOCR_NO_NARROW_WIDE", "AOCR_WGRAD_HALO_MINN", "AOCR_BN_Y16", "AOCR_NO_BN_STATS_FUSE", "AOCR_BNB_FUSE",
             "AOCR_WGRAD_DMA_WGS", "AOCR_BN_PARTIAL_OLD", "AOCR_UNPOOL4", "AOCR_CONV1_SCALAR",
+            # the exact-fp32 conv / GEMM / step launchers
+            "AOCR_NO_LDS_F32", "AOCR_NO_F32T", "AOCR_F32T_TILE", "AOCR_NO_F32W", "AOCR_F32W_MINK", "AOCR_NO_STEP_F32", "AOCR_STEP_F32_W16",
+            "AOCR_NO_QUARTER_TILES",
             # the recurrent-step launchers
             "AOCR_NO_HALF_TILES", "AOCR_HALF_TILES_MAXGRID", "AOCR_NO_STEP_MT2", "AOCR_STEP_MT2_MINK", "AOCR_NO_STEPL", "AOCR_STEPL_MIN_WGS",
             "AOCR_STEP_WAVES4", "AOCR_STEP_WAVES16", "AOCR_BIG_STEP", "AOCR_BIG_STEP_MIN_ROWS",
@@ -44,6 +47,8 @@ _STEP = [vp, i32, vp, i32, i32]                                       # stream, 
 _INT = {                                                              # return int: hipGetLastError(), a yes / no, or a constant
     "kp_conv_forward": [vp, i32, vp, vp, vp, vp, vp] + [i32] * 9 + [vp] * 8,
     "kp_conv_backward_data": [vp, i32, vp, vp, vp] + [i32] * 7 + [vp, vp, vp],
+    "kp_conv_weight_transpose_f32": [vp, vp, vp, i32, i32, i32],
+    "kp_conv_backward_data_f32": [vp, vp, vp, vp, vp] + [i32] * 7,
     "kp_conv_backward_filter": [vp, i32, vp, vp, vp, vp] + [i32] * 7 + [vp, vp, vp, sz],
     "kp_conv_weight_shadows": [vp, vp, vp, vp, i32, i32, i32],
     "kp_splitk_reduce": [vp, vp, i32, sz, vp],
@@ -71,6 +76,10 @@ _INT = {                                                              # return i
     # the fused recurrent-step launchers (tests/test_step_kernels_bf16_gpu.py)
     "kp_small_gates_fwd_hh": _STEP, "kp_small_gates_fwd_h": _STEP, "kp_small_hh": _STEP, "kp_small_h": _STEP,
     "kp_small_gates_bwd_hh": _STEP, "kp_small_gates_bwd_h": _STEP,
+    # their exact-fp32 forms (tests/test_kernels_f32_gpu.py, tests/test_step_kernels_f32_gpu.py)
+    "kp_big_kk_f32": [vp, vp, i32, i32, i32],
+    "kp_small_f32_gates_fwd": _STEP, "kp_small_f32_kk": _STEP, "kp_small_f32_kmn": _STEP, "kp_small_f32_gates_bwd_kk": _STEP,
+    "kp_small_f32_gates_bwd": _STEP,
     "kp_gates_elem_bwd": [vp, vp, i32, i32],
     "kp_big_step_store": [vp, vp, i32, i32, vp],
     "kp_big_step_gates_fwd": [vp, vp, i32, i32, vp, sz, vp],
@@ -262,6 +271,94 @@ class Mat:
                            self.init.view(torch.int16 if now.dtype == torch.bfloat16 else torch.int32)), f"{what}: write outside its columns"
 
 
+# ---- the flat problem structs of tests/kprobe.hip's recurrent-step wrappers (KpOperand, KpStore, KpGatesFwd, KpGatesBwd), field by field
+class Operand(C.Structure):
+    _fields_ = [("p0", vp), ("ld0", i64), ("K0", i32), ("p1", vp), ("ld1", i64), ("K1", i32), ("rows", i32)]
+
+
+class Store(C.Structure):
+    _fields_ = [("a", Operand), ("b", Operand), ("C", vp), ("ldc", i64), ("bias", vp), ("bias2", vp), ("flags", i32),
+                ("C1", vp), ("ldc1", i64), ("N0", i32), ("Cb", vp), ("ldcb", i64), ("dg", vp), ("dout", vp), ("ldd", i64)]
+
+
+class GatesFwd(C.Structure):
+    _fields_ = [("a", Operand), ("b", Operand), ("zx", vp), ("ldzx", i64), ("b1", vp), ("b2", vp), ("c_prev", vp), ("ldcp", i64),
+                ("c_out", vp), ("ldc", i64), ("h_out", vp), ("ldh", i64), ("h_out2", vp), ("ldh2", i64), ("gates", vp), ("ldg", i64),
+                ("hb", vp), ("ldhb", i64), ("hb2", vp), ("ldhb2", i64), ("zx_tok", vp), ("zx_tok_stride", i64), ("drop", Drop)]
+
+
+class GatesBwd(C.Structure):
+    _fields_ = [("a", Operand), ("b", Operand), ("dh1", vp), ("ld1", i64), ("dh2", vp), ("ld2", i64), ("dh3", vp), ("ld3", i64),
+                ("dc_in", vp), ("lddc", i64), ("gates", vp), ("ldg", i64), ("c_prev", vp), ("ldcp", i64), ("c", vp), ("ldcc", i64),
+                ("dz", vp), ("lddz", i64), ("dc_out", vp), ("lddco", i64), ("dzb", vp), ("lddzb", i64), ("drop", Drop), ("gil", i32)]
+
+
+def operand(t, segs, dtype, vary=0):
+    """t [rows][K] as one or two K segments with different row strides -> (Operand, the Mats that own the memory)."""
+    o, K0 = Operand(), segs[0]
+    m0 = Mat(t.shape[0], K0, dtype, t[:, :K0], pad=8 + 8 * vary, off=8 * vary)
+    o.p0, o.ld0, o.K0, o.rows, o.p1, o.ld1, o.K1 = m0.addr, m0.ld, K0, t.shape[0], None, 0, 0
+    mats = [m0]
+    if len(segs) == 2:
+        m1 = Mat(t.shape[0], segs[1], dtype, t[:, K0:], pad=24, off=16)
+        o.p1, o.ld1, o.K1 = m1.addr, m1.ld, segs[1]
+        mats.append(m1)
+    return o, mats
+
+
+def no_drop():
+    return Drop(0, 0, 1.0, 0)
+
+
+# ---- max-pooling reference of the conv epilogue (EpConv), shared by the bf16 and the exact-fp32 conv files
+def pool_ref(z, pool):
+    """max-pool of an NCHW map and the kernels' arg-max rule: the FIRST maximum in window order (i = 2 dy + dx; (2,1): i = dy)."""
+    B, Cc, H, W = z.shape
+    if pool == 1:
+        Hp, Wp = H // 2, W // 2
+        v = z[:, :, :2 * Hp, :2 * Wp].reshape(B, Cc, Hp, 2, Wp, 2).permute(0, 1, 2, 4, 3, 5).reshape(B, Cc, Hp, Wp, 4)
+    else:
+        Hp = H // 2
+        v = z[:, :, :2 * Hp, :].reshape(B, Cc, Hp, 2, W).permute(0, 1, 2, 4, 3)
+    m = v.max(dim=-1).values
+    first = (v == m.unsqueeze(-1)).float().argmax(dim=-1)          # first index holding the maximum
+    return m, first.to(torch.uint8)
+
+
+def check_exact(res, z, pool, what):
+    """z: the exact pre-pool map (NCHW).  y / yb equal the (pooled) map; idx is the first maximum of every window."""
+    m, first = (z, None) if pool == 0 else pool_ref(z, pool)
+    m = nhwc(m)
+    if res["y"] is not None:
+        assert torch.equal(res["y"].cpu(), m), f"{what}: y (max diff {(res['y'].cpu() - m).abs().max().item()})"
+    if res["yb"] is not None:
+        assert torch.equal(bits(res["yb"]), bf(m)), f"{what}: yb"
+    if pool:
+        bad = res["idx"].cpu() != nhwc(first)
+        assert not bad.any(), f"{what}: arg-max not the first maximum of its window at {bad.sum().item()} of {bad.numel()} outputs"
+
+
+# ---- wide-integer operands of the exact-fp32 files: a bf16 demotion of an operand changes them, small integers (|v| <= 4) would not notice it
+WIDE = 300
+
+
+def wide_ints(*shape, seed):
+    """integers in [-300, 300]; every second element (at least) an ODD magnitude in 257..299, which bf16 (8 significand bits) cannot hold"""
+    g = torch.Generator().manual_seed(seed)
+    base = torch.randint(-WIDE, WIDE + 1, shape, generator=g)
+    odd = (2 * torch.randint(128, 150, shape, generator=g) + 1) * (2 * torch.randint(0, 2, shape, generator=g) - 1)      # +-(257, 259 .. 299)
+    n = base.numel()
+    pick = (torch.randperm(n, generator=g) < (n + 1) // 2).view(base.shape)          # exactly half of the positions (rounded up)
+    t = torch.where(pick, odd, base).float()
+    assert 2 * (t != rb(t)).sum().item() >= n, "wide_ints: fewer than half of the values change under a bf16 rounding"
+    return t
+
+
+def assert_exact_range(K, amax, bmax, extra=0.0):
+    """every partial sum of K products (plus what the epilogue adds) is an integer below 2^24: fp32 accumulation is exact in ANY order"""
+    assert K * amax * bmax + extra < 2 ** 24, f"K {K} x {amax} x {bmax} + {extra} reaches 2^24: fp32 sums are no longer exact"
+
+
 def out(rows, cols, dtype=torch.float32, pad=8, off=0):
     return Mat(rows, cols, dtype, None, pad, off, SENT if dtype == torch.float32 else -3.0)
 
@@ -274,3 +371,90 @@ def rb(t):
 def ratio(got, ref, tol):
     """largest |got - ref| / tol (tol a number or a tensor)"""
     return ((got.double() - ref).abs() / tol).max().item()
+
+
+# ---- exact-fp32 EpStore problems, shared by tests/test_kernels_f32_gpu.py (launch_big_kk) and tests/test_step_kernels_f32_gpu.py (launch_small_kk / _kmn)
+def eq_bits(got, ref64, what):
+    """got (fp32) equals the float64 reference cast to fp32, bit for bit"""
+    ref = ref64.float()
+    same = torch.equal(got.contiguous().view(torch.int32), ref.contiguous().view(torch.int32))
+    assert same, f"{what}: {(got != ref).sum().item()} of {got.numel()} elements differ (max diff {(got.double() - ref64).abs().max().item()})"
+
+
+def pair(M, N, K, seed, wide_a):
+    """A [M][K], B [N][K]: one side wide integers, the other in [-4, 4]"""
+    return (wide_ints(M, K, seed=seed), ints(N, K, seed=seed + 1)) if wide_a else (ints(M, K, seed=seed), wide_ints(N, K, seed=seed + 1))
+
+
+ST_VARIANTS = ("bias", "bias2", "relu", "accum", "tanh", "split")          # (any other name: a plain store)
+TQ = 2.0 ** -12                     # the tanh variant's B-side quantum: |x| stays near 1, every product still exact
+
+
+def store_problem(M, N, segs, variant, seed, wide_a, random=False, b_mn=False):
+    """One exact-fp32 EpStore problem as tests/kprobe.hip's KpStore (A [M][K] in one or two K segments; B [N][K] likewise, or with b_mn ONE segment stored
+    [K][N]), its output windows and the float64 reference."""
+    K = sum(segs)
+    if random:
+        A, Bm = rnd(M, K, seed=seed).float(), rnd(N, K, seed=seed + 1).float()
+    else:
+        A, Bm = pair(M, N, K, seed, wide_a)
+        assert_exact_range(K, WIDE, 4, 1000)
+        if variant == "tanh":
+            Bm = Bm * TQ
+    p, keep, o = Store(), [], {}
+    p.a, ka = operand(A, segs, torch.float32, vary=seed % 2)
+    if b_mn:
+        mb = Mat(K, N, data=Bm.t(), pad=8, off=4)
+        p.b.p0, p.b.ld0, p.b.K0, p.b.rows, kb = mb.addr, mb.ld, K, N, [mb]
+    else:
+        p.b, kb = operand(Bm, segs, torch.float32, vary=(seed + 1) % 2)
+    x, mag = A.double() @ Bm.double().t(), A.double().abs() @ Bm.double().abs().t()
+    if variant in ("bias", "bias2", "relu", "accum", "split"):
+        b1, b2 = ints(N, seed=seed + 2, lo=-500, hi=500), ints(N, seed=seed + 3, lo=-500, hi=500)
+        m1, m2 = Buf(b1), Buf(b2)
+        keep += [m1, m2]
+        p.bias = m1.full.data_ptr()
+        x = x + b1.double()
+        if variant in ("bias2", "relu", "split"):
+            p.bias2 = m2.full.data_ptr()
+            x = x + b2.double()
+    if variant == "relu":
+        p.flags = EP_RELU
+        x = x.clamp(min=0)
+    if variant == "tanh":
+        p.flags = EP_TANH
+        x = torch.tanh(x)
+    N0 = N
+    if variant == "accum":
+        c0 = ints(M, N, seed=seed + 6, lo=-1000, hi=1000)
+        o["C"] = Mat(M, N, data=c0, pad=8)
+        p.flags = EP_ACCUM
+        x = c0.double() + x
+    else:
+        o["C"] = out(M, N, pad=8)
+    if variant == "split":
+        N0 = N - 24                                                       # the second destination takes the last 24 columns
+        o["C1"] = out(M, N - N0, pad=4, off=4)
+        p.C1, p.ldc1, p.N0 = o["C1"].addr, o["C1"].ld, N0
+    p.C, p.ldc = o["C"].addr, o["C"].ld
+    return p, o, dict(x=x, mag=mag, N0=N0, variant=variant), keep + ka + kb
+
+
+def store_check(o, ref, K, what, random=False, tanh_tol=1e-5):
+    for k, m in o.items():
+        m.check(f"{what} {k}")
+    x, N0, N = ref["x"], ref["N0"], ref["x"].shape[1]
+    got = o["C"].win()
+    if random:
+        r = ratio(got, x, bound(ref["mag"], K) + 1e-30)
+        assert r <= 1.0, f"{what}: error / bound = {r:.3f}"
+        return r
+    if ref["variant"] == "tanh":                                          # the kernel's own tanh: not exact (tests/test_kernels_bf16_gpu.py: 1e-5)
+        e = (got.double() - x).abs().max().item()
+        assert e <= tanh_tol, f"{what}: tanh error {e:.2e}"
+        return e
+    eq_bits(got[:, :N0], x[:, :N0], f"{what}: C")
+    if N0 < N:
+        assert torch.equal(got[:, N0:], torch.full((got.shape[0], N - N0), SENT)), f"{what}: C written past N0"
+        eq_bits(o["C1"].win(), x[:, N0:], f"{what}: C1")
+    return 0.0

@@ -1,7 +1,11 @@
 // tests/libkprobe.so: extern "C" wrappers around the host launchers of the bf16-source conv / GEMM paths, of the fused recurrent-step
 // kernels, of the attention kernels, of the BatchNorm / un-pool / conv1 / column-sum kernels and of the loss, token-sum, optimizer, beam-search and small
 // elementwise kernels, and of the whole-sequence encoder recurrences (csrc/ops.h), for tests/test_kernels_bf16_gpu.py, tests/test_step_kernels_bf16_gpu.py,
-// tests/test_attention_kernels_gpu.py, tests/test_cnn_elementwise_kernels_gpu.py, tests/test_tail_kernels_gpu.py and tests/test_encoder_seq_kernels_gpu.py.  Test infrastructure: no kernels of its own, not part of the product's C ABI (include/aocr.h).
+// tests/test_attention_kernels_gpu.py, tests/test_cnn_elementwise_kernels_gpu.py, tests/test_tail_kernels_gpu.py and tests/test_encoder_seq_kernels_gpu.py; and of
+// the exact-fp32 (compute="f32") forms of the same launchers -- kp_conv_weight_transpose_f32, kp_conv_backward_data_f32 (the re-laid taps wtf), kp_big_kk_f32
+// (two-segment LoadK operands, ksplit), kp_small_f32_gates_fwd / _kk / _kmn / _gates_bwd_kk / _gates_bwd -- for tests/test_kernels_f32_gpu.py and
+// tests/test_step_kernels_f32_gpu.py (kp_conv_forward, kp_conv_backward_filter, kp_grouped_wgrad and kp_gemm take bf16 = 0 as they are).
+// Test infrastructure: no kernels of its own, not part of the product's C ABI (include/aocr.h).
 // Every wrapper enqueues on the given stream and returns hipGetLastError().  Pointers to bf16 data are passed as the raw addresses
 // of torch.bfloat16 tensors (the same bit layout as bf16_t).
 #include "ops.h"
@@ -23,6 +27,16 @@ int kp_conv_forward(hipStream_t s, int bf16, const float* x, const float* w, con
 int kp_conv_backward_data(hipStream_t s, int bf16, const float* dy, const float* w, float* dx, int B, int H, int W, int Cin, int Cout,
                           int ks, int pad, const void* dyb, const void* wtb, int* dx16) {
   aocr::conv_backward_data(s, bf16 != 0, dy, w, dx, B, H, W, Cin, Cout, ks, pad, H16(dyb), H16(wtb), nullptr, dx16, nullptr, nullptr);
+  return (int)hipGetLastError();
+}
+
+// exact-fp32 mode as the model runs it: the taps re-laid [Cin][tap][Cout] (wtf, from kp_conv_weight_transpose_f32) -> LoadConvK x LoadK
+int kp_conv_weight_transpose_f32(hipStream_t s, const float* w, float* wt, int Cout, int KK, int Cin) {
+  aocr::conv_weight_transpose_f32(s, w, wt, Cout, KK, Cin);
+  return (int)hipGetLastError();
+}
+int kp_conv_backward_data_f32(hipStream_t s, const float* dy, const float* w, const float* wtf, float* dx, int B, int H, int W, int Cin, int Cout, int ks, int pad) {
+  aocr::conv_backward_data(s, false, dy, w, dx, B, H, W, Cin, Cout, ks, pad, nullptr, nullptr, wtf, nullptr, nullptr, nullptr);
   return (int)hipGetLastError();
 }
 
@@ -242,6 +256,14 @@ template <class ARGS, class P> int fill(ARGS (&z)[3], int nz, const P* p, int M,
   for (int i = 0; i < nz; ++i) { load_a(z[i].a, p[i].a); z[i].b = kh(p[i].b); z[i].ep = ep_of(p[i], M, cols); z[i].K = z[i].a.K; }
   return 0;
 }
+// the exact-fp32 launchers' argument sets: A and B from fp32 buffers, B as its loader type says
+void load_b(LoadK& l, const KpOperand& o) { l = kf(o); }
+void load_b(LoadMN& l, const KpOperand& o) { l = make_loadmn((const float*)o.p0, o.ld0, o.rows, o.K0); }
+template <class ARGS, class P> int fill_f32(ARGS (&z)[3], int nz, const P* p, int M, int cols) {
+  if (nz < 1 || nz > 3) return (int)hipErrorInvalidValue;
+  for (int i = 0; i < nz; ++i) { z[i].a = kf(p[i].a); load_b(z[i].b, p[i].b); z[i].ep = ep_of(p[i], M, cols); z[i].K = z[i].a.K; }
+  return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -260,6 +282,44 @@ KP_SMALL(kp_small_h, SmallArgsH, KpStore, launch_small_h)
 KP_SMALL(kp_small_gates_bwd_hh, GatesBwdArgsHH, KpGatesBwd, launch_small_gates_bwd_hh)
 KP_SMALL(kp_small_gates_bwd_h, GatesBwdArgsH, KpGatesBwd, launch_small_gates_bwd_h)
 #undef KP_SMALL
+
+// ---- the exact-fp32 forms (tests/test_kernels_f32_gpu.py, tests/test_step_kernels_f32_gpu.py): both operands fp32.  A is K-contiguous (kf: one or two
+// segments); B is K-contiguous too (LoadK, [cols][K]) or, for _kmn and _gates_bwd, M/N-contiguous (LoadMN: ONE segment, p0 [K0][rows] with row stride ld0).
+int kp_big_kk_f32(hipStream_t s, const KpStore* p, int M, int N, int ksplit) {
+  const aocr::LoadK a = kf(p->a), b = kf(p->b);
+  aocr::launch_big_kk(s, false, a, b, ep_of(*p, M, N), M, N, a.K, ksplit);
+  return (int)hipGetLastError();
+}
+int kp_small_f32_gates_fwd(hipStream_t s, int nz, const KpGatesFwd* p, int M, int cols) {
+  aocr::GatesFwdArgs z[3];
+  if (int rc = fill_f32(z, nz, p, M, cols)) return rc;
+  aocr::launch_small_gates_fwd(s, false, nz, z, M, cols);
+  return (int)hipGetLastError();
+}
+int kp_small_f32_kk(hipStream_t s, int nz, const KpStore* p, int M, int cols) {
+  aocr::SmallKKArgs z[3];
+  if (int rc = fill_f32(z, nz, p, M, cols)) return rc;
+  aocr::launch_small_kk(s, false, nz, z, M, cols);
+  return (int)hipGetLastError();
+}
+int kp_small_f32_kmn(hipStream_t s, int nz, const KpStore* p, int M, int cols) {
+  aocr::SmallKMNArgs z[3];
+  if (int rc = fill_f32(z, nz, p, M, cols)) return rc;
+  aocr::launch_small_kmn(s, false, nz, z, M, cols);
+  return (int)hipGetLastError();
+}
+int kp_small_f32_gates_bwd_kk(hipStream_t s, int nz, const KpGatesBwd* p, int M, int cols) {
+  aocr::GatesBwdKKArgs z[3];
+  if (int rc = fill_f32(z, nz, p, M, cols)) return rc;
+  aocr::launch_small_gates_bwd_kk(s, nz, z, M, cols);
+  return (int)hipGetLastError();
+}
+int kp_small_f32_gates_bwd(hipStream_t s, int nz, const KpGatesBwd* p, int M, int cols) {
+  aocr::GatesBwdArgs z[3];
+  if (int rc = fill_f32(z, nz, p, M, cols)) return rc;
+  aocr::launch_small_gates_bwd(s, false, nz, z, M, cols);
+  return (int)hipGetLastError();
+}
 
 // the cell backward without a product (the operands of *p are ignored)
 int kp_gates_elem_bwd(hipStream_t s, const KpGatesBwd* p, int M, int H) {

@@ -12,7 +12,8 @@ import kernel_harness as KH
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL_MODULES = ("test_kernels_bf16_gpu", "test_step_kernels_bf16_gpu", "test_encoder_seq_kernels_gpu", "test_cnn_elementwise_kernels_gpu",
-                  "test_attention_kernels_gpu", "test_tail_kernels_gpu", "test_decoder_seq_kernels_gpu")
+                  "test_attention_kernels_gpu", "test_tail_kernels_gpu", "test_decoder_seq_kernels_gpu", "test_kernels_f32_gpu",
+                  "test_step_kernels_f32_gpu")
 
 
 def _count(params):

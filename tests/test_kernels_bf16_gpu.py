@@ -23,23 +23,9 @@ import torch
 import torch.nn.functional as F
 
 from kernel_harness import _switches  # noqa: F401  this import IS how the autouse fixture reaches the module (tests/test_kernel_harness_cpu.py checks it)
-from kernel_harness import EP_ACCUM, EP_RELU, EP_TANH, SENT, Buf, bf, bits, bound, call, expect, ints, kp, nhwc, rnd, setenv, trace_of
+from kernel_harness import EP_ACCUM, EP_RELU, EP_TANH, SENT, Buf, bf, bits, bound, call, check_exact, expect, ints, kp, nhwc, rnd, setenv, trace_of
 
 pytestmark = pytest.mark.gpu
-
-
-def pool_ref(z, pool):
-    """max-pool of an NCHW map and the kernels' arg-max rule: the FIRST maximum in window order (i = 2 dy + dx; (2,1): i = dy)."""
-    B, Cc, H, W = z.shape
-    if pool == 1:
-        Hp, Wp = H // 2, W // 2
-        v = z[:, :, :2 * Hp, :2 * Wp].reshape(B, Cc, Hp, 2, Wp, 2).permute(0, 1, 2, 4, 3, 5).reshape(B, Cc, Hp, Wp, 4)
-    else:
-        Hp = H // 2
-        v = z[:, :, :2 * Hp, :].reshape(B, Cc, Hp, 2, W).permute(0, 1, 2, 4, 3)
-    m = v.max(dim=-1).values
-    first = (v == m.unsqueeze(-1)).float().argmax(dim=-1)          # first index holding the maximum
-    return m, first.to(torch.uint8)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -93,19 +79,6 @@ def run_forward(x, w, b, ks, pad, relu, pool, out, bn=None, bn_part=None):
         if t is not None:
             t.check_tail(nm)
     return dict(y=y, yb=yb, idx=idx, wb=wb, wtb=wtb, xb=xb, chunks=chunks.value)
-
-
-def check_exact(res, z, pool, what):
-    """z: the exact pre-pool map (NCHW).  y / yb equal the (pooled) map; idx is the first maximum of every window."""
-    m, first = (z, None) if pool == 0 else pool_ref(z, pool)
-    m = nhwc(m)
-    if res["y"] is not None:
-        assert torch.equal(res["y"].cpu(), m), f"{what}: y (max diff {(res['y'].cpu() - m).abs().max().item()})"
-    if res["yb"] is not None:
-        assert torch.equal(bits(res["yb"]), bf(m)), f"{what}: yb"
-    if pool:
-        bad = res["idx"].cpu() != nhwc(first)
-        assert not bad.any(), f"{what}: arg-max not the first maximum of its window at {bad.sum().item()} of {bad.numel()} outputs"
 
 
 @pytest.mark.parametrize("case", FWD_CASES, ids=[c[0] for c in FWD_CASES])

@@ -42,6 +42,8 @@ def test_kprobe_symbols_resolve_in_libaocr(tmp_path):
                  "gemm_hh_shadow", "gemm_hh_cat", "grouped_wgrad", "bn_relu_forward",
                  "launch_small_gates_fwd_hh", "launch_small_gates_fwd_h", "launch_small_hh", "launch_small_h", "launch_small_gates_bwd_hh",
                  "launch_small_gates_bwd_h", "gates_elem_bwd", "big_step_store", "big_step_gates_fwd",
+                 "conv_weight_transpose_f32", "launch_big_kk", "launch_small_gates_fwd", "launch_small_kk", "launch_small_kmn",
+                 "launch_small_gates_bwd_kk", "launch_small_gates_bwd", "gemm",
                  "attention_forward", "attention_backward", "attention_forward_dual", "attention_backward_dual", "attention_dual_ok",
                  "attention_dctx", "bn_relu_backward", "unpool_relu_backward", "conv1_forward", "conv1_route_elems", "conv1_backward",
                  "colsum_accum", "colsum_defer", "colsum_flush",
@@ -61,6 +63,8 @@ def test_kprobe_symbols_resolve_in_libaocr(tmp_path):
     for name in ("kp_conv_forward", "kp_conv_backward_data", "kp_conv_backward_filter", "kp_grouped_wgrad", "kp_gemm_hh_cat",
                  "kp_small_gates_fwd_hh", "kp_small_gates_fwd_h", "kp_small_hh", "kp_small_h", "kp_small_gates_bwd_hh", "kp_small_gates_bwd_h",
                  "kp_gates_elem_bwd", "kp_big_step_store", "kp_big_step_gates_fwd",
+                 "kp_conv_weight_transpose_f32", "kp_conv_backward_data_f32", "kp_big_kk_f32", "kp_small_f32_gates_fwd", "kp_small_f32_kk",
+                 "kp_small_f32_kmn", "kp_small_f32_gates_bwd_kk", "kp_small_f32_gates_bwd",
                  "kp_attention_forward", "kp_attention_backward", "kp_attention_forward_dual", "kp_attention_backward_dual",
                  "kp_attention_dual_ok", "kp_attention_dctx", "kp_bn_relu_forward2", "kp_bn_relu_backward", "kp_unpool_relu_backward",
                  "kp_conv1_forward", "kp_conv1_route_elems", "kp_conv1_backward", "kp_colsum_accum", "kp_colsum_jobs",

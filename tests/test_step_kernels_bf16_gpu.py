@@ -42,47 +42,13 @@ import pytest
 import torch
 
 from kernel_harness import _switches  # noqa: F401  this import IS how the autouse fixture reaches the module (tests/test_kernel_harness_cpu.py checks it)
-from kernel_harness import (EP_ACCUM, EP_RELU, EP_TANH, SENT, TOL_BWD, TOL_CELL, Buf, Drop, Mat, bf, bound, call, expect, i32, i64, ints, out,
-                            ratio, rb, rnd, setenv, trace_of, vp)
+from kernel_harness import (EP_ACCUM, EP_RELU, EP_TANH, SENT, TOL_BWD, TOL_CELL, Buf, Drop, GatesBwd, GatesFwd, Mat, Store, bf, bound, call, expect,
+                            ints, no_drop, operand, out, ratio, rb, rnd, setenv, trace_of, vp)
 
 pytestmark = pytest.mark.gpu
 
 Q = 2.0 ** -4                       # B-side quantum of the gate cases
 HH, HF = "launch_small_bf16_hh", "launch_small_bf16"
-
-
-class Operand(C.Structure):
-    _fields_ = [("p0", vp), ("ld0", i64), ("K0", i32), ("p1", vp), ("ld1", i64), ("K1", i32), ("rows", i32)]
-
-
-class Store(C.Structure):
-    _fields_ = [("a", Operand), ("b", Operand), ("C", vp), ("ldc", i64), ("bias", vp), ("bias2", vp), ("flags", i32),
-                ("C1", vp), ("ldc1", i64), ("N0", i32), ("Cb", vp), ("ldcb", i64), ("dg", vp), ("dout", vp), ("ldd", i64)]
-
-
-class GatesFwd(C.Structure):
-    _fields_ = [("a", Operand), ("b", Operand), ("zx", vp), ("ldzx", i64), ("b1", vp), ("b2", vp), ("c_prev", vp), ("ldcp", i64),
-                ("c_out", vp), ("ldc", i64), ("h_out", vp), ("ldh", i64), ("h_out2", vp), ("ldh2", i64), ("gates", vp), ("ldg", i64),
-                ("hb", vp), ("ldhb", i64), ("hb2", vp), ("ldhb2", i64), ("zx_tok", vp), ("zx_tok_stride", i64), ("drop", Drop)]
-
-
-class GatesBwd(C.Structure):
-    _fields_ = [("a", Operand), ("b", Operand), ("dh1", vp), ("ld1", i64), ("dh2", vp), ("ld2", i64), ("dh3", vp), ("ld3", i64),
-                ("dc_in", vp), ("lddc", i64), ("gates", vp), ("ldg", i64), ("c_prev", vp), ("ldcp", i64), ("c", vp), ("ldcc", i64),
-                ("dz", vp), ("lddz", i64), ("dc_out", vp), ("lddco", i64), ("dzb", vp), ("lddzb", i64), ("drop", Drop), ("gil", i32)]
-
-
-def operand(t, segs, dtype, vary=0):
-    """t [rows][K] as one or two K segments with different row strides -> (Operand, the Mats that own the memory)."""
-    o, K0 = Operand(), segs[0]
-    m0 = Mat(t.shape[0], K0, dtype, t[:, :K0], pad=8 + 8 * vary, off=8 * vary)
-    o.p0, o.ld0, o.K0, o.rows, o.p1, o.ld1, o.K1 = m0.addr, m0.ld, K0, t.shape[0], None, 0, 0
-    mats = [m0]
-    if len(segs) == 2:
-        m1 = Mat(t.shape[0], segs[1], dtype, t[:, K0:], pad=24, off=16)
-        o.p1, o.ld1, o.K1 = m1.addr, m1.ld, segs[1]
-        mats.append(m1)
-    return o, mats
 
 
 def drop_spec(p, seed, step, site, off, n):
@@ -93,10 +59,6 @@ def drop_spec(p, seed, step, site, off, n):
         base = O._splitmix64(np.array([np.uint64(seed) ^ (stream * np.uint64(0xD1342543DE82EF95))], dtype=np.uint64))[0]
     d = Drop(int(base), int(math.ceil(p * 9007199254740992.0)), 1.0 / (1.0 - p), off)
     return d, torch.from_numpy(O.dropout_mask(p, seed, step, site, off, n)).float()
-
-
-def no_drop():
-    return Drop(0, 0, 1.0, 0)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

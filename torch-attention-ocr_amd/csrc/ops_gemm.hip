@@ -12,11 +12,16 @@ static void split_k(int K, int chunk, int& ksplit, int& kper) {
   if (kper < chunk) kper = chunk;
   ksplit = cdiv(K, kper); if (ksplit < 1) ksplit = 1;
 }
-// dispatch trace (AOCR_TRACE set, read per call): one stderr line per launch of the bf16-source conv / GEMM entry points,
+// dispatch trace (AOCR_TRACE set, read per call): one stderr line per launch of the conv / GEMM / recurrent-step entry points, bf16-source and exact-fp32,
 // "[aocr] <function>: <kernel>[<instantiation>] M N K", so the kernel tests can prove which branch a shape reached
 static thread_local const char* t_trace_fn = nullptr;
-struct TraceScope { explicit TraceScope(const char* fn) { t_trace_fn = fn; } ~TraceScope() { t_trace_fn = nullptr; } };
-// (note: a word behind the line for a variant that keeps the kernel's name and instantiation -- gemm_halo4_bf16_kernel's "skip")
+// (the OUTERMOST scope names the line: grouped_wgrad's fp32 problems go through gemm, gemm's skinny products through launch_small_kk)
+struct TraceScope {
+  const char* outer;
+  explicit TraceScope(const char* fn) : outer(t_trace_fn) { if (!outer) t_trace_fn = fn; }
+  ~TraceScope() { t_trace_fn = outer; }
+};
+// (note: a word behind the line for a variant that keeps the kernel's name and instantiation -- gemm_halo4_bf16_kernel's "skip", gemm_f32w_kernel's effective k split)
 static void trace_launch(const char* kernel, const char* inst, long long M, long long N, long long K, const char* note = nullptr) {
   if (t_trace_fn && knob::AOCR_TRACE()) fprintf(stderr, "[aocr] %s: %s[%s] %lld %lld %lld%s%s\n", t_trace_fn, kernel, inst, M, N, K, note ? " " : "", note ? note : "");
 }
@@ -169,6 +174,7 @@ static void launch_big(hipStream_t s, bool bf16, const AL& a, const BL& b, const
       const int force = knob::AOCR_F32T_TILE();                        // A/B: 1 = 128 x 128, 2 = 64 x 128, 3 = 64 x 64
       auto wgs = [&](int bm, int bn) { return (long long)cdiv(M, bm) * cdiv(N, bn) * ksplit; };
       const int pick = force ? force : (N > 64 && wgs(128, 128) >= 512) ? 1 : (N > 64 && wgs(64, 128) >= 512) ? 2 : 3;
+      trace_launch("gemm_f32t_kernel", pick == 1 ? "128x128" : pick == 2 ? "64x128" : "64x64", M, N, K);
       if (pick == 1) {
         const int gx = cdiv(N, 128), gy = cdiv(M, 128);
         hipLaunchKernelGGL((gemm_f32t_kernel<128, 128, AL, BL, EP>), dim3(gx * gy, 1, ksplit), dim3(256), 0, s, a, b, ep, K, kp, gx, gy);
@@ -185,6 +191,7 @@ static void launch_big(hipStream_t s, bool bf16, const AL& a, const BL& b, const
   if (KContig<AL>::v && KContig<BL>::v && !no_lds32 && M >= 96 && N >= 64 && K >= 32) {
     int kp; split_k(K, 32, ksplit, kp);
     const int gx = cdiv(N, 128), gy = cdiv(M, 128);
+    trace_launch("gemm_lds_f32_kernel", "", M, N, K);
     hipLaunchKernelGGL((gemm_lds_f32_kernel<AL, BL, EP>), dim3(gx * gy, 1, ksplit), dim3(256), 0, s, a, b, ep, K, kp, gx, gy);
     return;
   }
@@ -198,15 +205,18 @@ static void launch_big(hipStream_t s, bool bf16, const AL& a, const BL& b, const
       ksplit = std::min(ksplit, std::max(1, K / knob::AOCR_F32W_MINK()));
       int kp; split_k(K, 32, ksplit, kp);
       const int gx = cdiv(N, 128), gy = cdiv(M, 128);
+      { char note[16]; snprintf(note, sizeof note, "%d", ksplit); trace_launch("gemm_f32w_kernel", "", M, N, K, note); }
       hipLaunchKernelGGL((gemm_f32w_kernel<AL, BL, EP>), dim3(gx * gy, 1, ksplit), dim3(256), 0, s, a, b, ep, K, kp, gx, gy);
       return;
     }
   }
   int kper; split_k(K, 8, ksplit, kper);
+  trace_launch("gemm_big_kernel", "f32", M, N, K);
   hipLaunchKernelGGL((gemm_big_kernel<false, 2, 2, AL, BL, EP>), dim3(cdiv(N, 128), cdiv(M, 128), ksplit), dim3(256), 0, s, a, b, ep, K, kper);
 }
 
 void launch_big_kk(hipStream_t s, bool bf16, const LoadK& a, const LoadK& b, const EpStore& ep, int M, int N, int K, int ksplit) {
+  const TraceScope ts("launch_big_kk");
   launch_big(s, bf16, a, b, ep, M, N, K, ksplit);
 }
 void launch_big_kmn(hipStream_t s, bool bf16, const LoadK& a, const LoadMN& b, const EpStore& ep, int M, int N, int K, int ksplit) {
@@ -229,6 +239,7 @@ static bool quarter_gate_tiles(int H, int M, int nz) { return !knob::AOCR_NO_QUA
 template <int NT, bool GATES, class ARGS>
 static void launch_small(hipStream_t s, bool bf16, int nz, const ARGS* z, int M, int ncols, int gate_stride) {
   if (M <= 0 || ncols <= 0) return;
+  const TraceScope ts("launch_small");
   dim3 grid(GATES ? cdiv(ncols, 32) : cdiv(ncols, 32 * NT), cdiv(M, 32), nz);
   SmallArgs2<decltype(z[0].a), decltype(z[0].b), decltype(z[0].ep)> zz; zz.z[0] = z[0]; zz.z[1] = z[nz > 1 ? 1 : 0]; zz.z[2] = z[nz > 2 ? 2 : 0];
   if (bf16) {
@@ -251,6 +262,7 @@ static void launch_small(hipStream_t s, bool bf16, int nz, const ARGS* z, int M,
       // C2 7.67 -> 7.81 ms per step: the 1024-thread workgroup's launch and 16-way reduction cost more than the shorter K loop saves): opt-in.
       const int wgs = (GATES ? ncols / 8 : ncols / 32) * cdiv(M, 32) * nz;
       const bool deep = knob::AOCR_STEP_F32_W16() && z[0].K >= 2048 && wgs <= 128;
+      trace_launch("gemm_step_f32_kernel", GATES ? "gates" : deep ? "plain,w16" : "plain,w8", M, ncols, z[0].K);
       if constexpr (GATES) hipLaunchKernelGGL((gemm_step_f32_kernel<true, EPT>), dim3(ncols / 8, cdiv(M, 32), nz), dim3(512), 0, s, zz, gate_stride);
       else if (deep) hipLaunchKernelGGL((gemm_step_f32_kernel<false, EPT, 16>), dim3(ncols / 32, cdiv(M, 32), nz), dim3(1024), 0, s, zz, gate_stride);
       else hipLaunchKernelGGL((gemm_step_f32_kernel<false, EPT>), dim3(ncols / 32, cdiv(M, 32), nz), dim3(512), 0, s, zz, gate_stride);
@@ -261,11 +273,15 @@ static void launch_small(hipStream_t s, bool bf16, int nz, const ARGS* z, int M,
     if (quarter_gate_tiles(ncols, M, nz)) {
       // small batch: 8 hidden units x 4 gates per workgroup (the A and B tiles are loaded straight from global memory here, so
       // the narrower tile costs nothing but a shuffle in the epilogue)
+      trace_launch("gemm_small_kernel", "f32,quarter", M, ncols, z[0].K);
       hipLaunchKernelGGL((gemm_small_kernel<false, 1, true, decltype(z[0].a), decltype(z[0].b), decltype(z[0].ep), 8, true>),
                          dim3(ncols / 8, cdiv(M, 32), nz), dim3(512), 0, s, zz, gate_stride);
       return;
     }
   }
+  // the fragment-from-global kernel's line: gemm_small_kernel[f32,<NT>,gates|plain,w8|w4]
+  { char inst[32]; snprintf(inst, sizeof inst, "f32,%d,%s,%s", NT, GATES ? "gates" : "plain", knob::AOCR_STEP_WAVES4() ? "w4" : "w8");
+    trace_launch("gemm_small_kernel", inst, M, ncols, z[0].K); }
   if (!knob::AOCR_STEP_WAVES4())
     hipLaunchKernelGGL((gemm_small_kernel<false, NT, GATES, decltype(z[0].a), decltype(z[0].b), decltype(z[0].ep), 8>), grid, dim3(512), 0, s,
                        zz, gate_stride);
@@ -490,6 +506,7 @@ static int pick_ksplit(int M, int N, int K, bool bf16, int slots = 768) {
 
 int gemm(hipStream_t s, bool bf16, const float* A, int64_t lda, bool a_k, const float* B, int64_t ldb, bool b_k, float* C,
           int64_t ldc, int M, int N, int K, const float* bias, const float* bias2, int flags) {
+  const TraceScope ts("gemm");
   EpStore ep = make_store(C, ldc, M, N, bias, bias2, flags);
   int ks = (flags & EP_ATOMIC) ? pick_ksplit(M, N, K, bf16) : 1;
   // skinny products (a 20- or 39-wide side: embedding part of the first decoder layer, projector and their backward): 128 x 128 tiles
