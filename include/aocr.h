@@ -898,6 +898,64 @@ int aocr_remove_rules(void* stream, const uint8_t* page_dev, int64_t pitch, int3
                       const aocr_rule_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch,
                       int32_t counts_dev[8]);
 
+/* ---- reversed-out panels: find the dark slabs that carry light text and invert them, after aocr_resize_page, before aocr_clean_page ---------
+ * light_text is one flag for the whole page, but a table header row, a form's section bar, a magazine banner or a sidebar box is white
+ * text on a dark slab.  To aocr_segment_page the slab is one huge box that holds no readable crop; aocr_clean_page paints it over as a
+ * figure (max_w / max_h), and the words on it go with it.  This stage finds the slabs among the connected components of the ink and
+ * replaces the bytes inside them by 255 - v, so that every later stage sees dark text on light paper there too.  Integer arithmetic
+ * only, specified exactly; every product that can pass 2^31 is formed in 64 bits.
+ *
+ * The page and the output follow the rules of aocr_clean_page: any base address, any pitch >= W, 1 <= H, W <= 16384, H*W <= 2^26; out_dev
+ * is H rows of W bytes, out_pitch >= W apart, bytes between W and out_pitch are untouched; 1 <= max_panels <= 1024; counts_dev is 8
+ * int32 and panels_dev, which may be NULL, max_panels rows of 8 int32, both 4-byte aligned; the page, the output, the scratch, panels_dev
+ * and counts_dev must not overlap one another.
+ *   ink, components  exactly those of aocr_label_components for threshold, light_text and connectivity (the same launches): threshold
+ *               0..254, or -1 for Otsu (steps 1-2 of aocr_segment_page, bit for bit); ink = (v <= threshold), or (v > threshold) with
+ *               light_text (the page is dark then and a panel is a light slab); a component's label is the raster index of its first pixel;
+ *   candidate   a component whose tight box [x0, x1) x [y0, y1) has x1 - x0 >= min_w and y1 - y0 >= min_h.  Candidates are taken in
+ *               ascending label order, the raster order of their first pixels, and only the first max_panels of them are examined;
+ *   span        for an examined candidate c and a row y of its box, lo(y) is the smallest x whose label is c and hi(y) the largest such x
+ *               plus one (a connected component has a pixel in every row of its box, so every row has a span);  hull = the sum over
+ *               the rows of hi - lo.  The spans are the row-convex hull of the component: because the region is the hull and not the box,
+ *               a rounded, elliptical or slightly rotated panel is not inverted outside itself;
+ *   panel       an examined candidate with  area * 100 >= fill_percent * hull  and  (hull - area) * 100 >= min_inside_percent * hull.
+ *               The first test keeps out glyphs, figures and blotchy photographs; the second keeps out solid bars with nothing written
+ *               on them, which are left to aocr_clean_page and aocr_remove_rules; min_inside_percent = 0 switches the second test off;
+ *   output      out[y][x] = 255 - page[y][x] when some panel has y in its box and lo(y) <= x < hi(y); every other byte is copied bit for
+ *               bit.  A pixel inside the spans of two panels is inverted once, not twice: its source is always the page, never the
+ *               output.  A page with no panel comes back identical; an Otsu threshold of -1 (one gray value) copies the page;
+ *   panels_dev  one row of 8 int32 per examined candidate, in label order: {x0, y0, x1, y1, label, area, hull, accepted (1 or 0)}; rows
+ *               beyond the examined candidates are untouched;
+ *   counts_dev  [components, candidates found, candidates examined, panels inverted, the threshold used, the total ink, the sum of the
+ *               inverted panels' hulls (capped at 2^31 - 1: hulls of nested rings can add up past it), 0].  candidates found >
+ *               max_panels is how the caller sees that the list was cut short; later candidates are not inverted.
+ * Limits: one level only -- a dark box inside a light box inside a panel comes out reversed; anti-aliased rim pixels of a panel that sit
+ * above the threshold are not part of the component and stay gray, a thin gray frame around the inverted slab; a solid bar without text
+ * is not a panel unless min_inside_percent is 0; a slab that touches other ink (a table grid drawn in the same dark) is one component
+ * with it and is judged with it.  The defaults of the Python mirror (min_w 64, min_h 24, fill_percent 60, min_inside_percent 2) are a
+ * judgement for text at 300 dpi and nobody has tuned them on real scans.
+ * scratch_dev: aocr_panels_scratch_bytes(H, W, max_panels) bytes, 16-byte aligned, overwritten by the call (0 and an error for bad
+ * sizes): the scratch of aocr_label_components, the label plane (4 bytes per pixel), one word per 64 columns of a row, and 8 bytes per
+ * (candidate, row): max_panels * H spans.
+ * The call enqueues only, never synchronises or allocates; the result is a function of the page and the params alone (integer sums,
+ * minima and maxima: no dependence on launch geometry, atomics order or run).  Invalid params (connectivity other than 4 or 8, min_w or
+ * min_h < 1, fill_percent outside 1..100, min_inside_percent outside 0..99, fill_percent + min_inside_percent > 100, non-zero
+ * reserved), bad sizes, NULLs or overlap return an error before anything is enqueued and leave every output untouched. */
+typedef struct aocr_panel_params {
+  int32_t threshold;           /* 0..254, or -1: Otsu, steps 1-2 of aocr_segment_page, bit for bit */
+  int32_t light_text;          /* 1: ink = (v > threshold): the page is dark, a panel is a light slab */
+  int32_t connectivity;        /* 4 or 8 */
+  int32_t min_w, min_h;        /* >= 1: a candidate's tight box is at least this wide and this high */
+  int32_t fill_percent;        /* 1..100: a panel's ink fills at least this share of its hull */
+  int32_t min_inside_percent;  /* 0..99, fill_percent + min_inside_percent <= 100: at least this share of the hull is not ink */
+  int32_t reserved;            /* must be 0 */
+} aocr_panel_params;
+
+size_t aocr_panels_scratch_bytes(int32_t H, int32_t W, int32_t max_panels);
+int aocr_invert_panels(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                       const aocr_panel_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch,
+                       int32_t max_panels, int32_t* panels_dev, int32_t counts_dev[8]);
+
 /* ---- page orientation: quarter turns, and which way the text lines run, in front of aocr_estimate_skew ------------------------------------
  * Every stage above reads row profiles and assumes that the lines run along x; aocr_estimate_skew sweeps slopes up to 0.25 only.  A page
  * fed sideways or upside down is turned here, on the device.  Integer arithmetic only, specified exactly.

@@ -148,6 +148,33 @@ class RuleParams(C.Structure):
         super().__init__(threshold, light_text, axes, min_len, max_thick, edge, (C.c_int32 * 2)(0, 0))
 
 
+class PanelParams(C.Structure):
+    """mirror of `aocr_panel_params` (include/aocr.h): which connected components `aocr_invert_panels` takes for reversed-out panels -- dark
+    slabs that carry light text -- and inverts inside their row spans.  A component whose tight box is at least min_w x min_h is a candidate;
+    it is a panel when its ink fills at least fill_percent of its row-convex hull (glyphs, figures and photographs do not) and at least
+    min_inside_percent of the hull is not ink (something is written on it; 0 takes solid bars too).  threshold -1: Otsu.  The defaults are a
+    judgement for text at 300 dpi -- a slab holds at least one line of body text and a short word -- and nobody has tuned them on real scans.
+    The constructor raises ValueError for what the library would turn down."""
+    _fields_ = [(n, C.c_int32) for n in ("threshold", "light_text", "connectivity", "min_w", "min_h", "fill_percent", "min_inside_percent", "reserved")]
+
+    def __init__(self, threshold=-1, light_text=0, connectivity=8, min_w=64, min_h=24, fill_percent=60, min_inside_percent=2):
+        threshold, light_text, connectivity, min_w, min_h, fill_percent, min_inside_percent = (
+            int(v) for v in (threshold, light_text, connectivity, min_w, min_h, fill_percent, min_inside_percent))
+        if not -1 <= threshold <= 254:
+            raise ValueError(f"threshold={threshold}: 0..254, or -1 for Otsu")
+        if connectivity not in (4, 8):
+            raise ValueError(f"connectivity={connectivity}: 4 or 8")
+        if min_w < 1 or min_h < 1:
+            raise ValueError(f"min_w={min_w} min_h={min_h} must be >= 1")
+        if not 1 <= fill_percent <= 100:
+            raise ValueError(f"fill_percent={fill_percent}: 1..100")
+        if not 0 <= min_inside_percent <= 99:
+            raise ValueError(f"min_inside_percent={min_inside_percent}: 0..99")
+        if fill_percent + min_inside_percent > 100:
+            raise ValueError(f"fill_percent={fill_percent} + min_inside_percent={min_inside_percent} is more than 100")
+        super().__init__(threshold, light_text, connectivity, min_w, min_h, fill_percent, min_inside_percent, 0)
+
+
 class RectifyParams:
     """how `Model.recognize_page(rectify=...)` finds and straightens a photographed page (`aocr_find_page_quad`, `aocr_rectify_plan`,
     `aocr_warp_page`; plain Python: there is no C struct behind it).  threshold -1: Otsu; dark_paper 1: the paper is the dark side of the threshold
@@ -343,6 +370,8 @@ SIGNATURES = {
     "aocr_clean_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, C.c_int64, _vp]),
     "aocr_rules_scratch_bytes": (C.c_size_t, [_i32, _i32]),
     "aocr_remove_rules": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, C.c_int64, _vp]),
+    "aocr_panels_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
+    "aocr_invert_panels": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, C.c_int64, _i32, _vp, _vp]),
     "aocr_rotate_page": (C.c_int,[_vp, _vp, C.c_int64, _i32, _i32, _vp, _i32, _vp, C.c_int64]),
     "aocr_orient_scratch_bytes": (C.c_size_t, [_i32, _i32]),
     "aocr_estimate_orientation": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _i32, _i32, _vp, _vp]),

@@ -21,7 +21,7 @@ from . import _lib, dist
 from ._lib import Config, check, lib, ptr
 from .dictionary import edit_distance_device
 from .page import backmap_corners, bucket_width, crop_lines_device, crop_lines_slanted_device, rotate_page_device, slant_extent
-from .page_pipeline import asked, clean_stage, colour_stage, flatten_stage, orient_stage, page_boxes, paper, rectify_stage, scale_stage
+from .page_pipeline import asked, clean_stage, colour_stage, flatten_stage, orient_stage, page_boxes, panels_stage, paper, rectify_stage, scale_stage
 
 PAD, GO, EOS = 1, 2, 3
 GROUPS = ["cnn", "enc_fw", "enc_bw", "dec", "proj"]
@@ -466,12 +466,14 @@ class Model:
             res.word = [lexicon.words[i] if i >= 0 else None for i in res.word_index.tolist()]
         return res
 
-    def _page_boxes(self, page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None, deslant=None, spacing=None, rules=None):
+    def _page_boxes(self, page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None, deslant=None, spacing=None, rules=None,
+                    panels_dev=None):
         """the middle of recognize_page (aocr.page_pipeline.page_boxes), reached through the model so that a caller can wrap it."""
-        return page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev, deslant, spacing, rules)
+        return page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev, deslant, spacing, rules, panels_dev)
 
     def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None, flatten=None,
-                       layout=None, clean=None, orient=None, rectify=None, scale=None, dewarp=None, colour=None, deslant=None, spacing=None, rules=None):
+                       layout=None, clean=None, orient=None, rectify=None, scale=None, dewarp=None, colour=None, deslant=None, spacing=None,
+                       panels=None, rules=None):
         """Read a scanned page: segment it into word boxes (aocr_segment_page), crop them (aocr_crop_lines) and recognise the crops.
         page: a uint8 (H,W) numpy array or tensor (gray; a 3-D array raises ValueError unless `colour` is asked for: see below).  params: an
         `aocr.SegmentParams` (default: Otsu threshold, dark text).  The counts and boxes are read back once (the one sync), then the boxes are
@@ -597,7 +599,19 @@ class Model:
         crossings, of horizontal rules, of vertical rules, candidates kept, 0), rules_erased and rules_kept.  With clean: clean runs earlier
         and still deletes a grid higher than its max_h together with what touches it: for forms pass clean=aocr.CleanParams(max_h=0) (specks
         only) together with rules=True.  Limits (rules thicker than max_thick, dashed leaders, pages not deskewed, letter bottoms within
-        `edge` of a rule they sit on, long thin headline strokes): DESIGN.md section 24."""
+        `edge` of a rule they sit on, long thin headline strokes): DESIGN.md section 24.
+        panels: None or False (the default) reads the page with one polarity, that of `params`.  True or an `aocr.PanelParams` first finds
+        the reversed-out panels -- table header rows, section bars, banners, sidebar boxes: light text on a dark slab -- and inverts the
+        bytes inside them (aocr_invert_panels: a connected component whose box is at least min_w x min_h, that fills at least
+        fill_percent of its row-convex hull and has at least min_inside_percent of the hull not ink; True: 64 x 24, 60 %, 2 %, with the
+        threshold and light_text of `params`: a judgement for 300 dpi, untuned), after scale and before clean, which would otherwise
+        paint the slab over as a figure, words and all; every later stage reads the page with the slabs inverted.  At most 256
+        candidates are examined.  The boxes do not move, so every *_corners field stays what it is.  The counts and the panel rows come
+        back with the existing readback (no additional sync).  The namespace then also carries panels (n, 8) int32, one row x0 y0 x1 y1
+        label area hull accepted per examined candidate in label order, in the coordinates of the page after the scale stage (before
+        any quarter turn, deskew or dewarp), and panel_counts (8) int64 (components, candidates found, candidates examined, panels
+        inverted, threshold, total ink, the sum of the inverted hulls, 0).  Limits (one level of nesting, gray rim pixels, solid bars,
+        slabs that touch a grid): DESIGN.md section 26."""
         if asked(colour):
             ok = isinstance(page, (np.ndarray, torch.Tensor)) and len(page.shape) == 3 and page.shape[2] == 3 and \
                 page.dtype == (np.uint8 if isinstance(page, np.ndarray) else torch.uint8)
@@ -626,6 +640,7 @@ class Model:
         page, rect = rectify_stage(page, stream, seg, rectify)
         page, flat = flatten_stage(page, stream, seg, flatten)
         page, scl = scale_stage(page, stream, seg, scale)
+        page, panels_dev = panels_stage(page, stream, seg, panels)
         page0, clean_dev = clean_stage(page, stream, seg, clean)
         page, quarter, orient_runs = orient_stage(page0, stream, seg, orient)
         middle = (stream, seg, max_boxes, deskew, dewarp, layout, clean_dev) + (() if colour_dev is None else (colour_dev,))
@@ -634,6 +649,8 @@ class Model:
             extra["spacing"] = spacing
         if asked(rules):
             extra["rules"] = rules
+        if panels_dev is not None:
+            extra["panels_dev"] = panels_dev
         st = self._page_boxes(page, *middle, **extra)
         orient_scores = None
         if orient is True:
@@ -701,6 +718,9 @@ class Model:
         if st.rules is not None:
             res.rules_counts = st.rules.astype(np.int64)
             res.rules_erased, res.rules_kept = int(st.rules[2]), int(st.rules[6])
+        if st.panels is not None:
+            res.panel_counts = st.panels[:8].astype(np.int64)
+            res.panels = st.panels[8:].reshape(-1, 8)[:int(st.panels[2])].astype(np.int32)
         curl = skew = turn = None                                   # what each stage left behind for aocr.page.backmap_corners
         if st.curl is not None:
             res.curl_shifts, res.curl_group = st.curl[4:].astype(np.int32), st.curl_group

@@ -26,7 +26,9 @@ such a crop reaches beyond its box on either side.  The boxes do not move.  One 
 whose lines are set in different sizes goes through `segment_page_spaced_device` (`aocr_segment_page_spaced`: the gap of every line
 estimated from the line's own gaps) in place of `segment_page_device`.  A form or a table is text that touches rules, one component with
 them: `remove_rules_device` (`aocr_remove_rules`: run lengths per pixel) takes out what is long one way and thin the other and leaves the
-strokes that cross it, after the deskew and before layout and segmentation.  The boxes do not move."""
+strokes that cross it, after the deskew and before layout and segmentation.  The boxes do not move.  A table header row or a section bar
+is light text on a dark slab, one component that holds no readable crop: `invert_panels_device` (`aocr_invert_panels`) finds such slabs
+among the components and inverts the bytes inside their row spans, in front of `clean_page_device`.  The boxes do not move."""
 from __future__ import annotations
 
 import ctypes as C
@@ -35,7 +37,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import Box, CleanParams, ColourParams, CurlParams, FlattenParams, GlyphParams, LayoutParams, RectifyParams, RuleParams, ScaleParams, SegmentParams, SkewParams, SlantParams, SpacingParams, check, lib, ptr
+from ._lib import Box, CleanParams, ColourParams, CurlParams, FlattenParams, GlyphParams, LayoutParams, PanelParams, RectifyParams, RuleParams, ScaleParams, SegmentParams, SkewParams, SlantParams, SpacingParams, check, lib, ptr
 
 IMG_H = 32
 MIN_ASPECT = 0.5
@@ -292,6 +294,27 @@ def remove_rules_device(page_dev, params=None, stream=None):
     check(lib.aocr_remove_rules(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), ptr(out), W, ptr(counts)),
           "aocr_remove_rules")
     return out, counts
+
+
+def invert_panels_device(page_dev, params=None, max_panels=256, stream=None):
+    """(out, panels, counts): out a new (H, W) uint8 device tensor, the page with its reversed-out panels inverted by `aocr_invert_panels`
+    (255 - v inside the row spans of every dark slab that carries light text, every other byte copied); panels (max_panels, 8) int32, one
+    row x0 y0 x1 y1 label area hull accepted per examined candidate in label order (the rows behind them are 0); counts (8) int32:
+    components, candidates found, candidates examined (min(found, max_panels)), panels inverted, threshold, total ink, the sum of the
+    inverted panels' hulls, 0.  params: a `PanelParams` (default: Otsu, boxes of at least 64 x 24, 60 % filled, 2 % inside).  Enqueues only.
+    stream: as for `segment_page_device`, the current torch stream; the scratch (a little over 4 bytes per pixel and 8 bytes per candidate
+    and row) is freed when this returns."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    params = params if params is not None else PanelParams()
+    dev = page_dev.device
+    scratch = _scratch("aocr_panels_scratch_bytes", dev, H, W, int(max_panels))
+    out = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    panels = torch.zeros((int(max_panels), 8), dtype=torch.int32, device=dev)
+    counts = torch.zeros(8, dtype=torch.int32, device=dev)
+    check(lib.aocr_invert_panels(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), ptr(out), W, int(max_panels),
+                                 ptr(panels), ptr(counts)), "aocr_invert_panels")
+    return out, panels, counts
 
 
 def rotate_page_device(page_dev, quarter, orient_dev=None, stream=None):

@@ -1,5 +1,5 @@
-"""The stage chain of `Model.recognize_page` in front of the recogniser, as plain functions of the page: colour, rectify, flatten, scale, clean
-and the quarter turn (one function each, in that order), then `page_boxes`: deskew, dewarp, rule removal, layout and segmentation down to
+"""The stage chain of `Model.recognize_page` in front of the recogniser, as plain functions of the page: colour, rectify, flatten, scale, panels,
+clean and the quarter turn (one function each, in that order), then `page_boxes`: deskew, dewarp, rule removal, layout and segmentation down to
 the boxes on the host.  Every function takes the page on the device, the raw handle of the current torch stream and the page's resolved `SegmentParams`,
 enqueues on that stream, and returns the page with a small record of what it did (None when the stage was not asked for).  What needs a
 model -- the which-way-up probe, the crop-and-recognise loop, the lexicon -- stays in `Model`; the way back from box corners to the page as
@@ -13,11 +13,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from .page import (clean_page_device, deskew_page_device, estimate_slant_device, dewarp_page_device, estimate_curl_device, estimate_glyph_size_device,
+from .page import (clean_page_device, invert_panels_device, deskew_page_device, estimate_slant_device, dewarp_page_device, estimate_curl_device, estimate_glyph_size_device,
                    estimate_orientation_device, gray_page_device, estimate_skew_device, find_page_quad_device, flatten_page_device, layout_page_device,
                    rectify_plan, remove_rules_device, resize_page_device, rotate_page_device, scale_plan, segment_page_device, segment_page_spaced_device, warp_page_device)
 
 MAX_BLOCKS = 256
+MAX_PANELS = 256
 
 
 def asked(option):
@@ -107,6 +108,22 @@ def scale_stage(page, stream, seg, scale):
     return page, scl
 
 
+def panels_stage(page, stream, seg, panels):
+    """(page, [the eight panel counts, the MAX_PANELS panel rows] on the device: they come back with the boxes' readback).  After the scale
+    stage (min_w and min_h are pixels at the normalised size) and before the clean stage, which then sees the text of an inverted slab
+    and not the slab, a figure to paint over.  panels True: the defaults with the threshold and light_text of the segment params."""
+    if not asked(panels):
+        return page, None
+    if isinstance(panels, _lib.PanelParams):
+        pp = panels
+    elif panels is True:
+        pp = _lib.PanelParams(threshold=seg.threshold, light_text=seg.light_text)
+    else:
+        raise ValueError(f"panels={panels!r}: None, False, True or an aocr.PanelParams")
+    page, rows_dev, counts_dev = invert_panels_device(page, pp, MAX_PANELS, stream)
+    return page, [counts_dev, rows_dev]
+
+
 def clean_stage(page, stream, seg, clean):
     """(page, the eight clean counts on the device: they come back with the boxes' readback)."""
     if not asked(clean):
@@ -162,7 +179,7 @@ def rule_params(seg, rules):
     raise ValueError(f"rules={rules!r}: None, False, True or an aocr.RuleParams")
 
 
-def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None, deslant=None, spacing=None, rules=None):
+def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None, deslant=None, spacing=None, rules=None, panels_dev=None):
     """the middle of recognize_page, from the deskew to the boxes on the host: everything that reads the page in its final orientation and
     has to be redone when recognize_page(orient=True) turns the page by another half turn.  Returns a namespace: page, boxes_dev, rows, counts,
     n, truncated; skew, cleaned, curl, colour (the words read back, None without the stage), curl_group; lay, blocks, block_id, nb, lcounts
@@ -171,7 +188,9 @@ def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, 
     readback of its own.  spacing (n_lines, 8): the rows of aocr_segment_page_spaced, which then takes the place of aocr_segment_page (None
     without spacing); they too come back with the boxes.  rules: aocr_remove_rules after the deskew and the dewarp (a rule is a pure row run
     only on a straight page) and before layout and segmentation (a column-separator rule sits in the gutter the XY cut looks for); st.page
-    is then the page with the rules taken out, st.rules its eight counts, which ride with the first readback (None without rules)."""
+    is then the page with the rules taken out, st.rules its eight counts, which ride with the first readback (None without rules).
+    panels_dev: what panels_stage left on the device, one more rider of the first readback; st.panels is then its words end to end, the
+    eight counts and the MAX_PANELS rows of eight (None without the stage)."""
     st = SimpleNamespace(curl_group=None, lay=None, blocks=None, block_id=None, nb=None, lcounts=None, slant=None, slant_dev=None, spacing=None)
     skew_dev = curl_dev = rules_dev = None
     ruled = rule_params(seg, rules) if asked(rules) else None
@@ -194,7 +213,7 @@ def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, 
     if ruled is not None:
         page, rules_dev = remove_rules_device(page, ruled, stream)
     st.page = page
-    riders = dict(skew=skew_dev, cleaned=clean_dev, curl=curl_dev, colour=colour_dev, rules=rules_dev)            # what comes back with the first readback, whichever it is
+    riders = dict(skew=skew_dev, cleaned=clean_dev, curl=curl_dev, colour=colour_dev, rules=rules_dev, panels=panels_dev)            # what comes back with the first readback, whichever it is
     if asked(layout):
         st.lay = layout if isinstance(layout, _lib.LayoutParams) else _lib.LayoutParams()
         blocks_dev, lcounts_dev, info_dev = layout_page_device(page, st.lay, seg.threshold, seg.light_text, MAX_BLOCKS, stream)
@@ -272,4 +291,5 @@ def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, 
                 st.spacing = back[at:at + 8 * lines].reshape(-1, 8)
         st.truncated = bool(st.counts[0] > max_boxes)
     st.skew, st.cleaned, st.curl, st.colour, st.rules = got.get("skew"), got.get("cleaned"), got.get("curl"), got.get("colour"), got.get("rules")
+    st.panels = got.get("panels")
     return st

@@ -1130,6 +1130,51 @@ int aocr_remove_rules(void* stream, const uint8_t* page_dev, int64_t pitch, int3
   return check_launch("aocr_remove_rules");
 }
 
+static bool panels_size_ok(int32_t H, int32_t W, int32_t max_panels) { return page_size_ok(H, W) && max_panels >= 1 && max_panels <= 1024; }
+
+size_t aocr_panels_scratch_bytes(int32_t H, int32_t W, int32_t max_panels) {
+  if (!panels_size_ok(H, W, max_panels)) {
+    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26) max_panels=%d (1..1024)", H, W, max_panels);
+    return 0;
+  }
+  return panels_scratch_bytes(H, W, max_panels);
+}
+
+int aocr_invert_panels(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_panel_params* params,
+                       void* scratch_dev, uint8_t* out_dev, int64_t out_pitch, int32_t max_panels, int32_t* panels_dev, int32_t counts_dev[8]) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(params, "params is NULL");
+  if (check_threshold(params->threshold)) return 1;
+  REQUIRE(params->connectivity == 4 || params->connectivity == 8, "connectivity=%d: 4 or 8", params->connectivity);
+  REQUIRE(params->min_w >= 1 && params->min_h >= 1, "min_w=%d min_h=%d must be >= 1", params->min_w, params->min_h);
+  REQUIRE(params->fill_percent >= 1 && params->fill_percent <= 100, "fill_percent=%d: 1..100", params->fill_percent);
+  REQUIRE(params->min_inside_percent >= 0 && params->min_inside_percent <= 99, "min_inside_percent=%d: 0..99", params->min_inside_percent);
+  REQUIRE(params->fill_percent + params->min_inside_percent <= 100, "fill_percent=%d + min_inside_percent=%d is more than 100", params->fill_percent,
+          params->min_inside_percent);
+  REQUIRE(params->reserved == 0, "the reserved word must be 0");
+  REQUIRE(max_panels >= 1 && max_panels <= 1024, "max_panels=%d: 1..1024", max_panels);
+  if (check_scratch(scratch_dev, out_dev && counts_dev)) return 1;
+  REQUIRE(((uintptr_t)counts_dev & 3) == 0 && ((uintptr_t)panels_dev & 3) == 0, "counts_dev and panels_dev must be 4-byte aligned");
+  if (check_out(page_dev, pitch, H, W, out_dev, out_pitch, H, W)) return 1;
+  const Span page = span_rows(page_dev, pitch, H, W), out = span_rows(out_dev, out_pitch, H, W);
+  const Span scratch = span_bytes(scratch_dev, panels_scratch_bytes(H, W, max_panels));
+  REQUIRE(disjoint(out, scratch), "out_dev overlaps the scratch");
+  REQUIRE(disjoint(scratch, page), "scratch_dev overlaps the page");
+  const Span counts = span_bytes(counts_dev, 8 * sizeof(int32_t));
+  REQUIRE(disjoint(counts, page), "counts_dev overlaps the page");
+  REQUIRE(disjoint(counts, out), "counts_dev overlaps out_dev");
+  REQUIRE(disjoint(counts, scratch), "counts_dev overlaps the scratch");
+  if (panels_dev) {
+    const Span panels = span_bytes(panels_dev, (size_t)max_panels * 8 * sizeof(int32_t));
+    REQUIRE(disjoint(panels, page), "panels_dev overlaps the page");
+    REQUIRE(disjoint(panels, out), "out_dev overlaps panels_dev");
+    REQUIRE(disjoint(panels, scratch), "panels_dev overlaps the scratch");
+    REQUIRE(disjoint(panels, counts), "panels_dev overlaps counts_dev");
+  }
+  invert_panels((hipStream_t)stream, page_dev, pitch, H, W, *params, scratch_dev, out_dev, out_pitch, max_panels, panels_dev, counts_dev);
+  return check_launch("aocr_invert_panels");
+}
+
 int aocr_rotate_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const int32_t* orient_dev, int32_t quarter,
                      uint8_t* out_dev, int64_t out_pitch) {
   if (check_page(page_dev, pitch, H, W)) return 1;

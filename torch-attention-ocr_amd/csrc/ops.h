@@ -439,6 +439,11 @@ void clean_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W,
 size_t rules_scratch_bytes(int H, int W);
 void remove_rules(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_rule_params& p, void* scratch, uint8_t* out,
                   int64_t out_pitch, int32_t* counts);
+// reversed-out panels (panels.hip; include/aocr.h: aocr_invert_panels): the slabs among the components of components.hip, 255 - v inside their row
+// spans; panels may be nullptr
+size_t panels_scratch_bytes(int H, int W, int max_panels);
+void invert_panels(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_panel_params& p, void* scratch, uint8_t* out,
+                   int64_t out_pitch, int max_panels, int32_t* panels, int32_t* counts);
 // where the launches of label_components leave every component's area (components.hip): the record of the component whose first pixel in
 // raster order is (rx, ry) is the four words at rec + 4 * (ry * sw + (rx >> 1)): area, min x, max x, max y.  scratch: label_components' own
 struct ComponentAreas { const int32_t* rec; int sw; };
