@@ -349,3 +349,173 @@ def words(seed, n=25, alphabet="abcdefghij0123", lo=1, hi=4):
     g = _gen(seed)
     pick = lambda k: int(torch.randint(0, k, (1,), generator=g))
     return ["".join(alphabet[pick(len(alphabet))] for _ in range(lo + pick(hi - lo + 1))) for _ in range(n)]
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# beam search (the kernels' BEAM instantiations; model.lua:360-536, the rule of tail_ref.beam_step / select_topk / gather_rows)
+# ------------------------------------------------------------------------------------------------------------------------------
+EOS_BOOST = 6.0                     # flag "eos": added to the EOS bias, so that hypotheses finish early and compete with live ones
+# (B, T, L, k, seed, flags) of the beam cases of tests/test_decoder_seq_kernels_gpu.py; flags: "" / "dict-<alphabet>" (beam_words) / "eos" / "pool".  Seeds picked with the
+# free-running reference below so that beam_conditions holds (tests/test_dec_seq_ref_cpu.py asserts it).  The XCD-cap shape depends on the device
+# (beam_cap_case) and is added there -- the CPU test takes it at a cap of 8 groups.
+BEAM_CASES = [(16, 5, 8, 2, 104, ""), (5, 17, 26, 3, 151, ""), (11, 16, 12, 3, 122, ""), (11, 16, 24, 3, 50, ""), (7, 65, 20, 5, 35, ""), (9, 64, 16, 7, 87, ""),
+              (11, 16, 12, 3, 51, "dict-6ga"), (9, 64, 16, 7, 52, "dict-6g"), (11, 16, 12, 3, 50, "eos")]
+BEAM_CAP_SEED = 62
+# The XCD-cap case ("pool"): a search of 32 steps at k = 8 keeps hypotheses that differ in one early token and end within fp32 rounding of each other, more of
+# them than the near-tie cap allows in a batch taken as generated.  The images of a batch do not interact, so the case takes its images (context, ctx W_a,
+# initial state) as rows of a larger batch of `operands` with the case's seed -- weights, token table and projector are the seed's as in every other case.  The
+# rows are those with the fewest near-tied picks in the free-running reference at a cap of 8 groups (33 images); another cap takes further rows in order, and
+# tests/test_dec_seq_ref_cpu.py checks the conditions at 8 only.
+BEAM_CAP_POOL = 256
+BEAM_CAP_ROWS = [6, 13, 17, 20, 25, 35, 46, 73, 81, 95, 99, 100, 106, 109, 112, 119, 123, 125, 129, 132, 138, 145, 152, 156, 170, 183, 185, 195, 197, 203, 208, 218, 251]
+
+
+def beam_cap_case(cap):
+    """the smallest two-pass shape of the one-group-per-XCD cap at k = 8 (4 images per group): 4 cap + 1 images, L the smallest with L B >= 128 cap"""
+    B = 4 * cap + 1
+    return (B, 5, -(-128 * cap // B), 8, BEAM_CAP_SEED, "pool")
+
+
+def beam_operands(B, T, seed, flags):
+    """`operands` of a beam case; "pool": the images are rows of a larger batch of the same generator (BEAM_CAP_ROWS, then the pool's other rows in order)"""
+    if "pool" not in flags:
+        return operands(B, T, seed)
+    rows = BEAM_CAP_ROWS + [r for r in range(BEAM_CAP_POOL) if r not in BEAM_CAP_ROWS]
+    return take_rows(operands(max(BEAM_CAP_POOL, B), T, seed), (rows + list(range(BEAM_CAP_POOL, B)))[:B])
+
+
+def beam_projector(seed, flags):
+    wo, bo = projector(seed)
+    if "eos" in flags:
+        bo[EOS - 1] += EOS_BOOST
+    return wo, bo
+
+
+BEAM_WORDS = 6000
+
+
+def beam_words(seed, L, alphabet):
+    """the word list of a "dict-<alphabet>" case: words(seed) over `alphabet`, 1 .. L + 2 characters, each behind one of the two planted twin classes as a
+    character ("6" = 10, "g" = 20).  The start node so has TWO children, fewer than any beam used with it: an exact tie, then the repeat-the-best fallback.  The
+    alphabet is small and the list long so that the tree stays dense down to depth ~L: where a node has one child, PAD (always admissible) enters the beam and no
+    image is left without a finished hypothesis."""
+    return ["6g"[i % 2] + w for i, w in enumerate(words(seed, n=BEAM_WORDS, alphabet=alphabet, lo=1, hi=L + 2))]
+
+
+def beam_trie(seed, flags, L):
+    """the flat trie (mask, base, child) of the case's word list (dict_oracle.load_dictionary, tail_ref.flat_trie), or None"""
+    if "dict" not in flags:
+        return None
+    import dict_oracle as DO
+    import tail_ref as TR
+    return TR.flat_trie(DO.load_dictionary(beam_words(seed, L, flags.split("dict-")[1])))[:3]
+
+
+def take_rows(o, rows):
+    """the operands of `operands` with the per-image ones (context, ctx W_a, initial state) replaced by those of the images `rows` (repeats allowed)"""
+    rows = torch.as_tensor(rows).long()
+    return {**o, "ctx": o["ctx"][rows].contiguous(), "ctxa": o["ctxa"][rows].contiguous(), "c0": o["c0"][:, rows].contiguous(),
+            "h0": o["h0"][:, rows].contiguous(), "feed0": o["feed0"][rows].contiguous()}
+
+
+def beam(w, table, wo, bo, c0, h0, feed0, L, k, trie=None, round=True):
+    """free-running beam search from GO: greedy's step arithmetic on the rows image * kin + hypothesis (kin = 1 at step 0; the context is not replicated),
+    tail_ref.beam_step's selection, tail_ref.gather_rows' state gather by parent.  -> dict(hist_tok, hist_par [L][B][k] int64, scores [L][B][k] running,
+    totals: per step [B][kin V] (the candidates the selection saw, -inf = inadmissible), free: the same without the dictionary, out: per step
+    [B kin][H] and a: per step [B kin][T] of the rows that ENTERED the step, tol_mag: per step [B kin] = max_v |out| . |W_o|)"""
+    import tail_ref as TR
+    r = rne if round else (lambda x: x)
+    B = c0.shape[1]
+    cs, hs, out = [c0[0].to(F64), c0[1].to(F64)], [h0[0].to(F64), h0[1].to(F64)], feed0.to(F64)
+    tok, scores, loc = torch.full((B,), GO, dtype=torch.int64), None, None
+    res = dict(hist_tok=[], hist_par=[], scores=[], totals=[], free=[], out=[], a=[], tol_mag=[])
+    for t in range(L):
+        kin = 1 if t == 0 else k
+        img = torch.arange(B).repeat_interleave(kin)
+        z1 = table.to(F64)[tok - 1] + r(out) @ w.W1i.t() + r(hs[0]) @ w.W1h.t()
+        cs[0], hs[0], _ = cell(z1, cs[0])
+        z2 = w.b2 + r(hs[0]) @ w.W2i.t() + r(hs[1]) @ w.W2h.t()
+        cs[1], hs[1], _ = cell(z2, cs[1])
+        h2b = r(hs[1])
+        a, c, _ = attention(h2b, w.ctx[img], w.ctxa[img])
+        out = torch.tanh(torch.cat([r(c), h2b], 1) @ w.Wc.t())
+        lp, mag = logprobs(out.float() if round else out, wo, bo)      # (the projector reads the fp32 out)
+        prev = None if t == 0 else tok
+        res["free"].append(TR.beam_totals(lp, prev, scores, B, kin, lp.shape[1]))
+        res["totals"].append(TR.beam_totals(lp, prev, scores, B, kin, lp.shape[1], trie, loc) if trie is not None else res["free"][-1])
+        toks, pars, vals, locs = TR.beam_step(lp, prev, scores, B, kin, k, lp.shape[1], trie, loc, check_gap=False)
+        res["hist_tok"].append(toks); res["hist_par"].append(pars); res["scores"].append(vals)
+        res["out"].append(out); res["a"].append(a); res["tol_mag"].append(mag.amax(dim=1))
+        cs = [TR.gather_rows(x, pars, B, kin, k) for x in cs]
+        hs = [TR.gather_rows(x, pars, B, kin, k) for x in hs]
+        out = TR.gather_rows(out, pars, B, kin, k)
+        tok, scores, loc = toks.reshape(-1), vals, (locs.reshape(-1) if trie is not None else None)
+    for n in ("hist_tok", "hist_par", "scores"):
+        res[n] = torch.stack(res[n])
+    return res
+
+
+def pick_classes(tot, tol, k):
+    """One selection against its reference candidates.  tot: [n] float64 reference totals, tol: [n] the tolerance of every candidate (its parent row's).
+    Reference order = tail_ref.select_topk (descending, ties -> lowest index, the best repeated when fewer than k are admissible).  Rank i is UNDECIDED
+    when the next distinct candidate value BELOW the reference's rank-i value lies within 2 tol of it (exact ties, the planted twins', are not distinct
+    values), and LOOSE when it is undecided or the next distinct value ABOVE it lies within 2 tol (the device may have swapped it with the undecided pick
+    above).  -> dict(ref: the reference indices, kth: the reference's k-th best value, undecided, loose: [k] bool, fallback: the ranks that repeat the best,
+    ties: the ranks whose successor has exactly the same value)"""
+    import tail_ref as TR
+    vals = [float(v) for v in tot]
+    ref, rv = TR.select_topk(vals, k)
+    nfin = sum(1 for v in vals if v > -float("inf"))
+    fin = tot[torch.isfinite(tot)]
+    und, loose, ties = [], [], []
+    for i in range(k):
+        if i >= nfin:
+            und.append(False); loose.append(False)
+            continue
+        lo, hi = fin[fin < rv[i]], fin[fin > rv[i]]
+        t2 = 2 * float(tol[ref[i]])
+        und.append(bool(len(lo)) and rv[i] - lo.max().item() <= t2)
+        loose.append(und[-1] or (bool(len(hi)) and hi.min().item() - rv[i] <= t2))
+        if i + 1 < min(k, nfin) and rv[i + 1] == rv[i]:
+            ties.append(i)
+    return dict(ref=ref, kth=rv[min(k, nfin) - 1] if nfin else -float("inf"), undecided=und, loose=loose,
+                fallback=list(range(max(nfin, 1), k)) if nfin < k else [], ties=ties)
+
+
+def beam_conditions(hist_tok, hist_par, totals, free, k, dictionary):
+    """the conditions on a beam case (of the free-running reference, or of the device's own history with the reference totals of stage 2) -> (ok, text, counts)"""
+    L, B = hist_tok.shape[0], hist_tok.shape[1]
+    fin = (hist_tok == PAD) | (hist_tok == EOS)                         # [L][B][k]: the hypothesis is finished after the step
+    n = dict(eos=int((hist_tok[:L - 1] == EOS).sum()), mixed=int((fin.any(2) & ~fin.all(2)).any(0).sum()), never=int((~fin.any(2).any(0)).sum()),
+             moved=0, twice=0, ties=0, few=0, masked=0)
+    own = torch.arange(k).view(1, 1, k)
+    n["moved"] = int((hist_par[1:] != own).sum())
+    n["twice"] = sum(int(len(set(hist_par[t, b].tolist())) < k) for t in range(1, L) for b in range(B))
+    for t in range(L):
+        V = totals[t].shape[1] // (1 if t == 0 else k)
+        for b in range(B):
+            tk, pr = hist_tok[t, b].tolist(), hist_par[t, b].tolist()
+            row = totals[t][b]
+            for i in range(k - 1):
+                if (tk[i], tk[i + 1]) == TIE and pr[i] == pr[i + 1] and row[pr[i] * V + tk[i] - 1] == row[pr[i + 1] * V + tk[i + 1] - 1]:
+                    n["ties"] += 1
+            if dictionary:
+                n["few"] += int(int(torch.isfinite(row).sum()) < k)
+                top = torch.sort(free[t][b], descending=True, stable=True).indices[:k]
+                n["masked"] += int(bool((row[top] == -float("inf")).any()))
+    ok = n["eos"] >= 3 and n["mixed"] >= 1 and n["never"] >= 1 and n["moved"] >= 1 and n["twice"] >= 1 and n["ties"] >= 1
+    if dictionary:
+        ok = ok and n["few"] >= 1 and n["masked"] >= 1
+    return ok, ", ".join(f"{a} {v}" for a, v in n.items()), n
+
+
+def beam_undecided_share(ref, k, tol_of, factor):
+    """share of the ranks of every selection of a free-running reference that are undecided at `factor` / 2 times the 2 tol of pick_classes"""
+    und = total = 0
+    for t, tot in enumerate(ref["totals"]):
+        kin = 1 if t == 0 else k
+        tol = tol_of(ref["tol_mag"][t]).view(-1, kin, 1).expand(-1, kin, tot.shape[1] // kin).reshape(tot.shape) * (factor / 2.0)
+        for b in range(tot.shape[0]):
+            c = pick_classes(tot[b], tol[b], k)
+            und += sum(c["undecided"]); total += k
+    return und / total

@@ -30,7 +30,7 @@ SWITCHES = ("AOCR_FORCE_DMA", "AOCR_HALO8", "AOCR_HALO4_STAGED", "AOCR_NO_HALO",
             # the attention launchers
             "AOCR_NO_ATTN_BF16", "AOCR_ATTN_NW16", "AOCR_NO_ATTN_BEAM_GROUP", "AOCR_ATTN_BWD_TWO_PASS", "AOCR_NO_CHAIN_CTXA",
             # the whole-sequence decoder launchers
-            "AOCR_NO_DEC_CHAINS", "AOCR_NO_DEC_CHAINS_BWD", "AOCR_NO_DEC_CHAINS_GREEDY", "AOCR_CH_NO_RES", "AOCR_NO_DEC_EARLY", "AOCR_CL_REMOTE",
+            "AOCR_NO_DEC_CHAINS", "AOCR_NO_DEC_CHAINS_BWD", "AOCR_NO_DEC_CHAINS_GREEDY", "AOCR_NO_DEC_CHAINS_BEAM", "AOCR_CH_NO_RES", "AOCR_NO_DEC_EARLY", "AOCR_CL_REMOTE",
             "AOCR_DC_STAMPS")
 EP_RELU, EP_TANH, EP_ACCUM = 1, 2, 4
 TOL_CELL = 2e-5                     # test_ops_gpu.py::test_lstm_cell, exact-fp32 cell
@@ -120,6 +120,9 @@ _INT = {                                                              # return i
     # the whole-sequence decoder kernels (tests/test_decoder_seq_kernels_gpu.py)
     "kp_dec_cluster_supported": [i32] * 5, "kp_dec_cluster_bwd_supported": [i32] * 5,
     "kp_dec_cluster_forward": [vp, vp], "kp_dec_cluster_backward": [vp, vp],
+    # beam search on the chain kernel (the beam tests of tests/test_decoder_seq_kernels_gpu.py)
+    "kp_dec_chain_beam_supported": [i32] * 4, "kp_dec_chain_beam_passes": [i32] * 3, "kp_dec_chain_beam_group_cap": [],
+    "kp_dec_chain_beam_forward": [vp, vp],
 }
 _SIZE = {                                                             # return size_t
     "kp_bn_scratch_bytes": [i32],

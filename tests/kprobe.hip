@@ -677,4 +677,39 @@ int kp_dec_cluster_backward(hipStream_t s, const KpDecBwd* p) {
   return (int)hipGetLastError();
 }
 
+// ---- beam search on the chain kernel (csrc/dec_chain.hip, the BEAM instantiations of dec_ch_fwd_kernel), for the beam tests of
+// tests/test_decoder_seq_kernels_gpu.py.  f: what model.hip's decode function sets in the k > 1 branch (greedy, gates, out, the dropout and zx_tok fields are not read);
+// a launch is dec_chain_beam_passes() kernels with consecutive epochs from f.epoch, each indexing pbuf / xtab by the group WITHIN the launch, so those two are
+// sized -- as the model sizes them -- for max(B, 32 * dec_chain_beam_group_cap()) rows.  labels / scores are carried but not written: the model's back-trace fills them.
+struct KpDecBeam { KpDecFwd f; int beam; int32_t* hist_tok; int32_t* hist_par; float* beam_scores; };
+
+int kp_dec_chain_beam_supported(int B, int L, int k, int V) { return aocr::dec_chain_beam_supported(B, L, k, V) ? 1 : 0; }
+int kp_dec_chain_beam_passes(int B, int L, int k) { return aocr::dec_chain_beam_passes(B, L, k); }
+int kp_dec_chain_beam_group_cap() { return aocr::dec_chain_beam_group_cap(); }
+int kp_dec_chain_beam_forward(hipStream_t s, const KpDecBeam* b) {
+  const KpDecFwd* p = &b->f;
+  if (p->V < 1 || !aocr::dec_chain_beam_supported(p->B, p->L, b->beam, p->V)) return KP_DEC_UNSUPPORTED;
+  if (!aocr::dec_cluster_supported(p->Hd, 2, 1, p->T, p->L, kp_cus())) return KP_DEC_UNSUPPORTED;
+  const unsigned passes = (unsigned)aocr::dec_chain_beam_passes(p->B, p->L, b->beam);
+  if (p->epoch == 0 || p->epoch >= (1u << 20) || p->epoch + passes >= (1u << 20)) return KP_DEC_BAD_ARGS;
+  if (!b->hist_tok || !b->hist_par || !b->beam_scores || (p->sc_hist && !p->a_all)) return KP_DEC_BAD_ARGS;      // (HIST stores the attention rows too)
+  if (!p->tok0 || p->tok0_stride < p->L || !p->wo || !p->bo) return KP_DEC_BAD_ARGS;
+  const int rows = std::max(p->B, 32 * aocr::dec_chain_beam_group_cap());
+  if (!p->xbuf || p->xbuf_bytes < aocr::dec_cluster_xbuf_bytes(p->B)) return KP_DEC_XBUF_SMALL;
+  if (!p->pbuf || p->pbuf_bytes < aocr::dec_cluster_pbuf_bytes(rows)) return KP_DEC_PBUF_SMALL;
+  if (!p->xtab || p->xtab_bytes < aocr::dec_cluster_xtab_bytes(rows)) return KP_DEC_XTAB_SMALL;
+  if (!p->err || p->err_ints < 16 + 256 * 8 + 4096) return KP_DEC_ERR_SMALL;
+  aocr::DecClFwdArgs a; a.B = p->B; a.T = p->T; a.L = p->L; a.epoch = p->epoch;
+  a.w1i = H16(p->w1i); a.w1h = H16(p->w1h); a.w2i = H16(p->w2i); a.w2h = H16(p->w2h); a.wc = H16(p->wc);
+  a.b2i = p->b2i; a.b2h = p->b2h; a.zx1 = p->zx1; a.ctxb = H16(p->ctxb); a.ctxa = H16(p->ctxa);
+  for (int l = 0; l < 2; ++l) { a.cs[l] = p->cs[l]; a.hsb[l] = W16(p->hsb[l]); a.gates[l] = nullptr; }
+  a.a_all = p->a_all; a.sc_hist = p->sc_hist; a.out = p->out; a.cat_b = W16(p->cat_b); a.out_b = W16(p->out_b);
+  a.xbuf = p->xbuf; a.xtab = p->xtab; a.err = p->err;
+  a.tok0 = p->tok0; a.tok0_stride = p->tok0_stride; a.wo = p->wo; a.bo = p->bo; a.V = p->V; a.pbuf = p->pbuf; a.labels = p->labels; a.scores = p->scores;
+  a.beam = b->beam; a.hist_tok = b->hist_tok; a.hist_par = b->hist_par; a.beam_scores = b->beam_scores;
+  a.trie_mask = p->trie_mask; a.trie_base = p->trie_base; a.trie_child = p->trie_child;
+  aocr::dec_chain_beam_forward(s, a);
+  return (int)hipGetLastError();
+}
+
 }  // extern "C"

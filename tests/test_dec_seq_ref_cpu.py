@@ -164,3 +164,68 @@ def test_greedy_cases_keep_their_conditions(B, T, L, seed):
     gt = R.greedy(w, table, wo, bo, o["c0"], o["h0"], o["feed0"], L, trie=trie)
     free = R.logprobs(gt["out"][1:].reshape(L * B, R.H).float(), wo, bo)[0].argmax(1).view(L, B) + 1
     assert ((free != gt["labels"].t()) & (gt["labels"].t() != R.PAD)).any(), "the dictionary never masks the unconstrained arg-max"
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# beam search
+# ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k,with_trie", [(3, False), (4, True)])
+def test_beam_reference_matches_oracle_decode_beam(k, with_trie, monkeypatch):
+    """R.beam (rounding off) against oracle_torch.decode_beam on the same decoder: the CNN, the encoder and the initial state of the oracle are replaced by
+    the problem's context and state, so both run the same free-running search; history, labels and scores after the back-trace must agree"""
+    import dict_oracle as DO
+    import tail_ref as TR
+    B, T, L = 4, 5, 7
+    cfg, P, ctx, _, c0, h0, _, _ = _oracle_problem(B, T, L, seed=5)
+    g = torch.Generator().manual_seed(11)
+    P["proj.w"] = (torch.rand(cfg.vocab, H, generator=g, dtype=F64) * 2 - 1) * 1.5
+    P["proj.b"] = torch.rand(cfg.vocab, generator=g, dtype=F64) - 0.5
+    P["proj.b"][R.EOS - 1] += 2.0                                     # some hypotheses finish inside L steps
+    monkeypatch.setattr(O, "cnn_forward", lambda P_, st, images, training, **kw: images)
+    monkeypatch.setattr(O, "encoder_forward", lambda P_, cfg_, feats: (ctx, None))
+    monkeypatch.setattr(O, "decoder_init_state", lambda cfg_, traces, B_, like: ([c0[0], c0[1]], [h0[0], h0[1]]))
+    root = DO.load_dictionary(R.words(3)) if with_trie else None
+    tgt = torch.full((B, L), R.PAD, dtype=torch.int64); tgt[:, 0] = R.GO
+    ref = O.decode_beam(P, None, cfg, torch.zeros(B, 1, dtype=F64), tgt, tgt, beam=k, max_decoder_l=L, trie=root)
+    E, Wi1 = cfg.emb, P["dec.l1.i2h.w"]
+    table = P["dec.lookup"] @ Wi1[:, :E].t() + P["dec.l1.i2h.b"] + P["dec.l1.h2h.b"]
+    w = R.Weights(Wi1[:, E:], P["dec.l1.h2h.w"], P["dec.l2.i2h.w"], P["dec.l2.h2h.w"], P["dec.l2.i2h.b"] + P["dec.l2.h2h.b"], P["dec.attn.wa"],
+                  P["dec.attn.wc"], ctx)
+    trie = TR.flat_trie(root)[:3] if with_trie else None
+    r = R.beam(w, table, P["proj.w"], P["proj.b"], c0, h0, torch.zeros(B, H, dtype=F64), L, k, trie=trie, round=False)
+    assert torch.equal(r["hist_tok"], ref["hist_tok"]) and torch.equal(r["hist_par"], ref["hist_par"])
+    labels, scores = TR.backtrace(r["hist_tok"], r["hist_par"], r["scores"][L - 1])
+    assert torch.equal(labels, ref["labels"])
+    torch.testing.assert_close(scores, ref["scores"], rtol=1e-10, atol=1e-12)
+    assert ((r["hist_tok"] == R.EOS).any() and (r["hist_par"][1:] != torch.arange(k)).any()), "the anchor problem is trivial: no EOS, or no hypothesis changes its slot"
+
+
+def test_pick_classes_hand_cases():
+    inf = float("inf")
+    tol = torch.full((6,), 0.01, dtype=F64)
+    c = R.pick_classes(torch.tensor([1.0, 5.0, 5.0, 3.0, 2.985, -inf], dtype=F64), tol, 3)
+    assert c["ref"] == [1, 2, 3] and c["ties"] == [0] and c["undecided"] == [False, False, True] and c["fallback"] == [] and c["kth"] == 3.0
+    c = R.pick_classes(torch.tensor([-inf, 4.0, -inf, 1.0, -inf, -inf], dtype=F64), tol, 3)
+    assert c["ref"] == [1, 3, 1] and c["fallback"] == [2] and c["undecided"] == [False, False, False] and c["kth"] == 1.0
+
+
+def _beam_cases():
+    return R.BEAM_CASES + [R.beam_cap_case(8)]
+
+
+@pytest.mark.parametrize("B,T,L,k,seed,flags", _beam_cases(), ids=[f"{c[0]}-{c[1]}-{c[2]}-{c[3]}{'-' + c[5] if c[5] else ''}" for c in _beam_cases()])
+def test_beam_cases_keep_their_conditions(B, T, L, k, seed, flags):
+    """the free-running beam reference on the GPU test's inputs: hypotheses that end, finished beside live ones, an image that never ends, picks that change
+    slot, parents chosen twice, planted ties inside a selection; with a dictionary the repeat-the-best fallback and masked free picks; near-ties within 1 %.
+    The XCD-cap shape draws its images from a pool: R.BEAM_CAP_ROWS."""
+    from kernel_harness import TOL_CELL, bound
+    assert L * B >= 128 and 2 <= k <= 8
+    o = R.beam_operands(B, T, seed, flags)
+    w, (table, _) = R.weights_of(o), R.gate_inputs(L, B, seed, True)
+    wo, bo = R.beam_projector(seed, flags)
+    trie = R.beam_trie(seed, flags, L)
+    r = R.beam(w, table, wo, bo, o["c0"], o["h0"], o["feed0"], L, k, trie=trie)
+    ok, txt, _ = R.beam_conditions(r["hist_tok"], r["hist_par"], r["totals"], r["free"], k, trie is not None)
+    assert ok, txt
+    share = R.beam_undecided_share(r, k, lambda mag: TOL_CELL + bound(mag, 512), 4.0)
+    assert share <= 0.01, f"{share:.4f} of the picks have another candidate value within 4 tol"

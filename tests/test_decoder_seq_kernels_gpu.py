@@ -50,6 +50,36 @@ inside them.  A swapped f / o gate in the reference fails every forward and back
   greedy 45-5-12    stage 1 mismatch share 0;  final score error / (n tol) 0.000;  planted ties won 48;  hist: running score 0.002, a_all 0.000;
                     dictionary: score 0.003, 142 steps with the free arg-max masked   (chain [dec,res(,hist)] and cluster [dec(,hist)] alike)
   greedy 33-65-6    stage 1 mismatch share 0;  score 0.001;  ties won 5;  hist: running score 0.002, a_all 0.000;  dictionary: score 0.002, 79 steps masked
+Beam search (dec_chain_beam_forward: DEC + BEAM [+ HIST] through kp_dec_chain_beam_forward; cases R.BEAM_CASES + the XCD-cap shape, seeds chosen with the free-running
+CPU reference R.beam).  Buffers as above plus hist_tok / hist_par / beam_scores / sc_hist / the [L][B k][T] attention history, all sentinel-filled; pbuf / xtab sized
+for max(B, 32 group_cap) rows as in model.hip.  labels / scores KEEP their sentinel: the beam launcher does not write them (model.hip's back-trace does), and so do
+out, the gates, cs behind slot 0 and everything of hsb / out_b / cat_b behind the initial rows and the four rolling step slots.  Stage 1 -- the hypothesis tree is
+rebuilt from the device's own hist_tok / hist_par and every distinct maximal token prefix runs as one row of the teacher-forced kernel (rp.check applied; the XCD-cap
+case replays group by group and applies rp.check to the first and last image of each pass only): the HIST attention rows (row image * kin + hypothesis, kin = 1 at step
+0, the other rows sentinel) and the surviving rolling slots of the last min(4, L) steps (hsb[0], hsb[1], out_b, the h half of cat_b; groups of the last pass) are
+BIT-EQUAL to the replay: product_sum adds the four partial tiles in product's order (mismatch shares 0 in every case).  Stage 2 -- tail_ref.beam_totals of the float64
+logprobs of the replay's fp32 out, the device's own previous sc_hist row, tokens and trie nodes, tol = TOL_CELL + bound(|out| . |W_o|, 512) of the parent row: every
+pick >= the k-th best - 2 tol, scores non-increasing, exact ties in index order, score within tol of the picked candidate's total, PAD after a finished parent at the
+parent's score bits, the repeat-the-best fallback bit for bit, and every DECIDED rank (no other candidate value within 2 tol above or below) equal to the reference's;
+undecided ranks (next value below within 2 tol) <= 2 % of a case.  beam_scores = sc_hist[L-1] in bits; no-history, AOCR_CL_REMOTE=1, AOCR_CH_NO_RES=1 (T <= 64) and a
+second call on the used buffers (epoch advanced by the pass count) give bit-identical histories; kp_beam_backtrace = tail_ref.backtrace; recognize_gather finite and
+summing to sc_hist on the winner.
+  beam (B-T-L-k)       groups/passes  replay rows  a_all  a_all / slot mismatch share  score increment  undecided (loose)  ties won  fallback selections  steps masked
+  16-5-8-2             1/1            64           0.000  0 / 0                        0.006            0.0078 (0.0156)    3         0                    0
+  5-17-26-3            1/1            53           0.000  0 / 0                        0.004            0.0077 (0.0154)    2         0                    0
+  11-16-12-3           2/2            90           0.000  0 / 0                        0.007            0.0000 (0.0000)    1         0                    0
+  11-16-24-3           2/1            129          0.000  0 / 0                        0.004            0.0025 (0.0051)    1         0                    0
+  7-65-20-5            2/2            145          0.000  0 / 0                        0.004            0.0029 (0.0043)    2         0                    0
+  9-64-16-7            3/3            215          0.000  0 / 0                        0.004            0.0050 (0.0089)    5         0                    0
+  11-16-12-3 dict-6ga  2/2            80           0.000  0 / 0                        0.009            0.0051 (0.0126)    90        11                   127
+  9-64-16-7 dict-6g    3/3            132          0.000  0 / 0                        0.010            0.0069 (0.0069)    711       9                    144
+  11-16-12-3 eos       2/2            81           0.000  0 / 0                        0.004            0.0000 (0.0000)    1         0                    0
+  33-5-32-8 (cap 8)    9/2            1287         0.000  0 / 0                        0.006            0.0049 (0.0089)    19        0                    0
+(loose: the share of ranks that get the membership check only -- the undecided ones and those whose next value ABOVE is within 2 tol, which the device may have
+swapped with an undecided neighbour; the 2 % cap is on the undecided share.)  The "dict" cases are word lists (R.beam_words: R.words over a small alphabet behind
+the two twin characters) through dict_oracle.load_dictionary and tail_ref.flat_trie, ~20000 nodes; the test requires that the hypotheses of an image sit at nodes
+with different child sets after at least a quarter of the selections, so that a node taken from the wrong slot, a wrong trie_base or a wrong child offset shows in
+the admissibility of later picks.  The XCD-cap case takes its 33 images as rows of a 256-image batch of the same generator (R.BEAM_CAP_ROWS).
 Before `#pragma clang fp contract(off)` in the forward cell bodies the cluster kernel's DEC instantiation differed from the teacher-forced kernels (f c + i g
 contracted differently): 18372 of 772608 bf16 trajectory values at 45-5-12 (one-ulp flips, compounded along the row), 2 of 251904 at 33-65-6; now 0.
 Before `#pragma clang fp contract(off)` in the two cell_bwd bodies the BPTT kernels differed: at 45-5-5, 4559 of 92160 d z values per step by one fp32 ulp and
@@ -135,16 +165,17 @@ def d64(t):
 class Exchange:
     """exchange, xtab and err buffers sized as model.hip sizes them for B rows; kind "f": dec_cluster_xbuf_bytes, "b": dec_cluster_bwd_xbuf_bytes"""
 
-    def __init__(self, B, kind):
+    def __init__(self, B, kind, tab_rows=None):
         n = kp().kp_dec_cluster_xbuf_bytes(B) if kind == "f" else kp().kp_dec_cluster_bwd_xbuf_bytes(B)
         self.xbuf = Buf(((n + 7) // 8,), torch.int64, fill=0)
-        self.xtab = Buf(((kp().kp_dec_cluster_xtab_bytes(B) + 7) // 8,), torch.int64, fill=0)
+        self.xtab = Buf(((kp().kp_dec_cluster_xtab_bytes(tab_rows or B) + 7) // 8,), torch.int64, fill=0)      # (beam search: the model's max(B, 32 group_cap) rows)
         self.err = Buf((ERR_INTS,), torch.int32, fill=0)
         self.epoch = 0
 
-    def fill(self, a):
-        self.epoch += 1
-        a.epoch = self.epoch
+    def fill(self, a, epochs=1):
+        """the next epoch; a beam launch takes `epochs` consecutive ones (one per pass)"""
+        a.epoch = self.epoch + 1
+        self.epoch += epochs
         a.xbuf, a.xbuf_bytes, a.xtab, a.xtab_bytes = self.xbuf.full.data_ptr(), self.xbuf.n * 8, self.xtab.full.data_ptr(), self.xtab.n * 8
         a.err, a.err_ints = self.err.full.data_ptr(), self.err.n
 
@@ -156,9 +187,9 @@ class Exchange:
 
 
 class Common:
-    def __init__(self, B, T, L, seed):
+    def __init__(self, B, T, L, seed, o=None):
         self.B, self.T, self.L = B, T, L
-        self.o = R.operands(B, T, seed)
+        self.o = R.operands(B, T, seed) if o is None else o            # o: explicit operands (R.take_rows: the context and initial state of chosen rows)
         self.w = R.weights_of(self.o)
         self.maxctx = self.o["ctx"].abs().max().item()
         self.ctxb = Buf(self.o["ctx"], torch.bfloat16)
@@ -179,8 +210,9 @@ class Common:
 class Fwd(Common):
     """table: zx1 is the per-token table [V][4H] and the tokens are a strided window (token of (t, b) at 1 + 2 t + (2 L + 3) b) with JUNK around it"""
 
-    def __init__(self, B, T, L, table, seed, zx=None, drop=None):
-        super().__init__(B, T, L, seed)
+    def __init__(self, B, T, L, table, seed, zx=None, drop=None, o=None, lean=False):
+        super().__init__(B, T, L, seed, o)
+        self.lean = lean                                               # no saved gates (one row each): the beam tests' replays and the beam problem itself
         if drop:
             self.set_drop(drop)
         self.table = table
@@ -206,7 +238,7 @@ class Fwd(Common):
             self.cs[l].t[0] = o["c0"][l].cuda()
             self.hsb[l].t[0] = o["h0"][l].to(torch.bfloat16).cuda()
         self.out_b.t[0] = o["feed0"].to(torch.bfloat16).cuda()
-        self.gates = [Buf((L, B, 4 * H), fill=SENT) for _ in range(2)]
+        self.gates = [Buf((1, 1, 4 * H) if self.lean else (L, B, 4 * H), fill=SENT) for _ in range(2)]
         self.a_all, self.cat_b = Buf((L, B, T), fill=SENT), Buf((L, B, 2 * H), torch.bfloat16, fill=SENT_B)
         self.hm_b = Buf((L, B, H), torch.bfloat16, fill=SENT_B) if self.mask_h is not None else None
 
@@ -235,10 +267,15 @@ class Fwd(Common):
             a.drop_h, a.drop_out, a.hm_b = self.specs[0], self.specs[1], p(self.hm_b)
         return a
 
-    def check(self, what, gates=True):
-        """device-fed check of every step -> dict of the largest error / tolerance per quantity"""
+    def check(self, what, gates=True, rows=None):
+        """device-fed check of every step -> dict of the largest error / tolerance per quantity.  rows: only these batch rows (the outputs are [step][row][..])"""
         B, L, w, o = self.B, self.L, self.w, self.o
         d = self.outputs()
+        if rows is not None:
+            rows = torch.as_tensor(rows).long()
+            B, o, w = len(rows), R.take_rows(o, rows), R.weights_of(R.take_rows(o, rows))
+            d = {k: v if k.startswith("gates") and self.lean else v[:, rows] for k, v in d.items()}
+        tok_ = self.tok if rows is None or self.tok is None else self.tok[:, rows]
         worst = dict(c=0.0, gates=0.0, a=0.0, out=0.0)
         zs = []
         assert same_bits(d["cs0"][0], o["c0"][0]) and same_bits(d["cs1"][0], o["c0"][1]), f"{what}: slot 0 of cs changed"
@@ -246,7 +283,7 @@ class Fwd(Common):
         assert same_bits(d["out_b"][0], o["feed0"].to(torch.bfloat16)) and is_sentinel(d["out"][0]), f"{what}: slot 0 of out / out_b changed"
         for t in range(L):
             h1b, h2b, cat_b = d64(d["hsb0"][t + 1]), d64(d["hsb1"][t + 1]), d64(d["cat_b"][t])
-            s = R.step_fed(w, R.zx_at(self.zx1, self.tok, t), d64(d["out_b"][t]), d64(d["hsb0"][t]), d64(d["hsb1"][t]), d["cs0"][t].double(),
+            s = R.step_fed(w, R.zx_at(self.zx1, tok_, t), d64(d["out_b"][t]), d64(d["hsb0"][t]), d64(d["hsb1"][t]), d["cs0"][t].double(),
                            d["cs1"][t].double(), h1b, h2b, cat_b, x2b=d64(d["hm_b"][t]) if self.hm_b else None)
             zs.append(s["z"].reshape(-1))
             wt = f"{what} step {t}"
@@ -805,3 +842,362 @@ def test_wrappers_refuse_what_the_model_would_not_launch(cuda, capfd):
         assert "[aocr] dec_" not in capfd.readouterr().err
     torch.cuda.synchronize()
     assert all(is_sentinel(v) for v in b.outputs().values())
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# beam search (DEC + BEAM, HIST): dec_chain_beam_forward
+# ------------------------------------------------------------------------------------------------------------------------------
+class DecBeam(C.Structure):
+    _fields_ = [("f", DecFwd), ("beam", i32), ("hist_tok", vp), ("hist_par", vp), ("beam_scores", vp)]
+
+
+def beam_cases():
+    return R.BEAM_CASES + [R.beam_cap_case(kp().kp_dec_chain_beam_group_cap())]
+
+
+BEAM_IDS = [f"{c[0]}-{c[1]}-{c[2]}-{c[3]}{'-' + c[5] if c[5] else ''}" for c in R.BEAM_CASES] + ["xcd-cap"]
+I16 = lambda t: t.contiguous().view(torch.int16)
+
+
+class Beam:
+    """The BEAM problem on the operands of Fwd(B, T, L, table=True, seed): GO tokens in column 1 of a [B][L + 3] window with JUNK around it, R.beam_projector
+    (the planted twin classes; "eos": a boosted EOS bias), optional flat trie; pbuf / xtab sized for max(B, 32 group_cap) rows as in model.hip."""
+
+    def __init__(self, B, T, L, k, seed, flags):
+        self.B, self.T, self.L, self.k, self.seed = B, T, L, k, seed
+        self.p = Fwd(B, T, L, table=True, seed=seed, lean=True, o=R.beam_operands(B, T, seed, flags))
+        self.wo, self.bo = R.beam_projector(seed, flags)
+        self.wod, self.bod = Buf(self.wo), Buf(self.bo)
+        self.stride = L + 3
+        host = torch.full((B * self.stride + 8,), int(JUNK), dtype=torch.int32)
+        host[1 + self.stride * torch.arange(B)] = R.GO
+        self.tok0 = Buf(host, torch.int32)
+        self.cap = kp().kp_dec_chain_beam_group_cap()
+        assert self.cap == per_pass(), f"dec_chain_beam_group_cap() = {self.cap}, from the compute units: {per_pass()}"
+        rows = max(B, 32 * self.cap)
+        self.pbuf = Buf(((kp().kp_dec_cluster_pbuf_bytes(rows) + 3) // 4,), fill=0.0)
+        self.ex = Exchange(B, "f", tab_rows=rows)
+        self.trie = R.beam_trie(seed, flags, L)
+        self.tried = [Buf(torch.from_numpy(t.astype("int64") if i == 0 else t), torch.int64 if i == 0 else torch.int32) for i, t in enumerate(self.trie)] if self.trie else None
+        ipg = 2 * (16 // k)
+        self.groups = (B + ipg - 1) // ipg
+        self.per = min(self.cap, self.groups, L * B // 128)                # dec_chain.hip: beam_pass_groups
+        self.passes = (self.groups + self.per - 1) // self.per
+        assert kp().kp_dec_chain_beam_supported(B, L, k, V) == 1 and kp().kp_dec_chain_beam_passes(B, L, k) == self.passes
+
+    def args(self, hist):
+        p, B, L, k = self.p, self.B, self.L, self.k
+        p.fresh()
+        self.hist_tok, self.hist_par = Buf((L, B, k), torch.int32, fill=0x5B), Buf((L, B, k), torch.int32, fill=0x5B)
+        self.beam_scores, self.sc_hist = Buf((B, k), fill=SENT), Buf((L, B, k), fill=SENT)
+        self.a_hist = Buf((L, B * k, self.T), fill=SENT)
+        self.labels, self.scores = Buf((B * self.stride + 8,), torch.int32, fill=0x5B), Buf((B,), fill=SENT)
+        a = DecBeam()
+        a.f = p.args(gates=False)
+        f = a.f
+        f.zx_tok, f.greedy, f.V = None, 0, V
+        f.tok0, f.tok0_stride, f.wo, f.bo = self.tok0.full.data_ptr() + 4, self.stride, self.wod.full.data_ptr(), self.bod.full.data_ptr()
+        f.pbuf, f.pbuf_bytes, f.labels, f.scores = self.pbuf.full.data_ptr(), self.pbuf.n * 4, self.labels.full.data_ptr() + 4, self.scores.full.data_ptr()
+        if hist:
+            f.sc_hist, f.a_all = self.sc_hist.full.data_ptr(), self.a_hist.full.data_ptr()
+        if self.tried:
+            f.trie_mask, f.trie_base, f.trie_child = (b.full.data_ptr() for b in self.tried)
+        a.beam, a.hist_tok, a.hist_par, a.beam_scores = k, self.hist_tok.full.data_ptr(), self.hist_par.full.data_ptr(), self.beam_scores.full.data_ptr()
+        self.ex.fill(f, epochs=self.passes)
+        return a
+
+    def outputs_untouched(self, what, d, hist):
+        """what the beam launcher must not write: labels / scores (the model's back-trace fills them from the history; dec_chain_beam_forward itself leaves
+        them alone), the fp32 out, the gates, the cell-state slots, everything of hsb / out_b / cat_b outside the initial rows and the four rolling slots"""
+        B, L, o, Rs = self.B, self.L, self.p.o, 32 * self.per
+        assert bool((self.labels.cpu() == 0x5B).all()) and is_sentinel(self.scores.cpu()), f"{what}: labels / scores written by the beam launcher"
+        assert all(is_sentinel(d[n]) for n in ("out", "gates0", "gates1")) and (hist or is_sentinel(d["a_all"])), f"{what}: out, gates or a_all written"
+        assert is_sentinel(self.p.a_all.cpu()), f"{what}: the [L][B][T] attention buffer of the other kernels written"
+        for l in range(2):
+            assert same_bits(d[f"cs{l}"][0], o["c0"][l]) and is_sentinel(d[f"cs{l}"][1:]), f"{what}: cs[{l}] written"
+        for n, init in (("hsb0", o["h0"][0]), ("hsb1", o["h0"][1]), ("out_b", o["feed0"])):
+            flat = d[n].view(-1, H)
+            assert same_bits(flat[:B], init.to(torch.bfloat16)), f"{what}: the initial rows of {n} changed"
+            assert is_sentinel(flat[B + 4 * Rs:]), f"{what}: {n} written behind the four rolling step slots"
+        assert is_sentinel(d["cat_b"].view(-1, 2 * H)[4 * Rs:]), f"{what}: cat_b written behind the four rolling step slots"
+
+    def run(self, capfd, monkeypatch, env, hist):
+        p, B, L, k = self.p, self.B, self.L, self.k
+        setenv(monkeypatch, env)
+        a = self.args(hist)
+        capfd.readouterr()
+        rc = launch("kp_dec_chain_beam_forward", a)
+        assert rc == 0, f"wrapper / hipGetLastError() = {rc}"
+        torch.cuda.synchronize()
+        line, cfg = config_of(capfd, "dec_chain_beam_forward", others=("dec_cluster_forward", "dec_chain_forward"))
+        inst = "dec" + (",res" if self.T <= 64 and "AOCR_CH_NO_RES" not in env else "") + ",beam" + (",hist" if hist else "")
+        assert f": dec_ch_fwd_kernel[{inst}] {B} {self.T} {L} " in line, line
+        assert cfg == dict(groups=self.groups, passes=self.passes, remote=1 if "AOCR_CL_REMOTE" in env else 0), (line, self.groups, self.passes)
+        for n in env:
+            monkeypatch.delenv(n)
+        self.ex.ok(line)
+        bufs = dict(hist_tok=self.hist_tok, hist_par=self.hist_par, beam_scores=self.beam_scores, sc_hist=self.sc_hist, a_hist=self.a_hist, labels=self.labels,
+                    scores=self.scores, pbuf=self.pbuf, tok0=self.tok0, **p.bufs())
+        for n, b in bufs.items():
+            b.check_tail(f"{line} {n}")
+        d = p.outputs()
+        g = dict(line=line, hist_tok=self.hist_tok.cpu().clone().long(), hist_par=self.hist_par.cpu().clone().long(), beam_scores=self.beam_scores.cpu().clone(),
+                 sc_hist=self.sc_hist.cpu().clone(), a_hist=self.a_hist.cpu().clone(), hsb0=d["hsb0"], hsb1=d["hsb1"], out_b=d["out_b"], cat_b=d["cat_b"])
+        d["a_all"] = g["a_hist"]
+        self.outputs_untouched(line, d, hist)
+        if not hist:
+            assert is_sentinel(g["sc_hist"]) and is_sentinel(g["a_hist"]), f"{line}: search history written without sc_hist"
+        return g
+
+    # ---- stage 1: the hypothesis tree of the device's own history, replayed by the teacher-forced kernel
+    def prefixes(self, g):
+        """pre[t][b][j]: the token prefix (GO, x_1 .. x_t) of the hypothesis in slot j of image b that ENTERS step t (kin = 1 at step 0)"""
+        L, B, k = self.L, self.B, self.k
+        ht, hp = g["hist_tok"], g["hist_par"]
+        assert bool(((ht >= 1) & (ht <= V)).all()), "tokens outside 1..V"
+        assert bool((hp[0] == 0).all()) and bool(((hp >= 0) & (hp < k)).all()), "parents outside the beam (step 0: one hypothesis per image)"
+        pre = [[[(R.GO,)] for _ in range(B)]]
+        for t in range(1, L):
+            pre.append([[pre[t - 1][b][int(hp[t - 1, b, j])] + (int(ht[t - 1, b, j]),) for j in range(k)] for b in range(B)])
+        return pre
+
+    def replay(self, g, pre, images, check_images, capfd, monkeypatch, what, acc):
+        """every distinct maximal prefix of `images` as one row of the teacher-forced kernel (context and initial state of the row's image); rp.check on the
+        rows of check_images.  acc[name][t][b kin + j] <- the replay's values of the hypothesis that entered step t"""
+        L, k, T = self.L, self.k, self.T
+        allp = {(b, q) for t in range(L) for b in images for q in pre[t][b]}
+        inner = {(b, q[:-1]) for b, q in allp if len(q) > 1}
+        rows = sorted(allp - inner)
+        at = {}
+        for r, (b, q) in enumerate(rows):
+            for n in range(1, len(q) + 1):
+                at[(b, q[:n])] = r
+        tok = torch.full((L, len(rows)), R.PAD, dtype=torch.int32)
+        for r, (b, q) in enumerate(rows):
+            tok[:len(q), r] = torch.tensor(q, dtype=torch.int32)
+        rp = Fwd(len(rows), T, L, table=True, seed=self.seed, zx=(self.p.zx1, tok), o=R.take_rows(self.p.o, [b for b, _ in rows]), lean=True)
+        run_fwd(rp, Exchange(len(rows), "f"), capfd, monkeypatch, {}, gates=False)
+        crow = [r for r, (b, _) in enumerate(rows) if b in check_images]
+        if crow:
+            rp.check(f"{what} replay", gates=False, rows=None if len(crow) == len(rows) else crow)
+        r = rp.outputs()
+        for t in range(L):
+            kin = 1 if t == 0 else k
+            for b in images:
+                for j in range(kin):
+                    row = at[(b, pre[t][b][j])]
+                    acc["out"][t][b * kin + j] = r["out"][t + 1, row]
+                    acc["a"][t][b * kin + j] = r["a_all"][t, row]
+                    if t >= L - 4:
+                        for n in ("hsb0", "hsb1", "out_b"):
+                            acc[n][t][b * kin + j] = r[n][t + 1, row]
+                        acc["cat_h"][t][b * kin + j] = r["cat_b"][t, row, H:]
+        return len(rows)
+
+    def verify(self, g, capfd, monkeypatch, what, chunks=None, check_images=None):
+        B, T, L, k = self.B, self.T, self.L, self.k
+        pre = self.prefixes(g)
+        kin_of = lambda t: 1 if t == 0 else k
+        acc = dict(out=[torch.zeros(B * kin_of(t), H) for t in range(L)], a=[torch.zeros(B * kin_of(t), T) for t in range(L)])
+        for n in ("hsb0", "hsb1", "out_b", "cat_h"):
+            acc[n] = [torch.zeros(B * kin_of(t), H, dtype=torch.bfloat16) for t in range(L)]
+        nrows = 0
+        for images in (chunks or [list(range(B))]):
+            nrows += self.replay(g, pre, images, set(range(B)) if check_images is None else check_images, capfd, monkeypatch, what, acc)
+        fig = dict(rows=nrows)
+        # HIST attention rows: [L][B k][T], row image * kin + hypothesis, kin = 1 at step 0; everything else keeps the sentinel
+        worst = diff = total = 0
+        for t in range(L):
+            kin = kin_of(t)
+            at = torch.tensor([b * kin + j for b in range(B) for j in range(kin)])                  # the history's row of (image, hypothesis)
+            rest = torch.ones(B * k, dtype=torch.bool)
+            rest[at] = False
+            dev = g["a_hist"][t][at]
+            worst = max(worst, ratio(dev, acc["a"][t].double(), TOL_A))
+            diff += int((dev.view(torch.int32) != acc["a"][t].view(torch.int32)).sum()); total += dev.numel()
+            assert is_sentinel(g["a_hist"][t][rest]), f"{what}: step {t}: attention rows other than image * kin + hypothesis written"
+        assert worst <= 1.0, f"{what}: a_all error / tolerance = {worst:.3f}"
+        assert diff == 0, f"{what}: {diff} of {total} a_all values differ in bits from the teacher-forced replay"
+        fig.update(a=worst, a_share=diff / total)
+        # the rolling slots of the last min(4, L) steps, groups of the last pass
+        Rs, ipc, g0 = 32 * self.per, 16 // k, (self.passes - 1) * self.per
+        diff = total = 0
+        for t in range(max(0, L - 4), L):
+            kin = kin_of(t)
+            for gl in range(self.groups - g0):
+                for c in range(2):
+                    for lr in range(ipc * k):
+                        b, j = ((g0 + gl) * 2 + c) * ipc + lr // k, lr % k
+                        if b >= B:
+                            continue
+                        src = b * kin + (j if kin > 1 else 0)
+                        row = gl * 32 + 16 * c + lr
+                        for n in ("hsb0", "hsb1", "out_b"):
+                            x = g[n].view(-1, H)[B + ((t + 1) & 3) * Rs + row]
+                            diff += int((I16(x) != I16(acc[n][t][src])).sum()); total += H
+                        x = g["cat_b"].view(-1, 2 * H)[(t & 3) * Rs + row, H:]
+                        diff += int((I16(x) != I16(acc["cat_h"][t][src])).sum()); total += H
+        assert diff == 0, f"{what}: {diff} of {total} bf16 values of the surviving step slots differ from the teacher-forced replay"
+        fig.update(slot_share=diff / total)
+        fig.update(self.selection(g, acc, what))
+        return fig
+
+    # ---- stage 2: every selection against tail_ref.beam_totals of the replay's out, the device's own previous scores, tokens and trie nodes
+    def selection(self, g, acc, what):
+        B, L, k, trie = self.B, self.L, self.k, self.trie
+        ht, hp, sc = g["hist_tok"], g["hist_par"], g["sc_hist"]
+        bits32 = lambda x: int(x.view(torch.int32))
+        node = [[0] for _ in range(B)]
+        totals, frees = [], []
+        n = dict(picks=0, undecided=0, loose=0, ties=0, fallback=0, split=0, worst=0.0)
+        for t in range(L):
+            kin, first = (1 if t == 0 else k), t == 0
+            lp, mag = R.logprobs(acc["out"][t], self.wo, self.bo)
+            tolr = TOL_CELL + bound(mag.amax(dim=1), 512)                       # [B kin]: per parent row
+            prev, psc = (None, None) if first else (ht[t - 1].reshape(-1), sc[t - 1].double())
+            loc = None if trie is None else [x for b in range(B) for x in node[b]]
+            tot = TR.beam_totals(lp, prev, psc, B, kin, V, trie, loc)
+            totals.append(tot)
+            frees.append(TR.beam_totals(lp, prev, psc, B, kin, V) if trie is not None else tot)
+            tolc = tolr.view(B, kin, 1).expand(B, kin, V).reshape(B, kin * V)
+            for b in range(B):
+                wt = f"{what}: step {t} image {b}"
+                c = R.pick_classes(tot[b], tolc[b], k)
+                idx = [int(hp[t, b, i]) * V + int(ht[t, b, i]) - 1 for i in range(k)]
+                assert all(int(hp[t, b, i]) < kin for i in range(k)), f"{wt}: a parent outside the {kin} hypotheses that entered the step"
+                for i in range(k):
+                    v, tl = tot[b, idx[i]].item(), tolc[b, idx[i]].item()
+                    assert v >= c["kth"] - 2 * tl, f"{wt}: pick {i} (token {int(ht[t, b, i])} of parent {int(hp[t, b, i])}) has the reference total {v:.5f}, the k-th best is {c['kth']:.5f}"
+                    e = abs(sc[t, b, i].item() - v) / tl
+                    assert e <= 1.0, f"{wt}: pick {i}: score error / tolerance = {e:.3f}"
+                    n["worst"] = max(n["worst"], e)
+                    if i > 0:
+                        assert sc[t, b, i].item() <= sc[t, b, i - 1].item(), f"{wt}: the scores increase from slot {i - 1} to slot {i}"
+                    if i in c["fallback"]:
+                        assert idx[i] == idx[0] and bits32(sc[t, b, i]) == bits32(sc[t, b, 0]), f"{wt}: pick {i} does not repeat pick 0 (fewer than {k} admissible)"
+                        continue
+                    assert idx[i] not in idx[:i], f"{wt}: candidate {idx[i]} chosen twice"
+                    if i > 0 and tot[b, idx[i]] == tot[b, idx[i - 1]]:
+                        assert idx[i - 1] < idx[i], f"{wt}: exactly tied candidates {idx[i - 1]}, {idx[i]} not in index order"
+                    if not c["loose"][i]:
+                        assert idx[i] == c["ref"][i], f"{wt}: pick {i} is candidate {idx[i]}, the reference's (decided) is {c['ref'][i]}"
+                    if not first and int(ht[t, b, i]) == R.PAD and int(ht[t - 1, b, int(hp[t, b, i])]) in (R.PAD, R.EOS):
+                        assert bits32(sc[t, b, i]) == bits32(sc[t - 1, b, int(hp[t, b, i])]), f"{wt}: pick {i}: PAD after a finished parent changes the score bits"
+                n["picks"] += k; n["undecided"] += sum(c["undecided"]); n["loose"] += sum(c["loose"]); n["fallback"] += int(bool(c["fallback"]))
+                n["ties"] += sum(1 for i in c["ties"] if idx[i] == c["ref"][i] and idx[i + 1] == c["ref"][i + 1])
+                if trie is not None:
+                    node[b] = [TR.trie_next(trie[0], trie[1], trie[2], node[b][int(hp[t, b, i])], int(ht[t, b, i]), first) for i in range(k)]
+                    n["split"] += int(len({int(trie[0][x]) for x in node[b]}) > 1)
+        share = n["undecided"] / n["picks"]
+        assert share <= 0.02, f"{what}: the case lost its conditions: {share:.4f} of the picks are undecided"
+        ok, txt, cnt = R.beam_conditions(ht, hp, totals, frees, k, trie is not None)
+        assert ok, f"{what}: the case lost its conditions: {txt}"
+        # (the nodes are checked through the admissibility of every later pick: that only bites where the hypotheses of an image sit at nodes with different children)
+        assert trie is None or n["split"] >= L * B // 4, f"{what}: the case lost its conditions: only {n['split']} selections leave an image's hypotheses at nodes with different child sets"
+        assert same_bits(g["beam_scores"], sc[L - 1]), f"{what}: beam_scores is not sc_hist of the last step"
+        return dict(score=n["worst"], undecided=share, loose=n["loose"] / n["picks"], ties=n["ties"], fallback=n["fallback"], masked=cnt["masked"])
+
+    def tail(self, g, what):
+        """kp_beam_backtrace on the device's history against tail_ref.backtrace; tail_ref.recognize_gather of it finite and consistent with sc_hist"""
+        B, L, k = self.B, self.L, self.k
+        lab, scr = Buf((B, L), torch.int32, fill=0x5B), Buf((B,), fill=SENT)
+        rc = getattr(kp(), "kp_beam_backtrace")(C.c_void_p(torch.cuda.current_stream().cuda_stream), self.hist_tok.ptr(), self.hist_par.ptr(), self.beam_scores.ptr(),
+                                                lab.ptr(), scr.ptr(), L, B, k)
+        torch.cuda.synchronize()
+        assert rc == 0, f"kp_beam_backtrace: {rc}"
+        labels, scores = TR.backtrace(g["hist_tok"], g["hist_par"], g["beam_scores"].double())
+        assert torch.equal(lab.cpu().long(), labels) and same_bits(scr.cpu(), scores.float()), f"{what}: beam_backtrace differs from tail_ref.backtrace"
+        cl, at = TR.recognize_gather(labels, g["hist_par"], g["beam_scores"].double(), g["sc_hist"].double(), g["a_hist"])
+        assert bool(torch.isfinite(cl).all()) and bool(torch.isfinite(at).all()), f"{what}: recognize_gather of the history is not finite"
+        for b in range(B):
+            tend = next((t for t in range(L) if int(labels[b, t]) in (R.PAD, R.EOS)), L - 1)
+            idx = TR.winner(g["beam_scores"][b].double())[0]
+            for t in range(L - 1, tend, -1):
+                idx = int(g["hist_par"][t, b, idx])
+            assert abs(cl[b, :tend + 1].sum().item() - g["sc_hist"][tend, b, idx].item()) <= 1e-4, f"{what}: image {b}: per-character scores do not sum to sc_hist on the winner"
+            assert bool(((at[b, :tend + 1].sum(1) - 1).abs() <= 1e-4).all()), f"{what}: image {b}: an attention row of the winner does not sum to 1"
+
+
+def same_history(a, b):
+    return torch.equal(a["hist_tok"], b["hist_tok"]) and torch.equal(a["hist_par"], b["hist_par"]) and same_bits(a["beam_scores"], b["beam_scores"])
+
+
+@pytest.mark.parametrize("i", range(len(BEAM_IDS)), ids=BEAM_IDS)
+def test_beam(i, cuda, capfd, monkeypatch):
+    """Measured on an MI355X (group cap 8), per case: see the module docstring's table"""
+    B, T, L, k, seed, flags = beam_cases()[i]
+    q = Beam(B, T, L, k, seed, flags)
+    g = q.run(capfd, monkeypatch, {}, hist=True)
+    chunks = check_images = None
+    if i == len(BEAM_IDS) - 1:                                         # the XCD-cap case: selection on all images, replay group by group, rp.check on the first and last image of each pass
+        chunks = [list(range(b, min(b + 4, B))) for b in range(0, B, 4)]
+        check_images = {0, 4 * q.per - 1, 4 * q.per, B - 1}
+    fig = q.verify(g, capfd, monkeypatch, BEAM_IDS[i], chunks, check_images)
+    q.tail(g, BEAM_IDS[i])
+    report = [f"[dec-kernels] {g['line'][7:]}: replay rows {fig['rows']}, a_all {fig['a']:.3f} (mismatch share {fig['a_share']:.0f}), slot mismatch share {fig['slot_share']:.0f}, "
+              f"score increment {fig['score']:.3f}, undecided {fig['undecided']:.4f} (membership check only, with their upper neighbours: {fig['loose']:.4f}), ties won {fig['ties']}, fallback selections {fig['fallback']}, steps masked {fig['masked']}"]
+    runs = [("no history", {}), ("AOCR_CL_REMOTE=1", {"AOCR_CL_REMOTE": "1"})] + ([("AOCR_CH_NO_RES=1", {"AOCR_CH_NO_RES": "1"})] if T <= 64 else [])
+    for name, env in runs:                                             # each on the used buffers, the epoch advanced by the pass count
+        h = q.run(capfd, monkeypatch, env, hist=False)
+        assert same_history(g, h), f"{name}: hist_tok / hist_par / beam_scores differ from the first [.., hist] run"
+        report.append(f"[dec-kernels] {h['line'][7:]} ({name}): bit-identical history")
+    h = q.run(capfd, monkeypatch, {}, hist=True)
+    assert same_history(g, h) and same_bits(g["sc_hist"], h["sc_hist"]) and same_bits(g["a_hist"], h["a_hist"]), "a second [.., hist] call on the used buffers differs"
+    print("\n".join(report))
+
+
+def test_beam_switch_and_refusals(cuda, capfd, monkeypatch):
+    """AOCR_NO_DEC_CHAINS_BEAM=1 and every refusal of kp_dec_chain_beam_forward: its code, no trace line, every buffer still all-sentinel"""
+    B, T, L, k, seed, flags = R.BEAM_CASES[2]
+    assert k == 3
+    q = Beam(B, T, L, k, seed, flags)
+    rows = max(B, 32 * q.cap)
+    bad, tok0 = [], q.tok0.cpu().clone()
+
+    def refused(code, env=None, **change):
+        setenv(monkeypatch, env or {})
+        a = q.args(hist=True)
+        for n, v in change.items():
+            setattr(a if n in ("beam", "hist_tok", "hist_par", "beam_scores") else a.f, n, v)
+        capfd.readouterr()
+        rc = launch("kp_dec_chain_beam_forward", a)
+        torch.cuda.synchronize()
+        for n in (env or {}):
+            monkeypatch.delenv(n)
+        assert rc == code, (change, env, rc)
+        assert "[aocr] dec_" not in capfd.readouterr().err, change
+        d = q.p.outputs()
+        ok = all(is_sentinel(d[n].view(-1, H)[B:]) for n in ("hsb0", "hsb1", "out_b")) and all(is_sentinel(d[n]) for n in ("out", "cat_b", "a_all", "gates0", "gates1"))
+        ok = ok and all(bool((b.cpu() == 0x5B).all()) for b in (q.hist_tok, q.hist_par, q.labels)) and all(is_sentinel(b.cpu()) for b in (q.beam_scores, q.sc_hist, q.a_hist, q.scores))
+        ok = ok and all(bool((b.cpu() == 0).all()) for b in (q.pbuf, q.ex.xbuf, q.ex.xtab, q.ex.err)) and torch.equal(q.tok0.cpu(), tok0)
+        ok = ok and all(same_bits(d[f"cs{l}"][0], q.p.o["c0"][l]) and is_sentinel(d[f"cs{l}"][1:]) for l in range(2))
+        ok = ok and all(same_bits(d[n].view(-1, H)[:B], init.to(torch.bfloat16)) for n, init in (("hsb0", q.p.o["h0"][0]), ("hsb1", q.p.o["h0"][1]), ("out_b", q.p.o["feed0"])))
+        if not ok:
+            bad.append((change, env))
+
+    monkeypatch.setenv("AOCR_NO_DEC_CHAINS_BEAM", "1")
+    assert kp().kp_dec_chain_beam_supported(B, L, k, V) == 0
+    monkeypatch.delenv("AOCR_NO_DEC_CHAINS_BEAM")
+    refused(KP_DEC_UNSUPPORTED, env={"AOCR_NO_DEC_CHAINS_BEAM": "1"})
+    refused(KP_DEC_UNSUPPORTED, env={"AOCR_NO_DEC_CHAINS": "1"})
+    assert kp().kp_dec_chain_beam_supported(B, L, 1, V) == 0 and kp().kp_dec_chain_beam_supported(B, L, 9, V) == 0 and kp().kp_dec_chain_beam_supported(B, L, k, 41) == 0
+    assert kp().kp_dec_chain_beam_supported(B, 128 // B, k, V) == 0 and kp().kp_dec_chain_beam_passes(B, 128 // B, k) == 0      # L B < 128: no group fits the four slots
+    refused(KP_DEC_UNSUPPORTED, beam=1)
+    refused(KP_DEC_UNSUPPORTED, beam=9)
+    refused(KP_DEC_UNSUPPORTED, V=41)
+    refused(KP_DEC_UNSUPPORTED, L=128 // B)                            # !dec_chain_beam_supported
+    refused(KP_DEC_UNSUPPORTED, Hd=1024)                               # !dec_cluster_supported
+    refused(KP_DEC_UNSUPPORTED, T=257)
+    refused(KP_DEC_BAD_ARGS, epoch=0)
+    refused(KP_DEC_BAD_ARGS, epoch=(1 << 20) - q.passes)
+    refused(KP_DEC_BAD_ARGS, hist_tok=None)
+    refused(KP_DEC_BAD_ARGS, hist_par=None)
+    refused(KP_DEC_BAD_ARGS, beam_scores=None)
+    refused(KP_DEC_BAD_ARGS, tok0_stride=L - 1)
+    refused(KP_DEC_XBUF_SMALL, xbuf_bytes=q.ex.xbuf.n * 8 - 8)
+    refused(KP_DEC_PBUF_SMALL, pbuf_bytes=kp().kp_dec_cluster_pbuf_bytes(rows) - 4)
+    refused(KP_DEC_PBUF_SMALL, pbuf_bytes=kp().kp_dec_cluster_pbuf_bytes(B))          # sized for B rows as for the greedy kernel: below the launch's group cap
+    refused(KP_DEC_XTAB_SMALL, xtab_bytes=kp().kp_dec_cluster_xtab_bytes(rows) - 8)
+    refused(KP_DEC_XTAB_SMALL, xtab_bytes=kp().kp_dec_cluster_xtab_bytes(B))
+    refused(KP_DEC_ERR_SMALL, err_ints=16 + 256 * 4)
+    assert not bad, f"a refused call wrote a buffer: {bad}"

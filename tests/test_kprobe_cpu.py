@@ -54,7 +54,8 @@ def test_kprobe_symbols_resolve_in_libaocr(tmp_path):
                  "enc_seq_supported", "enc_seq_forward", "enc_seq_backward", "enc_cluster_plan", "enc_cluster_xbuf_bytes", "enc_cluster_pbuf_bytes",
                  "enc_cluster_forward", "enc_cluster_backward",
                  "dec_cluster_supported", "dec_cluster_bwd_supported", "dec_cluster_xbuf_bytes", "dec_cluster_bwd_xbuf_bytes", "dec_cluster_pbuf_bytes",
-                 "dec_cluster_xtab_bytes", "dec_cluster_forward", "dec_cluster_backward"):
+                 "dec_cluster_xtab_bytes", "dec_cluster_forward", "dec_cluster_backward",
+                 "dec_chain_beam_supported", "dec_chain_beam_passes", "dec_chain_beam_group_cap", "dec_chain_beam_forward"):
         assert any(f"{len(name)}{name}E" in s for s in wanted), f"the shim does not call aocr::{name}"
     defined = _symbols(LIB, "--defined-only")
     missing = sorted(wanted - defined)
@@ -76,7 +77,8 @@ def test_kprobe_symbols_resolve_in_libaocr(tmp_path):
                  "kp_enc_seq_supported", "kp_enc_seq_forward", "kp_enc_seq_backward", "kp_enc_cluster_plan", "kp_enc_cluster_xbuf_bytes",
                  "kp_enc_cluster_pbuf_bytes", "kp_enc_cluster_forward", "kp_enc_cluster_backward",
                  "kp_dec_cluster_supported", "kp_dec_cluster_bwd_supported", "kp_dec_cluster_xbuf_bytes", "kp_dec_cluster_bwd_xbuf_bytes",
-                 "kp_dec_cluster_pbuf_bytes", "kp_dec_cluster_xtab_bytes", "kp_dec_cluster_forward", "kp_dec_cluster_backward"):
+                 "kp_dec_cluster_pbuf_bytes", "kp_dec_cluster_xtab_bytes", "kp_dec_cluster_forward", "kp_dec_cluster_backward",
+                 "kp_dec_chain_beam_supported", "kp_dec_chain_beam_passes", "kp_dec_chain_beam_group_cap", "kp_dec_chain_beam_forward"):
         assert name in exported
     unexported = sorted(set(SIGS) - exported)
     assert not unexported, f"in kernel_harness.SIGS, not exported by the compiled shim: {unexported}"
