@@ -10,6 +10,12 @@
 //   interleaved (SKIP):                     block 2 mi + wm  -- both wave-rows have a part of every pair of blocks, so the first map row's
 //                                           blocks (dead in kernel row dy = -1) and the last one's (dy = +1) are shared evenly
 // dyi = dy + 1 is the halo row offset of a tap: forward kh, data gradient 2 - kh.
+//
+// The (2,1)-pooled layers (pmode == 2: the launch's rows are ordered in window pairs, row 2 j of the map beside row 2 j + 1) take SKIP too, with the
+// ROW-SPLIT order inside the tile: the tile is the same 256 / W whole map rows, y0 its first, and a lane addresses its pixels in plain order exactly as
+// above, so the blocks, their rows and the dead counts are those of the interleaved ownership.  What changes is where a pool window's two values sit:
+// not in neighbouring accumulator entries of one lane but in the same entry of acc[mi] (map row 2 j) and acc[mi + W / 64] (row 2 j + 1: the same x
+// range, so the same wave-row and lane), which needs W >= 64 -- at W = 32 the partner block 2 mi + wm + 1 belongs to the other wave-row.
 #pragma once
 
 namespace aocr {
@@ -28,6 +34,15 @@ constexpr int halo4_ndead(int wm, int dyi, int W, int H, int y0) {
   for (int mi = 0; mi < 4; ++mi) n += halo4_dead(halo4_block(true, wm, mi), dyi, W, H, y0) ? 1 : 0;
   return n;
 }
+
+// ---- the row-split pooled order (interleaved ownership, W = 64 or 128)
+constexpr bool halo4_pool_width(int W) { return W == 64 || W == 128; }
+// acc[mi + halo4_pool_partner(W)] is the block one map row below acc[mi]'s: W / 32 blocks further on, two blocks per mi
+constexpr int halo4_pool_partner(int W) { return W / 64; }
+// acc[mi] is the upper row of its pool window (the tile's rows are whole windows: 256 / W is even and y0 with it); the same for both wave-rows
+constexpr bool halo4_pool_top(int mi, int W) { return ((2 * mi * 32 / W) & 1) == 0; }
+// first of the 32 pooled rows (of the tile's 128: window row * W + x) that the pair (acc[mi], acc[mi + partner]) of wave-row wm leaves
+constexpr int halo4_pool_row(int wm, int mi, int W) { return (halo4_block(true, wm, mi) * 32 / W >> 1) * W + halo4_block(true, wm, mi) * 32 % W; }
 
 // ---- a half-step with the live accumulators mi = lo .. hi-1: its MFMAs are j = 0 .. 4 (hi - lo) - 1 (mi = lo + j / 4, ni = j % 4).
 // Between them go, in the order of the full half-step: per mi the A read of mi (only rlo <= mi < rhi: a dead block's fragment is not

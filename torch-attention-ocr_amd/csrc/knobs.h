@@ -38,6 +38,7 @@ KNOB(AOCR_NO_HALO,               ON,   0,    "no halo-resident 3 x 3 kernel (the
 KNOB(AOCR_HALO8,                 SET,  0,    "the 8-wave gemm_halo_bf16_kernel instead of the 4-wave gemm_halo4_bf16_kernel")
 KNOB(AOCR_HALO4_STAGED,          INT,  7,    "bits: output tiles of the 256 x 256 kernels through LDS -- 1 fp32 data gradient, 2 fp32 conv forward, 4 pooled")
 KNOB(AOCR_NO_HALO4_SKIP,         ON,   0,    "gemm_halo4_bf16_kernel with contiguous blocks per wave-row and no skipped padding-row MFMAs (its first form)")
+KNOB(AOCR_NO_HALO4_POOL_SKIP,    ON,   0,    "the first form for the (2,1)-pooled launches of gemm_halo4_bf16_kernel only (conv4 / conv6 forward)")
 KNOB(AOCR_NO_NARROW_WIDE,        SET,  0,    "conv7 forward on 128 x 128 tiles instead of 256 x 128 tiles of the narrow LDS-DMA kernel")
 KNOB(AOCR_NO_NARROW_STAGED,      ON,   0,    "quad epilogue of the narrow LDS-DMA kernel instead of the staged tile")
 KNOB(AOCR_NO_DMA128,             ON,   0,    "128 x 128 tiles on the register-staged kernel instead of gemm_dma128_kernel")

@@ -1184,8 +1184,11 @@ __device__ __forceinline__ void tile256_store_f32(float* dst, int64_t ldc, const
     }
   }
 }
-// the (2,1)-pooled tile: 128 pooled rows of 256 bf16 + 256 arg-max bytes
-template <int NI, int NTH>
+// the (2,1)-pooled tile: 128 pooled rows of 256 bf16 + 256 arg-max bytes.  PW == 0: the tile's rows are in window-pair order, a window's two values are
+// neighbouring accumulator entries.  PW == 64 / 128 (gemm_halo4_bf16_kernel's SKIP form at that map width, halo4_skip.h's row-split order): acc[mi] of
+// wave-row wm is block 2 mi + wm of the tile in PLAIN order, a window is the same entry of acc[mi] (upper row) and acc[mi + PW / 64]; the same values
+// through the same expressions land at the same place of the same LDS image, so both forms store the same bits
+template <int NI, int NTH, int PW = 0>
 __device__ __forceinline__ void tile256_store_pooled(bf16_t* yb, uint8_t* idxp, int Cout, const float* bias, bool relu, const f32x16 (&acc)[4][NI], unsigned char* lds,
                                                      int m_blk, int n_blk, int wm, int wn, int r, int h, int tid) {
   constexpr int PB = 528, PI = 272, IOFF = 128 * PB;      // pooled rows: 256 bf16 + 16 bytes; 256 arg-max bytes + 16
@@ -1193,6 +1196,26 @@ __device__ __forceinline__ void tile256_store_pooled(bf16_t* yb, uint8_t* idxp, 
 #pragma unroll
   for (int ni = 0; ni < NI; ++ni) bb[ni] = bias ? bias[n_blk + wn * 32 * NI + ni * 32 + r] : 0.f;
   __syncthreads();
+  if constexpr (PW != 0) {
+    aocr_static_for<4>([&](auto mic) {                    // compile-time mi: the partner's index is one too
+      constexpr int mi = decltype(mic)::value;
+      if constexpr (halo4_pool_top(mi, PW)) {
+        const int prow0 = halo4_pool_row(wm, mi, PW);
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              float a_ = acc[mi][ni][4 * q + i] + bb[ni], b_ = acc[mi + halo4_pool_partner(PW)][ni][4 * q + i] + bb[ni];
+              if (relu) { a_ = fmaxf(a_, 0.f); b_ = fmaxf(b_, 0.f); }
+              const int prow = prow0 + 8 * q + 4 * h + i, col = wn * 32 * NI + ni * 32 + r;
+              *reinterpret_cast<bf16_t*>(lds + prow * PB + col * 2) = (bf16_t)((b_ > a_) ? b_ : a_);
+              *reinterpret_cast<uint8_t*>(lds + IOFF + prow * PI + col) = (uint8_t)(b_ > a_);
+            }
+      }
+    });
+  } else {
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
@@ -1210,6 +1233,7 @@ __device__ __forceinline__ void tile256_store_pooled(bf16_t* yb, uint8_t* idxp, 
           *reinterpret_cast<uint8_t*>(lds + IOFF + prow * PI + col) = (uint8_t)(b_ > a_);
         }
       }
+  }
   __syncthreads();
   const int64_t prow0 = m_blk >> 1;
 #pragma unroll 4
@@ -1280,16 +1304,25 @@ __device__ __forceinline__ void tile256_store_bf16(bf16_t* yb, int Cout, const f
     }
   }
 }
+// "a full tile of this conv epilogue leaves as the staged pooled tile": shared by tile256_store_staged and the launcher's choice of the pooled SKIP form
+// (ops_gemm.hip's halo4_pool_skip_eligible), whose pixel order no other epilogue understands
+template <class EP>
+__host__ __device__ __forceinline__ bool tile256_pooled_staged(const EP& ep, int opt) { return ep.pmode == 2 && ep.yb && ep.idx && !ep.y && !ep.bn_save && (opt & 4); }
 // full 256 x 256 tiles only (the callers' grids may end in a ragged tile: that one takes the quad epilogue)
 template <int NI, int NTH, bool ILV = false, class EP>
-__device__ __forceinline__ bool tile256_store_staged(const EP& ep, const f32x16 (&acc)[4][NI], unsigned char* lds, int m_blk, int n_blk, int wm, int wn, int r, int h, int tid, int opt) {
+__device__ __forceinline__ bool tile256_store_staged(const EP& ep, const f32x16 (&acc)[4][NI], unsigned char* lds, int m_blk, int n_blk, int wm, int wn, int r, int h, int tid, int opt, int pool_w = 0) {
   if constexpr (std::is_same<EP, EpConv>::value) {
     if (m_blk + 256 > ep.rows || n_blk + 256 > ep.Cout) return false;
     if (ep.pmode == 0 && ep.y16 && ep.bn_part && !ep.yb && !ep.bn_save && (opt & 2)) {     // pre-BatchNorm output as bf16 + its statistics (training)
       tile256_store_bf16<NI, NTH, ILV>(ep.y16, ep.Cout, ep.bias, ep.relu != 0, nullptr, nullptr, nullptr, acc, lds, m_blk, n_blk, wm, wn, r, h, tid, ep.bn_part); return true; }
     if (ep.pmode == 0 && ep.yb && !ep.y && (opt & 2)) { tile256_store_bf16<NI, NTH, ILV>(ep.yb, ep.Cout, ep.bias, ep.relu != 0, ep.bn_save, ep.bn_w, ep.bn_b, acc, lds, m_blk, n_blk, wm, wn, r, h, tid); return true; }
     if (ep.bn_save) return false;
-    if (!ILV && ep.pmode == 2 && ep.yb && ep.idx && !ep.y && (opt & 4)) { tile256_store_pooled<NI, NTH>(ep.yb, ep.idx, ep.Cout, ep.bias, ep.relu != 0, acc, lds, m_blk, n_blk, wm, wn, r, h, tid); return true; }
+    if (tile256_pooled_staged(ep, opt)) {
+      if constexpr (!ILV) tile256_store_pooled<NI, NTH>(ep.yb, ep.idx, ep.Cout, ep.bias, ep.relu != 0, acc, lds, m_blk, n_blk, wm, wn, r, h, tid);
+      else if (pool_w == 64) tile256_store_pooled<NI, NTH, 64>(ep.yb, ep.idx, ep.Cout, ep.bias, ep.relu != 0, acc, lds, m_blk, n_blk, wm, wn, r, h, tid);   // ILV: the row-split order at map width pool_w
+      else tile256_store_pooled<NI, NTH, 128>(ep.yb, ep.idx, ep.Cout, ep.bias, ep.relu != 0, acc, lds, m_blk, n_blk, wm, wn, r, h, tid);
+      return true;
+    }
     if (ep.pmode == 0 && ep.y && !ep.yb && (opt & 2)) { tile256_store_f32<NI, NTH, ILV>(ep.y, ep.Cout, ep.bias, ep.relu != 0, acc, lds, m_blk, n_blk, wm, wn, r, h, tid, ep.bn_part, ep.Cout); return true; }
     return false;
   } else if constexpr (std::is_same<EP, EpStore>::value) {
@@ -1689,6 +1722,10 @@ void gemm_halo_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const 
 //   map row (W >= 64) and loses the same number of blocks in the same steps: the first n (dy = -1) or the last n (dy = +1) of its four, n <= 2
 //   (halo4_skip.h), a wave-uniform count taken once per tile.  A shortened half-step keeps every B read and every LDS-DMA piece in its order (the vmcnt
 //   counts stand) and spreads them evenly over the MFMAs that remain.  A skipped product adds +0 per term: bit-identical outputs for finite weights.
+//   The (2,1)-pooled launches (conv4 / conv6 forward, ops_gemm.hip's halo4_pool_skip_eligible; AOCR_NO_HALO4_POOL_SKIP=1: the form above) take SKIP with the
+//   ROW-SPLIT order: their tile is the same 256 / W whole map rows, so a lane addresses its pixels in plain order, blocks, rows and dead counts are the plain
+//   order's, and a pool window is the same entry of acc[mi] and acc[mi + W / 64] (W = 64, 128) -- tile256_store_pooled's PW form, the only epilogue that knows
+//   this order: the launcher sends only launches whose every tile takes it.
 template <class EP, int SGN, int TAG = 0, bool SKIP = false>
 __global__ __launch_bounds__(256, 1)
 void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const bf16_t* zero, int opt) {
@@ -1715,8 +1752,10 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
   for (int mi = 0; mi < 4; ++mi) {
     const int local = halo4_block(SKIP, wm, mi) * 32 + r;
     int ty, tx;
+    // SKIP at pmode 2 is the row-split order: the lane's pixels in PLAIN order within the tile's 256 / W map rows (the halo image is in image order anyway,
+    // and y0 is the first of those rows in either order); only the pooled epilogue knows the difference
     if (g.pmode == 1) { const int win = local >> 2, wx = win % g.Wp; ty = 2 * (win / g.Wp) + ((local >> 1) & 1); tx = 2 * wx + (local & 1); }
-    else if (g.pmode == 2) { const int win = local >> 1; tx = win % W; ty = 2 * (win / W) + (local & 1); }
+    else if (g.pmode == 2 && !SKIP) { const int win = local >> 1; tx = win % W; ty = 2 * (win / W) + (local & 1); }
     else { ty = local / W; tx = local - ty * W; }
 #pragma unroll
     for (int dxi = 0; dxi < 3; ++dxi) {
@@ -1724,7 +1763,7 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
       abase[mi][dxi] = lbase + (unsigned)(ty * P + col) * 64u + (unsigned)((h ^ sw) << 4);
     }
   }
-  // SKIP: this wave's dead blocks in the steps of halo row 0 (the first ntop of its four) and of halo row 2 (the last nbot); plain pixel order only
+  // SKIP: this wave's dead blocks in the steps of halo row 0 (the first ntop of its four) and of halo row 2 (the last nbot); plain or row-split pixel order
   int ntop = 0, nbot = 0;
   if constexpr (SKIP) {
     ntop = __builtin_amdgcn_readfirstlane(halo4_ndead(wm, 0, W, H, y0));
@@ -1933,7 +1972,7 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
   for (int i = 0; i < 4; ++i) asm volatile("" ::"v"(a0[i]), "v"(b0[i]), "v"(a1[i]), "v"(b1[i]));
   if constexpr (TAG == 1) { if ((blockIdx.x == 17 || blockIdx.x == 300) && tid == 0) { const int o = blockIdx.x == 17 ? 4 : 0; g_kprobe[o] = __builtin_readcyclecounter() - pc0; g_kprobe[o + 1] = wall_clock64() - pw0; g_kprobe[o + 2] = pw0 - pe0; } }
   const int m0 = m_blk + (SKIP ? wm * 32 : wm * 128), n0 = n_blk + wn * 128;          // SKIP: block 2 mi + wm
-  if (tile256_store_staged<4, 256, SKIP>(ep, acc, lds, m_blk, n_blk, wm, wn, r, h, tid, opt)) {
+  if (tile256_store_staged<4, 256, SKIP>(ep, acc, lds, m_blk, n_blk, wm, wn, r, h, tid, opt, W)) {
     if constexpr (TAG == 1) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); if ((blockIdx.x == 17 || blockIdx.x == 300) && tid == 0) g_kprobe[blockIdx.x == 17 ? 7 : 3] = wall_clock64() - pe0; }
     return;
   }

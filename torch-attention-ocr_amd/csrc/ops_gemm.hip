@@ -21,7 +21,7 @@ struct TraceScope {
   explicit TraceScope(const char* fn) : outer(t_trace_fn) { if (!outer) t_trace_fn = fn; }
   ~TraceScope() { t_trace_fn = outer; }
 };
-// (note: a word behind the line for a variant that keeps the kernel's name and instantiation -- gemm_halo4_bf16_kernel's "skip", gemm_f32w_kernel's effective k split)
+// (note: a word behind the line for a variant that keeps the kernel's name and instantiation -- gemm_halo4_bf16_kernel's "skip" / "pskip", gemm_f32w_kernel's effective k split)
 static void trace_launch(const char* kernel, const char* inst, long long M, long long N, long long K, const char* note = nullptr) {
   if (t_trace_fn && knob::AOCR_TRACE()) fprintf(stderr, "[aocr] %s: %s[%s] %lld %lld %lld%s%s\n", t_trace_fn, kernel, inst, M, N, K, note ? " " : "", note ? note : "");
 }
@@ -110,7 +110,7 @@ static bool halo_eligible(const LoadConvK& g, int N, int MT, int NT) {
   return true;
 }
 // "this launch of the 4-wave halo kernel takes its SKIP form" (interleaved blocks per wave-row, the padding rows' dead blocks skipped): plain pixel order -- the
-// pooled orders put a pool window's rows side by side, so no 32-pixel block lies in one map row -- with blocks inside one map row (W % 32 == 0) and whole rows per
+// pooled orders put a pool window's rows side by side, so no 32-pixel block lies in one map row (halo4_pool_skip_eligible below re-orders them) -- with blocks inside one map row (W % 32 == 0) and whole rows per
 // tile (256 % W == 0; halo_eligible's widths all are).  Not with AOCR_BN_Y16's epilogue, whose fp32 column sums depend on which rows a lane holds.
 // AOCR_NO_HALO4_SKIP=1: the first form everywhere (the parity reference and the A/B baseline)
 template <class EP>
@@ -119,6 +119,17 @@ static bool halo4_skip_eligible(const LoadConvK& g, const EP& ep) {
   if constexpr (std::is_same<EP, EpConv>::value) { if (ep.y16 && ep.bn_part) return false; }
   return true;
 }
+// "this (2,1)-pooled launch takes the SKIP form in its row-split order" (halo4_skip.h: a pool window's rows in acc[mi] and acc[mi + W / 64] of one lane): widths
+// 64 and 128 -- at 32 the partner row belongs to the other wave-row -- and only where EVERY tile leaves through tile256_store_pooled (the kernel's own predicate,
+// full tiles), the one epilogue that knows this order: an fp32 destination, a null idx or AOCR_HALO4_STAGED without bit 4 keep the first form and its quad epilogue.
+// AOCR_NO_HALO4_POOL_SKIP=1: the first form for these launches only (the A/B switch); AOCR_NO_HALO4_SKIP=1 covers them too
+template <class EP>
+static bool halo4_pool_skip_eligible(const LoadConvK& g, const EP& ep, int opt) {
+  if constexpr (std::is_same<EP, EpConv>::value) {
+    if (knob::AOCR_NO_HALO4_SKIP() || knob::AOCR_NO_HALO4_POOL_SKIP() || g.pmode != 2 || !halo4_pool_width(g.Wr)) return false;
+    return tile256_pooled_staged(ep, opt) && ep.rows % 256 == 0 && ep.Cout % 256 == 0;
+  } else return false;
+}
 void kprobe_read(unsigned long long out[8]) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_kprobe), 64); }
 template <int SGN, int MT, int NT, class EP>
 static void launch_halo(hipStream_t s, const LoadConvKh& a, const LoadKh& b, const EP& ep, int M, int N, int tag = 0) {
@@ -126,8 +137,8 @@ static void launch_halo(hipStream_t s, const LoadConvKh& a, const LoadKh& b, con
   if constexpr (MT == 256 && NT == 256) {                 // four waves of 128 x 128 with hand-placed reads / DMA (AOCR_HALO8=1: the 8-wave kernel; bit-identical)
     if (!knob::AOCR_HALO8()) {
       const int opt = knob::AOCR_HALO4_STAGED();   // staged256's bits
-      const bool skip = halo4_skip_eligible(a.g, ep);
-      trace_launch("gemm_halo4_bf16_kernel", SGN > 0 ? "fwd" : "dgrad", M, N, 9LL * a.g.C, skip ? "skip" : nullptr);
+      const bool pskip = SGN > 0 && halo4_pool_skip_eligible(a.g, ep, opt), skip = pskip || halo4_skip_eligible(a.g, ep);
+      trace_launch("gemm_halo4_bf16_kernel", SGN > 0 ? "fwd" : "dgrad", M, N, 9LL * a.g.C, pskip ? "pskip" : skip ? "skip" : nullptr);
       if (skip && tag) hipLaunchKernelGGL((gemm_halo4_bf16_kernel<EP, SGN, 1, true>), dim3(gx * gy), dim3(256), 0, s, a, b, ep, gx, gy, zero_page(), opt);
       else if (skip) hipLaunchKernelGGL((gemm_halo4_bf16_kernel<EP, SGN, 0, true>), dim3(gx * gy), dim3(256), 0, s, a, b, ep, gx, gy, zero_page(), opt);
       else if (tag) hipLaunchKernelGGL((gemm_halo4_bf16_kernel<EP, SGN, 1>), dim3(gx * gy), dim3(256), 0, s, a, b, ep, gx, gy, zero_page(), opt);
