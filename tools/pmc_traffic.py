@@ -1,6 +1,6 @@
 """HBM-side traffic per launch of the two kernels bench.py's roofline fields name, from two rocprofv3 --pmc passes (FETCH_SIZE,
 WRITE_SIZE) of the bench command: the tagged launches of aocr_profile_kernel -- id 0 = conv6 forward (gemm_halo4_bf16_kernel<EpConv, 1, TAG 1>; under AOCR_HALO8=1 the 8-wave gemm_halo_bf16_kernel<..., 1>),
-id 1 = conv6 filter gradient (round 4: conv_wgrad_halo_kernel<1>; round 3: conv_wgrad_dma_kernel<EpStore, 256>; + the splitk_reduce_kernel launch behind each of them).
+id 1 = conv6 filter gradient (round 4: conv_wgrad_halo_kernel<1>; round 3: conv_wgrad_dma_kernel<EpStore, 0, 1>; + the splitk_reduce_kernel launch behind each of them).
 Units and the gfx950 correction follow /opt/skills/guides/MI355X_MICROARCH.md (HBM section): counters are in KB; FETCH_SIZE reports
 exactly half the bytes of a wide (16 B/lane) coalesced read stream -> doubled.  Writes JSON next to the text summary when asked:
     python tools/pmc_traffic.py fetch.csv write.csv [out_dir]"""
@@ -10,7 +10,7 @@ import os
 import sys
 
 FWD = "gemm_halo4_bf16_kernel<aocr::EpConv, 1, 1>"
-WG = "conv_wgrad_halo_kernel<1,"          # round 4 (round 3: "conv_wgrad_dma_kernel<aocr::EpStore, 256>")
+WG = "conv_wgrad_halo_kernel<1,"          # round 4 (round 3: "conv_wgrad_dma_kernel<aocr::EpStore, 0, 1>")
 RED = "splitk_reduce_kernel"
 
 

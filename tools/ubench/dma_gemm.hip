@@ -1,5 +1,6 @@
 // Timing-only ablations of gemm_dma_bf16_kernel at the conv6-forward shape of workload C3
-// (B=256, 4 x 64 map, 512 -> 512, 3x3): which of {LDS-DMA stream, fragment reads, MFMA issue} bounds the K loop.
+// (B=256, 4 x 64 map, 512 -> 512, 3x3): how much of the launch is the LDS-DMA stream, and which operand's.
+// (The no-MFMA / no-fragment-read ablations lived on the kernel's pipelined-read form and went with it: DESIGN.md section 3.1.)
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../include -I../../torch-attention-ocr_amd/csrc dma_gemm.hip -o dma_gemm
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -16,14 +17,14 @@ __global__ void fill(bf16_t* p, size_t n, unsigned seed) {
   }
 }
 
-template <int ABL, bool PIPE = true, bool PAIRS = false> static int run(const LoadConvKh& a, const LoadKh& b, const EpConv& ep, int M, int N, int K, const bf16_t* zero, const char* name) {
+template <int ABL> static int run(const LoadConvKh& a, const LoadKh& b, const EpConv& ep, int M, int N, int K, const bf16_t* zero, const char* name) {
   const int gx = N / 256, gy = (M + 255) / 256;
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-  for (int i = 0; i < 3; ++i) hipLaunchKernelGGL((gemm_dma_bf16_kernel<LoadConvKh, LoadKh, EpConv, ABL, PIPE, PAIRS>), dim3(gx * gy), dim3(512), 0, 0, a, b, ep, K, gx, gy, zero);
+  for (int i = 0; i < 3; ++i) hipLaunchKernelGGL((gemm_dma_bf16_kernel<LoadConvKh, LoadKh, EpConv, ABL>), dim3(gx * gy), dim3(512), 0, 0, a, b, ep, K, gx, gy, zero);
   CK(hipDeviceSynchronize());
   CK(hipEventRecord(e0));
   const int it = 20;
-  for (int i = 0; i < it; ++i) hipLaunchKernelGGL((gemm_dma_bf16_kernel<LoadConvKh, LoadKh, EpConv, ABL, PIPE, PAIRS>), dim3(gx * gy), dim3(512), 0, 0, a, b, ep, K, gx, gy, zero);
+  for (int i = 0; i < it; ++i) hipLaunchKernelGGL((gemm_dma_bf16_kernel<LoadConvKh, LoadKh, EpConv, ABL>), dim3(gx * gy), dim3(512), 0, 0, a, b, ep, K, gx, gy, zero);
   CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
   float ms; CK(hipEventElapsedTime(&ms, e0, e1));
   double us = ms * 1e3 / it;
@@ -50,27 +51,13 @@ int main() {
   printf("conv6 forward as implicit GEMM: M %d N %d K %d, %d workgroups\n", M, N, K, (N / 256) * ((M + 255) / 256));
   run<0>(a, b, ep, M, N, K, zero, "full kernel");
   run<1>(a, b, ep, M, N, K, zero, "no in-loop DMA (reads + MFMA + barrier)");
-  // run<2>: faults (under investigation)
-  run<6>(a, b, ep, M, N, K, zero, "DMA + barrier only");
-  run<3>(a, b, ep, M, N, K, zero, "reads + barrier only");
-  run<5>(a, b, ep, M, N, K, zero, "MFMA + barrier only");
-  run<7>(a, b, ep, M, N, K, zero, "barrier + epilogue only");
-  { EpConv e2 = ep; e2.y = nullptr; run<7>(a, b, e2, M, N, K, zero, "barrier + epilogue only, no fp32 y");
-    run<0, false>(a, b, e2, M, N, K, zero, "full kernel, plain reads, no fp32 y");
-    e2.idx = nullptr; run<7>(a, b, e2, M, N, K, zero, "barrier + epilogue only, bf16 y only");
-    e2.yb = nullptr; run<7>(a, b, e2, M, N, K, zero, "barrier + epilogue only, no stores at all"); }
+  { EpConv e2 = ep; e2.y = nullptr; run<0>(a, b, e2, M, N, K, zero, "full kernel, no fp32 y"); }
   for (int rep = 0; rep < 2; ++rep) {                     // round 2: how much of the launch is the im2col (A) stream?
-    run<0, false>(a, b, ep, M, N, K, zero, "full kernel, plain reads");
-    run<16, false>(a, b, ep, M, N, K, zero, "plain reads, A pieces from the zero page");
-    run<32, false>(a, b, ep, M, N, K, zero, "plain reads, no A pieces");
-    run<128, false>(a, b, ep, M, N, K, zero, "plain reads, B pieces from the zero page");
-    run<128 + 16, false>(a, b, ep, M, N, K, zero, "plain reads, A and B pieces from the zero page");
-  }
-  for (int rep = 0; rep < 1; ++rep) {
-    run<0, true>(a, b, ep, M, N, K, zero, "full kernel, pipelined reads");
-    run<0, false>(a, b, ep, M, N, K, zero, "full kernel, plain reads");
-    run<0, false, true>(a, b, ep, M, N, K, zero, "full kernel, two tiles per barrier");
-    run<8, false>(a, b, ep, M, N, K, zero, "full kernel, s_setprio around the MFMA blocks");
+    run<0>(a, b, ep, M, N, K, zero, "full kernel");
+    run<16>(a, b, ep, M, N, K, zero, "A pieces from the zero page");
+    run<32>(a, b, ep, M, N, K, zero, "no A pieces");
+    run<128>(a, b, ep, M, N, K, zero, "B pieces from the zero page");
+    run<128 + 16>(a, b, ep, M, N, K, zero, "A and B pieces from the zero page");
   }
   return 0;
 }

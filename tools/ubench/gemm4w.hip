@@ -25,9 +25,7 @@ __global__ void fill(bf16_t* p, size_t n, unsigned seed) {
 template <int MODE, int HALFBAR>
 __global__ __launch_bounds__(256, 1) void gemm4w_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bm, float* __restrict__ C, int M, int N, int K, int gx, int gy, int lda, int kwrap) {
   __shared__ __attribute__((aligned(1024))) unsigned char lds[4 * 32768];
-  const int nwg = gx * gy, orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-  const int bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int bid = xcd_major_id(gx * gy, blockIdx.x);
   const int m_blk = (bid / gx) * 256, n_blk = (bid % gx) * 256;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5, wm = wave >> 1, wn = wave & 1;
@@ -50,12 +48,7 @@ __global__ __launch_bounds__(256, 1) void gemm4w_kernel(const bf16_t* __restrict
     for (int j = 0; j < 4; ++j) dma16(bsrc[j] + k, base + 16384 + j * 1024);
   };
   f32x16 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  acc_zero(acc);
   const int swz = (r >> 2) & 3;
   unsigned aoff[2], boff[2];
 #pragma unroll
@@ -334,11 +327,11 @@ template <int MODE, int HALFBAR> static int run(const bf16_t* A, const bf16_t* B
 template <int ABL> static int run8(const LoadKh& a, const LoadKh& b, const EpStore& ep, int M, int N, int K, const bf16_t* zero, const char* name) {
   const int gx = N / 256, gy = M / 256;
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-  for (int i = 0; i < 3; ++i) hipLaunchKernelGGL((gemm_dma_bf16_kernel<LoadKh, LoadKh, EpStore, ABL, false, false>), dim3(gx * gy), dim3(512), 0, 0, a, b, ep, K, gx, gy, zero);
+  for (int i = 0; i < 3; ++i) hipLaunchKernelGGL((gemm_dma_bf16_kernel<LoadKh, LoadKh, EpStore, ABL>), dim3(gx * gy), dim3(512), 0, 0, a, b, ep, K, gx, gy, zero);
   CK(hipDeviceSynchronize());
   CK(hipEventRecord(e0));
   const int it = 20;
-  for (int i = 0; i < it; ++i) hipLaunchKernelGGL((gemm_dma_bf16_kernel<LoadKh, LoadKh, EpStore, ABL, false, false>), dim3(gx * gy), dim3(512), 0, 0, a, b, ep, K, gx, gy, zero);
+  for (int i = 0; i < it; ++i) hipLaunchKernelGGL((gemm_dma_bf16_kernel<LoadKh, LoadKh, EpStore, ABL>), dim3(gx * gy), dim3(512), 0, 0, a, b, ep, K, gx, gy, zero);
   CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
   float ms; CK(hipEventElapsedTime(&ms, e0, e1));
   const double us = ms * 1e3 / it;
@@ -409,7 +402,7 @@ int main(int argc, char** argv) {
   std::vector<float> c4((size_t)256 * N), c8((size_t)256 * N);
   hipLaunchKernelGGL((gemm4w_kernel<0, 3>), dim3((N / 256) * (M / 256)), dim3(256), 0, 0, A, B, C, M, N, K, N / 256, M / 256, K, 8192);
   CK(hipMemcpy(c4.data(), C + (size_t)1000 * 256 / 256 * 256 * N, c4.size() * 4, hipMemcpyDeviceToHost));
-  hipLaunchKernelGGL((gemm_dma_bf16_kernel<LoadKh, LoadKh, EpStore, 0, false, false>), dim3((N / 256) * (M / 256)), dim3(512), 0, 0, a, b, ep, K, N / 256, M / 256, zero);
+  hipLaunchKernelGGL((gemm_dma_bf16_kernel<LoadKh, LoadKh, EpStore>), dim3((N / 256) * (M / 256)), dim3(512), 0, 0, a, b, ep, K, N / 256, M / 256, zero);
   CK(hipMemcpy(c8.data(), C + (size_t)1000 * 256 / 256 * 256 * N, c8.size() * 4, hipMemcpyDeviceToHost));
   double md = 0, mx = 0;
   for (size_t i = 0; i < c4.size(); ++i) { md = std::max(md, (double)fabsf(c4[i] - c8[i])); mx = std::max(mx, (double)fabsf(c8[i])); }

@@ -31,6 +31,44 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 template <int... I, class F> __device__ __forceinline__ void aocr_static_for_impl(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
 template <int N, class F> __device__ __forceinline__ void aocr_static_for(F&& f) { aocr_static_for_impl(std::make_integer_sequence<int, N>{}, f); }
 
+// XCD-major workgroup renumbering (bijective): the hardware deals the workgroup ids of a launch round-robin to the 8 XCDs, so ids orig, orig + 8, ... share
+// an XCD and its L2.  The renumbered ids of one XCD are consecutive: neighbouring tiles (one M row-panel, which shares the A operand; one k range of a
+// split-K launch) run on one XCD's L2.
+__device__ __forceinline__ int xcd_major_id(int nwg, int orig) {
+  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+}
+template <int M, int N> __device__ __forceinline__ void acc_zero(f32x16 (&acc)[M][N]) {
+#pragma unroll
+  for (int i = 0; i < M; ++i)
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+}
+// the quad epilogue of a wave's M x NI accumulator tiles: rows m0 + 32 mi + 8 q + 4 h .. + 3 of columns n0 + r + 32 ni
+template <int NI, int M, class EP>
+__device__ __forceinline__ void store_quads(const EP& ep, const f32x16 (&acc)[M][NI], int m0, int n0, int r, int h) {
+#pragma unroll
+  for (int mi = 0; mi < M; ++mi)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float v[NI][4];
+#pragma unroll
+      for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[ni][i] = acc[mi][ni][4 * q + i];
+      ep.template quad<NI>(m0 + 32 * mi + 8 * q + 4 * h, n0 + r, 32, v);
+    }
+}
+// LDS fragment reads whose lgkmcnt waits are counted by hand (the builtins' reads are ordered by hipcc behind ALL pending LDS-DMA: see AOCR_WGRAD_DMA_KLOOP)
+template <int OFF, class T> __device__ __forceinline__ void lds_read_b128(T& dst, unsigned addr) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
+}
+template <int OFF, class T> __device__ __forceinline__ void lds_read_tr_b64(T& dst, unsigned addr) {
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
+}
+
 // one operand fragment of a 32-row tile for one k-chunk: 4 floats (f32 mode, chunk 8)
 // or 8 floats (bf16 mode, chunk 16) per lane.
 template <int NV> struct Frag { float v[NV]; };
@@ -305,12 +343,7 @@ __global__ __launch_bounds__(256) void gemm_big_kernel(AL a, BL b, EP ep, int K,
   for (int i = 0; i < WN; ++i) cb[i] = b.row(n0 + 32 * i + r);
 
   f32x16 acc[WM][WN];
-#pragma unroll
-  for (int i = 0; i < WM; ++i)
-#pragma unroll
-    for (int j = 0; j < WN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  acc_zero(acc);
 
   Frag<NV> fa[WM], fb[WN], ga[WM], gb[WN];
   if (kbeg < kend) {
@@ -333,17 +366,7 @@ __global__ __launch_bounds__(256) void gemm_big_kernel(AL a, BL b, EP ep, int K,
 #pragma unroll
     for (int i = 0; i < WN; ++i) fb[i] = gb[i];
   }
-#pragma unroll
-  for (int mi = 0; mi < WM; ++mi)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float v[WN][4];
-#pragma unroll
-      for (int ni = 0; ni < WN; ++ni)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[ni][i] = acc[mi][ni][4 * q + i];
-      ep.template quad<WN>(m0 + 32 * mi + 8 * q + 4 * h, n0 + r, 32, v);
-    }
+  store_quads<WN>(ep, acc, m0, n0, r, h);
 }
 
 // ---------------------------------------------------------------------------
@@ -717,12 +740,7 @@ __device__ __forceinline__ void lds_tile(const AL& a, const BL& b, const EP& ep,
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  acc_zero(acc);
 
 #pragma unroll
   for (int d = 0; d < D; ++d) if (d < nk) gload(sa[d], sb[d]);
@@ -757,17 +775,7 @@ __device__ __forceinline__ void lds_tile(const AL& a, const BL& b, const EP& ep,
     }
   }
   const int m0 = m_blk + wm * 64, n0 = n_blk + wn * 64;
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float v[2][4];
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[ni][i] = acc[mi][ni][4 * q + i];
-      ep.template quad<2>(m0 + 32 * mi + 8 * q + 4 * h, n0 + r, 32, v);
-    }
+  store_quads<2>(ep, acc, m0, n0, r, h);
 }
 
 // ---------------------------------------------------------------------------
@@ -789,12 +797,7 @@ __device__ __forceinline__ void lds_tile_f32(const AL& a, const BL& b, const EP&
   Stager<AL, 32> sa; Stager<BL, 32> sb;
   sa.init(a, m_blk, tid, 0, kbeg); sb.init(b, n_blk, tid, 1, kbeg);
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  acc_zero(acc);
   if (nk > 0) { sa.load(a); sb.load(b); sa.store32(&lds[0][0][0]); sb.store32(&lds[0][1][0]); }
   __syncthreads();
   for (int kt = 0; kt < nk; ++kt) {
@@ -825,24 +828,12 @@ __device__ __forceinline__ void lds_tile_f32(const AL& a, const BL& b, const EP&
     __syncthreads();
   }
   const int m0 = m_blk + wm * 64, n0 = n_blk + wn * 64;
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float v[2][4];
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[ni][i] = acc[mi][ni][4 * q + i];
-      ep.template quad<2>(m0 + 32 * mi + 8 * q + 4 * h, n0 + r, 32, v);
-    }
+  store_quads<2>(ep, acc, m0, n0, r, h);
 }
 template <class AL, class BL, class EP>
 __global__ __launch_bounds__(256, 2) void gemm_lds_f32_kernel(AL a, BL b, EP ep, int K, int kper, int gx, int gy) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[2][2][128 * LDS_PITCH32];        // 73.7 KB: two workgroups per CU
-  const int nwg = gx * gy, orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-  const int bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int bid = xcd_major_id(gx * gy, blockIdx.x);
   const int kbeg = blockIdx.z * kper;
   lds_tile_f32(a, b, ep, (bid / gx) * 128, (bid % gx) * 128, kbeg, min(K, kbeg + kper), lds);
 }
@@ -892,9 +883,7 @@ template <int BM, int BN, class AL, class BL, class EP>
 __global__ __launch_bounds__(256, (BM + BN <= 128) ? 4 : 2) void gemm_f32t_kernel(AL a, BL b, EP ep, int K, int kper, int gx, int gy) {
   constexpr int PITCH = LDS_PITCH32, MI = BM / 64, NI = BN / 64, SLOT = (BM + BN) * PITCH;
   __shared__ __attribute__((aligned(16))) unsigned char lds[2][SLOT];      // 128 x 128: 73.7 KB (2 per CU), 64 x 128: 55.3 KB (2), 64 x 64: 36.9 KB (4)
-  const int nwg = gx * gy, orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-  const int bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);      // consecutive ids share an XCD
+  const int bid = xcd_major_id(gx * gy, blockIdx.x);
   const int m_blk = (bid / gx) * BM, n_blk = (bid % gx) * BN;
   const int kbeg = blockIdx.z * kper, kend = min(K, kbeg + kper);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -904,12 +893,7 @@ __global__ __launch_bounds__(256, (BM + BN <= 128) ? 4 : 2) void gemm_f32t_kerne
   StagerF32<AL, BM> sa; StagerF32<BL, BN> sb;
   sa.init(a, m_blk, tid, kbeg); sb.init(b, n_blk, tid, kbeg);
   f32x16 acc[MI][NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  acc_zero(acc);
   if (nk > 0) { sa.load(a); sb.load(b); sa.store(&lds[0][0]); sb.store(&lds[0][BM * PITCH]); }
   __syncthreads();
   for (int kt = 0; kt < nk; ++kt) {
@@ -944,17 +928,7 @@ __global__ __launch_bounds__(256, (BM + BN <= 128) ? 4 : 2) void gemm_f32t_kerne
     __syncthreads();
   }
   const int m0 = m_blk + wm * (BM / 2), n0 = n_blk + wn * (BN / 2);
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float v[NI][4];
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[ni][i] = acc[mi][ni][4 * q + i];
-      ep.template quad<NI>(m0 + 32 * mi + 8 * q + 4 * h, n0 + r, 32, v);
-    }
+  store_quads<NI>(ep, acc, m0, n0, r, h);
 }
 // ---------------------------------------------------------------------------
 // Round 4: gemm_f32w_kernel -- exact-fp32 products of two M/N-CONTIGUOUS operands (conv filter gradients: A = dY^T (LoadMN), B = im2col
@@ -1019,9 +993,7 @@ template <class AL, class BL, class EP>
 __global__ __launch_bounds__(256, 2) void gemm_f32w_kernel(AL a, BL b, EP ep, int K, int kper, int gx, int gy) {
   constexpr int PK = F32W_PITCH, OPB = 32 * PK;
   __shared__ __attribute__((aligned(16))) unsigned char lds[2][2 * OPB];
-  const int nwg = gx * gy, orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-  const int bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int bid = xcd_major_id(gx * gy, blockIdx.x);
   const int m_blk = (bid / gx) * 128, n_blk = (bid % gx) * 128;
   const int kbeg = blockIdx.z * kper, kend = min(K, kbeg + kper);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1031,12 +1003,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32w_kernel(AL a, BL b, EP ep, in
   StagerW<AL> sa; StagerW<BL> sb;
   sa.init(a, m_blk, tid, kbeg); sb.init(b, n_blk, tid, kbeg);
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  acc_zero(acc);
   if (nk > 0) { sa.load(a); sb.load(b); stagerw_store(sa, &lds[0][0], tid); stagerw_store(sb, &lds[0][OPB], tid); }
   __syncthreads();
   for (int kt = 0; kt < nk; ++kt) {
@@ -1058,17 +1025,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32w_kernel(AL a, BL b, EP ep, in
     __syncthreads();
   }
   const int m0 = m_blk + wm * 64, n0 = n_blk + wn * 64;
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float v[2][4];
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[ni][i] = acc[mi][ni][4 * q + i];
-      ep.template quad<2>(m0 + 32 * mi + 8 * q + 4 * h, n0 + r, 32, v);
-    }
+  store_quads<2>(ep, acc, m0, n0, r, h);
 }
 template <class L> struct HasStagerW { static constexpr bool v = false; };
 template <> struct HasStagerW<LoadMN> { static constexpr bool v = true; };
@@ -1082,10 +1039,7 @@ template <class AL, class BL, class EP, int BK = 32>
 __global__ __launch_bounds__(256, (SrcBf16<AL>::v && SrcBf16<BL>::v) ? 4 : 1)      // bf16-source pairs fit 128 VGPRs: 4 workgroups per CU
 void gemm_lds_bf16_kernel(AL a, BL b, EP ep, int K, int kper, int gx, int gy) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[2][2][128 * (BK * 2 + 16)];
-  // XCD-aware renumbering (bijective form): consecutive renumbered ids share an XCD (ids are dealt round-robin to 8 XCDs)
-  const int nwg = gx * gy, orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-  const int bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int bid = xcd_major_id(gx * gy, blockIdx.x);
   const int kbeg = blockIdx.z * kper;
   lds_tile<BK>(a, b, ep, (bid / gx) * 128, (bid % gx) * 128, kbeg, min(K, kbeg + kper), lds);
 }
@@ -1343,13 +1297,14 @@ __device__ __forceinline__ void dma16(const void* g, unsigned char* l) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
 }
 
-template <class AL, class BL, class EP, int ABL = 0, bool PIPE = false, bool PAIRS = false, int TAG = 0>     // TAG: distinct symbol for aocr_profile_kernel's launches (so that rocprofv3 --stats lists them on their own row); PAIRS: two K tiles per barrier; PIPE: fragment reads pipelined across the barrier (inline asm; measured 4-7 % slower); ABL: timing-only ablations (tools/ubench/dma_gemm.hip): 1 no in-loop DMA, 2 no MFMA, 4 no fragment reads, 16 / 128 A / B pieces from the zero page (plain form), 32 no A pieces at all (plain form)
+// TAG: distinct symbol for aocr_profile_kernel's launches (so that rocprofv3 --stats lists them on their own row).  ABL: timing-only ablations
+// (tools/ubench/dma_gemm.hip, gemm4w.hip): 1 no in-loop DMA, 16 / 128 A / B pieces from the zero page, 32 no A pieces at all.
+// (Tried on this body and removed, DESIGN.md section 3.1: fragment reads pipelined across the barrier, two K tiles per barrier, s_setprio around the MFMA blocks.)
+template <class AL, class BL, class EP, int ABL = 0, int TAG = 0>
 __global__ __launch_bounds__(512, 1)
 void gemm_dma_bf16_kernel(AL a, BL b, EP ep, int K, int gx, int gy, const bf16_t* zero, int opt = 0) {
   __shared__ __attribute__((aligned(1024))) unsigned char lds[4 * 32768];          // the ONLY LDS object (a second one makes hipcc drain vmcnt)
-  const int nwg = gx * gy, orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-  const int bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int bid = xcd_major_id(gx * gy, blockIdx.x);
   const int m_blk = (bid / gx) * 256, n_blk = (bid % gx) * 256;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5, wm = wave >> 2, wn = wave & 3;
@@ -1375,12 +1330,7 @@ void gemm_dma_bf16_kernel(AL a, BL b, EP ep, int K, int gx, int gy, const bf16_t
   };
 
   f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  acc_zero(acc);
 
   const int swz = (r >> 2) & 3;
   unsigned aoff[2], boff[2];
@@ -1390,137 +1340,39 @@ void gemm_dma_bf16_kernel(AL a, BL b, EP ep, int K, int gx, int gy, const bf16_t
     boff[s] = 16384 + (wn * 64 + r) * 64 + (((2 * s + h) ^ swz) << 4);
   }
 
-  // Fragment reads are software-pipelined across the barrier: the k 16..31 half of tile t is fetched under the MFMAs of
-  // its k 0..15 half, and the first half of tile t+1 under the MFMAs of the second half of tile t -- right after the
-  // barrier the MFMA pipe already has operands in registers.  The reads are inline asm with hand-counted lgkmcnt waits
-  // (hipcc's own insertion waits lgkmcnt(0) for the loop-carried half, i.e. for the reads just issued); every wait is
-  // followed by sched_barrier(0) so that no MFMA is hoisted above it.
-  const unsigned lbase = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned char*)lds);
-  bf16x8 fa0[4], fb0[2], fa1[4], fb1[2];
-#define AOCR_DSR(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=v"(dst) : "v"(addr))
-  auto read0 = [&](int sl) {
-    const unsigned pa = lbase + sl * 32768 + aoff[0], pb = lbase + sl * 32768 + boff[0];
-    AOCR_DSR(fa0[0], pa, 0); AOCR_DSR(fa0[1], pa, 2048); AOCR_DSR(fb0[0], pb, 0); AOCR_DSR(fb0[1], pb, 2048);
-    AOCR_DSR(fa0[2], pa, 4096); AOCR_DSR(fa0[3], pa, 6144);
-  };
-  auto read1 = [&](int sl) {
-    const unsigned pa = lbase + sl * 32768 + aoff[1], pb = lbase + sl * 32768 + boff[1];
-    AOCR_DSR(fa1[0], pa, 0); AOCR_DSR(fa1[1], pa, 2048); AOCR_DSR(fb1[0], pb, 0); AOCR_DSR(fb1[1], pb, 2048);
-    AOCR_DSR(fa1[2], pa, 4096); AOCR_DSR(fa1[3], pa, 6144);
-  };
-#undef AOCR_DSR
-  if constexpr (!PIPE && PAIRS) {                       // two K tiles per barrier: 72 instead of 144 barriers at K = 4608 (a bare
-    // s_waitcnt + s_barrier iteration costs ~0.1 us: 30 us of the 300 us launch, tools/ubench/dma_gemm.hip).  Ring = two pairs of
-    // slots; pair p+1 is issued right after the barrier that ends pair p-1 and lands under the 32 MFMAs per wave of pair p.
-    const int npairs = (nk + 1) >> 1;                   // an odd last tile is padded by a zero-page tile
-    issue_a(); issue_b(); issue_a(); issue_b();
-    for (int pr = 0; pr < npairs; ++pr) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of pair pr have landed
-      __builtin_amdgcn_s_barrier();                     // ... everyone's have, and everyone is done reading pair pr-1
-      if constexpr (!(ABL & 1)) { issue_a(); issue_b(); issue_a(); issue_b(); }
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        const unsigned char* L = lds + (((pr & 1) << 1) + half) * 32768;
-        bf16x8 af[2][4], bf[2][2];
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-#pragma unroll
-          for (int mi = 0; mi < 4; ++mi) af[s2][mi] = *reinterpret_cast<const bf16x8*>(L + aoff[s2] + mi * 2048);
-#pragma unroll
-          for (int ni = 0; ni < 2; ++ni) bf[s2][ni] = *reinterpret_cast<const bf16x8*>(L + boff[s2] + ni * 2048);
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-          for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-              acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s2][mi], bf[s2][ni], acc[mi][ni], 0, 0, 0);
-      }
-    }
-  } else if constexpr (!PIPE) {                         // plain form: compiler-managed reads, tile kt+3 issued under tile kt
-#pragma unroll
-    for (int t = 0; t < 3; ++t) { issue_a(); issue_b(); }
-    for (int kt = 0; kt < nk; ++kt) {
-      if constexpr (ABL & 32) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      const unsigned char* L = lds + (kt & 3) * 32768;
-      bf16x8 af[2][4], bf[2][2];
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) af[s2][mi] = *reinterpret_cast<const bf16x8*>(L + aoff[s2] + mi * 2048);
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) bf[s2][ni] = *reinterpret_cast<const bf16x8*>(L + boff[s2] + ni * 2048);
-      }
-      if constexpr (!(ABL & 1)) issue_a();
-      if constexpr (ABL & 8) __builtin_amdgcn_s_setprio(1);      // experiment: raise the wave's priority over its MFMA block
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][mi], bf[0][ni], acc[mi][ni], 0, 0, 0);
-      if constexpr (ABL & 8) __builtin_amdgcn_s_setprio(0);
-      if constexpr (!(ABL & 1)) issue_b();
-      if constexpr (ABL & 8) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][mi], bf[1][ni], acc[mi][ni], 0, 0, 0);
-      if constexpr (ABL & 8) __builtin_amdgcn_s_setprio(0);
-    }
-  } else {
+  // compiler-managed fragment reads, tile kt+3 issued under tile kt
 #pragma unroll
   for (int t = 0; t < 3; ++t) { issue_a(); issue_b(); }
-  asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  __builtin_amdgcn_s_barrier();                         // tile 0 is resident
-  issue_a(); issue_b();                                 // tile 3
-  read0(0);
   for (int kt = 0; kt < nk; ++kt) {
-    if constexpr (!(ABL & 4)) read1(kt & 3);
-    asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");  // the six older reads (first half, issued one barrier ago) are back
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!(ABL & 2)) {
+    if constexpr (ABL & 32) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else
+    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    const unsigned char* L = lds + (kt & 3) * 32768;
+    bf16x8 af[2][4], bf[2][2];
 #pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
+    for (int s2 = 0; s2 < 2; ++s2) {
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa0[mi], fb0[ni], acc[mi][ni], 0, 0, 0);
+      for (int mi = 0; mi < 4; ++mi) af[s2][mi] = *reinterpret_cast<const bf16x8*>(L + aoff[s2] + mi * 2048);
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni) bf[s2][ni] = *reinterpret_cast<const bf16x8*>(L + boff[s2] + ni * 2048);
     }
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");   // own pieces of tile kt+1 landed (kt+2, kt+3 in flight); own reads of tile kt done
-    __builtin_amdgcn_s_barrier();                       // ... everyone's: tile kt+1 is resident and slot kt is free
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!(ABL & 1)) issue_a();                // tile kt+4 -> the slot of tile kt
-    if constexpr (!(ABL & 4)) read0((kt + 1) & 3);
+    if constexpr (!(ABL & 1)) issue_a();
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni)
+        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][mi], bf[0][ni], acc[mi][ni], 0, 0, 0);
     if constexpr (!(ABL & 1)) issue_b();
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!(ABL & 2)) {
 #pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
+    for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa1[mi], fb1[ni], acc[mi][ni], 0, 0, 0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
+      for (int ni = 0; ni < 2; ++ni)
+        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][mi], bf[1][ni], acc[mi][ni], 0, 0, 0);
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // the trailing (zero-page) tiles must land before the LDS is released
   const int m0 = m_blk + wm * 128, n0 = n_blk + wn * 64;
   if constexpr (ABL == 0) { if (opt && tile256_store_staged<2, 512>(ep, acc, lds, m_blk, n_blk, wm, wn, r, h, tid, opt)) return; }
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float v[2][4];
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[ni][i] = acc[mi][ni][4 * q + i];
-      ep.template quad<2>(m0 + 32 * mi + 8 * q + 4 * h, n0 + r, 32, v);
-    }
+  store_quads<2>(ep, acc, m0, n0, r, h);
 }
 
 // ---------------------------------------------------------------------------
@@ -1565,9 +1417,7 @@ void gemm_halo_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const 
   constexpr int NBW = NT >= 128 ? NT / 128 : 1;          // weight pieces per wave and step (NT = 64: waves 4-7 issue a dummy)
   static_assert(MI == 4 || MI == 2, "wave tile");
   __shared__ __attribute__((aligned(1024))) unsigned char lds[LDS_BYTES];          // the ONLY LDS object (a second one makes hipcc drain vmcnt)
-  const int nwg = gx * gy, orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-  const int bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int bid = xcd_major_id(gx * gy, blockIdx.x);
   const int m_blk = (bid / gx) * MT, n_blk = (bid % gx) * NT;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5, wm = wave / NWN, wn = wave % NWN;
@@ -1625,12 +1475,7 @@ void gemm_halo_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const 
   };
 
   f32x16 acc[MI][2];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  acc_zero(acc);
 
   // prologue: the whole halo of chunk 0 and three weight tiles, all landed before the first step
   for (int gq = wave; gq < NG; gq += 8) issue_halo(gq, 0, true);
@@ -1683,17 +1528,7 @@ void gemm_halo_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const 
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // the trailing (zero-page) pieces must land before the LDS is released
   if constexpr (TAG == 1) { if (blockIdx.x == 17 && tid == 0) { g_kprobe[0] = __builtin_readcyclecounter() - pc0; g_kprobe[1] = wall_clock64() - pw0; g_kprobe[2] = pw0 - pe0; } }
   const int m0 = m_blk + wm * WM, n0 = n_blk + wn * 64;
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float v[2][4];
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[ni][i] = acc[mi][ni][4 * q + i];
-      ep.template quad<2>(m0 + 32 * mi + 8 * q + 4 * h, n0 + r, 32, v);
-    }
+  store_quads<2>(ep, acc, m0, n0, r, h);
   if constexpr (TAG == 1) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); if (blockIdx.x == 17 && tid == 0) g_kprobe[3] = wall_clock64() - pe0; }
 }
 
@@ -1732,9 +1567,7 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
   unsigned long long pe0 = 0; if constexpr (TAG == 1) pe0 = wall_clock64();
   constexpr int MT = 256, NT = 256, HMAX = HaloGeom<MT>::HMAX, BSLOT = NT * 64, BRING = 2 * HMAX, DUMP = BRING + 4 * BSLOT, LDS_BYTES = DUMP + 4 * 1024;
   __shared__ __attribute__((aligned(1024))) unsigned char lds[LDS_BYTES];          // the ONLY LDS object
-  const int nwg = gx * gy, orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-  const int bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int bid = xcd_major_id(gx * gy, blockIdx.x);
   const int m_blk = (bid / gx) * MT, n_blk = (bid % gx) * NT;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5, wm = wave >> 1, wn = wave & 1;
@@ -1813,7 +1646,7 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
     dma16(dma_select(ok, img + ((int64_t)(y * W + x) * C + ((hchunk ^ ((row & 1) << 1)) << 3)), zero), lds + gq * 1024);
   };
 
-  f32x16 acc[4][4];
+  f32x16 acc[4][4];                                       // (zeroed in place: through acc_zero the non-SKIP forms' epilogue spill reloads grew by half)
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1831,7 +1664,6 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
   __builtin_amdgcn_s_barrier();
 
   bf16x8 a0[4], b0[4], a1[4], b1[4];
-#define AOCR_DSR(dst, addr, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF))
 #define AOCR_SB() __builtin_amdgcn_sched_barrier(0)
   // A fragment addresses: ab[mi][dxi] = abase + (halo buffer + dyi P 64) for the CURRENT (chunk, kernel row) -- twelve adds per three
   // steps -- and per read one XOR with the uniform (row-parity flip | k-half) bits, which sit below the 64-byte pixel pitch
@@ -1852,8 +1684,8 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
   };
   set_ab(0, 0);
   {                                                       // F0 of step 0
-    AOCR_DSR(a0[0], a_addr(0, 0, 0), 0); AOCR_DSR(a0[1], a_addr(1, 0, 0), 0); AOCR_DSR(a0[2], a_addr(2, 0, 0), 0); AOCR_DSR(a0[3], a_addr(3, 0, 0), 0);
-    AOCR_DSR(b0[0], boff[0], 0); AOCR_DSR(b0[1], boff[0], 2048); AOCR_DSR(b0[2], boff[0], 4096); AOCR_DSR(b0[3], boff[0], 6144);
+    lds_read_b128<0>(a0[0], a_addr(0, 0, 0)); lds_read_b128<0>(a0[1], a_addr(1, 0, 0)); lds_read_b128<0>(a0[2], a_addr(2, 0, 0)); lds_read_b128<0>(a0[3], a_addr(3, 0, 0));
+    lds_read_b128<0>(b0[0], boff[0]); lds_read_b128<2048>(b0[1], boff[0]); lds_read_b128<4096>(b0[2], boff[0]); lds_read_b128<6144>(b0[3], boff[0]);
   }
   unsigned long long pc0 = 0, pw0 = 0; if constexpr (TAG == 1) { pc0 = __builtin_readcyclecounter(); pw0 = wall_clock64(); }
   typedef std::integral_constant<int, 0> I0; typedef std::integral_constant<int, 1> I1; typedef std::integral_constant<int, 2> I2; typedef std::integral_constant<int, 4> I4;
@@ -1879,8 +1711,8 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
       // of a new kernel row, whose dead blocks are others), otherwise of the live ones (a dead block's registers keep their old value, which no MFMA takes)
       auto half_op = [&](auto halfc, auto codec) {
         constexpr int HALF = decltype(halfc)::value, CODE = decltype(codec)::value, ARG = CODE & 3;
-        if constexpr (CODE < 4) { if constexpr (HALF == 0) AOCR_DSR(a1[ARG], a_addr(ARG, TAP, 1), 0); else AOCR_DSR(a0[ARG], a_addr(ARG, TN, 0), 0); }
-        else if constexpr (CODE < 8) { if constexpr (HALF == 0) AOCR_DSR(b1[ARG], boff[1] + bs1, ARG * 2048); else AOCR_DSR(b0[ARG], boff[0] + bs0n, ARG * 2048); }
+        if constexpr (CODE < 4) { if constexpr (HALF == 0) lds_read_b128<0>(a1[ARG], a_addr(ARG, TAP, 1)); else lds_read_b128<0>(a0[ARG], a_addr(ARG, TN, 0)); }
+        else if constexpr (CODE < 8) { if constexpr (HALF == 0) lds_read_b128<ARG * 2048>(b1[ARG], boff[1] + bs1); else lds_read_b128<ARG * 2048>(b0[ARG], boff[0] + bs0n); }
         else if constexpr (CODE < 12) issue_b1(step + 3, k3, 2 * HALF + ARG);
         else issue_halo_i(2 * TAP + HALF, chn, hbn);
       };
@@ -1911,8 +1743,8 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
         for (int ni = 0; ni < 4; ++ni) {
           acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0[mi], b0[ni], acc[mi][ni], 0, 0, 0);
           AOCR_SB();
-          if (ni == 0) AOCR_DSR(a1[mi], a_addr(mi, TAP, 1), 0);
-          if (ni == 2) { if (mi == 0) AOCR_DSR(b1[0], boff[1] + bs1, 0); else if (mi == 1) AOCR_DSR(b1[1], boff[1] + bs1, 2048); else if (mi == 2) AOCR_DSR(b1[2], boff[1] + bs1, 4096); else AOCR_DSR(b1[3], boff[1] + bs1, 6144); }
+          if (ni == 0) lds_read_b128<0>(a1[mi], a_addr(mi, TAP, 1));
+          if (ni == 2) { if (mi == 0) lds_read_b128<0>(b1[0], boff[1] + bs1); else if (mi == 1) lds_read_b128<2048>(b1[1], boff[1] + bs1); else if (mi == 2) lds_read_b128<4096>(b1[2], boff[1] + bs1); else lds_read_b128<6144>(b1[3], boff[1] + bs1); }
           if (ni == 3 && mi < 2) issue_b1(step + 3, k3, mi);
           if (ni == 3 && mi == 2 && HT) issue_halo_i(2 * TAP, chn, hbn);
           AOCR_SB();
@@ -1934,8 +1766,8 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
         for (int ni = 0; ni < 4; ++ni) {
           acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[mi], b1[ni], acc[mi][ni], 0, 0, 0);
           AOCR_SB();
-          if (ni == 0) AOCR_DSR(a0[mi], a_addr(mi, TN, 0), 0);
-          if (ni == 2) { if (mi == 0) AOCR_DSR(b0[0], boff[0] + bs0n, 0); else if (mi == 1) AOCR_DSR(b0[1], boff[0] + bs0n, 2048); else if (mi == 2) AOCR_DSR(b0[2], boff[0] + bs0n, 4096); else AOCR_DSR(b0[3], boff[0] + bs0n, 6144); }
+          if (ni == 0) lds_read_b128<0>(a0[mi], a_addr(mi, TN, 0));
+          if (ni == 2) { if (mi == 0) lds_read_b128<0>(b0[0], boff[0] + bs0n); else if (mi == 1) lds_read_b128<2048>(b0[1], boff[0] + bs0n); else if (mi == 2) lds_read_b128<4096>(b0[2], boff[0] + bs0n); else lds_read_b128<6144>(b0[3], boff[0] + bs0n); }
           if (ni == 3 && mi < 2) issue_b1(step + 3, k3, 2 + mi);
           if (ni == 3 && mi == 2 && HT) issue_halo_i(2 * TAP + 1, chn, hbn);
           AOCR_SB();
@@ -1963,7 +1795,6 @@ void gemm_halo4_bf16_kernel(LoadConvKh a, LoadKh b, EP ep, int gx, int gy, const
     else if (ntop == 1) kloop(I1{}, I0{});                // (no such shape: skip what one form covers; fewer skipped blocks are always correct)
     else kloop(I0{}, I0{});
   } else kloop(I0{}, I0{});
-#undef AOCR_DSR
 #undef AOCR_SB
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // the trailing (zero-page) pieces and reads must land before the LDS is released
   // the last half-step's reads of "the next step" are never consumed: keep their destination registers allocated up to here, or the compiler
@@ -2006,9 +1837,7 @@ __global__ __launch_bounds__(512, 2)
 void gemm_dma_narrow_kernel(AL a, BL b, EP ep, int K, int gx, int gy, const bf16_t* zero, int staged) {
   constexpr int BN = 64 * NT, SLOT = 16384 + BN * 64;
   __shared__ __attribute__((aligned(1024))) unsigned char lds[3 * SLOT];             // the ONLY LDS object
-  const int nwg = gx * gy, orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-  const int bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int bid = xcd_major_id(gx * gy, blockIdx.x);
   const int m_blk = (bid / gx) * 256, n_blk = (bid % gx) * BN;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5, wm = wave >> 1, wn = wave & 1;
@@ -2033,12 +1862,7 @@ void gemm_dma_narrow_kernel(AL a, BL b, EP ep, int K, int gx, int gy, const bf16
   };
 
   f32x16 acc[2][NT];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  acc_zero(acc);
 
   const int swz = (r >> 2) & 3;
   unsigned aoff[2], boff[2];
@@ -2078,17 +1902,7 @@ void gemm_dma_narrow_kernel(AL a, BL b, EP ep, int K, int gx, int gy, const bf16
     if (staged && narrow_store_staged<NT, EP>(ep, acc, lds, m_blk, n_blk, wm, wn, r, h, tid)) return;
   }
   const int m0 = m_blk + wm * 64, n0 = n_blk + wn * 32 * NT;
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float v[NT][4];
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[ni][i] = acc[mi][ni][4 * q + i];
-      ep.template quad<NT>(m0 + 32 * mi + 8 * q + 4 * h, n0 + r, 32, v);
-    }
+  store_quads<NT>(ep, acc, m0, n0, r, h);
 }
 
 // ---------------------------------------------------------------------------
@@ -2108,9 +1922,7 @@ void gemm_dma128_kernel(AL a, BL b, EP ep, int K, int gx, int gy, const bf16_t* 
   // 32 lines 74 us); two waves per SIMD issue half the pieces each and multiply under each other's issue stalls.
   constexpr int SLOT = 16384, NI = NW == 4 ? 2 : 1, PPW = 16 / NW;      // N tiles per wave; DMA pieces per wave, tile and operand... (A and B: 8 pieces each)
   __shared__ __attribute__((aligned(1024))) unsigned char lds[NS * SLOT];            // the ONLY LDS object
-  const int nwg = gx * gy, orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-  const int bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int bid = xcd_major_id(gx * gy, blockIdx.x);
   const int m_blk = (bid / gx) * 128, n_blk = (bid % gx) * 128;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5, wm = NW == 4 ? wave >> 1 : wave >> 2, wn = NW == 4 ? wave & 1 : wave & 3;
@@ -2137,12 +1949,7 @@ void gemm_dma128_kernel(AL a, BL b, EP ep, int K, int gx, int gy, const bf16_t* 
   (void)PPW;
 
   f32x16 acc[2][NI];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  acc_zero(acc);
 
   const int swz = (r >> 2) & 3;
   unsigned aoff[2], boff[2];
@@ -2179,17 +1986,7 @@ void gemm_dma128_kernel(AL a, BL b, EP ep, int K, int gx, int gy, const bf16_t* 
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the trailing (zero-page) tiles must land before the LDS is released
   const int m0 = m_blk + wm * 64, n0 = n_blk + wn * 32 * NI;
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float v[NI][4];
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[ni][i] = acc[mi][ni][4 * q + i];
-      ep.template quad<NI>(m0 + 32 * mi + 8 * q + 4 * h, n0 + r, 32, v);
-    }
+  store_quads<NI>(ep, acc, m0, n0, r, h);
 }
 
 // ---------------------------------------------------------------------------
@@ -2237,12 +2034,7 @@ __device__ __forceinline__ void tr_tile(const LoadMNh& a, const BL& b, const EP&
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  acc_zero(acc);
 
   // transposed-read addressing: lane = 16g + 4q + p supplies row (.. + q), columns 16*(g&1) + 4p .. +3 of its 32-channel tile
   const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
@@ -2278,30 +2070,83 @@ __device__ __forceinline__ void tr_tile(const LoadMNh& a, const BL& b, const EP&
   }
   const int r = lane & 31;
   const int m0 = m_blk + wm * 64, n0 = n_blk + wn * 64;
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int qq = 0; qq < 4; ++qq) {
-      float v[2][4];
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[ni][i] = acc[mi][ni][4 * qq + i];
-      ep.template quad<2>(m0 + 32 * mi + 8 * qq + 4 * h, n0 + r, 32, v);
-    }
+  store_quads<2>(ep, acc, m0, n0, r, h);
 }
 
 template <class EP>
 __global__ __launch_bounds__(256, 4) void conv_wgrad_tr_kernel(LoadMNh a, LoadConvXcolh b, EP ep, int K, int kper, int gx, int gy, int gz, float* part, long long pstride) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[2][2][32 * TR_PITCH];
-  const int nwg = gx * gy * gz, orig = blockIdx.x;                    // flat k-range-major order, see conv_wgrad_dma_kernel
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-  const int lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int lin = xcd_major_id(gx * gy * gz, blockIdx.x);                    // flat k-range-major order, see conv_wgrad_dma_kernel
   const int zsp = lin / (gx * gy), bid = lin - zsp * (gx * gy);
   const int kbeg = zsp * kper;
   if (part) { ep.C = part + (size_t)zsp * pstride; ep.flags &= ~8 /* EP_ATOMIC (epilogues.h) */; }     // split-K slab of this k range: plain stores, summed by splitk_reduce
   tr_tile(a, b, ep, (bid / gx) * 128, (bid % gx) * 128, kbeg, min(K, kbeg + kper), lds);
 }
+
+// ---------------------------------------------------------------------------
+// The K loop that both LDS-DMA filter-gradient kernels (conv_wgrad_dma_kernel, wgrad_dma_grouped_kernel) run, once: a wave's 4 x 2 accumulator tiles `acc` (wave-row
+// wm, wave-column wn) over nk tiles of 32 k on the 4-slot ring at LDS byte address lbase (slot: A image [32 k][256] bf16 | B image at + 16 KB); issue() puts this wave's
+// four DMA pieces of the next tile (the zero page past the end of K) into the next slot; three tiles are issued ahead, tile kt+3 goes into the slot of tile kt-1.
+// Uses the caller's lane, h, wm, wn, nk, lbase, issue and acc.  ABL_: timing-only ablations (tools/ubench/wgrad_dma.hip): 1 no in-loop DMA, 2 no MFMA, 4 no fragment reads.
+//   vmcnt(8): this wave's pieces of tile kt have landed (two later tiles in flight); the barrier: everyone's have, and everyone is done reading tile kt-1.
+//   Transposed-read addressing (cf. tr_tile): lane = 16g + 4q + p supplies pixel row (.. + q), channels 16 (g&1) + 4p .. +3; fa / fb = [k half][tile][low / high four k].
+//   The transposed reads are inline asm with a hand-placed lgkmcnt wait: behind the builtin (__builtin_amdgcn_ds_read_tr16_b64) hipcc put `s_waitcnt vmcnt(0)` in
+//   front of the first read of every step -- it orders LDS reads behind ALL pending LDS-DMA -- which drained the two tiles in flight, i.e. every step paid a full DMA
+//   round trip (found in the ISA; the kernel ran 1.37 us per step against 1.04 for the forward kernel).  The wait asm takes the fragments as in/out operands so that
+//   no MFMA moves above it.
+// A macro, not a function: as a __forceinline__ function template (issue by reference or by value, the ring by address or by pointer) the same text made hipcc unroll
+// the staged epilogue behind it (6 instead of 4 barriers in both kernels) and gave conv_wgrad_dma_kernel<EpStore> 256 VGPRs and 8 bytes of scratch.
+// ---------------------------------------------------------------------------
+#define AOCR_WGRAD_DMA_KLOOP(ABL_) \
+  const int trg = lane >> 4, q = (lane >> 2) & 3, p4 = lane & 3; \
+  const unsigned rowoff = (8 * h + q) * 512 + (16 * (trg & 1) + 4 * p4) * 2; \
+  unsigned aseg[4], bseg[2]; \
+  _Pragma("unroll") \
+  for (int i = 0; i < 4; ++i) aseg[i] = rowoff + (((wm * 4 + i) ^ q) << 6); \
+  _Pragma("unroll") \
+  for (int i = 0; i < 2; ++i) bseg[i] = 16384 + rowoff + (((wn * 2 + i) ^ q) << 6); \
+  typedef unsigned long long u64; \
+  typedef u64 u64x2 __attribute__((ext_vector_type(2))); \
+  _Pragma("unroll") \
+  for (int t = 0; t < 3; ++t) issue(); \
+  for (int kt = 0; kt < nk; ++kt) { \
+    asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); \
+    __builtin_amdgcn_s_barrier(); \
+    const unsigned sl = lbase + (kt & 3) * 32768; \
+    u64 fa[2][4][2], fb[2][2][2]; \
+  _Pragma("unroll") \
+    for (int i = 0; i < 4; ++i) { \
+      const unsigned ad = sl + aseg[i]; \
+      if constexpr (ABL_ & 4) { fa[0][i][0] = fa[0][i][1] = fa[1][i][0] = fa[1][i][1] = ad; continue; } \
+      lds_read_tr_b64<0>(fa[0][i][0], ad); lds_read_tr_b64<2048>(fa[0][i][1], ad); lds_read_tr_b64<8192>(fa[1][i][0], ad); lds_read_tr_b64<10240>(fa[1][i][1], ad); \
+    } \
+  _Pragma("unroll") \
+    for (int i = 0; i < 2; ++i) { \
+      const unsigned ad = sl + bseg[i]; \
+      if constexpr (ABL_ & 4) { fb[0][i][0] = fb[0][i][1] = fb[1][i][0] = fb[1][i][1] = ad; continue; } \
+      lds_read_tr_b64<0>(fb[0][i][0], ad); lds_read_tr_b64<2048>(fb[0][i][1], ad); lds_read_tr_b64<8192>(fb[1][i][0], ad); lds_read_tr_b64<10240>(fb[1][i][1], ad); \
+    } \
+    if constexpr (!(ABL_ & 1)) issue(); \
+    asm volatile("s_waitcnt lgkmcnt(0)" \
+                 : "+v"(fa[0][0][0]), "+v"(fa[0][0][1]), "+v"(fa[0][1][0]), "+v"(fa[0][1][1]), "+v"(fa[0][2][0]), "+v"(fa[0][2][1]), \
+                   "+v"(fa[0][3][0]), "+v"(fa[0][3][1]), "+v"(fb[0][0][0]), "+v"(fb[0][0][1]), "+v"(fb[0][1][0]), "+v"(fb[0][1][1]) \
+                 :: "memory"); \
+    asm volatile("" \
+                 : "+v"(fa[1][0][0]), "+v"(fa[1][0][1]), "+v"(fa[1][1][0]), "+v"(fa[1][1][1]), "+v"(fa[1][2][0]), "+v"(fa[1][2][1]), \
+                   "+v"(fa[1][3][0]), "+v"(fa[1][3][1]), "+v"(fb[1][0][0]), "+v"(fb[1][0][1]), "+v"(fb[1][1][0]), "+v"(fb[1][1][1]) \
+                 :: "memory"); \
+  _Pragma("unroll") \
+    for (int s2 = 0; s2 < 2; ++s2) \
+  _Pragma("unroll") \
+      for (int mi = 0; mi < 4; ++mi) \
+  _Pragma("unroll") \
+        for (int ni = 0; ni < 2; ++ni) { \
+          const u64x2 av = {fa[s2][mi][0], fa[s2][mi][1]}, bv = {fb[s2][ni][0], fb[s2][ni][1]}; \
+          if constexpr (ABL_ & 2) { acc[mi][ni][0] += (float)(unsigned)(av[0] ^ bv[1]); continue; } \
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, bv), acc[mi][ni], 0, 0, 0); \
+        } \
+  } \
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 
 // ---------------------------------------------------------------------------
 // Filter gradient on the LDS-DMA skeleton of gemm_dma_bf16_kernel: 256 (Cout) x 256 (tap, ci) tiles, 8 waves, K = output
@@ -2312,7 +2157,7 @@ __global__ __launch_bounds__(256, 4) void conv_wgrad_tr_kernel(LoadMNh a, LoadCo
 // pixel rows one transposed read touches then sit in four different quarters of the 256-byte bank row.
 // The im2col operand's piece addresses are per lane: (tap, ci) is a lane constant, the pixel cursor advances by 32.
 // ---------------------------------------------------------------------------
-template <class EP, int ABL = 0>                        // ABL: timing-only ablations (tools/ubench/wgrad_dma.hip): 1 no in-loop DMA, 2 no MFMA, 4 no fragment reads, 16 / 128 d y / x pieces from the zero page
+template <class EP, int ABL = 0, int TAG = 0>           // ABL: timing-only ablations (tools/ubench/wgrad_dma.hip): 1 no in-loop DMA, 2 no MFMA, 4 no fragment reads, 16 / 128 d y / x pieces from the zero page; TAG: distinct symbol for aocr_profile_kernel's launch
 __global__ __launch_bounds__(512, 1) void conv_wgrad_dma_kernel(LoadMNh a, LoadConvXcolh b, EP ep, int K, int kper, int gx, int gy, const bf16_t* zero, int gz, float* part, long long pstride) {
   __shared__ __attribute__((aligned(1024))) unsigned char lds[4 * 32768];          // the ONLY LDS object
   // (Round 1 gave every XCD its own K range with 36 tiles on its 32 CUs, i.e. two rounds: 1.5-2.5x slower.)
@@ -2320,9 +2165,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_dma_kernel(LoadMNh a, LoadC
   // XCD's co-resident workgroups then share one (at most two) pixel ranges, so its L2 fetches d y and x of that range once for all
   // their tiles (before, with the k range on blockIdx.z, every XCD saw every range: 56 % L2 misses, 917 MB of fills per launch).
   // Worth 1 % on this kernel and 8 % on conv_wgrad_tr_kernel -- neither is bound by those misses.
-  const int nwg = gx * gy * gz, orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-  const int lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int lin = xcd_major_id(gx * gy * gz, blockIdx.x);
   const int zsp = lin / (gx * gy), bid = lin - zsp * (gx * gy);
   const int m_blk = (bid / gx) * 256, n_blk = (bid % gx) * 256;
   const int kbeg = zsp * kper, kend = min(K, kbeg + kper);
@@ -2368,71 +2211,10 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_dma_kernel(LoadMNh a, LoadC
   };
 
   f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  acc_zero(acc);
 
-  // transposed-read addressing (cf. tr_tile): lane = 16g + 4q + p supplies pixel row (.. + q), channels 16 (g&1) + 4p .. +3
-  const int g = lane >> 4, q = (lane >> 2) & 3, p4 = lane & 3;
-  const unsigned rowoff = (8 * h + q) * 512 + (16 * (g & 1) + 4 * p4) * 2;
-  unsigned aseg[4], bseg[2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) aseg[i] = rowoff + (((wm * 4 + i) ^ q) << 6);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) bseg[i] = 16384 + rowoff + (((wn * 2 + i) ^ q) << 6);
-
-  // The transposed reads are inline asm with a hand-placed lgkmcnt wait: behind the builtin (__builtin_amdgcn_ds_read_tr16_b64) hipcc
-  // put `s_waitcnt vmcnt(0)` in front of the first read of every step -- it orders LDS reads behind ALL pending LDS-DMA -- which
-  // drained the two tiles in flight, i.e. every step paid a full DMA round trip (found in the ISA; the kernel ran 1.37 us per
-  // step against 1.04 for the forward kernel).  The wait asm takes the fragments as in/out operands so that no MFMA moves above it.
-  typedef unsigned long long u64;
-  typedef u64 u64x2 __attribute__((ext_vector_type(2)));
   const unsigned lbase = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned char*)lds);
-#define AOCR_TRR(dst, addr, OFF) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #OFF : "=v"(dst) : "v"(addr))
-#pragma unroll
-  for (int t = 0; t < 3; ++t) issue();
-  for (int kt = 0; kt < nk; ++kt) {
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");    // this wave's pieces of tile kt have landed (two later tiles in flight)
-    __builtin_amdgcn_s_barrier();                       // ... everyone's have, and everyone is done reading tile kt-1
-    const unsigned sl = lbase + (kt & 3) * 32768;
-    u64 fa[2][4][2], fb[2][2][2];                       // [k half][tile][low / high four k]
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const unsigned ad = sl + aseg[i];
-      if constexpr (ABL & 4) { fa[0][i][0] = fa[0][i][1] = fa[1][i][0] = fa[1][i][1] = ad; continue; }
-      AOCR_TRR(fa[0][i][0], ad, 0); AOCR_TRR(fa[0][i][1], ad, 2048); AOCR_TRR(fa[1][i][0], ad, 8192); AOCR_TRR(fa[1][i][1], ad, 10240);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const unsigned ad = sl + bseg[i];
-      if constexpr (ABL & 4) { fb[0][i][0] = fb[0][i][1] = fb[1][i][0] = fb[1][i][1] = ad; continue; }
-      AOCR_TRR(fb[0][i][0], ad, 0); AOCR_TRR(fb[0][i][1], ad, 2048); AOCR_TRR(fb[1][i][0], ad, 8192); AOCR_TRR(fb[1][i][1], ad, 10240);
-    }
-    if constexpr (!(ABL & 1)) issue();                  // tile kt+3 -> the slot of tile kt-1
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(fa[0][0][0]), "+v"(fa[0][0][1]), "+v"(fa[0][1][0]), "+v"(fa[0][1][1]), "+v"(fa[0][2][0]), "+v"(fa[0][2][1]),
-                   "+v"(fa[0][3][0]), "+v"(fa[0][3][1]), "+v"(fb[0][0][0]), "+v"(fb[0][0][1]), "+v"(fb[0][1][0]), "+v"(fb[0][1][1])
-                 :: "memory");
-    asm volatile(""
-                 : "+v"(fa[1][0][0]), "+v"(fa[1][0][1]), "+v"(fa[1][1][0]), "+v"(fa[1][1][1]), "+v"(fa[1][2][0]), "+v"(fa[1][2][1]),
-                   "+v"(fa[1][3][0]), "+v"(fa[1][3][1]), "+v"(fb[1][0][0]), "+v"(fb[1][0][1]), "+v"(fb[1][1][0]), "+v"(fb[1][1][1])
-                 :: "memory");
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          const u64x2 av = {fa[s2][mi][0], fa[s2][mi][1]}, bv = {fb[s2][ni][0], fb[s2][ni][1]};
-          if constexpr (ABL & 2) { acc[mi][ni][0] += (float)(unsigned)(av[0] ^ bv[1]); continue; }
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, bv), acc[mi][ni], 0, 0, 0);
-        }
-  }
-#undef AOCR_TRR
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  AOCR_WGRAD_DMA_KLOOP(ABL)
   const int r = lane & 31;
   const int m0 = m_blk + wm * 128, n0 = n_blk + wn * 64;
   if constexpr (std::is_same<EP, EpStore>::value && ABL == 0) {
@@ -2443,17 +2225,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_dma_kernel(LoadMNh a, LoadC
       return;
     }
   }
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int qq = 0; qq < 4; ++qq) {
-      float v[2][4];
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[ni][i] = acc[mi][ni][4 * qq + i];
-      ep.template quad<2>(m0 + 32 * mi + 8 * qq + 4 * h, n0 + r, 32, v);
-    }
+  store_quads<2>(ep, acc, m0, n0, r, h);
 }
 
 // ---------------------------------------------------------------------------
@@ -2502,63 +2274,12 @@ __global__ __launch_bounds__(512, 1) void wgrad_dma_grouped_kernel(WgDmaArgs g, 
     slot = (slot + 1) & 3;
   };
   f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  const int gq = lane >> 4, q = (lane >> 2) & 3, p4 = lane & 3;
-  const unsigned rowoff = (8 * h + q) * 512 + (16 * (gq & 1) + 4 * p4) * 2;
-  unsigned aseg[4], bseg[2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) aseg[i] = rowoff + (((wm * 4 + i) ^ q) << 6);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) bseg[i] = 16384 + rowoff + (((wn * 2 + i) ^ q) << 6);
-  typedef unsigned long long u64;
-  typedef u64 u64x2 __attribute__((ext_vector_type(2)));
+  acc_zero(acc);
   const unsigned lbase = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned char*)lds);
-#define AOCR_TRR(dst, addr, OFF) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #OFF : "=v"(dst) : "v"(addr))
-#pragma unroll
-  for (int t = 0; t < 3; ++t) issue();
-  for (int kt = 0; kt < nk; ++kt) {
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");    // this wave's pieces of tile kt have landed (two later tiles in flight)
-    __builtin_amdgcn_s_barrier();
-    const unsigned sl = lbase + (kt & 3) * 32768;
-    u64 fa[2][4][2], fb[2][2][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const unsigned ad = sl + aseg[i];
-      AOCR_TRR(fa[0][i][0], ad, 0); AOCR_TRR(fa[0][i][1], ad, 2048); AOCR_TRR(fa[1][i][0], ad, 8192); AOCR_TRR(fa[1][i][1], ad, 10240);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const unsigned ad = sl + bseg[i];
-      AOCR_TRR(fb[0][i][0], ad, 0); AOCR_TRR(fb[0][i][1], ad, 2048); AOCR_TRR(fb[1][i][0], ad, 8192); AOCR_TRR(fb[1][i][1], ad, 10240);
-    }
-    issue();                                            // tile kt+3 -> the slot of tile kt-1
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(fa[0][0][0]), "+v"(fa[0][0][1]), "+v"(fa[0][1][0]), "+v"(fa[0][1][1]), "+v"(fa[0][2][0]), "+v"(fa[0][2][1]),
-                   "+v"(fa[0][3][0]), "+v"(fa[0][3][1]), "+v"(fb[0][0][0]), "+v"(fb[0][0][1]), "+v"(fb[0][1][0]), "+v"(fb[0][1][1])
-                 :: "memory");
-    asm volatile(""
-                 : "+v"(fa[1][0][0]), "+v"(fa[1][0][1]), "+v"(fa[1][1][0]), "+v"(fa[1][1][1]), "+v"(fa[1][2][0]), "+v"(fa[1][2][1]),
-                   "+v"(fa[1][3][0]), "+v"(fa[1][3][1]), "+v"(fb[1][0][0]), "+v"(fb[1][0][1]), "+v"(fb[1][1][0]), "+v"(fb[1][1][1])
-                 :: "memory");
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          const u64x2 av = {fa[s2][mi][0], fa[s2][mi][1]}, bv = {fb[s2][ni][0], fb[s2][ni][1]};
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, bv), acc[mi][ni], 0, 0, 0);
-        }
-  }
-#undef AOCR_TRR
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  AOCR_WGRAD_DMA_KLOOP(0)
   tile256_store_f32<2, 512>(P.part + (size_t)zsp * P.M * P.N, P.N, nullptr, false, acc, lds, m_blk, n_blk, wm, wn, lane & 31, h, tid);
 }
+#undef AOCR_WGRAD_DMA_KLOOP
 // C[m][n] (row stride ldc) += sum over the k ranges of the problem's slabs; one launch for all problems of a group (float4 items)
 template <int UNUSED = 0>
 __global__ __launch_bounds__(256) void wgrad_slab_reduce_kernel(WgDmaArgs g) {
@@ -2613,9 +2334,7 @@ void conv_wgrad_halo_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restr
   constexpr int MT = 64 * MG, NWV = 2 * MG, AROW = MT * 2, RPP = 1024 / AROW, LPR = 64 / RPP;   // tile rows (output channels), waves, bytes per pixel row of the d y image, pixel rows / lanes per row of a 1 KB piece
   constexpr int BOFF = 32 * AROW, SLOT = BOFF + 8192, NS = 6, PW = 34, HPW = 8 / NWV;          // halo pieces per wave
   __shared__ __attribute__((aligned(1024))) unsigned char lds[NWV * 20480 > NS * SLOT ? NWV * 20480 : NS * SLOT];   // the ONLY LDS object: ring of NS slots; epilogue: NWV waves x 32 rows x 160 fp32
-  const int nwg = gx * gy * gz, orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-  const int lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int lin = xcd_major_id(gx * gy * gz, blockIdx.x);
   const int zsp = lin / (gx * gy), bid = lin - zsp * (gx * gy);
   const int m_blk = (bid / gx) * MT, cchunk = bid % gx;                            // MT output channels x input channels [32 cchunk, +32)
   const int spr = (W + 31) >> 5, S = nimg * H * spr;                               // segments per row (round 6: the last one of a row may be ragged -- pixel slots past W are zero), in all
@@ -2691,18 +2410,12 @@ void conv_wgrad_halo_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restr
   const int r = lane & 31;
   float* const slab = part + (size_t)zsp * pstride;
   const int64_t ldw = (int64_t)9 * Cin;
-#define AOCR_TRH(dst, addr, OFF) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF))
 
   issue(); issue(); issue();
   auto body = [&](auto tgc) {                           // TG = 0: taps 0 .. 4, TG = 1: taps 5 .. 8
     constexpr int TG = decltype(tgc)::value, T0 = TG ? 5 : 0, NTP = TG ? 4 : 5;
     f32x16 acc[2][NTP];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < NTP; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    acc_zero(acc);
     int rslot = 0;
     for (int kt = 0; kt < nk; ++kt) {
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (2 + HPW)) : "memory");  // this wave's pieces of segment kt have landed (two later segments in flight)
@@ -2711,10 +2424,10 @@ void conv_wgrad_halo_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restr
       rslot = rslot == NS - 1 ? 0 : rslot + 1;
       u64 fa[2][2][2], fb[2][NTP][2];                   // [k half][tile / tap][low / high four k]
       const unsigned a0 = aseg0 + so, a1 = aseg1 + so, bd = brd + so;
-      AOCR_TRH(fa[0][0][0], a0, 0); AOCR_TRH(fa[0][0][1], a0, 4 * AROW); AOCR_TRH(fa[0][1][0], a1, 0); AOCR_TRH(fa[0][1][1], a1, 4 * AROW);
-#define AOCR_TAPH(S2, T) do { AOCR_TRH(fb[S2][T][0], bd, (((T0 + T) / 3) * PW + (T0 + T) % 3) * 64 + S2 * 1024); AOCR_TRH(fb[S2][T][1], bd, (((T0 + T) / 3) * PW + (T0 + T) % 3) * 64 + S2 * 1024 + 256); } while (0)
+      lds_read_tr_b64<0>(fa[0][0][0], a0); lds_read_tr_b64<4 * AROW>(fa[0][0][1], a0); lds_read_tr_b64<0>(fa[0][1][0], a1); lds_read_tr_b64<4 * AROW>(fa[0][1][1], a1);
+#define AOCR_TAPH(S2, T) do { lds_read_tr_b64<(((T0 + T) / 3) * PW + (T0 + T) % 3) * 64 + S2 * 1024>(fb[S2][T][0], bd); lds_read_tr_b64<(((T0 + T) / 3) * PW + (T0 + T) % 3) * 64 + S2 * 1024 + 256>(fb[S2][T][1], bd); } while (0)
       AOCR_TAPH(0, 0); AOCR_TAPH(0, 1); AOCR_TAPH(0, 2); AOCR_TAPH(0, 3); if constexpr (NTP == 5) AOCR_TAPH(0, NTP - 1);
-      AOCR_TRH(fa[1][0][0], a0, 16 * AROW); AOCR_TRH(fa[1][0][1], a0, 20 * AROW); AOCR_TRH(fa[1][1][0], a1, 16 * AROW); AOCR_TRH(fa[1][1][1], a1, 20 * AROW);
+      lds_read_tr_b64<16 * AROW>(fa[1][0][0], a0); lds_read_tr_b64<20 * AROW>(fa[1][0][1], a0); lds_read_tr_b64<16 * AROW>(fa[1][1][0], a1); lds_read_tr_b64<20 * AROW>(fa[1][1][1], a1);
       AOCR_TAPH(1, 0); AOCR_TAPH(1, 1); AOCR_TAPH(1, 2); AOCR_TAPH(1, 3); if constexpr (NTP == 5) AOCR_TAPH(1, NTP - 1);
 #undef AOCR_TAPH
       auto mma_half = [&](auto s2c) {
@@ -2782,7 +2495,6 @@ void conv_wgrad_halo_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restr
     }
   };
   if (tg == 0) body(std::integral_constant<int, 0>{}); else body(std::integral_constant<int, 1>{});
-#undef AOCR_TRH
 }
 
 // Grouped form: up to 8 independent contractions of the same operand kinds in ONE launch (the hoisted weight gradients
@@ -2842,10 +2554,7 @@ __device__ __forceinline__ void gemm_small_body(const SmallArgs<AL, BL, EP>& g, 
   for (int i = 0; i < NT; ++i) cb[i] = g.b.row(QG ? (r >> 3) * gate_stride + n0 + (r & 7) : (GATES ? i * gate_stride + n0 + r : n0 + 32 * i + r));
 
   f32x16 acc[1][NT];
-#pragma unroll
-  for (int j = 0; j < NT; ++j)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[0][j][e] = 0.f;
+  acc_zero(acc);
 
   typedef typename FragOf<AL, NV>::type FA; typedef typename FragOf<BL, NV>::type FB;
   // The step kernels are latency-bound (one workgroup per CU, a serial chain of L2 round trips), so each wave keeps
@@ -3018,12 +2727,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_step_kernel(SmallArgs2<AL, LoadK
   const int brow0 = n0 + br;                                  // N % 32 == 0 so always valid
 
   f32x16 acc[MT][NT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[mt][j][e] = 0.f;
+  acc_zero(acc);
 
   // the epilogue's own operands (zx, c_prev, gates, ...) are requested now so that they arrive during the K loop
   // accumulator index i = E*wave + e of a 32x32 tile sits in row 8*(i/4) + 4h + i%4

@@ -97,7 +97,7 @@ static void launch_dma(hipStream_t s, const AL& a, const BL& b, const EP& ep, in
   const int gx = N / 256, gy = cdiv(M, 256);
   const int opt = knob::AOCR_HALO4_STAGED();                 // the same switch as the halo kernel's: output tiles through LDS
   trace_launch("gemm_dma_bf16_kernel", tag ? "tag" : "", M, N, K);
-  if (tag) hipLaunchKernelGGL((gemm_dma_bf16_kernel<AL, BL, EP, 0, false, false, 1>), dim3(gx * gy), dim3(512), 0, s, a, b, ep, K, gx, gy, zero_page(), opt);
+  if (tag) hipLaunchKernelGGL((gemm_dma_bf16_kernel<AL, BL, EP, 0, 1>), dim3(gx * gy), dim3(512), 0, s, a, b, ep, K, gx, gy, zero_page(), opt);
   else hipLaunchKernelGGL((gemm_dma_bf16_kernel<AL, BL, EP>), dim3(gx * gy), dim3(512), 0, s, a, b, ep, K, gx, gy, zero_page(), opt);
 }
 // halo-resident 3 x 3 kernel (gemm_halo_bf16_kernel): the tile must be MT / W whole rows of one image
@@ -918,8 +918,8 @@ void conv_backward_filter(hipStream_t s, bool bf16, const float* x, const float*
       const size_t mn = (size_t)Cout * N;
       float* const slab = (part && ks2 > 1 && mn * ks2 <= part_floats && !knob::AOCR_WGRAD_ATOMIC()) ? part : nullptr;
       trace_launch("conv_wgrad_dma_kernel", slab ? "slab" : "atomic", Cout, N, P);
-      if (profile_tag)        // the same kernel under its own symbol (ABL bit 256 selects nothing): aocr_profile_kernel, per-kernel rocprofv3 / PMC rows
-        hipLaunchKernelGGL((conv_wgrad_dma_kernel<EpStore, 256>), dim3(tiles * ks2), dim3(512), 0, s, ah, bh, ep, P, kper2, cdiv(N, 256), Cout / 256, zero_page(), ks2, slab, (long long)mn);
+      if (profile_tag)        // the same kernel under its own symbol (TAG 1): aocr_profile_kernel, per-kernel rocprofv3 / PMC rows
+        hipLaunchKernelGGL((conv_wgrad_dma_kernel<EpStore, 0, 1>), dim3(tiles * ks2), dim3(512), 0, s, ah, bh, ep, P, kper2, cdiv(N, 256), Cout / 256, zero_page(), ks2, slab, (long long)mn);
       else
         hipLaunchKernelGGL((conv_wgrad_dma_kernel<EpStore>), dim3(tiles * ks2), dim3(512), 0, s, ah, bh, ep, P, kper2, cdiv(N, 256), Cout / 256, zero_page(), ks2, slab, (long long)mn);
       if (slab) splitk_reduce(s, slab, ks2, mn, dw);
