@@ -725,6 +725,51 @@ size_t aocr_flatten_scratch_bytes(int32_t H, int32_t W, int32_t radius);
 int aocr_flatten_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
                       const aocr_flatten_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch);
 
+/* ---- local adaptive binarisation: a threshold per pixel (Sauvola and Pietikainen), behind aocr_flatten_page and in front of every stage that
+ * separates ink from paper ----------------------------------------------------------------------------------------------------------------
+ * Every other page stage separates ink from paper with ONE threshold, fixed or Otsu's.  Faded print beside strong print, stains and foxing,
+ * show-through and carbon copies have no such threshold, even on evenly lit paper: where a stain's paper (say 140) is darker than faded ink
+ * elsewhere (say 175), every global threshold loses one or swallows the other.  This call thresholds every pixel against the mean and the
+ * standard deviation of the window around it, and writes a page on which the fixed threshold 127 is that local decision.  Integer
+ * arithmetic only, specified exactly; every / is a floor division of non-negative integers.  The page and the output follow the rules of
+ * aocr_flatten_page: any base address, any pitch >= W, 1 <= H, W <= 16384, H*W <= 2^26; out_dev: H rows of W bytes, out_pitch >= W apart, any
+ * alignment; bytes between W and out_pitch are untouched; it must not overlap the page.
+ *   v          page[y][x], or 255 - page[y][x] with light_text: the paper is the bright side from here on;
+ *   window     of (x, y), r = radius: [max(x-r,0), min(x+r,W-1)] x [max(y-r,0), min(y+r,H-1)], clipped to the page, n pixels (n <= 127^2);
+ *   sums       S1 = the sum of v over the window, S2 = the sum of v*v;
+ *   deviation  D = n*S2 - S1*S1 (>= 0, < 2^43);  q = floor(sqrt(D)), the exact integer square root: q*q <= D < (q+1)*(q+1);
+ *   threshold  T = ( S1 * ((256 - k_q8)*range*n + k_q8*q) ) / (256*range*n*n): Sauvola's m*(1 + k*(s/R - 1)) with the mean m = S1/n, the
+ *              standard deviation s = q/n, k = k_q8/256 and R = range; the numerator is < 2^53;
+ *   decision   the pixel is ink when v <= T;
+ *   output     hard = 1: ink 0, paper 255.  hard = 0 (the recogniser reads gray crops, and this keeps the anti-aliasing):
+ *              ink out = (v*127) / max(T, 1), which is <= 127;  paper out = min(255, 128 + ((v - T - 1)*127) / max(254 - T, 1));
+ *              with light_text the byte written is 255 - out.
+ *   counts_dev [ink pixels, the smallest T, the largest T, 0] over the page (integer atomics: the order does not matter); may be NULL.
+ * Consequences: is_ink(out, 127, light_text) -- out <= 127, or out > 127 with light_text -- is the local decision at every pixel, in both
+ * modes, so every later stage run with the fixed threshold 127 sees exactly the Sauvola ink map.  A constant page c has q = 0 and
+ * T = (c*(256 - k_q8)) / 256 < c for c >= 1 and k_q8 >= 1: nothing on it is ink (c = 0: everything is).  k_q8 = 0: T is the floored local
+ * mean.  r larger than H or W is legal: the window is the whole page along that axis.
+ * Limits: a glyph stroke wider than the window is hollowed out (its inside has no contrast to its window); a sharp edge between paper and
+ * a stain darker than about 0.8 of it leaves a rim of ink just inside the stain (the window's mean there is well above the stain: an edge
+ * wider than the window leaves none); k and the radius are untuned defaults for 300 dpi; this handles local contrast and does not replace aocr_flatten_page for strong shading across the page: the two
+ * compose, flatten first.
+ * scratch_dev: aocr_binarize_scratch_bytes(H, W, radius) bytes, 16-byte aligned (0 and an error for bad sizes); the window sums live in
+ * registers and LDS, so the size is a small constant and the call leaves those bytes alone.  Enqueues only, never synchronises or allocates; the result does not
+ * depend on launch geometry or run (integer sums; the double sqrt and division are stepped to the exact integers).  Invalid params, sizes
+ * or overlap return an error before anything is enqueued and leave out_dev and counts_dev untouched. */
+typedef struct aocr_binarize_params {
+  int32_t radius;        /* r in 1..63: windows are (2r+1) x (2r+1), clipped to the page */
+  int32_t k_q8;          /* k*256, 0..255 (default 51: k = 0.2) */
+  int32_t range;         /* R, 1..255 (default 128): the dynamic range of the standard deviation */
+  int32_t light_text;    /* 1: light ink on dark paper (the page is inverted, binarised, inverted back) */
+  int32_t hard;          /* 0: gray output (above); 1: ink 0, paper 255 */
+  int32_t reserved[3];   /* must be 0 */
+} aocr_binarize_params;
+
+size_t aocr_binarize_scratch_bytes(int32_t H, int32_t W, int32_t radius);
+int aocr_binarize_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W,
+                       const aocr_binarize_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch, int32_t counts_dev[4]);
+
 /* ---- page layout: the blocks of a multi-column page, in reading order, in front of aocr_segment_page -------------------------------------
  * aocr_segment_page takes its row profiles across the whole width of the page: the lines of two columns fall into one band and their words
  * come back interleaved.  These two calls cut the page into blocks (headline, columns, paragraphs) by a recursive XY cut; every block is

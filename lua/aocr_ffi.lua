@@ -128,6 +128,9 @@ int aocr_clean_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_
 typedef struct aocr_rule_params { int32_t threshold; int32_t light_text; int32_t axes; int32_t min_len; int32_t max_thick; int32_t edge; int32_t reserved[2]; } aocr_rule_params;
 size_t aocr_rules_scratch_bytes(int32_t H, int32_t W);
 int aocr_remove_rules(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_rule_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch, int32_t counts_dev[8]);
+typedef struct aocr_binarize_params { int32_t radius; int32_t k_q8; int32_t range; int32_t light_text; int32_t hard; int32_t reserved[3]; } aocr_binarize_params;
+size_t aocr_binarize_scratch_bytes(int32_t H, int32_t W, int32_t radius);
+int aocr_binarize_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_binarize_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch, int32_t counts_dev[4]);
 typedef struct aocr_panel_params { int32_t threshold; int32_t light_text; int32_t connectivity; int32_t min_w, min_h; int32_t fill_percent; int32_t min_inside_percent; int32_t reserved; } aocr_panel_params;
 size_t aocr_panels_scratch_bytes(int32_t H, int32_t W, int32_t max_panels);
 int aocr_invert_panels(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_panel_params* params, void* scratch_dev, uint8_t* out_dev, int64_t out_pitch, int32_t max_panels, int32_t* panels_dev, int32_t counts_dev[8]);

@@ -104,6 +104,17 @@ class FlattenParams(C.Structure):
         super().__init__(int(radius), int(light_text), (C.c_int32 * 2)(0, 0))
 
 
+class BinarizeParams(C.Structure):
+    """mirror of `aocr_binarize_params` (include/aocr.h): the window radius, Sauvola's k (k_q8 / 256) and the dynamic range R of
+    `aocr_binarize_page`.  hard 0 writes a gray page on which the fixed threshold 127 is the local decision (ink 0..127, paper 128..255, the
+    anti-aliasing kept); hard 1 writes ink 0 and paper 255.  The window must be wider than a stroke (a wider stroke is hollowed out); the
+    defaults are a judgement for text at 300 dpi and nobody has tuned them on real scans."""
+    _fields_ = [(n, C.c_int32) for n in ("radius", "k_q8", "range", "light_text", "hard")] + [("reserved", C.c_int32 * 3)]
+
+    def __init__(self, radius=20, k_q8=51, range=128, light_text=0, hard=0):
+        super().__init__(int(radius), int(k_q8), int(range), int(light_text), int(hard), (C.c_int32 * 3)(0, 0, 0))
+
+
 class LayoutParams(C.Structure):
     """mirror of `aocr_layout_params` (include/aocr.h): the recursive XY cut of `aocr_layout_blocks`.  gap_x is what a gutter must exceed and a
     word gap must not; gap_y what a paragraph gap must exceed and a line gap must not."""
@@ -360,6 +371,8 @@ SIGNATURES = {
     "aocr_deskew_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _i32, _i32, _vp, C.c_int64]),
     "aocr_flatten_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
     "aocr_flatten_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, C.c_int64]),
+    "aocr_binarize_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),
+    "aocr_binarize_page": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _vp, _vp, _vp, C.c_int64, _vp]),
     "aocr_integral_scratch_bytes": (C.c_size_t, [_i32, _i32]),
     "aocr_ink_integral": (C.c_int, [_vp, _vp, C.c_int64, _i32, _i32, _i32, _i32, _vp, _vp, C.c_int64, _vp]),
     "aocr_layout_scratch_bytes": (C.c_size_t, [_i32, _i32, _i32]),

@@ -21,7 +21,7 @@ from . import _lib, dist
 from ._lib import Config, check, lib, ptr
 from .dictionary import edit_distance_device
 from .page import backmap_corners, bucket_width, crop_lines_device, crop_lines_slanted_device, rotate_page_device, slant_extent
-from .page_pipeline import asked, clean_stage, colour_stage, flatten_stage, orient_stage, page_boxes, panels_stage, paper, rectify_stage, scale_stage
+from .page_pipeline import asked, binarize_stage, binarized_params, clean_stage, colour_stage, flatten_stage, orient_stage, page_boxes, panels_stage, paper, rectify_stage, scale_stage
 
 PAD, GO, EOS = 1, 2, 3
 GROUPS = ["cnn", "enc_fw", "enc_bw", "dec", "proj"]
@@ -467,13 +467,14 @@ class Model:
         return res
 
     def _page_boxes(self, page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None, deslant=None, spacing=None, rules=None,
-                    panels_dev=None):
+                    panels_dev=None, binarize_dev=None):
         """the middle of recognize_page (aocr.page_pipeline.page_boxes), reached through the model so that a caller can wrap it."""
-        return page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev, deslant, spacing, rules, panels_dev)
+        return page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev, deslant, spacing, rules, panels_dev,
+                          binarize_dev)
 
     def recognize_page(self, page, params=None, width=None, width_step=32, beam_size=1, trie=None, lexicon=None, max_boxes=1024, deskew=None, flatten=None,
                        layout=None, clean=None, orient=None, rectify=None, scale=None, dewarp=None, colour=None, deslant=None, spacing=None,
-                       panels=None, rules=None):
+                       panels=None, binarize=None, rules=None):
         """Read a scanned page: segment it into word boxes (aocr_segment_page), crop them (aocr_crop_lines) and recognise the crops.
         page: a uint8 (H,W) numpy array or tensor (gray; a 3-D array raises ValueError unless `colour` is asked for: see below).  params: an
         `aocr.SegmentParams` (default: Otsu threshold, dark text).  The counts and boxes are read back once (the one sync), then the boxes are
@@ -611,7 +612,17 @@ class Model:
         label area hull accepted per examined candidate in label order, in the coordinates of the page after the scale stage (before
         any quarter turn, deskew or dewarp), and panel_counts (8) int64 (components, candidates found, candidates examined, panels
         inverted, threshold, total ink, the sum of the inverted hulls, 0).  Limits (one level of nesting, gray rim pixels, solid bars,
-        slabs that touch a grid): DESIGN.md section 26."""
+        slabs that touch a grid): DESIGN.md section 26.
+        binarize: None or False (the default) separates ink from paper with one threshold for the whole page.  True or an
+        `aocr.BinarizeParams` first thresholds every pixel against the mean and the standard deviation of the window around it
+        (aocr_binarize_page, Sauvola; True: radius 20, k = 51 / 256, R = 128, gray output, with the light_text of `params`: a judgement
+        for 300 dpi, untuned), directly after flatten and before scale, for faded print beside strong print, stains, show-through and
+        carbon copies, where no single gray level is right everywhere.  On its output the fixed threshold 127 is the local decision, so
+        when `params` asks for Otsu (-1) every later stage runs with 127 on a copy of `params` (the caller's object is not modified, and
+        res.threshold is then 127); a fixed threshold in `params` is kept.  The boxes do not move.  The four count words come back with
+        the existing readback (no additional sync).  The namespace then also carries binarize_radius, binarize_ink (the ink pixels of the
+        local decision) and binarize_threshold_range (the smallest and the largest local T).  Limits (strokes wider than the window are
+        hollowed out; it does not replace flatten for strong shading: the two compose, flatten first): DESIGN.md section 27."""
         if asked(colour):
             ok = isinstance(page, (np.ndarray, torch.Tensor)) and len(page.shape) == 3 and page.shape[2] == 3 and \
                 page.dtype == (np.uint8 if isinstance(page, np.ndarray) else torch.uint8)
@@ -639,6 +650,9 @@ class Model:
         seg = params if params is not None else _lib.SegmentParams()
         page, rect = rectify_stage(page, stream, seg, rectify)
         page, flat = flatten_stage(page, stream, seg, flatten)
+        page, binar, binarize_dev = binarize_stage(page, stream, seg, binarize)
+        if binar is not None:
+            seg = binarized_params(seg)
         page, scl = scale_stage(page, stream, seg, scale)
         page, panels_dev = panels_stage(page, stream, seg, panels)
         page0, clean_dev = clean_stage(page, stream, seg, clean)
@@ -651,6 +665,8 @@ class Model:
             extra["rules"] = rules
         if panels_dev is not None:
             extra["panels_dev"] = panels_dev
+        if binarize_dev is not None:
+            extra["binarize_dev"] = binarize_dev
         st = self._page_boxes(page, *middle, **extra)
         orient_scores = None
         if orient is True:
@@ -704,6 +720,9 @@ class Model:
             res.n_blocks, res.layout_overflow = st.nb, bool(st.lcounts[3])
         if flat is not None:
             res.flatten_radius = int(flat.radius)
+        if binar is not None:
+            res.binarize_radius, res.binarize_ink = int(binar.radius), int(st.binarize[0])
+            res.binarize_threshold_range = (int(st.binarize[1]), int(st.binarize[2]))
         if st.cleaned is not None:
             res.clean_components, res.clean_specks, res.clean_rules, res.clean_ink_removed = (int(st.cleaned[0]), int(st.cleaned[1]),
                                                                                               int(st.cleaned[2]), int(st.cleaned[5]))

@@ -26,7 +26,10 @@ such a crop reaches beyond its box on either side.  The boxes do not move.  One 
 whose lines are set in different sizes goes through `segment_page_spaced_device` (`aocr_segment_page_spaced`: the gap of every line
 estimated from the line's own gaps) in place of `segment_page_device`.  A form or a table is text that touches rules, one component with
 them: `remove_rules_device` (`aocr_remove_rules`: run lengths per pixel) takes out what is long one way and thin the other and leaves the
-strokes that cross it, after the deskew and before layout and segmentation.  The boxes do not move.  A table header row or a section bar
+strokes that cross it, after the deskew and before layout and segmentation.  The boxes do not move.  Faded print beside strong print, a
+stain, show-through: no single threshold is right everywhere even on evenly lit paper; `binarize_page_device` (`aocr_binarize_page`: a
+Sauvola threshold per pixel from the window's mean and standard deviation) writes a page on which the fixed threshold 127 is the local
+decision, behind `flatten_page_device` and in front of everything that thresholds.  A table header row or a section bar
 is light text on a dark slab, one component that holds no readable crop: `invert_panels_device` (`aocr_invert_panels`) finds such slabs
 among the components and inverts the bytes inside their row spans, in front of `clean_page_device`.  The boxes do not move."""
 from __future__ import annotations
@@ -37,7 +40,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import Box, CleanParams, ColourParams, CurlParams, FlattenParams, GlyphParams, LayoutParams, PanelParams, RectifyParams, RuleParams, ScaleParams, SegmentParams, SkewParams, SlantParams, SpacingParams, check, lib, ptr
+from ._lib import BinarizeParams, Box, CleanParams, ColourParams, CurlParams, FlattenParams, GlyphParams, LayoutParams, PanelParams, RectifyParams, RuleParams, ScaleParams, SegmentParams, SkewParams, SlantParams, SpacingParams, check, lib, ptr
 
 IMG_H = 32
 MIN_ASPECT = 0.5
@@ -200,6 +203,24 @@ def flatten_page_device(page_dev, params=None, stream=None):
     out = torch.empty((H, W), dtype=torch.uint8, device=dev)
     check(lib.aocr_flatten_page(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), ptr(out), W), "aocr_flatten_page")
     return out
+
+
+def binarize_page_device(page_dev, params=None, stream=None, counts=False):
+    """a new (H, W) uint8 device tensor: the page binarised locally by `aocr_binarize_page` (a Sauvola threshold per pixel from the mean and
+    the standard deviation of the window around it): on it the fixed threshold 127 is the local decision, ink 0..127 and paper 128..255
+    (0 and 255 with params.hard; mirrored with params.light_text).  params: a `BinarizeParams` (default: radius 20, k = 51 / 256, R = 128,
+    dark text, gray output).  counts=True: (out, counts (4) int32 on the device: ink pixels, the smallest T, the largest T, 0).  Enqueues
+    only.  stream: as for `segment_page_device`, the current torch stream; the scratch is freed when this returns."""
+    page_dev, pitch = _page_view(page_dev)
+    H, W = page_dev.shape
+    params = params if params is not None else BinarizeParams()
+    dev = page_dev.device
+    scratch = _scratch("aocr_binarize_scratch_bytes", dev, H, W, params.radius)
+    out = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    words = torch.zeros(4, dtype=torch.int32, device=dev) if counts else None
+    check(lib.aocr_binarize_page(_stream(stream, dev), ptr(page_dev), pitch, H, W, C.byref(params), ptr(scratch), ptr(out), W, ptr(words)),
+          "aocr_binarize_page")
+    return (out, words) if counts else out
 
 
 def _ink_integral(page_dev, pitch, threshold, light_text, stream):
@@ -772,5 +793,5 @@ def bucket_width(w, h, max_img_w, width_step=32, max_aspect=None):
 
 
 __all__ = ["backmap_corners", "SpacingParams", "segment_page_spaced_device", "SlantParams", "estimate_slant_device", "crop_lines_slanted_device", "slant_extent", "ColourParams", "estimate_page_colour_device", "gray_page_device", "CurlParams", "estimate_curl_device", "dewarp_page_device", "curl_shift_q8", "uncurl_points", "source_points", "box_corners", "GlyphParams", "ScaleParams", "estimate_glyph_size_device", "resize_page_device", "scale_plan", "unscale_points", "RectifyParams", "find_page_quad_device", "rectify_plan", "warp_page_device", "warp_points", "SegmentParams", "SkewParams", "FlattenParams", "LayoutParams", "CleanParams", "Box", "label_components_device", "clean_page_device", "segment_page_device", "crop_lines_device",
-           "estimate_skew_device", "deskew_page_device", "flatten_page_device", "ink_integral_device", "layout_page_device", "source_corners",
+           "estimate_skew_device", "deskew_page_device", "flatten_page_device", "BinarizeParams", "binarize_page_device", "ink_integral_device", "layout_page_device", "source_corners",
            "rotate_page_device", "estimate_orientation_device", "unrotate_boxes", "unrotate_points", "bucket_width"]

@@ -1,4 +1,4 @@
-"""The stage chain of `Model.recognize_page` in front of the recogniser, as plain functions of the page: colour, rectify, flatten, scale, panels,
+"""The stage chain of `Model.recognize_page` in front of the recogniser, as plain functions of the page: colour, rectify, flatten, binarize, scale, panels,
 clean and the quarter turn (one function each, in that order), then `page_boxes`: deskew, dewarp, rule removal, layout and segmentation down to
 the boxes on the host.  Every function takes the page on the device, the raw handle of the current torch stream and the page's resolved `SegmentParams`,
 enqueues on that stream, and returns the page with a small record of what it did (None when the stage was not asked for).  What needs a
@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .page import (clean_page_device, invert_panels_device, deskew_page_device, estimate_slant_device, dewarp_page_device, estimate_curl_device, estimate_glyph_size_device,
+from .page import (binarize_page_device, clean_page_device, invert_panels_device, deskew_page_device, estimate_slant_device, dewarp_page_device, estimate_curl_device, estimate_glyph_size_device,
                    estimate_orientation_device, gray_page_device, estimate_skew_device, find_page_quad_device, flatten_page_device, layout_page_device,
                    rectify_plan, remove_rules_device, resize_page_device, rotate_page_device, scale_plan, segment_page_device, segment_page_spaced_device, warp_page_device)
 
@@ -84,6 +84,32 @@ def flatten_stage(page, stream, seg, flatten):
         return page, None
     flat = flatten if isinstance(flatten, _lib.FlattenParams) else _lib.FlattenParams(light_text=seg.light_text)
     return flatten_page_device(page, flat, stream), flat
+
+
+def binarize_stage(page, stream, seg, binarize):
+    """(page, the BinarizeParams used, the four count words on the device: they come back with the boxes' readback).  Directly after the
+    flatten stage, which takes strong shading out first, and before the scale stage: the pixel values change and no geometry does, so
+    there is nothing to map back.  binarize True: the defaults with the light_text of the segment params."""
+    if not asked(binarize):
+        return page, None, None
+    if isinstance(binarize, _lib.BinarizeParams):
+        bp = binarize
+    elif binarize is True:
+        bp = _lib.BinarizeParams(light_text=seg.light_text)
+    else:
+        raise ValueError(f"binarize={binarize!r}: None, False, True or an aocr.BinarizeParams")
+    page, counts_dev = binarize_page_device(page, bp, stream, counts=True)
+    return page, bp, counts_dev
+
+
+def binarized_params(seg):
+    """the segment params of the stages behind binarize_stage: a copy, with the fixed threshold 127 -- the local decision on the binarised
+    page -- in the place of Otsu (-1), which could land below 127 on the output and drop faint ink.  A fixed threshold is the caller's."""
+    if seg.threshold >= 0:
+        return seg
+    fixed = _lib.SegmentParams(*[getattr(seg, f) for f, _ in seg._fields_][:9])
+    fixed.threshold = 127
+    return fixed
 
 
 def scale_stage(page, stream, seg, scale):
@@ -179,7 +205,8 @@ def rule_params(seg, rules):
     raise ValueError(f"rules={rules!r}: None, False, True or an aocr.RuleParams")
 
 
-def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None, deslant=None, spacing=None, rules=None, panels_dev=None):
+def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, colour_dev=None, deslant=None, spacing=None, rules=None, panels_dev=None,
+               binarize_dev=None):
     """the middle of recognize_page, from the deskew to the boxes on the host: everything that reads the page in its final orientation and
     has to be redone when recognize_page(orient=True) turns the page by another half turn.  Returns a namespace: page, boxes_dev, rows, counts,
     n, truncated; skew, cleaned, curl, colour (the words read back, None without the stage), curl_group; lay, blocks, block_id, nb, lcounts
@@ -190,7 +217,8 @@ def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, 
     only on a straight page) and before layout and segmentation (a column-separator rule sits in the gutter the XY cut looks for); st.page
     is then the page with the rules taken out, st.rules its eight counts, which ride with the first readback (None without rules).
     panels_dev: what panels_stage left on the device, one more rider of the first readback; st.panels is then its words end to end, the
-    eight counts and the MAX_PANELS rows of eight (None without the stage)."""
+    eight counts and the MAX_PANELS rows of eight (None without the stage).  binarize_dev: the four count words binarize_stage left on the
+    device, another rider of the first readback; st.binarize is then those words (None without the stage)."""
     st = SimpleNamespace(curl_group=None, lay=None, blocks=None, block_id=None, nb=None, lcounts=None, slant=None, slant_dev=None, spacing=None)
     skew_dev = curl_dev = rules_dev = None
     ruled = rule_params(seg, rules) if asked(rules) else None
@@ -213,7 +241,7 @@ def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, 
     if ruled is not None:
         page, rules_dev = remove_rules_device(page, ruled, stream)
     st.page = page
-    riders = dict(skew=skew_dev, cleaned=clean_dev, curl=curl_dev, colour=colour_dev, rules=rules_dev, panels=panels_dev)            # what comes back with the first readback, whichever it is
+    riders = dict(skew=skew_dev, cleaned=clean_dev, curl=curl_dev, colour=colour_dev, rules=rules_dev, panels=panels_dev, binarize=binarize_dev)            # what comes back with the first readback, whichever it is
     if asked(layout):
         st.lay = layout if isinstance(layout, _lib.LayoutParams) else _lib.LayoutParams()
         blocks_dev, lcounts_dev, info_dev = layout_page_device(page, st.lay, seg.threshold, seg.light_text, MAX_BLOCKS, stream)
@@ -291,5 +319,5 @@ def page_boxes(page, stream, seg, max_boxes, deskew, dewarp, layout, clean_dev, 
                 st.spacing = back[at:at + 8 * lines].reshape(-1, 8)
         st.truncated = bool(st.counts[0] > max_boxes)
     st.skew, st.cleaned, st.curl, st.colour, st.rules = got.get("skew"), got.get("cleaned"), got.get("curl"), got.get("colour"), got.get("rules")
-    st.panels = got.get("panels")
+    st.panels, st.binarize = got.get("panels"), got.get("binarize")
     return st

@@ -1013,6 +1013,34 @@ int aocr_flatten_page(void* stream, const uint8_t* page_dev, int64_t pitch, int3
   return check_launch("aocr_flatten_page");
 }
 
+size_t aocr_binarize_scratch_bytes(int32_t H, int32_t W, int32_t radius) {
+  if (!(page_size_ok(H, W) && radius >= 1 && radius <= 63)) {
+    fail("bad sizes H=%d W=%d (1..16384 each, H*W <= 2^26) radius=%d (1..63)", H, W, radius);
+    return 0;
+  }
+  return binarize_scratch_bytes(H, W, radius);
+}
+
+int aocr_binarize_page(void* stream, const uint8_t* page_dev, int64_t pitch, int32_t H, int32_t W, const aocr_binarize_params* params,
+                       void* scratch_dev, uint8_t* out_dev, int64_t out_pitch, int32_t counts_dev[4]) {
+  if (check_page(page_dev, pitch, H, W)) return 1;
+  REQUIRE(params, "params is NULL");
+  REQUIRE(params->radius >= 1 && params->radius <= 63, "radius=%d: 1..63", params->radius);
+  REQUIRE(params->k_q8 >= 0 && params->k_q8 <= 255, "k_q8=%d: 0..255", params->k_q8);
+  REQUIRE(params->range >= 1 && params->range <= 255, "range=%d: 1..255", params->range);
+  REQUIRE(params->reserved[0] == 0 && params->reserved[1] == 0 && params->reserved[2] == 0, "reserved words must be 0");
+  if (check_scratch(scratch_dev, out_dev)) return 1;
+  REQUIRE(((uintptr_t)counts_dev & 3) == 0, "counts_dev must be 4-byte aligned");
+  if (check_out(page_dev, pitch, H, W, out_dev, out_pitch, H, W)) return 1;
+  if (counts_dev) {
+    const Span counts = span_bytes(counts_dev, 4 * sizeof(int32_t));
+    REQUIRE(disjoint(counts, span_rows(page_dev, pitch, H, W)), "counts_dev overlaps the page");
+    REQUIRE(disjoint(counts, span_rows(out_dev, out_pitch, H, W)), "counts_dev overlaps out_dev");
+  }
+  binarize_page((hipStream_t)stream, page_dev, pitch, H, W, *params, out_dev, out_pitch, counts_dev);
+  return check_launch("aocr_binarize_page");
+}
+
 size_t aocr_integral_scratch_bytes(int32_t H, int32_t W) { return scratch_size_ok(H, W) ? integral_scratch_bytes(H, W) : 0; }
 
 static int check_sat(const uint32_t* sat_dev, int64_t sat_pitch, int32_t H, int32_t W) {

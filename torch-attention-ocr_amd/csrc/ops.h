@@ -419,6 +419,11 @@ void gray_page(hipStream_t s, const uint8_t* rgb, int64_t pitch, int H, int W, c
 size_t flatten_scratch_bytes(int H, int W);
 void flatten_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_flatten_params& p, void* scratch, uint8_t* out,
                   int64_t out_pitch);
+// local adaptive binarisation (binarize.hip; include/aocr.h: aocr_binarize_page): a Sauvola threshold from the window sums of v and v^2, one
+// fused launch; counts may be nullptr; the scratch is not used
+size_t binarize_scratch_bytes(int H, int W, int radius);
+void binarize_page(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, const aocr_binarize_params& p, uint8_t* out, int64_t out_pitch,
+                   int32_t* counts);
 // page layout (layout.hip; include/aocr.h: aocr_ink_integral, aocr_layout_blocks): the summed-area table of the ink mask and the XY cut on it
 size_t integral_scratch_bytes(int H, int W);
 void ink_integral(hipStream_t s, const uint8_t* page, int64_t pitch, int H, int W, int threshold, int light_text, void* scratch, uint32_t* sat,
